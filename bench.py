@@ -11,12 +11,15 @@ WORLD_SIZE / MASTER_* in the environment), or — a plain `python bench.py --gpu
 interpreters itself (`launch_ranks`: the parent never imports torch or touches a GPU, no exec), forwards rank 0's JSON
 line and returns the worst child's exit code.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--repeats R] [--batch B] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--repeats R] [--batch B] [--no-cpu-baseline] [--dump-outputs DIR]
 
-Timing: after W warm-up steps, R blocks of EXACTLY K steps, each block bracketed by barrier + device synchronise on both
-sides and reduced with MAX over the ranks; `value` / `ms_per_step` come from the MEDIAN block, every block is listed under
-"repeats". Extra objects on the line: "roofline" (algorithmic HBM bytes/tick x ticks / kernel time from HIP events on the
-launch stream against 8 TB/s — reported because the contract asks for it; what bounds this kernel is issue/latency, see
+Timing: after at least W warm-up steps (the GPU engine warms up for SETTLE_S at least: from idle the tick needs ~100 steps
+before its time per step settles), EXACTLY K timed steps, split into R blocks (default 1) whose sizes add up to K, each
+block bracketed by barrier + device synchronise on both sides and reduced with MAX over the ranks; `value` / `ms_per_step`
+come from the MEDIAN block (per step), every block is listed under "repeats". --dump-outputs DIR writes what the last timed step
+returned on rank 0 (qdot, status, iters) as DIR/<name>.npy in float64; the inputs depend only on the arguments.
+Extra objects on the line: "roofline" (algorithmic HBM bytes/tick x ticks / kernel time from HIP events on the launch stream
+against 8 TB/s — reported because the contract asks for it; what bounds this kernel is issue/latency, see
 "issue") and "cpu_baseline" (the CPU oracle, oracle/wbc_oracle.c, timed on this host's cores on a bounded sample of the
 same inputs — the oracle is only the yardstick/checker here, never the thing measured). The run FAILS (exit code 1, line
 still printed) if the q̇ error against the oracle exceeds the tolerance or any solver status differs.
@@ -48,6 +51,7 @@ TRAFFIC_PROFILE = "r04_traffic_calibration.txt"   # FETCH_SIZE / WRITE_SIZE of t
                                                   # tick's own access pattern (tools/calib_traffic.sh): roofline.traffic
 DT = 0.002
 QDOT_TOL = 1e-5
+SETTLE_S = 0.1                 # minimum warm-up time of the GPU engine (clocks ramp for ~20 ms after idle)
 
 
 def _pmc_lines(kernels):
@@ -132,6 +136,7 @@ class Comm:
 class GpuEngine:
     """wbc_tick on one MI355X through the C-ABI (WbcBatch); inputs generated with the product's own FK, resident in HBM."""
     name = "hip"
+    settle_s = SETTLE_S
 
     def __init__(self, args, local):
         import torch
@@ -305,7 +310,11 @@ def run_rank(args, comm, engine, make_inputs):
     """What every rank does: seed-by-rank inputs -> warm-up -> R bracketed blocks of K steps -> MAX over ranks ->
     rank 0 assembles the JSON line. Returns (line or None, results dict)."""
     rank, world = comm.rank, comm.world
-    B, K, R = args.batch, args.steps, max(1, args.repeats)
+    B, K = args.batch, args.steps
+    if K < 1:
+        raise SystemExit("--steps must be at least 1")
+    R = min(max(1, args.repeats), K)
+    sizes = [K // R + (1 if i < K % R else 0) for i in range(R)]    # the blocks' steps: K in all
     host_in = make_inputs(engine, B, seed=rank, stress=True)
     engine.host_in = host_in
     engine.load(host_in)
@@ -317,36 +326,47 @@ def run_rank(args, comm, engine, make_inputs):
 
     for _ in range(args.warmup):
         engine.step()
+    warm = args.warmup
+    settle = getattr(engine, "settle_s", 0.0)
+    if settle > 0:                                  # the W steps and then more, in tens, until the warm-up has lasted settle_s
+        engine.sync()
+        t0 = time.perf_counter()
+        while time.perf_counter() - t0 < settle:
+            for _ in range(10):
+                engine.step()
+            engine.sync()
+            warm += 10
     elapsed, kernel_ms = [], []
-    for _ in range(R):
+    for k in sizes:
         barrier()
         t0 = time.perf_counter()
-        km = engine.timed_block(K)
+        km = engine.timed_block(k)
         barrier()
         elapsed.append(time.perf_counter() - t0)
-        kernel_ms.append(km() / K)
+        kernel_ms.append(km() / k)
     elapsed = comm.max(elapsed)                     # the job is as slow as its slowest rank, block by block
     res = engine.results()
     if rank != 0:
         return None, res
-    order = np.argsort(elapsed)
+    per_step = [e / k for e, k in zip(elapsed, sizes)]
+    order = np.argsort(per_step)
     med = int(order[len(order) // 2])
-    t_med, k_med = elapsed[med], kernel_ms[med]
-    ticks = float(B) * world * K
+    t_med, k_med = per_step[med], kernel_ms[med]    # seconds / milliseconds of ONE step
+    ticks = float(B) * world
     ach = ALGO_BYTES_PER_TICK * B / (k_med * 1e-3) / 1e9
     traffic, issue = pmc_static()
     status, iters = res["status"], res["iters"]
     line = {
         "metric": "wbc_qp_solves_per_sec", "value": ticks / t_med, "unit": "ticks/s", "n_gpus": world,
-        "steps": K, "warmup": args.warmup, "ms_per_step": 1e3 * t_med / K,
+        "steps": K, "warmup": args.warmup, "warmup_steps_run": warm, "ms_per_step": 1e3 * t_med,
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
         "config": {"workload": "BASELINE configs[2] / SURVEY C3: A1+wx200 (nq 27, nv 26), sim3 switch set: Grip task + " + args.posture + " posture, "
                                "12 contact equalities + 4 trunk-box rows + 26 damper bounds (3 locked), m=32 p=16 n=26",
                    "batch_per_gpu": B, "global_batch": B * world, "dt": DT, "parallelism": "shard%d (no collective)" % world,
                    "engine": engine.name, "backend": getattr(engine, "backend", None), "kernel_path": engine.path(), "options": getattr(engine, "options", {}),
                    "jtj": "mfma_f64" if getattr(engine, "options", {}).get("jtj_mfma", -1) > 0 else "valu_f64"},
-        "repeats": {"n": R, "ms_per_step": [1e3 * e / K for e in elapsed], "kernel_ms_per_step": kernel_ms,
-                    "spread": (max(elapsed) - min(elapsed)) / t_med, "reported": "median block"},
+        "repeats": {"n": R, "steps_per_block": sizes, "ms_per_step": [1e3 * e for e in per_step], "kernel_ms_per_step": kernel_ms,
+                    "spread": (max(per_step) - min(per_step)) / t_med, "reported": "median block"},
         "roofline": {"bound": "valu_lds_issue_latency", "contract_bound": "hbm",
                      "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
                      "traffic": traffic, "traffic_unit": "bytes/launch (PMC FETCH_SIZE + WRITE_SIZE at batch 65536, calibrated on a known-byte-count kernel "
@@ -366,6 +386,25 @@ def run_rank(args, comm, engine, make_inputs):
                    "iters_p95": float(np.percentile(iters, 95)), "iters_max": int(iters.max())},
     }
     return line, res
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, res):
+    """--dump-outputs: the arrays a caller of the timed path receives from its last step, as <out_dir>/<name>.npy in float64. If they
+    would exceed DUMP_MAX_BYTES, the same fixed, seeded sample of instances is taken from every array and its indices go to sample_index.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = {k: np.asarray(v, dtype=np.float64) for k, v in sorted(res.items())}
+    B = next(iter(arrs.values())).shape[0]
+    per_inst = sum(a[:1].nbytes for a in arrs.values())
+    n = B if per_inst * B <= DUMP_MAX_BYTES else DUMP_MAX_BYTES // (per_inst + 8)    # + 8: the sample's index
+    if n < B:
+        idx = np.sort(np.random.default_rng(0).choice(B, size=n, replace=False))
+        arrs = {k: a[idx] for k, a in arrs.items()}
+        arrs["sample_index"] = idx.astype(np.float64)
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
 
 
 def make_inputs(engine, B, seed, stress):
@@ -429,9 +468,9 @@ def cpu_baseline_and_accuracy(line, engine, host_in, res, args):
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps in all")
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=5, help="timed blocks of --steps steps; the median block is reported")
+    ap.add_argument("--repeats", type=int, default=1, help="timed blocks the --steps steps are split into; the median block is reported")
     ap.add_argument("--batch", type=int, default=65536, help="instances per GPU")
     ap.add_argument("--cpu-sample", type=int, default=0, help="instances for the CPU baseline and the accuracy gate (0 = the whole batch)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -439,6 +478,8 @@ def main(argv=None):
     ap.add_argument("--rollout-ticks", type=int, default=10, help="closed-loop ticks of the extra wbc_rollout measurement (0 = skip)")
     ap.add_argument("--posture", default="PREV", choices=["PREV", "HYBRID", "MANI"],
                     help="posture mode of the tick (default PREV = the BASELINE workload; HYBRID is what sim3.py:145 sets)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0) as DIR/<name>.npy in float64")
     args = ap.parse_args(argv)
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:     # plain `python bench.py --gpus N`: be the launcher
@@ -468,6 +509,8 @@ def main(argv=None):
         comm = Comm("gloo" if share else "nccl", rank, world, None if share else engine.dev)
         engine.backend = "gloo (ranks share GPUs: rehearsal)" if share else "nccl (RCCL)"
     line, res = run_rank(args, comm, engine, make_inputs)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, res)
     ok = True
     if rank == 0:
         if args.rollout_ticks > 0 and world == 1:     # closed loop, extra leg of single-GPU runs

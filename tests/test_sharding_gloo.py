@@ -63,11 +63,11 @@ def _bench_worker(rank, world, port, out_dir):
     import conftest  # noqa: F401
     import bench
     os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    args = argparse.Namespace(batch=40, steps=2, warmup=1, repeats=3, posture="PREV")
+    args = argparse.Namespace(batch=40, steps=6, warmup=1, repeats=3, posture="PREV")
     comm = bench.Comm("gloo", rank, world, None)
     eng = _OracleEngine()
     line, res = bench.run_rank(args, comm, eng, bench.make_inputs)
-    assert eng.steps_run == args.warmup + args.steps * args.repeats         # exactly K steps per timed block
+    assert eng.steps_run == args.warmup + args.steps                        # exactly K timed steps, split over the blocks
     np.savez(os.path.join(out_dir, "bench_r%d.npz" % rank), qdot=res["qdot"], q=eng.host_in["q"])
     if rank == 0:
         assert line is not None
@@ -88,7 +88,8 @@ def test_bench_rank_body_over_gloo(tmp_path):
     assert line["metric"] == "wbc_qp_solves_per_sec" and line["unit"] == "ticks/s" and line["n_gpus"] == 2
     assert line["scaling"] == "weak" and line["higher_is_better"] is True and line["vs_baseline"] is None and line["dtype"] == "f64"
     assert line["config"]["global_batch"] == 80 and line["config"]["batch_per_gpu"] == 40 and line["config"]["parallelism"].startswith("shard2")
-    assert line["steps"] == 2 and line["warmup"] == 1 and line["repeats"]["n"] == 3 and len(line["repeats"]["ms_per_step"]) == 3
+    assert line["steps"] == 6 and line["warmup"] == 1 and line["repeats"]["n"] == 3 and len(line["repeats"]["ms_per_step"]) == 3
+    assert line["repeats"]["steps_per_block"] == [2, 2, 2]
     # whole-job aggregate: all ranks' ticks over the (max-over-ranks) time of the median block
     assert abs(line["value"] * line["ms_per_step"] * 1e-3 - 80.0) < 1e-6
     assert sorted(line["repeats"]["ms_per_step"])[1] == pytest.approx(line["ms_per_step"])
@@ -153,3 +154,58 @@ def test_bench_under_an_external_launcher_still_works(tmp_path):
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert line["n_gpus"] == 1 and line["config"]["global_batch"] == 16
+
+
+def test_bench_dump_outputs_are_the_last_steps_results(tmp_path):
+    """--dump-outputs DIR: the last timed step's outputs as DIR/<name>.npy in float64, the same from run to run (inputs depend only on
+    the arguments) and equal to the oracle's answer on those inputs; --steps is the number of timed steps in all"""
+    import json
+    import subprocess
+    root = os.path.dirname(HERE)
+    env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29564",
+               WBC_BENCH_ENGINE_STUB=os.path.join(HERE, "bench_engine_stub.py") + ":OracleEngine")
+    dirs = []
+    for run in range(2):
+        d = os.path.join(str(tmp_path), "out%d" % run)
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "1", "--repeats", "2",
+                            "--batch", "16", "--no-cpu-baseline", "--rollout-ticks", "0", "--dump-outputs", d],
+                           env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+        assert line["steps"] == 5 and sum(line["repeats"]["steps_per_block"]) == 5 and line["ms_per_step"] > 0
+        dirs.append(d)
+    names = sorted(os.listdir(dirs[0]))
+    assert {"qdot.npy", "status.npy"} <= set(names) and names == sorted(os.listdir(dirs[1]))
+    for n in names:
+        a, b = np.load(os.path.join(dirs[0], n)), np.load(os.path.join(dirs[1], n))
+        assert a.dtype == np.float64 and np.array_equal(a, b)
+    import common
+    import oracle
+    import wbc_workload
+    wx = common.models()[0]
+    cfg = common.config("c3", wx)
+    d = wbc_workload.make_tick_inputs(wx, cfg, 16, seed=0, fk=common.OracleFK([wx]), stress=True)
+    ref = oracle.tick([wx], [cfg], d, 0.002, 16, want_q_next=False)
+    assert np.array_equal(np.load(os.path.join(dirs[0], "qdot.npy")), ref["qdot"])
+    assert np.array_equal(np.load(os.path.join(dirs[0], "status.npy")), ref["status"].astype(np.float64))
+
+
+def test_bench_dump_outputs_samples_above_the_size_cap(tmp_path, monkeypatch):
+    """outputs larger than the cap: the same fixed, seeded rows of every array, their indices in sample_index.npy, under the cap in all"""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 64 << 10)
+    rng = np.random.default_rng(3)
+    res = {"qdot": rng.normal(size=(4096, 26)), "status": rng.integers(0, 4, 4096).astype(np.int32)}
+    for run in ("a", "b"):
+        bench.dump_outputs(os.path.join(str(tmp_path), run), res)
+    total = 0
+    for n in ("qdot.npy", "status.npy", "sample_index.npy"):
+        a, b = (np.load(os.path.join(str(tmp_path), run, n)) for run in ("a", "b"))
+        assert np.array_equal(a, b)
+        total += a.nbytes
+    assert total <= bench.DUMP_MAX_BYTES
+    idx = np.load(os.path.join(str(tmp_path), "a", "sample_index.npy")).astype(np.int64)
+    assert len(idx) > 100 and (np.diff(idx) > 0).all()
+    assert np.array_equal(np.load(os.path.join(str(tmp_path), "a", "qdot.npy")), res["qdot"][idx])
+    assert np.array_equal(np.load(os.path.join(str(tmp_path), "a", "status.npy")), res["status"][idx].astype(np.float64))
