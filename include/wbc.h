@@ -80,7 +80,10 @@ typedef struct WbcModelBlob {
   int32_t parent[WBC_MAX_JOINTS];
   int32_t idx_q[WBC_MAX_JOINTS];
   int32_t idx_v[WBC_MAX_JOINTS];
-  double place_R[WBC_MAX_JOINTS][9];     /* joint placement in parent joint frame                 */
+  double place_R[WBC_MAX_JOINTS][9];     /* joint placement in parent joint frame (row-major); the
+                                          * identity or a proper rotation (orthonormal, det +1, both
+                                          * within 1e-12: the ViperX-300's rpy="3.14 0 0"); the root
+                                          * joint's is the identity                                */
   double place_p[WBC_MAX_JOINTS][3];
   double mass[WBC_MAX_JOINTS];           /* lumped body (fixed children merged), joint frame      */
   double com[WBC_MAX_JOINTS][3];
@@ -88,7 +91,9 @@ typedef struct WbcModelBlob {
   double v_max[WBC_MAX_NV];                  /* model.velocityLimit (nv-sized)                     */
   int32_t nframes;                       /* >= WBC_FR_NROLES                                      */
   int32_t frame_joint[WBC_MAX_FRAMES];   /* supporting joint                                      */
-  double frame_R[WBC_MAX_FRAMES][9];     /* placement in the supporting joint's frame             */
+  double frame_R[WBC_MAX_FRAMES][9];     /* placement in the supporting joint's frame: must be the
+                                          * identity (no robot of the reference needs a rotated
+                                          * frame offset; any other is refused)                   */
   double frame_p[WBC_MAX_FRAMES][3];
   int32_t ee_joint[WBC_NEE];             /* end_effector_index_list_joint (Robot_Wrapper4.py:49)  */
 } WbcModelBlob;
@@ -196,7 +201,9 @@ typedef struct WbcBatch WbcBatch;
 
 /* ------------------------------------------------------------------ entry points */
 
-/* replaces pin.buildModelFromUrdf + createData (Robot_Wrapper4.py:21-23); validates the blob. */
+/* replaces pin.buildModelFromUrdf + createData (Robot_Wrapper4.py:21-23); validates the blob: sizes, a free-flyer root,
+ * axis-aligned 1-DoF joints, joint placements that are the identity or a proper rotation, unrotated frame offsets
+ * (WBC_E_UNSUPPORTED otherwise, with "rotated joint placement" / "rotated frame offset" in wbc_last_error()). */
 int wbc_model_create(const WbcModelBlob* blob, WbcModel** out);
 void wbc_model_destroy(WbcModel* m);
 

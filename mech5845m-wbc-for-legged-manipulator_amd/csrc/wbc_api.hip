@@ -66,6 +66,7 @@ struct WbcBatch {
   int last_qp_path;      // problems per wavefront of the last wbc_qp_solve / wbc_qp_solve_ls: 1 (wbc_qp_kernel), 2 or 4 (wbc_qp_packed_kernel)
   int last_path;         // kernel the last wbc_tick / wbc_rollout tick ran on: 0 general, 1 sim3 (+ deferred pass), 2 packed sim3, 3 packed orth, 4 packed box
   int max_nj, max_nf;    // FK output strides: the largest model's joint / frame counts
+  int rot;               // a model of the handle has a rotated joint placement: the packed kernels run their ROT instantiations
   unsigned long long* d_prof;
   double *d_pu, *d_pq;   // qpJointb MANI/HYBRID results: u [max_batch][26], q_after [max_batch][27] (lazy)
   void* d_roll;          // wbc_rollout's mutable controller state for max_batch instances (lazy)
@@ -77,6 +78,17 @@ static bool is_identity(const double* R) {
   for (int i = 0; i < 9; ++i)
     if (R[i] != I[i]) return false;
   return true;
+}
+// A proper rotation: R R' = I and det R = +1, each within 1e-12 (the URDF's rpy="3.14 0 0" of the ViperX-300 elbow / wrist_rotate is one;
+// a reflection or a sheared matrix is not).
+static bool is_rotation(const double* R) {
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      const double d = R[3 * i] * R[3 * j] + R[3 * i + 1] * R[3 * j + 1] + R[3 * i + 2] * R[3 * j + 2];
+      if (!(fabs(d - (i == j ? 1.0 : 0.0)) <= 1e-12)) return false;
+    }
+  const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
+  return fabs(det - 1.0) <= 1e-12;
 }
 
 extern "C" int wbc_model_create(const WbcModelBlob* b, WbcModel** out) {
@@ -98,7 +110,10 @@ extern "C" int wbc_model_create(const WbcModelBlob* b, WbcModel** out) {
     const int t = b->jtype[j];
     if (b->parent[j] < 0 || b->parent[j] >= j) { delete m; return fail(WBC_E_ARG, "joint %d: parent %d not before it", j, b->parent[j]); }
     if (j > 1 && !(t >= WBC_JT_RX && t <= WBC_JT_PZ)) { delete m; return fail(WBC_E_UNSUPPORTED, "joint %d: type %d unsupported on device", j, t); }
-    if (!is_identity(b->place_R[j])) { delete m; return fail(WBC_E_UNSUPPORTED, "joint %d: rotated joint placement unsupported on device", j); }
+    if (j == 1 && !is_identity(b->place_R[1])) { delete m; return fail(WBC_E_UNSUPPORTED, "root joint placement must be identity"); }
+    if (!is_identity(b->place_R[j]) && !is_rotation(b->place_R[j])) {
+      delete m; return fail(WBC_E_UNSUPPORTED, "joint %d: rotated joint placement is not a proper rotation (orthonormal, det +1)", j);
+    }
     if (j > 1 && b->parent[j] < 1) { delete m; return fail(WBC_E_UNSUPPORTED, "joint %d: only one root joint supported", j); }
     if (j == 1 && (b->place_p[1][0] != 0 || b->place_p[1][1] != 0 || b->place_p[1][2] != 0)) { delete m; return fail(WBC_E_UNSUPPORTED, "root joint placement must be identity"); }
     depth[j] = depth[b->parent[j]] + 1;
@@ -107,6 +122,13 @@ extern "C" int wbc_model_create(const WbcModelBlob* b, WbcModel** out) {
     const int a = (t >= WBC_JT_RX && t <= WBC_JT_RZ) ? t - WBC_JT_RX : (t >= WBC_JT_PX ? t - WBC_JT_PX : 0);
     d.ax0[j] = a; d.ax1[j] = (a + 1) % 3; d.ax2[j] = (a + 2) % 3;
     d.tp[j][0] = b->place_p[j][d.ax0[j]]; d.tp[j][1] = b->place_p[j][d.ax1[j]]; d.tp[j][2] = b->place_p[j][d.ax2[j]];
+    if (!is_identity(b->place_R[j])) {   // columns P e_a, P e_a1, P e_a2 of the row-major placement rotation, then t (fk_place_rot)
+      d.rot_mask |= 1u << j;
+      const int ax[3] = {d.ax0[j], d.ax1[j], d.ax2[j]};
+      for (int c = 0; c < 3; ++c)
+        for (int r = 0; r < 3; ++r) d.rp[j][3 * c + r] = b->place_R[j][3 * r + ax[c]];
+      for (int r = 0; r < 3; ++r) d.rp[j][9 + r] = b->place_p[j][r];
+    }
     d.mass[j] = b->mass[j];
     for (int i = 0; i < 3; ++i) d.com[j][i] = b->com[j][i];
     total += b->mass[j];
@@ -133,7 +155,7 @@ extern "C" int wbc_model_create(const WbcModelBlob* b, WbcModel** out) {
   for (int f = 0; f < b->nframes; ++f) {
     const int jf = b->frame_joint[f];
     if (jf < 1 || jf >= b->njoints) { delete m; return fail(WBC_E_ARG, "frame %d: supporting joint %d out of range", f, jf); }
-    if (!is_identity(b->frame_R[f])) { delete m; return fail(WBC_E_UNSUPPORTED, "frame %d: rotated frame offset unsupported on device", f); }
+    if (!is_identity(b->frame_R[f])) { delete m; return fail(WBC_E_UNSUPPORTED, "frame %d: rotated frame offset unsupported on device (no robot of the reference needs one)", f); }
     d.frame_joint[f] = jf;
     for (int i = 0; i < 3; ++i) d.frame_p[f][i] = b->frame_p[f][i];
     uint32_t mask = 0;
@@ -168,6 +190,7 @@ extern "C" int wbc_batch_create(const WbcModel* const* models, int n_models, int
     dm[i] = models[i]->dev;
     if (models[i]->blob.njoints > b->max_nj) b->max_nj = models[i]->blob.njoints;
     if (models[i]->blob.nframes > b->max_nf) b->max_nf = models[i]->blob.nframes;
+    if (models[i]->dev.rot_mask) b->rot = 1;
   }
   // everything allocated so far is released on any failure below (wbc_batch_destroy frees what is non-null)
 #define HIP_TRY_B(expr)                                                                                              \
@@ -312,7 +335,7 @@ static bool build_pk_fk(const DevModel& M, int need_depth, DevPlan* P) {
           DevPlan::PkJoint& r = P->pk_fk[L][cnt];
           const bool rev = M.jtype[j] >= WBC_JT_RX && M.jtype[j] <= WBC_JT_RZ;
           r.joint = j; r.parent = M.parent[j]; r.a0 = 3 * M.ax0[j]; r.a1 = 3 * M.ax1[j]; r.a2 = 3 * M.ax2[j];
-          r.rev = rev ? 1 : 0; r.q_idx = M.idx_q[j]; r.t0 = M.tp[j][0]; r.t1 = M.tp[j][1]; r.t2 = M.tp[j][2];
+          r.rev = rev ? 1 : 0; r.q_idx = M.idx_q[j]; r.t0 = M.tp[j][0]; r.t1 = M.tp[j][1]; r.t2 = M.tp[j][2]; r.rot = (M.rot_mask >> j) & 1u;
           if (rev && j < 32) P->pk_scq[j] = M.idx_q[j];
         }
         ++cnt;
@@ -337,7 +360,7 @@ static bool build_q_tables(const DevModel& M, DevPlan* P, bool need_subtree) {
         DevPlan::PkJoint& r = P->q_fk[L][cnt++];
         const bool rev = M.jtype[j] >= WBC_JT_RX && M.jtype[j] <= WBC_JT_RZ;
         r.joint = j; r.parent = M.parent[j]; r.a0 = 3 * M.ax0[j]; r.a1 = 3 * M.ax1[j]; r.a2 = 3 * M.ax2[j];
-        r.rev = rev ? 1 : 0; r.q_idx = M.idx_q[j]; r.t0 = M.tp[j][0]; r.t1 = M.tp[j][1]; r.t2 = M.tp[j][2];
+        r.rev = rev ? 1 : 0; r.q_idx = M.idx_q[j]; r.t0 = M.tp[j][0]; r.t1 = M.tp[j][1]; r.t2 = M.tp[j][2]; r.rot = (M.rot_mask >> j) & 1u;
         if (rev) P->q_scq[j] = M.idx_q[j];
       }
   }
@@ -790,7 +813,7 @@ static int validate_tick_in(const WbcBatch* b, const WbcTickIn* in, const char* 
 static int run_posture(WbcBatch* b, int B, const double* q, const int32_t* model_id, double* u, double* q_after, void* stream) {
   PostureArgs pa;
   memset(&pa, 0, sizeof pa);
-  pa.models = b->d_models; pa.cfgs = b->d_cfgs; pa.plans = b->d_plans; pa.B = B; pa.n_models = b->n_models; pa.q = q; pa.model_id = model_id; pa.u = u; pa.q_after = q_after;
+  pa.models = b->d_models; pa.cfgs = b->d_cfgs; pa.plans = b->d_plans; pa.B = B; pa.n_models = b->n_models; pa.q = q; pa.model_id = model_id; pa.u = u; pa.q_after = q_after; pa.rot = b->rot;
   bool par = b->posture_par != 0;
   for (int i = 0; i < b->n_models && par; ++i) par = b->configured[i] && b->plan_host[i].mp_ok != 0;
   bool three = par && b->posture_par != 3;                 // three instances per wavefront where every model has at most 21 sweeps (option value 3: one per wavefront)
@@ -827,7 +850,7 @@ static int auto_posture(WbcBatch* b, KernelArgs& a, int B, void* stream) {
 
 static void fill_args(KernelArgs& a, const WbcBatch* b, int B, double dt) {
   memset(&a, 0, sizeof a);
-  a.models = b->d_models; a.cfgs = b->d_cfgs; a.plans = b->d_plans; a.n_models = b->n_models;
+  a.models = b->d_models; a.cfgs = b->d_cfgs; a.plans = b->d_plans; a.n_models = b->n_models; a.rot = b->rot;
   // J'J on the matrix cores: forced (1), off (0) or, by default (-1), for wide Cartesian stacks only — measured on MI355X
   // (profiles/r02_mfma_evidence.txt): +9 % ticks/s at 33 and 45 Cartesian rows (config 2, "everything"), a wash at 6 (config 3)
   a.B = B; a.mrows = b->mrows; a.prows = b->prows; a.mcart = b->mcart; a.jtj_mfma = b->jtj_mfma < 0 ? (b->mcart >= WBC_MFMA_AUTO_ROWS) : b->jtj_mfma; a.presolve = b->presolve; a.presolve_orth = b->presolve_orth ? 1 + any_orth_plan(b) : 0; a.orth_qr = b->orth_qr; a.refine = b->refine; a.sing_tol = b->sing_tol; a.dbg_alias = b->dbg_alias; a.dt = dt;
@@ -1063,7 +1086,7 @@ extern "C" int wbc_update_state(WbcBatch* b, int B, const double* q_cur, const d
   HIP_TRY(hipSetDevice(b->device_id));
   UpdateArgs a;
   memset(&a, 0, sizeof a);
-  a.models = b->d_models; a.cfgs = b->d_cfgs; a.B = B; a.n_models = b->n_models;
+  a.models = b->d_models; a.cfgs = b->d_cfgs; a.B = B; a.n_models = b->n_models; a.rot = b->rot;
   a.q_cur = q_cur; a.q_next = q_next; a.imu = imu; a.foot_targets = foot_targets; a.model_id = model_id; a.q_new = q_new;
   Stager st{b, mem, (hipStream_t)stream, {}};
   const size_t n = (size_t)B;
@@ -1133,7 +1156,7 @@ extern "C" int wbc_rollout(WbcBatch* b, int B, const WbcTickIn* in0, double dt, 
 
   UpdateArgs u;
   memset(&u, 0, sizeof u);
-  u.models = b->d_models; u.cfgs = b->d_cfgs; u.B = B; u.n_models = b->n_models; u.mode = r->mode;
+  u.models = b->d_models; u.cfgs = b->d_cfgs; u.B = B; u.n_models = b->n_models; u.mode = r->mode; u.rot = b->rot;
   u.q_cur = blk(O_Q); u.q_next = blk(O_QN); u.imu = ro.imu; u.foot_targets = blk(O_EET); u.model_id = a.in.model_id; u.q_new = blk(O_Q);
   u.ee_target = blk(O_EET); u.prev_ee_target = blk(O_EEP);
   u.trunk_target = first.trunk_target ? blk(O_TT) : nullptr; u.prev_trunk_target = first.prev_trunk_target ? blk(O_TP) : nullptr;

@@ -1154,9 +1154,46 @@ __device__ __forceinline__ Hdr load_hdr(const DevModel& M) {
   h.trunk_joint = M.frame_joint[WBC_FR_TRUNK];
   return h;
 }
+// A joint whose placement rotation P is not the identity (DevModel.rot_mask), composed in pinocchio's order oMi[parent] * (placement *
+// jointTransform(q)) as the oracle does (orc_fk): L = P Rot_a(th) column by column — the axis column P e_a as it is, the other two turned by
+// (cs, sn) exactly as the unrotated FK turns the parent's — then R = R_parent L, p = p_parent + R_parent (t + P e_a pris).
+// X, Y, Z, Pv: the parent's rotation columns and origin; pl = DevModel.rp[j] (P e_a, P e_a1, P e_a2, t). Out: the joint's columns a, a1, a2
+// and origin. The axis column depends on no angle of the joint itself, so the posture kernels' "does not matter" analysis still holds.
+__device__ __forceinline__ void fk_place_rot(const double* X, const double* Y, const double* Z, const double* Pv, const double* pl,
+                                             const double sn, const double cs, const double pris, double* nA, double* nB, double* nC,
+                                             double* np) {
+  double la[3], lb[3], lc[3], u[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    la[k] = pl[k];
+    lb[k] = cs * pl[3 + k] + sn * pl[6 + k];
+    lc[k] = cs * pl[6 + k] - sn * pl[3 + k];
+    u[k] = pl[9 + k] + pl[k] * pris;
+  }
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    nA[r] = X[r] * la[0] + Y[r] * la[1] + Z[r] * la[2];
+    nB[r] = X[r] * lb[0] + Y[r] * lb[1] + Z[r] * lb[2];
+    nC[r] = X[r] * lc[0] + Y[r] * lc[1] + Z[r] * lc[2];
+    np[r] = Pv[r] + (X[r] * u[0] + Y[r] * u[1] + Z[r] * u[2]);
+  }
+}
+// the same for the packed kernels' level loops: parent oMi record Pp (LDS, R column-major then p), output record Po, axis offsets a0..a2
+__device__ __forceinline__ void fk_place_rot_lds(double* const Po, const double* const Pp, const double* const pl, const int a0, const int a1,
+                                                 const int a2, const double sn, const double cs, const double pris) {
+  double X[3], Y[3], Z[3], Pv[3], nA[3], nB[3], nC[3], np[3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) { X[r] = Pp[r]; Y[r] = Pp[3 + r]; Z[r] = Pp[6 + r]; Pv[r] = Pp[9 + r]; }
+  fk_place_rot(X, Y, Z, Pv, pl, sn, cs, pris, nA, nB, nC, np);
+#pragma unroll
+  for (int r = 0; r < 3; ++r) { Po[a0 + r] = nA[r]; Po[a1 + r] = nB[r]; Po[a2 + r] = nC[r]; Po[9 + r] = np[r]; }
+}
 // P1: pin.forwardKinematics. qv = the configuration (LDS), oMi = [joint][12] (R column-major, then p), lane j = joint j.
+// ROT: the handle holds a model with rotated joint placements (KernelArgs.rot); Mr is then the instance's model (rot_mask, rp). Without ROT
+// the function compiles exactly as before (Mr unused).
+template <bool ROT = false>
 __device__ __forceinline__ void fk_levels(double* const oMi, const double* const qv, const Hdr& H, const LaneConst& lc,
-                                          const int lane) {
+                                          const int lane, const DevModel* const Mr = nullptr) {
   // root free-flyer: R from the quaternion exactly as Eigen's toRotationMatrix, p = xyz
   if (lane == 1) {
     double Rt[9];
@@ -1174,7 +1211,9 @@ __device__ __forceinline__ void fk_levels(double* const oMi, const double* const
   WSYNC();
 #pragma unroll 1
   for (int lvl = 2; lvl <= H.maxdepth; ++lvl) {
-    if (lc.depth == lvl) {
+    if (ROT && lc.depth == lvl && lc.is_joint && ((Mr->rot_mask >> lane) & 1u)) {
+      fk_place_rot_lds(oMi + 12 * lane, oMi + lc.par_off, Mr->rp[lane & 31], lc.a0, lc.a1, lc.a2, sn, cs, pris);
+    } else if (lc.depth == lvl) {
       const double* Pp = oMi + lc.par_off;
       double Av[3], Bv[3], Cv[3], P[3];
 #pragma unroll
@@ -1205,12 +1244,12 @@ __device__ __forceinline__ void jac_column(const double* const oMi, const LaneCo
 }
 struct FkOut { double lin[3], ang[3], com[3], jc[3], Rtr[9], ptr[3]; };
 // P1..P3 + frames + CoM. oMi and (oMi + OFF_MC) are scratch in LDS; frame origins go to S.pf.
-template <class SM>
+template <bool ROT = false, class SM>
 __device__ __forceinline__ void fk_pass(SM& S, double* const oMi, const double* const qv, const Hdr& H,
                                         const LaneConst& lc, const bool need_com, const int lane, FkOut& o,
-                                        unsigned long long* ts = nullptr) {
+                                        unsigned long long* ts = nullptr, const DevModel* const Mr = nullptr) {
   const int nv = H.nv, nj = H.nj;
-  fk_levels(oMi, qv, H, lc, lane);
+  fk_levels<ROT>(oMi, qv, H, lc, lane, Mr);
 #ifdef WBC_PROFILE
   if (ts) STAMP(ts, T_F1);
 #endif
@@ -1990,7 +2029,7 @@ __device__ __forceinline__ bool orth_direct_assemble(Smem& S, const KA& A, const
 // One instance: FK -> Jacobians -> task stack -> H, g, C, bounds [-> QP -> qdot -> q_next]
 // (inputs already staged in S.in)
 // ------------------------------------------------------------------------------------------------
-template <int MODE, bool WARM = false, bool ORTH = false, class KA = KernelArgs>
+template <int MODE, bool WARM = false, bool ORTH = false, bool ROT = false, class KA = KernelArgs>
 __device__ __forceinline__ void process_instance(Smem& S, const KA& A, const DevModel& M, const WbcConfig& cfg,
                                                  const DevPlan& P, const LaneConst& lc, const InRegs& inr, const int b,
                                                  const int lane, const unsigned long long t_entry = 0) {
@@ -2013,7 +2052,7 @@ __device__ __forceinline__ void process_instance(Smem& S, const KA& A, const Dev
   const bool need_com = cfg.task_com || cfg.con_com || (MODE == MODE_FK && (A.fk.com || A.fk.Jcom));
   FkOut fo;
   const Hdr H = load_hdr(M);
-  fk_pass(S, oMi, qv, H, lc, need_com, lane, fo, ts);
+  fk_pass<ROT>(S, oMi, qv, H, lc, need_com, lane, fo, ts, ROT ? &M : nullptr);
   double (&lin)[3] = fo.lin; double (&ang)[3] = fo.ang; double (&com)[3] = fo.com; double (&jc)[3] = fo.jc;
   double (&Rtr)[9] = fo.Rtr; double (&ptr)[3] = fo.ptr;
 
@@ -2242,14 +2281,14 @@ __device__ __forceinline__ void process_instance(Smem& S, const KA& A, const Dev
     // findConstraints, velDamperJointConstraints and integrate see THAT state. oMi scratch = RB (At is dead).
     if (lane < NQ) S.in[IN_Q + lane] = inr.qc;
     WSYNC();
-    fk_pass(S, S.RB, qv, H, lc, cfg.con_com != 0, lane, fo);
+    fk_pass<ROT>(S, S.RB, qv, H, lc, cfg.con_com != 0, lane, fo, nullptr, ROT ? &M : nullptr);
     WSYNC();
   } else if (A.post_static && P.post_pert) {
     // the same state leak when every finite difference of qpJointb is structurally zero (DevPlan.post_static): each
     // perturbed entry is left at (q + d) - 2 d, and the kinematics are redone only if an active constraint depends on one
     if (lane < NQ && ((P.post_pert >> lane) & 1u)) S.in[IN_Q + lane] = (qv[lane] + 0.0002) - (0.0002 * 2);
     WSYNC();
-    if (P.post_fk2) { fk_pass(S, S.RB, qv, H, lc, cfg.con_com != 0, lane, fo); WSYNC(); }
+    if (P.post_fk2) { fk_pass<ROT>(S, S.RB, qv, H, lc, cfg.con_com != 0, lane, fo, nullptr, ROT ? &M : nullptr); WSYNC(); }
   }
 
   // ---- P6: constraints in order CoM, Trunk, FR, FL, RR, RL, Grip: findConstraints (Robot_Wrapper4.py:764-836)
@@ -2458,7 +2497,7 @@ __device__ __forceinline__ void process_instance(Smem& S, const KA& A, const Dev
 // kernel parameter of both callers): handed the caller's own `A`, the general path's ~90 scalars were fetched at kernel entry and kept alive —
 // spilled to VGPR lanes — across the whole packed path: 480 extra v_writelane / v_readlane in the common path, 3 % of the step (same-box A/B,
 // tools/ab_bench.sh). A real call is not an option: arguments arrive in VGPRs, and the general path pins configuration scalars to SGPRs.
-template <bool WARM, bool ORTH>
+template <bool WARM, bool ORTH, bool ROT = false>
 __device__ __forceinline__ void tail_instance(Smem* Sp, const int bt_v, const DevModel* __restrict__ models, const WbcConfig* __restrict__ cfgs,
                                               const DevPlan* __restrict__ plans) {   // (the kernel's own noalias table pointers: scalar loads)
   Smem& S = *Sp;
@@ -2480,7 +2519,7 @@ __device__ __forceinline__ void tail_instance(Smem* Sp, const int bt_v, const De
   const LaneConst lc = load_lane_const(models[mi], cfgs[mi], ln);
   stage_inputs(S, cur, ln, has2, has3);
   WSYNC();
-  process_instance<MODE_TICK, WARM, ORTH>(S, A, models[mi], cfgs[mi], plans[mi], lc, cur, bt_, ln, 0ull);
+  process_instance<MODE_TICK, WARM, ORTH, ROT>(S, A, models[mi], cfgs[mi], plans[mi], lc, cur, bt_, ln, 0ull);
   WSYNC();
   asm volatile("; WBC_TAIL_END" ::: "memory");
 }

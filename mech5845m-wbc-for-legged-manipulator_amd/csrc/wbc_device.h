@@ -27,6 +27,9 @@ struct DevModel {
   double frame_p[WBC_MAX_FRAMES][3];
   uint32_t frame_support[WBC_MAX_FRAMES];  // bit k: column k moves the frame
   double total_mass;
+  // rotated joint placements (appended: the fields above keep their offsets)
+  uint32_t rot_mask, pad1_;            // bit j: joint j's placement rotation is not the identity (fk_place_rot composes it)
+  double rp[NL][12];                   // rotated joints: placement columns P e_a, P e_a1, P e_a2, then the translation t (unpermuted)
 };
 
 // Structural presolve plan of one (model, configuration): which stance feet's contact equalities are eliminated and
@@ -42,7 +45,8 @@ struct DevPlan {
   int32_t orth;                      // tasks touch the stance legs: contact elimination through an orthonormal null-space basis (contact_presolve_orth)
   int32_t pk_update_ok;              // the packed FK schedule reaches every frame wbc_update_packed_kernel reads, and no trunk task is on
   // packed kernel (wbc_tick_sim3p_kernel): everything a lane needs, one record per role, so that no load depends on another
-  struct PkJoint { int32_t joint, parent, a0, a1, a2, rev, q_idx, pad_; double t0, t1, t2; };   // a*: 3 x column of the axis / its successors in R
+  struct PkJoint { int32_t joint, parent, a0, a1, a2, rev, q_idx, rot; double t0, t1, t2; };   // a*: 3 x column of the axis / its successors in R;
+                                                                                                  // rot: the placement is rotated (DevModel.rp)
   struct PkCol { int32_t dof, joint, lin, ang, dq_idx, pad_[3]; double d_lo, d_hi, d_vm; };       // Jacobian column + velocity-damper entries of a DoF
   PkJoint pk_fk[5][16];              // joints of tree depth 2 + L, one per lane-in-instance (joint -1: none)
   PkCol pk_var[16], pk_leg[16];      // reduced variable s / eliminated leg DoF s
@@ -132,6 +136,7 @@ struct KernelArgs {
   WbcTickOut out;
   WbcQpData qp;
   WbcFkOut fk;
+  int32_t rot;                      // a model of the handle has a rotated joint placement: the packed kernels' ROT instantiations run
 };
 
 struct QpArgs {
@@ -162,6 +167,7 @@ struct PostureArgs {
   const double* q;
   const int32_t* model_id;
   double *u, *q_after;
+  int32_t rot;                         // a model of the handle has a rotated joint placement (wbc_posture_par*_kernel<true>)
 };
 
 // updateState(running=True) + trunkWorldPos, and (rollout only; every pointer below `q_new` may be null) the reference-state
@@ -180,6 +186,7 @@ struct UpdateArgs {
   double* grip_trace;                  // [B][3] of this tick
   const int32_t *status, *iters;       // this tick's
   int32_t *status_max, *iters_sum;
+  int32_t rot;                         // a model of the handle has a rotated joint placement (wbc_update_packed_kernel<true>)
 };
 
 // launchers (one per kernel family, wbc_k_*.hip): single-wave workgroups; tick kernels take grid = B, the QP / integrate kernels min(B, resident waves)

@@ -47,7 +47,7 @@ struct XIntegrate { const double* in; const double* xv; };   // what integrate_f
 #endif
 // WARM: the variant that takes / returns working sets (KernelArgs.ws_in / ws_out, word 0: velocity bounds by DoF) — the packed sim3 kernel's scheme
 // (seeds through the add step, x / u rebuilt from the factors, restoration) on the kept variables; eliminated and locked DoF carry no seed.
-template <bool WARM>
+template <bool WARM, bool ROT = false>   // ROT: rotated joint placements in the batch (wbc_k_sim3p.hip)
 __global__ void __launch_bounds__(64, 2) wbc_tick_boxp_kernel(const KernelArgs A, const DevModel* __restrict__ models,
                                                               const WbcConfig* __restrict__ cfgs, const DevPlan* __restrict__ plans) {
   __shared__ union { XInst Q[4]; Smem G; } SU;
@@ -194,16 +194,20 @@ __global__ void __launch_bounds__(64, 2) wbc_tick_boxp_kernel(const KernelArgs A
       const double* Pp = oMi + 12 * fk.parent;
       const double sn = rev ? sc[2 * j] : 0.0, cs = rev ? sc[2 * j + 1] : 1.0;
       const double pris = rev ? 0.0 : qv[fk.q_idx];
-      double Av[3], Bv[3], Cv[3], Pv[3];
+      if (ROT && fk.rot) {   // rotated placement (ROT instantiations only: the others compile exactly as before)
+        fk_place_rot_lds(oMi + 12 * j, Pp, M.rp[j], a0, a1, a2, sn, cs, pris);
+      } else {
+        double Av[3], Bv[3], Cv[3], Pv[3];
 #pragma unroll
-      for (int rr = 0; rr < 3; ++rr) { Av[rr] = Pp[a0 + rr]; Bv[rr] = Pp[a1 + rr]; Cv[rr] = Pp[a2 + rr]; Pv[rr] = Pp[9 + rr]; }
-      double* Po = oMi + 12 * j;
+        for (int rr = 0; rr < 3; ++rr) { Av[rr] = Pp[a0 + rr]; Bv[rr] = Pp[a1 + rr]; Cv[rr] = Pp[a2 + rr]; Pv[rr] = Pp[9 + rr]; }
+        double* Po = oMi + 12 * j;
 #pragma unroll
-      for (int rr = 0; rr < 3; ++rr) {
-        Po[a0 + rr] = Av[rr];
-        Po[a1 + rr] = cs * Bv[rr] + sn * Cv[rr];
-        Po[a2 + rr] = cs * Cv[rr] - sn * Bv[rr];
-        Po[9 + rr] = Pv[rr] + Av[rr] * (fk.t0 + pris) + Bv[rr] * fk.t1 + Cv[rr] * fk.t2;
+        for (int rr = 0; rr < 3; ++rr) {
+          Po[a0 + rr] = Av[rr];
+          Po[a1 + rr] = cs * Bv[rr] + sn * Cv[rr];
+          Po[a2 + rr] = cs * Cv[rr] - sn * Bv[rr];
+          Po[9 + rr] = Pv[rr] + Av[rr] * (fk.t0 + pris) + Bv[rr] * fk.t1 + Cv[rr] * fk.t2;
+        }
       }
     }
     WSYNC();
@@ -831,7 +835,7 @@ __global__ void __launch_bounds__(64, 2) wbc_tick_boxp_kernel(const KernelArgs A
 #pragma unroll 1
     for (int rr = 0; rr < 4; ++rr) {
       if (!((tailm >> (16 * rr)) & 1ull)) continue;
-      tail_instance<WARM, false>(&SU.G, 4 * (int)blockIdx.x + rr, models, cfgs, plans);
+      tail_instance<WARM, false, ROT>(&SU.G, 4 * (int)blockIdx.x + rr, models, cfgs, plans);
     }
   }
 }
@@ -851,10 +855,22 @@ KINST(true)
 #elif BOXP_PART == 0
 KDECL(true)
 #endif
+#if BOXP_PART == 2 || BOXP_PART == -1
+KINST(false, true)
+KINST(true, true)
+#elif BOXP_PART == 0
+KDECL(false, true)
+KDECL(true, true)
+#endif
 #undef KINST
 #undef KDECL
 #if BOXP_PART <= 0
 int launch_tick_boxp(const KernelArgs& a, void* stream) {
+  if (a.rot) {
+    if (a.ws_in || a.ws_out) hipLaunchKernelGGL((wbc_tick_boxp_kernel<true, true>), dim3((a.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
+    else hipLaunchKernelGGL((wbc_tick_boxp_kernel<false, true>), dim3((a.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
+    return check_launch("tick_boxp");
+  }
   if (a.ws_in || a.ws_out) hipLaunchKernelGGL(wbc_tick_boxp_kernel<true>, dim3((a.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
   else hipLaunchKernelGGL(wbc_tick_boxp_kernel<false>, dim3((a.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
   return check_launch("tick_boxp");

@@ -10,7 +10,8 @@ namespace wbc {
 // WARM: the variant that reads / writes working sets (warm start, KernelArgs.ws_in / ws_out); the cold variant carries none of it
 // ORTH: the variant that carries contact_presolve_orth (chosen by launch_tick when a plan of the batch asks for it: the other
 // variants keep their register allocation — with the extra code inlined the general kernel went from 198 VGPRs to 256 + spills)
-template <int MODE, bool WARM = false, bool ORTH = false>
+// ROT: rotated joint placements in the handle (KernelArgs.rot, fk_levels)
+template <int MODE, bool WARM = false, bool ORTH = false, bool ROT = false>
 __global__ void __launch_bounds__(64, 2) wbc_tick_kernel(const KernelArgs A, const DevModel* __restrict__ models,
                                                          const WbcConfig* __restrict__ cfgs, const DevPlan* __restrict__ plans) {
   // models / cfgs are separate __restrict__ const parameters so that the compiler may read them with scalar loads
@@ -37,7 +38,7 @@ __global__ void __launch_bounds__(64, 2) wbc_tick_kernel(const KernelArgs A, con
   const LaneConst lc = load_lane_const(models[mid], cfgs[mid], lane);   // L1/L2-resident 3 KB table
   stage_inputs(S, cur, lane, has2, has3);
   WSYNC();
-  process_instance<MODE, WARM, ORTH>(S, A, models[mid], cfgs[mid], plans[mid], lc, cur, b, lane, t_entry);
+  process_instance<MODE, WARM, ORTH, ROT>(S, A, models[mid], cfgs[mid], plans[mid], lc, cur, b, lane, t_entry);
 }
 
 // One translation unit per PART (csrc/Makefile compiles this file once per part, in parallel): each part instantiates some of the kernel's
@@ -67,11 +68,35 @@ KINST(MODE_FK)
 KDECL(MODE_ASSEMBLE)
 KDECL(MODE_FK)
 #endif
+#if GENERAL_PART == 4 || GENERAL_PART == -1
+KINST(MODE_TICK, false, false, true)
+KINST(MODE_TICK, true, false, true)
+#elif GENERAL_PART == 0
+KDECL(MODE_TICK, false, false, true)
+KDECL(MODE_TICK, true, false, true)
+#endif
+#if GENERAL_PART == 5 || GENERAL_PART == -1
+KINST(MODE_TICK, false, true, true)
+KINST(MODE_ASSEMBLE, false, false, true)
+KINST(MODE_FK, false, false, true)
+#elif GENERAL_PART == 0
+KDECL(MODE_TICK, false, true, true)
+KDECL(MODE_ASSEMBLE, false, false, true)
+KDECL(MODE_FK, false, false, true)
+#endif
 #undef KINST
 #undef KDECL
 #if GENERAL_PART <= 0
 int launch_tick(const KernelArgs& a, int mode, int grid, void* stream) {
   hipStream_t s = (hipStream_t)stream;
+  if (a.rot) {
+    if (mode == MODE_TICK && (a.ws_in || a.ws_out)) hipLaunchKernelGGL((wbc_tick_kernel<MODE_TICK, true, false, true>), dim3(grid), dim3(64), 0, s, a, a.models, a.cfgs, a.plans);
+    else if (mode == MODE_TICK && a.presolve && a.presolve_orth == 2) hipLaunchKernelGGL((wbc_tick_kernel<MODE_TICK, false, true, true>), dim3(grid), dim3(64), 0, s, a, a.models, a.cfgs, a.plans);
+    else if (mode == MODE_TICK) hipLaunchKernelGGL((wbc_tick_kernel<MODE_TICK, false, false, true>), dim3(grid), dim3(64), 0, s, a, a.models, a.cfgs, a.plans);
+    else if (mode == MODE_ASSEMBLE) hipLaunchKernelGGL((wbc_tick_kernel<MODE_ASSEMBLE, false, false, true>), dim3(grid), dim3(64), 0, s, a, a.models, a.cfgs, a.plans);
+    else hipLaunchKernelGGL((wbc_tick_kernel<MODE_FK, false, false, true>), dim3(grid), dim3(64), 0, s, a, a.models, a.cfgs, a.plans);
+    return check_launch("tick");
+  }
   if (mode == MODE_TICK && (a.ws_in || a.ws_out)) hipLaunchKernelGGL((wbc_tick_kernel<MODE_TICK, true>), dim3(grid), dim3(64), 0, s, a, a.models, a.cfgs, a.plans);
   else if (mode == MODE_TICK && a.presolve && a.presolve_orth == 2) hipLaunchKernelGGL((wbc_tick_kernel<MODE_TICK, false, true>), dim3(grid), dim3(64), 0, s, a, a.models, a.cfgs, a.plans);
   else if (mode == MODE_TICK) hipLaunchKernelGGL(wbc_tick_kernel<MODE_TICK>, dim3(grid), dim3(64), 0, s, a, a.models, a.cfgs, a.plans);

@@ -238,10 +238,11 @@ __device__ __forceinline__ double det6_spd(const double* G) {
   }
   return det > 0.0 ? det : 0.0;
 }
+template <bool ROT>
 __device__ __forceinline__ double manipulability(PSmem& P, const DevModel& M, const LaneConst& lc, const int joint_id,
                                                  const int lane) {
   const int nv = M.nv;
-  fk_levels(P.oMi, P.q, load_hdr(M), lc, lane);
+  fk_levels<ROT>(P.oMi, P.q, load_hdr(M), lc, lane, ROT ? &M : nullptr);
   double lin[3], ang[3];
   jac_column(P.oMi, lc, lane, nv, lin, ang);
   const double* Pj = P.oMi + 12 * joint_id;
@@ -267,6 +268,7 @@ __device__ __forceinline__ double manipulability(PSmem& P, const DevModel& M, co
   return f;
 }
 
+template <bool ROT = false>   // ROT: rotated joint placements in the handle (fk_levels)
 __global__ void __launch_bounds__(64) wbc_posture_kernel(const PostureArgs A, const DevModel* __restrict__ models,
                                                          const WbcConfig* __restrict__ cfgs) {
   __shared__ PSmem P;
@@ -305,10 +307,10 @@ __global__ void __launch_bounds__(64) wbc_posture_kernel(const PostureArgs A, co
       if (lane == 0) P.q[qi] = keep + dq;
       WSYNC();
       double f1 = 0.0, f2 = 0.0;
-      if (matters) f1 = manipulability(P, M, lc, joint_id, lane);
+      if (matters) f1 = manipulability<ROT>(P, M, lc, joint_id, lane);
       if (lane == 0) P.q[qi] = (keep + dq) - (dq * 2);
       WSYNC();
-      if (matters) f2 = manipulability(P, M, lc, joint_id, lane);
+      if (matters) f2 = manipulability<ROT>(P, M, lc, joint_id, lane);
       if (lane == i) u = 0.5 * (f1 - f2) / dq;
       if (!literal) { if (lane == 0) P.q[qi] = keep; WSYNC(); }
     }
@@ -335,6 +337,7 @@ struct __attribute__((aligned(16))) MPSmem {
   double f[64];
   double uo[32];          // u of the swept DoF
 };
+template <bool ROT = false>   // ROT: rotated joint placements in the batch (wbc_k_sim3p.hip)
 __global__ void __launch_bounds__(64) wbc_posture_par_kernel(const PostureArgs A, const DevModel* __restrict__ models,
                                                              const WbcConfig* __restrict__ cfgs, const DevPlan* __restrict__ plans) {
   __shared__ MPSmem S;
@@ -430,11 +433,18 @@ __global__ void __launch_bounds__(64) wbc_posture_par_kernel(const PostureArgs A
           Cv[rr] = (a == 0) ? Z[rr] : ((a == 1) ? X[rr] : Y[rr]);
         }
         double nB[3], nC[3];
+        if (ROT && ((M.rot_mask >> j) & 1u)) {         // rotated placement: its new axis column takes Av's place (ROT instantiation only)
+          double nA[3], np[3];
+          fk_place_rot(X, Y, Z, p, M.rp[j], sn, cs, pris, nA, nB, nC, np);
 #pragma unroll
-        for (int rr = 0; rr < 3; ++rr) {
-          nB[rr] = cs * Bv[rr] + sn * Cv[rr];
-          nC[rr] = cs * Cv[rr] - sn * Bv[rr];
-          p[rr] = p[rr] + Av[rr] * (t0 + pris) + Bv[rr] * t1 + Cv[rr] * t2;
+          for (int rr = 0; rr < 3; ++rr) { Av[rr] = nA[rr]; p[rr] = np[rr]; }
+        } else {
+#pragma unroll
+          for (int rr = 0; rr < 3; ++rr) {
+            nB[rr] = cs * Bv[rr] + sn * Cv[rr];
+            nC[rr] = cs * Cv[rr] - sn * Bv[rr];
+            p[rr] = p[rr] + Av[rr] * (t0 + pris) + Bv[rr] * t1 + Cv[rr] * t2;
+          }
         }
 #pragma unroll
         for (int rr = 0; rr < 3; ++rr) {
@@ -500,6 +510,7 @@ __global__ void __launch_bounds__(64) wbc_posture_par_kernel(const PostureArgs A
 // sweep k = lane % 21, and the lane evaluates BOTH sides of its central difference one after the other — 63 of 64 lanes busy where the kernel above
 // keeps 42; the same arithmetic per evaluation (bit-identical u). Roles with more than 21 entries (configuration, sin / cos table, outputs) take
 // two or three rounds of the instance's 21 lanes.
+template <bool ROT = false>
 __global__ void __launch_bounds__(64) wbc_posture_par3_kernel(const PostureArgs A, const DevModel* __restrict__ models,
                                                               const WbcConfig* __restrict__ cfgs, const DevPlan* __restrict__ plans) {
   __shared__ MPSmem S3[3];
@@ -608,11 +619,18 @@ __global__ void __launch_bounds__(64) wbc_posture_par3_kernel(const PostureArgs 
           Cv[rr] = (a == 0) ? Z[rr] : ((a == 1) ? X[rr] : Y[rr]);
         }
         double nB[3], nC[3];
+        if (ROT && ((M.rot_mask >> j) & 1u)) {         // rotated placement: its new axis column takes Av's place (ROT instantiation only)
+          double nA[3], np[3];
+          fk_place_rot(X, Y, Z, p, M.rp[j], sn, cs, pris, nA, nB, nC, np);
 #pragma unroll
-        for (int rr = 0; rr < 3; ++rr) {
-          nB[rr] = cs * Bv[rr] + sn * Cv[rr];
-          nC[rr] = cs * Cv[rr] - sn * Bv[rr];
-          p[rr] = p[rr] + Av[rr] * (t0 + pris) + Bv[rr] * t1 + Cv[rr] * t2;
+          for (int rr = 0; rr < 3; ++rr) { Av[rr] = nA[rr]; p[rr] = np[rr]; }
+        } else {
+#pragma unroll
+          for (int rr = 0; rr < 3; ++rr) {
+            nB[rr] = cs * Bv[rr] + sn * Cv[rr];
+            nC[rr] = cs * Cv[rr] - sn * Bv[rr];
+            p[rr] = p[rr] + Av[rr] * (t0 + pris) + Bv[rr] * t1 + Cv[rr] * t2;
+          }
         }
 #pragma unroll
         for (int rr = 0; rr < 3; ++rr) {
@@ -689,6 +707,7 @@ struct __attribute__((aligned(16))) USmem {
   double pf[WBC_MAX_FRAMES * 3];
   double ft[16];
 };
+template <bool ROT = false>   // ROT: rotated joint placements in the handle (fk_levels)
 __global__ void __launch_bounds__(64) wbc_update_kernel(const UpdateArgs A, const DevModel* __restrict__ models,
                                                         const WbcConfig* __restrict__ cfgs) {
   __shared__ USmem U;
@@ -722,7 +741,7 @@ __global__ void __launch_bounds__(64) wbc_update_kernel(const UpdateArgs A, cons
   if (lane < 32) U.q[lane] = c;
   if (lane < 12) U.ft[lane] = ft;
   WSYNC();
-  fk_levels(U.oMi, U.q, load_hdr(M), lc, lane);
+  fk_levels<ROT>(U.oMi, U.q, load_hdr(M), lc, lane, ROT ? &M : nullptr);
   if (lane < M.nframes) {
     const double* Pj = U.oMi + lc.fj_off;
 #pragma unroll
@@ -793,6 +812,7 @@ struct __attribute__((aligned(16))) UInst {
   double ft[16];
 };
 struct __attribute__((aligned(16))) USmemP { UInst I[4]; };
+template <bool ROT = false>   // ROT: rotated joint placements in the batch (wbc_k_sim3p.hip)
 __global__ void __launch_bounds__(64) wbc_update_packed_kernel(const UpdateArgs A, const DevModel* __restrict__ models,
                                                                const WbcConfig* __restrict__ cfgs, const DevPlan* __restrict__ plans) {
   __shared__ USmemP UP;
@@ -866,16 +886,20 @@ __global__ void __launch_bounds__(64) wbc_update_packed_kernel(const UpdateArgs 
       const double* Pp = oMi + 12 * fk.parent;
       const double sn = rev ? U.sc[2 * j] : 0.0, cs = rev ? U.sc[2 * j + 1] : 1.0;
       const double pris = rev ? 0.0 : qv[fk.q_idx];
-      double Av[3], Bv[3], Cv[3], Pv[3];
+      if (ROT && fk.rot) {   // rotated placement (ROT instantiations only: the others compile exactly as before)
+        fk_place_rot_lds(oMi + 12 * j, Pp, M.rp[j], a0, a1, a2, sn, cs, pris);
+      } else {
+        double Av[3], Bv[3], Cv[3], Pv[3];
 #pragma unroll
-      for (int rr = 0; rr < 3; ++rr) { Av[rr] = Pp[a0 + rr]; Bv[rr] = Pp[a1 + rr]; Cv[rr] = Pp[a2 + rr]; Pv[rr] = Pp[9 + rr]; }
-      double* Po = oMi + 12 * j;
+        for (int rr = 0; rr < 3; ++rr) { Av[rr] = Pp[a0 + rr]; Bv[rr] = Pp[a1 + rr]; Cv[rr] = Pp[a2 + rr]; Pv[rr] = Pp[9 + rr]; }
+        double* Po = oMi + 12 * j;
 #pragma unroll
-      for (int rr = 0; rr < 3; ++rr) {
-        Po[a0 + rr] = Av[rr];
-        Po[a1 + rr] = cs * Bv[rr] + sn * Cv[rr];
-        Po[a2 + rr] = cs * Cv[rr] - sn * Bv[rr];
-        Po[9 + rr] = Pv[rr] + Av[rr] * (fk.t0 + pris) + Bv[rr] * fk.t1 + Cv[rr] * fk.t2;
+        for (int rr = 0; rr < 3; ++rr) {
+          Po[a0 + rr] = Av[rr];
+          Po[a1 + rr] = cs * Bv[rr] + sn * Cv[rr];
+          Po[a2 + rr] = cs * Cv[rr] - sn * Bv[rr];
+          Po[9 + rr] = Pv[rr] + Av[rr] * (fk.t0 + pris) + Bv[rr] * fk.t1 + Cv[rr] * fk.t2;
+        }
       }
     }
     WSYNC();
@@ -954,23 +978,28 @@ int launch_integrate(const IntegrateArgs& a, int grid, void* stream) {
 }
 
 int launch_posture(const PostureArgs& a, int grid, void* stream) {
-  hipLaunchKernelGGL(wbc_posture_kernel, dim3(grid), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs);
+  if (a.rot) hipLaunchKernelGGL(wbc_posture_kernel<true>, dim3(grid), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs);
+  else hipLaunchKernelGGL(wbc_posture_kernel<false>, dim3(grid), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs);
   return check_launch("posture");
 }
 
 int launch_posture_par(const PostureArgs& a, int grid, void* stream, int three) {
-  if (three) hipLaunchKernelGGL(wbc_posture_par3_kernel, dim3((a.B + 2) / 3), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
-  else hipLaunchKernelGGL(wbc_posture_par_kernel, dim3(grid), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
+  if (three && a.rot) hipLaunchKernelGGL(wbc_posture_par3_kernel<true>, dim3((a.B + 2) / 3), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
+  else if (three) hipLaunchKernelGGL(wbc_posture_par3_kernel<false>, dim3((a.B + 2) / 3), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
+  else if (a.rot) hipLaunchKernelGGL(wbc_posture_par_kernel<true>, dim3(grid), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
+  else hipLaunchKernelGGL(wbc_posture_par_kernel<false>, dim3(grid), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
   return check_launch("posture_par");
 }
 
 int launch_update(const UpdateArgs& a, int grid, void* stream) {
-  hipLaunchKernelGGL(wbc_update_kernel, dim3(grid), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs);
+  if (a.rot) hipLaunchKernelGGL(wbc_update_kernel<true>, dim3(grid), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs);
+  else hipLaunchKernelGGL(wbc_update_kernel<false>, dim3(grid), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs);
   return check_launch("update");
 }
 
 int launch_update_packed(const UpdateArgs& a, void* stream) {
-  hipLaunchKernelGGL(wbc_update_packed_kernel, dim3((a.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
+  if (a.rot) hipLaunchKernelGGL(wbc_update_packed_kernel<true>, dim3((a.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
+  else hipLaunchKernelGGL(wbc_update_packed_kernel<false>, dim3((a.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
   return check_launch("update_packed");
 }
 #endif

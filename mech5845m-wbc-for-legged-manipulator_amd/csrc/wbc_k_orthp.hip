@@ -46,7 +46,7 @@ static_assert(offsetof(QInst, xv) - offsetof(QInst, cl) == 80 * sizeof(double), 
 // the tail with the flagged ones.
 // WARM (INEQ only): working sets in and out — the packed sim3 kernel's scheme (seeds through the add step, x / u rebuilt from the factors, restoration).
 // In FULL-problem indexing a row of Z is the velocity bound of its DoF (word 0), the trunk / CoM box rows are findConstraints' rows (word 1).
-template <bool INEQ, bool WARM = false>
+template <bool INEQ, bool WARM = false, bool ROT = false>   // ROT: rotated joint placements in the batch (wbc_k_sim3p.hip)
 __global__ void __launch_bounds__(64, 2) wbc_tick_orthp_kernel(const KernelArgs A, const DevModel* __restrict__ models,
                                                                const WbcConfig* __restrict__ cfgs, const DevPlan* __restrict__ plans) {
   __shared__ union { QInst Q[4]; Smem G; } SU;
@@ -199,16 +199,20 @@ __global__ void __launch_bounds__(64, 2) wbc_tick_orthp_kernel(const KernelArgs 
       const double* Pp = oMi + 12 * fk.parent;
       const double sn = rev ? sc[2 * j] : 0.0, cs = rev ? sc[2 * j + 1] : 1.0;
       const double pris = rev ? 0.0 : qv[fk.q_idx];
-      double Av[3], Bv[3], Cv[3], Pv[3];
+      if (ROT && fk.rot) {   // rotated placement (ROT instantiations only: the others compile exactly as before)
+        fk_place_rot_lds(oMi + 12 * j, Pp, M.rp[j], a0, a1, a2, sn, cs, pris);
+      } else {
+        double Av[3], Bv[3], Cv[3], Pv[3];
 #pragma unroll
-      for (int rr = 0; rr < 3; ++rr) { Av[rr] = Pp[a0 + rr]; Bv[rr] = Pp[a1 + rr]; Cv[rr] = Pp[a2 + rr]; Pv[rr] = Pp[9 + rr]; }
-      double* Po = oMi + 12 * j;
+        for (int rr = 0; rr < 3; ++rr) { Av[rr] = Pp[a0 + rr]; Bv[rr] = Pp[a1 + rr]; Cv[rr] = Pp[a2 + rr]; Pv[rr] = Pp[9 + rr]; }
+        double* Po = oMi + 12 * j;
 #pragma unroll
-      for (int rr = 0; rr < 3; ++rr) {
-        Po[a0 + rr] = Av[rr];
-        Po[a1 + rr] = cs * Bv[rr] + sn * Cv[rr];
-        Po[a2 + rr] = cs * Cv[rr] - sn * Bv[rr];
-        Po[9 + rr] = Pv[rr] + Av[rr] * (fk.t0 + pris) + Bv[rr] * fk.t1 + Cv[rr] * fk.t2;
+        for (int rr = 0; rr < 3; ++rr) {
+          Po[a0 + rr] = Av[rr];
+          Po[a1 + rr] = cs * Bv[rr] + sn * Cv[rr];
+          Po[a2 + rr] = cs * Cv[rr] - sn * Bv[rr];
+          Po[9 + rr] = Pv[rr] + Av[rr] * (fk.t0 + pris) + Bv[rr] * fk.t1 + Cv[rr] * fk.t2;
+        }
       }
     }
     WSYNC();
@@ -1093,8 +1097,8 @@ __global__ void __launch_bounds__(64, 2) wbc_tick_orthp_kernel(const KernelArgs 
 #pragma unroll 1
     for (int rr = 0; rr < 4; ++rr) {
       if (!((tailm >> (16 * rr)) & 1ull)) continue;
-      if (INEQ && WARM) tail_instance<true, false>(&SU.G, 4 * (int)blockIdx.x + rr, models, cfgs, plans);     // (the general kernel's warm path: full-size solve)
-      else tail_instance<false, true>(&SU.G, 4 * (int)blockIdx.x + rr, models, cfgs, plans);
+      if (INEQ && WARM) tail_instance<true, false, ROT>(&SU.G, 4 * (int)blockIdx.x + rr, models, cfgs, plans);     // (the general kernel's warm path: full-size solve)
+      else tail_instance<false, true, ROT>(&SU.G, 4 * (int)blockIdx.x + rr, models, cfgs, plans);
     }
   }
 }
@@ -1119,10 +1123,25 @@ KINST(true, true)
 #elif ORTHP_PART == 0
 KDECL(true, true)
 #endif
+#if ORTHP_PART == 3 || ORTHP_PART == -1
+KINST(false, false, true)
+KINST(true, false, true)
+KINST(true, true, true)
+#elif ORTHP_PART == 0
+KDECL(false, false, true)
+KDECL(true, false, true)
+KDECL(true, true, true)
+#endif
 #undef KINST
 #undef KDECL
 #if ORTHP_PART <= 0
 int launch_tick_orthp(const KernelArgs& a, void* stream, int ineq) {
+  if (a.rot) {
+    if (ineq && (a.ws_in || a.ws_out)) hipLaunchKernelGGL((wbc_tick_orthp_kernel<true, true, true>), dim3((a.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
+    else if (ineq) hipLaunchKernelGGL((wbc_tick_orthp_kernel<true, false, true>), dim3((a.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
+    else hipLaunchKernelGGL((wbc_tick_orthp_kernel<false, false, true>), dim3((a.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
+    return check_launch("tick_orthp");
+  }
   if (ineq && (a.ws_in || a.ws_out)) hipLaunchKernelGGL((wbc_tick_orthp_kernel<true, true>), dim3((a.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
   else if (ineq) hipLaunchKernelGGL(wbc_tick_orthp_kernel<true>, dim3((a.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
   else hipLaunchKernelGGL(wbc_tick_orthp_kernel<false>, dim3((a.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);

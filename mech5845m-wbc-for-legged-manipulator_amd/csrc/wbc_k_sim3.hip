@@ -62,7 +62,7 @@ __device__ __forceinline__ void jtj_block_c(SmemC& S, const double* At, const in
 #define DBG_STOP_ARG 0
 #endif
 
-template <bool WARM>
+template <bool WARM, bool ROT = false>
 __device__ __forceinline__ void process_sim3(SmemC& S, const KernelArgs& A, const DevModel& M, const WbcConfig& cfg,
                                              const DevPlan& P, const Hdr& H, const LaneConst& lc, const InRegs& inr,
                                              const int b, const int lane, const unsigned long long ws0, const unsigned long long ws1) {
@@ -82,7 +82,7 @@ __device__ __forceinline__ void process_sim3(SmemC& S, const KernelArgs& A, cons
   STAMP(ts, T_START);
   // ---- P1..P3 (updateState, Robot_Wrapper4.py:400-405)
   FkOut fo;
-  fk_pass(S, S.RA, qv, H, lc, c_con_com, lane, fo);
+  fk_pass<ROT>(S, S.RA, qv, H, lc, c_con_com, lane, fo, nullptr, ROT ? &M : nullptr);
   double (&lin)[3] = fo.lin; double (&ang)[3] = fo.ang; double (&com)[3] = fo.com; double (&jc)[3] = fo.jc;
   double (&Rtr)[9] = fo.Rtr; double (&ptr)[3] = fo.ptr;
 
@@ -244,12 +244,12 @@ __device__ __forceinline__ void process_sim3(SmemC& S, const KernelArgs& A, cons
   if (A.in.q_con) {   // the configuration qpJointb MANI/HYBRID left behind: constraints, bounds, integrate see it
     if (lane < NQ) S.in[IN_Q + lane] = inr.qc;
     WSYNC();
-    fk_pass(S, S.RB, qv, H, lc, c_con_com, lane, fo);
+    fk_pass<ROT>(S, S.RB, qv, H, lc, c_con_com, lane, fo, nullptr, ROT ? &M : nullptr);
     WSYNC();
   } else if (A.post_static && P.post_pert) {   // same leak, structurally-zero gradients (see process_instance)
     if (lane < NQ && ((P.post_pert >> lane) & 1u)) S.in[IN_Q + lane] = (qv[lane] + 0.0002) - (0.0002 * 2);
     WSYNC();
-    if (P.post_fk2) { fk_pass(S, S.RB, qv, H, lc, c_con_com, lane, fo); WSYNC(); }
+    if (P.post_fk2) { fk_pass<ROT>(S, S.RB, qv, H, lc, c_con_com, lane, fo, nullptr, ROT ? &M : nullptr); WSYNC(); }
   }
 
   // ---- original constraint rows (findConstraints order, Robot_Wrapper4.py:764-836) into the scratch image Co = RB [p][26]
@@ -621,7 +621,7 @@ __device__ __forceinline__ void process_sim3(SmemC& S, const KernelArgs& A, cons
 #endif
 }
 
-template <bool WARM>
+template <bool WARM, bool ROT = false>   // ROT: rotated joint placements in the handle (KernelArgs.rot, fk_levels)
 __global__ void __launch_bounds__(64, 3) wbc_tick_sim3_kernel(const KernelArgs A, const DevModel* __restrict__ models,
                                                               const WbcConfig* __restrict__ cfgs, const DevPlan* __restrict__ plans) {
   __shared__ SmemC S;
@@ -638,7 +638,7 @@ __global__ void __launch_bounds__(64, 3) wbc_tick_sim3_kernel(const KernelArgs A
   const unsigned long long ws0 = (WARM && A.ws_in) ? A.ws_in[2 * (size_t)b] : 0ull, ws1 = (WARM && A.ws_in) ? A.ws_in[2 * (size_t)b + 1] : 0ull;
   stage_inputs(S, cur, lane, has2, false);
   WSYNC();
-  process_sim3<WARM>(S, A, models[mid], cfgs[mid], plans[mid], H, lc, cur, b, lane, ws0, ws1);
+  process_sim3<WARM, ROT>(S, A, models[mid], cfgs[mid], plans[mid], H, lc, cur, b, lane, ws0, ws1);
 }
 
 // Second pass after wbc_tick_sim3_kernel: the instances it deferred (a stance-leg block it could not eliminate) are redone on
@@ -646,6 +646,7 @@ __global__ void __launch_bounds__(64, 3) wbc_tick_sim3_kernel(const KernelArgs A
 // order); workgroup i takes entries i, i + gridDim.x, ... — with at most gridDim.x deferred instances (the usual handful)
 // every one has a workgroup of its own, and a batch that defers everything is spread over the whole chip instead of being
 // walked 64 instances per wave. Every wave reaches the loop exit (i >= count).
+template <bool ROT = false>
 __global__ void __launch_bounds__(64, 2) wbc_tick_deferred_kernel(const KernelArgs A, const DevModel* __restrict__ models,
                                                                   const WbcConfig* __restrict__ cfgs, const DevPlan* __restrict__ plans) {
   __shared__ Smem S;
@@ -673,7 +674,7 @@ __global__ void __launch_bounds__(64, 2) wbc_tick_deferred_kernel(const KernelAr
     const LaneConst lc = load_lane_const(models[mid], cfgs[mid], lane);
     stage_inputs(S, cur, lane, has2, has3);
     WSYNC();
-    process_instance<MODE_TICK, true>(S, A, models[mid], cfgs[mid], plans[mid], lc, cur, b, lane, 0ull);
+    process_instance<MODE_TICK, true, false, ROT>(S, A, models[mid], cfgs[mid], plans[mid], lc, cur, b, lane, 0ull);
     WSYNC();
   }
   if (lane0 == 0) {
@@ -684,18 +685,39 @@ __global__ void __launch_bounds__(64, 2) wbc_tick_deferred_kernel(const KernelAr
 }
 
 
+// One translation unit per PART (csrc/Makefile): part 0 holds the kernels' unrotated variants and the launchers, part 1 the ROT variants (kept
+// apart: instantiated in the same unit they moved the unrotated variants' spill counts).
+#ifndef SIM3_PART
+#define SIM3_PART -1      // -1: everything in one unit
+#endif
+#define KARGS const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__
+#if SIM3_PART == 1 || SIM3_PART == -1
+template __global__ void wbc_tick_sim3_kernel<false, true>(KARGS);
+template __global__ void wbc_tick_sim3_kernel<true, true>(KARGS);
+template __global__ void wbc_tick_deferred_kernel<true>(KARGS);
+#elif SIM3_PART == 0
+extern template __global__ void wbc_tick_sim3_kernel<false, true>(KARGS);
+extern template __global__ void wbc_tick_sim3_kernel<true, true>(KARGS);
+extern template __global__ void wbc_tick_deferred_kernel<true>(KARGS);
+#endif
+#undef KARGS
+#if SIM3_PART <= 0
 int launch_tick_sim3(const KernelArgs& a, int grid, void* stream) {
-  if (a.ws_in || a.ws_out) hipLaunchKernelGGL(wbc_tick_sim3_kernel<true>, dim3(grid), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
+  if (a.rot && (a.ws_in || a.ws_out)) hipLaunchKernelGGL((wbc_tick_sim3_kernel<true, true>), dim3(grid), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
+  else if (a.rot) hipLaunchKernelGGL((wbc_tick_sim3_kernel<false, true>), dim3(grid), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
+  else if (a.ws_in || a.ws_out) hipLaunchKernelGGL(wbc_tick_sim3_kernel<true>, dim3(grid), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
   else hipLaunchKernelGGL(wbc_tick_sim3_kernel<false>, dim3(grid), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
   return check_launch("tick_sim3");
 }
 
 int launch_tick_deferred(const KernelArgs& a, void* stream) {
   const int grid = a.B < 2048 ? a.B : 2048;    // 8 general-path workgroups per CU: one round of the chip
-  hipLaunchKernelGGL(wbc_tick_deferred_kernel, dim3(grid), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
+  if (a.rot) hipLaunchKernelGGL(wbc_tick_deferred_kernel<true>, dim3(grid), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
+  else hipLaunchKernelGGL(wbc_tick_deferred_kernel<false>, dim3(grid), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
   return check_launch("tick_deferred");
 }
 
 int sim3_lds_bytes() { return (int)sizeof(SmemC); }
+#endif
 
 }  // namespace wbc

@@ -23,7 +23,9 @@ namespace wbc {
 #ifndef SIM3P_WAVES
 #define SIM3P_WAVES 2      // waves per SIMD the register allocation is made for (3: an experiment, tools/hot_path_spills.py with WBC_XFLAGS="-DSIM3P_WAVES=3 -DWBC_NO_TAIL")
 #endif
-template <bool WARM, bool TRUNK = false, bool QCON = false>
+// ROT: the batch holds a model with a rotated joint placement (DevModel.rot_mask): its FK records with `rot` go through fk_place_rot_lds.
+// The instantiations without it compile to exactly the code they had before the flag existed.
+template <bool WARM, bool TRUNK = false, bool QCON = false, bool ROT = false>
 #ifdef SIM3P_NUM_VGPR
 __attribute__((amdgpu_waves_per_eu(SIM3P_NUM_VGPR, SIM3P_NUM_VGPR)))
 #endif
@@ -236,16 +238,20 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
       const double* Pp = oMi + 12 * fk.parent;
       const double sn = rev ? sc[2 * j] : 0.0, cs = rev ? sc[2 * j + 1] : 1.0;
       const double pris = rev ? 0.0 : qv[fk.q_idx];
-      double Av[3], Bv[3], Cv[3], Pv[3];
+      if (ROT && fk.rot) {   // rotated placement (ROT instantiations only: the others compile exactly as before)
+        fk_place_rot_lds(oMi + 12 * j, Pp, M.rp[j], a0, a1, a2, sn, cs, pris);
+      } else {
+        double Av[3], Bv[3], Cv[3], Pv[3];
 #pragma unroll
-      for (int rr = 0; rr < 3; ++rr) { Av[rr] = Pp[a0 + rr]; Bv[rr] = Pp[a1 + rr]; Cv[rr] = Pp[a2 + rr]; Pv[rr] = Pp[9 + rr]; }
-      double* Po = oMi + 12 * j;
+        for (int rr = 0; rr < 3; ++rr) { Av[rr] = Pp[a0 + rr]; Bv[rr] = Pp[a1 + rr]; Cv[rr] = Pp[a2 + rr]; Pv[rr] = Pp[9 + rr]; }
+        double* Po = oMi + 12 * j;
 #pragma unroll
-      for (int rr = 0; rr < 3; ++rr) {
-        Po[a0 + rr] = Av[rr];
-        Po[a1 + rr] = cs * Bv[rr] + sn * Cv[rr];
-        Po[a2 + rr] = cs * Cv[rr] - sn * Bv[rr];
-        Po[9 + rr] = Pv[rr] + Av[rr] * (fk.t0 + pris) + Bv[rr] * fk.t1 + Cv[rr] * fk.t2;
+        for (int rr = 0; rr < 3; ++rr) {
+          Po[a0 + rr] = Av[rr];
+          Po[a1 + rr] = cs * Bv[rr] + sn * Cv[rr];
+          Po[a2 + rr] = cs * Cv[rr] - sn * Bv[rr];
+          Po[9 + rr] = Pv[rr] + Av[rr] * (fk.t0 + pris) + Bv[rr] * fk.t1 + Cv[rr] * fk.t2;
+        }
       }
     }
     WSYNC();
@@ -409,16 +415,20 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
       const double* Pp = oMi + 12 * fk.parent;
       const double sn = rev ? sc[2 * j] : 0.0, cs = rev ? sc[2 * j + 1] : 1.0;
       const double pris = rev ? 0.0 : qv[fk.q_idx];
-      double Av[3], Bv[3], Cv[3], Pv[3];
+      if (ROT && fk.rot) {   // rotated placement (ROT instantiations only: the others compile exactly as before)
+        fk_place_rot_lds(oMi + 12 * j, Pp, M.rp[j], a0, a1, a2, sn, cs, pris);
+      } else {
+        double Av[3], Bv[3], Cv[3], Pv[3];
 #pragma unroll
-      for (int rr = 0; rr < 3; ++rr) { Av[rr] = Pp[a0 + rr]; Bv[rr] = Pp[a1 + rr]; Cv[rr] = Pp[a2 + rr]; Pv[rr] = Pp[9 + rr]; }
-      double* Po = oMi + 12 * j;
+        for (int rr = 0; rr < 3; ++rr) { Av[rr] = Pp[a0 + rr]; Bv[rr] = Pp[a1 + rr]; Cv[rr] = Pp[a2 + rr]; Pv[rr] = Pp[9 + rr]; }
+        double* Po = oMi + 12 * j;
 #pragma unroll
-      for (int rr = 0; rr < 3; ++rr) {
-        Po[a0 + rr] = Av[rr];
-        Po[a1 + rr] = cs * Bv[rr] + sn * Cv[rr];
-        Po[a2 + rr] = cs * Cv[rr] - sn * Bv[rr];
-        Po[9 + rr] = Pv[rr] + Av[rr] * (fk.t0 + pris) + Bv[rr] * fk.t1 + Cv[rr] * fk.t2;
+        for (int rr = 0; rr < 3; ++rr) {
+          Po[a0 + rr] = Av[rr];
+          Po[a1 + rr] = cs * Bv[rr] + sn * Cv[rr];
+          Po[a2 + rr] = cs * Cv[rr] - sn * Bv[rr];
+          Po[9 + rr] = Pv[rr] + Av[rr] * (fk.t0 + pris) + Bv[rr] * fk.t1 + Cv[rr] * fk.t2;
+        }
       }
     }
     WSYNC();
@@ -1287,7 +1297,7 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
 #pragma unroll 1
     for (int rr = 0; rr < 4; ++rr) {
       if (!((tailm >> (16 * rr)) & 1ull)) continue;
-      tail_instance<WARM, false>(&SU.G, 4 * grp + rr, models, cfgs, plans);
+      tail_instance<WARM, false, ROT>(&SU.G, 4 * grp + rr, models, cfgs, plans);
     }
   }
 #endif
@@ -1319,18 +1329,41 @@ KINST(true, false, true)
 KDECL(false, false, true)
 KDECL(true, false, true)
 #endif
+#if SIM3P_PART == 3 || SIM3P_PART == -1
+KINST(false, false, false, true)
+KINST(true, false, false, true)
+KINST(false, true, false, true)
+KINST(true, true, false, true)
+#elif SIM3P_PART == 0
+KDECL(false, false, false, true)
+KDECL(true, false, false, true)
+KDECL(false, true, false, true)
+KDECL(true, true, false, true)
+#endif
+#if SIM3P_PART == 4 || SIM3P_PART == -1
+KINST(false, false, true, true)
+KINST(true, false, true, true)
+#elif SIM3P_PART == 0
+KDECL(false, false, true, true)
+KDECL(true, false, true, true)
+#endif
 #undef KINST
 #undef KDECL
 #if SIM3P_PART <= 0
-int launch_tick_sim3p(const KernelArgs& a, void* stream) {
+template <bool ROT>
+static void launch_sim3p_variant(const KernelArgs& a, void* stream) {
   const bool warm = a.ws_in || a.ws_out, trunk = a.in.trunk_target && a.packed_trunk, qcon = a.in.q_con || a.in.posture_u;
   const dim3 grid((a.B + 3) / 4);
-  if (qcon && warm) hipLaunchKernelGGL((wbc_tick_sim3p_kernel<true, false, true>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
-  else if (qcon) hipLaunchKernelGGL((wbc_tick_sim3p_kernel<false, false, true>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
-  else if (warm && trunk) hipLaunchKernelGGL((wbc_tick_sim3p_kernel<true, true>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
-  else if (trunk) hipLaunchKernelGGL((wbc_tick_sim3p_kernel<false, true>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
-  else if (warm) hipLaunchKernelGGL((wbc_tick_sim3p_kernel<true, false>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
-  else hipLaunchKernelGGL((wbc_tick_sim3p_kernel<false, false>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
+  if (qcon && warm) hipLaunchKernelGGL((wbc_tick_sim3p_kernel<true, false, true, ROT>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
+  else if (qcon) hipLaunchKernelGGL((wbc_tick_sim3p_kernel<false, false, true, ROT>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
+  else if (warm && trunk) hipLaunchKernelGGL((wbc_tick_sim3p_kernel<true, true, false, ROT>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
+  else if (trunk) hipLaunchKernelGGL((wbc_tick_sim3p_kernel<false, true, false, ROT>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
+  else if (warm) hipLaunchKernelGGL((wbc_tick_sim3p_kernel<true, false, false, ROT>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
+  else hipLaunchKernelGGL((wbc_tick_sim3p_kernel<false, false, false, ROT>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
+}
+int launch_tick_sim3p(const KernelArgs& a, void* stream) {
+  if (a.rot) launch_sim3p_variant<true>(a, stream);
+  else launch_sim3p_variant<false>(a, stream);
   return check_launch("tick_sim3p");
 }
 int sim3p_lds_bytes() { return (int)sizeof(SmemP); }

@@ -82,7 +82,9 @@ class Model:
         raise KeyError("frame %r (%s) not in model %s" % (name, kind, self.name))
 
     def joint_id(self, name):
-        return self.joint_names.index(name)
+        """pin.Model.getJointId: a name that is no joint of the model (the Laikago URDF's *fixed* "gripper", which sim3.py still
+        passes as EE_joint_names[4]) gives model.njoints, not an error."""
+        return self.joint_names.index(name) if name in self.joint_names else self.njoints
 
     def neutral(self):
         """pin.neutral(model): zeros with identity quaternion (x, y, z, w) = (0, 0, 0, 1)."""

@@ -49,11 +49,13 @@ def sample_q(model, B, rng):
     legs = legs + rng.normal(0, 0.02, (B, 12))
     lo, hi = model.q_lo[7:19], model.q_hi[7:19]
     q[:, 7:19] = np.clip(legs, lo + 0.03, hi - 0.03)
-    n_arm = nq - 19 - 3                                                   # waist .. last wrist joint
+    grip = "gripper" in model.joint_names                                 # a1 arms: a revolute gripper at nq - 3; Laikago's is fixed
+    n_arm = nq - 19 - (3 if grip else 2)                                  # waist .. last wrist joint
     lo, hi = model.q_lo[19:19 + n_arm], model.q_hi[19:19 + n_arm]
     mid, half = 0.5 * (lo + hi), 0.4 * (hi - lo)
     q[:, 19:19 + n_arm] = mid + half * rng.uniform(-1, 1, (B, n_arm))
-    q[:, nq - 3] = 0.0                                                    # gripper
+    if grip:
+        q[:, nq - 3] = 0.0                                                # gripper
     q[:, nq - 2], q[:, nq - 1] = 0.02, -0.02                              # fingers, as in the mocap log
     return q
 

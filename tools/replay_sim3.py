@@ -37,7 +37,12 @@ MILESTONES = {
                          [0., -0.2, 0.47], [0.07, -0.2, 0.44], [0.22, -0.20, 0.44], [0.32, -0.05, 0.44], [0.32, 0.1, 0.44],
                          [0.22, 0.2, 0.44], [0.07, 0.2, 0.44], [0, 0.2, 0.47], [0, 0.2, 0.52], [0.07, 0.2, 0.55],
                          [0.22, 0.2, 0.55], [0.28, 0.1, 0.55], [0.28, 0, 0.55]],
+    "laikago_vx300": [[0.4, 0., 0.80], [0.4, 0.2, 0.80], [0.25, 0.38, 0.80], [-0.1, 0.38, 0.80], [-0.3, 0.38, 0.75],
+                      [-0.3, 0.38, 0.55], [-0.1, 0.38, 0.5], [0.3, 0.38, 0.5], [0.4, 0.2, 0.5], [0.4, -0.25, 0.5],
+                      [0.3, -0.38, 0.5], [-0.1, -0.38, 0.5], [-0.3, -0.38, 0.55], [-0.3, -0.38, 0.75], [-0.1, -0.38, 0.80],
+                      [0.3, -0.38, 0.80], [0.4, -0.2, 0.80], [0.4, 0, 0.80]],
 }
+FOOT_OFFSET = {"laikago_vx300": False}   # sim3.py:16-22: robot_index 2 runs without the foot-radius offset
 
 
 def build_robot(robot, posture):
@@ -46,7 +51,7 @@ def build_robot(robot, posture):
     from Robot_Wrapper4 import RobotModel
     r = wbc_model.A1_ROLES
     rm = RobotModel("/replay/%s.urdf" % robot, "/unused/meshes", r["EE_frame_names"], r["EE_joint_names"], r["G_base"],
-                    r["imu"], "FR_hip_joint", r["hip_waist_joint_names"], foot_offset=True)
+                    r["imu"], "FR_hip_joint", r["hip_waist_joint_names"], foot_offset=FOOT_OFFSET.get(robot, True))
     rm.setTasks(Grip=True, Joint=posture)
     rm.setConstraints(Trunk=True, FR=True, FL=True, RR=True, RL=True)
     rm.staticReachMode()
