@@ -131,6 +131,23 @@ typedef struct WbcConfig {
   double com_box_scale;        /* 0.8   (Robot_Wrapper4.py:675-677)                               */
 } WbcConfig;
 
+/* ------------------------------------------------------------------ per-instance task weights and gains
+ * The weight / gain block of WbcConfig (ee_W .. joint_w: 85 contiguous doubles, same names, order and meaning, the ee_gain
+ * indexing of Robot_Wrapper4.py:908 included), one row per instance: what a weight / gain sweep or domain randomisation varies.
+ * Passed as `tp` [B] to wbc_tick_tp / wbc_assemble_tp / wbc_rollout_tp, in the same memory kind as the call's other arrays; row b
+ * replaces the block of cfgs[model_id[b]] for instance b only (switches, posture mode, damper tables, box constants and lock_from
+ * stay per model). Rows are read on the device by every call. A row with a non-finite entry or joint_w == 0 (H = A'A singular)
+ * gives its instance WBC_QP_NUMERICAL and zero qdot; the other instances are unaffected. */
+typedef struct WbcTaskParams {
+  double ee_W[WBC_NEE][6];     /* diag(EE_weight[i])                                              */
+  double ee_w[WBC_NEE];        /* cart_task_weight_EE_list[i]                                     */
+  double ee_gain[WBC_NEE][6];  /* diag(EE_gains[i]), indexed by EE index as at Robot_Wrapper4.py:908 */
+  double trunk_W[6], trunk_w, trunk_gain[6];
+  double com_W[3], com_gain[3];
+  double joint_w;              /* joint_task_weight                                               */
+} WbcTaskParams;
+#define WBC_TASK_PARAMS_DOUBLES 85
+
 /* ------------------------------------------------------------------ per-instance tick inputs
  * (the arguments of runWBC plus the controller state it reads). NULL is allowed where noted. */
 typedef struct WbcTickIn {
@@ -307,6 +324,13 @@ typedef struct WbcRollout {
   int32_t pad_;
 } WbcRollout;
 int wbc_rollout(WbcBatch* b, int B, const WbcTickIn* in0, double dt, const WbcRollout* r, int mem, void* stream);
+
+/* per-instance task weights and gains (WbcTaskParams, tp [B]); tp == NULL is exactly the call without the suffix.
+ * wbc_tick_tp: every kernel of wbc_tick takes the rows (the one-instance compact sim3 kernel of option refine = 0 excepted: such a call
+ * runs on the general kernel, statistic "last_path" 0). wbc_rollout_tp: the same rows on every tick, RUNNING and WARMUP alike. */
+int wbc_tick_tp(WbcBatch* b, int B, const WbcTickIn* in, const WbcTaskParams* tp, double dt, int mem, const WbcTickOut* out, void* stream);
+int wbc_assemble_tp(WbcBatch* b, int B, const WbcTickIn* in, const WbcTaskParams* tp, double dt, int mem, const WbcQpData* out, void* stream);
+int wbc_rollout_tp(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r, int mem, void* stream);
 
 /* Knobs of a handle (none of them changes a result beyond rounding; defaults in brackets):
  *   "jtj_mfma"        [-1] H = A'A of wbc_tick / wbc_assemble (QP_Wrapper.py:17) on the fp64 matrix cores (v_mfma_f64_16x16x4_f64)

@@ -911,7 +911,7 @@ static bool boxp_eligible(const WbcBatch* b, const KernelArgs& a) {
   for (int i = 0; i < b->n_models; ++i) if (!b->plan_host[i].x_ok) return false;
   return true;
 }
-static int launch_tick_auto(WbcBatch* b, KernelArgs& a, int B, void* stream) {
+static int launch_tick_auto(WbcBatch* b, KernelArgs& a, int B, void* stream, const WbcTaskParams* tp = nullptr) {
   if (boxp_eligible(b, a)) {    // ONE kernel per tick; last_path 4
     b->last_path = 4;
     b->last_orth = 0;
@@ -926,7 +926,7 @@ static int launch_tick_auto(WbcBatch* b, KernelArgs& a, int B, void* stream) {
     a.defer_stat = b->d_dstat;
     a.tick_seq = ++b->tick_seq;
     if (!b->tick_seq) a.tick_seq = ++b->tick_seq;
-    if (int e = launch_tick_boxp(a, stream)) return fail(WBC_E_HIP, "packed box tick kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    if (int e = launch_tick_boxp(a, stream, tp)) return fail(WBC_E_HIP, "packed box tick kernel launch failed: %s", hipGetErrorString((hipError_t)e));
     return WBC_OK;
   }
   if (orthp_eligible(b, a)) {   // ONE kernel per tick; last_path 3
@@ -943,16 +943,17 @@ static int launch_tick_auto(WbcBatch* b, KernelArgs& a, int B, void* stream) {
     a.defer_stat = b->d_dstat;
     a.tick_seq = ++b->tick_seq;
     if (!b->tick_seq) a.tick_seq = ++b->tick_seq;
-    if (int e = launch_tick_orthp(a, stream, b->plan_host[0].q_ok == 2)) return fail(WBC_E_HIP, "packed orth tick kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    if (int e = launch_tick_orthp(a, stream, b->plan_host[0].q_ok == 2, tp)) return fail(WBC_E_HIP, "packed orth tick kernel launch failed: %s", hipGetErrorString((hipError_t)e));
     return WBC_OK;
   }
   // The one-instance compact kernel (path 1) does not refine: it lives on 168 VGPRs / 13.2 KB LDS (3 waves per SIMD) and has room neither for the
   // task image nor for the Jacobian columns the residual is formed from. With the refinement on (default) what the packed kernel does not take
   // runs on the general kernel, whose structural presolve solves the same reduced problem and refines it (option refine = 0 brings path 1 back).
-  if (!sim3_eligible(b, a) || (b->refine > 0 && !packed_eligible(b, a))) {
+  // per-instance weights (wbc_tick_tp): the one-instance compact kernel has no TP variant — what the packed kernel does not take runs here too
+  if (!sim3_eligible(b, a) || ((b->refine > 0 || tp) && !packed_eligible(b, a))) {
     b->last_path = 0;
     b->last_orth = a.presolve && a.presolve_orth == 2 && !(a.ws_in || a.ws_out);
-    if (int e = launch_tick(a, MODE_TICK, grid_tick(b, B), stream)) return fail(WBC_E_HIP, "tick kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    if (int e = launch_tick(a, MODE_TICK, grid_tick(b, B), stream, tp)) return fail(WBC_E_HIP, "tick kernel launch failed: %s", hipGetErrorString((hipError_t)e));
     return WBC_OK;
   }
   b->last_path = 1;
@@ -982,7 +983,7 @@ static int launch_tick_auto(WbcBatch* b, KernelArgs& a, int B, void* stream) {
     a.packed_trunk = b->cfg_host[0].task_trunk != 0;
     a.tick_seq = ++b->tick_seq;
     if (!b->tick_seq) a.tick_seq = ++b->tick_seq;          // (0 is the cleared word's sequence number)
-    if (int e = launch_tick_sim3p(a, stream)) return fail(WBC_E_HIP, "packed sim3 tick kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    if (int e = launch_tick_sim3p(a, stream, tp)) return fail(WBC_E_HIP, "packed sim3 tick kernel launch failed: %s", hipGetErrorString((hipError_t)e));
     return WBC_OK;
   }
   if (int e = launch_tick_sim3(a, B, stream)) return fail(WBC_E_HIP, "sim3 tick kernel launch failed: %s", hipGetErrorString((hipError_t)e));
@@ -1022,6 +1023,10 @@ extern "C" int wbc_fk_jacobians(WbcBatch* b, int B, const double* q, const int32
 }
 
 extern "C" int wbc_assemble(WbcBatch* b, int B, const WbcTickIn* in, double dt, int mem, const WbcQpData* out, void* stream) {
+  return wbc_assemble_tp(b, B, in, nullptr, dt, mem, out, stream);
+}
+extern "C" int wbc_assemble_tp(WbcBatch* b, int B, const WbcTickIn* in, const WbcTaskParams* tp, double dt, int mem, const WbcQpData* out,
+                               void* stream) {
   int rc = check_batch(b, B, "wbc_assemble", true);
   if (rc) return rc;
   if (!out || !(dt > 0)) return fail(WBC_E_ARG, "wbc_assemble: null output or dt <= 0");
@@ -1032,16 +1037,21 @@ extern "C" int wbc_assemble(WbcBatch* b, int B, const WbcTickIn* in, double dt, 
   a.in = *in; a.qp = *out;
   Stager st{b, mem, (hipStream_t)stream, {}};
   stage_tick_in(st, a.in, B, b);
+  st.in(&tp, (size_t)B);
   const size_t n = (size_t)B, m = b->mrows, p = b->prows, V = WBC_V_STRIDE;
   st.out(&a.qp.A, n * m * V); st.out(&a.qp.b, n * m); st.out(&a.qp.H, n * V * V); st.out(&a.qp.g, n * V);
   st.out(&a.qp.C, n * p * V); st.out(&a.qp.Clb, n * p); st.out(&a.qp.Cub, n * p); st.out(&a.qp.lb, n * V); st.out(&a.qp.ub, n * V);
   if ((rc = st.stage())) return rc;
   if ((rc = auto_posture(b, a, B, stream))) return rc;
-  if (int e = launch_tick(a, MODE_ASSEMBLE, grid_tick(b, B), stream)) return fail(WBC_E_HIP, "assemble kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+  if (int e = launch_tick(a, MODE_ASSEMBLE, grid_tick(b, B), stream, tp)) return fail(WBC_E_HIP, "assemble kernel launch failed: %s", hipGetErrorString((hipError_t)e));
   return st.finish();
 }
 
 extern "C" int wbc_tick(WbcBatch* b, int B, const WbcTickIn* in, double dt, int mem, const WbcTickOut* out, void* stream) {
+  return wbc_tick_tp(b, B, in, nullptr, dt, mem, out, stream);
+}
+extern "C" int wbc_tick_tp(WbcBatch* b, int B, const WbcTickIn* in, const WbcTaskParams* tp, double dt, int mem, const WbcTickOut* out,
+                           void* stream) {
   int rc = check_batch(b, B, "wbc_tick", true);
   if (rc) return rc;
   if (!out || !out->qdot || !(dt > 0)) return fail(WBC_E_ARG, "wbc_tick: qdot output required and dt > 0");
@@ -1052,13 +1062,14 @@ extern "C" int wbc_tick(WbcBatch* b, int B, const WbcTickIn* in, double dt, int 
   a.in = *in; a.out = *out;
   Stager st{b, mem, (hipStream_t)stream, {}};
   stage_tick_in(st, a.in, B, b);
+  st.in(&tp, (size_t)B);
   const size_t n = (size_t)B;
   st.out(&a.out.qdot, n * WBC_V_STRIDE); st.out(&a.out.status, n); st.out(&a.out.iters, n); st.out(&a.out.q_next, n * WBC_Q_STRIDE);
   st.out(&a.out.working_set, n * 2);
   if ((rc = st.stage())) return rc;
   a.ws_in = (const unsigned long long*)a.in.working_set; a.ws_out = (unsigned long long*)a.out.working_set;
   if ((rc = auto_posture(b, a, B, stream))) return rc;
-  if ((rc = launch_tick_auto(b, a, B, stream))) return rc;
+  if ((rc = launch_tick_auto(b, a, B, stream, tp))) return rc;
   return st.finish();
 }
 
@@ -1102,6 +1113,10 @@ extern "C" int wbc_update_state(WbcBatch* b, int B, const double* q_cur, const d
 
 // K closed-loop ticks: the mutable controller state lives in the handle's rollout workspace; in0 is only read.
 extern "C" int wbc_rollout(WbcBatch* b, int B, const WbcTickIn* in0, double dt, const WbcRollout* r, int mem, void* stream) {
+  return wbc_rollout_tp(b, B, in0, nullptr, dt, r, mem, stream);
+}
+extern "C" int wbc_rollout_tp(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r, int mem,
+                              void* stream) {
   int rc = check_batch(b, B, "wbc_rollout", true);
   if (rc) return rc;
   if (!r || r->ticks < 1 || !(dt > 0)) return fail(WBC_E_ARG, "wbc_rollout: ticks >= 1 and dt > 0 required");
@@ -1127,6 +1142,7 @@ extern "C" int wbc_rollout(WbcBatch* b, int B, const WbcTickIn* in0, double dt, 
   WbcRollout ro = *r;
   Stager st{b, mem, s, {}};
   stage_tick_in(st, a.in, B, b);
+  st.in(&tp, n);                         // (every tick reads the same rows)
   st.in(&ro.ee_target_step, n * 15); st.in(&ro.trunk_target_step, n * 3); st.in(&ro.imu, n * 4);
   st.out(&ro.q_final, n * WBC_Q_STRIDE); st.out(&ro.qdot_last, n * WBC_V_STRIDE); st.out(&ro.ee_target_final, n * 15);
   st.out(&ro.grip_trace, (size_t)(r->ticks + r->hold_ticks) * n * 3); st.out(&ro.status_max, n); st.out(&ro.iters_sum, n);
@@ -1169,7 +1185,7 @@ extern "C" int wbc_rollout(WbcBatch* b, int B, const WbcTickIn* in0, double dt, 
     if (k == r->ticks) { u.ee_step = nullptr; u.trunk_step = nullptr; }   // hold phase: the targets stay where they are
     a.in = loop_in;                       // auto_posture fills posture_u / q_con afresh every tick
     if ((rc = auto_posture(b, a, B, stream))) return rc;
-    if ((rc = launch_tick_auto(b, a, B, stream))) return rc;
+    if ((rc = launch_tick_auto(b, a, B, stream, tp))) return rc;
     u.grip_trace = ro.grip_trace ? ro.grip_trace + (size_t)k * n * 3 : nullptr;
     if (int e = launch_update_auto(b, u, B, stream)) return fail(WBC_E_HIP, "update kernel launch failed: %s", hipGetErrorString((hipError_t)e));
   }

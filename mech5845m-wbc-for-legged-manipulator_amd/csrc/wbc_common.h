@@ -1913,6 +1913,34 @@ __device__ __forceinline__ bool contact_presolve_orth(Smem& S, const KA& A, cons
 }
 
 // ------------------------------------------------------------------------------------------------
+// Per-instance task weights and gains (WbcTaskParams, the TP kernels' parameter `tp`): the TP instantiations read the weight / gain block through TPW(field)
+// from the instance's row instead of its model's configuration — same field names, same offsets. A wave-uniform row is read through the
+// constant address space (scalar loads, as the configuration itself).
+// ------------------------------------------------------------------------------------------------
+typedef const __attribute__((address_space(4))) WbcTaskParams* TpRow;
+#define TPW(f) (TP ? (double)(tpr->f) : (double)(cfg.f))
+// A row with a non-finite entry or joint_w == 0 (H = A'A singular): the instance reports WBC_QP_NUMERICAL with zero qdot and is computed with its
+// model's own block meanwhile (nothing non-finite enters the solve). One wave, one row: lanes 0..63 and 64..84 (lane 20: joint_w).
+__device__ __forceinline__ bool tp_row_bad(const WbcTaskParams* row, const int lane) {
+  const double* w = reinterpret_cast<const double*>(row);
+  const double v0 = w[lane], v1 = (lane < WBC_TASK_PARAMS_DOUBLES - 64) ? w[64 + lane] : 1.0;
+  const bool bad = !(fabs(v0) <= 1.7976931348623157e308) || !(fabs(v1) <= 1.7976931348623157e308) || (lane == 20 && v1 == 0.0);
+  return __ballot(bad) != 0ull;
+}
+// ... the same for a 16-lane group (lane s of the group at rbase): six entries per lane, joint_w on s = 4 of the last
+__device__ __forceinline__ bool tp_row_bad16(const WbcTaskParams* row, const int s, const int rbase) {
+  const double* w = reinterpret_cast<const double*>(row);
+  bool bad = false;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    const int i = s + 16 * k;
+    const double v = (i < WBC_TASK_PARAMS_DOUBLES) ? w[i] : 1.0;
+    bad = bad || !(fabs(v) <= 1.7976931348623157e308) || (i == WBC_TASK_PARAMS_DOUBLES - 1 && v == 0.0);
+  }
+  return ((__ballot(bad) >> rbase) & 0xFFFFull) != 0ull;
+}
+
+// ------------------------------------------------------------------------------------------------
 // The orthonormal presolve without the 26-wide H: right after the task pass (At = the Cartesian task stack by DoF in LDS) the contact
 // rows go through orth_qr_z, A Z is formed for the base block (one Cartesian row per lane), and H' = (A Z)'(A Z) + posture comes out of
 // ONE 16 x 16 tile of the fp64 matrix cores (the full J'J is three tiles and was then reduced by Z'(H Z): 0.15 ms of the C2 step).
@@ -1920,10 +1948,10 @@ __device__ __forceinline__ bool contact_presolve_orth(Smem& S, const KA& A, cons
 // constraint stage. Only where the constraints are evaluated at the same state as the tasks (no second FK pass). Returns false —
 // RA zeroed again for the general path — when two contact rows are numerically dependent.
 // ------------------------------------------------------------------------------------------------
-template <class KA>
+template <class KA, bool TP = false>
 __device__ __forceinline__ bool orth_direct_assemble(Smem& S, const KA& A, const DevModel& M, const WbcConfig& cfg,
                                                      const DevPlan& P, const double* const At, const int mtp,
-                                                     const double (&lin)[3], const int lane) {
+                                                     const double (&lin)[3], const int lane, TpRow tpr = nullptr) {
   const int nv = M.nv, nelim = P.nelim, nl = 3 * nelim, n_red = P.n_red, mc = A.mcart;
   constexpr int NB = 18;
   double* const Esc = S.RA;                      // [12][LDJ] contact rows (dead once the QR has loaded them)
@@ -2012,7 +2040,7 @@ __device__ __forceinline__ bool orth_direct_assemble(Smem& S, const KA& A, const
     acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, a0, acc, 0, 0, 0);
   }
   WSYNC();                                       // every read of A Z and of At is done: RA rows < NR become H', RB rows >= NR take Z
-  const double dp = cfg.task_joint ? (1.0 / nv) * cfg.joint_w : 0.0;   // posture rows: Z'(d^2 I)Z = d^2 I on the reduced variables
+  const double dp = cfg.task_joint ? (1.0 / nv) * TPW(joint_w) : 0.0;   // posture rows: Z'(d^2 I)Z = d^2 I on the reduced variables
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int row = kq + 4 * r;
@@ -2027,12 +2055,13 @@ __device__ __forceinline__ bool orth_direct_assemble(Smem& S, const KA& A, const
 
 // ------------------------------------------------------------------------------------------------
 // One instance: FK -> Jacobians -> task stack -> H, g, C, bounds [-> QP -> qdot -> q_next]
-// (inputs already staged in S.in)
+// (inputs already staged in S.in; TP: weights and gains from the row tpr, tp_bad: the row is unusable — see tp_row_bad)
 // ------------------------------------------------------------------------------------------------
-template <int MODE, bool WARM = false, bool ORTH = false, bool ROT = false, class KA = KernelArgs>
+template <int MODE, bool WARM = false, bool ORTH = false, bool ROT = false, bool TP = false, class KA = KernelArgs>
 __device__ __forceinline__ void process_instance(Smem& S, const KA& A, const DevModel& M, const WbcConfig& cfg,
                                                  const DevPlan& P, const LaneConst& lc, const InRegs& inr, const int b,
-                                                 const int lane, const unsigned long long t_entry = 0) {
+                                                 const int lane, const unsigned long long t_entry = 0, TpRow tpr = nullptr,
+                                                 const bool tp_bad = false) {
   const int nv = M.nv, nq = M.nq, nj = M.njoints;
   const double dt = A.dt, inv_dt = 1.0 / A.dt;   // x * (1/dt) for x / dt: one rounding more than the reference's division
   (void)dt;
@@ -2104,8 +2133,8 @@ __device__ __forceinline__ void process_instance(Smem& S, const KA& A, const Dev
   for (unsigned tm = P.task_ee_mask; tm; tm &= tm - 1) {
     const int e = __ffs((int)tm) - 1;
     const unsigned fsup = M.frame_support[WBC_FR_EE0 + e];
-    double w = cfg.ee_w[e], W0 = cfg.ee_W[e][0], W1 = cfg.ee_W[e][1], W2 = cfg.ee_W[e][2], W3 = cfg.ee_W[e][3],
-           W4 = cfg.ee_W[e][4], W5 = cfg.ee_W[e][5], G0 = cfg.ee_gain[e][0], G1 = cfg.ee_gain[e][1], G2 = cfg.ee_gain[e][2];
+    double w = TPW(ee_w[e]), W0 = TPW(ee_W[e][0]), W1 = TPW(ee_W[e][1]), W2 = TPW(ee_W[e][2]), W3 = TPW(ee_W[e][3]),
+           W4 = TPW(ee_W[e][4]), W5 = TPW(ee_W[e][5]), G0 = TPW(ee_gain[e][0]), G1 = TPW(ee_gain[e][1]), G2 = TPW(ee_gain[e][2]);
     asm volatile("" : "+s"(w), "+s"(W0), "+s"(W1), "+s"(W2), "+s"(W3), "+s"(W4), "+s"(W5), "+s"(G0), "+s"(G1), "+s"(G2));
     const double Wd[6] = {W0, W1, W2, W3, W4, W5}, Gd[3] = {G0, G1, G2};
     const bool sup = (lane < nv) && ((fsup >> lane) & 1u);
@@ -2150,14 +2179,14 @@ __device__ __forceinline__ void process_instance(Smem& S, const KA& A, const Dev
     double a[6];
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
-      a[r] = sup ? (cfg.trunk_W[r] * lin[r]) * cfg.trunk_w : 0.0;
-      a[3 + r] = sup ? (cfg.trunk_W[3 + r] * ang[r]) * cfg.trunk_w : 0.0;
+      a[r] = sup ? (TPW(trunk_W[r]) * lin[r]) * TPW(trunk_w) : 0.0;
+      a[3 + r] = sup ? (TPW(trunk_W[3 + r]) * ang[r]) * TPW(trunk_w) : 0.0;
     }
     const double* xt = S.in + IN_TT;
     const double* xp = S.in + IN_TP;
     double vel[6];
 #pragma unroll
-    for (int i = 0; i < 3; ++i) vel[i] = (xt[i] - xp[i]) * inv_dt + cfg.trunk_gain[i] * ((xt[i] - ptr[i]) * inv_dt);
+    for (int i = 0; i < 3; ++i) vel[i] = (xt[i] - xp[i]) * inv_dt + TPW(trunk_gain[i]) * ((xt[i] - ptr[i]) * inv_dt);
     double fq[4], rq[4], Rs[9];
     R_to_quat(Rtr, fq);
     const double* er = S.in + IN_TRE;
@@ -2186,12 +2215,12 @@ __device__ __forceinline__ void process_instance(Smem& S, const KA& A, const Dev
 #pragma unroll
     for (int i = 0; i < 9; ++i) D[i] = (Rs[i] - Ro[i]) * inv_dt;
     // skew = D Rs (R*, not R*^T: :984); omega = (S[2][1], S[0][2], S[1][0]) + K qe
-    vel[3] = (D[6] * Rs[1] + D[7] * Rs[4] + D[8] * Rs[7]) + cfg.trunk_gain[3] * qe0;
-    vel[4] = (D[0] * Rs[2] + D[1] * Rs[5] + D[2] * Rs[8]) + cfg.trunk_gain[4] * qe1;
-    vel[5] = (D[3] * Rs[0] + D[4] * Rs[3] + D[5] * Rs[6]) + cfg.trunk_gain[5] * qe2;
+    vel[3] = (D[6] * Rs[1] + D[7] * Rs[4] + D[8] * Rs[7]) + TPW(trunk_gain[3]) * qe0;
+    vel[4] = (D[0] * Rs[2] + D[1] * Rs[5] + D[2] * Rs[8]) + TPW(trunk_gain[4]) * qe1;
+    vel[5] = (D[3] * Rs[0] + D[4] * Rs[3] + D[5] * Rs[6]) + TPW(trunk_gain[5]) * qe2;
 #pragma unroll
     for (int r = 0; r < 6; ++r) {
-      const double br = vel[r] * cfg.trunk_w;                  // TrunkB (:914-920)
+      const double br = vel[r] * TPW(trunk_w);                  // TrunkB (:914-920)
       g = fma(-a[r], br, g);
       if (lane == 0) S.bt[row + r] = br;
       if (lane < NV) At[lane * mtp + row + r] = a[r];
@@ -2203,8 +2232,8 @@ __device__ __forceinline__ void process_instance(Smem& S, const KA& A, const Dev
     const double* cv = S.in + IN_CV;
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
-      const double ar = cfg.com_W[r] * jc[r];
-      const double br = cv[r] + cfg.com_gain[r] * (ct[r] - com[r]);
+      const double ar = TPW(com_W[r]) * jc[r];
+      const double br = cv[r] + TPW(com_gain[r]) * (ct[r] - com[r]);
       g = fma(-ar, br, g);
       if (lane == 0) S.bt[row + r] = br;
       if (lane < NV) At[lane * mtp + row + r] = ar;
@@ -2222,7 +2251,7 @@ __device__ __forceinline__ void process_instance(Smem& S, const KA& A, const Dev
   // evaluated at this same state, the reduced H' directly (orth_direct_assemble)
   bool direct = false;
   if (ORTH && MODE == MODE_TICK && A.presolve && A.presolve_orth && P.orth && !A.in.q_con && !(A.post_static && P.post_pert))
-    direct = orth_direct_assemble(S, A, M, cfg, P, At, mtp, lin, lane);
+    direct = orth_direct_assemble<KA, TP>(S, A, M, cfg, P, At, mtp, lin, lane, tpr);
   if (direct) {
   } else if (A.jtj_mfma) {
     // dense contraction on the fp64 matrix cores (the operand comes straight from the At image in LDS)
@@ -2242,13 +2271,13 @@ __device__ __forceinline__ void process_instance(Smem& S, const KA& A, const Dev
   // posture rows: qpJointA (Robot_Wrapper4.py:1199-1206), qpJointb (:1209-1268)
   double dpost = 0.0, upost = 0.0;
   if (cfg.task_joint) {
-    dpost = (1.0 / nv) * cfg.joint_w;
+    dpost = (1.0 / nv) * TPW(joint_w);
     if (cfg.task_joint == WBC_JOINT_PREV && lane < nv) upost = qv[lane < 6 ? lane : lane + 1];   // np.delete(q, 6)
     if (cfg.task_joint >= WBC_JOINT_MANI && lane < nv) {               // MANI / HYBRID (:1220-1260)
       if (A.post_static) upost = ((P.post_zero >> lane) & 1u) ? 0.0 : qv[lane < 6 ? lane : lane + 1];   // see DevPlan.post_static
       else upost = inr.pu;                                              // wbc_posture_kernel's u (or the caller's)
     }
-    const double bj = (1.0 / nv) * upost * cfg.joint_w;
+    const double bj = (1.0 / nv) * upost * TPW(joint_w);
     if (lane < nv) g = fma(-dpost, bj, g);
     upost = bj;
   }
@@ -2397,13 +2426,13 @@ __device__ __forceinline__ void process_instance(Smem& S, const KA& A, const Dev
     for (unsigned tm = P.task_ee_mask; tm; tm &= tm - 1) {
       const int e = __ffs((int)tm) - 1;
       const bool sup = (lane < nv) && ((M.frame_support[WBC_FR_EE0 + e] >> lane) & 1u);
-      const double w = cfg.ee_w[e];
+      const double w = TPW(ee_w[e]);
       const double pfe[3] = {S.pft[3 * e], S.pft[3 * e + 1], S.pft[3 * e + 2]};
       double wxp[3];
       cross3(at, pfe, wxp);
 #pragma unroll
       for (int r = 0; r < 6; ++r) {
-        const double a = sup ? cfg.ee_W[e][r] * ((r < 3 ? lt[r < 3 ? r : 0] + wxp[r < 3 ? r : 0] : at[r < 3 ? 0 : r - 3]) * w) : 0.0;
+        const double a = sup ? TPW(ee_W[e][r]) * ((r < 3 ? lt[r < 3 ? r : 0] + wxp[r < 3 ? r : 0] : at[r < 3 ? 0 : r - 3]) * w) : 0.0;
         const double er = S.bt[row_ + r] - wsum(a * xd);
         rr_ = fma(a, er, rr_);
       }
@@ -2413,7 +2442,7 @@ __device__ __forceinline__ void process_instance(Smem& S, const KA& A, const Dev
       const bool sup = (lane < nv) && ((M.frame_support[WBC_FR_TRUNK] >> lane) & 1u);
 #pragma unroll
       for (int r = 0; r < 6; ++r) {
-        const double a = sup ? (cfg.trunk_W[r] * (r < 3 ? lt[r < 3 ? r : 0] : at[r < 3 ? 0 : r - 3])) * cfg.trunk_w : 0.0;
+        const double a = sup ? (TPW(trunk_W[r]) * (r < 3 ? lt[r < 3 ? r : 0] : at[r < 3 ? 0 : r - 3])) * TPW(trunk_w) : 0.0;
         const double er = S.bt[row_ + r] - wsum(a * xd);
         rr_ = fma(a, er, rr_);
       }
@@ -2448,6 +2477,7 @@ __device__ __forceinline__ void process_instance(Smem& S, const KA& A, const Dev
     } else
     res = qp_core<NV, Smem, LDJ, WARM, RFULL>(S, g, lb, ub, clb, cub, nv, A.prows, lane, ts, 0, sb == 3 ? 0 : sb, sr == 3 ? 0 : sr, rfull, n_refine);
   }
+  if (TP && tp_bad) { res.status = WBC_QP_NUMERICAL; res.x = 0.0; res.iters = 0; res.ws_b = 0; res.ws_r = 0; }   // (tp_row_bad)
   if (WARM && A.ws_out) {   // (res.ws_* are in full-problem indexing on every path; an unsolved QP carries nothing)
     const unsigned long long o0 = (__ballot(res.ws_b == 1) & 0xFFFFFFFFull) | (__ballot(res.ws_b == 2) << 32);
     const unsigned long long o1 = (__ballot(res.ws_r == 1) & 0xFFFFFFFFull) | (__ballot(res.ws_r == 2) << 32);
@@ -2497,7 +2527,8 @@ __device__ __forceinline__ void process_instance(Smem& S, const KA& A, const Dev
 // kernel parameter of both callers): handed the caller's own `A`, the general path's ~90 scalars were fetched at kernel entry and kept alive —
 // spilled to VGPR lanes — across the whole packed path: 480 extra v_writelane / v_readlane in the common path, 3 % of the step (same-box A/B,
 // tools/ab_bench.sh). A real call is not an option: arguments arrive in VGPRs, and the general path pins configuration scalars to SGPRs.
-template <bool WARM, bool ORTH, bool ROT = false>
+// TP: the instance's own row of the kernel's `tp` (TpKernarg; wbc_tick_tp), never its model's block.
+template <bool WARM, bool ORTH, bool ROT = false, bool TP = false>
 __device__ __forceinline__ void tail_instance(Smem* Sp, const int bt_v, const DevModel* __restrict__ models, const WbcConfig* __restrict__ cfgs,
                                               const DevPlan* __restrict__ plans) {   // (the kernel's own noalias table pointers: scalar loads)
   Smem& S = *Sp;
@@ -2518,8 +2549,16 @@ __device__ __forceinline__ void tail_instance(Smem* Sp, const int bt_v, const De
   const InRegs cur = load_inputs(A.in, bt_, ln, has2, has3);
   const LaneConst lc = load_lane_const(models[mi], cfgs[mi], ln);
   stage_inputs(S, cur, ln, has2, has3);
-  WSYNC();
-  process_instance<MODE_TICK, WARM, ORTH, ROT>(S, A, models[mi], cfgs[mi], plans[mi], lc, cur, bt_, ln, 0ull);
+  if (TP) {
+    const WbcTaskParams* const tps = ((const __attribute__((address_space(4))) TpKernarg*)Ap)->tp;   // (a TP kernel's fifth parameter)
+    const bool tp_bad = tp_row_bad(tps + bt_, ln);
+    const TpRow tpr = tp_bad ? (TpRow)&cfgs[mi].ee_W[0][0] : (TpRow)(tps + bt_);
+    WSYNC();
+    process_instance<MODE_TICK, WARM, ORTH, ROT, TP>(S, A, models[mi], cfgs[mi], plans[mi], lc, cur, bt_, ln, 0ull, tpr, tp_bad);
+  } else {
+    WSYNC();
+    process_instance<MODE_TICK, WARM, ORTH, ROT>(S, A, models[mi], cfgs[mi], plans[mi], lc, cur, bt_, ln, 0ull);
+  }
   WSYNC();
   asm volatile("; WBC_TAIL_END" ::: "memory");
 }

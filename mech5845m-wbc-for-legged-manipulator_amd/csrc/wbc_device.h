@@ -1,5 +1,6 @@
 // wbc_device.h — host-visible description of what the gfx950 kernels consume (internal, C++).
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 #include "../../include/wbc.h"
 
@@ -139,6 +140,23 @@ struct KernelArgs {
   int32_t rot;                      // a model of the handle has a rotated joint placement: the packed kernels' ROT instantiations run
 };
 
+// The kernel parameters of the TP kernels (wbc_tick_tp & co.): the other kernels' four, then the per-instance rows [B]. KernelArgs keeps its size,
+// so that the kernels without rows keep their code; the packed kernels' tail reads `tp` back through the kernarg segment like KernelArgs itself.
+struct TpKernarg {
+  KernelArgs A;
+  const DevModel* models;
+  const WbcConfig* cfgs;
+  const DevPlan* plans;
+  const WbcTaskParams* tp;
+};
+
+// WbcTaskParams is the weight / gain block of WbcConfig, field for field: a row and &cfg.ee_W[0][0] are read through the same offsets
+#define WBC_TP_SAME_OFFSET(f) static_assert(offsetof(WbcTaskParams, f) == offsetof(WbcConfig, f) - offsetof(WbcConfig, ee_W), #f);
+WBC_TP_SAME_OFFSET(ee_W) WBC_TP_SAME_OFFSET(ee_w) WBC_TP_SAME_OFFSET(ee_gain) WBC_TP_SAME_OFFSET(trunk_W) WBC_TP_SAME_OFFSET(trunk_w)
+WBC_TP_SAME_OFFSET(trunk_gain) WBC_TP_SAME_OFFSET(com_W) WBC_TP_SAME_OFFSET(com_gain) WBC_TP_SAME_OFFSET(joint_w)
+#undef WBC_TP_SAME_OFFSET
+static_assert(sizeof(WbcTaskParams) == WBC_TASK_PARAMS_DOUBLES * sizeof(double), "85 doubles, no padding");
+
 struct QpArgs {
   int32_t B, n, p, m;               // m > 0: least-squares form (A, b given)
   int32_t dbg_stop;                 // diagnostic (ablation build): the packed QP kernel returns after stage dbg_stop - 400 (0 = the whole solve)
@@ -190,11 +208,11 @@ struct UpdateArgs {
 };
 
 // launchers (one per kernel family, wbc_k_*.hip): single-wave workgroups; tick kernels take grid = B, the QP / integrate kernels min(B, resident waves)
-int launch_tick(const KernelArgs& a, int mode, int grid, void* stream);
+int launch_tick(const KernelArgs& a, int mode, int grid, void* stream, const WbcTaskParams* tp = nullptr);
 int launch_tick_sim3(const KernelArgs& a, int grid, void* stream);
-int launch_tick_sim3p(const KernelArgs& a, void* stream);      // packed: four instances per wavefront, grid = ceil(B / 4)
-int launch_tick_boxp(const KernelArgs& a, void* stream);       // packed box kernel (task problems without constraint rows), grid = ceil(B / 4)
-int launch_tick_orthp(const KernelArgs& a, void* stream, int ineq);      // packed orth kernel (equality-only task problems), grid = ceil(B / 4)
+int launch_tick_sim3p(const KernelArgs& a, void* stream, const WbcTaskParams* tp = nullptr);      // packed: four instances per wavefront, grid = ceil(B / 4)
+int launch_tick_boxp(const KernelArgs& a, void* stream, const WbcTaskParams* tp = nullptr);       // packed box kernel (task problems without constraint rows), grid = ceil(B / 4)
+int launch_tick_orthp(const KernelArgs& a, void* stream, int ineq, const WbcTaskParams* tp = nullptr);      // packed orth kernel (equality-only task problems), grid = ceil(B / 4)
 int orthp_lds_bytes();
 int sim3p_lds_bytes();
 int launch_tick_deferred(const KernelArgs& a, void* stream);   // general path for the instances the sim3 kernel deferred

@@ -1,4 +1,5 @@
 // wbc_k_boxp.hip — the packed box kernel wbc_tick_boxp_kernel<WARM>: task problems without constraint rows (the warm-up problem), four instances per wavefront.
+#ifndef WBC_KPASS
 #include "wbc_packed.h"
 
 namespace wbc {
@@ -47,9 +48,24 @@ struct XIntegrate { const double* in; const double* xv; };   // what integrate_f
 #endif
 // WARM: the variant that takes / returns working sets (KernelArgs.ws_in / ws_out, word 0: velocity bounds by DoF) — the packed sim3 kernel's scheme
 // (seeds through the add step, x / u rebuilt from the factors, restoration) on the kept variables; eliminated and locked DoF carry no seed.
-template <bool WARM, bool ROT = false>   // ROT: rotated joint placements in the batch (wbc_k_sim3p.hip)
+#endif
+#ifdef WBC_KPASS
+// ROT: rotated joint placements in the batch (wbc_k_sim3p.hip). TP: per-instance weights and gains (wbc_tick_tp: the kernel's fifth parameter
+// tps [B]) staged into wt in place of the configuration's block; a row with a non-finite entry or joint_w == 0 gives its instance
+// WBC_QP_NUMERICAL. The text below is compiled twice, as wbc_k_sim3p.hip's kernel is: wbc_tick_boxp_kernel (no rows, its code as before)
+// and wbc_tick_boxp_tp_kernel.
+template <bool WARM, bool ROT = false>
+#if WBC_KPASS == 1
 __global__ void __launch_bounds__(64, 2) wbc_tick_boxp_kernel(const KernelArgs A, const DevModel* __restrict__ models,
                                                               const WbcConfig* __restrict__ cfgs, const DevPlan* __restrict__ plans) {
+  constexpr bool TP = false;
+  const WbcTaskParams* const tps = nullptr;
+#else
+__global__ void __launch_bounds__(64, 2) wbc_tick_boxp_tp_kernel(const KernelArgs A, const DevModel* __restrict__ models,
+                                                                 const WbcConfig* __restrict__ cfgs, const DevPlan* __restrict__ plans,
+                                                                 const WbcTaskParams* __restrict__ tps) {
+  constexpr bool TP = true;
+#endif
   __shared__ union { XInst Q[4]; Smem G; } SU;
   const int lane = threadIdx.x, r = lane >> 4, s = lane & 15, rbase = lane & 48;
   XInst& I = SU.Q[r];
@@ -61,6 +77,7 @@ __global__ void __launch_bounds__(64, 2) wbc_tick_boxp_kernel(const KernelArgs A
   const DevModel& M = models[mid];
   const WbcConfig& cfg = cfgs[mid];
   const DevPlan& P = plans[mid];
+  bool tpbad = false;                     // TP: the instance's row is refused
   const double dt = A.dt, inv_dt = 1.0 / A.dt;
   double* const et = I.R;                    // ee_target [5][3]
   double* const ep = I.R + 15;               // prev_ee_target [5][3]
@@ -102,9 +119,24 @@ __global__ void __launch_bounds__(64, 2) wbc_tick_boxp_kernel(const KernelArgs A
       }
       ow[s] = om;
     }
-    const double* cw = &cfg.ee_W[0][0];
+    const double* cw = TP ? reinterpret_cast<const double*>(tps + b) : &cfg.ee_W[0][0];
 #pragma unroll
     for (int i = 0; i < 6; ++i) wt[s + 16 * i] = (s + 16 * i < 85) ? cw[s + 16 * i] : 0.0;
+    if (TP) {                             // the row refused (tp_row_bad16's rule): computed with the configuration's block, reported WBC_QP_NUMERICAL
+      bool bad = false;
+#pragma unroll
+      for (int i = 0; i < 6; ++i) {
+        const int k = s + 16 * i;
+        const double v = wt[k];
+        bad = bad || (k < WBC_TASK_PARAMS_DOUBLES && (!(fabs(v) <= 1.7976931348623157e308) || (k == WBC_TASK_PARAMS_DOUBLES - 1 && v == 0.0)));
+      }
+      tpbad = ((__ballot(bad) >> rbase) & 0xFFFFull) != 0ull;
+      if (tpbad) {
+        const double* fw = &cfg.ee_W[0][0];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) wt[s + 16 * i] = (s + 16 * i < 85) ? fw[s + 16 * i] : 0.0;
+      }
+    }
   }
   const int nv = M.nv, nq = M.nq, nk = P.x_nk, ne = P.x_ne;
   const DevPlan::QDof D0 = P.q_dof[s], D1 = P.q_dof[16 + s];
@@ -772,6 +804,7 @@ __global__ void __launch_bounds__(64, 2) wbc_tick_boxp_kernel(const KernelArgs A
     const unsigned long long bad = __ballot(s < ne && !(fabs(xe) <= 1.7976931348623157e308));
     if ((bad >> rbase) & 0xFFFFull) status = WBC_QP_NUMERICAL;
   }
+  if (TP && tpbad) status = WBC_QP_NUMERICAL;
   bool flagged = false;
   {
     const bool out = (s < ne) && ((elb > -QP_INF && xe - elb < -1e-9 * fmax(1.0, fabs(elb))) || (eub < QP_INF && eub - xe < -1e-9 * fmax(1.0, fabs(eub))));
@@ -835,10 +868,18 @@ __global__ void __launch_bounds__(64, 2) wbc_tick_boxp_kernel(const KernelArgs A
 #pragma unroll 1
     for (int rr = 0; rr < 4; ++rr) {
       if (!((tailm >> (16 * rr)) & 1ull)) continue;
-      tail_instance<WARM, false, ROT>(&SU.G, 4 * (int)blockIdx.x + rr, models, cfgs, plans);
+      tail_instance<WARM, false, ROT, TP>(&SU.G, 4 * (int)blockIdx.x + rr, models, cfgs, plans);
     }
   }
 }
+#else
+// the two kernels from the text above: wbc_tick_boxp_kernel (no rows, the code it always had) and wbc_tick_boxp_tp_kernel (TP)
+#define WBC_KPASS 1
+#include "wbc_k_boxp.hip"
+#undef WBC_KPASS
+#define WBC_KPASS 2
+#include "wbc_k_boxp.hip"
+#undef WBC_KPASS
 
 // One translation unit per PART (csrc/Makefile compiles this file once per part, in parallel): each part instantiates some of the kernel's
 // variants; part 0 also holds the launcher and sees the other parts' variants as explicit-instantiation declarations.
@@ -862,10 +903,37 @@ KINST(true, true)
 KDECL(false, true)
 KDECL(true, true)
 #endif
+#define TINST(...) template __global__ void wbc_tick_boxp_tp_kernel<__VA_ARGS__>(const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__, const WbcTaskParams* __restrict__);
+#define TDECL(...) extern template __global__ void wbc_tick_boxp_tp_kernel<__VA_ARGS__>(const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__, const WbcTaskParams* __restrict__);
+// the TP kernels: a part of their own (the parts above keep their code objects)
+#if BOXP_PART == 3 || BOXP_PART == -1
+TINST(false)
+TINST(true)
+TINST(false, true)
+TINST(true, true)
+#elif BOXP_PART == 0
+TDECL(false)
+TDECL(true)
+TDECL(false, true)
+TDECL(true, true)
+#endif
 #undef KINST
 #undef KDECL
+#undef TINST
+#undef TDECL
 #if BOXP_PART <= 0
-int launch_tick_boxp(const KernelArgs& a, void* stream) {
+static int launch_tick_boxp_tp(const KernelArgs& a, void* stream, const WbcTaskParams* tp) {
+  const dim3 grid((a.B + 3) / 4);
+  const bool warm = a.ws_in || a.ws_out;
+  if (a.rot) {
+    if (warm) hipLaunchKernelGGL((wbc_tick_boxp_tp_kernel<true, true>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
+    else hipLaunchKernelGGL((wbc_tick_boxp_tp_kernel<false, true>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
+  } else if (warm) hipLaunchKernelGGL(wbc_tick_boxp_tp_kernel<true>, grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
+  else hipLaunchKernelGGL(wbc_tick_boxp_tp_kernel<false>, grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
+  return check_launch("tick_boxp_tp");
+}
+int launch_tick_boxp(const KernelArgs& a, void* stream, const WbcTaskParams* tp) {
+  if (tp) return launch_tick_boxp_tp(a, stream, tp);
   if (a.rot) {
     if (a.ws_in || a.ws_out) hipLaunchKernelGGL((wbc_tick_boxp_kernel<true, true>), dim3((a.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
     else hipLaunchKernelGGL((wbc_tick_boxp_kernel<false, true>), dim3((a.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
@@ -878,3 +946,4 @@ int launch_tick_boxp(const KernelArgs& a, void* stream) {
 #endif
 
 }  // namespace wbc
+#endif

@@ -1,4 +1,5 @@
 // wbc_k_orthp.hip — the packed orth kernel wbc_tick_orthp_kernel<INEQ, WARM>: task problems whose tasks touch the stance legs, four instances per wavefront.
+#ifndef WBC_KPASS
 #include "wbc_packed.h"
 
 namespace wbc {
@@ -46,9 +47,24 @@ static_assert(offsetof(QInst, xv) - offsetof(QInst, cl) == 80 * sizeof(double), 
 // the tail with the flagged ones.
 // WARM (INEQ only): working sets in and out — the packed sim3 kernel's scheme (seeds through the add step, x / u rebuilt from the factors, restoration).
 // In FULL-problem indexing a row of Z is the velocity bound of its DoF (word 0), the trunk / CoM box rows are findConstraints' rows (word 1).
-template <bool INEQ, bool WARM = false, bool ROT = false>   // ROT: rotated joint placements in the batch (wbc_k_sim3p.hip)
+#endif
+#ifdef WBC_KPASS
+// ROT: rotated joint placements in the batch (wbc_k_sim3p.hip). TP: per-instance weights and gains (wbc_tick_tp: the kernel's fifth parameter
+// tps [B]) staged into wt in place of the configuration's block; a row with a non-finite entry or joint_w == 0 gives its instance
+// WBC_QP_NUMERICAL. The text below is compiled twice, as wbc_k_sim3p.hip's kernel is: wbc_tick_orthp_kernel (no rows, its code as before)
+// and wbc_tick_orthp_tp_kernel.
+template <bool INEQ, bool WARM = false, bool ROT = false>
+#if WBC_KPASS == 1
 __global__ void __launch_bounds__(64, 2) wbc_tick_orthp_kernel(const KernelArgs A, const DevModel* __restrict__ models,
                                                                const WbcConfig* __restrict__ cfgs, const DevPlan* __restrict__ plans) {
+  constexpr bool TP = false;
+  const WbcTaskParams* const tps = nullptr;
+#else
+__global__ void __launch_bounds__(64, 2) wbc_tick_orthp_tp_kernel(const KernelArgs A, const DevModel* __restrict__ models,
+                                                                  const WbcConfig* __restrict__ cfgs, const DevPlan* __restrict__ plans,
+                                                                  const WbcTaskParams* __restrict__ tps) {
+  constexpr bool TP = true;
+#endif
   __shared__ union { QInst Q[4]; Smem G; } SU;
   const int lane = threadIdx.x, r = lane >> 4, s = lane & 15, rbase = lane & 48;
   QInst& I = SU.Q[r];
@@ -63,6 +79,7 @@ __global__ void __launch_bounds__(64, 2) wbc_tick_orthp_kernel(const KernelArgs 
   const double dt = A.dt, inv_dt = 1.0 / A.dt;
   const unsigned long long ws_mine = (INEQ && WARM && s < 2 && A.ws_in && valid) ? A.ws_in[2 * (size_t)b + s] : 0ull;   // (lane 0: bounds, lane 1: rows)
   unsigned long long ws_o0 = 0ull, ws_o1 = 0ull;
+  bool tpbad = false;                     // TP: the instance's row is refused
   // ---- loads: inputs (coalesced per instance), then the per-lane records
   {
     const double* qg = A.in.q + (size_t)b * NQ;
@@ -91,8 +108,25 @@ __global__ void __launch_bounds__(64, 2) wbc_tick_orthp_kernel(const KernelArgs 
     }
     // the configuration's weights and gains: 85 contiguous doubles of WbcConfig, six per lane, parked in wt (= cl | yv | zv | xv)
     const double* cw = &cfg.ee_W[0][0];
+    if (TP) {                             // the instance's row for entries 0..84 (the box constants @85..88 stay the configuration's)
+      const double* rw = reinterpret_cast<const double*>(tps + b);
+      bool bad = false;
+#pragma unroll
+      for (int i = 0; i < 6; ++i) {
+        const int k = s + 16 * i;
+        const double v = (k < WBC_TASK_PARAMS_DOUBLES) ? rw[k] : ((k < 89) ? cw[k] : 0.0);
+        bad = bad || (k < WBC_TASK_PARAMS_DOUBLES && (!(fabs(v) <= 1.7976931348623157e308) || (k == WBC_TASK_PARAMS_DOUBLES - 1 && v == 0.0)));
+        I.cl[s + 16 * i] = v;
+      }
+      tpbad = ((__ballot(bad) >> rbase) & 0xFFFFull) != 0ull;
+      if (tpbad) {                        // (tp_row_bad16's rule) computed with the configuration's block, reported WBC_QP_NUMERICAL
+#pragma unroll
+        for (int i = 0; i < 6; ++i) I.cl[s + 16 * i] = (s + 16 * i < 89) ? cw[s + 16 * i] : 0.0;
+      }
+    } else {
 #pragma unroll
     for (int i = 0; i < 6; ++i) I.cl[s + 16 * i] = (s + 16 * i < 89) ? cw[s + 16 * i] : 0.0;     // (+ trunk_box_z_frac, _ang, _scale, com_box_scale @85..88)
+    }
     if (INEQ) {
       const bool c_tr = cfg.task_trunk != 0;
       double t0 = 0.0, t1 = 0.0;
@@ -1013,6 +1047,7 @@ __global__ void __launch_bounds__(64, 2) wbc_tick_orthp_kernel(const KernelArgs 
       const unsigned long long om = __ballot(valid && overflow);
       if ((om >> rbase) & 0xFFFFull) { defer = true; live = false; }
     }
+    if (TP && tpbad) status = WBC_QP_NUMERICAL;
     if (WARM && A.ws_out) {   // the final working set in FULL-problem indexing; an unsolved QP carries nothing
       const int cc = a_code & 255, sd = (a_code >> 8) & 1;
       const int rr = cc >= 32 ? cc - 32 : 0;
@@ -1031,6 +1066,7 @@ __global__ void __launch_bounds__(64, 2) wbc_tick_orthp_kernel(const KernelArgs 
     const unsigned long long bad = __ballot(s < n && !(fabs(x) <= 1.7976931348623157e308));
     if ((bad >> rbase) & 0xFFFFull) status = WBC_QP_NUMERICAL;
   }
+  if (TP && tpbad) status = WBC_QP_NUMERICAL;
   if (status != WBC_QP_OPTIMAL) x = 0.0;
   // ---- qd = Z y by DoF, outputs
   I.xv[s] = x;
@@ -1097,11 +1133,20 @@ __global__ void __launch_bounds__(64, 2) wbc_tick_orthp_kernel(const KernelArgs 
 #pragma unroll 1
     for (int rr = 0; rr < 4; ++rr) {
       if (!((tailm >> (16 * rr)) & 1ull)) continue;
-      if (INEQ && WARM) tail_instance<true, false, ROT>(&SU.G, 4 * (int)blockIdx.x + rr, models, cfgs, plans);     // (the general kernel's warm path: full-size solve)
-      else tail_instance<false, true, ROT>(&SU.G, 4 * (int)blockIdx.x + rr, models, cfgs, plans);
+      if (INEQ && WARM) tail_instance<true, false, ROT, TP>(&SU.G, 4 * (int)blockIdx.x + rr, models, cfgs, plans);     // (the general kernel's warm path: full-size solve)
+      else tail_instance<false, true, ROT, TP>(&SU.G, 4 * (int)blockIdx.x + rr, models, cfgs, plans);
     }
   }
 }
+
+#else
+// the two kernels from the text above: wbc_tick_orthp_kernel (no rows, the code it always had) and wbc_tick_orthp_tp_kernel (TP)
+#define WBC_KPASS 1
+#include "wbc_k_orthp.hip"
+#undef WBC_KPASS
+#define WBC_KPASS 2
+#include "wbc_k_orthp.hip"
+#undef WBC_KPASS
 
 // One translation unit per PART (csrc/Makefile compiles this file once per part, in parallel): each part instantiates some of the kernel's
 // variants; part 0 also holds the launcher and sees the other parts' variants as explicit-instantiation declarations.
@@ -1132,10 +1177,47 @@ KDECL(false, false, true)
 KDECL(true, false, true)
 KDECL(true, true, true)
 #endif
+#define TINST(...) template __global__ void wbc_tick_orthp_tp_kernel<__VA_ARGS__>(const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__, const WbcTaskParams* __restrict__);
+#define TDECL(...) extern template __global__ void wbc_tick_orthp_tp_kernel<__VA_ARGS__>(const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__, const WbcTaskParams* __restrict__);
+// the TP kernels: parts of their own (the parts above keep their code objects)
+#if ORTHP_PART == 4 || ORTHP_PART == -1
+TINST(false)
+TINST(true)
+TINST(true, true)
+#elif ORTHP_PART == 0
+TDECL(false)
+TDECL(true)
+TDECL(true, true)
+#endif
+#if ORTHP_PART == 5 || ORTHP_PART == -1
+TINST(false, false, true)
+TINST(true, false, true)
+TINST(true, true, true)
+#elif ORTHP_PART == 0
+TDECL(false, false, true)
+TDECL(true, false, true)
+TDECL(true, true, true)
+#endif
 #undef KINST
 #undef KDECL
+#undef TINST
+#undef TDECL
 #if ORTHP_PART <= 0
-int launch_tick_orthp(const KernelArgs& a, void* stream, int ineq) {
+static int launch_tick_orthp_tp(const KernelArgs& a, void* stream, int ineq, const WbcTaskParams* tp) {
+  const dim3 grid((a.B + 3) / 4);
+  hipStream_t s = (hipStream_t)stream;
+  const bool warm = ineq && (a.ws_in || a.ws_out);
+  if (a.rot) {
+    if (warm) hipLaunchKernelGGL((wbc_tick_orthp_tp_kernel<true, true, true>), grid, dim3(64), 0, s, a, a.models, a.cfgs, a.plans, tp);
+    else if (ineq) hipLaunchKernelGGL((wbc_tick_orthp_tp_kernel<true, false, true>), grid, dim3(64), 0, s, a, a.models, a.cfgs, a.plans, tp);
+    else hipLaunchKernelGGL((wbc_tick_orthp_tp_kernel<false, false, true>), grid, dim3(64), 0, s, a, a.models, a.cfgs, a.plans, tp);
+  } else if (warm) hipLaunchKernelGGL((wbc_tick_orthp_tp_kernel<true, true>), grid, dim3(64), 0, s, a, a.models, a.cfgs, a.plans, tp);
+  else if (ineq) hipLaunchKernelGGL(wbc_tick_orthp_tp_kernel<true>, grid, dim3(64), 0, s, a, a.models, a.cfgs, a.plans, tp);
+  else hipLaunchKernelGGL(wbc_tick_orthp_tp_kernel<false>, grid, dim3(64), 0, s, a, a.models, a.cfgs, a.plans, tp);
+  return check_launch("tick_orthp_tp");
+}
+int launch_tick_orthp(const KernelArgs& a, void* stream, int ineq, const WbcTaskParams* tp) {
+  if (tp) return launch_tick_orthp_tp(a, stream, ineq, tp);
   if (a.rot) {
     if (ineq && (a.ws_in || a.ws_out)) hipLaunchKernelGGL((wbc_tick_orthp_kernel<true, true, true>), dim3((a.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
     else if (ineq) hipLaunchKernelGGL((wbc_tick_orthp_kernel<true, false, true>), dim3((a.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
@@ -1151,3 +1233,4 @@ int orthp_lds_bytes() { return (int)(4 * sizeof(QInst)); }
 #endif
 
 }  // namespace wbc
+#endif

@@ -1,4 +1,5 @@
 // wbc_k_sim3p.hip — the packed sim3 kernel wbc_tick_sim3p_kernel<WARM, TRUNK, QCON>: the benchmark path, four instances per wavefront.
+#ifndef WBC_KPASS
 #include "wbc_packed.h"
 
 namespace wbc {
@@ -25,12 +26,28 @@ namespace wbc {
 #endif
 // ROT: the batch holds a model with a rotated joint placement (DevModel.rot_mask): its FK records with `rot` go through fk_place_rot_lds.
 // The instantiations without it compile to exactly the code they had before the flag existed.
+#endif
+#ifdef WBC_KPASS
+// TP: per-instance weights and gains (wbc_tick_tp: the kernel's fifth parameter tps [B]): each group reads its instance's row in place of
+// cfgs[mid]'s block and the tail hands the row on; a row that tp_row_bad16 refuses gives its instance WBC_QP_NUMERICAL. The text below is
+// compiled twice (this file includes itself with WBC_KPASS = 1, 2): wbc_tick_sim3p_kernel without rows — its name and its code exactly as
+// before, TP constant false — and wbc_tick_sim3p_tp_kernel. (A template flag would rename the existing kernels; a shared inlined body
+// changed their register allocation.)
 template <bool WARM, bool TRUNK = false, bool QCON = false, bool ROT = false>
 #ifdef SIM3P_NUM_VGPR
 __attribute__((amdgpu_waves_per_eu(SIM3P_NUM_VGPR, SIM3P_NUM_VGPR)))
 #endif
+#if WBC_KPASS == 1
 __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const KernelArgs A, const DevModel* __restrict__ models,
                                                                const WbcConfig* __restrict__ cfgs, const DevPlan* __restrict__ plans) {
+  constexpr bool TP = false;
+  const WbcTaskParams* const tps = nullptr;
+#else
+__global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_tp_kernel(const KernelArgs A, const DevModel* __restrict__ models,
+                                                                  const WbcConfig* __restrict__ cfgs, const DevPlan* __restrict__ plans,
+                                                                  const WbcTaskParams* __restrict__ tps) {
+  constexpr bool TP = true;
+#endif
   // (the general kernel's layout shares the allocation: an instance this kernel cannot reduce — a stance-leg block of rank < 2 — is
   //  redone on the general path by the SAME wave at the end, see the tail; both layouts leave 8 waves per CU)
 #ifdef SIM3P_NUM_VGPR      // (compile-only experiment: with the LDS size unknown to the compiler the occupancy attribute alone decides the register budget)
@@ -59,6 +76,12 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
   const WbcConfig& cfg = cfgs[mid];
   const DevPlan& P = plans[mid];
   const double dt = A.dt, inv_dt = 1.0 / A.dt;
+  const WbcTaskParams* tpr = nullptr;       // TP: the row the weights and gains come from (a refused row: the model's own block)
+  bool tpbad = false;
+  if (TP) {
+    tpbad = tp_row_bad16(tps + b, s, rbase);
+    tpr = tpbad ? reinterpret_cast<const WbcTaskParams*>(&cfg.ee_W[0][0]) : tps + b;
+  }
 
   // ---- loads: inputs (coalesced per instance), then the per-lane tables
   {
@@ -79,7 +102,7 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
              : (k < 9) ? A.in.trunk_ref_euler[(size_t)b * 3 + (k - 6)] : A.in.trunk_prev_rot[(size_t)b * 9 + (k - 9)];
       };
       const double t0 = tin(s), t1 = (s < 2) ? tin(16 + s) : 0.0;
-      const double tw = (s < 13) ? (&cfg.trunk_W[0])[s] : 0.0;
+      const double tw = (s < 13) ? (TP ? (&tpr->trunk_W[0])[s] : (&cfg.trunk_W[0])[s]) : 0.0;
       V.tv[s] = t0;
       if (s < 2) V.xv[s] = t1;
       if (s < 13) V.xv[2 + s] = tw;
@@ -196,13 +219,13 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
   const int gj = M.frame_joint[WBC_FR_EE0 + 4];
   const double gp0 = M.frame_p[WBC_FR_EE0 + 4][0], gp1 = M.frame_p[WBC_FR_EE0 + 4][1], gp2 = M.frame_p[WBC_FR_EE0 + 4][2];
   const unsigned gsup = P.redsup[WBC_FR_EE0 + 4];
-  const double ee_w = cfg.ee_w[4];
+  const double ee_w = TPW(ee_w[4]);
   double eW[6], eG[3];
 #pragma unroll
-  for (int i = 0; i < 6; ++i) eW[i] = cfg.ee_W[4][i];
+  for (int i = 0; i < 6; ++i) eW[i] = TPW(ee_W[4][i]);
 #pragma unroll
-  for (int i = 0; i < 3; ++i) eG[i] = cfg.ee_gain[4][i];
-  const double joint_w = cfg.joint_w, tb_z = cfg.trunk_box_z_frac, tb_a = cfg.trunk_box_ang, tb_s = cfg.trunk_box_scale;
+  for (int i = 0; i < 3; ++i) eG[i] = TPW(ee_gain[4][i]);
+  const double joint_w = TPW(joint_w), tb_z = cfg.trunk_box_z_frac, tb_a = cfg.trunk_box_ang, tb_s = cfg.trunk_box_scale;
   WSYNC();
   const double* const qv = V.in;
   PSTOP(6, qv[s] + dlo0 + dlo1 + eW[0] + (double)(fkn.joint + scq0 + scq1));
@@ -1231,6 +1254,7 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
     const unsigned long long bad = __ballot(has_b && !(fabs(x) <= 1.7976931348623157e308));
     if ((bad >> rbase) & 0xFFFFull) status = WBC_QP_NUMERICAL;
   }
+  if (TP && tpbad) status = WBC_QP_NUMERICAL;
   if (status != WBC_QP_OPTIMAL) x = 0.0;
   if (WARM && A.ws_out) {   // the final working set in FULL-problem indexing (KernelArgs.ws_in); an unsolved QP carries nothing
     const int cc = a_code & 255, sd = (a_code >> 8) & 1;
@@ -1297,11 +1321,20 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
 #pragma unroll 1
     for (int rr = 0; rr < 4; ++rr) {
       if (!((tailm >> (16 * rr)) & 1ull)) continue;
-      tail_instance<WARM, false, ROT>(&SU.G, 4 * grp + rr, models, cfgs, plans);
+      tail_instance<WARM, false, ROT, TP>(&SU.G, 4 * grp + rr, models, cfgs, plans);
     }
   }
 #endif
 }
+
+#else
+// the two kernels from the text above: wbc_tick_sim3p_kernel (no rows, the code it always had) and wbc_tick_sim3p_tp_kernel (TP)
+#define WBC_KPASS 1
+#include "wbc_k_sim3p.hip"
+#undef WBC_KPASS
+#define WBC_KPASS 2
+#include "wbc_k_sim3p.hip"
+#undef WBC_KPASS
 
 // One translation unit per PART (csrc/Makefile compiles this file once per part, in parallel): each part instantiates some of the kernel's
 // variants; part 0 also holds the launcher and sees the other parts' variants as explicit-instantiation declarations.
@@ -1347,11 +1380,64 @@ KINST(true, false, true, true)
 KDECL(false, false, true, true)
 KDECL(true, false, true, true)
 #endif
+#define TINST(...) template __global__ void wbc_tick_sim3p_tp_kernel<__VA_ARGS__>(const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__, const WbcTaskParams* __restrict__);
+#define TDECL(...) extern template __global__ void wbc_tick_sim3p_tp_kernel<__VA_ARGS__>(const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__, const WbcTaskParams* __restrict__);
+// the TP kernels: parts of their own (the parts above keep their code objects)
+#if SIM3P_PART == 5 || SIM3P_PART == -1
+TINST(false, false)
+TINST(true, false)
+TINST(false, true)
+#elif SIM3P_PART == 0
+TDECL(false, false)
+TDECL(true, false)
+TDECL(false, true)
+#endif
+#if SIM3P_PART == 6 || SIM3P_PART == -1
+TINST(true, true)
+TINST(false, false, true)
+TINST(true, false, true)
+#elif SIM3P_PART == 0
+TDECL(true, true)
+TDECL(false, false, true)
+TDECL(true, false, true)
+#endif
+#if SIM3P_PART == 7 || SIM3P_PART == -1
+TINST(false, false, false, true)
+TINST(true, false, false, true)
+TINST(false, true, false, true)
+#elif SIM3P_PART == 0
+TDECL(false, false, false, true)
+TDECL(true, false, false, true)
+TDECL(false, true, false, true)
+#endif
+#if SIM3P_PART == 8 || SIM3P_PART == -1
+TINST(true, true, false, true)
+TINST(false, false, true, true)
+TINST(true, false, true, true)
+#elif SIM3P_PART == 0
+TDECL(true, true, false, true)
+TDECL(false, false, true, true)
+TDECL(true, false, true, true)
+#endif
 #undef KINST
 #undef KDECL
+#undef TINST
+#undef TDECL
 #if SIM3P_PART <= 0
 template <bool ROT>
-static void launch_sim3p_variant(const KernelArgs& a, void* stream) {
+static void launch_sim3p_tp_variant(const KernelArgs& a, void* stream, const WbcTaskParams* tp) {
+  const bool warm = a.ws_in || a.ws_out, trunk = a.in.trunk_target && a.packed_trunk, qcon = a.in.q_con || a.in.posture_u;
+  const dim3 grid((a.B + 3) / 4);
+  if (qcon && warm) hipLaunchKernelGGL((wbc_tick_sim3p_tp_kernel<true, false, true, ROT>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
+  else if (qcon) hipLaunchKernelGGL((wbc_tick_sim3p_tp_kernel<false, false, true, ROT>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
+  else if (warm && trunk) hipLaunchKernelGGL((wbc_tick_sim3p_tp_kernel<true, true, false, ROT>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
+  else if (trunk) hipLaunchKernelGGL((wbc_tick_sim3p_tp_kernel<false, true, false, ROT>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
+  else if (warm) hipLaunchKernelGGL((wbc_tick_sim3p_tp_kernel<true, false, false, ROT>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
+  else hipLaunchKernelGGL((wbc_tick_sim3p_tp_kernel<false, false, false, ROT>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
+}
+template <bool ROT>
+static void launch_sim3p_variant(const KernelArgs& a, void* stream, const WbcTaskParams* tp) {
+  if (tp) { launch_sim3p_tp_variant<ROT>(a, stream, tp); return; }
   const bool warm = a.ws_in || a.ws_out, trunk = a.in.trunk_target && a.packed_trunk, qcon = a.in.q_con || a.in.posture_u;
   const dim3 grid((a.B + 3) / 4);
   if (qcon && warm) hipLaunchKernelGGL((wbc_tick_sim3p_kernel<true, false, true, ROT>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
@@ -1361,12 +1447,13 @@ static void launch_sim3p_variant(const KernelArgs& a, void* stream) {
   else if (warm) hipLaunchKernelGGL((wbc_tick_sim3p_kernel<true, false, false, ROT>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
   else hipLaunchKernelGGL((wbc_tick_sim3p_kernel<false, false, false, ROT>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
 }
-int launch_tick_sim3p(const KernelArgs& a, void* stream) {
-  if (a.rot) launch_sim3p_variant<true>(a, stream);
-  else launch_sim3p_variant<false>(a, stream);
+int launch_tick_sim3p(const KernelArgs& a, void* stream, const WbcTaskParams* tp) {
+  if (a.rot) launch_sim3p_variant<true>(a, stream, tp);
+  else launch_sim3p_variant<false>(a, stream, tp);
   return check_launch("tick_sim3p");
 }
 int sim3p_lds_bytes() { return (int)sizeof(SmemP); }
 #endif
 
 }  // namespace wbc
+#endif

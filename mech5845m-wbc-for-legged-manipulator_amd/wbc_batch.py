@@ -60,6 +60,29 @@ def _prep(a, dtype, keep, B=None, width=None, name="array", device_id=None):
     return arr.ctypes.data
 
 
+def _task_params(tp, B, keep, device_id):
+    """-> pointer to the [B, 85] float64 rows (wbc_model.task_params), or None. Strict: a wrong dtype or shape is an error, never a
+    silent conversion (a float32 sweep would otherwise be rounded without notice)."""
+    if tp is None:
+        return None
+    shape = tuple(tp.shape)
+    if shape != (B, capi.TASK_PARAMS_DOUBLES):
+        raise capi.WbcError("task_params: shape %s, want (%d, %d)" % (shape, B, capi.TASK_PARAMS_DOUBLES))
+    if _is_torch(tp):
+        import torch
+        if tp.dtype != torch.float64 or not tp.is_contiguous():
+            raise capi.WbcError("task_params: device tensors must be contiguous torch.float64")
+        if not tp.is_cuda or tp.device.index != device_id:
+            raise capi.WbcError("task_params lives on %s, the handle on cuda:%d" % (tp.device, device_id))
+        keep.append(tp)
+        return tp.data_ptr()
+    if not isinstance(tp, np.ndarray) or tp.dtype != np.float64:
+        raise capi.WbcError("task_params: want a float64 numpy array or torch tensor, got %s" % getattr(tp, "dtype", type(tp)))
+    arr = np.ascontiguousarray(tp)
+    keep.append(arr)
+    return arr.ctypes.data
+
+
 class WbcBatch:
     def __init__(self, models, max_batch, device_id=0):
         self.lib = capi.load_library()
@@ -186,10 +209,11 @@ class WbcBatch:
                                               mem, C.byref(o), self._stream(mem)), self.lib)
         return out
 
-    def assemble(self, inputs, dt, want=("A", "b", "H", "g", "C", "Clb", "Cub", "lb", "ub")):
-        """qpA/qpb/findConstraints/velDamperJointConstraints + H, g for every instance."""
+    def assemble(self, inputs, dt, want=("A", "b", "H", "g", "C", "Clb", "Cub", "lb", "ub"), task_params=None):
+        """qpA/qpb/findConstraints/velDamperJointConstraints + H, g for every instance. task_params: [B, 85] per-instance weights and
+        gains (wbc_model.task_params; wbc_assemble_tp), None = the configuration's."""
         keep = []
-        mem = _mem_of(list(inputs.values()))
+        mem = _mem_of(list(inputs.values()) + [task_params])
         q = inputs.get("q")
         B = self._batch_of(q)
         m, p = self.task_rows, self.constraint_rows
@@ -199,14 +223,16 @@ class WbcBatch:
         for k, v in out.items():
             setattr(o, k, self._p(v, np.float64, keep))
         tin = self._tick_in(inputs, keep, B)
-        capi.check(self.lib.wbc_assemble(self._h, B, C.byref(tin), float(dt), mem, C.byref(o), self._stream(mem)), self.lib)
+        tp = _task_params(task_params, B, keep, self.device_id)
+        capi.check(self.lib.wbc_assemble_tp(self._h, B, C.byref(tin), tp, float(dt), mem, C.byref(o), self._stream(mem)), self.lib)
         return out
 
     _TICK_OUT_WIDTH = dict(qdot=NV, status=1, iters=1, q_next=NQS, working_set=2)
 
-    def tick(self, inputs, dt, want_q_next=False, out=None, want_working_set=False):
+    def tick(self, inputs, dt, want_q_next=False, out=None, want_working_set=False, task_params=None):
         """One runWBC tick per instance up to the QP (+ integrate): returns dict(qdot, status, iters[, q_next][, working_set]).
-        inputs["working_set"] (int64 [B,2], the previous tick's out["working_set"]) warm-starts the QP (include/wbc.h)."""
+        inputs["working_set"] (int64 [B,2], the previous tick's out["working_set"]) warm-starts the QP (include/wbc.h).
+        task_params: [B, 85] per-instance weights and gains (wbc_model.task_params; wbc_tick_tp), None = the configuration's."""
         keep = []
         q = inputs.get("q")
         B = self._batch_of(q)
@@ -216,25 +242,28 @@ class WbcBatch:
                 out["q_next"] = self._alloc(q, (B, NQS))
             if want_working_set:
                 out["working_set"] = self._alloc(q, (B, 2), np.int64)
-        mem = _mem_of(list(inputs.values()) + list(out.values()))
+        mem = _mem_of(list(inputs.values()) + list(out.values()) + [task_params])
         o = self._outs(out, self._TICK_OUT_WIDTH, keep, B, capi.WbcTickOut())
         tin = self._tick_in(inputs, keep, B)
-        capi.check(self.lib.wbc_tick(self._h, B, C.byref(tin), float(dt), mem, C.byref(o), self._stream(mem)), self.lib)
+        tp = _task_params(task_params, B, keep, self.device_id)
+        capi.check(self.lib.wbc_tick_tp(self._h, B, C.byref(tin), tp, float(dt), mem, C.byref(o), self._stream(mem)), self.lib)
         return out
 
-    def make_tick_call(self, inputs, out, dt):
-        """Bind device tensors once; the returned closure issues exactly one wbc_tick on the handle's current stream."""
+    def make_tick_call(self, inputs, out, dt, task_params=None):
+        """Bind device tensors once; the returned closure issues exactly one wbc_tick (wbc_tick_tp with task_params, [B, 85] on the
+        device: read afresh by every call) on the handle's current stream."""
         keep = []
-        if _mem_of(list(inputs.values()) + list(out.values())) != capi.MEM_DEVICE:
+        if _mem_of(list(inputs.values()) + list(out.values()) + [task_params]) != capi.MEM_DEVICE:
             raise capi.WbcError("make_tick_call wants device tensors")
         B = self._batch_of(inputs.get("q"))
         o = self._outs(out, self._TICK_OUT_WIDTH, keep, B, capi.WbcTickOut())
         tin = self._tick_in(inputs, keep, B)
+        tp = _task_params(task_params, B, keep, self.device_id)
         lib, h, dtv, dev = self.lib, self._h, float(dt), self.device_id
         import torch
 
         def call():
-            rc = lib.wbc_tick(h, B, C.byref(tin), dtv, capi.MEM_DEVICE, C.byref(o), torch.cuda.current_stream(dev).cuda_stream)
+            rc = lib.wbc_tick_tp(h, B, C.byref(tin), tp, dtv, capi.MEM_DEVICE, C.byref(o), torch.cuda.current_stream(dev).cuda_stream)
             if rc:
                 capi.check(rc, lib)
         call._keep = keep
@@ -318,14 +347,14 @@ class WbcBatch:
         return qn
 
     def rollout(self, inputs, dt, ticks, ee_target_step=None, trunk_target_step=None, imu=None, want_trace=True,
-                mode=capi.ROLLOUT_RUNNING, hold_ticks=0):
+                mode=capi.ROLLOUT_RUNNING, hold_ticks=0, task_params=None):
         """K closed-loop ticks on the device: tick -> update_state -> reference-state side effects ->
         targets advance by their step; then `hold_ticks` more ticks with the targets held. mode: ROLLOUT_RUNNING
         (updateState(running=True): IMU fed back, base re-estimated from the stance feet) or ROLLOUT_WARMUP
         (updateState(running=False), the loop of setInitialState). Returns dict(q, qdot, ee_target, status, iters[,
-        grip_trace [K + hold, B, 3]])."""
+        grip_trace [K + hold, B, 3]]). task_params: [B, 85] per-instance weights and gains for every tick (wbc_rollout_tp)."""
         keep = []
-        extra = [ee_target_step, trunk_target_step, imu]
+        extra = [ee_target_step, trunk_target_step, imu, task_params]
         mem = _mem_of(list(inputs.values()) + extra)
         q = inputs.get("q")
         B = self._batch_of(q)
@@ -344,7 +373,8 @@ class WbcBatch:
         if want_trace:
             r.grip_trace = P(out["grip_trace"], f, keep)
         tin = self._tick_in(inputs, keep, B)
-        capi.check(self.lib.wbc_rollout(self._h, B, C.byref(tin), float(dt), C.byref(r), mem, self._stream(mem)), self.lib)
+        tp = _task_params(task_params, B, keep, self.device_id)
+        capi.check(self.lib.wbc_rollout_tp(self._h, B, C.byref(tin), tp, float(dt), C.byref(r), mem, self._stream(mem)), self.lib)
         return out
 
     def integrate(self, q, v, dt, model_id=None):

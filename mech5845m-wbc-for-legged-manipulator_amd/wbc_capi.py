@@ -86,6 +86,19 @@ class WbcFkOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("oMi", "oMf", "J", "com", "Jcom")]
 
 
+# the weight / gain block of WbcConfig (ee_W .. joint_w), one row per instance: wbc_tick_tp / wbc_assemble_tp / wbc_rollout_tp
+class WbcTaskParams(C.Structure):
+    _fields_ = [
+        ("ee_W", (C.c_double * 6) * NEE), ("ee_w", C.c_double * NEE), ("ee_gain", (C.c_double * 6) * NEE),
+        ("trunk_W", C.c_double * 6), ("trunk_w", C.c_double), ("trunk_gain", C.c_double * 6),
+        ("com_W", C.c_double * 3), ("com_gain", C.c_double * 3),
+        ("joint_w", C.c_double),
+    ]
+
+
+TASK_PARAMS_DOUBLES = 85
+
+
 # every symbol include/wbc.h declares, with its ctypes signature
 _vp, _i, _d = C.c_void_p, C.c_int, C.c_double
 SIGNATURES = {
@@ -104,6 +117,9 @@ SIGNATURES = {
     "wbc_tick": (_i, [_vp, _i, C.POINTER(WbcTickIn), _d, _i, C.POINTER(WbcTickOut), _vp]),
     "wbc_update_state": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "wbc_rollout": (_i, [_vp, _i, C.POINTER(WbcTickIn), _d, C.POINTER(WbcRollout), _i, _vp]),
+    "wbc_tick_tp": (_i, [_vp, _i, C.POINTER(WbcTickIn), _vp, _d, _i, C.POINTER(WbcTickOut), _vp]),
+    "wbc_assemble_tp": (_i, [_vp, _i, C.POINTER(WbcTickIn), _vp, _d, _i, C.POINTER(WbcQpData), _vp]),
+    "wbc_rollout_tp": (_i, [_vp, _i, C.POINTER(WbcTickIn), _vp, _d, C.POINTER(WbcRollout), _i, _vp]),
     "wbc_integrate": (_i, [_vp, _i, _vp, _vp, _vp, _d, _i, _vp, _vp]),
     "wbc_batch_set_option": (_i, [_vp, C.c_char_p, _i]),
     "wbc_batch_get_stat": (_i, [_vp, C.c_char_p, _vp, C.POINTER(C.c_int64)]),

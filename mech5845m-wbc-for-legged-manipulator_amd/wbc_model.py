@@ -6,6 +6,7 @@ tree (models/*.json, produced at build time by tools/bake_model.py from the refe
 ``make_config`` gathers the attributes ``__init__`` / ``setTasks`` / ``setConstraints`` /
 ``staticReachMode`` set (Robot_Wrapper4.py:72-125, 176-193, 1415-1464) into the C-ABI ``WbcConfig``.
 """
+import ctypes as C
 import json
 import math
 import os
@@ -206,3 +207,50 @@ def equality_only_config(model):
     no box bounds."""
     return make_config(model, FR=True, FL=True, RR=True, RL=True, Grip=True, Joint=True, task_com=True,
                        cFR=True, cFL=True, cRR=True, cRL=True, use_bounds=False)
+
+
+# ---- per-instance task weights and gains (WbcTaskParams: the ee_W .. joint_w block of WbcConfig, 85 doubles per instance)
+def _tp_layout():
+    out, off = {}, 0
+    for name, ctype in capi.WbcTaskParams._fields_:
+        n = C.sizeof(ctype) // 8
+        shape = ()
+        t = ctype
+        while hasattr(t, "_length_"):
+            shape += (t._length_,)
+            t = t._type_
+        out[name] = (slice(off, off + n), shape)
+        off += n
+    assert off == capi.TASK_PARAMS_DOUBLES
+    return out
+
+
+# field name -> (slice of the 85-double row, per-instance shape): e.g. TASK_PARAMS_LAYOUT["ee_gain"] = (slice(35, 65), (5, 6))
+TASK_PARAMS_LAYOUT = _tp_layout()
+TASK_PARAMS_SLICES = {k: v[0] for k, v in TASK_PARAMS_LAYOUT.items()}
+
+
+def task_params(cfg, B, **overrides):
+    """[B, 85] float64 rows for WbcBatch.tick / assemble / rollout(task_params=...): every row the configuration's weights and gains,
+    then `overrides` (field name -> per-instance values of shape [B, *field shape], e.g. ee_gain=[B, 5, 6], joint_w=[B]; a value without
+    the batch dimension is taken for every instance). Field names and meaning as in WbcConfig (ee_gain indexed as at Robot_Wrapper4.py:908)."""
+    B = int(B)
+    if B < 1:
+        raise ValueError("task_params: B = %d" % B)
+    row = np.zeros(capi.TASK_PARAMS_DOUBLES)
+    for name, (sl, shape) in TASK_PARAMS_LAYOUT.items():
+        row[sl] = np.asarray(np.ctypeslib.as_array(getattr(cfg, name)) if shape else getattr(cfg, name), dtype=np.float64).reshape(-1)
+    out = np.tile(row, (B, 1))
+    for name, v in overrides.items():
+        if name not in TASK_PARAMS_LAYOUT:
+            raise KeyError("task_params: unknown field %r (fields: %s)" % (name, ", ".join(TASK_PARAMS_LAYOUT)))
+        sl, shape = TASK_PARAMS_LAYOUT[name]
+        a = np.asarray(v)
+        if a.dtype.kind not in "fiu":
+            raise TypeError("task_params: %s must be numeric, got %s" % (name, a.dtype))
+        if a.shape == shape:
+            a = np.broadcast_to(a, (B,) + shape)
+        if a.shape != (B,) + shape:
+            raise ValueError("task_params: %s has shape %s, want %s or %s" % (name, a.shape, (B,) + shape, shape))
+        out[:, sl] = a.reshape(B, -1).astype(np.float64)
+    return out
