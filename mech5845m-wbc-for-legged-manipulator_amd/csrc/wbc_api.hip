@@ -911,38 +911,36 @@ static bool boxp_eligible(const WbcBatch* b, const KernelArgs& a) {
   for (int i = 0; i < b->n_models; ++i) if (!b->plan_host[i].x_ok) return false;
   return true;
 }
+// What the compact and packed kernels need before a launch: a status buffer when the caller passed none; with `packed` also the word of the
+// "deferred_last" statistic (the instances a packed kernel's tail redid) and this launch's sequence number (0 is the cleared word's).
+static int prepare_tick(WbcBatch* b, KernelArgs& a, void* stream, bool packed) {
+  if (!a.out.status) {
+    if (!b->d_status) HIP_TRY(hipMalloc((void**)&b->d_status, sizeof(int32_t) * (size_t)b->max_batch));
+    a.out.status = b->d_status;
+  }
+  if (!packed) return WBC_OK;
+  if (!b->d_dstat) {
+    HIP_TRY(hipMalloc((void**)&b->d_dstat, sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(b->d_dstat, 0, sizeof(unsigned long long), (hipStream_t)stream));
+  }
+  a.defer_stat = b->d_dstat;
+  a.tick_seq = ++b->tick_seq;
+  if (!b->tick_seq) a.tick_seq = ++b->tick_seq;
+  return WBC_OK;
+}
 static int launch_tick_auto(WbcBatch* b, KernelArgs& a, int B, void* stream, const WbcTaskParams* tp = nullptr) {
+  int rc;
   if (boxp_eligible(b, a)) {    // ONE kernel per tick; last_path 4
     b->last_path = 4;
     b->last_orth = 0;
-    if (!a.out.status) {
-      if (!b->d_status) HIP_TRY(hipMalloc((void**)&b->d_status, sizeof(int32_t) * (size_t)b->max_batch));
-      a.out.status = b->d_status;
-    }
-    if (!b->d_dstat) {
-      HIP_TRY(hipMalloc((void**)&b->d_dstat, sizeof(unsigned long long)));
-      HIP_TRY(hipMemsetAsync(b->d_dstat, 0, sizeof(unsigned long long), (hipStream_t)stream));
-    }
-    a.defer_stat = b->d_dstat;
-    a.tick_seq = ++b->tick_seq;
-    if (!b->tick_seq) a.tick_seq = ++b->tick_seq;
+    if ((rc = prepare_tick(b, a, stream, true))) return rc;
     if (int e = launch_tick_boxp(a, stream, tp)) return fail(WBC_E_HIP, "packed box tick kernel launch failed: %s", hipGetErrorString((hipError_t)e));
     return WBC_OK;
   }
   if (orthp_eligible(b, a)) {   // ONE kernel per tick; last_path 3
     b->last_path = 3;
     b->last_orth = 1;
-    if (!a.out.status) {
-      if (!b->d_status) HIP_TRY(hipMalloc((void**)&b->d_status, sizeof(int32_t) * (size_t)b->max_batch));
-      a.out.status = b->d_status;
-    }
-    if (!b->d_dstat) {
-      HIP_TRY(hipMalloc((void**)&b->d_dstat, sizeof(unsigned long long)));
-      HIP_TRY(hipMemsetAsync(b->d_dstat, 0, sizeof(unsigned long long), (hipStream_t)stream));
-    }
-    a.defer_stat = b->d_dstat;
-    a.tick_seq = ++b->tick_seq;
-    if (!b->tick_seq) a.tick_seq = ++b->tick_seq;
+    if ((rc = prepare_tick(b, a, stream, true))) return rc;
     if (int e = launch_tick_orthp(a, stream, b->plan_host[0].q_ok == 2, tp)) return fail(WBC_E_HIP, "packed orth tick kernel launch failed: %s", hipGetErrorString((hipError_t)e));
     return WBC_OK;
   }
@@ -957,10 +955,7 @@ static int launch_tick_auto(WbcBatch* b, KernelArgs& a, int B, void* stream, con
     return WBC_OK;
   }
   b->last_path = 1;
-  if (!a.out.status) {
-    if (!b->d_status) HIP_TRY(hipMalloc((void**)&b->d_status, sizeof(int32_t) * (size_t)b->max_batch));
-    a.out.status = b->d_status;
-  }
+  if ((rc = prepare_tick(b, a, stream, false))) return rc;
   if (!b->d_defer) {
     HIP_TRY(hipMalloc((void**)&b->d_defer, sizeof(int32_t) * ((size_t)b->max_batch + 4)));
     // (on the CALL's stream: a null-stream memset is not ordered against a non-blocking caller stream)
@@ -975,14 +970,8 @@ static int launch_tick_auto(WbcBatch* b, KernelArgs& a, int B, void* stream, con
   }
   if (packed_eligible(b, a)) {   // ONE kernel per tick: what the packed kernel cannot reduce its own wave redoes on the general path
     b->last_path = 2;
-    if (!b->d_dstat) {
-      HIP_TRY(hipMalloc((void**)&b->d_dstat, sizeof(unsigned long long)));
-      HIP_TRY(hipMemsetAsync(b->d_dstat, 0, sizeof(unsigned long long), (hipStream_t)stream));
-    }
-    a.defer_stat = b->d_dstat;
+    if ((rc = prepare_tick(b, a, stream, true))) return rc;   // (the status buffer is in place already)
     a.packed_trunk = b->cfg_host[0].task_trunk != 0;
-    a.tick_seq = ++b->tick_seq;
-    if (!b->tick_seq) a.tick_seq = ++b->tick_seq;          // (0 is the cleared word's sequence number)
     if (int e = launch_tick_sim3p(a, stream, tp)) return fail(WBC_E_HIP, "packed sim3 tick kernel launch failed: %s", hipGetErrorString((hipError_t)e));
     return WBC_OK;
   }

@@ -1913,7 +1913,7 @@ __device__ __forceinline__ bool contact_presolve_orth(Smem& S, const KA& A, cons
 }
 
 // ------------------------------------------------------------------------------------------------
-// Per-instance task weights and gains (WbcTaskParams, the TP kernels' parameter `tp`): the TP instantiations read the weight / gain block through TPW(field)
+// Per-instance task weights and gains (WbcTaskParams, the general and packed tick kernels' fifth parameter `tps`): the TP instantiations read the weight / gain block through TPW(field)
 // from the instance's row instead of its model's configuration — same field names, same offsets. A wave-uniform row is read through the
 // constant address space (scalar loads, as the configuration itself).
 // ------------------------------------------------------------------------------------------------
@@ -2550,7 +2550,7 @@ __device__ __forceinline__ void tail_instance(Smem* Sp, const int bt_v, const De
   const LaneConst lc = load_lane_const(models[mi], cfgs[mi], ln);
   stage_inputs(S, cur, ln, has2, has3);
   if (TP) {
-    const WbcTaskParams* const tps = ((const __attribute__((address_space(4))) TpKernarg*)Ap)->tp;   // (a TP kernel's fifth parameter)
+    const WbcTaskParams* const tps = ((const __attribute__((address_space(4))) TpKernarg*)Ap)->tp;   // (the kernel's fifth parameter)
     const bool tp_bad = tp_row_bad(tps + bt_, ln);
     const TpRow tpr = tp_bad ? (TpRow)&cfgs[mi].ee_W[0][0] : (TpRow)(tps + bt_);
     WSYNC();

@@ -140,8 +140,9 @@ struct KernelArgs {
   int32_t rot;                      // a model of the handle has a rotated joint placement: the packed kernels' ROT instantiations run
 };
 
-// The kernel parameters of the TP kernels (wbc_tick_tp & co.): the other kernels' four, then the per-instance rows [B]. KernelArgs keeps its size,
-// so that the kernels without rows keep their code; the packed kernels' tail reads `tp` back through the kernarg segment like KernelArgs itself.
+// The kernel parameters of every tick kernel (wbc_tick_kernel, wbc_tick_sim3p / orthp / boxp_kernel): KernelArgs, the three tables, then the
+// per-instance rows [B] (wbc_tick_tp & co.; nullptr for the instantiations without TP, which never read it). KernelArgs keeps its size, so that
+// the kernels without rows keep their code; the packed kernels' tail reads `tp` back through the kernarg segment like KernelArgs itself.
 struct TpKernarg {
   KernelArgs A;
   const DevModel* models;

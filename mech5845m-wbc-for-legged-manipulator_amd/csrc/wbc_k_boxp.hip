@@ -1,5 +1,4 @@
-// wbc_k_boxp.hip — the packed box kernel wbc_tick_boxp_kernel<WARM>: task problems without constraint rows (the warm-up problem), four instances per wavefront.
-#ifndef WBC_KPASS
+// wbc_k_boxp.hip — the packed box kernel wbc_tick_boxp_kernel<WARM, ROT, TP>: task problems without constraint rows (the warm-up problem), four instances per wavefront.
 #include "wbc_packed.h"
 
 namespace wbc {
@@ -48,24 +47,13 @@ struct XIntegrate { const double* in; const double* xv; };   // what integrate_f
 #endif
 // WARM: the variant that takes / returns working sets (KernelArgs.ws_in / ws_out, word 0: velocity bounds by DoF) — the packed sim3 kernel's scheme
 // (seeds through the add step, x / u rebuilt from the factors, restoration) on the kept variables; eliminated and locked DoF carry no seed.
-#endif
-#ifdef WBC_KPASS
 // ROT: rotated joint placements in the batch (wbc_k_sim3p.hip). TP: per-instance weights and gains (wbc_tick_tp: the kernel's fifth parameter
 // tps [B]) staged into wt in place of the configuration's block; a row with a non-finite entry or joint_w == 0 gives its instance
-// WBC_QP_NUMERICAL. The text below is compiled twice, as wbc_k_sim3p.hip's kernel is: wbc_tick_boxp_kernel (no rows, its code as before)
-// and wbc_tick_boxp_tp_kernel.
-template <bool WARM, bool ROT = false>
-#if WBC_KPASS == 1
+// WBC_QP_NUMERICAL. Without TP, tps is nullptr and never read.
+template <bool WARM, bool ROT = false, bool TP = false>
 __global__ void __launch_bounds__(64, 2) wbc_tick_boxp_kernel(const KernelArgs A, const DevModel* __restrict__ models,
-                                                              const WbcConfig* __restrict__ cfgs, const DevPlan* __restrict__ plans) {
-  constexpr bool TP = false;
-  const WbcTaskParams* const tps = nullptr;
-#else
-__global__ void __launch_bounds__(64, 2) wbc_tick_boxp_tp_kernel(const KernelArgs A, const DevModel* __restrict__ models,
-                                                                 const WbcConfig* __restrict__ cfgs, const DevPlan* __restrict__ plans,
-                                                                 const WbcTaskParams* __restrict__ tps) {
-  constexpr bool TP = true;
-#endif
+                                                              const WbcConfig* __restrict__ cfgs, const DevPlan* __restrict__ plans,
+                                                              const WbcTaskParams* __restrict__ tps) {
   __shared__ union { XInst Q[4]; Smem G; } SU;
   const int lane = threadIdx.x, r = lane >> 4, s = lane & 15, rbase = lane & 48;
   XInst& I = SU.Q[r];
@@ -872,22 +860,14 @@ __global__ void __launch_bounds__(64, 2) wbc_tick_boxp_tp_kernel(const KernelArg
     }
   }
 }
-#else
-// the two kernels from the text above: wbc_tick_boxp_kernel (no rows, the code it always had) and wbc_tick_boxp_tp_kernel (TP)
-#define WBC_KPASS 1
-#include "wbc_k_boxp.hip"
-#undef WBC_KPASS
-#define WBC_KPASS 2
-#include "wbc_k_boxp.hip"
-#undef WBC_KPASS
 
 // One translation unit per PART (csrc/Makefile compiles this file once per part, in parallel): each part instantiates some of the kernel's
 // variants; part 0 also holds the launcher and sees the other parts' variants as explicit-instantiation declarations.
 #ifndef BOXP_PART
 #define BOXP_PART -1      // -1: everything in one unit
 #endif
-#define KINST(...) template __global__ void wbc_tick_boxp_kernel<__VA_ARGS__>(const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__);
-#define KDECL(...) extern template __global__ void wbc_tick_boxp_kernel<__VA_ARGS__>(const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__);
+#define KINST(...) template __global__ void wbc_tick_boxp_kernel<__VA_ARGS__>(const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__, const WbcTaskParams* __restrict__);
+#define KDECL(...) extern template __global__ void wbc_tick_boxp_kernel<__VA_ARGS__>(const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__, const WbcTaskParams* __restrict__);
 #if BOXP_PART == 0 || BOXP_PART == -1
 KINST(false)
 #endif
@@ -903,47 +883,32 @@ KINST(true, true)
 KDECL(false, true)
 KDECL(true, true)
 #endif
-#define TINST(...) template __global__ void wbc_tick_boxp_tp_kernel<__VA_ARGS__>(const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__, const WbcTaskParams* __restrict__);
-#define TDECL(...) extern template __global__ void wbc_tick_boxp_tp_kernel<__VA_ARGS__>(const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__, const WbcTaskParams* __restrict__);
-// the TP kernels: a part of their own (the parts above keep their code objects)
+// with rows (TP): a part of their own
 #if BOXP_PART == 3 || BOXP_PART == -1
-TINST(false)
-TINST(true)
-TINST(false, true)
-TINST(true, true)
+KINST(false, false, true)
+KINST(true, false, true)
+KINST(false, true, true)
+KINST(true, true, true)
 #elif BOXP_PART == 0
-TDECL(false)
-TDECL(true)
-TDECL(false, true)
-TDECL(true, true)
+KDECL(false, false, true)
+KDECL(true, false, true)
+KDECL(false, true, true)
+KDECL(true, true, true)
 #endif
 #undef KINST
 #undef KDECL
-#undef TINST
-#undef TDECL
 #if BOXP_PART <= 0
-static int launch_tick_boxp_tp(const KernelArgs& a, void* stream, const WbcTaskParams* tp) {
+template <bool ROT, bool TP>
+static void launch_boxp_variant(const KernelArgs& a, void* stream, const WbcTaskParams* tp) {
   const dim3 grid((a.B + 3) / 4);
-  const bool warm = a.ws_in || a.ws_out;
-  if (a.rot) {
-    if (warm) hipLaunchKernelGGL((wbc_tick_boxp_tp_kernel<true, true>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
-    else hipLaunchKernelGGL((wbc_tick_boxp_tp_kernel<false, true>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
-  } else if (warm) hipLaunchKernelGGL(wbc_tick_boxp_tp_kernel<true>, grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
-  else hipLaunchKernelGGL(wbc_tick_boxp_tp_kernel<false>, grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
-  return check_launch("tick_boxp_tp");
+  if (a.ws_in || a.ws_out) hipLaunchKernelGGL((wbc_tick_boxp_kernel<true, ROT, TP>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
+  else hipLaunchKernelGGL((wbc_tick_boxp_kernel<false, ROT, TP>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
 }
 int launch_tick_boxp(const KernelArgs& a, void* stream, const WbcTaskParams* tp) {
-  if (tp) return launch_tick_boxp_tp(a, stream, tp);
-  if (a.rot) {
-    if (a.ws_in || a.ws_out) hipLaunchKernelGGL((wbc_tick_boxp_kernel<true, true>), dim3((a.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
-    else hipLaunchKernelGGL((wbc_tick_boxp_kernel<false, true>), dim3((a.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
-    return check_launch("tick_boxp");
-  }
-  if (a.ws_in || a.ws_out) hipLaunchKernelGGL(wbc_tick_boxp_kernel<true>, dim3((a.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
-  else hipLaunchKernelGGL(wbc_tick_boxp_kernel<false>, dim3((a.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
+  if (a.rot) tp ? launch_boxp_variant<true, true>(a, stream, tp) : launch_boxp_variant<true, false>(a, stream, tp);
+  else tp ? launch_boxp_variant<false, true>(a, stream, tp) : launch_boxp_variant<false, false>(a, stream, tp);
   return check_launch("tick_boxp");
 }
 #endif
 
 }  // namespace wbc
-#endif

@@ -1,4 +1,4 @@
-// wbc_k_general.hip — the general tick kernel wbc_tick_kernel<MODE, WARM, ORTH> (one instance per wavefront; tick / assemble / FK outputs).
+// wbc_k_general.hip — the general tick kernel wbc_tick_kernel<MODE, WARM, ORTH, ROT, TP> (one instance per wavefront; tick / assemble / FK outputs).
 #include "wbc_common.h"
 
 namespace wbc {
@@ -11,9 +11,12 @@ namespace wbc {
 // ORTH: the variant that carries contact_presolve_orth (chosen by launch_tick when a plan of the batch asks for it: the other
 // variants keep their register allocation — with the extra code inlined the general kernel went from 198 VGPRs to 256 + spills)
 // ROT: rotated joint placements in the handle (KernelArgs.rot, fk_levels)
-template <int MODE, bool WARM = false, bool ORTH = false, bool ROT = false>
+// TP: per-instance weights and gains (tps [B], wbc_tick_tp / wbc_assemble_tp): row b replaces cfgs[mid]'s weight / gain block (a row that
+// tp_row_bad refuses gives the instance WBC_QP_NUMERICAL). Every tick kernel takes tps; the kernels without rows get nullptr and never read it.
+template <int MODE, bool WARM = false, bool ORTH = false, bool ROT = false, bool TP = false>
 __global__ void __launch_bounds__(64, 2) wbc_tick_kernel(const KernelArgs A, const DevModel* __restrict__ models,
-                                                         const WbcConfig* __restrict__ cfgs, const DevPlan* __restrict__ plans) {
+                                                         const WbcConfig* __restrict__ cfgs, const DevPlan* __restrict__ plans,
+                                                         const WbcTaskParams* __restrict__ tps) {
   // models / cfgs are separate __restrict__ const parameters so that the compiler may read them with scalar loads
   // (as members of A it must assume the kernel's own stores clobber them: every access became a vector load + full wait).
   // ONE instance per single-wave workgroup, no loop: inside a persistent loop the compiler hoists hundreds of
@@ -36,33 +39,15 @@ __global__ void __launch_bounds__(64, 2) wbc_tick_kernel(const KernelArgs A, con
   const int mid = model_index(A.in.model_id, b, A.n_models);
   const InRegs cur = load_inputs(A.in, A.dbg_alias ? 0 : b, lane, has2, has3);   // dbg_alias: diagnostic, every wave reads instance 0
   const LaneConst lc = load_lane_const(models[mid], cfgs[mid], lane);   // L1/L2-resident 3 KB table
+  bool tp_bad = false;
+  TpRow tpr = nullptr;
+  if constexpr (TP) {   // (an assembly reports no status: its rows enter as they are)
+    tp_bad = MODE == MODE_TICK && tp_row_bad(tps + b, lane);
+    tpr = tp_bad ? (TpRow)&cfgs[mid].ee_W[0][0] : (TpRow)(tps + b);
+  }
   stage_inputs(S, cur, lane, has2, has3);
   WSYNC();
-  process_instance<MODE, WARM, ORTH, ROT>(S, A, models[mid], cfgs[mid], plans[mid], lc, cur, b, lane, t_entry);
-}
-
-// TP: the same tick with per-instance weights and gains (tp [B], wbc_tick_tp / wbc_assemble_tp): row b replaces cfgs[mid]'s weight / gain
-// block (a row that tp_row_bad refuses gives the instance WBC_QP_NUMERICAL). A kernel of its own, so that the kernels above keep their code.
-template <int MODE, bool WARM = false, bool ORTH = false, bool ROT = false>
-__global__ void __launch_bounds__(64, 2) wbc_tick_tp_kernel(const KernelArgs A, const DevModel* __restrict__ models,
-                                                            const WbcConfig* __restrict__ cfgs, const DevPlan* __restrict__ plans,
-                                                            const WbcTaskParams* __restrict__ tp) {
-  __shared__ Smem S;
-  const int lane = threadIdx.x;
-  const int b = blockIdx.x;
-  S.cl[lane] = 0.0;
-  const bool has2 = A.in.trunk_target || A.in.prev_trunk_target || A.in.trunk_ref_euler || A.in.trunk_prev_rot ||
-                    A.in.com_target || A.in.com_target_vel;
-  const bool has3 = A.in.ee_ref_rot != nullptr;
-  const int mid = model_index(A.in.model_id, b, A.n_models);
-  const InRegs cur = load_inputs(A.in, A.dbg_alias ? 0 : b, lane, has2, has3);
-  const LaneConst lc = load_lane_const(models[mid], cfgs[mid], lane);
-  // (an assembly reports no status: its rows enter as they are)
-  const bool tp_bad = MODE == MODE_TICK && tp_row_bad(tp + b, lane);
-  const TpRow tpr = tp_bad ? (TpRow)&cfgs[mid].ee_W[0][0] : (TpRow)(tp + b);
-  stage_inputs(S, cur, lane, has2, has3);
-  WSYNC();
-  process_instance<MODE, WARM, ORTH, ROT, true>(S, A, models[mid], cfgs[mid], plans[mid], lc, cur, b, lane, 0ull, tpr, tp_bad);
+  process_instance<MODE, WARM, ORTH, ROT, TP>(S, A, models[mid], cfgs[mid], plans[mid], lc, cur, b, lane, t_entry, tpr, tp_bad);
 }
 
 // One translation unit per PART (csrc/Makefile compiles this file once per part, in parallel): each part instantiates some of the kernel's
@@ -70,8 +55,8 @@ __global__ void __launch_bounds__(64, 2) wbc_tick_tp_kernel(const KernelArgs A, 
 #ifndef GENERAL_PART
 #define GENERAL_PART -1      // -1: everything in one unit
 #endif
-#define KINST(...) template __global__ void wbc_tick_kernel<__VA_ARGS__>(const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__);
-#define KDECL(...) extern template __global__ void wbc_tick_kernel<__VA_ARGS__>(const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__);
+#define KINST(...) template __global__ void wbc_tick_kernel<__VA_ARGS__>(const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__, const WbcTaskParams* __restrict__);
+#define KDECL(...) extern template __global__ void wbc_tick_kernel<__VA_ARGS__>(const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__, const WbcTaskParams* __restrict__);
 #if GENERAL_PART == 0 || GENERAL_PART == -1
 KINST(MODE_TICK)
 #endif
@@ -108,70 +93,48 @@ KDECL(MODE_TICK, false, true, true)
 KDECL(MODE_ASSEMBLE, false, false, true)
 KDECL(MODE_FK, false, false, true)
 #endif
-#define TINST(...) template __global__ void wbc_tick_tp_kernel<__VA_ARGS__>(const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__, const WbcTaskParams* __restrict__);
-#define TDECL(...) extern template __global__ void wbc_tick_tp_kernel<__VA_ARGS__>(const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__, const WbcTaskParams* __restrict__);
-// the TP kernels: parts of their own (the parts above keep their code objects)
+// with rows (TP): parts of their own; no FK kernel (it reads no weight)
 #if GENERAL_PART == 6 || GENERAL_PART == -1
-TINST(MODE_TICK)
-TINST(MODE_TICK, true)
-TINST(MODE_ASSEMBLE)
+KINST(MODE_TICK, false, false, false, true)
+KINST(MODE_TICK, true, false, false, true)
+KINST(MODE_ASSEMBLE, false, false, false, true)
 #elif GENERAL_PART == 0
-TDECL(MODE_TICK)
-TDECL(MODE_TICK, true)
-TDECL(MODE_ASSEMBLE)
+KDECL(MODE_TICK, false, false, false, true)
+KDECL(MODE_TICK, true, false, false, true)
+KDECL(MODE_ASSEMBLE, false, false, false, true)
 #endif
 #if GENERAL_PART == 7 || GENERAL_PART == -1
-TINST(MODE_TICK, false, true)
-TINST(MODE_TICK, false, true, true)
+KINST(MODE_TICK, false, true, false, true)
+KINST(MODE_TICK, false, true, true, true)
 #elif GENERAL_PART == 0
-TDECL(MODE_TICK, false, true)
-TDECL(MODE_TICK, false, true, true)
+KDECL(MODE_TICK, false, true, false, true)
+KDECL(MODE_TICK, false, true, true, true)
 #endif
 #if GENERAL_PART == 8 || GENERAL_PART == -1
-TINST(MODE_TICK, false, false, true)
-TINST(MODE_TICK, true, false, true)
-TINST(MODE_ASSEMBLE, false, false, true)
+KINST(MODE_TICK, false, false, true, true)
+KINST(MODE_TICK, true, false, true, true)
+KINST(MODE_ASSEMBLE, false, false, true, true)
 #elif GENERAL_PART == 0
-TDECL(MODE_TICK, false, false, true)
-TDECL(MODE_TICK, true, false, true)
-TDECL(MODE_ASSEMBLE, false, false, true)
+KDECL(MODE_TICK, false, false, true, true)
+KDECL(MODE_TICK, true, false, true, true)
+KDECL(MODE_ASSEMBLE, false, false, true, true)
 #endif
 #undef KINST
 #undef KDECL
-#undef TINST
-#undef TDECL
 #if GENERAL_PART <= 0
-// the TP kernels: the same choice of variant as launch_tick (no FK mode: it reads no weight)
-static int launch_tick_tp(const KernelArgs& a, int mode, int grid, hipStream_t s, const WbcTaskParams* tp) {
-  if (a.rot) {
-    if (mode == MODE_TICK && (a.ws_in || a.ws_out)) hipLaunchKernelGGL((wbc_tick_tp_kernel<MODE_TICK, true, false, true>), dim3(grid), dim3(64), 0, s, a, a.models, a.cfgs, a.plans, tp);
-    else if (mode == MODE_TICK && a.presolve && a.presolve_orth == 2) hipLaunchKernelGGL((wbc_tick_tp_kernel<MODE_TICK, false, true, true>), dim3(grid), dim3(64), 0, s, a, a.models, a.cfgs, a.plans, tp);
-    else if (mode == MODE_TICK) hipLaunchKernelGGL((wbc_tick_tp_kernel<MODE_TICK, false, false, true>), dim3(grid), dim3(64), 0, s, a, a.models, a.cfgs, a.plans, tp);
-    else hipLaunchKernelGGL((wbc_tick_tp_kernel<MODE_ASSEMBLE, false, false, true>), dim3(grid), dim3(64), 0, s, a, a.models, a.cfgs, a.plans, tp);
-    return check_launch("tick_tp");
-  }
-  if (mode == MODE_TICK && (a.ws_in || a.ws_out)) hipLaunchKernelGGL((wbc_tick_tp_kernel<MODE_TICK, true>), dim3(grid), dim3(64), 0, s, a, a.models, a.cfgs, a.plans, tp);
-  else if (mode == MODE_TICK && a.presolve && a.presolve_orth == 2) hipLaunchKernelGGL((wbc_tick_tp_kernel<MODE_TICK, false, true>), dim3(grid), dim3(64), 0, s, a, a.models, a.cfgs, a.plans, tp);
-  else if (mode == MODE_TICK) hipLaunchKernelGGL(wbc_tick_tp_kernel<MODE_TICK>, dim3(grid), dim3(64), 0, s, a, a.models, a.cfgs, a.plans, tp);
-  else hipLaunchKernelGGL(wbc_tick_tp_kernel<MODE_ASSEMBLE>, dim3(grid), dim3(64), 0, s, a, a.models, a.cfgs, a.plans, tp);
-  return check_launch("tick_tp");
+template <bool ROT, bool TP>
+static void launch_tick_variant(const KernelArgs& a, int mode, int grid, hipStream_t s, const WbcTaskParams* tp) {
+  if (mode == MODE_TICK && (a.ws_in || a.ws_out)) hipLaunchKernelGGL((wbc_tick_kernel<MODE_TICK, true, false, ROT, TP>), dim3(grid), dim3(64), 0, s, a, a.models, a.cfgs, a.plans, tp);
+  else if (mode == MODE_TICK && a.presolve && a.presolve_orth == 2) hipLaunchKernelGGL((wbc_tick_kernel<MODE_TICK, false, true, ROT, TP>), dim3(grid), dim3(64), 0, s, a, a.models, a.cfgs, a.plans, tp);
+  else if (mode == MODE_TICK) hipLaunchKernelGGL((wbc_tick_kernel<MODE_TICK, false, false, ROT, TP>), dim3(grid), dim3(64), 0, s, a, a.models, a.cfgs, a.plans, tp);
+  else if (TP || mode == MODE_ASSEMBLE) hipLaunchKernelGGL((wbc_tick_kernel<MODE_ASSEMBLE, false, false, ROT, TP>), dim3(grid), dim3(64), 0, s, a, a.models, a.cfgs, a.plans, tp);
+  else if constexpr (!TP) hipLaunchKernelGGL((wbc_tick_kernel<MODE_FK, false, false, ROT>), dim3(grid), dim3(64), 0, s, a, a.models, a.cfgs, a.plans, tp);
 }
 int launch_tick(const KernelArgs& a, int mode, int grid, void* stream, const WbcTaskParams* tp) {
   hipStream_t s = (hipStream_t)stream;
-  if (tp && mode != MODE_FK) return launch_tick_tp(a, mode, grid, s, tp);
-  if (a.rot) {
-    if (mode == MODE_TICK && (a.ws_in || a.ws_out)) hipLaunchKernelGGL((wbc_tick_kernel<MODE_TICK, true, false, true>), dim3(grid), dim3(64), 0, s, a, a.models, a.cfgs, a.plans);
-    else if (mode == MODE_TICK && a.presolve && a.presolve_orth == 2) hipLaunchKernelGGL((wbc_tick_kernel<MODE_TICK, false, true, true>), dim3(grid), dim3(64), 0, s, a, a.models, a.cfgs, a.plans);
-    else if (mode == MODE_TICK) hipLaunchKernelGGL((wbc_tick_kernel<MODE_TICK, false, false, true>), dim3(grid), dim3(64), 0, s, a, a.models, a.cfgs, a.plans);
-    else if (mode == MODE_ASSEMBLE) hipLaunchKernelGGL((wbc_tick_kernel<MODE_ASSEMBLE, false, false, true>), dim3(grid), dim3(64), 0, s, a, a.models, a.cfgs, a.plans);
-    else hipLaunchKernelGGL((wbc_tick_kernel<MODE_FK, false, false, true>), dim3(grid), dim3(64), 0, s, a, a.models, a.cfgs, a.plans);
-    return check_launch("tick");
-  }
-  if (mode == MODE_TICK && (a.ws_in || a.ws_out)) hipLaunchKernelGGL((wbc_tick_kernel<MODE_TICK, true>), dim3(grid), dim3(64), 0, s, a, a.models, a.cfgs, a.plans);
-  else if (mode == MODE_TICK && a.presolve && a.presolve_orth == 2) hipLaunchKernelGGL((wbc_tick_kernel<MODE_TICK, false, true>), dim3(grid), dim3(64), 0, s, a, a.models, a.cfgs, a.plans);
-  else if (mode == MODE_TICK) hipLaunchKernelGGL(wbc_tick_kernel<MODE_TICK>, dim3(grid), dim3(64), 0, s, a, a.models, a.cfgs, a.plans);
-  else if (mode == MODE_ASSEMBLE) hipLaunchKernelGGL(wbc_tick_kernel<MODE_ASSEMBLE>, dim3(grid), dim3(64), 0, s, a, a.models, a.cfgs, a.plans);
-  else hipLaunchKernelGGL(wbc_tick_kernel<MODE_FK>, dim3(grid), dim3(64), 0, s, a, a.models, a.cfgs, a.plans);
+  if (mode == MODE_FK) tp = nullptr;   // (FK reads no weight: no kernel with rows)
+  if (a.rot) tp ? launch_tick_variant<true, true>(a, mode, grid, s, tp) : launch_tick_variant<true, false>(a, mode, grid, s, tp);
+  else tp ? launch_tick_variant<false, true>(a, mode, grid, s, tp) : launch_tick_variant<false, false>(a, mode, grid, s, tp);
   return check_launch("tick");
 }
 int tick_lds_bytes() { return (int)sizeof(Smem); }

@@ -1,5 +1,4 @@
-// wbc_k_orthp.hip — the packed orth kernel wbc_tick_orthp_kernel<INEQ, WARM>: task problems whose tasks touch the stance legs, four instances per wavefront.
-#ifndef WBC_KPASS
+// wbc_k_orthp.hip — the packed orth kernel wbc_tick_orthp_kernel<INEQ, WARM, ROT, TP>: task problems whose tasks touch the stance legs, four instances per wavefront.
 #include "wbc_packed.h"
 
 namespace wbc {
@@ -47,24 +46,13 @@ static_assert(offsetof(QInst, xv) - offsetof(QInst, cl) == 80 * sizeof(double), 
 // the tail with the flagged ones.
 // WARM (INEQ only): working sets in and out — the packed sim3 kernel's scheme (seeds through the add step, x / u rebuilt from the factors, restoration).
 // In FULL-problem indexing a row of Z is the velocity bound of its DoF (word 0), the trunk / CoM box rows are findConstraints' rows (word 1).
-#endif
-#ifdef WBC_KPASS
 // ROT: rotated joint placements in the batch (wbc_k_sim3p.hip). TP: per-instance weights and gains (wbc_tick_tp: the kernel's fifth parameter
 // tps [B]) staged into wt in place of the configuration's block; a row with a non-finite entry or joint_w == 0 gives its instance
-// WBC_QP_NUMERICAL. The text below is compiled twice, as wbc_k_sim3p.hip's kernel is: wbc_tick_orthp_kernel (no rows, its code as before)
-// and wbc_tick_orthp_tp_kernel.
-template <bool INEQ, bool WARM = false, bool ROT = false>
-#if WBC_KPASS == 1
+// WBC_QP_NUMERICAL. Without TP, tps is nullptr and never read.
+template <bool INEQ, bool WARM = false, bool ROT = false, bool TP = false>
 __global__ void __launch_bounds__(64, 2) wbc_tick_orthp_kernel(const KernelArgs A, const DevModel* __restrict__ models,
-                                                               const WbcConfig* __restrict__ cfgs, const DevPlan* __restrict__ plans) {
-  constexpr bool TP = false;
-  const WbcTaskParams* const tps = nullptr;
-#else
-__global__ void __launch_bounds__(64, 2) wbc_tick_orthp_tp_kernel(const KernelArgs A, const DevModel* __restrict__ models,
-                                                                  const WbcConfig* __restrict__ cfgs, const DevPlan* __restrict__ plans,
-                                                                  const WbcTaskParams* __restrict__ tps) {
-  constexpr bool TP = true;
-#endif
+                                                               const WbcConfig* __restrict__ cfgs, const DevPlan* __restrict__ plans,
+                                                               const WbcTaskParams* __restrict__ tps) {
   __shared__ union { QInst Q[4]; Smem G; } SU;
   const int lane = threadIdx.x, r = lane >> 4, s = lane & 15, rbase = lane & 48;
   QInst& I = SU.Q[r];
@@ -1139,22 +1127,13 @@ __global__ void __launch_bounds__(64, 2) wbc_tick_orthp_tp_kernel(const KernelAr
   }
 }
 
-#else
-// the two kernels from the text above: wbc_tick_orthp_kernel (no rows, the code it always had) and wbc_tick_orthp_tp_kernel (TP)
-#define WBC_KPASS 1
-#include "wbc_k_orthp.hip"
-#undef WBC_KPASS
-#define WBC_KPASS 2
-#include "wbc_k_orthp.hip"
-#undef WBC_KPASS
-
 // One translation unit per PART (csrc/Makefile compiles this file once per part, in parallel): each part instantiates some of the kernel's
 // variants; part 0 also holds the launcher and sees the other parts' variants as explicit-instantiation declarations.
 #ifndef ORTHP_PART
 #define ORTHP_PART -1      // -1: everything in one unit
 #endif
-#define KINST(...) template __global__ void wbc_tick_orthp_kernel<__VA_ARGS__>(const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__);
-#define KDECL(...) extern template __global__ void wbc_tick_orthp_kernel<__VA_ARGS__>(const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__);
+#define KINST(...) template __global__ void wbc_tick_orthp_kernel<__VA_ARGS__>(const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__, const WbcTaskParams* __restrict__);
+#define KDECL(...) extern template __global__ void wbc_tick_orthp_kernel<__VA_ARGS__>(const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__, const WbcTaskParams* __restrict__);
 #if ORTHP_PART == 0 || ORTHP_PART == -1
 KINST(false)
 #endif
@@ -1177,60 +1156,42 @@ KDECL(false, false, true)
 KDECL(true, false, true)
 KDECL(true, true, true)
 #endif
-#define TINST(...) template __global__ void wbc_tick_orthp_tp_kernel<__VA_ARGS__>(const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__, const WbcTaskParams* __restrict__);
-#define TDECL(...) extern template __global__ void wbc_tick_orthp_tp_kernel<__VA_ARGS__>(const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__, const WbcTaskParams* __restrict__);
-// the TP kernels: parts of their own (the parts above keep their code objects)
+// with rows (TP): parts of their own
 #if ORTHP_PART == 4 || ORTHP_PART == -1
-TINST(false)
-TINST(true)
-TINST(true, true)
+KINST(false, false, false, true)
+KINST(true, false, false, true)
+KINST(true, true, false, true)
 #elif ORTHP_PART == 0
-TDECL(false)
-TDECL(true)
-TDECL(true, true)
+KDECL(false, false, false, true)
+KDECL(true, false, false, true)
+KDECL(true, true, false, true)
 #endif
 #if ORTHP_PART == 5 || ORTHP_PART == -1
-TINST(false, false, true)
-TINST(true, false, true)
-TINST(true, true, true)
+KINST(false, false, true, true)
+KINST(true, false, true, true)
+KINST(true, true, true, true)
 #elif ORTHP_PART == 0
-TDECL(false, false, true)
-TDECL(true, false, true)
-TDECL(true, true, true)
+KDECL(false, false, true, true)
+KDECL(true, false, true, true)
+KDECL(true, true, true, true)
 #endif
 #undef KINST
 #undef KDECL
-#undef TINST
-#undef TDECL
 #if ORTHP_PART <= 0
-static int launch_tick_orthp_tp(const KernelArgs& a, void* stream, int ineq, const WbcTaskParams* tp) {
+template <bool ROT, bool TP>
+static void launch_orthp_variant(const KernelArgs& a, void* stream, int ineq, const WbcTaskParams* tp) {
   const dim3 grid((a.B + 3) / 4);
   hipStream_t s = (hipStream_t)stream;
-  const bool warm = ineq && (a.ws_in || a.ws_out);
-  if (a.rot) {
-    if (warm) hipLaunchKernelGGL((wbc_tick_orthp_tp_kernel<true, true, true>), grid, dim3(64), 0, s, a, a.models, a.cfgs, a.plans, tp);
-    else if (ineq) hipLaunchKernelGGL((wbc_tick_orthp_tp_kernel<true, false, true>), grid, dim3(64), 0, s, a, a.models, a.cfgs, a.plans, tp);
-    else hipLaunchKernelGGL((wbc_tick_orthp_tp_kernel<false, false, true>), grid, dim3(64), 0, s, a, a.models, a.cfgs, a.plans, tp);
-  } else if (warm) hipLaunchKernelGGL((wbc_tick_orthp_tp_kernel<true, true>), grid, dim3(64), 0, s, a, a.models, a.cfgs, a.plans, tp);
-  else if (ineq) hipLaunchKernelGGL(wbc_tick_orthp_tp_kernel<true>, grid, dim3(64), 0, s, a, a.models, a.cfgs, a.plans, tp);
-  else hipLaunchKernelGGL(wbc_tick_orthp_tp_kernel<false>, grid, dim3(64), 0, s, a, a.models, a.cfgs, a.plans, tp);
-  return check_launch("tick_orthp_tp");
+  if (ineq && (a.ws_in || a.ws_out)) hipLaunchKernelGGL((wbc_tick_orthp_kernel<true, true, ROT, TP>), grid, dim3(64), 0, s, a, a.models, a.cfgs, a.plans, tp);
+  else if (ineq) hipLaunchKernelGGL((wbc_tick_orthp_kernel<true, false, ROT, TP>), grid, dim3(64), 0, s, a, a.models, a.cfgs, a.plans, tp);
+  else hipLaunchKernelGGL((wbc_tick_orthp_kernel<false, false, ROT, TP>), grid, dim3(64), 0, s, a, a.models, a.cfgs, a.plans, tp);
 }
 int launch_tick_orthp(const KernelArgs& a, void* stream, int ineq, const WbcTaskParams* tp) {
-  if (tp) return launch_tick_orthp_tp(a, stream, ineq, tp);
-  if (a.rot) {
-    if (ineq && (a.ws_in || a.ws_out)) hipLaunchKernelGGL((wbc_tick_orthp_kernel<true, true, true>), dim3((a.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
-    else if (ineq) hipLaunchKernelGGL((wbc_tick_orthp_kernel<true, false, true>), dim3((a.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
-    else hipLaunchKernelGGL((wbc_tick_orthp_kernel<false, false, true>), dim3((a.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
-    return check_launch("tick_orthp");
-  }
-  if (ineq && (a.ws_in || a.ws_out)) hipLaunchKernelGGL((wbc_tick_orthp_kernel<true, true>), dim3((a.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
-  else if (ineq) hipLaunchKernelGGL(wbc_tick_orthp_kernel<true>, dim3((a.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
-  else hipLaunchKernelGGL(wbc_tick_orthp_kernel<false>, dim3((a.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
+  if (a.rot) tp ? launch_orthp_variant<true, true>(a, stream, ineq, tp) : launch_orthp_variant<true, false>(a, stream, ineq, tp);
+  else tp ? launch_orthp_variant<false, true>(a, stream, ineq, tp) : launch_orthp_variant<false, false>(a, stream, ineq, tp);
   return check_launch("tick_orthp");
 }
 int orthp_lds_bytes() { return (int)(4 * sizeof(QInst)); }
 #endif
 
 }  // namespace wbc
-#endif

@@ -1,5 +1,4 @@
-// wbc_k_sim3p.hip — the packed sim3 kernel wbc_tick_sim3p_kernel<WARM, TRUNK, QCON>: the benchmark path, four instances per wavefront.
-#ifndef WBC_KPASS
+// wbc_k_sim3p.hip — the packed sim3 kernel wbc_tick_sim3p_kernel<WARM, TRUNK, QCON, ROT, TP>: the benchmark path, four instances per wavefront.
 #include "wbc_packed.h"
 
 namespace wbc {
@@ -26,28 +25,16 @@ namespace wbc {
 #endif
 // ROT: the batch holds a model with a rotated joint placement (DevModel.rot_mask): its FK records with `rot` go through fk_place_rot_lds.
 // The instantiations without it compile to exactly the code they had before the flag existed.
-#endif
-#ifdef WBC_KPASS
 // TP: per-instance weights and gains (wbc_tick_tp: the kernel's fifth parameter tps [B]): each group reads its instance's row in place of
-// cfgs[mid]'s block and the tail hands the row on; a row that tp_row_bad16 refuses gives its instance WBC_QP_NUMERICAL. The text below is
-// compiled twice (this file includes itself with WBC_KPASS = 1, 2): wbc_tick_sim3p_kernel without rows — its name and its code exactly as
-// before, TP constant false — and wbc_tick_sim3p_tp_kernel. (A template flag would rename the existing kernels; a shared inlined body
-// changed their register allocation.)
-template <bool WARM, bool TRUNK = false, bool QCON = false, bool ROT = false>
+// cfgs[mid]'s block and the tail hands the row on; a row that tp_row_bad16 refuses gives its instance WBC_QP_NUMERICAL. Without TP, tps is
+// nullptr and never read.
+template <bool WARM, bool TRUNK = false, bool QCON = false, bool ROT = false, bool TP = false>
 #ifdef SIM3P_NUM_VGPR
 __attribute__((amdgpu_waves_per_eu(SIM3P_NUM_VGPR, SIM3P_NUM_VGPR)))
 #endif
-#if WBC_KPASS == 1
 __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const KernelArgs A, const DevModel* __restrict__ models,
-                                                               const WbcConfig* __restrict__ cfgs, const DevPlan* __restrict__ plans) {
-  constexpr bool TP = false;
-  const WbcTaskParams* const tps = nullptr;
-#else
-__global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_tp_kernel(const KernelArgs A, const DevModel* __restrict__ models,
-                                                                  const WbcConfig* __restrict__ cfgs, const DevPlan* __restrict__ plans,
-                                                                  const WbcTaskParams* __restrict__ tps) {
-  constexpr bool TP = true;
-#endif
+                                                               const WbcConfig* __restrict__ cfgs, const DevPlan* __restrict__ plans,
+                                                               const WbcTaskParams* __restrict__ tps) {
   // (the general kernel's layout shares the allocation: an instance this kernel cannot reduce — a stance-leg block of rank < 2 — is
   //  redone on the general path by the SAME wave at the end, see the tail; both layouts leave 8 waves per CU)
 #ifdef SIM3P_NUM_VGPR      // (compile-only experiment: with the LDS size unknown to the compiler the occupancy attribute alone decides the register budget)
@@ -1327,22 +1314,13 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_tp_kernel(cons
 #endif
 }
 
-#else
-// the two kernels from the text above: wbc_tick_sim3p_kernel (no rows, the code it always had) and wbc_tick_sim3p_tp_kernel (TP)
-#define WBC_KPASS 1
-#include "wbc_k_sim3p.hip"
-#undef WBC_KPASS
-#define WBC_KPASS 2
-#include "wbc_k_sim3p.hip"
-#undef WBC_KPASS
-
 // One translation unit per PART (csrc/Makefile compiles this file once per part, in parallel): each part instantiates some of the kernel's
 // variants; part 0 also holds the launcher and sees the other parts' variants as explicit-instantiation declarations.
 #ifndef SIM3P_PART
 #define SIM3P_PART -1      // -1: everything in one unit
 #endif
-#define KINST(...) template __global__ void wbc_tick_sim3p_kernel<__VA_ARGS__>(const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__);
-#define KDECL(...) extern template __global__ void wbc_tick_sim3p_kernel<__VA_ARGS__>(const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__);
+#define KINST(...) template __global__ void wbc_tick_sim3p_kernel<__VA_ARGS__>(const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__, const WbcTaskParams* __restrict__);
+#define KDECL(...) extern template __global__ void wbc_tick_sim3p_kernel<__VA_ARGS__>(const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__, const WbcTaskParams* __restrict__);
 #if SIM3P_PART == 0 || SIM3P_PART == -1
 KINST(false, false)
 #endif
@@ -1380,80 +1358,63 @@ KINST(true, false, true, true)
 KDECL(false, false, true, true)
 KDECL(true, false, true, true)
 #endif
-#define TINST(...) template __global__ void wbc_tick_sim3p_tp_kernel<__VA_ARGS__>(const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__, const WbcTaskParams* __restrict__);
-#define TDECL(...) extern template __global__ void wbc_tick_sim3p_tp_kernel<__VA_ARGS__>(const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__, const WbcTaskParams* __restrict__);
-// the TP kernels: parts of their own (the parts above keep their code objects)
+// with rows (TP): parts of their own
 #if SIM3P_PART == 5 || SIM3P_PART == -1
-TINST(false, false)
-TINST(true, false)
-TINST(false, true)
+KINST(false, false, false, false, true)
+KINST(true, false, false, false, true)
+KINST(false, true, false, false, true)
 #elif SIM3P_PART == 0
-TDECL(false, false)
-TDECL(true, false)
-TDECL(false, true)
+KDECL(false, false, false, false, true)
+KDECL(true, false, false, false, true)
+KDECL(false, true, false, false, true)
 #endif
 #if SIM3P_PART == 6 || SIM3P_PART == -1
-TINST(true, true)
-TINST(false, false, true)
-TINST(true, false, true)
+KINST(true, true, false, false, true)
+KINST(false, false, true, false, true)
+KINST(true, false, true, false, true)
 #elif SIM3P_PART == 0
-TDECL(true, true)
-TDECL(false, false, true)
-TDECL(true, false, true)
+KDECL(true, true, false, false, true)
+KDECL(false, false, true, false, true)
+KDECL(true, false, true, false, true)
 #endif
 #if SIM3P_PART == 7 || SIM3P_PART == -1
-TINST(false, false, false, true)
-TINST(true, false, false, true)
-TINST(false, true, false, true)
+KINST(false, false, false, true, true)
+KINST(true, false, false, true, true)
+KINST(false, true, false, true, true)
 #elif SIM3P_PART == 0
-TDECL(false, false, false, true)
-TDECL(true, false, false, true)
-TDECL(false, true, false, true)
+KDECL(false, false, false, true, true)
+KDECL(true, false, false, true, true)
+KDECL(false, true, false, true, true)
 #endif
 #if SIM3P_PART == 8 || SIM3P_PART == -1
-TINST(true, true, false, true)
-TINST(false, false, true, true)
-TINST(true, false, true, true)
+KINST(true, true, false, true, true)
+KINST(false, false, true, true, true)
+KINST(true, false, true, true, true)
 #elif SIM3P_PART == 0
-TDECL(true, true, false, true)
-TDECL(false, false, true, true)
-TDECL(true, false, true, true)
+KDECL(true, true, false, true, true)
+KDECL(false, false, true, true, true)
+KDECL(true, false, true, true, true)
 #endif
 #undef KINST
 #undef KDECL
-#undef TINST
-#undef TDECL
 #if SIM3P_PART <= 0
-template <bool ROT>
-static void launch_sim3p_tp_variant(const KernelArgs& a, void* stream, const WbcTaskParams* tp) {
-  const bool warm = a.ws_in || a.ws_out, trunk = a.in.trunk_target && a.packed_trunk, qcon = a.in.q_con || a.in.posture_u;
-  const dim3 grid((a.B + 3) / 4);
-  if (qcon && warm) hipLaunchKernelGGL((wbc_tick_sim3p_tp_kernel<true, false, true, ROT>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
-  else if (qcon) hipLaunchKernelGGL((wbc_tick_sim3p_tp_kernel<false, false, true, ROT>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
-  else if (warm && trunk) hipLaunchKernelGGL((wbc_tick_sim3p_tp_kernel<true, true, false, ROT>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
-  else if (trunk) hipLaunchKernelGGL((wbc_tick_sim3p_tp_kernel<false, true, false, ROT>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
-  else if (warm) hipLaunchKernelGGL((wbc_tick_sim3p_tp_kernel<true, false, false, ROT>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
-  else hipLaunchKernelGGL((wbc_tick_sim3p_tp_kernel<false, false, false, ROT>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
-}
-template <bool ROT>
+template <bool ROT, bool TP>
 static void launch_sim3p_variant(const KernelArgs& a, void* stream, const WbcTaskParams* tp) {
-  if (tp) { launch_sim3p_tp_variant<ROT>(a, stream, tp); return; }
   const bool warm = a.ws_in || a.ws_out, trunk = a.in.trunk_target && a.packed_trunk, qcon = a.in.q_con || a.in.posture_u;
   const dim3 grid((a.B + 3) / 4);
-  if (qcon && warm) hipLaunchKernelGGL((wbc_tick_sim3p_kernel<true, false, true, ROT>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
-  else if (qcon) hipLaunchKernelGGL((wbc_tick_sim3p_kernel<false, false, true, ROT>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
-  else if (warm && trunk) hipLaunchKernelGGL((wbc_tick_sim3p_kernel<true, true, false, ROT>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
-  else if (trunk) hipLaunchKernelGGL((wbc_tick_sim3p_kernel<false, true, false, ROT>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
-  else if (warm) hipLaunchKernelGGL((wbc_tick_sim3p_kernel<true, false, false, ROT>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
-  else hipLaunchKernelGGL((wbc_tick_sim3p_kernel<false, false, false, ROT>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
+  if (qcon && warm) hipLaunchKernelGGL((wbc_tick_sim3p_kernel<true, false, true, ROT, TP>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
+  else if (qcon) hipLaunchKernelGGL((wbc_tick_sim3p_kernel<false, false, true, ROT, TP>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
+  else if (warm && trunk) hipLaunchKernelGGL((wbc_tick_sim3p_kernel<true, true, false, ROT, TP>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
+  else if (trunk) hipLaunchKernelGGL((wbc_tick_sim3p_kernel<false, true, false, ROT, TP>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
+  else if (warm) hipLaunchKernelGGL((wbc_tick_sim3p_kernel<true, false, false, ROT, TP>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
+  else hipLaunchKernelGGL((wbc_tick_sim3p_kernel<false, false, false, ROT, TP>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
 }
 int launch_tick_sim3p(const KernelArgs& a, void* stream, const WbcTaskParams* tp) {
-  if (a.rot) launch_sim3p_variant<true>(a, stream, tp);
-  else launch_sim3p_variant<false>(a, stream, tp);
+  if (a.rot) tp ? launch_sim3p_variant<true, true>(a, stream, tp) : launch_sim3p_variant<true, false>(a, stream, tp);
+  else tp ? launch_sim3p_variant<false, true>(a, stream, tp) : launch_sim3p_variant<false, false>(a, stream, tp);
   return check_launch("tick_sim3p");
 }
 int sim3p_lds_bytes() { return (int)sizeof(SmemP); }
 #endif
 
 }  // namespace wbc
-#endif
