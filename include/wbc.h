@@ -358,6 +358,11 @@ int wbc_rollout_tp(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams
  *                          redone by its own wave on the general path at the end of the same kernel); 0: one instance per wavefront
  *                          (wbc_tick_sim3_kernel + second pass). Also gates "packed_orth", "packed_box" and the packed QP kernel of
  *                          wbc_qp_solve / wbc_qp_solve_ls (0: one problem per wavefront there too).
+ *   "wave_order"       [1] the packed sim3 kernel records how many dual iterations each instance needed, and the next launch on the
+ *                          handle groups instances of like work into the same wavefronts, heaviest first (wbc_rollout carries it from
+ *                          tick to tick; a changed batch size or wbc_batch_configure gives one launch in the identity order), from
+ *                          16384 instances on (below, one round of waves has nothing to regroup and the bookkeeping costs 2-5 us);
+ *                          2: at every batch size up to 130048; 0: the identity order (A/B timing). Results are bit-identical either way.
  *   "packed_orth"      [1] the equality-only task problems (BASELINE configs[1]: EE tasks + CoM task + posture Tikhonov / PREV, foot
  *                          contacts the only constraints, no velocity box) run FOUR instances per wavefront on wbc_tick_orthp_kernel
  *                          (orthonormal contact presolve, unconstrained reduced problem) from 4608 instances on — below that one round
@@ -428,7 +433,9 @@ int wbc_batch_set_option(WbcBatch* b, const char* name, int value);
  * "last_update_packed" (1: the last state update ran on the packed kernel), "last_posture_par" (1 / 2: the last MANI / HYBRID posture target
  * ran on the parallel posture kernel, one / three instances per wavefront), "deferred_last" (instances the last tick's kernel could not reduce itself: redone in the packed kernels'
  * tail or left to the one-instance kernel's second pass; waits for `stream`), "pivoted_last" (instances that took the pivoted
- * elimination, with option "count_pivoted"), "sim3_lds_bytes" / "tick_lds_bytes" / "orthp_lds_bytes" (LDS per workgroup of the tick kernels). */
+ * elimination, with option "count_pivoted"), "wave_order_slices" (slices of waves whose recorded order the next packed sim3 launch at
+ * the last such launch's batch size will read: ceil(ceil(B / 4) / 127) once the order is in effect, 0 without it; waits for `stream`),
+ * "sim3_lds_bytes" / "tick_lds_bytes" / "orthp_lds_bytes" (LDS per workgroup of the tick kernels). */
 int wbc_batch_get_stat(WbcBatch* b, const char* name, void* stream, int64_t* out);
 
 /* wait for everything queued by this handle on `stream`. */

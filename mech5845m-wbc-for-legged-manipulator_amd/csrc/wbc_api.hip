@@ -31,6 +31,10 @@ struct WbcModel {
 // The packed sim3 kernel's batch-size policy (tools/small_batch.py, profiles/r04_small_batch_c3.txt): below this many instances a launch is a
 // single partial round of waves and one tick's latency is what counts.
 constexpr int WBC_SIM3P_MIN_BATCH = 1;
+// The packed sim3 kernel's wave order (option "wave_order" 1) from this many instances on: it costs a launch a dependent load at entry and a
+// returning atomic at exit, 2-5 us at B = 1 .. 4096 (one partial round of waves, nothing to regroup), neutral at 8192, -21 % at 16384
+// (tools/small_batch.py, profiles/r07_small_batch_c3_wave_order.txt).
+constexpr int WBC_WAVE_ORDER_MIN_BATCH = 16384;
 
 struct WbcBatch {
   int device_id, n_models, max_batch, grid;
@@ -60,6 +64,11 @@ struct WbcBatch {
   int warm_start;        // 1: wbc_rollout carries each instance's working set from tick to tick (default 0: measured slower)
   int32_t* d_defer;      // [1 + max_batch]: count + compact list of the instances the sim3 kernel deferred (lazy)
   unsigned long long* d_dstat;   // packed kernel: (launch sequence, instances its tail redid on the general path) (lazy)
+  int wave_order;        // 1 (default): the packed sim3 kernel deals instances out by last launch's work (KernelArgs.worder) from WBC_WAVE_ORDER_MIN_BATCH
+                         // instances on; 2: at every batch size; 0: identity order
+  WaveOrder* d_worder;   // that order: slice blocks and two lists per slice (lazy)
+  int worder_reset;      // wbc_batch_configure was called: the next launch that uses the order clears it first, on its own stream
+  int worder_B;          // batch size of the last packed sim3 launch that used the order (0: none; statistic "wave_order_slices")
   uint32_t tick_seq;
   int packed_update, last_update_packed;   // option: wbc_update_packed_kernel where every plan allows it [1]; what the last update ran on
   int last_orth;         // the last general-kernel tick ran the variant with the orthonormal contact presolve
@@ -181,7 +190,7 @@ extern "C" int wbc_batch_create(const WbcModel* const* models, int n_models, int
   WbcBatch* b = new (std::nothrow) WbcBatch;
   if (!b) return fail(WBC_E_ARG, "out of memory");
   memset(b, 0, sizeof *b);
-  b->device_id = device_id; b->n_models = n_models; b->max_batch = max_batch; b->presolve = 1; b->presolve_orth = 1; b->packed_update = 1; b->sim3_kernel = 1; b->sing_tol = 1e-7;
+  b->device_id = device_id; b->n_models = n_models; b->max_batch = max_batch; b->presolve = 1; b->presolve_orth = 1; b->packed_update = 1; b->sim3_kernel = 1; b->sing_tol = 1e-7; b->wave_order = 1;
   b->jtj_mfma = -1; b->refine = 1; b->packed_min_batch = WBC_SIM3P_MIN_BATCH; b->warm_start = 0; b->packed_kernel = 1; b->packed_orth = 1; b->packed_box = 1; b->posture_par = 1;
   std::vector<DevModel> dm(n_models);
   for (int i = 0; i < n_models; ++i) {
@@ -228,6 +237,7 @@ extern "C" void wbc_batch_destroy(WbcBatch* b) {
   if (b->d_status) (void)hipFree(b->d_status);
   if (b->d_defer) (void)hipFree(b->d_defer);
   if (b->d_dstat) (void)hipFree(b->d_dstat);
+  if (b->d_worder) (void)hipFree(b->d_worder);
   delete b;
 }
 
@@ -628,6 +638,7 @@ extern "C" int wbc_batch_configure(WbcBatch* b, int mi, const WbcConfig* cfg) {
   build_plan(b->models[mi]->dev, *cfg, p, &plan);
   b->plan_host[mi] = plan;
   HIP_TRY(hipMemcpy(b->d_plans + mi, &plan, sizeof plan, hipMemcpyHostToDevice));
+  b->worder_reset = 1;                     // the next packed tick runs in the identity order (cleared on that tick's stream)
   return WBC_OK;
 }
 
@@ -644,6 +655,7 @@ extern "C" int wbc_batch_set_option(WbcBatch* b, const char* name, int value) {
   if (!strcmp(name, "presolve_tol_exp")) { double t = 1.0; for (int i = 0; i < value; ++i) t *= 0.1; b->sing_tol = t; return WBC_OK; }
   if (!strcmp(name, "sim3_kernel")) { b->sim3_kernel = value; return WBC_OK; }
   if (!strcmp(name, "packed_kernel")) { b->packed_kernel = value; return WBC_OK; }
+  if (!strcmp(name, "wave_order")) { b->wave_order = value < 0 ? 0 : (value > 2 ? 2 : value); return WBC_OK; }
   if (!strcmp(name, "packed_min_batch")) { b->packed_min_batch = value < 1 ? 1 : value; return WBC_OK; }
   if (!strcmp(name, "packed_orth")) { b->packed_orth = value; return WBC_OK; }
   if (!strcmp(name, "packed_box")) { b->packed_box = value; return WBC_OK; }
@@ -696,6 +708,15 @@ extern "C" int wbc_batch_get_stat(WbcBatch* b, const char* name, void* stream, i
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     HIP_TRY(hipMemcpy(&c, b->d_defer + 1 + b->max_batch, sizeof c, hipMemcpyDeviceToHost));
     *out = c;
+    return WBC_OK;
+  }
+  if (!strcmp(name, "wave_order_slices")) {  // slices whose published order the next launch of the last packed sim3 batch size reads; waits for `stream`
+    *out = 0;
+    if (!b->d_worder || !b->worder_B || b->last_path != 2) return WBC_OK;
+    std::vector<WaveOrder> sl(WO_NS);
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    HIP_TRY(hipMemcpy(sl.data(), b->d_worder, WO_NS * sizeof(WaveOrder), hipMemcpyDeviceToHost));
+    for (const WaveOrder& w : sl) *out += w.B == (uint32_t)b->worder_B;
     return WBC_OK;
   }
   if (!strcmp(name, "sim3_lds_bytes")) { *out = sim3_lds_bytes(); return WBC_OK; }
@@ -972,6 +993,21 @@ static int launch_tick_auto(WbcBatch* b, KernelArgs& a, int B, void* stream, con
     b->last_path = 2;
     if ((rc = prepare_tick(b, a, stream, true))) return rc;   // (the status buffer is in place already)
     a.packed_trunk = b->cfg_host[0].task_trunk != 0;
+    if ((b->wave_order == 2 || (b->wave_order == 1 && a.B >= WBC_WAVE_ORDER_MIN_BATCH)) && !b->dbg_stop) {   // (an ablation cut returns before the kernel records its instances; batches above 130048: identity)
+      if (!b->d_worder) {
+        const size_t bytes = wave_order_bytes(b->max_batch);
+        if (bytes) {
+          HIP_TRY(hipMalloc((void**)&b->d_worder, bytes));
+          b->worder_reset = 1;
+        }
+      }
+      if (b->d_worder && b->worder_reset) {   // (on the CALL's stream: ordered after any tick still running on it)
+        HIP_TRY(hipMemsetAsync(b->d_worder, 0, WO_NS * sizeof(WaveOrder), (hipStream_t)stream));
+        b->worder_reset = 0;
+      }
+      a.worder = b->d_worder;
+    }
+    b->worder_B = a.worder ? a.B : 0;
     if (int e = launch_tick_sim3p(a, stream, tp)) return fail(WBC_E_HIP, "packed sim3 tick kernel launch failed: %s", hipGetErrorString((hipError_t)e));
     return WBC_OK;
   }

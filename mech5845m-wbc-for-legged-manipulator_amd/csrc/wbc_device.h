@@ -104,6 +104,30 @@ struct DevPlan {
 
 enum Mode : int { MODE_TICK = 0, MODE_ASSEMBLE = 1, MODE_FK = 2 };
 
+// The packed sim3 kernel's wave order (option "wave_order"): each launch appends every instance to the list of its work class
+// (the dual iterations it ran, heaviest class first) and publishes the concatenated classes as the next launch's order, so that the next tick of
+// the same robots groups heavy instances into the same waves and dispatches those waves first. The order is kept per SLICE of waves (wave grp
+// is wave grp / ns of slice grp mod ns, ns = ceil(waves / WO_SW)), each slice with its own block on its own 128-byte line and ONE returning
+// atomic per wave on it: device atomics on one word serialise (about 90 per microsecond), and a few per wave on a single word cost 0.5 ms per
+// 65536-tick launch. One allocation per handle: WO_NS slice blocks, then the lists uint32 [2][WO_NS][WO_NCLS][WO_CAP] (instance indices; list
+// `cur` of a slice holds its order, the launch in flight appends to the other one).
+constexpr int WO_NCLS = 6;                 // work classes
+constexpr int WO_SW = 127;                 // waves per slice at most (a class count fits the 9 bits of its field)
+constexpr int WO_CAP = 4 * WO_SW;          // instances per slice at most
+constexpr int WO_NS = 256;                 // slices at most: the order covers batches up to 4 WO_SW WO_NS = 130048 instances
+struct WaveOrder {
+  unsigned long long word[2];        // per list: bits 9 c .. 9 c + 8 the instances appended to class c, bits 54.. the waves done (list 1 - cur: 0)
+  uint32_t cur;                      // 0 / 1: the list that holds the slice's order
+  uint32_t B;                        // batch size that order was built for (0: none — the identity order)
+  uint32_t off[8];                   // first position (inside the slice) of class c in the concatenated lists of `cur` (off[0] = 0)
+  uint32_t pad_[18];
+};
+static_assert(sizeof(WaveOrder) == 128, "one slice block per 128-byte line");
+inline size_t wave_order_bytes(int max_batch) {
+  const int ns = ((max_batch + 3) / 4 + WO_SW - 1) / WO_SW;
+  return ns > WO_NS ? 0 : WO_NS * sizeof(WaveOrder) + sizeof(uint32_t) * 2 * WO_NS * WO_NCLS * (size_t)WO_CAP;
+}
+
 struct KernelArgs {
   const DevModel* models;
   const WbcConfig* cfgs;
@@ -138,6 +162,7 @@ struct KernelArgs {
   WbcQpData qp;
   WbcFkOut fk;
   int32_t rot;                      // a model of the handle has a rotated joint placement: the packed kernels' ROT instantiations run
+  WaveOrder* worder;                 // packed sim3 kernel: the handle's wave order (option "wave_order", default on), or null (identity order)
 };
 
 // The kernel parameters of every tick kernel (wbc_tick_kernel, wbc_tick_sim3p / orthp / boxp_kernel): KernelArgs, the three tables, then the

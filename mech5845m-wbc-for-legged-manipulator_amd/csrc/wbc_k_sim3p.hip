@@ -53,10 +53,11 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
   //  even with a clean register allocation (opaque lane index + -mllvm -disable-machine-licm; without them the hoisted invariants spill 139 loads /
   //  91 stores into the packed path): profiles/r04_ab_licm_iters.txt. The first round of a launch costs twice a steady-state round — all waves
   //  stall on their inputs at once — and fewer, longer waves do not change that.)
+  // row r of group grp takes instance 4 grp + r, or the one the handle's wave order puts there (wbc_packed.h wo_instance)
   const int grp = (int)blockIdx.x;
-  const int b_raw = 4 * grp + r;
-  const bool valid = b_raw < A.B;
-  const int b = valid ? b_raw : A.B - 1;
+  const int pos = 4 * grp + r;
+  const bool valid = pos < A.B;
+  const int b = valid ? wo_instance(A.worder, A.B, grp, r, pos) : A.B - 1;
   int mid = 0;
   if (A.in.model_id) { mid = A.in.model_id[b]; mid = mid < 0 ? 0 : (mid >= A.n_models ? A.n_models - 1 : mid); }
   const DevModel& M = models[mid];
@@ -1298,6 +1299,7 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
       if (s < NQ - nq) qn[nq + s] = 0.0;
     }
   }
+  if (A.worder) wo_record(A.worder, A.B, grp, valid, b, wo_class(iters, flagged), r, s);   // (this launch's record: the next launch's order)
   // ---- the tail: an instance left out above (a stance-leg block of rank < 2 — never seen on the benchmark distribution — or the
   // diagnostic dbg_force_defer) is redone here, by this wave, on the general path (process_instance, one instance per wavefront, LDS
   // shared with the packed layout). No list, no second launch, and a batch that defers everything runs at the general kernel's occupancy.
@@ -1308,7 +1310,7 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
 #pragma unroll 1
     for (int rr = 0; rr < 4; ++rr) {
       if (!((tailm >> (16 * rr)) & 1ull)) continue;
-      tail_instance<WARM, false, ROT, TP>(&SU.G, 4 * grp + rr, models, cfgs, plans);
+      tail_instance<WARM, false, ROT, TP>(&SU.G, __builtin_amdgcn_readlane(b, 16 * rr), models, cfgs, plans);
     }
   }
 #endif

@@ -120,6 +120,76 @@ __device__ __forceinline__ double chol_sweep2(double (&h)[N], double (&y)[N], do
   return pmin;
 }
 
+// ---- the wave order (KernelArgs.worder, wbc_device.h WaveOrder). A wave runs as many dual passes as the slowest of its four rows:
+// each launch records how many iterations every instance needed, and the next launch on the same handle deals the instances out heaviest class first,
+// so that heavy rows share waves and those waves start first. Results do not depend on it: an instance's arithmetic does not depend on its wave or row.
+// Wave grp is wave k = grp / ns of slice grp mod ns (ns = ceil(waves / WO_SW)); its row r holds position j = 4 k + r of the slice's order.
+// Work class of an instance from the dual iterations it ran, 0 the heaviest (>= 10, or redone by the kernel's tail) .. 5 (none).
+__device__ __forceinline__ int wo_class(const int iters, const bool tail) {
+  return (tail || iters >= 10) ? 0 : iters >= 6 ? 1 : iters >= 3 ? 2 : 5 - iters;
+}
+__device__ __forceinline__ uint32_t* wo_list(WaveOrder* wo, const uint32_t l, const int g, const int c) {
+  return reinterpret_cast<uint32_t*>(wo + WO_NS) + ((size_t)(l * WO_NS + g) * WO_NCLS + c) * WO_CAP;
+}
+__device__ __forceinline__ int wo_slices() { return ((int)gridDim.x + WO_SW - 1) / WO_SW; }
+// The instance row r of wave grp takes: the identity (pos = 4 grp + r < B) unless the slice's order was built for this batch size. The slice's
+// block is wave-uniform (scalar loads at kernel entry); the index is read from the list of the position's class.
+__device__ __forceinline__ int wo_instance(WaveOrder* __restrict__ wo, const int B, const int grp, const int r, const int pos) {
+  const int ns = wo_slices();
+  if (!wo || ns > WO_NS) return pos;
+  const int g = grp % ns;
+  const WaveOrder& sl = wo[g];
+  if (sl.B != (uint32_t)B) return pos;
+  const uint32_t cur = sl.cur & 1u, j = 4u * (uint32_t)(grp / ns) + (uint32_t)r;
+  uint32_t k = 0, base = 0;
+#pragma unroll
+  for (int c = 1; c < WO_NCLS; ++c) {
+    const uint32_t o = sl.off[c];
+    if (j >= o) { k = c; base = o; }
+  }
+  const uint32_t i = wo_list(wo, cur, g, k)[min(j - base, (uint32_t)WO_CAP - 1u)];      // (base <= j < 4 WO_SW)
+  return i < (uint32_t)B ? (int)i : B - 1;
+}
+// Append the wave's instances to its slice's class lists that the next launch reads and count the wave done: ONE returning 64-bit atomicAdd per
+// wave carries both (the old word gives each row its place in its class list). The slice's last wave publishes the slice's order — prefix
+// offsets from the final word, the list, the batch size it was built for, or 0 if the slice did not count each of its instances once — and zeroes
+// the word the next launch will append to. No host sequence number: a captured graph replays this as it is. The lists are read by the next launch
+// only. `valid`: the row holds an instance (b, class cls: uniform over the row).
+__device__ __forceinline__ void wo_record(WaveOrder* wo, const int B, const int grp, const bool valid, const int b, const int cls, const int r,
+                                          const int s) {
+  const int ns = wo_slices(), G = (int)gridDim.x;
+  if (ns > WO_NS) return;
+  const int g = grp % ns;
+  WaveOrder& sl = wo[g];
+  const uint32_t cur = sl.cur & 1u, nxt = cur ^ 1u;
+  const unsigned long long vm = __ballot(valid && s == 0);
+  unsigned same = 0u;
+  unsigned long long add = 1ull << 54;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int ck = __builtin_amdgcn_readlane(cls, 16 * k);
+    const bool vk = (vm >> (16 * k)) & 1ull;
+    same |= (vk && ck == cls) ? 1u << k : 0u;
+    add += vk ? 1ull << (9 * ck) : 0ull;
+  }
+  unsigned long long old = 0ull;
+  if (r == 0 && s == 0) old = atomicAdd(&sl.word[nxt], add);
+  old = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(old >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)old);
+  const uint32_t at = (uint32_t)((old >> (9 * cls)) & 511ull) + (uint32_t)__popc(same & ((1u << r) - 1u));
+  if (valid && s == 0 && at < WO_CAP) wo_list(wo, nxt, g, cls)[at] = (uint32_t)b;
+  const uint32_t nwaves = (uint32_t)((G - g + ns - 1) / ns);                     // waves of slice g
+  if (r == 0 && s == 0 && (uint32_t)(old >> 54) == nwaves - 1u) {
+    const unsigned long long fin = old + add;
+    uint32_t n = 0u;
+#pragma unroll
+    for (int c = 0; c < WO_NCLS; ++c) { sl.off[c] = n; n += (uint32_t)((fin >> (9 * c)) & 511ull); }
+    const uint32_t expect = 4u * nwaves - ((g == (G - 1) % ns) ? (uint32_t)(4 * G - B) : 0u);   // (the batch's last wave may be short)
+    sl.B = (n == expect) ? (uint32_t)B : 0u;
+    sl.cur = nxt;
+    sl.word[cur] = 0ull;
+  }
+}
+
 // shared by the packed orth and box kernels: FK levels of their whole-tree schedule (DevPlan.q_fk) and the staged weights image wt [96]
 constexpr int QLEV = 6;
 static_assert(offsetof(WbcConfig, joint_w) - offsetof(WbcConfig, ee_W) == 84 * sizeof(double), "ee_W [30] ee_w [5] ee_gain [30] trunk [13] com_W [3] com_gain [3] joint_w");
