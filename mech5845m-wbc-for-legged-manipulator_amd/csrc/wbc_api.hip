@@ -23,6 +23,9 @@ static int fail(int code, const char* fmt, ...) {
     if (e_ != hipSuccess) return fail(WBC_E_HIP, "%s: %s", #expr, hipGetErrorString(e_));   \
   } while (0)
 
+// the kernels a tick runs on (select_tick_path); the values are those of the statistic "last_path"
+enum TickPath : int { TICK_GENERAL = 0, TICK_SIM3 = 1, TICK_SIM3P = 2, TICK_ORTHP = 3, TICK_BOXP = 4 };
+
 struct WbcModel {
   WbcModelBlob blob;
   DevModel dev;
@@ -73,7 +76,7 @@ struct WbcBatch {
   int packed_update, last_update_packed;   // option: wbc_update_packed_kernel where every plan allows it [1]; what the last update ran on
   int last_orth;         // the last general-kernel tick ran the variant with the orthonormal contact presolve
   int last_qp_path;      // problems per wavefront of the last wbc_qp_solve / wbc_qp_solve_ls: 1 (wbc_qp_kernel), 2 or 4 (wbc_qp_packed_kernel)
-  int last_path;         // kernel the last wbc_tick / wbc_rollout tick ran on: 0 general, 1 sim3 (+ deferred pass), 2 packed sim3, 3 packed orth, 4 packed box
+  int last_path;         // TickPath of the last wbc_tick / wbc_rollout tick: 0 general, 1 sim3 (+ deferred pass), 2 packed sim3, 3 packed orth, 4 packed box
   int max_nj, max_nf;    // FK output strides: the largest model's joint / frame counts
   int rot;               // a model of the handle has a rotated joint placement: the packed kernels run their ROT instantiations
   unsigned long long* d_prof;
@@ -683,10 +686,10 @@ extern "C" int wbc_batch_get_stat(WbcBatch* b, const char* name, void* stream, i
   if (!strcmp(name, "last_qp_path")) { *out = b->last_qp_path; return WBC_OK; }
   if (!strcmp(name, "last_update_packed")) { *out = b->last_update_packed; return WBC_OK; }
   if (!strcmp(name, "last_posture_par")) { *out = b->last_posture_par; return WBC_OK; }
-  if (!strcmp(name, "last_orth")) { *out = (b->last_path == 0 || b->last_path == 3) ? b->last_orth : 0; return WBC_OK; }
+  if (!strcmp(name, "last_orth")) { *out = (b->last_path == TICK_GENERAL || b->last_path == TICK_ORTHP) ? b->last_orth : 0; return WBC_OK; }
   if (!strcmp(name, "deferred_last")) {      // waits for `stream`
     *out = 0;
-    if (b->last_path >= 2) {                 // packed kernels: instances the tail redid on the general path in the last launch
+    if (b->last_path >= TICK_SIM3P) {       // packed kernels: instances the tail redid on the general path in the last launch
       if (!b->d_dstat) return WBC_OK;
       unsigned long long v = 0;
       HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
@@ -694,7 +697,7 @@ extern "C" int wbc_batch_get_stat(WbcBatch* b, const char* name, void* stream, i
       *out = ((uint32_t)(v >> 32) == b->tick_seq) ? (int64_t)(v & 0xFFFFFFFFull) : 0;
       return WBC_OK;
     }
-    if (!b->d_defer || !b->last_path) return WBC_OK;
+    if (!b->d_defer || b->last_path == TICK_GENERAL) return WBC_OK;
     int32_t c = 0;
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     HIP_TRY(hipMemcpy(&c, b->d_defer + 1 + b->max_batch + 2, sizeof c, hipMemcpyDeviceToHost));
@@ -703,7 +706,7 @@ extern "C" int wbc_batch_get_stat(WbcBatch* b, const char* name, void* stream, i
   }
   if (!strcmp(name, "pivoted_last")) {       // needs option "count_pivoted"; waits for `stream`
     *out = 0;
-    if (!b->d_defer || !b->last_path || !b->count_pivoted) return WBC_OK;
+    if (!b->d_defer || b->last_path == TICK_GENERAL || !b->count_pivoted) return WBC_OK;
     int32_t c = 0;
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     HIP_TRY(hipMemcpy(&c, b->d_defer + 1 + b->max_batch, sizeof c, hipMemcpyDeviceToHost));
@@ -712,7 +715,7 @@ extern "C" int wbc_batch_get_stat(WbcBatch* b, const char* name, void* stream, i
   }
   if (!strcmp(name, "wave_order_slices")) {  // slices whose published order the next launch of the last packed sim3 batch size reads; waits for `stream`
     *out = 0;
-    if (!b->d_worder || !b->worder_B || b->last_path != 2) return WBC_OK;
+    if (!b->d_worder || !b->worder_B || b->last_path != TICK_SIM3P) return WBC_OK;
     std::vector<WaveOrder> sl(WO_NS);
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     HIP_TRY(hipMemcpy(sl.data(), b->d_worder, WO_NS * sizeof(WaveOrder), hipMemcpyDeviceToHost));
@@ -879,16 +882,20 @@ static void fill_args(KernelArgs& a, const WbcBatch* b, int B, double dt) {
   a.fk_nj = b->max_nj; a.fk_nf = b->max_nf;
 }
 
-// The fused tick on the best kernel for the batch: wbc_tick_sim3_kernel (compact LDS, reduced QP only) when every
-// model's plan is enabled and the problem fits its layout, followed by wbc_tick_deferred_kernel (general path) over
-// the instances it deferred (singular leg block); otherwise the general kernel alone. `a` holds device pointers.
-static int launch_update_auto(WbcBatch* b, UpdateArgs& u, int B, void* stream) {
+// What a launcher (wbc_k_*.hip) returned (0, a hipError_t, or WBC_E_UNSUPPORTED: its variant table holds no kernel for the call's flags) -> ours
+static int launch_rc(int e, const char* what) {
+  if (e == WBC_E_UNSUPPORTED) return fail(e, "%s kernel: no variant of it is built for this combination of inputs", what);
+  return e ? fail(WBC_E_HIP, "%s kernel launch failed: %s", what, hipGetErrorString((hipError_t)e)) : WBC_OK;
+}
+static int launch_update_auto(WbcBatch* b, UpdateArgs& u, int B, void* stream) {   // the state update of wbc_update / wbc_rollout: four instances per wavefront where every plan allows it
   bool packed = b->packed_update != 0;
   for (int i = 0; i < b->n_models && packed; ++i) packed = b->configured[i] && b->plan_host[i].pk_update_ok != 0;
   u.plans = b->d_plans;
   b->last_update_packed = packed;
   return packed ? launch_update_packed(u, stream) : launch_update(u, B, stream);
 }
+// ---- The fused tick (wbc_tick, every tick of wbc_rollout): launch_tick_auto selects one of the five paths (select_tick_path: no side effects),
+// records it for the statistics, prepares what that path's kernels read and nothing else (prepare_tick), and launches. `a` holds device pointers.
 static bool packed_eligible(const WbcBatch* b, const KernelArgs& a) {
   const bool qcon = a.in.q_con || a.in.posture_u;     // the QCON variant (second kinematics pass at q_con, posture target from posture_u)
   bool packed = b->packed_kernel && a.B >= b->packed_min_batch &&
@@ -896,11 +903,10 @@ static bool packed_eligible(const WbcBatch* b, const KernelArgs& a) {
   for (int i = 0; i < b->n_models && packed; ++i) packed = qcon ? (b->plan_host[i].packed_ok_pu != 0) : (b->plan_host[i].packed_ok != 0);
   return packed;
 }
-static bool sim3_eligible(const WbcBatch* b, const KernelArgs& a) {
+static bool sim3_eligible(const WbcBatch* b, const KernelArgs& a) {   // the sim3 switch-set family (compact LDS, reduced QP only): every plan enabled, the problem fits the layout
   if (!b->sim3_kernel || !b->presolve || b->n_models < 1) return false;
   if (b->jtj_mfma > 0) return false;   // forced: the compact kernel has no matrix-core contraction, the option selects the general kernel
   if (a.in.com_target || a.in.com_target_vel) return false;
-  if (a.in.ee_ref_rot && !packed_eligible(b, a)) return false;   // orientation references: the packed kernel honours the gripper's, the one-instance compact kernel none
   if (b->prows > WBC_SIM3_MAXP || b->mcart > 12) return false;
   for (int i = 0; i < b->n_models; ++i) {
     const DevPlan& P = b->plan_host[i];
@@ -932,66 +938,49 @@ static bool boxp_eligible(const WbcBatch* b, const KernelArgs& a) {
   for (int i = 0; i < b->n_models; ++i) if (!b->plan_host[i].x_ok) return false;
   return true;
 }
-// What the compact and packed kernels need before a launch: a status buffer when the caller passed none; with `packed` also the word of the
-// "deferred_last" statistic (the instances a packed kernel's tail redid) and this launch's sequence number (0 is the cleared word's).
-static int prepare_tick(WbcBatch* b, KernelArgs& a, void* stream, bool packed) {
-  if (!a.out.status) {
+static TickPath select_tick_path(const WbcBatch* b, const KernelArgs& a, const WbcTaskParams* tp) {
+  if (boxp_eligible(b, a)) return TICK_BOXP;
+  if (orthp_eligible(b, a)) return TICK_ORTHP;
+  if (!sim3_eligible(b, a)) return TICK_GENERAL;
+  if (packed_eligible(b, a)) return TICK_SIM3P;
+  // What the packed kernel does not take runs on the one-instance compact kernel, unless the call asks for what that kernel does not have. Orientation
+  // references: the packed kernel honours the gripper's, the compact kernel none. The refinement (default on): the compact kernel lives on 168 VGPRs /
+  // 13.2 KB LDS (3 waves per SIMD) and has room neither for the task image nor for the Jacobian columns the residual is formed from; the general kernel's
+  // structural presolve solves the same reduced problem and refines it (refine = 0 brings the compact kernel back). Per-instance weights: it has no TP variant.
+  if (a.in.ee_ref_rot || b->refine > 0 || tp) return TICK_GENERAL;
+  return TICK_SIM3;
+}
+
+// What the kernels of `path` read, and nothing else. Paths 1-4: a status buffer when the caller passed none. The packed kernels (2-4): the word of
+// the "deferred_last" statistic (the instances a packed kernel's tail redid) and this launch's sequence number (0 is the cleared word's).
+static int prepare_tick(WbcBatch* b, KernelArgs& a, void* stream, TickPath path) {
+  if (path != TICK_GENERAL && !a.out.status) {
     if (!b->d_status) HIP_TRY(hipMalloc((void**)&b->d_status, sizeof(int32_t) * (size_t)b->max_batch));
     a.out.status = b->d_status;
   }
-  if (!packed) return WBC_OK;
-  if (!b->d_dstat) {
-    HIP_TRY(hipMalloc((void**)&b->d_dstat, sizeof(unsigned long long)));
-    HIP_TRY(hipMemsetAsync(b->d_dstat, 0, sizeof(unsigned long long), (hipStream_t)stream));
+  if (path >= TICK_SIM3P) {
+    if (!b->d_dstat) {
+      HIP_TRY(hipMalloc((void**)&b->d_dstat, sizeof(unsigned long long)));
+      HIP_TRY(hipMemsetAsync(b->d_dstat, 0, sizeof(unsigned long long), (hipStream_t)stream));
+    }
+    a.defer_stat = b->d_dstat;
+    a.tick_seq = ++b->tick_seq;
+    if (!b->tick_seq) a.tick_seq = ++b->tick_seq;
   }
-  a.defer_stat = b->d_dstat;
-  a.tick_seq = ++b->tick_seq;
-  if (!b->tick_seq) a.tick_seq = ++b->tick_seq;
-  return WBC_OK;
-}
-static int launch_tick_auto(WbcBatch* b, KernelArgs& a, int B, void* stream, const WbcTaskParams* tp = nullptr) {
-  int rc;
-  if (boxp_eligible(b, a)) {    // ONE kernel per tick; last_path 4
-    b->last_path = 4;
-    b->last_orth = 0;
-    if ((rc = prepare_tick(b, a, stream, true))) return rc;
-    if (int e = launch_tick_boxp(a, stream, tp)) return fail(WBC_E_HIP, "packed box tick kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    return WBC_OK;
+  if (path == TICK_SIM3 || path == TICK_SIM3P) a.dbg_force_defer = b->force_defer;
+  if (path == TICK_SIM3) {    // the list of the instances the compact kernel leaves to the deferred pass, the pivot counter
+    if (!b->d_defer) {
+      HIP_TRY(hipMalloc((void**)&b->d_defer, sizeof(int32_t) * ((size_t)b->max_batch + 4)));
+      HIP_TRY(hipMemsetAsync(b->d_defer, 0, sizeof(int32_t) * ((size_t)b->max_batch + 4), (hipStream_t)stream));   // (on the CALL's stream: a null-stream memset is not ordered against a non-blocking caller stream)
+    }
+    a.defer = b->d_defer;                                  // (count = 0 here: wbc_tick_deferred_kernel leaves the list empty behind it)
+    a.defer_aux = b->d_defer + 1 + b->max_batch;
+    if (b->count_pivoted) {
+      a.pivot_count = b->d_defer + 1 + b->max_batch;
+      HIP_TRY(hipMemsetAsync(a.pivot_count, 0, sizeof(int32_t), (hipStream_t)stream));
+    }
   }
-  if (orthp_eligible(b, a)) {   // ONE kernel per tick; last_path 3
-    b->last_path = 3;
-    b->last_orth = 1;
-    if ((rc = prepare_tick(b, a, stream, true))) return rc;
-    if (int e = launch_tick_orthp(a, stream, b->plan_host[0].q_ok == 2, tp)) return fail(WBC_E_HIP, "packed orth tick kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    return WBC_OK;
-  }
-  // The one-instance compact kernel (path 1) does not refine: it lives on 168 VGPRs / 13.2 KB LDS (3 waves per SIMD) and has room neither for the
-  // task image nor for the Jacobian columns the residual is formed from. With the refinement on (default) what the packed kernel does not take
-  // runs on the general kernel, whose structural presolve solves the same reduced problem and refines it (option refine = 0 brings path 1 back).
-  // per-instance weights (wbc_tick_tp): the one-instance compact kernel has no TP variant — what the packed kernel does not take runs here too
-  if (!sim3_eligible(b, a) || ((b->refine > 0 || tp) && !packed_eligible(b, a))) {
-    b->last_path = 0;
-    b->last_orth = a.presolve && a.presolve_orth == 2 && !(a.ws_in || a.ws_out);
-    if (int e = launch_tick(a, MODE_TICK, grid_tick(b, B), stream, tp)) return fail(WBC_E_HIP, "tick kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    return WBC_OK;
-  }
-  b->last_path = 1;
-  if ((rc = prepare_tick(b, a, stream, false))) return rc;
-  if (!b->d_defer) {
-    HIP_TRY(hipMalloc((void**)&b->d_defer, sizeof(int32_t) * ((size_t)b->max_batch + 4)));
-    // (on the CALL's stream: a null-stream memset is not ordered against a non-blocking caller stream)
-    HIP_TRY(hipMemsetAsync(b->d_defer, 0, sizeof(int32_t) * ((size_t)b->max_batch + 4), (hipStream_t)stream));
-  }
-  a.defer = b->d_defer;                                  // (count = 0 here: wbc_tick_deferred_kernel leaves the list empty behind it)
-  a.defer_aux = b->d_defer + 1 + b->max_batch;
-  a.dbg_force_defer = b->force_defer;
-  if (b->count_pivoted) {
-    a.pivot_count = b->d_defer + 1 + b->max_batch;
-    HIP_TRY(hipMemsetAsync(a.pivot_count, 0, sizeof(int32_t), (hipStream_t)stream));
-  }
-  if (packed_eligible(b, a)) {   // ONE kernel per tick: what the packed kernel cannot reduce its own wave redoes on the general path
-    b->last_path = 2;
-    if ((rc = prepare_tick(b, a, stream, true))) return rc;   // (the status buffer is in place already)
+  if (path == TICK_SIM3P) {   // the trunk task's variant, the wave order
     a.packed_trunk = b->cfg_host[0].task_trunk != 0;
     if ((b->wave_order == 2 || (b->wave_order == 1 && a.B >= WBC_WAVE_ORDER_MIN_BATCH)) && !b->dbg_stop) {   // (an ablation cut returns before the kernel records its instances; batches above 130048: identity)
       if (!b->d_worder) {
@@ -1008,16 +997,27 @@ static int launch_tick_auto(WbcBatch* b, KernelArgs& a, int B, void* stream, con
       a.worder = b->d_worder;
     }
     b->worder_B = a.worder ? a.B : 0;
-    if (int e = launch_tick_sim3p(a, stream, tp)) return fail(WBC_E_HIP, "packed sim3 tick kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    return WBC_OK;
-  }
-  if (int e = launch_tick_sim3(a, B, stream)) return fail(WBC_E_HIP, "sim3 tick kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-  if (int e = launch_tick_deferred(a, stream)) {
-    // the list the sim3 kernel may have filled stays behind: empty it, or the next tick appends after a stale count
-    (void)hipMemsetAsync(b->d_defer, 0, sizeof(int32_t), (hipStream_t)stream);
-    return fail(WBC_E_HIP, "deferred tick kernel launch failed: %s", hipGetErrorString((hipError_t)e));
   }
   return WBC_OK;
+}
+static int launch_tick_auto(WbcBatch* b, KernelArgs& a, int B, void* stream, const WbcTaskParams* tp = nullptr) {
+  const TickPath path = select_tick_path(b, a, tp);
+  b->last_path = path;
+  if (path == TICK_GENERAL) b->last_orth = a.presolve && a.presolve_orth == 2 && !(a.ws_in || a.ws_out);
+  else if (path >= TICK_ORTHP) b->last_orth = path == TICK_ORTHP;
+  int rc = prepare_tick(b, a, stream, path);
+  if (rc) return rc;
+  switch (path) {   // (the packed kernels: ONE kernel per tick, what a packed kernel cannot reduce its own wave redoes on the general path)
+    case TICK_GENERAL: return launch_rc(launch_tick(a, MODE_TICK, grid_tick(b, B), stream, tp), "tick");
+    case TICK_SIM3P: return launch_rc(launch_tick_sim3p(a, stream, tp), "packed sim3 tick");
+    case TICK_ORTHP: return launch_rc(launch_tick_orthp(a, stream, b->plan_host[0].q_ok == 2, tp), "packed orth tick");
+    case TICK_BOXP: return launch_rc(launch_tick_boxp(a, stream, tp), "packed box tick");
+    case TICK_SIM3: break;   // two kernels, below: the compact one, then the general path over the instances it deferred (singular leg block)
+  }
+  if ((rc = launch_rc(launch_tick_sim3(a, B, stream), "sim3 tick"))) return rc;
+  if ((rc = launch_rc(launch_tick_deferred(a, stream), "deferred tick")))
+    (void)hipMemsetAsync(b->d_defer, 0, sizeof(int32_t), (hipStream_t)stream);   // the list the sim3 kernel may have filled stays behind: empty it, or the next tick appends after a stale count
+  return rc;
 }
 
 // ---------------------------------------------------------------------------------------------- entry points
@@ -1043,7 +1043,7 @@ extern "C" int wbc_fk_jacobians(WbcBatch* b, int B, const double* q, const int32
   st.out(&a.fk.oMi, (size_t)B * nj * 12); st.out(&a.fk.oMf, (size_t)B * nf * 12);
   st.out(&a.fk.J, (size_t)B * 6 * WBC_V_STRIDE); st.out(&a.fk.com, (size_t)B * 3); st.out(&a.fk.Jcom, (size_t)B * 3 * WBC_V_STRIDE);
   if ((rc = st.stage())) return rc;
-  if (int e = launch_tick(a, MODE_FK, grid_tick(b, B), stream)) return fail(WBC_E_HIP, "fk kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+  if ((rc = launch_rc(launch_tick(a, MODE_FK, grid_tick(b, B), stream), "fk"))) return rc;
   return st.finish();
 }
 
@@ -1068,7 +1068,7 @@ extern "C" int wbc_assemble_tp(WbcBatch* b, int B, const WbcTickIn* in, const Wb
   st.out(&a.qp.C, n * p * V); st.out(&a.qp.Clb, n * p); st.out(&a.qp.Cub, n * p); st.out(&a.qp.lb, n * V); st.out(&a.qp.ub, n * V);
   if ((rc = st.stage())) return rc;
   if ((rc = auto_posture(b, a, B, stream))) return rc;
-  if (int e = launch_tick(a, MODE_ASSEMBLE, grid_tick(b, B), stream, tp)) return fail(WBC_E_HIP, "assemble kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+  if ((rc = launch_rc(launch_tick(a, MODE_ASSEMBLE, grid_tick(b, B), stream, tp), "assemble"))) return rc;
   return st.finish();
 }
 
@@ -1240,7 +1240,7 @@ static int qp_common(WbcBatch* b, int B, QpArgs& a, int mem, void* stream, const
   // several problems per wavefront (wbc_k_qpp.hip) unless the call carries working sets (hot start) or option packed_kernel is 0
   const int lanes = b->packed_kernel ? qp_packed_lanes(a) : 0;
   b->last_qp_path = lanes ? lanes : 1;
-  if (int e = lanes ? launch_qp_packed(a, stream) : launch_qp(a, grid_for(b, B), stream)) return fail(WBC_E_HIP, "qp kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+  if ((rc = launch_rc(lanes ? launch_qp_packed(a, stream) : launch_qp(a, grid_for(b, B), stream), "qp"))) return rc;
   return st.finish();
 }
 

@@ -2569,4 +2569,46 @@ static int check_launch(const char* what) {
   return e == hipSuccess ? 0 : (int)e;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Kernel variant tables. A family file (wbc_k_<family>.hip) ends in ONE list of its kernel's variants,
+//   #define FAMILY_VARIANTS(V) V(part, template arguments...) ...
+// and everything that has to know the list is generated from it with the row macros below. csrc/Makefile compiles the file once per part
+// (-D<FAMILY>_PART=k, in parallel; it states each family's part count, -DWBC_NPARTS): a row is instantiated by its own part, part 0 also holds
+// the launcher, and with no part given (-1) the file is a single unit that holds everything. The family file defines WBC_KERNEL (the kernel
+// template), WBC_KPARAMS (its parameter list, parenthesised) and WBC_PART before it uses them.
+//   WBC_VARIANT_INST  explicit instantiation of every row (the single unit)
+//   WBC_VARIANT_UNIT  explicit instantiation of the rows of part WBC_PART, `extern template` declaration of the others
+//   WBC_VARIANT_FIND  inside `kernel_pointer find(long long key)`: returns the row whose arguments are variant_key(...)'s; the launcher reduces
+//                     its call to the arguments it wants and launches what it finds — no row, no launch (WBC_E_UNSUPPORTED)
+// ------------------------------------------------------------------------------------------------
+#ifndef WBC_NPARTS
+#define WBC_NPARTS 9      // (the most WBC_PART_IS_ below can tell apart)
+#endif
+#define WBC_CAT_(a, b) a##b
+#define WBC_CAT(a, b) WBC_CAT_(a, b)
+#define WBC_SECOND_(a, b, ...) b
+#define WBC_SECOND(...) WBC_SECOND_(__VA_ARGS__)
+#define WBC_PART_IS_0_0 ~, 1
+#define WBC_PART_IS_1_1 ~, 1
+#define WBC_PART_IS_2_2 ~, 1
+#define WBC_PART_IS_3_3 ~, 1
+#define WBC_PART_IS_4_4 ~, 1
+#define WBC_PART_IS_5_5 ~, 1
+#define WBC_PART_IS_6_6 ~, 1
+#define WBC_PART_IS_7_7 ~, 1
+#define WBC_PART_IS_8_8 ~, 1
+#define WBC_PART_IS(p, q) WBC_SECOND(WBC_CAT(WBC_PART_IS_, WBC_CAT(p, WBC_CAT(_, q))), 0)   // 1 where the two numbers are the same token
+#define WBC_VARIANT_ROW(p) static_assert(p >= 0 && p < WBC_NPARTS && p < 9, "variant table: part number outside the family's parts (csrc/Makefile)");
+#define WBC_VARIANT_INST(p, ...) WBC_VARIANT_ROW(p) template __global__ void WBC_KERNEL<__VA_ARGS__> WBC_KPARAMS;
+#define WBC_VARIANT_DECL(p, ...) WBC_VARIANT_ROW(p) extern template __global__ void WBC_KERNEL<__VA_ARGS__> WBC_KPARAMS;
+#define WBC_VARIANT_UNIT_1 WBC_VARIANT_INST
+#define WBC_VARIANT_UNIT_0 WBC_VARIANT_DECL
+#define WBC_VARIANT_UNIT(p, ...) WBC_CAT(WBC_VARIANT_UNIT_, WBC_PART_IS(p, WBC_PART))(p, __VA_ARGS__)
+#define WBC_VARIANT_FIND(p, ...) if (key == variant_key(__VA_ARGS__)) return WBC_KERNEL<__VA_ARGS__>;
+constexpr long long variant_key(int a, int b = 0, int c = 0, int d = 0, int e = 0) {   // (template arguments: flags, modes, sizes — all below 256)
+  return ((((long long)a * 256 + b) * 256 + c) * 256 + d) * 256 + e;
+}
+#define WBC_TICK_KPARAMS (const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__, const WbcTaskParams* __restrict__)
+typedef void (*TickKernel) WBC_TICK_KPARAMS;   // the tick kernels with task rows (general, packed sim3 / orth / box)
+
 }  // namespace wbc

@@ -861,52 +861,37 @@ __global__ void __launch_bounds__(64, 2) wbc_tick_boxp_kernel(const KernelArgs A
   }
 }
 
-// One translation unit per PART (csrc/Makefile compiles this file once per part, in parallel): each part instantiates some of the kernel's
-// variants; part 0 also holds the launcher and sees the other parts' variants as explicit-instantiation declarations.
+// The variants (wbc_common.h, "Kernel variant tables"): the part that instantiates the row, then the template arguments. With rows (TP): a part of
+// their own.
 #ifndef BOXP_PART
 #define BOXP_PART -1      // -1: everything in one unit
 #endif
-#define KINST(...) template __global__ void wbc_tick_boxp_kernel<__VA_ARGS__>(const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__, const WbcTaskParams* __restrict__);
-#define KDECL(...) extern template __global__ void wbc_tick_boxp_kernel<__VA_ARGS__>(const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__, const WbcTaskParams* __restrict__);
-#if BOXP_PART == 0 || BOXP_PART == -1
-KINST(false)
+#define WBC_PART BOXP_PART
+#define WBC_KERNEL wbc_tick_boxp_kernel
+#define WBC_KPARAMS WBC_TICK_KPARAMS
+#define BOXP_VARIANTS(V) /* WARM, ROT, TP */ \
+  V(0, false, false, false) \
+  V(1, true, false, false)  \
+  V(2, false, true, false)  \
+  V(2, true, true, false)   \
+  V(3, false, false, true)  \
+  V(3, true, false, true)   \
+  V(3, false, true, true)   \
+  V(3, true, true, true)
+#if BOXP_PART == -1
+BOXP_VARIANTS(WBC_VARIANT_INST)
+#else
+BOXP_VARIANTS(WBC_VARIANT_UNIT)
 #endif
-#if BOXP_PART == 1 || BOXP_PART == -1
-KINST(true)
-#elif BOXP_PART == 0
-KDECL(true)
-#endif
-#if BOXP_PART == 2 || BOXP_PART == -1
-KINST(false, true)
-KINST(true, true)
-#elif BOXP_PART == 0
-KDECL(false, true)
-KDECL(true, true)
-#endif
-// with rows (TP): a part of their own
-#if BOXP_PART == 3 || BOXP_PART == -1
-KINST(false, false, true)
-KINST(true, false, true)
-KINST(false, true, true)
-KINST(true, true, true)
-#elif BOXP_PART == 0
-KDECL(false, false, true)
-KDECL(true, false, true)
-KDECL(false, true, true)
-KDECL(true, true, true)
-#endif
-#undef KINST
-#undef KDECL
 #if BOXP_PART <= 0
-template <bool ROT, bool TP>
-static void launch_boxp_variant(const KernelArgs& a, void* stream, const WbcTaskParams* tp) {
-  const dim3 grid((a.B + 3) / 4);
-  if (a.ws_in || a.ws_out) hipLaunchKernelGGL((wbc_tick_boxp_kernel<true, ROT, TP>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
-  else hipLaunchKernelGGL((wbc_tick_boxp_kernel<false, ROT, TP>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
+static TickKernel boxp_variant(long long key) {
+  BOXP_VARIANTS(WBC_VARIANT_FIND)
+  return nullptr;
 }
 int launch_tick_boxp(const KernelArgs& a, void* stream, const WbcTaskParams* tp) {
-  if (a.rot) tp ? launch_boxp_variant<true, true>(a, stream, tp) : launch_boxp_variant<true, false>(a, stream, tp);
-  else tp ? launch_boxp_variant<false, true>(a, stream, tp) : launch_boxp_variant<false, false>(a, stream, tp);
+  const TickKernel k = boxp_variant(variant_key(a.ws_in || a.ws_out, a.rot != 0, tp != nullptr));
+  if (!k) return WBC_E_UNSUPPORTED;
+  hipLaunchKernelGGL(k, dim3((a.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
   return check_launch("tick_boxp");
 }
 #endif

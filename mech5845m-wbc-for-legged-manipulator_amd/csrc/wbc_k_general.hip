@@ -50,91 +50,50 @@ __global__ void __launch_bounds__(64, 2) wbc_tick_kernel(const KernelArgs A, con
   process_instance<MODE, WARM, ORTH, ROT, TP>(S, A, models[mid], cfgs[mid], plans[mid], lc, cur, b, lane, t_entry, tpr, tp_bad);
 }
 
-// One translation unit per PART (csrc/Makefile compiles this file once per part, in parallel): each part instantiates some of the kernel's
-// variants; part 0 also holds the launcher and sees the other parts' variants as explicit-instantiation declarations.
+// The variants (wbc_common.h, "Kernel variant tables"): the part that instantiates the row, then the template arguments. With rows (TP): parts of
+// their own; no FK kernel (it reads no weight).
 #ifndef GENERAL_PART
 #define GENERAL_PART -1      // -1: everything in one unit
 #endif
-#define KINST(...) template __global__ void wbc_tick_kernel<__VA_ARGS__>(const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__, const WbcTaskParams* __restrict__);
-#define KDECL(...) extern template __global__ void wbc_tick_kernel<__VA_ARGS__>(const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__, const WbcTaskParams* __restrict__);
-#if GENERAL_PART == 0 || GENERAL_PART == -1
-KINST(MODE_TICK)
+#define WBC_PART GENERAL_PART
+#define WBC_KERNEL wbc_tick_kernel
+#define WBC_KPARAMS WBC_TICK_KPARAMS
+#define GENERAL_VARIANTS(V) /* MODE, WARM, ORTH, ROT, TP */ \
+  V(0, MODE_TICK, false, false, false, false)     \
+  V(1, MODE_TICK, true, false, false, false)      \
+  V(2, MODE_TICK, false, true, false, false)      \
+  V(3, MODE_ASSEMBLE, false, false, false, false) \
+  V(3, MODE_FK, false, false, false, false)       \
+  V(4, MODE_TICK, false, false, true, false)      \
+  V(4, MODE_TICK, true, false, true, false)       \
+  V(5, MODE_TICK, false, true, true, false)       \
+  V(5, MODE_ASSEMBLE, false, false, true, false)  \
+  V(5, MODE_FK, false, false, true, false)        \
+  V(6, MODE_TICK, false, false, false, true)      \
+  V(6, MODE_TICK, true, false, false, true)       \
+  V(6, MODE_ASSEMBLE, false, false, false, true)  \
+  V(7, MODE_TICK, false, true, false, true)       \
+  V(7, MODE_TICK, false, true, true, true)        \
+  V(8, MODE_TICK, false, false, true, true)       \
+  V(8, MODE_TICK, true, false, true, true)        \
+  V(8, MODE_ASSEMBLE, false, false, true, true)
+#if GENERAL_PART == -1
+GENERAL_VARIANTS(WBC_VARIANT_INST)
+#else
+GENERAL_VARIANTS(WBC_VARIANT_UNIT)
 #endif
-#if GENERAL_PART == 1 || GENERAL_PART == -1
-KINST(MODE_TICK, true)
-#elif GENERAL_PART == 0
-KDECL(MODE_TICK, true)
-#endif
-#if GENERAL_PART == 2 || GENERAL_PART == -1
-KINST(MODE_TICK, false, true)
-#elif GENERAL_PART == 0
-KDECL(MODE_TICK, false, true)
-#endif
-#if GENERAL_PART == 3 || GENERAL_PART == -1
-KINST(MODE_ASSEMBLE)
-KINST(MODE_FK)
-#elif GENERAL_PART == 0
-KDECL(MODE_ASSEMBLE)
-KDECL(MODE_FK)
-#endif
-#if GENERAL_PART == 4 || GENERAL_PART == -1
-KINST(MODE_TICK, false, false, true)
-KINST(MODE_TICK, true, false, true)
-#elif GENERAL_PART == 0
-KDECL(MODE_TICK, false, false, true)
-KDECL(MODE_TICK, true, false, true)
-#endif
-#if GENERAL_PART == 5 || GENERAL_PART == -1
-KINST(MODE_TICK, false, true, true)
-KINST(MODE_ASSEMBLE, false, false, true)
-KINST(MODE_FK, false, false, true)
-#elif GENERAL_PART == 0
-KDECL(MODE_TICK, false, true, true)
-KDECL(MODE_ASSEMBLE, false, false, true)
-KDECL(MODE_FK, false, false, true)
-#endif
-// with rows (TP): parts of their own; no FK kernel (it reads no weight)
-#if GENERAL_PART == 6 || GENERAL_PART == -1
-KINST(MODE_TICK, false, false, false, true)
-KINST(MODE_TICK, true, false, false, true)
-KINST(MODE_ASSEMBLE, false, false, false, true)
-#elif GENERAL_PART == 0
-KDECL(MODE_TICK, false, false, false, true)
-KDECL(MODE_TICK, true, false, false, true)
-KDECL(MODE_ASSEMBLE, false, false, false, true)
-#endif
-#if GENERAL_PART == 7 || GENERAL_PART == -1
-KINST(MODE_TICK, false, true, false, true)
-KINST(MODE_TICK, false, true, true, true)
-#elif GENERAL_PART == 0
-KDECL(MODE_TICK, false, true, false, true)
-KDECL(MODE_TICK, false, true, true, true)
-#endif
-#if GENERAL_PART == 8 || GENERAL_PART == -1
-KINST(MODE_TICK, false, false, true, true)
-KINST(MODE_TICK, true, false, true, true)
-KINST(MODE_ASSEMBLE, false, false, true, true)
-#elif GENERAL_PART == 0
-KDECL(MODE_TICK, false, false, true, true)
-KDECL(MODE_TICK, true, false, true, true)
-KDECL(MODE_ASSEMBLE, false, false, true, true)
-#endif
-#undef KINST
-#undef KDECL
 #if GENERAL_PART <= 0
-template <bool ROT, bool TP>
-static void launch_tick_variant(const KernelArgs& a, int mode, int grid, hipStream_t s, const WbcTaskParams* tp) {
-  if (mode == MODE_TICK && (a.ws_in || a.ws_out)) hipLaunchKernelGGL((wbc_tick_kernel<MODE_TICK, true, false, ROT, TP>), dim3(grid), dim3(64), 0, s, a, a.models, a.cfgs, a.plans, tp);
-  else if (mode == MODE_TICK && a.presolve && a.presolve_orth == 2) hipLaunchKernelGGL((wbc_tick_kernel<MODE_TICK, false, true, ROT, TP>), dim3(grid), dim3(64), 0, s, a, a.models, a.cfgs, a.plans, tp);
-  else if (mode == MODE_TICK) hipLaunchKernelGGL((wbc_tick_kernel<MODE_TICK, false, false, ROT, TP>), dim3(grid), dim3(64), 0, s, a, a.models, a.cfgs, a.plans, tp);
-  else if (TP || mode == MODE_ASSEMBLE) hipLaunchKernelGGL((wbc_tick_kernel<MODE_ASSEMBLE, false, false, ROT, TP>), dim3(grid), dim3(64), 0, s, a, a.models, a.cfgs, a.plans, tp);
-  else if constexpr (!TP) hipLaunchKernelGGL((wbc_tick_kernel<MODE_FK, false, false, ROT>), dim3(grid), dim3(64), 0, s, a, a.models, a.cfgs, a.plans, tp);
+static TickKernel general_variant(long long key) {
+  GENERAL_VARIANTS(WBC_VARIANT_FIND)
+  return nullptr;
 }
 int launch_tick(const KernelArgs& a, int mode, int grid, void* stream, const WbcTaskParams* tp) {
-  hipStream_t s = (hipStream_t)stream;
   if (mode == MODE_FK) tp = nullptr;   // (FK reads no weight: no kernel with rows)
-  if (a.rot) tp ? launch_tick_variant<true, true>(a, mode, grid, s, tp) : launch_tick_variant<true, false>(a, mode, grid, s, tp);
-  else tp ? launch_tick_variant<false, true>(a, mode, grid, s, tp) : launch_tick_variant<false, false>(a, mode, grid, s, tp);
+  const bool warm = mode == MODE_TICK && (a.ws_in || a.ws_out);                          // working sets and the orthonormal presolve: ticks only,
+  const bool orth = mode == MODE_TICK && !warm && a.presolve && a.presolve_orth == 2;   // and a working set wins over presolve_orth == 2
+  const TickKernel k = general_variant(variant_key(mode, warm, orth, a.rot != 0, tp != nullptr));
+  if (!k) return WBC_E_UNSUPPORTED;
+  hipLaunchKernelGGL(k, dim3(grid), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
   return check_launch("tick");
 }
 int tick_lds_bytes() { return (int)sizeof(Smem); }

@@ -138,46 +138,39 @@ __global__ void __launch_bounds__(64, 2) wbc_qp_kernel(const QpArgs A) {
 }
 
 // One translation unit per PART (csrc/Makefile compiles this file once per part, in parallel): part 0 holds every other kernel of this file and
-// the launchers; parts 1-3 hold the stand-alone QP kernel's size / warm-start variants (each carries a whole qp_core<NM>).
+// the launchers; parts 1-3 hold the stand-alone QP kernel's size / warm-start variants (each carries a whole qp_core<NM>), listed here
+// (wbc_common.h, "Kernel variant tables"): the part that instantiates the row, then the template arguments.
 #ifndef MISC_PART
 #define MISC_PART -1      // -1: everything in one unit
 #endif
-#define KINST(...) template __global__ void wbc_qp_kernel<__VA_ARGS__>(const QpArgs);
-#define KDECL(...) extern template __global__ void wbc_qp_kernel<__VA_ARGS__>(const QpArgs);
-#if MISC_PART == 1 || MISC_PART == -1
-KINST(12)
-KINST(16)
-#elif MISC_PART == 0
-KDECL(12)
-KDECL(16)
+#define WBC_PART MISC_PART
+#define WBC_KERNEL wbc_qp_kernel
+#define WBC_KPARAMS (const QpArgs)
+#define QP_VARIANTS(V) /* NM, WARM */ \
+  V(1, 12, false) \
+  V(1, 16, false) \
+  V(2, 24, false) \
+  V(2, NV, false) \
+  V(3, 16, true)  \
+  V(3, NV, true)
+#if MISC_PART == -1
+QP_VARIANTS(WBC_VARIANT_INST)
+#else
+QP_VARIANTS(WBC_VARIANT_UNIT)
 #endif
-#if MISC_PART == 2 || MISC_PART == -1
-KINST(24)
-KINST(NV)
-#elif MISC_PART == 0
-KDECL(24)
-KDECL(NV)
-#endif
-#if MISC_PART == 3 || MISC_PART == -1
-KINST(16, true)
-KINST(NV, true)
-#elif MISC_PART == 0
-KDECL(16, true)
-KDECL(NV, true)
-#endif
-#undef KINST
-#undef KDECL
 #if MISC_PART <= 0
+typedef void (*QpKernel)(const QpArgs);
+static QpKernel qp_variant(long long key) {
+  QP_VARIANTS(WBC_VARIANT_FIND)
+  return nullptr;
+}
 int launch_qp(const QpArgs& a, int grid, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (a.ws_in || a.ws_out) {   // hot start: the core sizes the tick problems come in (a reduced problem fits 16, the full one needs 26)
-    if (a.n <= 16) hipLaunchKernelGGL((wbc_qp_kernel<16, true>), dim3(grid), dim3(64), 0, s, a);
-    else hipLaunchKernelGGL((wbc_qp_kernel<NV, true>), dim3(grid), dim3(64), 0, s, a);
-  }
-  else if (a.n <= 12) hipLaunchKernelGGL(wbc_qp_kernel<12>, dim3(grid), dim3(64), 0, s, a);
-  else if (a.n <= 16) hipLaunchKernelGGL(wbc_qp_kernel<16>, dim3(grid), dim3(64), 0, s, a);
-  else if (a.n <= 24) hipLaunchKernelGGL(wbc_qp_kernel<24>, dim3(grid), dim3(64), 0, s, a);
-  else hipLaunchKernelGGL(wbc_qp_kernel<NV>, dim3(grid), dim3(64), 0, s, a);
+  const bool warm = a.ws_in || a.ws_out;
+  // the smallest core that holds the problem; hot start: the core sizes the tick problems come in (a reduced problem fits 16, the full one needs 26)
+  const int nm = warm ? (a.n <= 16 ? 16 : NV) : a.n <= 12 ? 12 : a.n <= 16 ? 16 : a.n <= 24 ? 24 : NV;
+  const QpKernel k = qp_variant(variant_key(nm, warm));
+  if (!k) return WBC_E_UNSUPPORTED;
+  hipLaunchKernelGGL(k, dim3(grid), dim3(64), 0, (hipStream_t)stream, a);
   return check_launch("qp");
 }
 

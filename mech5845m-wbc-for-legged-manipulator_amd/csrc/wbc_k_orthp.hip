@@ -1127,68 +1127,42 @@ __global__ void __launch_bounds__(64, 2) wbc_tick_orthp_kernel(const KernelArgs 
   }
 }
 
-// One translation unit per PART (csrc/Makefile compiles this file once per part, in parallel): each part instantiates some of the kernel's
-// variants; part 0 also holds the launcher and sees the other parts' variants as explicit-instantiation declarations.
+// The variants (wbc_common.h, "Kernel variant tables"): the part that instantiates the row, then the template arguments. With rows (TP): parts of
+// their own. WARM goes with INEQ only: without inequality rows there is no working set to seed.
 #ifndef ORTHP_PART
 #define ORTHP_PART -1      // -1: everything in one unit
 #endif
-#define KINST(...) template __global__ void wbc_tick_orthp_kernel<__VA_ARGS__>(const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__, const WbcTaskParams* __restrict__);
-#define KDECL(...) extern template __global__ void wbc_tick_orthp_kernel<__VA_ARGS__>(const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__, const WbcTaskParams* __restrict__);
-#if ORTHP_PART == 0 || ORTHP_PART == -1
-KINST(false)
+#define WBC_PART ORTHP_PART
+#define WBC_KERNEL wbc_tick_orthp_kernel
+#define WBC_KPARAMS WBC_TICK_KPARAMS
+#define ORTHP_VARIANTS(V) /* INEQ, WARM, ROT, TP */ \
+  V(0, false, false, false, false) \
+  V(1, true, false, false, false)  \
+  V(2, true, true, false, false)   \
+  V(3, false, false, true, false)  \
+  V(3, true, false, true, false)   \
+  V(3, true, true, true, false)    \
+  V(4, false, false, false, true)  \
+  V(4, true, false, false, true)   \
+  V(4, true, true, false, true)    \
+  V(5, false, false, true, true)   \
+  V(5, true, false, true, true)    \
+  V(5, true, true, true, true)
+#if ORTHP_PART == -1
+ORTHP_VARIANTS(WBC_VARIANT_INST)
+#else
+ORTHP_VARIANTS(WBC_VARIANT_UNIT)
 #endif
-#if ORTHP_PART == 1 || ORTHP_PART == -1
-KINST(true)
-#elif ORTHP_PART == 0
-KDECL(true)
-#endif
-#if ORTHP_PART == 2 || ORTHP_PART == -1
-KINST(true, true)
-#elif ORTHP_PART == 0
-KDECL(true, true)
-#endif
-#if ORTHP_PART == 3 || ORTHP_PART == -1
-KINST(false, false, true)
-KINST(true, false, true)
-KINST(true, true, true)
-#elif ORTHP_PART == 0
-KDECL(false, false, true)
-KDECL(true, false, true)
-KDECL(true, true, true)
-#endif
-// with rows (TP): parts of their own
-#if ORTHP_PART == 4 || ORTHP_PART == -1
-KINST(false, false, false, true)
-KINST(true, false, false, true)
-KINST(true, true, false, true)
-#elif ORTHP_PART == 0
-KDECL(false, false, false, true)
-KDECL(true, false, false, true)
-KDECL(true, true, false, true)
-#endif
-#if ORTHP_PART == 5 || ORTHP_PART == -1
-KINST(false, false, true, true)
-KINST(true, false, true, true)
-KINST(true, true, true, true)
-#elif ORTHP_PART == 0
-KDECL(false, false, true, true)
-KDECL(true, false, true, true)
-KDECL(true, true, true, true)
-#endif
-#undef KINST
-#undef KDECL
 #if ORTHP_PART <= 0
-template <bool ROT, bool TP>
-static void launch_orthp_variant(const KernelArgs& a, void* stream, int ineq, const WbcTaskParams* tp) {
-  const dim3 grid((a.B + 3) / 4);
-  hipStream_t s = (hipStream_t)stream;
-  if (ineq && (a.ws_in || a.ws_out)) hipLaunchKernelGGL((wbc_tick_orthp_kernel<true, true, ROT, TP>), grid, dim3(64), 0, s, a, a.models, a.cfgs, a.plans, tp);
-  else if (ineq) hipLaunchKernelGGL((wbc_tick_orthp_kernel<true, false, ROT, TP>), grid, dim3(64), 0, s, a, a.models, a.cfgs, a.plans, tp);
-  else hipLaunchKernelGGL((wbc_tick_orthp_kernel<false, false, ROT, TP>), grid, dim3(64), 0, s, a, a.models, a.cfgs, a.plans, tp);
+static TickKernel orthp_variant(long long key) {
+  ORTHP_VARIANTS(WBC_VARIANT_FIND)
+  return nullptr;
 }
 int launch_tick_orthp(const KernelArgs& a, void* stream, int ineq, const WbcTaskParams* tp) {
-  if (a.rot) tp ? launch_orthp_variant<true, true>(a, stream, ineq, tp) : launch_orthp_variant<true, false>(a, stream, ineq, tp);
-  else tp ? launch_orthp_variant<false, true>(a, stream, ineq, tp) : launch_orthp_variant<false, false>(a, stream, ineq, tp);
+  const bool warm = ineq && (a.ws_in || a.ws_out);
+  const TickKernel k = orthp_variant(variant_key(ineq != 0, warm, a.rot != 0, tp != nullptr));
+  if (!k) return WBC_E_UNSUPPORTED;
+  hipLaunchKernelGGL(k, dim3((a.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
   return check_launch("tick_orthp");
 }
 int orthp_lds_bytes() { return (int)(4 * sizeof(QInst)); }

@@ -815,34 +815,31 @@ __global__ void __launch_bounds__(64, 2) wbc_qp_packed_kernel(const QpArgs A) {
   }
 }
 
-// One translation unit per PART (csrc/Makefile): part 0 holds the cold variants and the launcher, part 1 the hot-start variants.
+// The variants (wbc_common.h, "Kernel variant tables"): the part that instantiates the row, then the template arguments. Part 0 holds the cold
+// variants and the launcher, part 1 the hot-start variants, part 2 the variants with the rows of C split over the two halves of a problem.
 #ifndef QPP_PART
-#define QPP_PART -1
+#define QPP_PART -1      // -1: everything in one unit
 #endif
-#if QPP_PART == 0
-extern template __global__ void wbc_qp_packed_kernel<16, 16, true, false>(const QpArgs);
-extern template __global__ void wbc_qp_packed_kernel<32, NV, true, false>(const QpArgs);
-extern template __global__ void wbc_qp_packed_kernel<32, NV, false, true>(const QpArgs);
-extern template __global__ void wbc_qp_packed_kernel<32, NV, true, true>(const QpArgs);
-#elif QPP_PART == 1
-template __global__ void wbc_qp_packed_kernel<16, 16, true, false>(const QpArgs);
-template __global__ void wbc_qp_packed_kernel<32, NV, true, false>(const QpArgs);
-#elif QPP_PART == 2
-template __global__ void wbc_qp_packed_kernel<32, NV, false, true>(const QpArgs);
-template __global__ void wbc_qp_packed_kernel<32, NV, true, true>(const QpArgs);
+#define WBC_PART QPP_PART
+#define WBC_KERNEL wbc_qp_packed_kernel
+#define WBC_KPARAMS (const QpArgs)
+#define QPP_VARIANTS(V) /* G, PV, WARM, HALF */ \
+  V(0, 16, 16, false, false) \
+  V(0, 32, NV, false, false) \
+  V(1, 16, 16, true, false)  \
+  V(1, 32, NV, true, false)  \
+  V(2, 32, NV, false, true)  \
+  V(2, 32, NV, true, true)
+#if QPP_PART == -1
+QPP_VARIANTS(WBC_VARIANT_INST)
+#else
+QPP_VARIANTS(WBC_VARIANT_UNIT)
 #endif
 #if QPP_PART <= 0
-template <int G, int PV>
-static int launch_qpp(const QpArgs& a, hipStream_t s) {
-  typedef QppLayout<G, PV> L;
-  const int grid = (a.B + L::NQ - 1) / L::NQ;
-  const bool warm = a.ws_in || a.ws_out;
-  if (G == 32 && a.p <= 16) {              // rows of C split over the two halves of a problem
-    if (warm) hipLaunchKernelGGL((wbc_qp_packed_kernel<G, PV, true, (G == 32)>), dim3(grid), dim3(64), 0, s, a);
-    else hipLaunchKernelGGL((wbc_qp_packed_kernel<G, PV, false, (G == 32)>), dim3(grid), dim3(64), 0, s, a);
-  } else if (warm) hipLaunchKernelGGL((wbc_qp_packed_kernel<G, PV, true, false>), dim3(grid), dim3(64), 0, s, a);
-  else hipLaunchKernelGGL((wbc_qp_packed_kernel<G, PV, false, false>), dim3(grid), dim3(64), 0, s, a);
-  return check_launch("qp packed");
+typedef void (*QppKernel)(const QpArgs);
+static QppKernel qpp_variant(long long key) {
+  QPP_VARIANTS(WBC_VARIANT_FIND)
+  return nullptr;
 }
 
 // 4: four problems per wavefront, 2: two
@@ -851,9 +848,12 @@ int qp_packed_lanes(const QpArgs& a) {
   return 2;
 }
 int launch_qp_packed(const QpArgs& a, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (qp_packed_lanes(a) == 4) return launch_qpp<16, 16>(a, s);
-  return launch_qpp<32, NV>(a, s);
+  const int nq = qp_packed_lanes(a), g = 64 / nq, pv = nq == 4 ? 16 : NV;   // QppLayout<G, PV>: NQ = 64 / G problems per wavefront
+  const bool half = g == 32 && a.p <= 16;                                    // rows of C split over the two halves of a problem
+  const QppKernel k = qpp_variant(variant_key(g, pv, a.ws_in || a.ws_out, half));
+  if (!k) return WBC_E_UNSUPPORTED;
+  hipLaunchKernelGGL(k, dim3((a.B + nq - 1) / nq), dim3(64), 0, (hipStream_t)stream, a);
+  return check_launch("qp packed");
 }
 #endif
 

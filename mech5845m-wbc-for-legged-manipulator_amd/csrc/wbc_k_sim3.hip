@@ -685,22 +685,29 @@ __global__ void __launch_bounds__(64, 2) wbc_tick_deferred_kernel(const KernelAr
 }
 
 
-// One translation unit per PART (csrc/Makefile): part 0 holds the kernels' unrotated variants and the launchers, part 1 the ROT variants (kept
-// apart: instantiated in the same unit they moved the unrotated variants' spill counts).
+// The two kernels' variants (wbc_common.h, "Kernel variant tables"): the part that instantiates the row, then the template arguments. Part 0 holds
+// the unrotated variants and the launchers, part 1 the ROT variants (kept apart: instantiated in the same unit they moved the unrotated variants'
+// spill counts). The launchers name the variants themselves.
 #ifndef SIM3_PART
 #define SIM3_PART -1      // -1: everything in one unit
 #endif
-#define KARGS const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__
-#if SIM3_PART == 1 || SIM3_PART == -1
-template __global__ void wbc_tick_sim3_kernel<false, true>(KARGS);
-template __global__ void wbc_tick_sim3_kernel<true, true>(KARGS);
-template __global__ void wbc_tick_deferred_kernel<true>(KARGS);
-#elif SIM3_PART == 0
-extern template __global__ void wbc_tick_sim3_kernel<false, true>(KARGS);
-extern template __global__ void wbc_tick_sim3_kernel<true, true>(KARGS);
-extern template __global__ void wbc_tick_deferred_kernel<true>(KARGS);
+#define WBC_PART SIM3_PART
+#define WBC_KPARAMS (const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__)
+#if SIM3_PART == -1
+#define V WBC_VARIANT_INST
+#else
+#define V WBC_VARIANT_UNIT
 #endif
-#undef KARGS
+#define WBC_KERNEL wbc_tick_sim3_kernel   /* WARM, ROT */
+V(0, false, false)
+V(0, true, false)
+V(1, false, true)
+V(1, true, true)
+#undef WBC_KERNEL
+#define WBC_KERNEL wbc_tick_deferred_kernel   /* ROT */
+V(0, false)
+V(1, true)
+#undef V
 #if SIM3_PART <= 0
 int launch_tick_sim3(const KernelArgs& a, int grid, void* stream) {
   if (a.rot && (a.ws_in || a.ws_out)) hipLaunchKernelGGL((wbc_tick_sim3_kernel<true, true>), dim3(grid), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);

@@ -1316,104 +1316,55 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
 #endif
 }
 
-// One translation unit per PART (csrc/Makefile compiles this file once per part, in parallel): each part instantiates some of the kernel's
-// variants; part 0 also holds the launcher and sees the other parts' variants as explicit-instantiation declarations.
+// The variants (wbc_common.h, "Kernel variant tables"): the part that instantiates the row, then the template arguments. With rows (TP): parts of
+// their own. No variant carries TRUNK and QCON together.
 #ifndef SIM3P_PART
 #define SIM3P_PART -1      // -1: everything in one unit
 #endif
-#define KINST(...) template __global__ void wbc_tick_sim3p_kernel<__VA_ARGS__>(const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__, const WbcTaskParams* __restrict__);
-#define KDECL(...) extern template __global__ void wbc_tick_sim3p_kernel<__VA_ARGS__>(const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__, const WbcTaskParams* __restrict__);
-#if SIM3P_PART == 0 || SIM3P_PART == -1
-KINST(false, false)
+#define WBC_PART SIM3P_PART
+#define WBC_KERNEL wbc_tick_sim3p_kernel
+#define WBC_KPARAMS WBC_TICK_KPARAMS
+#define SIM3P_VARIANTS(V) /* WARM, TRUNK, QCON, ROT, TP */ \
+  V(0, false, false, false, false, false) \
+  V(1, true, false, false, false, false)  \
+  V(1, false, true, false, false, false)  \
+  V(1, true, true, false, false, false)   \
+  V(2, false, false, true, false, false)  \
+  V(2, true, false, true, false, false)   \
+  V(3, false, false, false, true, false)  \
+  V(3, true, false, false, true, false)   \
+  V(3, false, true, false, true, false)   \
+  V(3, true, true, false, true, false)    \
+  V(4, false, false, true, true, false)   \
+  V(4, true, false, true, true, false)    \
+  V(5, false, false, false, false, true)  \
+  V(5, true, false, false, false, true)   \
+  V(5, false, true, false, false, true)   \
+  V(6, true, true, false, false, true)    \
+  V(6, false, false, true, false, true)   \
+  V(6, true, false, true, false, true)    \
+  V(7, false, false, false, true, true)   \
+  V(7, true, false, false, true, true)    \
+  V(7, false, true, false, true, true)    \
+  V(8, true, true, false, true, true)     \
+  V(8, false, false, true, true, true)    \
+  V(8, true, false, true, true, true)
+#if SIM3P_PART == -1
+SIM3P_VARIANTS(WBC_VARIANT_INST)
+#else
+SIM3P_VARIANTS(WBC_VARIANT_UNIT)
 #endif
-#if SIM3P_PART == 1 || SIM3P_PART == -1
-KINST(true, false)
-KINST(false, true)
-KINST(true, true)
-#elif SIM3P_PART == 0
-KDECL(true, false)
-KDECL(false, true)
-KDECL(true, true)
-#endif
-#if SIM3P_PART == 2 || SIM3P_PART == -1
-KINST(false, false, true)
-KINST(true, false, true)
-#elif SIM3P_PART == 0
-KDECL(false, false, true)
-KDECL(true, false, true)
-#endif
-#if SIM3P_PART == 3 || SIM3P_PART == -1
-KINST(false, false, false, true)
-KINST(true, false, false, true)
-KINST(false, true, false, true)
-KINST(true, true, false, true)
-#elif SIM3P_PART == 0
-KDECL(false, false, false, true)
-KDECL(true, false, false, true)
-KDECL(false, true, false, true)
-KDECL(true, true, false, true)
-#endif
-#if SIM3P_PART == 4 || SIM3P_PART == -1
-KINST(false, false, true, true)
-KINST(true, false, true, true)
-#elif SIM3P_PART == 0
-KDECL(false, false, true, true)
-KDECL(true, false, true, true)
-#endif
-// with rows (TP): parts of their own
-#if SIM3P_PART == 5 || SIM3P_PART == -1
-KINST(false, false, false, false, true)
-KINST(true, false, false, false, true)
-KINST(false, true, false, false, true)
-#elif SIM3P_PART == 0
-KDECL(false, false, false, false, true)
-KDECL(true, false, false, false, true)
-KDECL(false, true, false, false, true)
-#endif
-#if SIM3P_PART == 6 || SIM3P_PART == -1
-KINST(true, true, false, false, true)
-KINST(false, false, true, false, true)
-KINST(true, false, true, false, true)
-#elif SIM3P_PART == 0
-KDECL(true, true, false, false, true)
-KDECL(false, false, true, false, true)
-KDECL(true, false, true, false, true)
-#endif
-#if SIM3P_PART == 7 || SIM3P_PART == -1
-KINST(false, false, false, true, true)
-KINST(true, false, false, true, true)
-KINST(false, true, false, true, true)
-#elif SIM3P_PART == 0
-KDECL(false, false, false, true, true)
-KDECL(true, false, false, true, true)
-KDECL(false, true, false, true, true)
-#endif
-#if SIM3P_PART == 8 || SIM3P_PART == -1
-KINST(true, true, false, true, true)
-KINST(false, false, true, true, true)
-KINST(true, false, true, true, true)
-#elif SIM3P_PART == 0
-KDECL(true, true, false, true, true)
-KDECL(false, false, true, true, true)
-KDECL(true, false, true, true, true)
-#endif
-#undef KINST
-#undef KDECL
 #if SIM3P_PART <= 0
-template <bool ROT, bool TP>
-static void launch_sim3p_variant(const KernelArgs& a, void* stream, const WbcTaskParams* tp) {
-  const bool warm = a.ws_in || a.ws_out, trunk = a.in.trunk_target && a.packed_trunk, qcon = a.in.q_con || a.in.posture_u;
-  const dim3 grid((a.B + 3) / 4);
-  if (qcon && warm) hipLaunchKernelGGL((wbc_tick_sim3p_kernel<true, false, true, ROT, TP>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
-  else if (qcon) hipLaunchKernelGGL((wbc_tick_sim3p_kernel<false, false, true, ROT, TP>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
-  else if (warm && trunk) hipLaunchKernelGGL((wbc_tick_sim3p_kernel<true, true, false, ROT, TP>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
-  else if (trunk) hipLaunchKernelGGL((wbc_tick_sim3p_kernel<false, true, false, ROT, TP>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
-  else if (warm) hipLaunchKernelGGL((wbc_tick_sim3p_kernel<true, false, false, ROT, TP>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
-  else hipLaunchKernelGGL((wbc_tick_sim3p_kernel<false, false, false, ROT, TP>), grid, dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
+static TickKernel sim3p_variant(long long key) {
+  SIM3P_VARIANTS(WBC_VARIANT_FIND)
+  return nullptr;
 }
 int launch_tick_sim3p(const KernelArgs& a, void* stream, const WbcTaskParams* tp) {
-  if (a.rot) tp ? launch_sim3p_variant<true, true>(a, stream, tp) : launch_sim3p_variant<true, false>(a, stream, tp);
-  else tp ? launch_sim3p_variant<false, true>(a, stream, tp) : launch_sim3p_variant<false, false>(a, stream, tp);
+  const bool warm = a.ws_in || a.ws_out, qcon = a.in.q_con || a.in.posture_u;
+  const bool trunk = !qcon && a.in.trunk_target && a.packed_trunk;   // (QCON switches TRUNK off)
+  const TickKernel k = sim3p_variant(variant_key(warm, trunk, qcon, a.rot != 0, tp != nullptr));
+  if (!k) return WBC_E_UNSUPPORTED;
+  hipLaunchKernelGGL(k, dim3((a.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
   return check_launch("tick_sim3p");
 }
 int sim3p_lds_bytes() { return (int)sizeof(SmemP); }
