@@ -332,6 +332,51 @@ int wbc_tick_tp(WbcBatch* b, int B, const WbcTickIn* in, const WbcTaskParams* tp
 int wbc_assemble_tp(WbcBatch* b, int B, const WbcTickIn* in, const WbcTaskParams* tp, double dt, int mem, const WbcQpData* out, void* stream);
 int wbc_rollout_tp(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r, int mem, void* stream);
 
+/* ------------------------------------------------------------------ roll-outs along per-instance milestone trajectories, scored on device
+ * The experiment of sim3.py as one call: the target of one end effector follows a piecewise-linear trajectory through the instance's own
+ * milestones (sim3.py:207-228: klampt Trajectory(milestones=...), evaluated at a parameter that advances by 0.002 per tick, :225), and what
+ * the reference logs of it — the gripper's target against the position reached, sim3.py:287-296, :340-348 — comes back reduced per
+ * instance and per group of instances instead of as a [K][B][3] trace. Instances may differ in milestones, their number and their speed. */
+#define WBC_MAX_TRAJ_POINTS 32
+typedef struct WbcTrajectory {
+  int32_t max_points;       /* S: row length of `points`, 2 <= S <= WBC_MAX_TRAJ_POINTS                          */
+  int32_t ee_index;         /* 0..4: which end effector's target follows the trajectory (sim3.py: 4, the gripper) */
+  const double* points;     /* [B][S][3] milestones; milestone i sits at parameter i (klampt Trajectory(milestones=...)) */
+  const int32_t* n_points;  /* [B] milestones of instance b, 2..S; NULL => S for all                              */
+  const double* du;         /* [B] parameter advance per tick (sim3.py:225: 0.002); NULL => du_all for all        */
+  double du_all;
+} WbcTrajectory;
+
+typedef struct WbcRolloutSummary {   /* all optional; per instance [B], per group [B / group_size] */
+  double*  err_sq_sum;      /* sum over ticks of |gripper reached after tick k - gripper target of tick k|^2 */
+  double*  err_max;  int32_t* err_max_tick;   /* largest such error and the FIRST tick it occurred at */
+  double*  err_final;       /* the last tick's error */
+  int32_t* first_bad_tick;  /* first tick whose status != WBC_QP_OPTIMAL, -1 if none */
+  int32_t* bad_ticks;       /* number of such ticks */
+  int32_t  group_size;      /* M > 0: instances [g*M, (g+1)*M) form group g (B % M == 0 required); 0: no groups */
+  int32_t  pad_;
+  double*  group_rms;       /* sqrt(sum of err_sq_sum over the group / (M * ticks)) */
+  double*  group_err_max;
+  int32_t* group_worst_status;   /* max of status_max over the group */
+  int32_t* group_bad_instances;  /* instances of the group with bad_ticks > 0 */
+} WbcRolloutSummary;
+
+/* wbc_rollout_tp with the target of end effector traj->ee_index following the instance's trajectory: on tick k = 0 .. r->ticks - 1 it is
+ * eval_b(k * du_b) — the parameter is the PRODUCT, not a running sum, and eval is klampt's: t <= 0 gives the first milestone, t >= n_points - 1
+ * the last (the hold phase), otherwise i = floor(t), u = t - i, (1 - u) * m[i] + u * m[i + 1], each product and sum rounded on its own, so a host
+ * restatement (wbc_workload.traj_targets) is bit-exact. in0->ee_target's row of that end effector is not read (tick 0 gets eval(0)); every other
+ * target and every WbcRollout field is wbc_rollout's (trunk_target_step included; ee_target_final holds eval(ticks * du) in the followed row).
+ * Refused with WBC_E_ARG: r->ee_target_step not NULL, r->hold_ticks not 0, max_points / ee_index out of range, points NULL, du NULL with a
+ * du_all that is not finite and positive, a group_size that does not divide B. mode RUNNING and WARMUP alike; tp NULL = no per-instance rows.
+ * Bad rows — a non-finite point among the instance's first n_points, du non-finite or <= 0, n_points outside 2..S — are found on the device:
+ * that instance's followed target stays at in0's value for the whole roll-out (nothing non-finite reaches a solve), its status_max is
+ * WBC_QP_NUMERICAL, first_bad_tick 0 and bad_ticks = ticks; the other instances are unaffected (statistic "last_traj_bad_rows").
+ * The errors are those of the gripper (end effector 4) whichever end effector follows the trajectory. sum may be NULL (no summary). Group
+ * results come from one wavefront per group and a reduction of fixed shape, no floating-point atomics: two identical calls give identical bits.
+ * Per tick: the tick kernel and the update kernel of wbc_rollout plus one small kernel (csrc/wbc_k_traj.hip), one lane per instance. */
+int wbc_rollout_traj(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
+                     const WbcTrajectory* traj, const WbcRolloutSummary* sum /* may be NULL */, int mem, void* stream);
+
 /* Knobs of a handle (none of them changes a result beyond rounding; defaults in brackets):
  *   "jtj_mfma"        [-1] H = A'A of wbc_tick / wbc_assemble (QP_Wrapper.py:17) on the fp64 matrix cores (v_mfma_f64_16x16x4_f64)
  *                          or as the sparse vector-unit contraction. -1: matrix cores when the Cartesian task stack has
@@ -435,6 +480,7 @@ int wbc_batch_set_option(WbcBatch* b, const char* name, int value);
  * tail or left to the one-instance kernel's second pass; waits for `stream`), "pivoted_last" (instances that took the pivoted
  * elimination, with option "count_pivoted"), "wave_order_slices" (slices of waves whose recorded order the next packed sim3 launch at
  * the last such launch's batch size will read: ceil(ceil(B / 4) / 127) once the order is in effect, 0 without it; waits for `stream`),
+ * "last_traj_bad_rows" (bad WbcTrajectory rows the last wbc_rollout_traj on the handle found; waits for `stream`),
  * "sim3_lds_bytes" / "tick_lds_bytes" / "orthp_lds_bytes" (LDS per workgroup of the tick kernels). */
 int wbc_batch_get_stat(WbcBatch* b, const char* name, void* stream, int64_t* out);
 

@@ -3,9 +3,11 @@
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
+#include <cmath>
 #include <new>
 #include <vector>
 #include "wbc_device.h"
+#include "wbc_traj.h"
 
 using namespace wbc;
 
@@ -82,6 +84,7 @@ struct WbcBatch {
   unsigned long long* d_prof;
   double *d_pu, *d_pq;   // qpJointb MANI/HYBRID results: u [max_batch][26], q_after [max_batch][27] (lazy)
   void* d_roll;          // wbc_rollout's mutable controller state for max_batch instances (lazy)
+  void* d_traj;          // wbc_rollout_traj: per-instance summary, gripper row, bad-row flags and their count (lazy)
 };
 
 // ---------------------------------------------------------------------------------------------- model
@@ -237,6 +240,7 @@ extern "C" void wbc_batch_destroy(WbcBatch* b) {
   if (b->d_pu) (void)hipFree(b->d_pu);
   if (b->d_pq) (void)hipFree(b->d_pq);
   if (b->d_roll) (void)hipFree(b->d_roll);
+  if (b->d_traj) (void)hipFree(b->d_traj);
   if (b->d_status) (void)hipFree(b->d_status);
   if (b->d_defer) (void)hipFree(b->d_defer);
   if (b->d_dstat) (void)hipFree(b->d_dstat);
@@ -722,6 +726,15 @@ extern "C" int wbc_batch_get_stat(WbcBatch* b, const char* name, void* stream, i
     for (const WaveOrder& w : sl) *out += w.B == (uint32_t)b->worder_B;
     return WBC_OK;
   }
+  if (!strcmp(name, "last_traj_bad_rows")) {  // bad WbcTrajectory rows of the last wbc_rollout_traj; waits for `stream`
+    *out = 0;
+    if (!b->d_traj) return WBC_OK;
+    int32_t c = 0;
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    HIP_TRY(hipMemcpy(&c, (const char*)b->d_traj + (size_t)b->max_batch * (6 * sizeof(double) + 5 * sizeof(int32_t)), sizeof c, hipMemcpyDeviceToHost));
+    *out = c;
+    return WBC_OK;
+  }
   if (!strcmp(name, "sim3_lds_bytes")) { *out = sim3_lds_bytes(); return WBC_OK; }
   if (!strcmp(name, "orthp_lds_bytes")) { *out = orthp_lds_bytes(); return WBC_OK; }
   if (!strcmp(name, "tick_lds_bytes")) { *out = tick_lds_bytes(); return WBC_OK; }
@@ -1137,11 +1150,20 @@ extern "C" int wbc_update_state(WbcBatch* b, int B, const double* q_cur, const d
 }
 
 // K closed-loop ticks: the mutable controller state lives in the handle's rollout workspace; in0 is only read.
+static int rollout_run(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
+                       const WbcTrajectory* traj, const WbcRolloutSummary* sum, int mem, void* stream);
 extern "C" int wbc_rollout(WbcBatch* b, int B, const WbcTickIn* in0, double dt, const WbcRollout* r, int mem, void* stream) {
   return wbc_rollout_tp(b, B, in0, nullptr, dt, r, mem, stream);
 }
 extern "C" int wbc_rollout_tp(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r, int mem,
                               void* stream) {
+  return rollout_run(b, B, in0, tp, dt, r, nullptr, nullptr, mem, stream);
+}
+// The roll-out loop of wbc_rollout / wbc_rollout_tp / wbc_rollout_traj. traj == nullptr: one linear segment (WbcRollout.ee_target_step), the
+// launches, memsets and copies of wbc_rollout_tp and nothing else. With a trajectory (arguments checked by wbc_rollout_traj): the update kernel
+// leaves the EE targets alone and one wbc_traj_tick_kernel per tick scores the tick and writes the followed end effector's next target.
+static int rollout_run(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
+                       const WbcTrajectory* traj, const WbcRolloutSummary* sum, int mem, void* stream) {
   int rc = check_batch(b, B, "wbc_rollout", true);
   if (rc) return rc;
   if (!r || r->ticks < 1 || !(dt > 0)) return fail(WBC_E_ARG, "wbc_rollout: ticks >= 1 and dt > 0 required");
@@ -1171,6 +1193,18 @@ extern "C" int wbc_rollout_tp(WbcBatch* b, int B, const WbcTickIn* in0, const Wb
   st.in(&ro.ee_target_step, n * 15); st.in(&ro.trunk_target_step, n * 3); st.in(&ro.imu, n * 4);
   st.out(&ro.q_final, n * WBC_Q_STRIDE); st.out(&ro.qdot_last, n * WBC_V_STRIDE); st.out(&ro.ee_target_final, n * 15);
   st.out(&ro.grip_trace, (size_t)(r->ticks + r->hold_ticks) * n * 3); st.out(&ro.status_max, n); st.out(&ro.iters_sum, n);
+  WbcTrajectory tj;
+  WbcRolloutSummary so;
+  memset(&tj, 0, sizeof tj); memset(&so, 0, sizeof so);
+  if (traj) {
+    tj = *traj;
+    if (sum) so = *sum;
+    const size_t ng = so.group_size > 0 ? n / (size_t)so.group_size : 0;
+    st.in(&tj.points, n * (size_t)tj.max_points * 3); st.in(&tj.n_points, n); st.in(&tj.du, n);
+    st.out(&so.err_sq_sum, n); st.out(&so.err_max, n); st.out(&so.err_max_tick, n); st.out(&so.err_final, n);
+    st.out(&so.first_bad_tick, n); st.out(&so.bad_ticks, n);
+    st.out(&so.group_rms, ng); st.out(&so.group_err_max, ng); st.out(&so.group_worst_status, ng); st.out(&so.group_bad_instances, ng);
+  }
   if ((rc = st.stage())) return rc;
   // seed the mutable state from in0
   auto seed = [&](int off, const double* src, size_t k) -> int {
@@ -1203,8 +1237,25 @@ extern "C" int wbc_rollout_tp(WbcBatch* b, int B, const WbcTickIn* in0, const Wb
   u.trunk_target = first.trunk_target ? blk(O_TT) : nullptr; u.prev_trunk_target = first.prev_trunk_target ? blk(O_TP) : nullptr;
   u.ee_prev_rot = first.ee_prev_rot ? blk(O_EPR) : nullptr; u.trunk_prev_rot = first.trunk_prev_rot ? blk(O_TPR) : nullptr;
   u.ee_ref_rot = first.ee_ref_rot; u.trunk_ref_euler = first.trunk_ref_euler;
-  u.ee_step = ro.ee_target_step; u.trunk_step = ro.trunk_target_step;
+  u.ee_step = ro.ee_target_step; u.trunk_step = ro.trunk_target_step;   // (a trajectory call has no ee_target_step: wbc_traj_tick_kernel moves that target)
   u.status = w_status; u.iters = w_iters; u.status_max = ro.status_max; u.iters_sum = ro.iters_sum;
+  // the trajectory's own state: per-instance summary, the gripper row of a roll-out without a trace, the bad-row flags and their count
+  TrajArgs ta;
+  memset(&ta, 0, sizeof ta);
+  double* w_grip = nullptr;
+  if (traj) {
+    if (!b->d_traj) HIP_TRY(hipMalloc(&b->d_traj, NB * (6 * sizeof(double) + 5 * sizeof(int32_t)) + sizeof(int32_t)));
+    double* T = (double*)b->d_traj;
+    ta.err_sq_sum = T; ta.err_max = T + NB; ta.err_final = T + 2 * NB; w_grip = T + 3 * NB;
+    int32_t* I = (int32_t*)(T + 6 * NB);
+    ta.bad = I; ta.err_max_tick = I + NB; ta.first_bad_tick = I + 2 * NB; ta.bad_ticks = I + 3 * NB; ta.status_max = I + 4 * NB;
+    ta.bad_count = I + 5 * NB;
+    ta.B = B; ta.S = tj.max_points; ta.ee = tj.ee_index; ta.ticks = r->ticks; ta.do_sum = sum != nullptr;
+    ta.points = tj.points; ta.n_points = tj.n_points; ta.du = tj.du; ta.du_all = tj.du_all;
+    ta.ee_target = blk(O_EET); ta.status = w_status; ta.ro_status_max = ro.status_max;
+    HIP_TRY(hipMemsetAsync(ta.bad_count, 0, sizeof(int32_t), s));
+    if (int e = launch_traj_begin(ta, stream)) return fail(WBC_E_HIP, "trajectory kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+  }
   const WbcTickIn loop_in = a.in;
   for (int k = 0; k < r->ticks + r->hold_ticks; ++k) {
     if (k == r->ticks) { u.ee_step = nullptr; u.trunk_step = nullptr; }   // hold phase: the targets stay where they are
@@ -1212,12 +1263,53 @@ extern "C" int wbc_rollout_tp(WbcBatch* b, int B, const WbcTickIn* in0, const Wb
     if ((rc = auto_posture(b, a, B, stream))) return rc;
     if ((rc = launch_tick_auto(b, a, B, stream, tp))) return rc;
     u.grip_trace = ro.grip_trace ? ro.grip_trace + (size_t)k * n * 3 : nullptr;
+    if (traj && ta.do_sum && !u.grip_trace) u.grip_trace = w_grip;   // no trace asked for: the summary reads the tick's row from the workspace
     if (int e = launch_update_auto(b, u, B, stream)) return fail(WBC_E_HIP, "update kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    if (traj) {
+      ta.grip = u.grip_trace;
+      if (int e = launch_traj_tick(ta, k, stream)) return fail(WBC_E_HIP, "trajectory kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    }
+  }
+  if (traj && sum) {
+    auto give = [&](void* dst, const void* src, size_t bytes) -> int {
+      if (dst) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s));
+      return WBC_OK;
+    };
+    if ((rc = give(so.err_sq_sum, ta.err_sq_sum, n * sizeof(double))) || (rc = give(so.err_max, ta.err_max, n * sizeof(double))) ||
+        (rc = give(so.err_final, ta.err_final, n * sizeof(double))) || (rc = give(so.err_max_tick, ta.err_max_tick, n * sizeof(int32_t))) ||
+        (rc = give(so.first_bad_tick, ta.first_bad_tick, n * sizeof(int32_t))) || (rc = give(so.bad_ticks, ta.bad_ticks, n * sizeof(int32_t)))) return rc;
+    if (so.group_size > 0 && (so.group_rms || so.group_err_max || so.group_worst_status || so.group_bad_instances)) {
+      TrajGroupArgs ga;
+      memset(&ga, 0, sizeof ga);
+      ga.G = B / so.group_size; ga.M = so.group_size; ga.ticks = r->ticks;
+      ga.err_sq_sum = ta.err_sq_sum; ga.err_max = ta.err_max; ga.status_max = ta.status_max; ga.bad_ticks = ta.bad_ticks;
+      ga.group_rms = so.group_rms; ga.group_err_max = so.group_err_max; ga.group_worst_status = so.group_worst_status;
+      ga.group_bad_instances = so.group_bad_instances;
+      if (int e = launch_traj_groups(ga, stream)) return fail(WBC_E_HIP, "trajectory kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    }
   }
   if (ro.q_final) HIP_TRY(hipMemcpyAsync(ro.q_final, blk(O_Q), n * 27 * sizeof(double), hipMemcpyDeviceToDevice, s));
   if (ro.qdot_last) HIP_TRY(hipMemcpyAsync(ro.qdot_last, blk(O_QD), n * 26 * sizeof(double), hipMemcpyDeviceToDevice, s));
   if (ro.ee_target_final) HIP_TRY(hipMemcpyAsync(ro.ee_target_final, blk(O_EET), n * 15 * sizeof(double), hipMemcpyDeviceToDevice, s));
   return st.finish();
+}
+
+// The roll-out along per-instance milestone trajectories (WbcTrajectory), scored on the device (WbcRolloutSummary): argument checks, then
+// the shared loop.
+extern "C" int wbc_rollout_traj(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
+                                const WbcTrajectory* traj, const WbcRolloutSummary* sum, int mem, void* stream) {
+  if (!r || !traj) return fail(WBC_E_ARG, "wbc_rollout_traj: r and traj are required");
+  if (r->ee_target_step) return fail(WBC_E_ARG, "wbc_rollout_traj: ee_target_step must be NULL (the trajectory moves the followed target; the other EE targets are constant)");
+  if (r->hold_ticks != 0) return fail(WBC_E_ARG, "wbc_rollout_traj: hold_ticks must be 0 (a trajectory holds its last milestone by itself)");
+  if (traj->max_points < 2 || traj->max_points > WBC_MAX_TRAJ_POINTS)
+    return fail(WBC_E_ARG, "wbc_rollout_traj: max_points = %d outside [2, %d]", traj->max_points, WBC_MAX_TRAJ_POINTS);
+  if (traj->ee_index < 0 || traj->ee_index >= WBC_NEE) return fail(WBC_E_ARG, "wbc_rollout_traj: ee_index = %d outside [0, %d]", traj->ee_index, WBC_NEE - 1);
+  if (!traj->points) return fail(WBC_E_ARG, "wbc_rollout_traj: points is required");
+  if (!traj->du && !(std::isfinite(traj->du_all) && traj->du_all > 0))
+    return fail(WBC_E_ARG, "wbc_rollout_traj: du_all must be finite and positive when du is NULL");
+  if (sum && (sum->group_size < 0 || (sum->group_size > 0 && B % sum->group_size != 0)))
+    return fail(WBC_E_ARG, "wbc_rollout_traj: group_size = %d does not divide B = %d", sum->group_size, B);
+  return rollout_run(b, B, in0, tp, dt, r, traj, sum, mem, stream);
 }
 
 static int qp_common(WbcBatch* b, int B, QpArgs& a, int mem, void* stream, const char* who) {

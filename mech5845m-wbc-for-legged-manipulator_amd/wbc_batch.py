@@ -377,6 +377,69 @@ class WbcBatch:
         capi.check(self.lib.wbc_rollout_tp(self._h, B, C.byref(tin), tp, float(dt), C.byref(r), mem, self._stream(mem)), self.lib)
         return out
 
+    _SUMMARY = (("err_sq_sum", np.float64), ("err_max", np.float64), ("err_max_tick", np.int32), ("err_final", np.float64),
+                ("first_bad_tick", np.int32), ("bad_ticks", np.int32))
+    _GROUP_SUMMARY = (("group_rms", np.float64), ("group_err_max", np.float64), ("group_worst_status", np.int32),
+                      ("group_bad_instances", np.int32))
+
+    def rollout_traj(self, inputs, dt, ticks, points, n_points=None, du=0.002, ee_index=4, group_size=0, want_trace=False,
+                     want_summary=True, mode=capi.ROLLOUT_RUNNING, task_params=None, trunk_target_step=None, imu=None):
+        """`ticks` closed-loop ticks with the target of end effector `ee_index` following each instance's own milestone trajectory
+        (wbc_rollout_traj, include/wbc.h): points [B, S, 3], n_points [B] int32 (None: S milestones everywhere), du [B] or one number
+        (parameter advance per tick, sim3.py:225). Tick k's target is wbc_workload.traj_targets(points, n_points, du, k). Returns
+        rollout()'s dict (grip_trace only with want_trace) plus, with want_summary, the per-instance arrays err_sq_sum, err_max,
+        err_max_tick, err_final, first_bad_tick, bad_ticks [B] and, with group_size = M > 0 (B % M == 0), group_rms, group_err_max,
+        group_worst_status, group_bad_instances [B / M] — all reduced on the device."""
+        keep = []
+        du_arr = None if np.isscalar(du) else du
+        mem = _mem_of(list(inputs.values()) + [points, n_points, du_arr, trunk_target_step, imu, task_params])
+        q = inputs.get("q")
+        B = self._batch_of(q)
+        shape = tuple(getattr(points, "shape", ()))
+        if len(shape) != 3 or shape[0] != B or shape[2] != 3 or not 2 <= shape[1] <= capi.MAX_TRAJ_POINTS:
+            raise capi.WbcError("points: shape %s, want (%d, S, 3) with 2 <= S <= %d" % (shape, B, capi.MAX_TRAJ_POINTS))
+        S = int(shape[1])
+        if not 0 <= int(ee_index) < capi.NEE:
+            raise capi.WbcError("ee_index = %d outside [0, %d]" % (ee_index, capi.NEE - 1))
+        M = int(group_size)
+        if M < 0 or (M > 0 and B % M != 0):
+            raise capi.WbcError("group_size = %d does not divide B = %d" % (M, B))
+        if int(ticks) < 1:
+            raise capi.WbcError("ticks = %d, want >= 1" % ticks)
+        f = np.float64
+        P = self._p
+        t = capi.WbcTrajectory()
+        t.max_points, t.ee_index = S, int(ee_index)
+        t.points = P(points, f, keep, B, S * 3, "points")
+        t.n_points = P(n_points, np.int32, keep, B, 1, "n_points")
+        if du_arr is None:
+            t.du_all = float(du)
+        else:
+            t.du = P(du_arr, f, keep, B, 1, "du")
+        out = dict(q=self._alloc(q, (B, NQS)), qdot=self._alloc(q, (B, NV)), ee_target=self._alloc(q, (B, 5, 3)),
+                   status=self._alloc(q, (B,), np.int32), iters=self._alloc(q, (B,), np.int32))
+        if want_trace:
+            out["grip_trace"] = self._alloc(q, (int(ticks), B, 3))
+        r = capi.WbcRollout()
+        r.ticks, r.mode, r.hold_ticks = int(ticks), int(mode), 0
+        r.trunk_target_step, r.imu = P(trunk_target_step, f, keep, B, 3, "trunk_target_step"), P(imu, f, keep, B, 4, "imu")
+        r.q_final, r.qdot_last, r.ee_target_final = P(out["q"], f, keep), P(out["qdot"], f, keep), P(out["ee_target"], f, keep)
+        r.status_max, r.iters_sum = P(out["status"], np.int32, keep), P(out["iters"], np.int32, keep)
+        if want_trace:
+            r.grip_trace = P(out["grip_trace"], f, keep)
+        sm = None
+        if want_summary:
+            sm = capi.WbcRolloutSummary()
+            sm.group_size = M
+            for name, dtype in self._SUMMARY + (self._GROUP_SUMMARY if M > 0 else ()):
+                out[name] = self._alloc(q, (B // M if name.startswith("group_") else B,), dtype)
+                setattr(sm, name, P(out[name], dtype, keep))
+        tin = self._tick_in(inputs, keep, B)
+        tp = _task_params(task_params, B, keep, self.device_id)
+        capi.check(self.lib.wbc_rollout_traj(self._h, B, C.byref(tin), tp, float(dt), C.byref(r), C.byref(t),
+                                             C.byref(sm) if sm is not None else None, mem, self._stream(mem)), self.lib)
+        return out
+
     def integrate(self, q, v, dt, model_id=None):
         """pin.integrate(model, q, v * dt) for every instance."""
         keep = []

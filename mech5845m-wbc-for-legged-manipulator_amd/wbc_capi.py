@@ -82,6 +82,21 @@ class WbcRollout(C.Structure):
         "status_max", "iters_sum")] + [("hold_ticks", C.c_int32), ("pad_", C.c_int32)]
 
 
+# wbc_rollout_traj: per-instance milestone trajectory of one end effector's target, and the roll-out summary (include/wbc.h)
+MAX_TRAJ_POINTS = 32
+
+
+class WbcTrajectory(C.Structure):
+    _fields_ = [("max_points", C.c_int32), ("ee_index", C.c_int32), ("points", C.c_void_p), ("n_points", C.c_void_p), ("du", C.c_void_p),
+                ("du_all", C.c_double)]
+
+
+class WbcRolloutSummary(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("err_sq_sum", "err_max", "err_max_tick", "err_final", "first_bad_tick", "bad_ticks")] + [
+        ("group_size", C.c_int32), ("pad_", C.c_int32)] + [(n, C.c_void_p) for n in (
+            "group_rms", "group_err_max", "group_worst_status", "group_bad_instances")]
+
+
 class WbcFkOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("oMi", "oMf", "J", "com", "Jcom")]
 
@@ -120,6 +135,8 @@ SIGNATURES = {
     "wbc_tick_tp": (_i, [_vp, _i, C.POINTER(WbcTickIn), _vp, _d, _i, C.POINTER(WbcTickOut), _vp]),
     "wbc_assemble_tp": (_i, [_vp, _i, C.POINTER(WbcTickIn), _vp, _d, _i, C.POINTER(WbcQpData), _vp]),
     "wbc_rollout_tp": (_i, [_vp, _i, C.POINTER(WbcTickIn), _vp, _d, C.POINTER(WbcRollout), _i, _vp]),
+    "wbc_rollout_traj": (_i, [_vp, _i, C.POINTER(WbcTickIn), _vp, _d, C.POINTER(WbcRollout), C.POINTER(WbcTrajectory),
+                              C.POINTER(WbcRolloutSummary), _i, _vp]),
     "wbc_integrate": (_i, [_vp, _i, _vp, _vp, _vp, _d, _i, _vp, _vp]),
     "wbc_batch_set_option": (_i, [_vp, C.c_char_p, _i]),
     "wbc_batch_get_stat": (_i, [_vp, C.c_char_p, _vp, C.POINTER(C.c_int64)]),

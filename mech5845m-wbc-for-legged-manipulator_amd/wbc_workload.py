@@ -106,3 +106,23 @@ def make_tick_inputs(model, cfg, B, seed, fk, stress=True):
         d["com_target"] = com + rng.normal(0, 0.002, (B, 3))
         d["com_target_vel"] = rng.normal(0, 0.05, (B, 3))
     return d
+
+
+def traj_targets(points, n_points, du, k):
+    """Targets [B, 3] of tick k along per-instance milestone trajectories: wbc_rollout_traj's evaluation restated for a whole batch, bit for
+    bit (include/wbc.h). points [B, S, 3]; n_points [B] milestones of each instance (None: S); du [B] or a scalar: parameter advance per
+    tick. Instance b gets klampt's Trajectory(milestones=points[b, :n_points[b]]).eval(k * du[b]) (Robot_Wrapper4._LinearTrajectory):
+    clamped ends, otherwise i = floor(t), u = t - i, (1 - u) * m[i] + u * m[i + 1]."""
+    points = np.asarray(points, dtype=np.float64)
+    B, S = points.shape[0], points.shape[1]
+    n = np.full(B, S, dtype=np.int64) if n_points is None else np.asarray(n_points, dtype=np.int64).reshape(B)
+    t = float(k) * np.broadcast_to(np.asarray(du, dtype=np.float64), (B,))
+    inner = (t > 0) & (t < n - 1)
+    i = np.where(inner, np.floor(np.where(inner, t, 0.0)), 0.0).astype(np.int64)
+    u = (t - i)[:, None]
+    rows = np.arange(B)
+    out = (1 - u) * points[rows, i] + u * points[rows, np.minimum(i + 1, S - 1)]
+    out[t <= 0] = points[t <= 0, 0]
+    last = t >= n - 1
+    out[last] = points[last, n[last] - 1]
+    return out

@@ -1,0 +1,66 @@
+#!/usr/bin/env python3
+"""Closed-loop ticks/s of wbc_rollout_traj (two milestones = one segment, summary on, no trace) against wbc_rollout on the same inputs:
+what the per-tick trajectory kernel costs. Same process, same handle, interleaved rounds, HIP events around each call.
+    python3 tools/time_rollout_traj.py [B] [ticks] [rounds]"""
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "mech5845m-wbc-for-legged-manipulator_amd"))
+import numpy as np
+import torch
+
+import wbc_capi as capi
+import wbc_model
+import wbc_workload
+from wbc_batch import WbcBatch
+
+B = int(sys.argv[1]) if len(sys.argv) > 1 else 65536
+TICKS = int(sys.argv[2]) if len(sys.argv) > 2 else 500
+ROUNDS = int(sys.argv[3]) if len(sys.argv) > 3 else 5
+DT = 0.002
+
+model = wbc_model.load_model("a1_wx200")
+cfg = wbc_model.sim3_config(model)
+bt = WbcBatch(model, B)
+bt.configure(cfg)
+fk = lambda q: bt.fk(q, want=("oMf",))["oMf"]   # noqa: E731
+d = wbc_workload.make_tick_inputs(model, cfg, B, 0, fk)
+grip0 = fk(d["q"])[:, capi.FR_EE0 + 4, 9:]
+d["ee_target"][:, 4] = grip0
+d["prev_ee_target"][:, 4] = grip0
+seg = np.array([0.0, 0.25, 0.0])                          # sim3.py's first segment: 0.25 m in 500 ticks
+points = np.stack([grip0, grip0 + seg * (TICKS / 500.0)], axis=1)
+step = np.zeros((B, 5, 3))
+step[:, 4] = (points[:, 1] - points[:, 0]) / TICKS
+dev = {k: torch.from_numpy(np.ascontiguousarray(v)).cuda() for k, v in d.items()}
+imu = dev["q"][:, 3:7].contiguous()
+step_d, pts_d = torch.from_numpy(step).cuda(), torch.from_numpy(points).cuda()
+
+calls = {
+    "wbc_rollout (no trace)": lambda: bt.rollout(dev, DT, TICKS, ee_target_step=step_d, imu=imu, want_trace=False),
+    "wbc_rollout_traj (summary, no trace)": lambda: bt.rollout_traj(dev, DT, TICKS, pts_d, du=1.0 / TICKS, imu=imu),
+}
+ms = {k: [] for k in calls}
+last = {}
+for rnd in range(ROUNDS + 1):                             # (the first round settles clocks, caches and the lazy workspaces: not counted)
+    for label, call in calls.items():
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        last[label] = call()
+        e1.record()
+        torch.cuda.synchronize()
+        if rnd:
+            ms[label].append(e0.elapsed_time(e1))
+for label, t in ms.items():
+    med = float(np.median(t))
+    print(json.dumps({"call": label, "B": B, "ticks": TICKS, "rounds": ROUNDS, "ms_median": round(med, 3), "ms_min": round(min(t), 3),
+                      "ms_max": round(max(t), 3), "M_closed_loop_ticks_per_s": round(B * TICKS / med / 1e3, 2),
+                      "last_path": bt.stat("last_path")}))
+a, b = (float(np.median(ms[k])) for k in calls)
+print("# wbc_rollout_traj takes %+.2f %% against wbc_rollout (%.1f us per tick more)" % (100.0 * (b / a - 1.0), 1e3 * (b - a) / TICKS))
+old, new = (last[k] for k in calls)
+same = bool((old["status"] == new["status"]).all().item())
+print("# same inputs: status identical %s, q max-abs difference %.3e" % (same, float((old["q"] - new["q"]).abs().max().item())))
+bt.close()
