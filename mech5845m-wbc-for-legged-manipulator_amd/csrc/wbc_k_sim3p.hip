@@ -20,6 +20,17 @@ namespace wbc {
 // QCON: the variant for a caller's (or wbc_posture_par_kernel's) posture target `posture_u` and constraint state `q_con` — qpJointb "MANI" / literal
 // "HYBRID" with sweeps that matter (Robot_Wrapper4.py:1220-1260): the tasks are formed at q, then the kinematics are redone at
 // q_con and the contact rows, the trunk box, the damper bounds and the integration see THAT state (a second FK pass, as in process_instance).
+// RARE(c): a wave-level condition the benchmark distribution never or hardly ever meets. The hint gives the compiler's block placement the
+// probability it lacks: together with the sim3p parts' own flag (csrc/Makefile FAMFLAGS_sim3p) the guarded block is laid out behind the packed
+// path's exit instead of in the middle of the stream every wave fetches. COLD_MARK(): a comment in
+// the listing at the head of such a block — tools/hot_path_bytes.py counts what is reachable only through one as off the hot path.
+// Placement only: no arithmetic changes, results bit for bit the same.
+#ifdef SIM3P_NO_LAYOUT_HINTS   // (A/B variant builds only: make variant VFLAGS=-DSIM3P_NO_LAYOUT_HINTS FAMFLAGS_sim3p= gives the blocks back their source-order places)
+#define RARE(c) (c)
+#else
+#define RARE(c) __builtin_expect(!!(c), 0)
+#endif
+#define COLD_MARK() asm volatile("; WBC_COLD")
 #ifndef SIM3P_WAVES
 #define SIM3P_WAVES 2      // waves per SIMD the register allocation is made for (3: an experiment, tools/hot_path_spills.py with WBC_XFLAGS="-DSIM3P_WAVES=3 -DWBC_NO_TAIL")
 #endif
@@ -360,7 +371,8 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
     bp1 = (s < nl) ? (1.0 / nv) * u1 * joint_w : 0.0;
   }
   if (s >= n) g = 0.0;
-  if (A.post_static && P.post_pert) {     // the state qpJointb leaves behind: bounds and integrate see it
+  if (RARE(A.post_static && P.post_pert)) {     // the state qpJointb leaves behind: bounds and integrate see it
+    COLD_MARK();
     WSYNC();
     if (((P.post_pert >> s) & 1u)) V.in[s] = (qv[s] + 0.0002) - (0.0002 * 2);
     if (16 + s < NQ && ((P.post_pert >> (16 + s)) & 1u)) V.in[16 + s] = (qv[16 + s] + 0.0002) - (0.0002 * 2);
@@ -541,7 +553,8 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
   // the leg velocity z2 pivoted last are dealt with by the SWAP further down. Ex[f] = E [6], r22, g0x, g1x, l0, l1, l2.
   double* const Ex = I.M1;                        // [4][12]: M1 is free between the FK and the Cholesky sweep (M2 is full: At, Kb, Bb)
   bool defer = false;
-  if (__ballot(valid && fmask != 0)) {
+  if (RARE(__ballot(valid && fmask != 0) != 0)) {
+    COLD_MARK();
     bool bad_rank = false;
     if (s < 4 && ((fmask >> s) & 1u)) {
       const int f = s;
@@ -622,7 +635,8 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
   // coefficient in slot c*), the bound row of leg DoF l2 becomes the bound row of base DoF c* and vice versa; at the end lane c*
   // delivers z2 = q̇ of leg DoF l2 and row lane l2 delivers q̇ of base DoF c*.
   int dofA = dof0, dofB = dof1;            // DoF whose velocity lane s delivers as reduced variable / as eliminated-leg row
-  if (__ballot(valid && fmask != 0 && !defer)) {
+  if (RARE(__ballot(valid && fmask != 0 && !defer) != 0)) {
+    COLD_MARK();
 #pragma unroll 1
     for (int f = 0; f < 4; ++f) {
       const bool on = valid && !defer && ((fmask >> f) & 1u);
@@ -736,7 +750,8 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
   PSTOP(3, h[0] + h[3] + g + clb + cub + lb + ub);
   const bool flagged = defer;
   bool live = valid && !flagged;
-  if (valid && flagged && s == 0 && A.defer_stat) {   // statistic "deferred_last": (launch sequence number, count) in one word, no reset launch
+  if (RARE(valid && flagged && s == 0 && A.defer_stat)) {   // statistic "deferred_last": (launch sequence number, count) in one word, no reset launch
+    COLD_MARK();
     unsigned long long old = *(volatile unsigned long long*)A.defer_stat, assumed;
     do {
       assumed = old;
@@ -822,6 +837,7 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
   };
   // drop slot l of the rows `dr`: Givens sequence read off the removed row of T (rare path)
   auto drop_slot = [&](const bool dr, const int l_) {
+    COLD_MARK();
     const int l = dr ? l_ : 0;
     const int lc = bpermi(a_code, rbase + l) & 255;
     if (dr && s == ((lc >= n) ? lc - n : lc)) actm &= (lc >= n) ? ~2 : ~1;
@@ -1015,7 +1031,8 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
         const double um = rmin16((s < q) ? u : 0.0);
         bool rest = restoring && (um < 0.0);
         if (rest && ++iters > max_iter) { status = WBC_QP_MAX_ITER; rest = false; restoring = false; searching = false; }
-        if (!__ballot(rest)) {
+        if (!RARE(__ballot(rest) != 0)) {   // (rare per PASS of this loop even where seeds are dropped often: a few drops against every pass
+                                            //  of every wave; the WARM variants' layout was sized, not timed: DESIGN.md §3.21)
           if (!__ballot(restoring && did && !again)) break;
           const bool on = restoring && did && !again;
           refresh(on);
@@ -1081,7 +1098,7 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
     for (;;) {
       if (stepping && ++iters > max_iter) { status = WBC_QP_MAX_ITER; stepping = false; searching = false; }
       // ---- drop slot l of the rows that ask for it
-      if (__ballot(stepping && drop_l >= 0)) {
+      if (RARE(__ballot(stepping && drop_l >= 0) != 0)) {
         const bool dr = stepping && drop_l >= 0;
         drop_slot(dr, drop_l);
         // slack of the constraint being added, at the current x
@@ -1305,7 +1322,7 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
   // shared with the packed layout). No list, no second launch, and a batch that defers everything runs at the general kernel's occupancy.
 #ifndef WBC_NO_TAIL   // (A/B variant builds only: make variant VFLAGS=-DWBC_NO_TAIL measures what carrying the tail costs the common path)
   const unsigned long long tailm = __ballot(valid && flagged && s == 0);
-  if (tailm) {
+  if (RARE(tailm != 0)) {
     asm volatile("; WBC_TAIL_BEGIN" ::: "memory");   // (a comment in the assembly listing: tools/hot_path_spills.py cuts the control-flow graph here)
 #pragma unroll 1
     for (int rr = 0; rr < 4; ++rr) {

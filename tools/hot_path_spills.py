@@ -11,6 +11,8 @@ import sys
 import tempfile
 from concurrent.futures import ThreadPoolExecutor
 
+from hot_path_bytes import family_flags      # (the flags csrc/Makefile gives one family's parts alone)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mech5845m-wbc-for-legged-manipulator_amd", "csrc")
 
@@ -19,7 +21,7 @@ def listing(part):
     fam, k = part.split(".")
     out = os.path.join(tempfile.gettempdir(), "wbc_%s_%s.s" % (fam, k))
     subprocess.check_call(["hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-Wno-unused-function", "--cuda-device-only", "-S", "-g1",
-                           "-D%s_PART=%s" % (fam.upper(), k)] + os.environ.get("WBC_XFLAGS", "").split() + [os.path.join(CSRC, "wbc_k_%s.hip" % fam), "-o", out])
+                           "-D%s_PART=%s" % (fam.upper(), k), *family_flags(fam)] + os.environ.get("WBC_XFLAGS", "").split() + [os.path.join(CSRC, "wbc_k_%s.hip" % fam), "-o", out])
     return open(out).read()
 
 
