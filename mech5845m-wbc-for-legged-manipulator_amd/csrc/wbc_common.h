@@ -1927,6 +1927,10 @@ __device__ __forceinline__ bool tp_row_bad(const WbcTaskParams* row, const int l
   const bool bad = !(fabs(v0) <= 1.7976931348623157e308) || !(fabs(v1) <= 1.7976931348623157e308) || (lane == 20 && v1 == 0.0);
   return __ballot(bad) != 0ull;
 }
+// entry i (< WBC_TASK_PARAMS_DOUBLES) of a row holds v: the rule, for every kernel that reads rows
+__device__ __forceinline__ bool tp_entry_bad(const int i, const double v) {
+  return !(fabs(v) <= 1.7976931348623157e308) || (i == WBC_TASK_PARAMS_DOUBLES - 1 && v == 0.0);
+}
 // ... the same for a 16-lane group (lane s of the group at rbase): six entries per lane, joint_w on s = 4 of the last
 __device__ __forceinline__ bool tp_row_bad16(const WbcTaskParams* row, const int s, const int rbase) {
   const double* w = reinterpret_cast<const double*>(row);
@@ -1935,9 +1939,30 @@ __device__ __forceinline__ bool tp_row_bad16(const WbcTaskParams* row, const int
   for (int k = 0; k < 6; ++k) {
     const int i = s + 16 * k;
     const double v = (i < WBC_TASK_PARAMS_DOUBLES) ? w[i] : 1.0;
-    bad = bad || !(fabs(v) <= 1.7976931348623157e308) || (i == WBC_TASK_PARAMS_DOUBLES - 1 && v == 0.0);
+    bad = bad || tp_entry_bad(i, v);
   }
   return ((__ballot(bad) >> rbase) & 0xFFFFull) != 0ull;
+}
+
+// R* = Rz(c) Ry(b) Rx(a), row-major, from the sines and cosines of the reference's roll a, pitch b, yaw c (calcTargetVelTrunk2,
+// Robot_Wrapper4.py:960-972): every kernel that forms the trunk reference's rotation
+__device__ __forceinline__ void euler_to_R(const double sa, const double ca, const double sb, const double cb, const double sc, const double cc,
+                                           double (&Rs)[9]) {
+  Rs[0] = cc * cb; Rs[1] = cc * sb * sa - sc * ca; Rs[2] = cc * sb * ca + sc * sa;
+  Rs[3] = sc * cb; Rs[4] = sc * sb * sa + cc * ca; Rs[5] = sc * sb * ca - cc * sa;
+  Rs[6] = -sb;     Rs[7] = cb * sa;                Rs[8] = cb * ca;
+}
+
+// velDamperJointConstraints (Robot_Wrapper4.py:572-637) for one DoF: position qi in [lo, hi], velocity limit vm -> velocity bounds l <= 0 <= u.
+// The index map that picks qi (the reference's own) is the caller's record. Every packed kernel's bounds; the one-instance
+// kernels (process_instance below, wbc_k_sim3.hip) keep the same statements on the configuration's fields: through this function their
+// ISA moves, and with it the packed kernels' tails.
+__device__ __forceinline__ void damper_bounds(const double qi, const double lo, const double hi, const double vm, const double dcoef,
+                                              const double dqi, const double dqs, double& l, double& u) {
+  if (qi <= lo + dqi) { l = -dcoef * (qi - lo - dqs) / (dqi - dqs); if (l > vm) l = vm; if (l < -vm) l = -vm; } else l = -vm;
+  if (qi >= hi - dqi) { u = dcoef * (hi - qi - dqs) / (dqi - dqs); if (u < -vm) u = -vm; if (u > vm) u = vm; } else u = vm;
+  if (l > 0) l = -l;
+  if (u < 0) u = -u;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2199,9 +2224,7 @@ __device__ __forceinline__ void process_instance(Smem& S, const KA& A, const Dev
       }
       WSYNC();
       const double sa = S.yv[0], ca = S.yv[1], sb = S.yv[2], cb = S.yv[3], sc = S.yv[4], cc = S.yv[5];
-      Rs[0] = cc * cb; Rs[1] = cc * sb * sa - sc * ca; Rs[2] = cc * sb * ca + sc * sa;
-      Rs[3] = sc * cb; Rs[4] = sc * sb * sa + cc * ca; Rs[5] = sc * sb * ca - cc * sa;
-      Rs[6] = -sb;     Rs[7] = cb * sa;                Rs[8] = cb * ca;
+      euler_to_R(sa, ca, sb, cb, sc, cc, Rs);
       const double qx[4] = {S.yv[6], 0, 0, S.yv[7]}, qy[4] = {0, S.yv[8], 0, S.yv[9]}, qz[4] = {0, 0, S.yv[10], S.yv[11]};
       double tq[4];
       quat_mul(qy, qx, tq);

@@ -782,9 +782,7 @@ __global__ void __launch_bounds__(64) wbc_update_kernel(const UpdateArgs A, cons
   if (cfg.task_trunk && A.trunk_prev_rot && A.trunk_ref_euler) {                      // old_ref_trunk_rot_matrix = R* (:996)
     const SinCos a = sincos_cw(rdl(ter, 0)), bb = sincos_cw(rdl(ter, 1)), cc = sincos_cw(rdl(ter, 2));
     double Rs[9];
-    Rs[0] = cc.c * bb.c; Rs[1] = cc.c * bb.s * a.s - cc.s * a.c; Rs[2] = cc.c * bb.s * a.c + cc.s * a.s;
-    Rs[3] = cc.s * bb.c; Rs[4] = cc.s * bb.s * a.s + cc.c * a.c; Rs[5] = cc.s * bb.s * a.c - cc.c * a.s;
-    Rs[6] = -bb.s;       Rs[7] = bb.c * a.s;                     Rs[8] = bb.c * a.c;
+    euler_to_R(a.s, a.c, bb.s, bb.c, cc.s, cc.c, Rs);
     if (lane == 0) {
 #pragma unroll
       for (int i = 0; i < 9; ++i) A.trunk_prev_rot[(size_t)b * 9 + i] = Rs[i];
@@ -856,47 +854,9 @@ __global__ void __launch_bounds__(64) wbc_update_packed_kernel(const UpdateArgs 
   WSYNC();
   const double* const qv = U.q;
   double* const oMi = U.oMi;
-  if (scq0 >= 0) { const SinCos t = sincos_cw(qv[scq0]); U.sc[2 * (2 + s)] = t.s; U.sc[2 * (2 + s) + 1] = t.c; }
-  if (scq1 >= 0) { const SinCos t = sincos_cw(qv[scq1]); U.sc[2 * (18 + s)] = t.s; U.sc[2 * (18 + s) + 1] = t.c; }
-  if (s == 0) {
-    double Rt[9];
-    quat_to_R(qv + 3, Rt);
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-      for (int rr = 0; rr < 3; ++rr) oMi[12 + 3 * c + rr] = Rt[3 * rr + c];
-    oMi[12 + 9] = qv[0]; oMi[12 + 10] = qv[1]; oMi[12 + 11] = qv[2];
-  }
+  pk_fk_seed(oMi, U.sc, qv, scq0, scq1, s);
   WSYNC();
-#pragma unroll 1
-  for (int L = 0; L < 5; ++L) {             // the packed tick kernel's FK, record for record
-    const DevPlan::PkJoint fk = fkn;
-    if (L + 1 < 5) fkn = P.pk_fk[L + 1][s];
-    const int j = fk.joint;
-    if (j >= 0) {
-      const bool rev = fk.rev != 0;
-      const int a0 = fk.a0, a1 = fk.a1, a2 = fk.a2;
-      const double* Pp = oMi + 12 * fk.parent;
-      const double sn = rev ? U.sc[2 * j] : 0.0, cs = rev ? U.sc[2 * j + 1] : 1.0;
-      const double pris = rev ? 0.0 : qv[fk.q_idx];
-      if (ROT && fk.rot) {   // rotated placement (ROT instantiations only: the others compile exactly as before)
-        fk_place_rot_lds(oMi + 12 * j, Pp, M.rp[j], a0, a1, a2, sn, cs, pris);
-      } else {
-        double Av[3], Bv[3], Cv[3], Pv[3];
-#pragma unroll
-        for (int rr = 0; rr < 3; ++rr) { Av[rr] = Pp[a0 + rr]; Bv[rr] = Pp[a1 + rr]; Cv[rr] = Pp[a2 + rr]; Pv[rr] = Pp[9 + rr]; }
-        double* Po = oMi + 12 * j;
-#pragma unroll
-        for (int rr = 0; rr < 3; ++rr) {
-          Po[a0 + rr] = Av[rr];
-          Po[a1 + rr] = cs * Bv[rr] + sn * Cv[rr];
-          Po[a2 + rr] = cs * Cv[rr] - sn * Bv[rr];
-          Po[9 + rr] = Pv[rr] + Av[rr] * (fk.t0 + pris) + Bv[rr] * fk.t1 + Cv[rr] * fk.t2;
-        }
-      }
-    }
-    WSYNC();
-  }
+  pk_fk_sweep<ROT>(oMi, U.sc, qv, M, P.pk_fk, fkn, s);   // the packed tick kernel's FK
   if (s < 6) {
     const double* Pj = oMi + 12 * fjoint;
 #pragma unroll
@@ -951,9 +911,7 @@ __global__ void __launch_bounds__(64) wbc_update_packed_kernel(const UpdateArgs 
     const int rb = lane & 48;
     const double sa = bperm(t.s, rb), ca = bperm(t.c, rb), sb = bperm(t.s, rb + 1), cb = bperm(t.c, rb + 1), sc_ = bperm(t.s, rb + 2), cc = bperm(t.c, rb + 2);
     double Rs[9];
-    Rs[0] = cc * cb; Rs[1] = cc * sb * sa - sc_ * ca; Rs[2] = cc * sb * ca + sc_ * sa;
-    Rs[3] = sc_ * cb; Rs[4] = sc_ * sb * sa + cc * ca; Rs[5] = sc_ * sb * ca - cc * sa;
-    Rs[6] = -sb;      Rs[7] = cb * sa;                 Rs[8] = cb * ca;
+    euler_to_R(sa, ca, sb, cb, sc_, cc, Rs);
     if (valid && cfg.task_trunk && s < 9) {
       double v = Rs[0];
 #pragma unroll

@@ -81,49 +81,15 @@ __global__ void __launch_bounds__(64, 2) wbc_tick_orthp_kernel(const KernelArgs 
     if (16 + s < 28) I.in[16 + s] = q1;
     if (s < 15) { I.in[28 + s] = et; I.in[43 + s] = ep; }
     if (s < 6) I.in[58 + s] = cm;
-    // calcTargetVelEE3's orientation feed-forward (Robot_Wrapper4.py:1125-1133): omega = vee(((R* - R*_prev) / dt) R*^T), one component per lane
-    // (EE s / 3, component s % 3), straight from the caller's [B][5][9] references; zero when none are passed
-    {
-      double om = 0.0;
-      if (A.in.ee_ref_rot && s < 15) {
-        const int e = s / 3, i = s - 3 * e;
-        const double* Rs = A.in.ee_ref_rot + (size_t)b * 45 + 9 * e;
-        const double* Rp = A.in.ee_prev_rot + (size_t)b * 45 + 9 * e;
-        const int ra = (i == 0) ? 6 : ((i == 1) ? 0 : 3), rb = (i == 0) ? 3 : ((i == 1) ? 6 : 0);   // S[2][1] = D row 2 . R row 1; S[0][2]; S[1][0]
-        om = ((Rs[ra] - Rp[ra]) * inv_dt) * Rs[rb] + ((Rs[ra + 1] - Rp[ra + 1]) * inv_dt) * Rs[rb + 1] + ((Rs[ra + 2] - Rp[ra + 2]) * inv_dt) * Rs[rb + 2];
-      }
-      I.ow[s] = om;
-    }
-    // the configuration's weights and gains: 85 contiguous doubles of WbcConfig, six per lane, parked in wt (= cl | yv | zv | xv)
-    const double* cw = &cfg.ee_W[0][0];
-    if (TP) {                             // the instance's row for entries 0..84 (the box constants @85..88 stay the configuration's)
-      const double* rw = reinterpret_cast<const double*>(tps + b);
-      bool bad = false;
-#pragma unroll
-      for (int i = 0; i < 6; ++i) {
-        const int k = s + 16 * i;
-        const double v = (k < WBC_TASK_PARAMS_DOUBLES) ? rw[k] : ((k < 89) ? cw[k] : 0.0);
-        bad = bad || (k < WBC_TASK_PARAMS_DOUBLES && (!(fabs(v) <= 1.7976931348623157e308) || (k == WBC_TASK_PARAMS_DOUBLES - 1 && v == 0.0)));
-        I.cl[s + 16 * i] = v;
-      }
-      tpbad = ((__ballot(bad) >> rbase) & 0xFFFFull) != 0ull;
-      if (tpbad) {                        // (tp_row_bad16's rule) computed with the configuration's block, reported WBC_QP_NUMERICAL
-#pragma unroll
-        for (int i = 0; i < 6; ++i) I.cl[s + 16 * i] = (s + 16 * i < 89) ? cw[s + 16 * i] : 0.0;
-      }
-    } else {
-#pragma unroll
-    for (int i = 0; i < 6; ++i) I.cl[s + 16 * i] = (s + 16 * i < 89) ? cw[s + 16 * i] : 0.0;     // (+ trunk_box_z_frac, _ang, _scale, com_box_scale @85..88)
-    }
+    I.ow[s] = pk_ee_omega(A.in, b, s, inv_dt);   // the EE tasks' orientation feed-forward, one component per lane
+    // the configuration's weights and gains, or with TP the instance's row (the box constants @85..88 stay the configuration's), parked in
+    // wt (= cl | yv | zv | xv)
+    tpbad = pk_stage_weights<TP>(I.cl, cfg, tps, b, s, rbase, 89);
     if (INEQ) {
       const bool c_tr = cfg.task_trunk != 0;
       double t0 = 0.0, t1 = 0.0;
       if (c_tr) {
-        auto tinv = [&](const int k) -> double {
-          return (k < 3) ? A.in.trunk_target[(size_t)b * 3 + k] : (k < 6) ? A.in.prev_trunk_target[(size_t)b * 3 + (k - 3)]
-               : (k < 9) ? A.in.trunk_ref_euler[(size_t)b * 3 + (k - 6)] : A.in.trunk_prev_rot[(size_t)b * 9 + (k - 9)];
-        };
-        t0 = tinv(s); t1 = (s < 2) ? tinv(16 + s) : 0.0;
+        t0 = pk_trunk_input(A.in, b, s); t1 = (s < 2) ? pk_trunk_input(A.in, b, 16 + s) : 0.0;
       }
       I.gp[s] = t0;
       if (s < 2) I.gp[16 + s] = t1;
@@ -149,41 +115,10 @@ __global__ void __launch_bounds__(64, 2) wbc_tick_orthp_kernel(const KernelArgs 
   const double* const qv = I.in;
   const bool c_trunk = INEQ && cfg.task_trunk != 0, c_con_trunk = INEQ && cfg.con_trunk != 0, c_con_com = INEQ && cfg.con_com != 0;
   if (INEQ && __ballot(c_trunk)) {
-    // calcTargetVelTrunk2 (Robot_Wrapper4.py:948-1015) / TrunkB (:914-920), as in the packed sim3 / box kernels: the trunk frame is the free-flyer's own
-    // placement (the plan checks it); the target velocity x trunk_w is parked in gp [24..29]
+    // calcTargetVelTrunk2 / TrunkB (:914-920): the target velocity x trunk_w is parked in gp [24..29]
     const double* tw = wt + 65;              // trunk_W [0..5], trunk_w [6], trunk_gain [7..12]
-    const double* tin = I.gp;
-    const double* xt = tin;
-    const double* xp = tin + 3;
-    const double* er = tin + 6;
-    double* const sh = I.X;                  // (free until the FK)
-    double Rt_[9], fq[4], rq[4], Rs[9], vel[6];
-    quat_to_R(qv + 3, Rt_);
-    R_to_quat(Rt_, fq);
-    {
-      const SinCos t = sincos_cw(s < 3 ? er[s < 3 ? s : 0] : 0.5 * er[(s < 6 ? s : 3) - 3]);
-      if (s < 6) { sh[2 * s] = t.s; sh[2 * s + 1] = t.c; }
-      WSYNC();
-      const double sa = sh[0], ca = sh[1], sb = sh[2], cb = sh[3], sc_ = sh[4], cc_ = sh[5];
-      Rs[0] = cc_ * cb; Rs[1] = cc_ * sb * sa - sc_ * ca; Rs[2] = cc_ * sb * ca + sc_ * sa;
-      Rs[3] = sc_ * cb; Rs[4] = sc_ * sb * sa + cc_ * ca; Rs[5] = sc_ * sb * ca - cc_ * sa;
-      Rs[6] = -sb;      Rs[7] = cb * sa;                  Rs[8] = cb * ca;
-      const double qx[4] = {sh[6], 0, 0, sh[7]}, qy[4] = {0, sh[8], 0, sh[9]}, qz[4] = {0, 0, sh[10], sh[11]};
-      double tq[4];
-      quat_mul(qy, qx, tq);
-      quat_mul(qz, tq, rq);
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) vel[i] = (xt[i] - xp[i]) * inv_dt + tw[7 + i] * ((xt[i] - qv[i]) * inv_dt);
-    const double qe0 = fq[3] * rq[0] - fq[0] * rq[3] + fq[1] * rq[2] - fq[2] * rq[1];   // :974
-    const double qe1 = fq[3] * rq[1] - fq[1] * rq[3] - fq[0] * rq[2] + fq[2] * rq[0];   // :975
-    const double qe2 = fq[3] * rq[2] - fq[3] * rq[2] + fq[0] * rq[1] - fq[1] * rq[0];   // :976 (sic)
-    double D[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) D[i] = (Rs[i] - tin[9 + i]) * inv_dt;
-    vel[3] = (D[6] * Rs[1] + D[7] * Rs[4] + D[8] * Rs[7]) + tw[10] * qe0;
-    vel[4] = (D[0] * Rs[2] + D[1] * Rs[5] + D[2] * Rs[8]) + tw[11] * qe1;
-    vel[5] = (D[3] * Rs[0] + D[4] * Rs[3] + D[5] * Rs[6]) + tw[12] * qe2;
+    double Rt_[9], vel[6];
+    pk_trunk_target_vel(qv, I.gp, tw, I.X, inv_dt, s, Rt_, vel);   // (X is free until the FK)
     const double trunk_w = tw[6];
     if (s == 0) {
 #pragma unroll
@@ -194,51 +129,11 @@ __global__ void __launch_bounds__(64, 2) wbc_tick_orthp_kernel(const KernelArgs 
   double* const oMi = I.X;                   // [22][12]
   double* const sc = I.W;                    // sin / cos of joint j at 2 j
   double* const mc = I.W + 44;               // m_j c_j (world), m_j at 4 j
-  {
-    if (scq0 >= 0) { const SinCos t = sincos_cw(qv[scq0]); sc[2 * (2 + s)] = t.s; sc[2 * (2 + s) + 1] = t.c; }
-    if (scq1 >= 0) { const SinCos t = sincos_cw(qv[scq1]); sc[2 * (18 + s)] = t.s; sc[2 * (18 + s) + 1] = t.c; }
-    if (s == 0) {   // root free-flyer (joint 1): R from the quaternion as Eigen's toRotationMatrix, p = xyz; R column-major then p
-      double Rt[9];
-      quat_to_R(qv + 3, Rt);
-#pragma unroll
-      for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int rr = 0; rr < 3; ++rr) oMi[12 + 3 * c + rr] = Rt[3 * rr + c];
-      oMi[12 + 9] = qv[0]; oMi[12 + 10] = qv[1]; oMi[12 + 11] = qv[2];
-    }
-  }
+  pk_fk_seed(oMi, sc, qv, scq0, scq1, s);
   WSYNC();
   QSTOP(1, sc[4 + s] + oMi[12 + s]);
   // ---- pin.forwardKinematics, level by level (Robot_Wrapper4.py:400)
-#pragma unroll 1
-  for (int L = 0; L < QLEV; ++L) {
-    const DevPlan::PkJoint fk = fkn;
-    if (L + 1 < QLEV) fkn = P.q_fk[L + 1][s];
-    const int j = fk.joint;
-    if (j >= 0) {
-      const bool rev = fk.rev != 0;
-      const int a0 = fk.a0, a1 = fk.a1, a2 = fk.a2;
-      const double* Pp = oMi + 12 * fk.parent;
-      const double sn = rev ? sc[2 * j] : 0.0, cs = rev ? sc[2 * j + 1] : 1.0;
-      const double pris = rev ? 0.0 : qv[fk.q_idx];
-      if (ROT && fk.rot) {   // rotated placement (ROT instantiations only: the others compile exactly as before)
-        fk_place_rot_lds(oMi + 12 * j, Pp, M.rp[j], a0, a1, a2, sn, cs, pris);
-      } else {
-        double Av[3], Bv[3], Cv[3], Pv[3];
-#pragma unroll
-        for (int rr = 0; rr < 3; ++rr) { Av[rr] = Pp[a0 + rr]; Bv[rr] = Pp[a1 + rr]; Cv[rr] = Pp[a2 + rr]; Pv[rr] = Pp[9 + rr]; }
-        double* Po = oMi + 12 * j;
-#pragma unroll
-        for (int rr = 0; rr < 3; ++rr) {
-          Po[a0 + rr] = Av[rr];
-          Po[a1 + rr] = cs * Bv[rr] + sn * Cv[rr];
-          Po[a2 + rr] = cs * Cv[rr] - sn * Bv[rr];
-          Po[9 + rr] = Pv[rr] + Av[rr] * (fk.t0 + pris) + Bv[rr] * fk.t1 + Cv[rr] * fk.t2;
-        }
-      }
-    }
-    WSYNC();
-  }
+  pk_fk_sweep<ROT>(oMi, sc, qv, M, P.q_fk, fkn, s);
   QSTOP(2, oMi[12 * 4 + (s & 7)]);
   // ---- frame origins (updateFramePlacements, :405), m c per joint, Jacobian columns (WORLD) of DoF s and 16 + s
   double ms_l = 0.0, sl[3] = {0, 0, 0};
@@ -264,18 +159,8 @@ __global__ void __launch_bounds__(64, 2) wbc_tick_orthp_kernel(const KernelArgs 
     }
   }
   double lin0[3] = {0, 0, 0}, ang0[3] = {0, 0, 0}, lin1[3] = {0, 0, 0}, ang1[3] = {0, 0, 0};
-  {
-    const double* Pj = oMi + 12 * D0.joint;
-    const double pj[3] = {Pj[9], Pj[10], Pj[11]};
-    if (D0.ang >= 0) { ang0[0] = Pj[3 * D0.ang]; ang0[1] = Pj[3 * D0.ang + 1]; ang0[2] = Pj[3 * D0.ang + 2]; cross3(pj, ang0, lin0); }
-    if (D0.lin >= 0) { lin0[0] = Pj[3 * D0.lin]; lin0[1] = Pj[3 * D0.lin + 1]; lin0[2] = Pj[3 * D0.lin + 2]; }
-  }
-  if (has1) {
-    const double* Pj = oMi + 12 * D1.joint;
-    const double pj[3] = {Pj[9], Pj[10], Pj[11]};
-    if (D1.ang >= 0) { ang1[0] = Pj[3 * D1.ang]; ang1[1] = Pj[3 * D1.ang + 1]; ang1[2] = Pj[3 * D1.ang + 2]; cross3(pj, ang1, lin1); }
-    if (D1.lin >= 0) { lin1[0] = Pj[3 * D1.lin]; lin1[1] = Pj[3 * D1.lin + 1]; lin1[2] = Pj[3 * D1.lin + 2]; }
-  }
+  pk_jac_col(oMi, D0.joint, D0.lin, D0.ang, lin0, ang0);
+  if (has1) pk_jac_col(oMi, D1.joint, D1.lin, D1.ang, lin1, ang1);
   WSYNC();   // oMi is dead: X is free
   // ---- centre of mass and the CoM-Jacobian columns (pin.jacobianCenterOfMass): jc = (m_sub / M) (lin + ang x c_sub)
   double com[3] = {0, 0, 0}, jc0[3] = {0, 0, 0}, jc1[3] = {0, 0, 0};
@@ -569,16 +454,9 @@ __global__ void __launch_bounds__(64, 2) wbc_tick_orthp_kernel(const KernelArgs 
     double l0 = 0.0, u0 = 0.0, l1 = 0.0, u1 = 0.0, tl = -QP_INF, tu = QP_INF;
     {
       const double dcoef = cfg.damper_coef, dqi = cfg.damper_qi, dqs = cfg.damper_qs;
-      auto damper = [&](const DevPlan::XVar& v, double& l_, double& u_) {
-        const double qi = qv[v.dq_idx], lo = v.d_lo, hi = v.d_hi, vm = v.d_vm;
-        if (qi <= lo + dqi) { l_ = -dcoef * (qi - lo - dqs) / (dqi - dqs); if (l_ > vm) l_ = vm; if (l_ < -vm) l_ = -vm; } else l_ = -vm;
-        if (qi >= hi - dqi) { u_ = dcoef * (hi - qi - dqs) / (dqi - dqs); if (u_ < -vm) u_ = -vm; if (u_ > vm) u_ = vm; } else u_ = vm;
-        if (l_ > 0) l_ = -l_;
-        if (u_ < 0) u_ = -u_;
-      };
       const DevPlan::XVar v0 = P.q_dmp[s], v1 = P.q_dmp[(16 + s) & 31];
-      damper(v0, l0, u0);
-      if (has1) damper(v1, l1, u1);
+      damper_bounds(qv[v0.dq_idx], v0.d_lo, v0.d_hi, v0.d_vm, dcoef, dqi, dqs, l0, u0);
+      if (has1) damper_bounds(qv[v1.dq_idx], v1.d_lo, v1.d_hi, v1.d_vm, dcoef, dqi, dqs, l1, u1);
       // trunk box (lanes 0..3) and CoM box (lanes 4, 5)
       const double tb_z = wt[85], tb_a = wt[86], tb_s = wt[87], cb_s = wt[88];
       double Rtr[9];

@@ -181,9 +181,7 @@ __device__ __forceinline__ void process_sim3(SmemC& S, const KernelArgs& A, cons
       }
       WSYNC();
       const double sa = S.yv[0], ca = S.yv[1], sb = S.yv[2], cb = S.yv[3], sc = S.yv[4], cc = S.yv[5];
-      Rs[0] = cc * cb; Rs[1] = cc * sb * sa - sc * ca; Rs[2] = cc * sb * ca + sc * sa;
-      Rs[3] = sc * cb; Rs[4] = sc * sb * sa + cc * ca; Rs[5] = sc * sb * ca - cc * sa;
-      Rs[6] = -sb;     Rs[7] = cb * sa;                Rs[8] = cb * ca;
+      euler_to_R(sa, ca, sb, cb, sc, cc, Rs);
       const double qx[4] = {S.yv[6], 0, 0, S.yv[7]}, qy[4] = {0, S.yv[8], 0, S.yv[9]}, qz[4] = {0, 0, S.yv[10], S.yv[11]};
       double tq[4];
       quat_mul(qy, qx, tq);

@@ -94,16 +94,14 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
     if (16 + s < 28) V.in[16 + s] = q1;
     if (s < 10) V.in[28 + s] = ex;
     V.cl[s] = 0.0; V.cl[16 + s] = 0.0;
-    if (TRUNK) {   // trunk_target [3], prev_trunk_target [3], trunk_ref_euler [3], trunk_prev_rot [9] -> V.tv [16] + V.xv [0..1]; the configuration's
-                   // trunk_W [6], trunk_w, trunk_gain [6] -> V.xv [2..14] (both vectors are free until the contact stage)
-      auto tin = [&](const int k) -> double {
-        return (k < 3) ? A.in.trunk_target[(size_t)b * 3 + k] : (k < 6) ? A.in.prev_trunk_target[(size_t)b * 3 + (k - 3)]
-             : (k < 9) ? A.in.trunk_ref_euler[(size_t)b * 3 + (k - 6)] : A.in.trunk_prev_rot[(size_t)b * 9 + (k - 9)];
-      };
-      const double t0 = tin(s), t1 = (s < 2) ? tin(16 + s) : 0.0;
+    if (TRUNK) {   // trunk_target [3], prev_trunk_target [3], trunk_ref_euler [3], trunk_prev_rot [9] -> V.yv [14..15] | V.tv [16], contiguous; the
+                   // configuration's trunk_W [6], trunk_w, trunk_gain [6] -> V.xv [2..14] (these vectors are free until the contact stage)
+      static_assert(offsetof(PVec, tv) - offsetof(PVec, yv) == 16 * sizeof(double), "yv [14..15] runs on into tv");
+      double* const tin = V.yv + 14;
+      const double t0 = pk_trunk_input(A.in, b, s), t1 = (s < 2) ? pk_trunk_input(A.in, b, 16 + s) : 0.0;
       const double tw = (s < 13) ? (TP ? (&tpr->trunk_W[0])[s] : (&cfg.trunk_W[0])[s]) : 0.0;
-      V.tv[s] = t0;
-      if (s < 2) V.xv[s] = t1;
+      tin[s] = t0;
+      if (s < 2) tin[16 + s] = t1;
       if (s < 13) V.xv[2 + s] = tw;
     }
     if (WARM && s < 2) {                  // the carried working set: two words per instance, parked (as bit patterns) in V.in[38..39]
@@ -118,42 +116,10 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
   if (TRUNK) {
     WSYNC();                               // (the staged inputs are visible)
     const double* const qv = V.in;
-    // calcTargetVelTrunk2 (Robot_Wrapper4.py:948-1015) / TrunkB (:914-920): the trunk frame is the free-flyer's own placement (the plan checks
-    // it), so the target velocity depends on the inputs alone — formed here, where hardly anything is live
+    // calcTargetVelTrunk2 / TrunkB (:914-920): the target velocity depends on the inputs alone — formed here, where hardly anything is live
     const double* tw = V.xv + 2;           // trunk_W [0..5], trunk_w [6], trunk_gain [7..12]
-    const double* xt = V.tv;
-    const double* xp = V.tv + 3;
-    const double* er = V.tv + 6;
-    double* const sh = I.M2;               // (free until the FK)
-    double Rt_[9], fq[4], rq[4], Rs[9], vel[6];
-    quat_to_R(qv + 3, Rt_);
-    R_to_quat(Rt_, fq);
-    {
-      const SinCos t = sincos_cw(s < 3 ? er[s < 3 ? s : 0] : 0.5 * er[(s < 6 ? s : 3) - 3]);   // reference angles and their halves, one per lane
-      if (s < 6) { sh[2 * s] = t.s; sh[2 * s + 1] = t.c; }
-      WSYNC();
-      const double sa = sh[0], ca = sh[1], sb = sh[2], cb = sh[3], sc_ = sh[4], cc = sh[5];
-      Rs[0] = cc * cb; Rs[1] = cc * sb * sa - sc_ * ca; Rs[2] = cc * sb * ca + sc_ * sa;
-      Rs[3] = sc_ * cb; Rs[4] = sc_ * sb * sa + cc * ca; Rs[5] = sc_ * sb * ca - cc * sa;
-      Rs[6] = -sb;      Rs[7] = cb * sa;                 Rs[8] = cb * ca;
-      const double qx[4] = {sh[6], 0, 0, sh[7]}, qy[4] = {0, sh[8], 0, sh[9]}, qz[4] = {0, 0, sh[10], sh[11]};
-      double tq[4];
-      quat_mul(qy, qx, tq);
-      quat_mul(qz, tq, rq);
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) vel[i] = (xt[i] - xp[i]) * inv_dt + tw[7 + i] * ((xt[i] - qv[i]) * inv_dt);
-    const double qe0 = fq[3] * rq[0] - fq[0] * rq[3] + fq[1] * rq[2] - fq[2] * rq[1];   // :974
-    const double qe1 = fq[3] * rq[1] - fq[1] * rq[3] - fq[0] * rq[2] + fq[2] * rq[0];   // :975
-    const double qe2 = fq[3] * rq[2] - fq[3] * rq[2] + fq[0] * rq[1] - fq[1] * rq[0];   // :976 (sic)
-    const double Ro[9] = {V.tv[9], V.tv[10], V.tv[11], V.tv[12], V.tv[13], V.tv[14], V.tv[15], V.xv[0], V.xv[1]};
-    double D[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) D[i] = (Rs[i] - Ro[i]) * inv_dt;
-    // skew = D Rs (R*, not R*^T: :984); omega = (S[2][1], S[0][2], S[1][0]) + K qe
-    vel[3] = (D[6] * Rs[1] + D[7] * Rs[4] + D[8] * Rs[7]) + tw[10] * qe0;
-    vel[4] = (D[0] * Rs[2] + D[1] * Rs[5] + D[2] * Rs[8]) + tw[11] * qe1;
-    vel[5] = (D[3] * Rs[0] + D[4] * Rs[3] + D[5] * Rs[6]) + tw[12] * qe2;
+    double Rt_[9], vel[6];
+    pk_trunk_target_vel(qv, V.yv + 14, tw, I.M2, inv_dt, s, Rt_, vel);   // (M2 is free until the FK)
     const double trunk_w = tw[6];
     // trunkA (Robot_Wrapper4.py:487-490, WORLD): the task's rows live on the six base columns, and the free-flyer's own Jacobian columns are its
     // placement (linear DoF c: column c of R; angular DoF c: p x column c, column c) — so the task's WHOLE contribution, the 6 x 6 block of H'
@@ -231,68 +197,16 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
   // ---- sin / cos of the joint angles: joint j (>= 2) reads q[idx_q[j]]; two joints per lane
   double* const oMi = I.M1;                 // [22][12], runs on into M2
   double* const sc = I.M2 + PV * PLD - 48;  // sin / cos table: the tail of M2, free until J is written
-  {
-    if (scq0 >= 0) { const SinCos t = sincos_cw(qv[scq0]); sc[2 * (2 + s)] = t.s; sc[2 * (2 + s) + 1] = t.c; }
-    if (scq1 >= 0) { const SinCos t = sincos_cw(qv[scq1]); sc[2 * (18 + s)] = t.s; sc[2 * (18 + s) + 1] = t.c; }
-    // root free-flyer (joint 1): R from the quaternion exactly as Eigen's toRotationMatrix, p = xyz; R column-major then p
-    if (s == 0) {
-      double Rt[9];
-      quat_to_R(qv + 3, Rt);
-#pragma unroll
-      for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int rr = 0; rr < 3; ++rr) oMi[12 + 3 * c + rr] = Rt[3 * rr + c];
-      oMi[12 + 9] = qv[0]; oMi[12 + 10] = qv[1]; oMi[12 + 11] = qv[2];
-    }
-  }
+  pk_fk_seed(oMi, sc, qv, scq0, scq1, s);
   WSYNC();
   PSTOP(7, oMi[12 + s] + sc[4 + s]);
-  // ---- P1: pin.forwardKinematics, level by level (Robot_Wrapper4.py:400). The level's joint and its constants are fetched
-  // inside the loop (L1-resident tables): kept live for all five levels they cost 60 VGPRs
-#pragma unroll 1
-  for (int L = 0; L < 5; ++L) {
-    const DevPlan::PkJoint fk = fkn;
-    if (L + 1 < 5) fkn = P.pk_fk[L + 1][s];          // next level's record is on its way while this level is computed
-    const int j = fk.joint;
-    if (j >= 0) {
-      const bool rev = fk.rev != 0;
-      const int a0 = fk.a0, a1 = fk.a1, a2 = fk.a2;
-      const double* Pp = oMi + 12 * fk.parent;
-      const double sn = rev ? sc[2 * j] : 0.0, cs = rev ? sc[2 * j + 1] : 1.0;
-      const double pris = rev ? 0.0 : qv[fk.q_idx];
-      if (ROT && fk.rot) {   // rotated placement (ROT instantiations only: the others compile exactly as before)
-        fk_place_rot_lds(oMi + 12 * j, Pp, M.rp[j], a0, a1, a2, sn, cs, pris);
-      } else {
-        double Av[3], Bv[3], Cv[3], Pv[3];
-#pragma unroll
-        for (int rr = 0; rr < 3; ++rr) { Av[rr] = Pp[a0 + rr]; Bv[rr] = Pp[a1 + rr]; Cv[rr] = Pp[a2 + rr]; Pv[rr] = Pp[9 + rr]; }
-        double* Po = oMi + 12 * j;
-#pragma unroll
-        for (int rr = 0; rr < 3; ++rr) {
-          Po[a0 + rr] = Av[rr];
-          Po[a1 + rr] = cs * Bv[rr] + sn * Cv[rr];
-          Po[a2 + rr] = cs * Cv[rr] - sn * Bv[rr];
-          Po[9 + rr] = Pv[rr] + Av[rr] * (fk.t0 + pris) + Bv[rr] * fk.t1 + Cv[rr] * fk.t2;
-        }
-      }
-    }
-    WSYNC();
-  }
+  // ---- P1: pin.forwardKinematics, level by level (Robot_Wrapper4.py:400)
+  pk_fk_sweep<ROT>(oMi, sc, qv, M, P.pk_fk, fkn, s);
   // ---- P3: Jacobian columns (WORLD): of reduced variable s, and (linear part) of eliminated leg DoF s
   PSTOP(1, oMi[12 * 4 + (s & 7)]);
   double lin0[3] = {0, 0, 0}, ang0[3] = {0, 0, 0}, lin1[3] = {0, 0, 0};
-  if (s < n) {
-    const double* Pj = oMi + 12 * c0_joint;
-    const double pj[3] = {Pj[9], Pj[10], Pj[11]};
-    if (c0_ang >= 0) { ang0[0] = Pj[3 * c0_ang]; ang0[1] = Pj[3 * c0_ang + 1]; ang0[2] = Pj[3 * c0_ang + 2]; cross3(pj, ang0, lin0); }
-    if (c0_lin >= 0) { lin0[0] = Pj[3 * c0_lin]; lin0[1] = Pj[3 * c0_lin + 1]; lin0[2] = Pj[3 * c0_lin + 2]; }
-  }
-  if (s < nl) {
-    const double* Pj = oMi + 12 * c1_joint;
-    const double pj[3] = {Pj[9], Pj[10], Pj[11]};
-    if (c1_ang >= 0) { const double a1[3] = {Pj[3 * c1_ang], Pj[3 * c1_ang + 1], Pj[3 * c1_ang + 2]}; cross3(pj, a1, lin1); }
-    if (c1_lin >= 0) { lin1[0] = Pj[3 * c1_lin]; lin1[1] = Pj[3 * c1_lin + 1]; lin1[2] = Pj[3 * c1_lin + 2]; }
-  }
+  if (s < n) pk_jac_col(oMi, c0_joint, c0_lin, c0_ang, lin0, ang0);
+  if (s < nl) { double a1[3]; pk_jac_col(oMi, c1_joint, c1_lin, c1_ang, lin1, a1); }
   // trunk frame = the root joint's placement (imu frame: identity offset); gripper_bar origin
   double Rtr[9], ptr[3], pfe[3];
   {
@@ -402,7 +316,7 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
   PSTOP(2, h[0] + h[5] + h[11] + g);
   if (QCON && A.in.q_con) {
     // ---- the second pass: findConstraints, velDamperJointConstraints and the integration see q_con (the state qpJointb leaves behind); the task
-    // image has been consumed (h, g), so M1 / M2 are free for the kinematics again. Same code as the first pass.
+    // image has been consumed (h, g), so M1 / M2 are free for the kinematics again.
     WSYNC();
     {
       const double* qg = A.in.q_con + (size_t)b * NQ;
@@ -412,63 +326,42 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
     }
     fkn = P.pk_fk[0][s];
     WSYNC();
-  {
-    if (scq0 >= 0) { const SinCos t = sincos_cw(qv[scq0]); sc[2 * (2 + s)] = t.s; sc[2 * (2 + s) + 1] = t.c; }
-    if (scq1 >= 0) { const SinCos t = sincos_cw(qv[scq1]); sc[2 * (18 + s)] = t.s; sc[2 * (18 + s) + 1] = t.c; }
-    // root free-flyer (joint 1): R from the quaternion exactly as Eigen's toRotationMatrix, p = xyz; R column-major then p
-    if (s == 0) {
-      double Rt[9];
-      quat_to_R(qv + 3, Rt);
-#pragma unroll
-      for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int rr = 0; rr < 3; ++rr) oMi[12 + 3 * c + rr] = Rt[3 * rr + c];
-      oMi[12 + 9] = qv[0]; oMi[12 + 10] = qv[1]; oMi[12 + 11] = qv[2];
-    }
-  }
+    pk_fk_seed(oMi, sc, qv, scq0, scq1, s);
     WSYNC();
+    // pk_fk_sweep<ROT>(oMi, sc, qv, M, P.pk_fk, fkn, s), written out: through the call this site alone costs the <QCON, ROT, TP> instantiation
+    // 16 B of scratch and 4 VGPR spills. Keep it the sweep's text, statement for statement.
 #pragma unroll 1
-  for (int L = 0; L < 5; ++L) {   // (second pass)
-    const DevPlan::PkJoint fk = fkn;
-    if (L + 1 < 5) fkn = P.pk_fk[L + 1][s];          // next level's record is on its way while this level is computed
-    const int j = fk.joint;
-    if (j >= 0) {
-      const bool rev = fk.rev != 0;
-      const int a0 = fk.a0, a1 = fk.a1, a2 = fk.a2;
-      const double* Pp = oMi + 12 * fk.parent;
-      const double sn = rev ? sc[2 * j] : 0.0, cs = rev ? sc[2 * j + 1] : 1.0;
-      const double pris = rev ? 0.0 : qv[fk.q_idx];
-      if (ROT && fk.rot) {   // rotated placement (ROT instantiations only: the others compile exactly as before)
-        fk_place_rot_lds(oMi + 12 * j, Pp, M.rp[j], a0, a1, a2, sn, cs, pris);
-      } else {
-        double Av[3], Bv[3], Cv[3], Pv[3];
+    for (int L = 0; L < 5; ++L) {
+      const DevPlan::PkJoint fk = fkn;
+      if (L + 1 < 5) fkn = P.pk_fk[L + 1][s];
+      const int j = fk.joint;
+      if (j >= 0) {
+        const bool rev = fk.rev != 0;
+        const int a0 = fk.a0, a1 = fk.a1, a2 = fk.a2;
+        const double* Pp = oMi + 12 * fk.parent;
+        const double sn = rev ? sc[2 * j] : 0.0, cs = rev ? sc[2 * j + 1] : 1.0;
+        const double pris = rev ? 0.0 : qv[fk.q_idx];
+        if (ROT && fk.rot) {
+          fk_place_rot_lds(oMi + 12 * j, Pp, M.rp[j], a0, a1, a2, sn, cs, pris);
+        } else {
+          double Av[3], Bv[3], Cv[3], Pv[3];
 #pragma unroll
-        for (int rr = 0; rr < 3; ++rr) { Av[rr] = Pp[a0 + rr]; Bv[rr] = Pp[a1 + rr]; Cv[rr] = Pp[a2 + rr]; Pv[rr] = Pp[9 + rr]; }
-        double* Po = oMi + 12 * j;
+          for (int rr = 0; rr < 3; ++rr) { Av[rr] = Pp[a0 + rr]; Bv[rr] = Pp[a1 + rr]; Cv[rr] = Pp[a2 + rr]; Pv[rr] = Pp[9 + rr]; }
+          double* Po = oMi + 12 * j;
 #pragma unroll
-        for (int rr = 0; rr < 3; ++rr) {
-          Po[a0 + rr] = Av[rr];
-          Po[a1 + rr] = cs * Bv[rr] + sn * Cv[rr];
-          Po[a2 + rr] = cs * Cv[rr] - sn * Bv[rr];
-          Po[9 + rr] = Pv[rr] + Av[rr] * (fk.t0 + pris) + Bv[rr] * fk.t1 + Cv[rr] * fk.t2;
+          for (int rr = 0; rr < 3; ++rr) {
+            Po[a0 + rr] = Av[rr];
+            Po[a1 + rr] = cs * Bv[rr] + sn * Cv[rr];
+            Po[a2 + rr] = cs * Cv[rr] - sn * Bv[rr];
+            Po[9 + rr] = Pv[rr] + Av[rr] * (fk.t0 + pris) + Bv[rr] * fk.t1 + Cv[rr] * fk.t2;
+          }
         }
       }
+      WSYNC();
     }
-    WSYNC();
-  }
     lin0[0] = lin0[1] = lin0[2] = 0.0; ang0[0] = ang0[1] = ang0[2] = 0.0; lin1[0] = lin1[1] = lin1[2] = 0.0;
-    if (s < n) {
-      const double* Pj = oMi + 12 * c0_joint;
-      const double pj[3] = {Pj[9], Pj[10], Pj[11]};
-      if (c0_ang >= 0) { ang0[0] = Pj[3 * c0_ang]; ang0[1] = Pj[3 * c0_ang + 1]; ang0[2] = Pj[3 * c0_ang + 2]; cross3(pj, ang0, lin0); }
-      if (c0_lin >= 0) { lin0[0] = Pj[3 * c0_lin]; lin0[1] = Pj[3 * c0_lin + 1]; lin0[2] = Pj[3 * c0_lin + 2]; }
-    }
-    if (s < nl) {
-      const double* Pj = oMi + 12 * c1_joint;
-      const double pj[3] = {Pj[9], Pj[10], Pj[11]};
-      if (c1_ang >= 0) { const double a1[3] = {Pj[3 * c1_ang], Pj[3 * c1_ang + 1], Pj[3 * c1_ang + 2]}; cross3(pj, a1, lin1); }
-      if (c1_lin >= 0) { lin1[0] = Pj[3 * c1_lin]; lin1[1] = Pj[3 * c1_lin + 1]; lin1[2] = Pj[3 * c1_lin + 2]; }
-    }
+    if (s < n) pk_jac_col(oMi, c0_joint, c0_lin, c0_ang, lin0, ang0);
+    if (s < nl) { double a1[3]; pk_jac_col(oMi, c1_joint, c1_lin, c1_ang, lin1, a1); }
     {
       const double* Pr = oMi + 12 * M.frame_joint[WBC_FR_TRUNK];
 #pragma unroll
@@ -503,16 +396,8 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
   }
   // ---- velDamperJointConstraints (:572-637): of reduced variable s and of leg DoF s
   double lb = 0.0, ub = 0.0, lb1 = 0.0, ub1 = 0.0;
-  {
-    auto damper = [&](const double qi, const double lo, const double hi, const double vm, double& l_, double& u_) {
-      if (qi <= lo + dqi) { l_ = -dcoef * (qi - lo - dqs) / (dqi - dqs); if (l_ > vm) l_ = vm; if (l_ < -vm) l_ = -vm; } else l_ = -vm;
-      if (qi >= hi - dqi) { u_ = dcoef * (hi - qi - dqs) / (dqi - dqs); if (u_ < -vm) u_ = -vm; if (u_ > vm) u_ = vm; } else u_ = vm;
-      if (l_ > 0) l_ = -l_;
-      if (u_ < 0) u_ = -u_;
-    };
-    if (s < n) damper(qv[dq0], dlo0, dhi0, dvm0, lb, ub);
-    if (s < nl) damper(qv[dq1], dlo1, dhi1, dvm1, lb1, ub1);
-  }
+  if (s < n) damper_bounds(qv[dq0], dlo0, dhi0, dvm0, dcoef, dqi, dqs, lb, ub);
+  if (s < nl) damper_bounds(qv[dq1], dlo1, dhi1, dvm1, dcoef, dqi, dqs, lb1, ub1);
   WSYNC();
 
   // ---- G_e = -K_e^-1 B_e: lane l = 3 f + i owns row i of foot f (the base block B is the same for every foot)

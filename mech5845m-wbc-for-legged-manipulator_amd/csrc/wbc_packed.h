@@ -1,4 +1,8 @@
-// wbc_packed.h — lane helpers and the LDS layout shared by the packed kernels (four instances per wavefront, lane = 16 r + s).
+// wbc_packed.h — what the packed kernels share (four instances per wavefront, lane = 16 r + s): the packed sim3 tick's LDS layout, the DPP
+// row reductions, chol_sweep2, the wave order, and the kinematics and input staging every packed tick / update kernel runs — the FK seed and
+// level sweep (pk_fk_seed, pk_fk_sweep), the WORLD Jacobian column of a DoF (pk_jac_col), calcTargetVelTrunk2 (pk_trunk_target_vel) with its
+// inputs (pk_trunk_input), the EE orientation feed-forward (pk_ee_omega) and the staged weights image (pk_stage_weights). The per-DoF
+// velocity damper and the Euler matrix, which the one-instance kernels use too, are in wbc_common.h (damper_bounds, euler_to_R).
 #pragma once
 #include "wbc_common.h"
 
@@ -194,5 +198,154 @@ __device__ __forceinline__ void wo_record(WaveOrder* wo, const int B, const int 
 constexpr int QLEV = 6;
 static_assert(offsetof(WbcConfig, joint_w) - offsetof(WbcConfig, ee_W) == 84 * sizeof(double), "ee_W [30] ee_w [5] ee_gain [30] trunk [13] com_W [3] com_gain [3] joint_w");
 constexpr int WT_W = 0, WT_w = 30, WT_G = 35, WT_CW = 78, WT_CG = 81;   // offsets inside wt
+
+// ---- the packed kinematics (tick kernels: sim3p over DevPlan.pk_fk, orthp / boxp over DevPlan.q_fk; wbc_update_packed_kernel over pk_fk).
+// oMi [joint][12]: R column-major then p; sc: sin / cos of joint j at 2 j; qv: the staged configuration.
+// Seed: sin / cos of the joint angles, two joints per lane (joint j >= 2 reads q[idx_q[j]]: scq0 / scq1 = DevPlan.pk_scq / q_scq of joints 2 + s,
+// 18 + s), and the root free-flyer (joint 1) on lane 0: R from the quaternion exactly as Eigen's toRotationMatrix, p = xyz. The caller fences.
+__device__ __forceinline__ void pk_fk_seed(double* const oMi, double* const sc, const double* const qv, const int scq0, const int scq1, const int s) {
+  if (scq0 >= 0) { const SinCos t = sincos_cw(qv[scq0]); sc[2 * (2 + s)] = t.s; sc[2 * (2 + s) + 1] = t.c; }
+  if (scq1 >= 0) { const SinCos t = sincos_cw(qv[scq1]); sc[2 * (18 + s)] = t.s; sc[2 * (18 + s) + 1] = t.c; }
+  if (s == 0) {
+    double Rt[9];
+    quat_to_R(qv + 3, Rt);
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+      for (int rr = 0; rr < 3; ++rr) oMi[12 + 3 * c + rr] = Rt[3 * rr + c];
+    oMi[12 + 9] = qv[0]; oMi[12 + 10] = qv[1]; oMi[12 + 11] = qv[2];
+  }
+}
+// pin.forwardKinematics, level by level (Robot_Wrapper4.py:400): lane s places the joint of sched[L][s] (joint -1: none) on its parent's placement.
+// fkn: the caller's register record holding sched[0][s], loaded well before (its latency is hidden behind the caller's own work); the next
+// level's record is on its way while a level is computed (L1-resident tables: kept live for all levels the records cost 60 VGPRs).
+// ROT: the batch holds a model with a rotated joint placement; the instantiations without it compile to exactly the code they had before the
+// flag existed. Ends fenced: oMi is complete on return.
+template <bool ROT, int NLEV>
+__device__ __forceinline__ void pk_fk_sweep(double* const oMi, const double* const sc, const double* const qv, const DevModel& M,
+                                            const DevPlan::PkJoint (&sched)[NLEV][16], DevPlan::PkJoint& fkn, const int s) {
+#pragma unroll 1
+  for (int L = 0; L < NLEV; ++L) {
+    const DevPlan::PkJoint fk = fkn;
+    if (L + 1 < NLEV) fkn = sched[L + 1][s];
+    const int j = fk.joint;
+    if (j >= 0) {
+      const bool rev = fk.rev != 0;
+      const int a0 = fk.a0, a1 = fk.a1, a2 = fk.a2;
+      const double* Pp = oMi + 12 * fk.parent;
+      const double sn = rev ? sc[2 * j] : 0.0, cs = rev ? sc[2 * j + 1] : 1.0;
+      const double pris = rev ? 0.0 : qv[fk.q_idx];
+      if (ROT && fk.rot) {
+        fk_place_rot_lds(oMi + 12 * j, Pp, M.rp[j], a0, a1, a2, sn, cs, pris);
+      } else {
+        double Av[3], Bv[3], Cv[3], Pv[3];
+#pragma unroll
+        for (int rr = 0; rr < 3; ++rr) { Av[rr] = Pp[a0 + rr]; Bv[rr] = Pp[a1 + rr]; Cv[rr] = Pp[a2 + rr]; Pv[rr] = Pp[9 + rr]; }
+        double* Po = oMi + 12 * j;
+#pragma unroll
+        for (int rr = 0; rr < 3; ++rr) {
+          Po[a0 + rr] = Av[rr];
+          Po[a1 + rr] = cs * Bv[rr] + sn * Cv[rr];
+          Po[a2 + rr] = cs * Cv[rr] - sn * Bv[rr];
+          Po[9 + rr] = Pv[rr] + Av[rr] * (fk.t0 + pris) + Bv[rr] * fk.t1 + Cv[rr] * fk.t2;
+        }
+      }
+    }
+    WSYNC();
+  }
+}
+// WORLD Jacobian column of a DoF from oMi: the DoF's joint, and which column of its R is the linear / angular axis (-1: none). lin and ang come in
+// zero; a column whose angular part the caller has no use for passes a scratch ang.
+__device__ __forceinline__ void pk_jac_col(const double* const oMi, const int joint, const int lin_axis, const int ang_axis, double (&lin)[3],
+                                           double (&ang)[3]) {
+  const double* Pj = oMi + 12 * joint;
+  const double pj[3] = {Pj[9], Pj[10], Pj[11]};
+  if (ang_axis >= 0) { ang[0] = Pj[3 * ang_axis]; ang[1] = Pj[3 * ang_axis + 1]; ang[2] = Pj[3 * ang_axis + 2]; cross3(pj, ang, lin); }
+  if (lin_axis >= 0) { lin[0] = Pj[3 * lin_axis]; lin[1] = Pj[3 * lin_axis + 1]; lin[2] = Pj[3 * lin_axis + 2]; }
+}
+
+// ---- input staging of the tick kernels
+// Entry k of the trunk task's 18 inputs: trunk_target [3], prev_trunk_target [3], trunk_ref_euler [3], trunk_prev_rot [9]
+__device__ __forceinline__ double pk_trunk_input(const WbcTickIn& in, const int b, const int k) {
+  return (k < 3) ? in.trunk_target[(size_t)b * 3 + k] : (k < 6) ? in.prev_trunk_target[(size_t)b * 3 + (k - 3)]
+       : (k < 9) ? in.trunk_ref_euler[(size_t)b * 3 + (k - 6)] : in.trunk_prev_rot[(size_t)b * 9 + (k - 9)];
+}
+// calcTargetVelEE3's orientation feed-forward (Robot_Wrapper4.py:1125-1133): omega = vee(((R* - R*_prev) / dt) R*^T), one component per lane
+// (EE s / 3, component s % 3), straight from the caller's [B][5][9] references; zero when none are passed
+__device__ __forceinline__ double pk_ee_omega(const WbcTickIn& in, const int b, const int s, const double inv_dt) {
+  double om = 0.0;
+  if (in.ee_ref_rot && s < 15) {
+    const int e = s / 3, i = s - 3 * e;
+    const double* Rs = in.ee_ref_rot + (size_t)b * 45 + 9 * e;
+    const double* Rp = in.ee_prev_rot + (size_t)b * 45 + 9 * e;
+    const int ra = (i == 0) ? 6 : ((i == 1) ? 0 : 3), rb = (i == 0) ? 3 : ((i == 1) ? 6 : 0);   // S[2][1] = D row 2 . R row 1; S[0][2]; S[1][0]
+    om = ((Rs[ra] - Rp[ra]) * inv_dt) * Rs[rb] + ((Rs[ra + 1] - Rp[ra + 1]) * inv_dt) * Rs[rb + 1] + ((Rs[ra + 2] - Rp[ra + 2]) * inv_dt) * Rs[rb + 2];
+  }
+  return om;
+}
+// The weights and gains image wt: the 85 contiguous doubles of the configuration's block (WT_* offsets), or with TP of the instance's row, six per
+// lane; entries 85 .. ncfg - 1 (ncfg = 85, or 89: + trunk_box_z_frac, _ang, _scale, com_box_scale) stay the configuration's, the rest of wt [96]
+// is zero. Returns whether the row is refused (tp_row_bad16's rule): the image is then the configuration's block and the instance reports
+// WBC_QP_NUMERICAL. Without TP, tps is never read.
+template <bool TP>
+__device__ __forceinline__ bool pk_stage_weights(double* const wt, const WbcConfig& cfg, const WbcTaskParams* const tps, const int b, const int s,
+                                                 const int rbase, const int ncfg) {
+  const double* cw = &cfg.ee_W[0][0];
+  bool tpbad = false;
+  if (TP) {
+    const double* rw = reinterpret_cast<const double*>(tps + b);
+    bool bad = false;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+      const int k = s + 16 * i;
+      const double v = (k < WBC_TASK_PARAMS_DOUBLES) ? rw[k] : ((k < ncfg) ? cw[k] : 0.0);
+      bad = bad || (k < WBC_TASK_PARAMS_DOUBLES && tp_entry_bad(k, v));
+      wt[s + 16 * i] = v;
+    }
+    tpbad = ((__ballot(bad) >> rbase) & 0xFFFFull) != 0ull;
+  }
+  if (!TP || tpbad) {
+#pragma unroll
+    for (int i = 0; i < 6; ++i) wt[s + 16 * i] = (s + 16 * i < ncfg) ? cw[s + 16 * i] : 0.0;
+  }
+  return tpbad;
+}
+// calcTargetVelTrunk2 (Robot_Wrapper4.py:948-1015): the trunk task's target velocity vel [6] from the staged inputs alone — the trunk frame is
+// the free-flyer's own placement (the plan checks it). tin: pk_trunk_input's 18 entries; tw: trunk_W [0..5], trunk_w [6], trunk_gain [7..12];
+// sh [12]: LDS scratch of the instance (the six sines / cosines of the reference angles and their halves, one per lane); Rt: the trunk's
+// rotation, row-major, for the caller that goes on with it. Fences once inside (sh); the staged inputs are visible on entry.
+// Bug-compatible with the reference on purpose: qe2's first two terms cancel (:976), and the skew matrix is D R*, not D R*^T (:984).
+__device__ __forceinline__ void pk_trunk_target_vel(const double* const qv, const double* const tin, const double* const tw, double* const sh,
+                                                    const double inv_dt, const int s, double (&Rt_)[9], double (&vel)[6]) {
+  const double* xt = tin;
+  const double* xp = tin + 3;
+  const double* er = tin + 6;
+  double fq[4], rq[4], Rs[9];
+  quat_to_R(qv + 3, Rt_);
+  R_to_quat(Rt_, fq);
+  {
+    const SinCos t = sincos_cw(s < 3 ? er[s < 3 ? s : 0] : 0.5 * er[(s < 6 ? s : 3) - 3]);   // reference angles and their halves, one per lane
+    if (s < 6) { sh[2 * s] = t.s; sh[2 * s + 1] = t.c; }
+    WSYNC();
+    const double sa = sh[0], ca = sh[1], sb = sh[2], cb = sh[3], sc_ = sh[4], cc = sh[5];
+    euler_to_R(sa, ca, sb, cb, sc_, cc, Rs);
+    const double qx[4] = {sh[6], 0, 0, sh[7]}, qy[4] = {0, sh[8], 0, sh[9]}, qz[4] = {0, 0, sh[10], sh[11]};
+    double tq[4];
+    quat_mul(qy, qx, tq);
+    quat_mul(qz, tq, rq);
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i) vel[i] = (xt[i] - xp[i]) * inv_dt + tw[7 + i] * ((xt[i] - qv[i]) * inv_dt);
+  const double qe0 = fq[3] * rq[0] - fq[0] * rq[3] + fq[1] * rq[2] - fq[2] * rq[1];   // :974
+  const double qe1 = fq[3] * rq[1] - fq[1] * rq[3] - fq[0] * rq[2] + fq[2] * rq[0];   // :975
+  const double qe2 = fq[3] * rq[2] - fq[3] * rq[2] + fq[0] * rq[1] - fq[1] * rq[0];   // :976 (sic)
+  double D[9];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) D[i] = (Rs[i] - tin[9 + i]) * inv_dt;
+  // skew = D Rs (R*, not R*^T: :984); omega = (S[2][1], S[0][2], S[1][0]) + K qe
+  vel[3] = (D[6] * Rs[1] + D[7] * Rs[4] + D[8] * Rs[7]) + tw[10] * qe0;
+  vel[4] = (D[0] * Rs[2] + D[1] * Rs[5] + D[2] * Rs[8]) + tw[11] * qe1;
+  vel[5] = (D[3] * Rs[0] + D[4] * Rs[3] + D[5] * Rs[6]) + tw[12] * qe2;
+}
 
 }  // namespace wbc
