@@ -31,6 +31,10 @@ namespace wbc {
 #define RARE(c) __builtin_expect(!!(c), 0)
 #endif
 #define COLD_MARK() asm volatile("; WBC_COLD")
+// Issue order: the wave order's atomic is issued at the end of the dual loop and waited for at the end of the kernel; the FK seed
+// evaluates its two sines / cosines in one block (wbc_packed.h). Operations and operands are unchanged, results bit for bit the same. A/B switches
+// (make variant VFLAGS=-D...): SIM3P_LATE_ATOMIC issues the atomic right before its result is used, PK_SEED_SERIAL gives each joint's sine /
+// cosine its own branch.
 #ifndef SIM3P_WAVES
 #define SIM3P_WAVES 2      // waves per SIMD the register allocation is made for (3: an experiment, tools/hot_path_spills.py with WBC_XFLAGS="-DSIM3P_WAVES=3 -DWBC_NO_TAIL")
 #endif
@@ -1032,6 +1036,12 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
       if (stepping) drop_l = l;             // blocking slot: dropped at the top of the next pass, then the step is retried
     }
   }
+#ifndef SIM3P_LATE_ATOMIC
+  // the wave order's record: the classes are final here, so the atomic goes out now and its round trip runs behind the refinement and the outputs
+  const int wocls = wo_class(iters, flagged);
+  WoPost wop = {0ull, 0ull, 0u, 0u, WO_NS + 1, 0};
+  if (A.worder) wop = wo_post(A.worder, grp, valid, wocls, r, s);
+#endif
   // ================================ iterative refinement ==========================================
   // One step at the final working set (QP_Wrapper.py:37 asks qpOASES for numRefinementSteps = 100; oracle: qp_refine). With the slots' normals
   // n_k, right-hand sides b_k and multipliers u_k:   r1 = -(grad f(y) - sum u_k n_k),  r2_k = b_k - n_k'y,   dy = J1 T' r2 + J2 J2' r1.
@@ -1201,7 +1211,13 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
       if (s < NQ - nq) qn[nq + s] = 0.0;
     }
   }
-  if (A.worder) wo_record(A.worder, A.B, grp, valid, b, wo_class(iters, flagged), r, s);   // (this launch's record: the next launch's order)
+  if (A.worder) {                           // (this launch's record: the next launch's order)
+#ifdef SIM3P_LATE_ATOMIC
+    const int wocls = wo_class(iters, flagged);
+    const WoPost wop = wo_post(A.worder, grp, valid, wocls, r, s);
+#endif
+    wo_finish(A.worder, A.B, valid, b, wocls, r, s, wop);
+  }
   // ---- the tail: an instance left out above (a stance-leg block of rank < 2 — never seen on the benchmark distribution — or the
   // diagnostic dbg_force_defer) is redone here, by this wave, on the general path (process_instance, one instance per wavefront, LDS
   // shared with the packed layout). No list, no second launch, and a batch that defers everything runs at the general kernel's occupancy.

@@ -159,31 +159,52 @@ __device__ __forceinline__ int wo_instance(WaveOrder* __restrict__ wo, const int
 // offsets from the final word, the list, the batch size it was built for, or 0 if the slice did not count each of its instances once — and zeroes
 // the word the next launch will append to. No host sequence number: a captured graph replays this as it is. The lists are read by the next launch
 // only. `valid`: the row holds an instance (b, class cls: uniform over the row).
-__device__ __forceinline__ void wo_record(WaveOrder* wo, const int B, const int grp, const bool valid, const int b, const int cls, const int r,
-                                          const int s) {
-  const int ns = wo_slices(), G = (int)gridDim.x;
-  if (ns > WO_NS) return;
-  const int g = grp % ns;
-  WaveOrder& sl = wo[g];
-  const uint32_t cur = sl.cur & 1u, nxt = cur ^ 1u;
+// In two halves, so that the atomic's round trip runs behind the work between them: wo_post forms the wave's word and ISSUES the
+// atomic — as soon as the classes are final, which is at the end of the dual loop — and wo_finish, at the end of the kernel, is the first to wait
+// for the word that comes back: the list stores and the slice's publish step. A wave is counted at its post, so the publishing wave may find others
+// of its slice still before their list stores; like the lists themselves, what it publishes is read by the next launch only. The slice's `cur` is
+// read by wo_post, BEFORE the wave is counted, and handed on: once posted, the slice's block may be republished under this wave (a slice is
+// published when every one of its waves has posted), so wo_finish must not read it again.
+struct WoPost { unsigned long long old, add; unsigned same; uint32_t cur; int ns, g; };   // old: in lane 0 alone, still in flight
+__device__ __forceinline__ WoPost wo_post(WaveOrder* wo, const int grp, const bool valid, const int cls, const int r, const int s) {
+  WoPost t; t.old = 0ull; t.add = 1ull << 54; t.same = 0u; t.cur = 0u;
+  t.ns = wo_slices(); t.g = grp % t.ns;
+  if (t.ns > WO_NS) return t;
+  t.cur = wo[t.g].cur & 1u;
   const unsigned long long vm = __ballot(valid && s == 0);
-  unsigned same = 0u;
-  unsigned long long add = 1ull << 54;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const int ck = __builtin_amdgcn_readlane(cls, 16 * k);
     const bool vk = (vm >> (16 * k)) & 1ull;
-    same |= (vk && ck == cls) ? 1u << k : 0u;
-    add += vk ? 1ull << (9 * ck) : 0ull;
+    t.same |= (vk && ck == cls) ? 1u << k : 0u;
+    t.add += vk ? 1ull << (9 * ck) : 0ull;
   }
-  unsigned long long old = 0ull;
-  if (r == 0 && s == 0) old = atomicAdd(&sl.word[nxt], add);
-  old = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(old >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)old);
-  const uint32_t at = (uint32_t)((old >> (9 * cls)) & 511ull) + (uint32_t)__popc(same & ((1u << r) - 1u));
+  if (r == 0 && s == 0) {
+#ifdef SIM3P_LATE_ATOMIC
+    t.old = atomicAdd(&wo[t.g].word[t.cur ^ 1u], t.add);
+#else
+    // (the word's index goes through an opaque VGPR: with an address it can prove uniform the compiler's atomic optimizer rewrites the operation
+    //  as "first active lane adds, then broadcast" and waits for the result on the spot)
+    uint32_t wi = t.cur ^ 1u;
+    asm volatile("" : "+v"(wi));
+    t.old = atomicAdd(&wo[t.g].word[wi & 1u], t.add);
+#endif
+  }
+  return t;
+}
+__device__ __forceinline__ void wo_finish(WaveOrder* wo, const int B, const bool valid, const int b, const int cls, const int r, const int s,
+                                          const WoPost& t) {
+  const int ns = t.ns, g = t.g, G = (int)gridDim.x;
+  if (ns > WO_NS) return;
+  WaveOrder& sl = wo[g];
+  const uint32_t cur = t.cur, nxt = cur ^ 1u;
+  const unsigned long long old =
+      ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(t.old >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)t.old);
+  const uint32_t at = (uint32_t)((old >> (9 * cls)) & 511ull) + (uint32_t)__popc(t.same & ((1u << r) - 1u));
   if (valid && s == 0 && at < WO_CAP) wo_list(wo, nxt, g, cls)[at] = (uint32_t)b;
   const uint32_t nwaves = (uint32_t)((G - g + ns - 1) / ns);                     // waves of slice g
   if (r == 0 && s == 0 && (uint32_t)(old >> 54) == nwaves - 1u) {
-    const unsigned long long fin = old + add;
+    const unsigned long long fin = old + t.add;
     uint32_t n = 0u;
 #pragma unroll
     for (int c = 0; c < WO_NCLS; ++c) { sl.off[c] = n; n += (uint32_t)((fin >> (9 * c)) & 511ull); }
@@ -204,8 +225,17 @@ constexpr int WT_W = 0, WT_w = 30, WT_G = 35, WT_CW = 78, WT_CG = 81;   // offse
 // Seed: sin / cos of the joint angles, two joints per lane (joint j >= 2 reads q[idx_q[j]]: scq0 / scq1 = DevPlan.pk_scq / q_scq of joints 2 + s,
 // 18 + s), and the root free-flyer (joint 1) on lane 0: R from the quaternion exactly as Eigen's toRotationMatrix, p = xyz. The caller fences.
 __device__ __forceinline__ void pk_fk_seed(double* const oMi, double* const sc, const double* const qv, const int scq0, const int scq1, const int s) {
+#ifdef PK_SEED_SERIAL      // (A/B variant builds only: each joint's sine and cosine inside its own branch, as before DESIGN.md §3.23)
   if (scq0 >= 0) { const SinCos t = sincos_cw(qv[scq0]); sc[2 * (2 + s)] = t.s; sc[2 * (2 + s) + 1] = t.c; }
   if (scq1 >= 0) { const SinCos t = sincos_cw(qv[scq1]); sc[2 * (18 + s)] = t.s; sc[2 * (18 + s) + 1] = t.c; }
+#else
+  // both joints' angles in one straight-line block, so that their four polynomial chains interleave; a lane without a joint computes on 0 and
+  // stores nothing (the same operations on the same values for the joints that exist: bit for bit the same table)
+  const double a0 = qv[scq0 >= 0 ? scq0 : 0], a1 = qv[scq1 >= 0 ? scq1 : 0];
+  const SinCos t0 = sincos_cw(scq0 >= 0 ? a0 : 0.0), t1 = sincos_cw(scq1 >= 0 ? a1 : 0.0);
+  if (scq0 >= 0) { sc[2 * (2 + s)] = t0.s; sc[2 * (2 + s) + 1] = t0.c; }
+  if (scq1 >= 0) { sc[2 * (18 + s)] = t1.s; sc[2 * (18 + s) + 1] = t1.c; }
+#endif
   if (s == 0) {
     double Rt[9];
     quat_to_R(qv + 3, Rt);

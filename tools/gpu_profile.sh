@@ -2,7 +2,7 @@
 # Runs on the GPU box (via gpurun): kernel-trace stats + PMC passes of the bench command, each pass its own
 # rocprofv3 run (counters never combined with trace domains other than kernel-trace). Output under gpurun_out/$1.
 # A step that hits its timeout aborts the script (no further GPU work after a kill).
-# PASSES=ifetch runs only the instruction-fetch / instruction-cache passes: --pmc alone, no tracing of any kind, at the bench
+# PASSES=chain runs the kernel-trace stats and one pass of wave-cycle / wait counters. PASSES=ifetch runs only the instruction-fetch / instruction-cache passes: --pmc alone, no tracing of any kind, at the bench
 # batch and at B = 4 (one wavefront alone on the device); WBC_HIP_LIB picks the library as everywhere. Default: everything.
 set -u
 TAG=${1:-prof}
@@ -40,12 +40,19 @@ PY
 }
 trap condense EXIT
 PASSES=${PASSES:-all}
+pmc() { step "pmc_$1" 200 rocprofv3 --kernel-trace --pmc ${@:2} --output-format csv -d "$OUT/pmc_$1" -- $BENCH; }
+if [ "$PASSES" = chain ]; then
+# the length of a wave's dependent chain: the kernel's mean time, then ONE counter pass — wave cycles and waits against the
+# instruction counts, which a change of issue order leaves alone
+step stats 200 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 bench.py --rollout-ticks 0 --no-cpu-baseline ${BENCH_ARGS:-}
+pmc chain SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_LDS GRBM_GUI_ACTIVE
+exit 0
+fi
 if [ "$PASSES" = all ]; then
 step list 60 rocprofv3 -L
 # kernel time: the bench command in its default shape (3 warm-up + 5 x 20 timed steps), so that the kernel average covers the same launches
 # as bench.py's own HIP events (stats.log holds that run's JSON line: roofline.kernel_ms = the median block, repeats.kernel_ms_per_step = all)
 step stats 200 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 bench.py --rollout-ticks 0 --no-cpu-baseline ${BENCH_ARGS:-}
-pmc() { step "pmc_$1" 200 rocprofv3 --kernel-trace --pmc ${@:2} --output-format csv -d "$OUT/pmc_$1" -- $BENCH; }
 pmc inst SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM SQ_INSTS_VMEM
 pmc cyc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS
 pmc lds SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_LDS_ADDR_CONFLICT SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_VALU_MFMA_BUSY_CYCLES
