@@ -168,6 +168,7 @@ struct KernelArgs {
 // The kernel parameters of every tick kernel (wbc_tick_kernel, wbc_tick_sim3p / orthp / boxp_kernel): KernelArgs, the three tables, then the
 // per-instance rows [B] (wbc_tick_tp & co.; nullptr for the instantiations without TP, which never read it). KernelArgs keeps its size, so that
 // the kernels without rows keep their code; the packed kernels' tail reads `tp` back through the kernarg segment like KernelArgs itself.
+// (wbc_tick_sim3p_kernel alone has a sixth parameter behind these: the wave order's launch constants, wbc_wave_geom.h WoGeom.)
 struct TpKernarg {
   KernelArgs A;
   const DevModel* models;

@@ -35,6 +35,10 @@ namespace wbc {
 // evaluates its two sines / cosines in one block (wbc_packed.h). Operations and operands are unchanged, results bit for bit the same. A/B switches
 // (make variant VFLAGS=-D...): SIM3P_LATE_ATOMIC issues the atomic right before its result is used, PK_SEED_SERIAL gives each joint's sine /
 // cosine its own branch.
+// What is not arithmetic: the row reductions use the DPP helpers without the operand copy (wbc_packed.h rsum16a / rmin16a / ror16a:
+// every call site here is in wave-uniform control flow, all 64 lanes active — keep it so, or use rsum16 & co.), and the wave order's index
+// arithmetic runs on launch constants (the kernel's sixth parameter, wbc_wave_geom.h). A/B switches: SIM3P_DPP_COPY and SIM3P_WO_DIVIDE bring the
+// old forms back.
 #ifndef SIM3P_WAVES
 #define SIM3P_WAVES 2      // waves per SIMD the register allocation is made for (3: an experiment, tools/hot_path_spills.py with WBC_XFLAGS="-DSIM3P_WAVES=3 -DWBC_NO_TAIL")
 #endif
@@ -49,7 +53,7 @@ __attribute__((amdgpu_waves_per_eu(SIM3P_NUM_VGPR, SIM3P_NUM_VGPR)))
 #endif
 __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const KernelArgs A, const DevModel* __restrict__ models,
                                                                const WbcConfig* __restrict__ cfgs, const DevPlan* __restrict__ plans,
-                                                               const WbcTaskParams* __restrict__ tps) {
+                                                               const WbcTaskParams* __restrict__ tps, const WoGeom wg) {
   // (the general kernel's layout shares the allocation: an instance this kernel cannot reduce — a stance-leg block of rank < 2 — is
   //  redone on the general path by the SAME wave at the end, see the tail; both layouts leave 8 waves per CU)
 #ifdef SIM3P_NUM_VGPR      // (compile-only experiment: with the LDS size unknown to the compiler the occupancy attribute alone decides the register budget)
@@ -72,7 +76,7 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
   const int grp = (int)blockIdx.x;
   const int pos = 4 * grp + r;
   const bool valid = pos < A.B;
-  const int b = valid ? wo_instance(A.worder, A.B, grp, r, pos) : A.B - 1;
+  const int b = valid ? wo_instance(A.worder, wg, A.B, grp, r, pos) : A.B - 1;
   int mid = 0;
   if (A.in.model_id) { mid = A.in.model_id[b]; mid = mid < 0 ? 0 : (mid >= A.n_models ? A.n_models - 1 : mid); }
   const DevModel& M = models[mid];
@@ -535,7 +539,7 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
       // (any of the six slots may be taken, also one that an earlier swap already gave to a leg velocity: the base parts of the
       //  kept rows all lie in the 3-dimensional row space of B, so a fourth pivoted foot finds its pivot only there)
       const double cand = (on && s < 6) ? fabs(Ec) : -1.0;
-      const double emax = -rmin16(-cand);
+      const double emax = -rmin16a(-cand);
       const int cstar_ = __ffs((int)((__ballot(cand == emax && cand >= 0.0) >> rbase) & 0xFFFFull)) - 1;
       const int cstar = cstar_ < 0 ? 0 : cstar_;
       const double Ecs = bperm(Ec, rbase + cstar);
@@ -673,7 +677,7 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
   double sq = 0.0;
 #pragma unroll
   for (int k = 0; k < PV; ++k) sq = fma(y[k], y[k], sq);
-  const double jf2 = rsum16(s < PV ? sq : 0.0);
+  const double jf2 = rsum16a(s < PV ? sq : 0.0);
   double* const J = I.M2;
   double* const T = I.M1;
   if (!QCON) {                              // the Grip image of reduced variable s comes back from LDS before J takes its place (free registers across the sweep)
@@ -844,7 +848,7 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
     WSYNC();
     V.xv[s] = x;
     WSYNC();
-    const double near = 0.25 * fmax(1.0, -rmin16(has_b ? -fabs(x) : 0.0));
+    const double near = 0.25 * fmax(1.0, -rmin16a(has_b ? -fabs(x) : 0.0));
     double vr = 0.0;
     if (has_r) {
       const double2a c0 = lds2(I.Cq + s * 6), c1 = lds2(I.Cq + s * 6 + 2), c2 = lds2(I.Cq + s * 6 + 4);
@@ -877,7 +881,7 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
       WSYNC();
       V.dv[s] = d; V.yv[s] = (s >= q) ? d : 0.0;
       WSYNC();
-      const double zn = rsum16(s >= q ? d * d : 0.0);
+      const double zn = rsum16a(s >= q ? d * d : 0.0);
       const Zr zr = products(__ballot(seeding && q > 0) != 0);
       const bool add = seeding && (zn > 100.0 * n * EPS2 * jf2 * np2);      // (a dependent seed is simply not taken)
       if (__ballot(add)) {
@@ -917,7 +921,7 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
       bool restoring = seeded, did = false, again = false;
 #pragma unroll 1
       for (;;) {
-        const double um = rmin16((s < q) ? u : 0.0);
+        const double um = rmin16a((s < q) ? u : 0.0);
         bool rest = restoring && (um < 0.0);
         if (rest && ++iters > max_iter) { status = WBC_QP_MAX_ITER; rest = false; restoring = false; searching = false; }
         if (!RARE(__ballot(rest) != 0)) {   // (rare per PASS of this loop even where seeds are dropped often: a few drops against every pass
@@ -964,7 +968,7 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
       if (clb > -QP_INF) { const double sl = v - clb; if (sl < -1e-9 * fmax(1.0, fabs(clb)) && sl < best) { best = sl; code = n + s; cand_b = clb; cand_n2 = cn2; } }
       if (cub < QP_INF) { const double sl = cub - v; if (sl < -1e-9 * fmax(1.0, fabs(cub)) && sl < best) { best = sl; code = (n + s) | 256; cand_b = -cub; cand_n2 = cn2; } }
     }
-    const double worst = rmin16(best);
+    const double worst = rmin16a(best);
     if (searching && !(worst < 0.0)) searching = false;               // primal feasible -> this row is optimal
 #ifdef WBC_ABLATE
     if (A.dbg_stop == 108) searching = false;                         // timing cut: one violation scan, no working-set change
@@ -1011,13 +1015,13 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
       WSYNC();
       V.dv[s] = d; V.yv[s] = (s >= q) ? d : 0.0;
       WSYNC();
-      const double zn = rsum16(s >= q ? d * d : 0.0);
+      const double zn = rsum16a(s >= q ? d * d : 0.0);
       const Zr zr = products(__ballot(stepping && q > 0) != 0);
       const double z = zr.z, rv = zr.rv;
       const bool have_step = zn > 100.0 * n * EPS2 * jf2 * np2;
       const bool cand = (s < q) && (rv > 2.2250738585072014e-308);   // (normal: frcp's estimate of a denormal is inf)
       const double ratio = cand ? u * frcp(rv) : INFINITY;
-      const double t1 = rmin16(ratio);
+      const double t1 = rmin16a(ratio);
       const unsigned long long lm = __ballot(cand && ratio == t1);
       const int l = (t1 < INFINITY) ? __ffs((int)((lm >> rbase) & 0xFFFFull)) - 1 : -1;
       const double t2 = have_step ? -s_ip * frcp(zn) : INFINITY;
@@ -1039,8 +1043,8 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
 #ifndef SIM3P_LATE_ATOMIC
   // the wave order's record: the classes are final here, so the atomic goes out now and its round trip runs behind the refinement and the outputs
   const int wocls = wo_class(iters, flagged);
-  WoPost wop = {0ull, 0ull, 0u, 0u, WO_NS + 1, 0};
-  if (A.worder) wop = wo_post(A.worder, grp, valid, wocls, r, s);
+  WoPost wop = {0ull, 0ull, 0u, 0u, (uint32_t)WO_NS + 1u, 0u};
+  if (A.worder) wop = wo_post(A.worder, wg, grp, valid, wocls, r, s);
 #endif
   // ================================ iterative refinement ==========================================
   // One step at the final working set (QP_Wrapper.py:37 asks qpOASES for numRefinementSteps = 100; oracle: qp_refine). With the slots' normals
@@ -1101,7 +1105,7 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
       for (int rr = 0; rr < 6; ++rr) {
         double pr = a[rr] * xm;
         asm volatile("" : "+v"(pr));
-        r1 = fma(a[rr], btv[rr] - rsum16(pr), r1);
+        r1 = fma(a[rr], btv[rr] - rsum16a(pr), r1);
       }
       if (TRUNK) {                            // trunk rows (base columns): the same with their image and targets
         const double2a t0 = lds2(V.pad_), t1 = lds2(V.pad_ + 2), t2 = lds2(V.pad_ + 4);
@@ -1110,7 +1114,7 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
         for (int rr = 0; rr < 6; ++rr) {
           double pr = at6[rr] * xm;
           asm volatile("" : "+v"(pr));
-          r1 = fma(at6[rr], ttv[rr] - rsum16(pr), r1);
+          r1 = fma(at6[rr], ttv[rr] - rsum16a(pr), r1);
         }
       }
     }
@@ -1146,7 +1150,7 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
     for (int k = 0; k < PV; k += 2) { const double2a j2 = lds2(J + sv * PLD + k), w2 = lds2(V.yv + k); da = fma(j2.x, w2.x, da); db = fma(j2.y, w2.y, db); }
     // the correction is small against x (1e-6 on the tick, up to 1e-3 on a cond-1e10 problem); one that is not (> 0.25 max(1, |x|)) or is non-finite — a working set on the edge of dependence — is not applied (oracle: same rule)
     const double dxl = has_b ? da + db : 0.0;
-    const double dmax = -rmin16(-fabs(dxl)), xmax = fmax(1.0, -rmin16(has_b ? -fabs(x) : 0.0));
+    const double dmax = -rmin16a(-fabs(dxl)), xmax = fmax(1.0, -rmin16a(has_b ? -fabs(x) : 0.0));
     const bool nanr = ((__ballot(dxl != dxl) >> rbase) & 0xFFFFull) != 0;
     if (has_b && status == WBC_QP_OPTIMAL && !nanr && dmax <= 0.25 * xmax) x += dxl;
   }
@@ -1166,7 +1170,7 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
       else if (cc - n < p_keep) w1 = 1ull << (32 * sd + ((cc - n) & 31));
       else w0 = 1ull << (32 * sd + (dR & 31));
     }
-    w0 = ror16(w0); w1 = ror16(w1);
+    w0 = ror16a(w0); w1 = ror16a(w1);
     if (valid && !flagged && s == 0) { A.ws_out[2 * (size_t)b] = w0; A.ws_out[2 * (size_t)b + 1] = w1; }
   }
 
@@ -1214,9 +1218,9 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
   if (A.worder) {                           // (this launch's record: the next launch's order)
 #ifdef SIM3P_LATE_ATOMIC
     const int wocls = wo_class(iters, flagged);
-    const WoPost wop = wo_post(A.worder, grp, valid, wocls, r, s);
+    const WoPost wop = wo_post(A.worder, wg, grp, valid, wocls, r, s);
 #endif
-    wo_finish(A.worder, A.B, valid, b, wocls, r, s, wop);
+    wo_finish(A.worder, wg, A.B, valid, b, wocls, r, s, wop);
   }
   // ---- the tail: an instance left out above (a stance-leg block of rank < 2 — never seen on the benchmark distribution — or the
   // diagnostic dbg_force_defer) is redone here, by this wave, on the general path (process_instance, one instance per wavefront, LDS
@@ -1241,7 +1245,10 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
 #endif
 #define WBC_PART SIM3P_PART
 #define WBC_KERNEL wbc_tick_sim3p_kernel
-#define WBC_KPARAMS WBC_TICK_KPARAMS
+// (the tick kernels' parameters and, behind them, the wave order's launch constants: wbc_wave_geom.h. KernelArgs and the first five stay where every
+//  tick kernel has them — the tail reads them back through the kernarg segment)
+#define WBC_KPARAMS (const KernelArgs, const DevModel* __restrict__, const WbcConfig* __restrict__, const DevPlan* __restrict__, const WbcTaskParams* __restrict__, const WoGeom)
+typedef void (*Sim3pKernel) WBC_KPARAMS;
 #define SIM3P_VARIANTS(V) /* WARM, TRUNK, QCON, ROT, TP */ \
   V(0, false, false, false, false, false) \
   V(1, true, false, false, false, false)  \
@@ -1273,16 +1280,17 @@ SIM3P_VARIANTS(WBC_VARIANT_INST)
 SIM3P_VARIANTS(WBC_VARIANT_UNIT)
 #endif
 #if SIM3P_PART <= 0
-static TickKernel sim3p_variant(long long key) {
+static Sim3pKernel sim3p_variant(long long key) {
   SIM3P_VARIANTS(WBC_VARIANT_FIND)
   return nullptr;
 }
 int launch_tick_sim3p(const KernelArgs& a, void* stream, const WbcTaskParams* tp) {
   const bool warm = a.ws_in || a.ws_out, qcon = a.in.q_con || a.in.posture_u;
   const bool trunk = !qcon && a.in.trunk_target && a.packed_trunk;   // (QCON switches TRUNK off)
-  const TickKernel k = sim3p_variant(variant_key(warm, trunk, qcon, a.rot != 0, tp != nullptr));
+  const Sim3pKernel k = sim3p_variant(variant_key(warm, trunk, qcon, a.rot != 0, tp != nullptr));
   if (!k) return WBC_E_UNSUPPORTED;
-  hipLaunchKernelGGL(k, dim3((a.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
+  const uint32_t waves = (uint32_t)((a.B + 3) / 4);
+  hipLaunchKernelGGL(k, dim3(waves), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp, wo_geom(waves));
   return check_launch("tick_sim3p");
 }
 int sim3p_lds_bytes() { return (int)sizeof(SmemP); }

@@ -5,6 +5,7 @@
 // velocity damper and the Euler matrix, which the one-instance kernels use too, are in wbc_common.h (damper_bounds, euler_to_R).
 #pragma once
 #include "wbc_common.h"
+#include "wbc_wave_geom.h"
 
 namespace wbc {
 
@@ -81,6 +82,47 @@ __device__ __forceinline__ unsigned long long ror16(unsigned long long v) {   //
   return v;
 }
 
+// ---- the same reductions for call sites at which ALL 64 LANES ARE ACTIVE. dpp<> passes the moved value as the instruction's
+// `old` operand too, which ties the destination to it: the compiler copies each half first (v_mov_b32 tmp, src; v_mov_b32_dpp tmp, src). dpp_all<>
+// has no `old` (bound_ctrl: a lane whose source lane is switched off in exec reads 0 instead of keeping its own value) and needs no copy. The two
+// are the same function wherever every source lane is active — the row controls used here never leave the row, so that is the only difference.
+// Rows of a short last wave (valid == false) are active lanes. A site inside a divergent region keeps dpp<>. The packed sim3 tick alone uses
+// these (every rsum16 / rmin16 / ror16 site of wbc_k_sim3p.hip sits in wave-uniform control flow); the other packed kernels keep theirs.
+// A/B switch (make variant VFLAGS=-D...): SIM3P_DPP_COPY gives the sim3 tick the copying helpers back.
+template <int CTRL>
+__device__ __forceinline__ double dpp_all(double v) {
+#ifdef SIM3P_DPP_COPY
+  return dpp<CTRL>(v);
+#else
+  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xF, 0xF, true);
+  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, true);
+  return __hiloint2double(hi, lo);
+#endif
+}
+__device__ __forceinline__ double rsum16a(double v) {
+  v += dpp_all<DPP_XOR1>(v); v += dpp_all<DPP_XOR2>(v); v += dpp_all<DPP_HALF_MIRROR>(v); v += dpp_all<DPP_MIRROR>(v);
+  return v;
+}
+__device__ __forceinline__ double rmin16a(double v) {
+  v = fmin(v, dpp_all<DPP_XOR1>(v)); v = fmin(v, dpp_all<DPP_XOR2>(v)); v = fmin(v, dpp_all<DPP_HALF_MIRROR>(v)); v = fmin(v, dpp_all<DPP_MIRROR>(v));
+  return v;
+}
+template <int CTRL>
+__device__ __forceinline__ unsigned long long dpp_or_all(unsigned long long v) {
+#ifdef SIM3P_DPP_COPY
+  return dpp_or<CTRL>(v);
+#else
+  int lo = (int)(unsigned)v, hi = (int)(unsigned)(v >> 32);
+  lo |= __builtin_amdgcn_mov_dpp(lo, CTRL, 0xF, 0xF, true);
+  hi |= __builtin_amdgcn_mov_dpp(hi, CTRL, 0xF, 0xF, true);
+  return ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo;
+#endif
+}
+__device__ __forceinline__ unsigned long long ror16a(unsigned long long v) {
+  v = dpp_or_all<DPP_XOR1>(v); v = dpp_or_all<DPP_XOR2>(v); v = dpp_or_all<DPP_HALF_MIRROR>(v); v = dpp_or_all<DPP_MIRROR>(v);
+  return v;
+}
+
 // The packed kernels' Cholesky sweep H' = L L' fused with the forward substitution L y = rhs (y comes in holding the lane's right-hand side: e_s, or g'
 // on a padding lane), two columns per trip: the raw columns j and j + 1 of every row go through the LDS vectors c0v / c1v together and each lane redoes,
 // for the rows below, the one update that column j + 1 receives from step j — the same operations in the same order as two single steps, one LDS round
@@ -135,23 +177,36 @@ __device__ __forceinline__ int wo_class(const int iters, const bool tail) {
 __device__ __forceinline__ uint32_t* wo_list(WaveOrder* wo, const uint32_t l, const int g, const int c) {
   return reinterpret_cast<uint32_t*>(wo + WO_NS) + ((size_t)(l * WO_NS + g) * WO_NCLS + c) * WO_CAP;
 }
-__device__ __forceinline__ int wo_slices() { return ((int)gridDim.x + WO_SW - 1) / WO_SW; }
+// The index arithmetic runs on launch constants (wbc_wave_geom.h WoGeom, the kernel's own extra parameter): ns and a reciprocal
+// for grp / ns — one scalar multiply-high where the kernel used to run three signed 32-bit divisions by ns (the compiler's expansion: a float
+// reciprocal and two correction rounds each) — and the slices' wave counts as quotient and remainder. Unsigned throughout. Each of wo_instance and
+// wo_post forms g and k = grp / ns from the block index (three scalar instructions): carried from the kernel's entry to the end of the dual loop
+// they would live in spill lanes (§3.23). wo_post hands g on to wo_finish. A/B switch: SIM3P_WO_DIVIDE divides.
+static_assert(WO_GEOM_SW == (uint32_t)WO_SW && WO_GEOM_XMAX > (uint32_t)(WO_SW * WO_NS), "wbc_wave_geom.h: the slice width; the reciprocal's range covers every grid the order takes");
+__device__ __forceinline__ uint32_t wo_divk(const WoGeom& wg, const uint32_t x) {
+#ifdef SIM3P_WO_DIVIDE
+  return (uint32_t)((int)x / (int)wg.ns);
+#else
+  return wo_div(wg, x);
+#endif
+}
 // The instance row r of wave grp takes: the identity (pos = 4 grp + r < B) unless the slice's order was built for this batch size. The slice's
-// block is wave-uniform (scalar loads at kernel entry); the index is read from the list of the position's class.
-__device__ __forceinline__ int wo_instance(WaveOrder* __restrict__ wo, const int B, const int grp, const int r, const int pos) {
-  const int ns = wo_slices();
-  if (!wo || ns > WO_NS) return pos;
-  const int g = grp % ns;
+// block is wave-uniform (scalar loads at kernel entry); the index is read from the list of the position's class: the LAST class c with off[c] <= j
+// (the offsets ascend), entry j - off[c] of list c — j + (c WO_CAP - off[c]) in the slice's lists, clamped to them (off[c] <= j < 4 WO_SW: the
+// clamp changes nothing the launches write themselves; it keeps a stray block from turning into a read outside the allocation).
+__device__ __forceinline__ int wo_instance(WaveOrder* __restrict__ wo, const WoGeom& wg, const int B, const int grp, const int r, const int pos) {
+  if (!wo || wg.ns > (uint32_t)WO_NS) return pos;
+  const uint32_t k = wo_divk(wg, (uint32_t)grp), g = wo_mod(wg, (uint32_t)grp, k);
   const WaveOrder& sl = wo[g];
   if (sl.B != (uint32_t)B) return pos;
-  const uint32_t cur = sl.cur & 1u, j = 4u * (uint32_t)(grp / ns) + (uint32_t)r;
-  uint32_t k = 0, base = 0;
+  const uint32_t cur = sl.cur & 1u, j = 4u * k + (uint32_t)r;
+  uint32_t d = 0;
 #pragma unroll
   for (int c = 1; c < WO_NCLS; ++c) {
     const uint32_t o = sl.off[c];
-    if (j >= o) { k = c; base = o; }
+    if (j >= o) d = (uint32_t)(c * WO_CAP) - o;
   }
-  const uint32_t i = wo_list(wo, cur, g, k)[min(j - base, (uint32_t)WO_CAP - 1u)];      // (base <= j < 4 WO_SW)
+  const uint32_t i = wo_list(wo, cur, g, 0)[min(j + d, (uint32_t)(WO_NCLS * WO_CAP) - 1u)];
   return i < (uint32_t)B ? (int)i : B - 1;
 }
 // Append the wave's instances to its slice's class lists that the next launch reads and count the wave done: ONE returning 64-bit atomicAdd per
@@ -165,11 +220,12 @@ __device__ __forceinline__ int wo_instance(WaveOrder* __restrict__ wo, const int
 // of its slice still before their list stores; like the lists themselves, what it publishes is read by the next launch only. The slice's `cur` is
 // read by wo_post, BEFORE the wave is counted, and handed on: once posted, the slice's block may be republished under this wave (a slice is
 // published when every one of its waves has posted), so wo_finish must not read it again.
-struct WoPost { unsigned long long old, add; unsigned same; uint32_t cur; int ns, g; };   // old: in lane 0 alone, still in flight
-__device__ __forceinline__ WoPost wo_post(WaveOrder* wo, const int grp, const bool valid, const int cls, const int r, const int s) {
+struct WoPost { unsigned long long old, add; unsigned same; uint32_t cur, ns, g; };   // old: in lane 0 alone, still in flight
+__device__ __forceinline__ WoPost wo_post(WaveOrder* wo, const WoGeom& wg, const int grp, const bool valid, const int cls, const int r, const int s) {
   WoPost t; t.old = 0ull; t.add = 1ull << 54; t.same = 0u; t.cur = 0u;
-  t.ns = wo_slices(); t.g = grp % t.ns;
-  if (t.ns > WO_NS) return t;
+  t.ns = wg.ns; t.g = 0u;
+  if (t.ns > (uint32_t)WO_NS) return t;
+  t.g = wo_mod(wg, (uint32_t)grp, wo_divk(wg, (uint32_t)grp));
   t.cur = wo[t.g].cur & 1u;
   const unsigned long long vm = __ballot(valid && s == 0);
 #pragma unroll
@@ -192,23 +248,29 @@ __device__ __forceinline__ WoPost wo_post(WaveOrder* wo, const int grp, const bo
   }
   return t;
 }
-__device__ __forceinline__ void wo_finish(WaveOrder* wo, const int B, const bool valid, const int b, const int cls, const int r, const int s,
-                                          const WoPost& t) {
-  const int ns = t.ns, g = t.g, G = (int)gridDim.x;
-  if (ns > WO_NS) return;
+__device__ __forceinline__ void wo_finish(WaveOrder* wo, const WoGeom& wg, const int B, const bool valid, const int b, const int cls, const int r,
+                                          const int s, const WoPost& t) {
+  const uint32_t ns = t.ns, g = t.g;
+  if (ns > (uint32_t)WO_NS) return;
   WaveOrder& sl = wo[g];
   const uint32_t cur = t.cur, nxt = cur ^ 1u;
   const unsigned long long old =
       ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(t.old >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)t.old);
   const uint32_t at = (uint32_t)((old >> (9 * cls)) & 511ull) + (uint32_t)__popc(t.same & ((1u << r) - 1u));
   if (valid && s == 0 && at < WO_CAP) wo_list(wo, nxt, g, cls)[at] = (uint32_t)b;
-  const uint32_t nwaves = (uint32_t)((G - g + ns - 1) / ns);                     // waves of slice g
+#ifdef SIM3P_WO_DIVIDE
+  const int G_ = (int)gridDim.x;
+  const uint32_t nwaves = (uint32_t)((G_ - (int)g + (int)ns - 1) / (int)ns);
+#else
+  const uint32_t nwaves = wg.wq + (g < wg.wr ? 1u : 0u);                          // waves of slice g
+#endif
   if (r == 0 && s == 0 && (uint32_t)(old >> 54) == nwaves - 1u) {
     const unsigned long long fin = old + t.add;
     uint32_t n = 0u;
 #pragma unroll
     for (int c = 0; c < WO_NCLS; ++c) { sl.off[c] = n; n += (uint32_t)((fin >> (9 * c)) & 511ull); }
-    const uint32_t expect = 4u * nwaves - ((g == (G - 1) % ns) ? (uint32_t)(4 * G - B) : 0u);   // (the batch's last wave may be short)
+    const uint32_t G = gridDim.x, glast = (wg.wr ? wg.wr : ns) - 1u;             // (the batch's last wave may be short: it sits in slice (G - 1) % ns)
+    const uint32_t expect = 4u * nwaves - ((g == glast) ? 4u * G - (uint32_t)B : 0u);
     sl.B = (n == expect) ? (uint32_t)B : 0u;
     sl.cur = nxt;
     sl.word[cur] = 0ull;

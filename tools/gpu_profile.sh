@@ -45,7 +45,7 @@ if [ "$PASSES" = chain ]; then
 # the length of a wave's dependent chain: the kernel's mean time, then ONE counter pass — wave cycles and waits against the
 # instruction counts, which a change of issue order leaves alone
 step stats 200 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 bench.py --rollout-ticks 0 --no-cpu-baseline ${BENCH_ARGS:-}
-pmc chain SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_LDS GRBM_GUI_ACTIVE
+pmc chain SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS GRBM_GUI_ACTIVE
 exit 0
 fi
 if [ "$PASSES" = all ]; then

@@ -10,7 +10,10 @@ through `; WBC_TAIL_BEGIN` (the general-path tail); everything else reachable fr
   hot scratch ld/st   scratch_load / scratch_store instructions in the hot blocks (tools/hot_path_spills.py counts the cold blocks in as well)
 The layout without the hints and the family's flag (the parent's): WBC_XFLAGS=-DSIM3P_NO_LAYOUT_HINTS FAMFLAGS_sim3p= .
 CPU only (cross-compiles):
-    python tools/hot_path_bytes.py [-v] [family.part ...]      -v: the layout as runs of hot / cold bytes; default: every sim3p part   (WBC_XFLAGS="-D..." adds compiler flags)"""
+    python tools/hot_path_bytes.py [-v] [--mix] [family.part ...]      -v: the layout as runs of hot / cold bytes; default: every sim3p part   (WBC_XFLAGS="-D..." adds compiler flags)
+--mix: what the hot path is made of (DESIGN.md §3.24) — its instructions by class (fp64 arithmetic; moves of an immediate and of a register;
+selects; DPP; other VALU; scalar; exec-mask handling: saveexec, branches on exec, writes to exec; waits; nops; LDS; global and scratch) and,
+per class, the source lines that own most of them (the -g1 line tables; an inlined helper's instructions count for the helper's own line)."""
 import os
 import re
 import subprocess
@@ -61,6 +64,36 @@ def listing(part):
     return out, [int(v) for v in re.findall(r"; codeLenInByte = (\d+)", txt)]      # (the compiler's own figure per kernel, in listing order: a comment llvm-mc drops)
 
 
+MIX_CLASSES = ("fp64 arith", "mov imm", "mov reg", "select", "dpp", "other valu", "scalar", "exec-mask", "waitcnt", "nop", "lds", "global")
+
+
+def classify(ins):
+    """-> the --mix class of one instruction (mnemonic and operands as in the listing)"""
+    mn, _, ops = ins.partition(" ")
+    ops = [o.strip() for o in ops.split(",")]
+    if mn.endswith("_dpp") or "row_" in ins or "quad_perm" in ins:
+        return "dpp"
+    if re.match(r"v_(fmac|fma|mul|add|min|max)_f64", mn):
+        return "fp64 arith"
+    if re.match(r"v_mov_b(32|64)", mn):
+        return "mov reg" if len(ops) > 1 and re.match(r"[vsa]\d|[vsa]\[|vcc|exec|ttmp|m0", ops[1]) else "mov imm"
+    if mn.startswith("v_cndmask"):
+        return "select"
+    if mn.startswith("v_"):
+        return "other valu"
+    if mn.startswith("ds_"):
+        return "lds"
+    if re.match(r"(global|flat|scratch|buffer)_", mn):
+        return "global"
+    if mn.startswith("s_waitcnt"):
+        return "waitcnt"
+    if mn.startswith("s_nop"):
+        return "nop"
+    if "saveexec" in mn or mn.startswith("s_cbranch_exec") or (ops and ops[0].startswith("exec")):
+        return "exec-mask"
+    return "scalar"
+
+
 def analyse(part):
     """-> (part, [(kernel, hot instructions, hot bytes, span bytes, cold bytes inside the span, bytes behind the span, total)])"""
     txt, code_len = listing(part)
@@ -70,8 +103,15 @@ def analyse(part):
         name = re.sub(r"\(.*", "", name.replace("void wbc::", ""))
         # blocks in layout order: label, start address, instructions, bytes, successors, falls through, cut (a marker inside: cold from there on)
         blocks, addr = [], 0
-        cur = {"label": "entry", "start": 0, "n": 0, "bytes": 0, "hot_n": 0, "hot_bytes": 0, "sl": 0, "ss": 0, "hsl": 0, "hss": 0, "succ": [], "all_succ": [], "fall": True, "cut": False, "exit": False}
+        cur = {"label": "entry", "start": 0, "n": 0, "bytes": 0, "hot_n": 0, "hot_bytes": 0, "sl": 0, "ss": 0, "hsl": 0, "hss": 0, "succ": [], "all_succ": [], "fall": True, "cut": False, "exit": False, "mix": [], "hot_mix": []}
+        files, where = {}, "?"
+        for fm in re.finditer(r'^\s*\.file\s+(\d+)\s+(?:"[^"]*"\s+)?"([^"]*)"', txt, re.M):
+            files[fm.group(1)] = os.path.basename(fm.group(2))
         for line in m.group(2).splitlines():
+            loc = re.match(r"\s*\.loc\s+(\d+)\s+(\d+)", line)
+            if loc:
+                where = "%s:%s" % (files.get(loc.group(1), "file" + loc.group(1)), loc.group(2))
+                continue
             if re.match(r"\s*\.section", line):
                 break                            # (the kernel descriptor's section follows the code)
             if re.match(r"^WBC_(COLD|TAIL_BEGIN)_MARK_\d+:", line):
@@ -80,7 +120,7 @@ def analyse(part):
             lab = re.match(r"^(\.LBB\w+):", line)
             if lab:
                 blocks.append(cur)
-                cur = {"label": lab.group(1), "start": addr, "n": 0, "bytes": 0, "hot_n": 0, "hot_bytes": 0, "sl": 0, "ss": 0, "hsl": 0, "hss": 0, "succ": [], "all_succ": [], "fall": True, "cut": False, "exit": False}
+                cur = {"label": lab.group(1), "start": addr, "n": 0, "bytes": 0, "hot_n": 0, "hot_bytes": 0, "sl": 0, "ss": 0, "hsl": 0, "hss": 0, "succ": [], "all_succ": [], "fall": True, "cut": False, "exit": False, "mix": [], "hot_mix": []}
                 continue
             al = re.match(r"\s*\.p2align\s+(\d+)", line)
             if al:                               # padding in front of an aligned block: counted with the block it ends
@@ -96,12 +136,14 @@ def analyse(part):
             addr += nb
             cur["n"] += 1
             cur["bytes"] += nb
+            cur["mix"].append((classify(ins), where))
             sl, ss = ins.startswith("scratch_load"), ins.startswith("scratch_store")
             cur["sl"] += sl
             cur["ss"] += ss
             if not cur["cut"]:
                 cur["hot_n"] += 1
                 cur["hot_bytes"] += nb
+                cur["hot_mix"].append(cur["mix"][-1])
                 cur["hsl"] += sl
                 cur["hss"] += ss
             br = re.match(r"s_(c?branch\w*)\s+(\.LBB\w+)", ins)
@@ -134,12 +176,13 @@ def analyse(part):
         # issues it — it counts as hot
         for i, b in enumerate(blocks):
             if b["cut"] and not exits_without(i):
-                b["cut"], b["succ"], b["hot_n"], b["hot_bytes"], b["hsl"], b["hss"] = False, b["all_succ"], b["n"], b["bytes"], b["sl"], b["ss"]
+                b["cut"], b["succ"], b["hot_n"], b["hot_bytes"], b["hsl"], b["hss"], b["hot_mix"] = False, b["all_succ"], b["n"], b["bytes"], b["sl"], b["ss"], b["mix"]
         # a marked block with no branch in front of its marker is cold from its first instruction (the compiler hoisted the block's preamble
         # above the comment)
         for b in blocks:
             if b["cut"] and not b["succ"]:
                 b["hot_n"] = b["hot_bytes"] = b["hsl"] = b["hss"] = 0
+                b["hot_mix"] = []
         seen, stack = set(), [0]
         while stack:
             i = stack.pop()
@@ -168,13 +211,15 @@ def analyse(part):
         # self-check of the classification: the runs tile the kernel, and the kernel is as long as the compiler says
         assert sum(r[2] for r in runs) == addr and sum(r[2] for r in runs if r[0]) == hot_bytes, name
         assert code_len[kn] == addr, "%s: %d B counted, codeLenInByte = %d" % (name, addr, code_len[kn])
-        res.append((name, hot_n, hot_bytes, span, span - hot_bytes, addr - span, addr, scr, runs))
+        mix = [x for i in sorted(seen) for x in blocks[i]["hot_mix"]]
+        assert len(mix) == hot_n, name
+        res.append((name, hot_n, hot_bytes, span, span - hot_bytes, addr - span, addr, scr, runs, mix))
     return part, res
 
 
 def main():
     parts = [a for a in sys.argv[1:] if not a.startswith("-")] or ["sim3p.%d" % k for k in range(NPARTS["sim3p"])]
-    verbose = "-v" in sys.argv
+    verbose, want_mix = "-v" in sys.argv, "--mix" in sys.argv
     print("%-52s %6s %8s | %8s %8s | %8s %8s | %s" % ("kernel", "hot ins", "hot B", "span B", "inside B", "rest B", "total B", "hot scratch ld/st"))
     with ThreadPoolExecutor(max_workers=min(4, len(parts))) as ex:
         for part, res in ex.map(analyse, parts):
@@ -183,6 +228,14 @@ def main():
                 if verbose:
                     for hot, start, nb in r[8]:
                         print("      %-4s at %7d: %7d B" % ("hot" if hot else "cold", start, nb))
+                if want_mix:
+                    for cls in MIX_CLASSES:
+                        lines = {}
+                        for c, w in r[9]:
+                            if c == cls:
+                                lines[w] = lines.get(w, 0) + 1
+                        top = sorted(lines.items(), key=lambda kv: (-kv[1], kv[0]))[:6]
+                        print("      %-10s %5d   %s" % (cls, sum(lines.values()), "  ".join("%s x%d" % kv for kv in top)))
 
 
 if __name__ == "__main__":
