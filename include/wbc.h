@@ -377,6 +377,71 @@ typedef struct WbcRolloutSummary {   /* all optional; per instance [B], per grou
 int wbc_rollout_traj(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
                      const WbcTrajectory* traj, const WbcRolloutSummary* sum /* may be NULL */, int mem, void* stream);
 
+/* ------------------------------------------------------------------ roll-outs with several followed targets (tracks), trunk included
+ * What the reference's drivers do beyond one gripper trajectory: the trunk target follows its own milestones while the gripper target stands
+ * still (sim3.py:207, :216-217, :297-298 with sim_id == 1; sim2.py:202, :291-292), the trajectory is a Hermite spline (sim2.py:216-218:
+ * HermiteTrajectory().makeSpline(traj)), and several targets move at once (setInitialState, Robot_Wrapper4.py:264-283). A track is one target
+ * (an end effector's or the trunk's) on one per-instance trajectory; every frame may be scored against its target of the tick, followed or not. */
+#define WBC_MAX_TRACKS 6
+#define WBC_TARGET_TRUNK 5                 /* targets / frames: 0..4 = end effectors FR, FL, RR, RL, GRIP; 5 = trunk */
+enum { WBC_TRACK_LINEAR = 0, WBC_TRACK_HERMITE = 1 };
+
+typedef struct WbcTrack {
+  int32_t target;            /* 0..5, each target at most once per call */
+  int32_t kind;              /* WBC_TRACK_* */
+  int32_t max_points;        /* S: 2 <= S <= WBC_MAX_TRAJ_POINTS */
+  int32_t pad_;
+  const double*  points;     /* [B][S][3] milestones, milestone i at parameter i */
+  const double*  tangents;   /* [B][S][3] HERMITE only: d(target)/d(parameter) at the milestones (what klampt keeps as the second half of
+                                a HermiteTrajectory milestone); NULL => the rule below. Must be NULL for LINEAR */
+  const int32_t* n_points;   /* [B] 2..S; NULL => S */
+  const double*  du;         /* [B]; NULL => du_all */
+  double du_all;
+} WbcTrack;
+
+typedef struct WbcTracks {
+  int32_t n_tracks, pad_;    /* 1..WBC_MAX_TRACKS */
+  WbcTrack track[WBC_MAX_TRACKS];
+  double* trunk_target_final;   /* [B][3] optional: the trunk target the NEXT tick would get */
+} WbcTracks;
+
+typedef struct WbcTrackScores {  /* all arrays optional */
+  int32_t score_mask;        /* bit f: frame f is scored against its target of the tick, followed or constant; n_scored = popcount */
+  int32_t group_size;        /* as WbcRolloutSummary */
+  double  *err_sq_sum, *err_max, *err_final;  int32_t* err_max_tick;      /* [n_scored][B], frames in increasing index order */
+  int32_t *first_bad_tick, *bad_ticks;                                    /* [B] */
+  double  *trace;            /* [ticks][n_scored][B][3] positions reached (optional) */
+  double  *group_rms, *group_err_max;                                     /* [n_scored][B / M] */
+  int32_t *group_worst_status, *group_bad_instances;                      /* [B / M] */
+} WbcTrackScores;
+
+/* wbc_rollout_tp with every followed target on its track: on tick k = 0 .. r->ticks - 1 the target of track j is eval_b(k * du_b) (the PRODUCT,
+ * as in wbc_rollout_traj), clamped at both ends (t <= 0: the first milestone, t >= n_points - 1: the last). The followed rows of in0->ee_target
+ * and in0->trunk_target are not read; ee_target_final and trunk_target_final hold eval(ticks * du) in the followed rows. Everything else is
+ * wbc_rollout_tp's: both modes, tp, imu, grip_trace, status_max, iters_sum, the warm start carried between ticks.
+ *   LINEAR   i = floor(t), u = t - i: (1 - u) * m[i] + u * m[i + 1] — wbc_rollout_traj's arithmetic.
+ *   HERMITE  unit knot spacing, per component: u2 = u * u, u3 = u * u2, cx1 = (2.0 * u3 - 3.0 * u2) + 1.0, cx2 = (-2.0 * u3) + 3.0 * u2,
+ *            cv1 = (u3 - 2.0 * u2) + u, cv2 = u3 - u2, x = ((cx1 * m[i] + cx2 * m[i + 1]) + cv1 * v[i]) + cv2 * v[i + 1]; every operation
+ *            rounded on its own, so the host restatement (wbc_workload.track_targets) is bit-exact.
+ *   Default tangents (tangents == NULL; the rule of klampt's makeSpline(preventOvershoot=True)): n = 2: v[0] = v[1] = m[1] - m[0]. n >= 3:
+ *            v[0] = v[n - 1] = 0; interior i, per component with a = m[i - 1], x = m[i], b = m[i + 1], w = (b - a) * 0.5, third = 1.0 / 3.0,
+ *            the first case that matches: (1) x <= min(a, b) or x >= max(a, b): 0; (2) (w < 0 and x - w * third >= a) or (w > 0 and
+ *            x - w * third <= a): 3.0 * (x - a); (3) (w < 0 and x + w * third < b) or (w > 0 and x + w * third > b): 3.0 * (b - x); (4) w.
+ *            No segment of such a spline leaves the interval of its two milestones. Computed on the fly from the neighbouring milestones.
+ * The error of frame f on tick k is |frame f reached after tick k - target of frame f on tick k|, formed as (dx * dx + dy * dy) + dz * dz, summed
+ * in tick order, the maximum kept with a strictly-greater comparison (the first tick of the maximum). scores may be NULL.
+ * Refused with WBC_E_ARG, naming the field: r->ee_target_step not NULL; r->hold_ticks not 0; r->trunk_target_step together with a trunk track
+ * (without one it stays allowed); n_tracks outside 1..6; a repeated target; target, kind or max_points out of range; points NULL; tangents
+ * with a LINEAR track; du NULL with a du_all that is not finite and positive; a trunk track or score bit 5 without in0->trunk_target /
+ * prev_trunk_target; score_mask bits >= 6; a group_size that does not divide B.
+ * Bad rows, found on the device: an instance is bad if any of its tracks has a non-finite point or caller tangent among its first n_points, a
+ * du that is not finite and positive, or n_points outside 2..S. ALL of that instance's followed targets stay at in0's values (nothing
+ * non-finite reaches a solve), its status is WBC_QP_NUMERICAL, first_bad_tick 0 and bad_ticks = ticks; it is counted in the statistic
+ * "last_traj_bad_rows"; the other instances keep identical bits. Group results: one wavefront per group, fixed-shape reduction, no
+ * floating-point atomics. Per tick: the tick and update kernels of wbc_rollout plus ONE launch of the trajectory kernel however many tracks. */
+int wbc_rollout_tracks(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
+                       const WbcTracks* tracks, const WbcTrackScores* scores /* may be NULL */, int mem, void* stream);
+
 /* Knobs of a handle (none of them changes a result beyond rounding; defaults in brackets):
  *   "jtj_mfma"        [-1] H = A'A of wbc_tick / wbc_assemble (QP_Wrapper.py:17) on the fp64 matrix cores (v_mfma_f64_16x16x4_f64)
  *                          or as the sparse vector-unit contraction. -1: matrix cores when the Cartesian task stack has
@@ -480,7 +545,7 @@ int wbc_batch_set_option(WbcBatch* b, const char* name, int value);
  * tail or left to the one-instance kernel's second pass; waits for `stream`), "pivoted_last" (instances that took the pivoted
  * elimination, with option "count_pivoted"), "wave_order_slices" (slices of waves whose recorded order the next packed sim3 launch at
  * the last such launch's batch size will read: ceil(ceil(B / 4) / 127) once the order is in effect, 0 without it; waits for `stream`),
- * "last_traj_bad_rows" (bad WbcTrajectory rows the last wbc_rollout_traj on the handle found; waits for `stream`),
+ * "last_traj_bad_rows" (bad rows the last wbc_rollout_traj / wbc_rollout_tracks on the handle found; waits for `stream`),
  * "sim3_lds_bytes" / "tick_lds_bytes" / "orthp_lds_bytes" (LDS per workgroup of the tick kernels). */
 int wbc_batch_get_stat(WbcBatch* b, const char* name, void* stream, int64_t* out);
 

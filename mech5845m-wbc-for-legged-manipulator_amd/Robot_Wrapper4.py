@@ -114,6 +114,54 @@ class _LinearTrajectory:
         return ((1 - u) * self.m[i] + u * self.m[i + 1]).tolist()
 
 
+class _HermiteTrajectory:
+    """klampt ``trajectory.HermiteTrajectory().makeSpline(traj)`` (sim2.py:216-218; preventOvershoot=True, the default): the cubic Hermite
+    spline through a piecewise-linear trajectory's milestones, unit time per segment, clamped ends. The velocities are klampt's rule as
+    include/wbc.h states it (two milestones: the chord; otherwise zero at both ends, and at an interior milestone the centred difference
+    unless it is an extremum — zero — or would overshoot a neighbour — three times the distance to it)."""
+
+    def __init__(self):
+        self.m, self.v = [], []
+
+    def makeSpline(self, waypointTrajectory):
+        m = [np.asarray(x, dtype=float) for x in waypointTrajectory.m]
+        n = len(m)
+        if n == 2:
+            v = [m[1] - m[0], m[1] - m[0]]
+        else:
+            third = 1.0 / 3.0
+            v = [np.zeros(len(m[0])) for _ in range(n)]
+            for i in range(1, n - 1):
+                for c in range(len(m[i])):
+                    a, x, b = float(m[i - 1][c]), float(m[i][c]), float(m[i + 1][c])
+                    w = (b - a) * 0.5
+                    if x <= min(a, b) or x >= max(a, b):
+                        v[i][c] = 0.0
+                    elif (w < 0 and x - w * third >= a) or (w > 0 and x - w * third <= a):
+                        v[i][c] = 3.0 * (x - a)
+                    elif (w < 0 and x + w * third < b) or (w > 0 and x + w * third > b):
+                        v[i][c] = 3.0 * (b - x)
+                    else:
+                        v[i][c] = w
+        self.m, self.v = m, v
+        return self
+
+    def eval(self, t):
+        if t <= 0:
+            return self.m[0].tolist()
+        if t >= len(self.m) - 1:
+            return self.m[-1].tolist()
+        i = int(np.floor(t))
+        u = t - i
+        u2 = u * u
+        u3 = u * u2
+        cx1 = (2.0 * u3 - 3.0 * u2) + 1.0
+        cx2 = (-2.0 * u3) + 3.0 * u2
+        cv1 = (u3 - 2.0 * u2) + u
+        cv2 = u3 - u2
+        return (((cx1 * self.m[i] + cx2 * self.m[i + 1]) + cv1 * self.v[i]) + cv2 * self.v[i + 1]).tolist()
+
+
 class RobotModel:
     def __init__(self, urdf_path, mesh_dir_path, EE_frame_names, EE_joint_names, G_base, imu, FR_hip_joint,
                  hip_waist_joint_names, foot_offset=False, device_id=0, warm_up=True):

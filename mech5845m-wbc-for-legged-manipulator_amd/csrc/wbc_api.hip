@@ -9,6 +9,10 @@
 #include "wbc_device.h"
 #include "wbc_traj.h"
 
+// d_traj per instance of max_batch: err_sq_sum / err_max / err_final [6] each + the six frames' positions [6][3]; bad, err_max_tick [6],
+// first_bad_tick, bad_ticks, status_max. One int32 (the bad-row count) follows.
+enum { TRAJ_WS_DOUBLES = 3 * WBC_MAX_TRACKS + 3 * WBC_MAX_TRACKS, TRAJ_WS_INTS = 4 + WBC_MAX_TRACKS };
+
 using namespace wbc;
 
 static thread_local char g_err[512] = "";
@@ -84,7 +88,7 @@ struct WbcBatch {
   unsigned long long* d_prof;
   double *d_pu, *d_pq;   // qpJointb MANI/HYBRID results: u [max_batch][26], q_after [max_batch][27] (lazy)
   void* d_roll;          // wbc_rollout's mutable controller state for max_batch instances (lazy)
-  void* d_traj;          // wbc_rollout_traj: per-instance summary, gripper row, bad-row flags and their count (lazy)
+  void* d_traj;          // wbc_rollout_traj / wbc_rollout_tracks: per-instance scores of six frames, their positions of the tick, bad-row flags and their count (lazy)
 };
 
 // ---------------------------------------------------------------------------------------------- model
@@ -726,12 +730,12 @@ extern "C" int wbc_batch_get_stat(WbcBatch* b, const char* name, void* stream, i
     for (const WaveOrder& w : sl) *out += w.B == (uint32_t)b->worder_B;
     return WBC_OK;
   }
-  if (!strcmp(name, "last_traj_bad_rows")) {  // bad WbcTrajectory rows of the last wbc_rollout_traj; waits for `stream`
+  if (!strcmp(name, "last_traj_bad_rows")) {  // bad rows of the last wbc_rollout_traj / wbc_rollout_tracks; waits for `stream`
     *out = 0;
     if (!b->d_traj) return WBC_OK;
     int32_t c = 0;
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-    HIP_TRY(hipMemcpy(&c, (const char*)b->d_traj + (size_t)b->max_batch * (6 * sizeof(double) + 5 * sizeof(int32_t)), sizeof c, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&c, (const char*)b->d_traj + (size_t)b->max_batch * (TRAJ_WS_DOUBLES * sizeof(double) + TRAJ_WS_INTS * sizeof(int32_t)), sizeof c, hipMemcpyDeviceToHost));
     *out = c;
     return WBC_OK;
   }
@@ -1151,19 +1155,21 @@ extern "C" int wbc_update_state(WbcBatch* b, int B, const double* q_cur, const d
 
 // K closed-loop ticks: the mutable controller state lives in the handle's rollout workspace; in0 is only read.
 static int rollout_run(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
-                       const WbcTrajectory* traj, const WbcRolloutSummary* sum, int mem, void* stream);
+                       const WbcTracks* tracks, const WbcTrackScores* scores, bool one_track, int mem, void* stream);
 extern "C" int wbc_rollout(WbcBatch* b, int B, const WbcTickIn* in0, double dt, const WbcRollout* r, int mem, void* stream) {
   return wbc_rollout_tp(b, B, in0, nullptr, dt, r, mem, stream);
 }
 extern "C" int wbc_rollout_tp(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r, int mem,
                               void* stream) {
-  return rollout_run(b, B, in0, tp, dt, r, nullptr, nullptr, mem, stream);
+  return rollout_run(b, B, in0, tp, dt, r, nullptr, nullptr, false, mem, stream);
 }
-// The roll-out loop of wbc_rollout / wbc_rollout_tp / wbc_rollout_traj. traj == nullptr: one linear segment (WbcRollout.ee_target_step), the
-// launches, memsets and copies of wbc_rollout_tp and nothing else. With a trajectory (arguments checked by wbc_rollout_traj): the update kernel
-// leaves the EE targets alone and one wbc_traj_tick_kernel per tick scores the tick and writes the followed end effector's next target.
+// The roll-out loop of wbc_rollout / wbc_rollout_tp / wbc_rollout_traj / wbc_rollout_tracks. tracks == nullptr: one linear segment
+// (WbcRollout.ee_target_step), the launches, memsets and copies of wbc_rollout_tp and nothing else. With tracks (arguments checked by the entry
+// point): the update kernel leaves the targets alone and one wbc_traj_tick_kernel per tick scores the tick and writes every followed target of
+// the next. one_track: wbc_rollout_traj's call — the gripper's position comes from the update kernel's grip_trace row, and a constant trunk
+// step stays with the update kernel; otherwise the update kernel writes the six frames' positions of the tick into the workspace.
 static int rollout_run(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
-                       const WbcTrajectory* traj, const WbcRolloutSummary* sum, int mem, void* stream) {
+                       const WbcTracks* tracks, const WbcTrackScores* scores, bool one_track, int mem, void* stream) {
   int rc = check_batch(b, B, "wbc_rollout", true);
   if (rc) return rc;
   if (!r || r->ticks < 1 || !(dt > 0)) return fail(WBC_E_ARG, "wbc_rollout: ticks >= 1 and dt > 0 required");
@@ -1193,17 +1199,24 @@ static int rollout_run(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskPa
   st.in(&ro.ee_target_step, n * 15); st.in(&ro.trunk_target_step, n * 3); st.in(&ro.imu, n * 4);
   st.out(&ro.q_final, n * WBC_Q_STRIDE); st.out(&ro.qdot_last, n * WBC_V_STRIDE); st.out(&ro.ee_target_final, n * 15);
   st.out(&ro.grip_trace, (size_t)(r->ticks + r->hold_ticks) * n * 3); st.out(&ro.status_max, n); st.out(&ro.iters_sum, n);
-  WbcTrajectory tj;
-  WbcRolloutSummary so;
+  WbcTracks tj;
+  WbcTrackScores so;
   memset(&tj, 0, sizeof tj); memset(&so, 0, sizeof so);
-  if (traj) {
-    tj = *traj;
-    if (sum) so = *sum;
+  size_t nsc = 0;                        // scored frames
+  if (tracks) {
+    tj = *tracks;
+    if (scores) so = *scores;
+    nsc = (size_t)__builtin_popcount((unsigned)so.score_mask);
     const size_t ng = so.group_size > 0 ? n / (size_t)so.group_size : 0;
-    st.in(&tj.points, n * (size_t)tj.max_points * 3); st.in(&tj.n_points, n); st.in(&tj.du, n);
-    st.out(&so.err_sq_sum, n); st.out(&so.err_max, n); st.out(&so.err_max_tick, n); st.out(&so.err_final, n);
-    st.out(&so.first_bad_tick, n); st.out(&so.bad_ticks, n);
-    st.out(&so.group_rms, ng); st.out(&so.group_err_max, ng); st.out(&so.group_worst_status, ng); st.out(&so.group_bad_instances, ng);
+    for (int j = 0; j < tj.n_tracks; ++j) {
+      WbcTrack& t = tj.track[j];
+      const size_t np = n * (size_t)t.max_points * 3;
+      st.in(&t.points, np); st.in(&t.tangents, np); st.in(&t.n_points, n); st.in(&t.du, n);
+    }
+    st.out(&tj.trunk_target_final, n * 3);
+    st.out(&so.err_sq_sum, nsc * n); st.out(&so.err_max, nsc * n); st.out(&so.err_max_tick, nsc * n); st.out(&so.err_final, nsc * n);
+    st.out(&so.first_bad_tick, n); st.out(&so.bad_ticks, n); st.out(&so.trace, (size_t)r->ticks * nsc * n * 3);
+    st.out(&so.group_rms, nsc * ng); st.out(&so.group_err_max, nsc * ng); st.out(&so.group_worst_status, ng); st.out(&so.group_bad_instances, ng);
   }
   if ((rc = st.stage())) return rc;
   // seed the mutable state from in0
@@ -1237,22 +1250,39 @@ static int rollout_run(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskPa
   u.trunk_target = first.trunk_target ? blk(O_TT) : nullptr; u.prev_trunk_target = first.prev_trunk_target ? blk(O_TP) : nullptr;
   u.ee_prev_rot = first.ee_prev_rot ? blk(O_EPR) : nullptr; u.trunk_prev_rot = first.trunk_prev_rot ? blk(O_TPR) : nullptr;
   u.ee_ref_rot = first.ee_ref_rot; u.trunk_ref_euler = first.trunk_ref_euler;
-  u.ee_step = ro.ee_target_step; u.trunk_step = ro.trunk_target_step;   // (a trajectory call has no ee_target_step: wbc_traj_tick_kernel moves that target)
+  u.ee_step = ro.ee_target_step; u.trunk_step = ro.trunk_target_step;   // (a trajectory call has no ee_target_step: wbc_traj_tick_kernel moves those targets)
+  if (tracks && !one_track) u.trunk_step = nullptr;   // ... and wbc_rollout_tracks' constant trunk step is added there too, after the tick was scored
   u.status = w_status; u.iters = w_iters; u.status_max = ro.status_max; u.iters_sum = ro.iters_sum;
-  // the trajectory's own state: per-instance summary, the gripper row of a roll-out without a trace, the bad-row flags and their count
+  // the tracks' own state: per-instance scores ([scored frame][B] within regions sized for six frames of max_batch), the frames' positions of
+  // the tick (the gripper row alone in a one-track call without a trace), the bad-row flags and their count
   TrajArgs ta;
   memset(&ta, 0, sizeof ta);
-  double* w_grip = nullptr;
-  if (traj) {
-    if (!b->d_traj) HIP_TRY(hipMalloc(&b->d_traj, NB * (6 * sizeof(double) + 5 * sizeof(int32_t)) + sizeof(int32_t)));
+  double* w_frames = nullptr;
+  if (tracks) {
+    if (!b->d_traj) HIP_TRY(hipMalloc(&b->d_traj, NB * (TRAJ_WS_DOUBLES * sizeof(double) + TRAJ_WS_INTS * sizeof(int32_t)) + sizeof(int32_t)));
     double* T = (double*)b->d_traj;
-    ta.err_sq_sum = T; ta.err_max = T + NB; ta.err_final = T + 2 * NB; w_grip = T + 3 * NB;
-    int32_t* I = (int32_t*)(T + 6 * NB);
-    ta.bad = I; ta.err_max_tick = I + NB; ta.first_bad_tick = I + 2 * NB; ta.bad_ticks = I + 3 * NB; ta.status_max = I + 4 * NB;
-    ta.bad_count = I + 5 * NB;
-    ta.B = B; ta.S = tj.max_points; ta.ee = tj.ee_index; ta.ticks = r->ticks; ta.do_sum = sum != nullptr;
-    ta.points = tj.points; ta.n_points = tj.n_points; ta.du = tj.du; ta.du_all = tj.du_all;
-    ta.ee_target = blk(O_EET); ta.status = w_status; ta.ro_status_max = ro.status_max;
+    const size_t F = WBC_MAX_TRACKS;
+    ta.err_sq_sum = T; ta.err_max = T + F * NB; ta.err_final = T + 2 * F * NB; w_frames = T + 3 * F * NB;
+    int32_t* I = (int32_t*)(T + (size_t)TRAJ_WS_DOUBLES * NB);
+    ta.bad = I; ta.first_bad_tick = I + NB; ta.bad_ticks = I + 2 * NB; ta.status_max = I + 3 * NB; ta.err_max_tick = I + 4 * NB;
+    ta.bad_count = I + (size_t)TRAJ_WS_INTS * NB;
+    ta.B = B; ta.ticks = r->ticks; ta.n_tracks = tj.n_tracks; ta.do_sum = scores != nullptr; ta.score_mask = so.score_mask;
+    for (int j = 0; j < tj.n_tracks; ++j) {
+      const WbcTrack& t = tj.track[j];
+      TrajTrack& d = ta.tr[j];
+      d.target = t.target; d.kind = t.kind; d.S = t.max_points;
+      d.points = t.points; d.tangents = t.tangents; d.n_points = t.n_points; d.du = t.du; d.du_all = t.du_all;
+    }
+    ta.ee_target = blk(O_EET); ta.trunk_target = first.trunk_target ? blk(O_TT) : nullptr;
+    if (!one_track && ta.trunk_target) ta.trunk_step = ro.trunk_target_step;
+    ta.one_track = one_track ? 1 : 0;
+    if (one_track) ta.reached_stride = 3;                 // reached_off all 0: the gripper row
+    else {
+      ta.reached_stride = 3 * WBC_MAX_TRACKS;
+      for (int f = 0; f < WBC_MAX_TRACKS; ++f) ta.reached_off[f] = 3 * f;
+      if (ta.do_sum && nsc > 0) u.frames_out = w_frames;
+    }
+    ta.status = w_status; ta.ro_status_max = ro.status_max;
     HIP_TRY(hipMemsetAsync(ta.bad_count, 0, sizeof(int32_t), s));
     if (int e = launch_traj_begin(ta, stream)) return fail(WBC_E_HIP, "trajectory kernel launch failed: %s", hipGetErrorString((hipError_t)e));
   }
@@ -1263,25 +1293,26 @@ static int rollout_run(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskPa
     if ((rc = auto_posture(b, a, B, stream))) return rc;
     if ((rc = launch_tick_auto(b, a, B, stream, tp))) return rc;
     u.grip_trace = ro.grip_trace ? ro.grip_trace + (size_t)k * n * 3 : nullptr;
-    if (traj && ta.do_sum && !u.grip_trace) u.grip_trace = w_grip;   // no trace asked for: the summary reads the tick's row from the workspace
+    if (one_track && ta.do_sum && !u.grip_trace) u.grip_trace = w_frames;   // no trace asked for: the summary reads the tick's row from the workspace
     if (int e = launch_update_auto(b, u, B, stream)) return fail(WBC_E_HIP, "update kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    if (traj) {
-      ta.grip = u.grip_trace;
+    if (tracks) {
+      ta.reached = one_track ? u.grip_trace : w_frames;
+      ta.trace = so.trace ? so.trace + (size_t)k * nsc * n * 3 : nullptr;
       if (int e = launch_traj_tick(ta, k, stream)) return fail(WBC_E_HIP, "trajectory kernel launch failed: %s", hipGetErrorString((hipError_t)e));
     }
   }
-  if (traj && sum) {
+  if (tracks && scores) {
     auto give = [&](void* dst, const void* src, size_t bytes) -> int {
       if (dst) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s));
       return WBC_OK;
     };
-    if ((rc = give(so.err_sq_sum, ta.err_sq_sum, n * sizeof(double))) || (rc = give(so.err_max, ta.err_max, n * sizeof(double))) ||
-        (rc = give(so.err_final, ta.err_final, n * sizeof(double))) || (rc = give(so.err_max_tick, ta.err_max_tick, n * sizeof(int32_t))) ||
+    if ((rc = give(so.err_sq_sum, ta.err_sq_sum, nsc * n * sizeof(double))) || (rc = give(so.err_max, ta.err_max, nsc * n * sizeof(double))) ||
+        (rc = give(so.err_final, ta.err_final, nsc * n * sizeof(double))) || (rc = give(so.err_max_tick, ta.err_max_tick, nsc * n * sizeof(int32_t))) ||
         (rc = give(so.first_bad_tick, ta.first_bad_tick, n * sizeof(int32_t))) || (rc = give(so.bad_ticks, ta.bad_ticks, n * sizeof(int32_t)))) return rc;
     if (so.group_size > 0 && (so.group_rms || so.group_err_max || so.group_worst_status || so.group_bad_instances)) {
       TrajGroupArgs ga;
       memset(&ga, 0, sizeof ga);
-      ga.G = B / so.group_size; ga.M = so.group_size; ga.ticks = r->ticks;
+      ga.G = B / so.group_size; ga.M = so.group_size; ga.ticks = r->ticks; ga.n_scored = (int32_t)nsc;
       ga.err_sq_sum = ta.err_sq_sum; ga.err_max = ta.err_max; ga.status_max = ta.status_max; ga.bad_ticks = ta.bad_ticks;
       ga.group_rms = so.group_rms; ga.group_err_max = so.group_err_max; ga.group_worst_status = so.group_worst_status;
       ga.group_bad_instances = so.group_bad_instances;
@@ -1291,6 +1322,7 @@ static int rollout_run(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskPa
   if (ro.q_final) HIP_TRY(hipMemcpyAsync(ro.q_final, blk(O_Q), n * 27 * sizeof(double), hipMemcpyDeviceToDevice, s));
   if (ro.qdot_last) HIP_TRY(hipMemcpyAsync(ro.qdot_last, blk(O_QD), n * 26 * sizeof(double), hipMemcpyDeviceToDevice, s));
   if (ro.ee_target_final) HIP_TRY(hipMemcpyAsync(ro.ee_target_final, blk(O_EET), n * 15 * sizeof(double), hipMemcpyDeviceToDevice, s));
+  if (tj.trunk_target_final && first.trunk_target) HIP_TRY(hipMemcpyAsync(tj.trunk_target_final, blk(O_TT), n * 3 * sizeof(double), hipMemcpyDeviceToDevice, s));
   return st.finish();
 }
 
@@ -1309,7 +1341,61 @@ extern "C" int wbc_rollout_traj(WbcBatch* b, int B, const WbcTickIn* in0, const 
     return fail(WBC_E_ARG, "wbc_rollout_traj: du_all must be finite and positive when du is NULL");
   if (sum && (sum->group_size < 0 || (sum->group_size > 0 && B % sum->group_size != 0)))
     return fail(WBC_E_ARG, "wbc_rollout_traj: group_size = %d does not divide B = %d", sum->group_size, B);
-  return rollout_run(b, B, in0, tp, dt, r, traj, sum, mem, stream);
+  // the one-track call: a LINEAR track of end effector ee_index, the gripper scored
+  WbcTracks tk;
+  WbcTrackScores sc;
+  memset(&tk, 0, sizeof tk); memset(&sc, 0, sizeof sc);
+  tk.n_tracks = 1;
+  WbcTrack& t = tk.track[0];
+  t.target = traj->ee_index; t.kind = WBC_TRACK_LINEAR; t.max_points = traj->max_points;
+  t.points = traj->points; t.n_points = traj->n_points; t.du = traj->du; t.du_all = traj->du_all;
+  sc.score_mask = 1 << 4;
+  if (sum) {
+    sc.group_size = sum->group_size;
+    sc.err_sq_sum = sum->err_sq_sum; sc.err_max = sum->err_max; sc.err_final = sum->err_final; sc.err_max_tick = sum->err_max_tick;
+    sc.first_bad_tick = sum->first_bad_tick; sc.bad_ticks = sum->bad_ticks;
+    sc.group_rms = sum->group_rms; sc.group_err_max = sum->group_err_max;
+    sc.group_worst_status = sum->group_worst_status; sc.group_bad_instances = sum->group_bad_instances;
+  }
+  return rollout_run(b, B, in0, tp, dt, r, &tk, sum ? &sc : nullptr, true, mem, stream);
+}
+
+// The roll-out with several followed targets (WbcTracks: end effectors and trunk, LINEAR or HERMITE), any frame scored (WbcTrackScores):
+// argument checks, then the shared loop.
+extern "C" int wbc_rollout_tracks(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
+                                  const WbcTracks* tracks, const WbcTrackScores* scores, int mem, void* stream) {
+  if (!r || !tracks) return fail(WBC_E_ARG, "wbc_rollout_tracks: r and tracks are required");
+  if (r->ee_target_step) return fail(WBC_E_ARG, "wbc_rollout_tracks: ee_target_step must be NULL (tracks move the followed targets; the other EE targets are constant)");
+  if (r->hold_ticks != 0) return fail(WBC_E_ARG, "wbc_rollout_tracks: hold_ticks must be 0 (a track holds its last milestone by itself)");
+  if (tracks->n_tracks < 1 || tracks->n_tracks > WBC_MAX_TRACKS)
+    return fail(WBC_E_ARG, "wbc_rollout_tracks: n_tracks = %d outside [1, %d]", tracks->n_tracks, WBC_MAX_TRACKS);
+  unsigned seen = 0;
+  for (int j = 0; j < tracks->n_tracks; ++j) {
+    const WbcTrack& t = tracks->track[j];
+    if (t.target < 0 || t.target > WBC_TARGET_TRUNK) return fail(WBC_E_ARG, "wbc_rollout_tracks: track %d: target = %d outside [0, %d]", j, t.target, WBC_TARGET_TRUNK);
+    if (seen & (1u << t.target)) return fail(WBC_E_ARG, "wbc_rollout_tracks: track %d: target = %d is repeated (each target at most once)", j, t.target);
+    seen |= 1u << t.target;
+    if (t.kind != WBC_TRACK_LINEAR && t.kind != WBC_TRACK_HERMITE) return fail(WBC_E_ARG, "wbc_rollout_tracks: track %d: kind = %d is no WBC_TRACK_*", j, t.kind);
+    if (t.max_points < 2 || t.max_points > WBC_MAX_TRAJ_POINTS)
+      return fail(WBC_E_ARG, "wbc_rollout_tracks: track %d: max_points = %d outside [2, %d]", j, t.max_points, WBC_MAX_TRAJ_POINTS);
+    if (!t.points) return fail(WBC_E_ARG, "wbc_rollout_tracks: track %d: points is required", j);
+    if (t.tangents && t.kind == WBC_TRACK_LINEAR) return fail(WBC_E_ARG, "wbc_rollout_tracks: track %d: tangents must be NULL for a LINEAR track", j);
+    if (!t.du && !(std::isfinite(t.du_all) && t.du_all > 0))
+      return fail(WBC_E_ARG, "wbc_rollout_tracks: track %d: du_all must be finite and positive when du is NULL", j);
+  }
+  const bool trunk_track = (seen >> WBC_TARGET_TRUNK) & 1;
+  if (trunk_track && r->trunk_target_step)
+    return fail(WBC_E_ARG, "wbc_rollout_tracks: trunk_target_step must be NULL with a trunk track (the track moves that target)");
+  if (scores) {
+    if (scores->score_mask < 0 || scores->score_mask >= (1 << WBC_MAX_TRACKS))
+      return fail(WBC_E_ARG, "wbc_rollout_tracks: score_mask = 0x%x has bits beyond frame %d", (unsigned)scores->score_mask, WBC_TARGET_TRUNK);
+    if (scores->group_size < 0 || (scores->group_size > 0 && B % scores->group_size != 0))
+      return fail(WBC_E_ARG, "wbc_rollout_tracks: group_size = %d does not divide B = %d", scores->group_size, B);
+  }
+  const bool trunk_scored = scores && ((scores->score_mask >> WBC_TARGET_TRUNK) & 1);
+  if ((trunk_track || trunk_scored) && in0 && (!in0->trunk_target || !in0->prev_trunk_target))
+    return fail(WBC_E_ARG, "wbc_rollout_tracks: a trunk track or score bit %d needs in0->trunk_target and prev_trunk_target", WBC_TARGET_TRUNK);
+  return rollout_run(b, B, in0, tp, dt, r, tracks, scores, false, mem, stream);
 }
 
 static int qp_common(WbcBatch* b, int B, QpArgs& a, int mem, void* stream, const char* who) {

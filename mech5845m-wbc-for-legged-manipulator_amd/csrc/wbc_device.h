@@ -229,6 +229,7 @@ struct UpdateArgs {
   double *ee_target, *prev_ee_target, *trunk_target, *prev_trunk_target, *ee_prev_rot, *trunk_prev_rot;
   const double *ee_ref_rot, *trunk_ref_euler, *ee_step, *trunk_step;
   double* grip_trace;                  // [B][3] of this tick
+  double* frames_out;                  // [B][6][3] of this tick: the five EE frames and the trunk frame (wbc_rollout_tracks' scored positions), or null
   const int32_t *status, *iters;       // this tick's
   int32_t *status_max, *iters_sum;
   int32_t rot;                         // a model of the handle has a rotated joint placement (wbc_update_packed_kernel<true>)

@@ -759,6 +759,13 @@ __global__ void __launch_bounds__(64) wbc_update_kernel(const UpdateArgs A, cons
     const double d = (lane == 0) ? base[0] - U.q[0] : (lane == 1) ? base[1] - U.q[1] : base[2] - U.q[2];
     A.grip_trace[(size_t)b * 3 + lane] = U.pf[3 * (WBC_FR_EE0 + 4) + lane] + d;
   }
+  if (A.frames_out && lane < 18) {
+    // the five EE frames, then the trunk frame, with the same rigid correction
+    const int f = lane / 3, r = lane - 3 * f;
+    const int fr = (f < 5) ? WBC_FR_EE0 + f : WBC_FR_TRUNK;
+    const double d = (r == 0) ? base[0] - U.q[0] : (r == 1) ? base[1] - U.q[1] : base[2] - U.q[2];
+    A.frames_out[(size_t)b * 18 + lane] = U.pf[3 * fr + r] + d;
+  }
   if (lane == 0) {
     if (A.status_max && st > stm) A.status_max[b] = st;
     if (A.iters_sum) A.iters_sum[b] = its + it;
@@ -884,6 +891,18 @@ __global__ void __launch_bounds__(64) wbc_update_packed_kernel(const UpdateArgs 
   if (A.grip_trace && s < 3) {
     const double d = (s == 0) ? base[0] - qv[0] : (s == 1) ? base[1] - qv[1] : base[2] - qv[2];
     A.grip_trace[b * 3 + s] = U.pf[4 * 5 + s] + d;
+  }
+  if (A.frames_out) {
+    // the five EE frames (U.pf rows 0..3 the feet, 5 the gripper), then the trunk frame (row 4), with the same rigid correction
+    if (s < 15) {
+      const int f = s / 3, rr = s - 3 * f;
+      const double d = (rr == 0) ? base[0] - qv[0] : (rr == 1) ? base[1] - qv[1] : base[2] - qv[2];
+      A.frames_out[b * 18 + s] = U.pf[4 * ((f < 4) ? f : 5) + rr] + d;
+    }
+    if (s < 3) {
+      const double d = (s == 0) ? base[0] - qv[0] : (s == 1) ? base[1] - qv[1] : base[2] - qv[2];
+      A.frames_out[b * 18 + 15 + s] = U.pf[4 * 4 + s] + d;
+    }
   }
   if (s == 0) {
     if (A.status_max && st > stm) A.status_max[b] = st;

@@ -1,11 +1,13 @@
-// wbc_k_traj.hip — wbc_rollout_traj: per-instance milestone trajectories of one end effector's target, and the roll-out summary
-// (the gripper's target-versus-reached log of sim3.py:340-348 reduced on the device). Three small kernels beside the roll-out's tick and
-// update kernels, one lane per instance:
-//   wbc_traj_begin_kernel   once: bad-row check, summary reset, the target of tick 0
-//   wbc_traj_tick_kernel    after the update kernel of tick k: the tick's error and status into the summary, then the target of tick k + 1
+// wbc_k_traj.hip — wbc_rollout_traj / wbc_rollout_tracks: per-instance milestone trajectories (tracks) of the end effectors' and the trunk's
+// targets, piecewise linear or a Hermite spline, and the roll-out's scores (the target-versus-reached log of sim3.py:340-348 reduced on the
+// device, for any of the six frames). Three small kernels beside the roll-out's tick and update kernels, one lane per instance:
+//   wbc_traj_begin_kernel   once: bad-row check, score reset, the targets of tick 0
+//   wbc_traj_tick_kernel    after the update kernel of tick k: the tick's errors and status into the scores, then every followed target of
+//                           tick k + 1 (one launch however many tracks)
 //   wbc_traj_groups_kernel  once at the end: one wavefront per group of M consecutive instances, fixed-shape reduction (no atomics)
-// The target arithmetic is klampt's Trajectory.eval as Robot_Wrapper4._LinearTrajectory restates it, operation for operation and without
-// contraction into fused multiply-adds, so that the host restatement (wbc_workload.traj_targets) is bit-exact.
+// The target arithmetic is klampt's Trajectory.eval / HermiteTrajectory.eval as Robot_Wrapper4._LinearTrajectory / _HermiteTrajectory restate
+// them, operation for operation and without contraction into fused multiply-adds, so that the host restatements
+// (wbc_workload.traj_targets / track_targets) are bit-exact. wbc_rollout_traj is the one-track call (LINEAR, the gripper scored).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "wbc_traj.h"
@@ -18,8 +20,23 @@ constexpr int TRAJ_BLOCK = 256;
 
 __device__ __forceinline__ bool traj_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }   // false for NaN and +-inf
 
-// _LinearTrajectory.eval(t) over the n milestones m[n][3] (Robot_Wrapper4.py): clamped ends, unit parameter per segment
-__device__ __forceinline__ void traj_eval(const double* __restrict__ m, int n, double t, double out[3]) {
+// default tangent of component c at milestone i of the n milestones m[n][3]: the rule of klampt's makeSpline(preventOvershoot=True) as
+// include/wbc.h states it (no segment of the spline leaves the interval of its two milestones)
+__device__ __forceinline__ double traj_tangent(const double* __restrict__ m, int n, int i, int c) {
+  if (n == 2) return m[3 + c] - m[c];
+  if (i == 0 || i == n - 1) return 0.0;
+  const double a = m[3 * (i - 1) + c], x = m[3 * i + c], b = m[3 * (i + 1) + c];
+  const double w = (b - a) * 0.5, third = 1.0 / 3.0;
+  if (x <= fmin(a, b) || x >= fmax(a, b)) return 0.0;
+  if ((w < 0.0 && x - w * third >= a) || (w > 0.0 && x - w * third <= a)) return 3.0 * (x - a);
+  if ((w < 0.0 && x + w * third < b) || (w > 0.0 && x + w * third > b)) return 3.0 * (b - x);
+  return w;
+}
+
+// _LinearTrajectory.eval(t) (HERMITE: _HermiteTrajectory.eval(t)) over the n milestones m[n][3] (Robot_Wrapper4.py): clamped ends, unit
+// parameter per segment. v: the caller's tangents [n][3] or null (HERMITE only)
+template <bool HERMITE>
+__device__ __forceinline__ void traj_eval(const double* __restrict__ m, const double* __restrict__ v, int n, double t, double out[3]) {
   if (t <= 0.0) {
     out[0] = m[0]; out[1] = m[1]; out[2] = m[2];
   } else if (t >= (double)(n - 1)) {
@@ -30,64 +47,146 @@ __device__ __forceinline__ void traj_eval(const double* __restrict__ m, int n, d
     const int i = (int)fi;                 // 0 <= i <= n - 2 here
     const double u = t - fi;
     const double* a = m + 3 * i;
+    if (!HERMITE) {
 #pragma unroll
-    for (int c = 0; c < 3; ++c) out[c] = (1.0 - u) * a[c] + u * a[3 + c];
+      for (int c = 0; c < 3; ++c) out[c] = (1.0 - u) * a[c] + u * a[3 + c];
+    } else {
+      const double u2 = u * u, u3 = u * u2;
+      const double cx1 = (2.0 * u3 - 3.0 * u2) + 1.0, cx2 = (-2.0 * u3) + 3.0 * u2, cv1 = (u3 - 2.0 * u2) + u, cv2 = u3 - u2;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const double v0 = v ? v[3 * i + c] : traj_tangent(m, n, i, c);
+        const double v1 = v ? v[3 * i + 3 + c] : traj_tangent(m, n, i + 1, c);
+        out[c] = ((cx1 * a[c] + cx2 * a[3 + c]) + cv1 * v0) + cv2 * v1;
+      }
+    }
   }
+}
+
+// the target of track T for instance b at tick k (the parameter is the product k * du, not a running sum) into its row of the target blocks
+__device__ __forceinline__ void traj_write_target(const TrajArgs& A, const TrajTrack& T, int b, int k) {
+  const int n = T.n_points ? T.n_points[b] : T.S;
+  const double du = T.du ? T.du[b] : T.du_all;
+  const double* m = T.points + (size_t)b * T.S * 3;
+  const double t = (double)k * du;
+  double nx[3];
+  if (T.kind == WBC_TRACK_HERMITE) traj_eval<true>(m, T.tangents ? T.tangents + (size_t)b * T.S * 3 : nullptr, n, t, nx);
+  else traj_eval<false>(m, nullptr, n, t, nx);
+  double* out = T.target == WBC_TARGET_TRUNK ? A.trunk_target + (size_t)b * 3 : A.ee_target + (size_t)b * 15 + 3 * T.target;
+  out[0] = nx[0]; out[1] = nx[1]; out[2] = nx[2];
 }
 
 __global__ void __launch_bounds__(TRAJ_BLOCK) wbc_traj_begin_kernel(const TrajArgs A) {
   const int b = blockIdx.x * TRAJ_BLOCK + threadIdx.x;
   if (b >= A.B) return;
-  const int n = A.n_points ? A.n_points[b] : A.S;
-  const double du = A.du ? A.du[b] : A.du_all;
-  const double* m = A.points + (size_t)b * A.S * 3;
-  bool bad = n < 2 || n > A.S || !traj_finite(du) || !(du > 0.0);
-  if (!bad) {
+  bool bad = false;
 #pragma unroll 1
-    for (int i = 0; i < 3 * n; ++i) bad |= !traj_finite(m[i]);
+  for (int j = 0; j < A.n_tracks; ++j) {
+    const TrajTrack& T = A.tr[j];
+    const int n = T.n_points ? T.n_points[b] : T.S;
+    const double du = T.du ? T.du[b] : T.du_all;
+    const bool bad_n = n < 2 || n > T.S;
+    bad |= bad_n || !traj_finite(du) || !(du > 0.0);
+    if (!bad_n) {
+      const double* m = T.points + (size_t)b * T.S * 3;
+#pragma unroll 1
+      for (int i = 0; i < 3 * n; ++i) bad |= !traj_finite(m[i]);
+      if (T.tangents) {
+        const double* v = T.tangents + (size_t)b * T.S * 3;
+#pragma unroll 1
+        for (int i = 0; i < 3 * n; ++i) bad |= !traj_finite(v[i]);
+      }
+    }
   }
   A.bad[b] = bad ? 1 : 0;
-  A.err_sq_sum[b] = 0.0; A.err_max[b] = -1.0; A.err_final[b] = 0.0;
-  A.err_max_tick[b] = -1; A.first_bad_tick[b] = -1; A.bad_ticks[b] = 0;
+  int nsc = 0;
+#pragma unroll 1
+  for (int f = 0; f < TRAJ_FRAMES; ++f) {
+    if (!((A.score_mask >> f) & 1)) continue;
+    const size_t i = (size_t)nsc * A.B + b;
+    A.err_sq_sum[i] = 0.0; A.err_max[i] = -1.0; A.err_final[i] = 0.0; A.err_max_tick[i] = -1;
+    ++nsc;
+  }
+  A.first_bad_tick[b] = -1; A.bad_ticks[b] = 0;
   A.status_max[b] = bad ? WBC_QP_NUMERICAL : WBC_QP_OPTIMAL;
   if (bad) {
     atomicAdd(A.bad_count, 1);
     if (A.ro_status_max) A.ro_status_max[b] = WBC_QP_NUMERICAL;   // (the update kernels keep the maximum)
-    return;                                                        // the followed target stays at in0's value
+    return;                                                        // every followed target stays at in0's value
   }
-  double t0[3];
-  traj_eval(m, n, 0.0, t0);
-  double* tg = A.ee_target + (size_t)b * 15 + 3 * A.ee;
-  tg[0] = t0[0]; tg[1] = t0[1]; tg[2] = t0[2];
+#pragma unroll 1
+  for (int j = 0; j < A.n_tracks; ++j) traj_write_target(A, A.tr[j], b, 0);
 }
 
+// ONE: the one-track call (wbc_rollout_traj) — track 0 is LINEAR and follows an end effector, the gripper alone is scored from its own
+// [B][3] row, no trace, no trunk step. The same arithmetic with every loop and lookup of the general form resolved at compile time: the
+// general form costs that call 1.1 us per tick at B = 65536 (profiles/r08_rollout_tracks.txt).
+template <bool ONE>
 __global__ void __launch_bounds__(TRAJ_BLOCK) wbc_traj_tick_kernel(const TrajArgs A, const int k) {
   const int b = blockIdx.x * TRAJ_BLOCK + threadIdx.x;
   if (b >= A.B) return;
   const bool bad = A.bad[b] != 0;
+  if (ONE) {
+    if (A.do_sum) {
+      const double* g = A.reached + (size_t)b * 3;
+      const double* tg = A.ee_target + (size_t)b * 15 + 12;           // the gripper's target of THIS tick (the update kernel left it in place)
+      const double dx = g[0] - tg[0], dy = g[1] - tg[1], dz = g[2] - tg[2];
+      const double e2 = (dx * dx + dy * dy) + dz * dz;
+      const double e = sqrt(e2);
+      const int st = A.status[b];
+      A.err_sq_sum[b] = A.err_sq_sum[b] + e2;                         // summed in tick order
+      if (e > A.err_max[b]) { A.err_max[b] = e; A.err_max_tick[b] = k; }   // strictly larger: the FIRST tick of the maximum
+      A.err_final[b] = e;
+      if (!bad && st > A.status_max[b]) A.status_max[b] = st;
+      if (bad || st != WBC_QP_OPTIMAL) {
+        if (A.first_bad_tick[b] < 0) A.first_bad_tick[b] = k;
+        A.bad_ticks[b] = A.bad_ticks[b] + 1;
+      }
+    }
+    if (bad) return;
+    const TrajTrack& T = A.tr[0];
+    const int n = T.n_points ? T.n_points[b] : T.S;
+    const double du = T.du ? T.du[b] : T.du_all;
+    double nx[3];
+    traj_eval<false>(T.points + (size_t)b * T.S * 3, nullptr, n, (double)(k + 1) * du, nx);   // the parameter is the product, not a running sum
+    double* out = A.ee_target + (size_t)b * 15 + 3 * T.target;
+    out[0] = nx[0]; out[1] = nx[1]; out[2] = nx[2];
+    return;
+  }
   if (A.do_sum) {
-    const double* g = A.grip + (size_t)b * 3;
-    const double* tg = A.ee_target + (size_t)b * 15 + 12;           // the gripper's target of THIS tick (the update kernel left it in place)
-    const double dx = g[0] - tg[0], dy = g[1] - tg[1], dz = g[2] - tg[2];
-    const double e2 = (dx * dx + dy * dy) + dz * dz;
-    const double e = sqrt(e2);
+    int nsc = 0;
+#pragma unroll 1
+    for (int f = 0; f < TRAJ_FRAMES; ++f) {
+      if (!((A.score_mask >> f) & 1)) continue;
+      const double* g = A.reached + (size_t)b * A.reached_stride + A.reached_off[f];
+      // the frame's target of THIS tick (the update kernel left it in place)
+      const double* tg = f == WBC_TARGET_TRUNK ? A.trunk_target + (size_t)b * 3 : A.ee_target + (size_t)b * 15 + 3 * f;
+      const double gx = g[0], gy = g[1], gz = g[2];
+      const double dx = gx - tg[0], dy = gy - tg[1], dz = gz - tg[2];
+      const double e2 = (dx * dx + dy * dy) + dz * dz;
+      const double e = sqrt(e2);
+      const size_t i = (size_t)nsc * A.B + b;
+      A.err_sq_sum[i] = A.err_sq_sum[i] + e2;                         // summed in tick order
+      if (e > A.err_max[i]) { A.err_max[i] = e; A.err_max_tick[i] = k; }   // strictly larger: the FIRST tick of the maximum
+      A.err_final[i] = e;
+      if (A.trace) { double* tr = A.trace + i * 3; tr[0] = gx; tr[1] = gy; tr[2] = gz; }
+      ++nsc;
+    }
     const int st = A.status[b];
-    A.err_sq_sum[b] = A.err_sq_sum[b] + e2;                         // summed in tick order
-    if (e > A.err_max[b]) { A.err_max[b] = e; A.err_max_tick[b] = k; }   // strictly larger: the FIRST tick of the maximum
-    A.err_final[b] = e;
     if (!bad && st > A.status_max[b]) A.status_max[b] = st;
     if (bad || st != WBC_QP_OPTIMAL) {
       if (A.first_bad_tick[b] < 0) A.first_bad_tick[b] = k;
       A.bad_ticks[b] = A.bad_ticks[b] + 1;
     }
   }
+  if (A.trunk_step) {                                                 // a constant step of a trunk target no track follows (as the update kernel's)
+    double* tt = A.trunk_target + (size_t)b * 3;
+    const double* ts = A.trunk_step + (size_t)b * 3;
+    tt[0] = tt[0] + ts[0]; tt[1] = tt[1] + ts[1]; tt[2] = tt[2] + ts[2];
+  }
   if (bad) return;
-  const int n = A.n_points ? A.n_points[b] : A.S;
-  const double du = A.du ? A.du[b] : A.du_all;
-  double nx[3];
-  traj_eval(A.points + (size_t)b * A.S * 3, n, (double)(k + 1) * du, nx);   // the parameter is the product, not a running sum
-  double* out = A.ee_target + (size_t)b * 15 + 3 * A.ee;
-  out[0] = nx[0]; out[1] = nx[1]; out[2] = nx[2];
+#pragma unroll 1
+  for (int j = 0; j < A.n_tracks; ++j) traj_write_target(A, A.tr[j], b, k + 1);
 }
 
 // One wavefront per group: lane l takes instances l, l + 64, ... of the group in that order, then a butterfly over the 64 lanes. The
@@ -95,30 +194,43 @@ __global__ void __launch_bounds__(TRAJ_BLOCK) wbc_traj_tick_kernel(const TrajArg
 __global__ void __launch_bounds__(64) wbc_traj_groups_kernel(const TrajGroupArgs A) {
   const int g = blockIdx.x, lane = threadIdx.x;
   if (g >= A.G) return;
-  const size_t base = (size_t)g * A.M;
-  double sum = 0.0, emax = -1.0;
+  const size_t base = (size_t)g * A.M, nb = (size_t)A.G * A.M;
   int worst = 0, nbad = 0;
 #pragma unroll 1
   for (int i = lane; i < A.M; i += 64) {
-    sum = sum + A.err_sq_sum[base + i];
-    emax = fmax(emax, A.err_max[base + i]);
     const int s = A.status_max[base + i];
     worst = s > worst ? s : worst;
     nbad += A.bad_ticks[base + i] > 0;
   }
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) {
-    sum = sum + __shfl_xor(sum, off, 64);
-    emax = fmax(emax, __shfl_xor(emax, off, 64));
     const int w = __shfl_xor(worst, off, 64);
     worst = w > worst ? w : worst;
     nbad += __shfl_xor(nbad, off, 64);
   }
   if (lane == 0) {
-    if (A.group_rms) A.group_rms[g] = sqrt(sum / ((double)A.M * (double)A.ticks));
-    if (A.group_err_max) A.group_err_max[g] = emax;
     if (A.group_worst_status) A.group_worst_status[g] = worst;
     if (A.group_bad_instances) A.group_bad_instances[g] = nbad;
+  }
+#pragma unroll 1
+  for (int j = 0; j < A.n_scored; ++j) {
+    const double* sq = A.err_sq_sum + j * nb + base;
+    const double* em = A.err_max + j * nb + base;
+    double sum = 0.0, emax = -1.0;
+#pragma unroll 1
+    for (int i = lane; i < A.M; i += 64) {
+      sum = sum + sq[i];
+      emax = fmax(emax, em[i]);
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+      sum = sum + __shfl_xor(sum, off, 64);
+      emax = fmax(emax, __shfl_xor(emax, off, 64));
+    }
+    if (lane == 0) {
+      if (A.group_rms) A.group_rms[(size_t)j * A.G + g] = sqrt(sum / ((double)A.M * (double)A.ticks));
+      if (A.group_err_max) A.group_err_max[(size_t)j * A.G + g] = emax;
+    }
   }
 }
 
@@ -133,7 +245,9 @@ int launch_traj_begin(const TrajArgs& a, void* stream) {
 }
 
 int launch_traj_tick(const TrajArgs& a, int k, void* stream) {
-  hipLaunchKernelGGL(wbc_traj_tick_kernel, dim3((a.B + TRAJ_BLOCK - 1) / TRAJ_BLOCK), dim3(TRAJ_BLOCK), 0, (hipStream_t)stream, a, k);
+  const dim3 grid((a.B + TRAJ_BLOCK - 1) / TRAJ_BLOCK), block(TRAJ_BLOCK);
+  if (a.one_track) hipLaunchKernelGGL(wbc_traj_tick_kernel<true>, grid, block, 0, (hipStream_t)stream, a, k);
+  else hipLaunchKernelGGL(wbc_traj_tick_kernel<false>, grid, block, 0, (hipStream_t)stream, a, k);
   return traj_launched();
 }
 

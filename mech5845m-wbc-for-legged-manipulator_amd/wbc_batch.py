@@ -440,6 +440,132 @@ class WbcBatch:
                                              C.byref(sm) if sm is not None else None, mem, self._stream(mem)), self.lib)
         return out
 
+    _TRACK_KEYS = ("target", "points", "kind", "tangents", "n_points", "du")
+    _KINDS = {"linear": capi.TRACK_LINEAR, "hermite": capi.TRACK_HERMITE, capi.TRACK_LINEAR: capi.TRACK_LINEAR, capi.TRACK_HERMITE: capi.TRACK_HERMITE}
+    _FRAME_SCORES = (("err_sq_sum", np.float64), ("err_max", np.float64), ("err_final", np.float64), ("err_max_tick", np.int32))
+    _INSTANCE_SCORES = (("first_bad_tick", np.int32), ("bad_ticks", np.int32))
+
+    @staticmethod
+    def _target_index(t, what):
+        if isinstance(t, str):
+            if t != "trunk":
+                raise capi.WbcError("%s: %r is neither 'trunk' nor an end effector index 0..%d" % (what, t, capi.NEE - 1))
+            return capi.TARGET_TRUNK
+        if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or not 0 <= int(t) <= capi.TARGET_TRUNK:
+            raise capi.WbcError("%s: %r is neither 'trunk' nor an end effector index 0..%d" % (what, t, capi.NEE - 1))
+        return int(t)
+
+    def rollout_tracks(self, inputs, dt, ticks, tracks, score=(), group_size=0, want_trace=False, mode=capi.ROLLOUT_RUNNING,
+                       task_params=None, trunk_target_step=None, imu=None):
+        """`ticks` closed-loop ticks with several targets following per-instance tracks (wbc_rollout_tracks, include/wbc.h). tracks: a list of
+        dicts with target ("trunk" or an end effector index 0..4, each at most once), points [B, S, 3], and optionally kind ("linear",
+        the default, or "hermite"), tangents [B, S, 3] (hermite only; None: wbc_workload.spline_tangents), n_points [B] int32 (None: S),
+        du [B] or one number (default 0.002). Tick k's target is wbc_workload.track_targets(points, n_points, du, k, kind, tangents).
+        score: the frames ("trunk" or 0..4) scored against their target of the tick, followed or constant. Returns rollout()'s dict
+        (grip_trace only with want_trace) plus trunk_target [B, 3] (with a trunk target among the inputs) and, with frames to score,
+        err_sq_sum, err_max, err_final, err_max_tick [n_scored, B] (frames in increasing index order, the trunk last), first_bad_tick,
+        bad_ticks [B], with want_trace trace [ticks, n_scored, B, 3], and with group_size = M > 0 group_rms, group_err_max
+        [n_scored, B / M], group_worst_status, group_bad_instances [B / M] — all reduced on the device."""
+        keep = []
+        tracks = list(tracks)
+        if not 1 <= len(tracks) <= capi.MAX_TRACKS:
+            raise capi.WbcError("tracks: %d given, want 1..%d" % (len(tracks), capi.MAX_TRACKS))
+        arrays = []
+        for i, t in enumerate(tracks):
+            if not isinstance(t, dict) or set(t) - set(self._TRACK_KEYS) or "target" not in t or "points" not in t:
+                raise capi.WbcError("tracks[%d]: want a dict with target, points and optionally kind, tangents, n_points, du" % i)
+            arrays += [t["points"], t.get("tangents"), t.get("n_points"), None if np.isscalar(t.get("du", 0.002)) else t.get("du")]
+        mem = _mem_of(list(inputs.values()) + arrays + [trunk_target_step, imu, task_params])
+        q = inputs.get("q")
+        B = self._batch_of(q)
+        M = int(group_size)
+        if M < 0 or (M > 0 and B % M != 0):
+            raise capi.WbcError("group_size = %d does not divide B = %d" % (M, B))
+        if int(ticks) < 1:
+            raise capi.WbcError("ticks = %d, want >= 1" % ticks)
+        f = np.float64
+        P = self._p
+        tk = capi.WbcTracks()
+        tk.n_tracks = len(tracks)
+        seen = set()
+        for i, t in enumerate(tracks):
+            who = "tracks[%d]" % i
+            c = tk.track[i]
+            c.target = self._target_index(t["target"], who + ".target")
+            if c.target in seen:
+                raise capi.WbcError("%s.target: %r is followed twice" % (who, t["target"]))
+            seen.add(c.target)
+            kind = t.get("kind", "linear")
+            if not isinstance(kind, (str, int)) or kind not in self._KINDS:
+                raise capi.WbcError("%s.kind: %r is neither 'linear' nor 'hermite'" % (who, kind))
+            c.kind = self._KINDS[kind]
+            shape = tuple(getattr(t["points"], "shape", ()))
+            if len(shape) != 3 or shape[0] != B or shape[2] != 3 or not 2 <= shape[1] <= capi.MAX_TRAJ_POINTS:
+                raise capi.WbcError("%s.points: shape %s, want (%d, S, 3) with 2 <= S <= %d" % (who, shape, B, capi.MAX_TRAJ_POINTS))
+            S = int(shape[1])
+            c.max_points = S
+            c.points = P(t["points"], f, keep, B, S * 3, who + ".points")
+            tg = t.get("tangents")
+            if tg is not None:
+                if c.kind == capi.TRACK_LINEAR:
+                    raise capi.WbcError("%s.tangents: a linear track has no tangents" % who)
+                if tuple(getattr(tg, "shape", ())) != shape:
+                    raise capi.WbcError("%s.tangents: shape %s, want %s" % (who, tuple(getattr(tg, "shape", ())), shape))
+                c.tangents = P(tg, f, keep, B, S * 3, who + ".tangents")
+            c.n_points = P(t.get("n_points"), np.int32, keep, B, 1, who + ".n_points")
+            du = t.get("du", 0.002)
+            if np.isscalar(du):
+                c.du_all = float(du)
+            else:
+                c.du = P(du, f, keep, B, 1, who + ".du")
+        if capi.TARGET_TRUNK in seen and trunk_target_step is not None:
+            raise capi.WbcError("trunk_target_step: not together with a trunk track")
+        frames = sorted({self._target_index(s_, "score") for s_ in score})
+        if len(frames) != len(list(score)):
+            raise capi.WbcError("score: a frame is listed twice")
+        need_trunk = capi.TARGET_TRUNK in seen or capi.TARGET_TRUNK in frames
+        if need_trunk and (inputs.get("trunk_target") is None or inputs.get("prev_trunk_target") is None):
+            raise capi.WbcError("a trunk track or a scored trunk needs the inputs trunk_target and prev_trunk_target")
+        K, ns = int(ticks), len(frames)
+        out = dict(q=self._alloc(q, (B, NQS)), qdot=self._alloc(q, (B, NV)), ee_target=self._alloc(q, (B, 5, 3)),
+                   status=self._alloc(q, (B,), np.int32), iters=self._alloc(q, (B,), np.int32))
+        if inputs.get("trunk_target") is not None:
+            out["trunk_target"] = self._alloc(q, (B, 3))
+            tk.trunk_target_final = P(out["trunk_target"], f, keep)
+        if want_trace:
+            out["grip_trace"] = self._alloc(q, (K, B, 3))
+        r = capi.WbcRollout()
+        r.ticks, r.mode, r.hold_ticks = K, int(mode), 0
+        r.trunk_target_step, r.imu = P(trunk_target_step, f, keep, B, 3, "trunk_target_step"), P(imu, f, keep, B, 4, "imu")
+        r.q_final, r.qdot_last, r.ee_target_final = P(out["q"], f, keep), P(out["qdot"], f, keep), P(out["ee_target"], f, keep)
+        r.status_max, r.iters_sum = P(out["status"], np.int32, keep), P(out["iters"], np.int32, keep)
+        if want_trace:
+            r.grip_trace = P(out["grip_trace"], f, keep)
+        sc = None
+        if ns:
+            sc = capi.WbcTrackScores()
+            sc.group_size = M
+            for fr in frames:
+                sc.score_mask |= 1 << fr
+            for name, dtype in self._FRAME_SCORES:
+                out[name] = self._alloc(q, (ns, B), dtype)
+            for name, dtype in self._INSTANCE_SCORES:
+                out[name] = self._alloc(q, (B,), dtype)
+            if want_trace:
+                out["trace"] = self._alloc(q, (K, ns, B, 3))
+            if M > 0:
+                for name, dtype in self._GROUP_SUMMARY:
+                    out[name] = self._alloc(q, (ns, B // M) if name in ("group_rms", "group_err_max") else (B // M,), dtype)
+            dtypes = dict(self._FRAME_SCORES + self._INSTANCE_SCORES + self._GROUP_SUMMARY, trace=f)
+            for name, _ in capi.WbcTrackScores._fields_[2:]:
+                if name in out:
+                    setattr(sc, name, P(out[name], dtypes[name], keep))
+        tin = self._tick_in(inputs, keep, B)
+        tp = _task_params(task_params, B, keep, self.device_id)
+        capi.check(self.lib.wbc_rollout_tracks(self._h, B, C.byref(tin), tp, float(dt), C.byref(r), C.byref(tk),
+                                               C.byref(sc) if sc is not None else None, mem, self._stream(mem)), self.lib)
+        return out
+
     def integrate(self, q, v, dt, model_id=None):
         """pin.integrate(model, q, v * dt) for every instance."""
         keep = []

@@ -97,6 +97,26 @@ class WbcRolloutSummary(C.Structure):
             "group_rms", "group_err_max", "group_worst_status", "group_bad_instances")]
 
 
+# wbc_rollout_tracks: several followed targets (end effectors 0..4 and the trunk, 5), linear or Hermite, any frame scored (include/wbc.h)
+MAX_TRACKS, TARGET_TRUNK = 6, 5
+TRACK_LINEAR, TRACK_HERMITE = 0, 1
+
+
+class WbcTrack(C.Structure):
+    _fields_ = [("target", C.c_int32), ("kind", C.c_int32), ("max_points", C.c_int32), ("pad_", C.c_int32), ("points", C.c_void_p),
+                ("tangents", C.c_void_p), ("n_points", C.c_void_p), ("du", C.c_void_p), ("du_all", C.c_double)]
+
+
+class WbcTracks(C.Structure):
+    _fields_ = [("n_tracks", C.c_int32), ("pad_", C.c_int32), ("track", WbcTrack * MAX_TRACKS), ("trunk_target_final", C.c_void_p)]
+
+
+class WbcTrackScores(C.Structure):
+    _fields_ = [("score_mask", C.c_int32), ("group_size", C.c_int32)] + [(n, C.c_void_p) for n in (
+        "err_sq_sum", "err_max", "err_final", "err_max_tick", "first_bad_tick", "bad_ticks", "trace", "group_rms", "group_err_max",
+        "group_worst_status", "group_bad_instances")]
+
+
 class WbcFkOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("oMi", "oMf", "J", "com", "Jcom")]
 
@@ -137,6 +157,8 @@ SIGNATURES = {
     "wbc_rollout_tp": (_i, [_vp, _i, C.POINTER(WbcTickIn), _vp, _d, C.POINTER(WbcRollout), _i, _vp]),
     "wbc_rollout_traj": (_i, [_vp, _i, C.POINTER(WbcTickIn), _vp, _d, C.POINTER(WbcRollout), C.POINTER(WbcTrajectory),
                               C.POINTER(WbcRolloutSummary), _i, _vp]),
+    "wbc_rollout_tracks": (_i, [_vp, _i, C.POINTER(WbcTickIn), _vp, _d, C.POINTER(WbcRollout), C.POINTER(WbcTracks),
+                                C.POINTER(WbcTrackScores), _i, _vp]),
     "wbc_integrate": (_i, [_vp, _i, _vp, _vp, _vp, _d, _i, _vp, _vp]),
     "wbc_batch_set_option": (_i, [_vp, C.c_char_p, _i]),
     "wbc_batch_get_stat": (_i, [_vp, C.c_char_p, _vp, C.POINTER(C.c_int64)]),

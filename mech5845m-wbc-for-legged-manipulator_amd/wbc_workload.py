@@ -126,3 +126,66 @@ def traj_targets(points, n_points, du, k):
     last = t >= n - 1
     out[last] = points[last, n[last] - 1]
     return out
+
+
+def spline_tangents(points, n_points=None):
+    """Default tangents [B, S, 3] of Hermite tracks (wbc_rollout_tracks with tangents == NULL, include/wbc.h), bit for bit: the rule of
+    klampt's HermiteTrajectory.makeSpline(preventOvershoot=True). Two milestones: the chord. Three or more: zero at both ends; interior
+    milestone i per component with a = m[i - 1], x = m[i], b = m[i + 1], w = (b - a) * 0.5: 0 at an extremum or a flat, else 3 (x - a) /
+    3 (b - x) where the centred difference w would overshoot a / b, else w. Rows beyond n_points[b] are never read and come back zero."""
+    points = np.asarray(points, dtype=np.float64)
+    B, S = points.shape[0], points.shape[1]
+    n = np.full(B, S, dtype=np.int64) if n_points is None else np.asarray(n_points, dtype=np.int64).reshape(B)
+    v = np.zeros((B, S, 3))
+    third = 1.0 / 3.0
+    with np.errstate(invalid="ignore"):
+        for i in range(1, S - 1):
+            rows = n > i + 1                                            # milestone i is interior
+            if not rows.any():
+                continue
+            a, x, b = points[rows, i - 1], points[rows, i], points[rows, i + 1]
+            w = (b - a) * 0.5
+            flat = (x <= np.minimum(a, b)) | (x >= np.maximum(a, b))
+            lo = ((w < 0) & (x - w * third >= a)) | ((w > 0) & (x - w * third <= a))
+            hi = ((w < 0) & (x + w * third < b)) | ((w > 0) & (x + w * third > b))
+            v[rows, i] = np.where(flat, 0.0, np.where(lo, 3.0 * (x - a), np.where(hi, 3.0 * (b - x), w)))
+    two = n == 2
+    if two.any():
+        chord = points[two, 1] - points[two, 0]
+        v[two, 0] = chord
+        v[two, 1] = chord
+    return v
+
+
+def track_targets(points, n_points, du, k, kind="linear", tangents=None):
+    """Targets [B, 3] of tick k along per-instance tracks: wbc_rollout_tracks' evaluation restated for a whole batch, bit for bit
+    (include/wbc.h). kind "linear": traj_targets. kind "hermite": the cubic Hermite spline through the milestones with unit knot spacing
+    (Robot_Wrapper4._HermiteTrajectory); tangents [B, S, 3], None: spline_tangents(points, n_points)."""
+    if kind == "linear":
+        if tangents is not None:
+            raise ValueError("a linear track has no tangents")
+        return traj_targets(points, n_points, du, k)
+    if kind != "hermite":
+        raise ValueError("kind %r is neither 'linear' nor 'hermite'" % (kind,))
+    points = np.asarray(points, dtype=np.float64)
+    B, S = points.shape[0], points.shape[1]
+    n = np.full(B, S, dtype=np.int64) if n_points is None else np.asarray(n_points, dtype=np.int64).reshape(B)
+    vel = spline_tangents(points, n) if tangents is None else np.asarray(tangents, dtype=np.float64).reshape(B, S, 3)
+    t = float(k) * np.broadcast_to(np.asarray(du, dtype=np.float64), (B,))
+    inner = (t > 0) & (t < n - 1)
+    i = np.where(inner, np.floor(np.where(inner, t, 0.0)), 0.0).astype(np.int64)
+    i1 = np.minimum(i + 1, S - 1)
+    u = np.where(inner, t - i, 0.0)[:, None]
+    rows = np.arange(B)
+    u2 = u * u
+    u3 = u * u2
+    cx1 = (2.0 * u3 - 3.0 * u2) + 1.0
+    cx2 = (-2.0 * u3) + 3.0 * u2
+    cv1 = (u3 - 2.0 * u2) + u
+    cv2 = u3 - u2
+    with np.errstate(invalid="ignore"):                                 # (rows at a clamped end may touch entries beyond n_points: overwritten below)
+        out = ((cx1 * points[rows, i] + cx2 * points[rows, i1]) + cv1 * vel[rows, i]) + cv2 * vel[rows, i1]
+    out[t <= 0] = points[t <= 0, 0]
+    last = t >= n - 1
+    out[last] = points[last, n[last] - 1]
+    return out

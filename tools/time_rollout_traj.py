@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""Closed-loop ticks/s of wbc_rollout_traj (two milestones = one segment, summary on, no trace) against wbc_rollout on the same inputs:
-what the per-tick trajectory kernel costs. Same process, same handle, interleaved rounds, HIP events around each call.
-    python3 tools/time_rollout_traj.py [B] [ticks] [rounds]"""
+"""Closed-loop ticks/s of wbc_rollout_traj (two milestones = one segment, summary on, no trace) and of wbc_rollout_tracks with two tracks
+(the trunk on a four-milestone HERMITE spline, the gripper on the same LINEAR segment, both scored, no trace) against wbc_rollout on the
+same inputs: what the per-tick trajectory kernel costs. Same process, same handle, interleaved rounds, HIP events around each call.
+    python3 tools/time_rollout_traj.py [B] [ticks] [rounds] [only]      only: run the calls whose label contains one of these comma-separated
+                                                                        words (e.g. tracks, for a profiler run of that leg alone)"""
 import json
 import os
 import sys
@@ -19,6 +21,7 @@ from wbc_batch import WbcBatch
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 65536
 TICKS = int(sys.argv[2]) if len(sys.argv) > 2 else 500
 ROUNDS = int(sys.argv[3]) if len(sys.argv) > 3 else 5
+ONLY = sys.argv[4] if len(sys.argv) > 4 else ""
 DT = 0.002
 
 model = wbc_model.load_model("a1_wx200")
@@ -37,11 +40,19 @@ step[:, 4] = (points[:, 1] - points[:, 0]) / TICKS
 dev = {k: torch.from_numpy(np.ascontiguousarray(v)).cuda() for k, v in d.items()}
 imu = dev["q"][:, 3:7].contiguous()
 step_d, pts_d = torch.from_numpy(step).cuda(), torch.from_numpy(points).cuda()
+# the trunk's track: four milestones within a centimetre of its target, crossed in the call's ticks (three knots between ticks)
+trunk_pts = d["trunk_target"][:, None, :] + np.random.default_rng(1).normal(0, 0.003, (B, 4, 3))
+trunk_pts[:, 0] = d["trunk_target"]
+trunk_d = torch.from_numpy(trunk_pts).cuda()
+two_tracks = [dict(target="trunk", points=trunk_d, kind="hermite", du=3.0 / TICKS), dict(target=4, points=pts_d, du=1.0 / TICKS)]
 
 calls = {
     "wbc_rollout (no trace)": lambda: bt.rollout(dev, DT, TICKS, ee_target_step=step_d, imu=imu, want_trace=False),
     "wbc_rollout_traj (summary, no trace)": lambda: bt.rollout_traj(dev, DT, TICKS, pts_d, du=1.0 / TICKS, imu=imu),
+    "wbc_rollout_tracks (trunk HERMITE + gripper LINEAR, both scored, no trace)":
+        lambda: bt.rollout_tracks(dev, DT, TICKS, two_tracks, score=("trunk", 4), imu=imu),
 }
+calls = {k: v for k, v in calls.items() if any(w in k for w in ONLY.split(","))}
 ms = {k: [] for k in calls}
 last = {}
 for rnd in range(ROUNDS + 1):                             # (the first round settles clocks, caches and the lazy workspaces: not counted)
@@ -58,9 +69,11 @@ for label, t in ms.items():
     print(json.dumps({"call": label, "B": B, "ticks": TICKS, "rounds": ROUNDS, "ms_median": round(med, 3), "ms_min": round(min(t), 3),
                       "ms_max": round(max(t), 3), "M_closed_loop_ticks_per_s": round(B * TICKS / med / 1e3, 2),
                       "last_path": bt.stat("last_path")}))
-a, b = (float(np.median(ms[k])) for k in calls)
-print("# wbc_rollout_traj takes %+.2f %% against wbc_rollout (%.1f us per tick more)" % (100.0 * (b / a - 1.0), 1e3 * (b - a) / TICKS))
-old, new = (last[k] for k in calls)
-same = bool((old["status"] == new["status"]).all().item())
-print("# same inputs: status identical %s, q max-abs difference %.3e" % (same, float((old["q"] - new["q"]).abs().max().item())))
+if len(calls) == 3:
+    a, b, c = (float(np.median(ms[k])) for k in calls)
+    print("# wbc_rollout_traj takes %+.2f %% against wbc_rollout (%.1f us per tick more)" % (100.0 * (b / a - 1.0), 1e3 * (b - a) / TICKS))
+    print("# wbc_rollout_tracks (two tracks) takes %+.2f %% against wbc_rollout (%.1f us per tick more)" % (100.0 * (c / a - 1.0), 1e3 * (c - a) / TICKS))
+    old, new, _ = (last[k] for k in calls)
+    same = bool((old["status"] == new["status"]).all().item())
+    print("# same inputs: status identical %s, q max-abs difference %.3e" % (same, float((old["q"] - new["q"]).abs().max().item())))
 bt.close()
