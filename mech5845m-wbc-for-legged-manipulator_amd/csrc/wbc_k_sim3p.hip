@@ -663,14 +663,23 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
     const unsigned long long nb = __ballot(status != WBC_QP_OPTIMAL);
     if ((nb >> rbase) & 0xFFFFull) { status = WBC_QP_NUMERICAL; live = false; }
   }
-  // ---- Cholesky H' = L L' fused with the substitution L y = e_s (two columns per trip on fixed registers; columns broadcast through V.cl / V.yv)
+  // ---- Cholesky H' = L L' fused with the substitution L y = e_s (two columns per trip on fixed registers). The columns come by DPP row broadcast
+  // (top level, all lanes active; lanes s >= PV are a source for no column entry) and touch no LDS: V.cl, V.yv and V.tv keep what
+  // the stages above left there, and every reader below — x0's V.tv, the dual loop's V.yv, the refinement's and the outputs' V.cl — follows a
+  // store of all 16 entries by the row's own lanes. A/B switch: SIM3P_SWEEP_LDS brings back the LDS form with the zeroing of its column vectors.
   WSYNC();
+#ifdef SIM3P_SWEEP_LDS
   V.cl[s] = 0.0; V.cl[16 + s] = 0.0;        // (the row bounds were staged there)
   V.yv[s] = 0.0; V.tv[s] = 0.0;             // second column vector of the blocked sweep: yv | tv, 32 contiguous entries, zero tail
+#endif
   double y[PV];
 #pragma unroll
   for (int k = 0; k < PV; ++k) y[k] = (k == s) ? 1.0 : 0.0;
+#ifdef SIM3P_SWEEP_LDS
   const double pmin = chol_sweep2<PV>(h, y, V.cl, V.yv, s, s < PV);      // (wbc_packed.h)
+#else
+  const double pmin = chol_sweep2_bc<PV>(h, y);                          // (wbc_packed.h)
+#endif
   if (live && !(pmin > 0.0)) { status = WBC_QP_NUMERICAL; live = false; }
   PSTOP(4, y[0] + y[11] + h[11]);
   // y = row s of J0 = L^-T.  jf2 = |J0|_F^2 per instance

@@ -1,5 +1,5 @@
 // wbc_packed.h — what the packed kernels share (four instances per wavefront, lane = 16 r + s): the packed sim3 tick's LDS layout, the DPP
-// row reductions, chol_sweep2, the wave order, and the kinematics and input staging every packed tick / update kernel runs — the FK seed and
+// row reductions and broadcast, chol_sweep2, the wave order, and the kinematics and input staging every packed tick / update kernel runs — the FK seed and
 // level sweep (pk_fk_seed, pk_fk_sweep), the WORLD Jacobian column of a DoF (pk_jac_col), calcTargetVelTrunk2 (pk_trunk_target_vel) with its
 // inputs (pk_trunk_input), the EE orientation feed-forward (pk_ee_omega) and the staged weights image (pk_stage_weights). The per-DoF
 // velocity damper and the Euler matrix, which the one-instance kernels use too, are in wbc_common.h (damper_bounds, euler_to_R).
@@ -123,6 +123,20 @@ __device__ __forceinline__ unsigned long long ror16a(unsigned long long v) {
   return v;
 }
 
+// The value of lane K of the caller's 16-lane row, in every lane of the row: ONE v_mov_b64_dpp row_newbcast:K — no LDS, no wait.
+// The contract of rsum16a & co. above: only where ALL 64 LANES ARE ACTIVE, in wave-uniform control flow. There is no `old` operand (bound_ctrl): a
+// lane whose source lane is switched off in exec reads 0, not its own value. Rows of a short last wave (valid == false) are active lanes. The
+// 64-bit builtin form is the one that lowers to a single move; the two-halves form of dpp_all<> gives two v_mov_b32_dpp.
+template <int K>
+__device__ __forceinline__ double row_bc(double v) {
+  static_assert(K >= 0 && K < 16, "a lane of the 16-lane row");
+  return __builtin_amdgcn_update_dpp(0.0, v, 0x150 + K, 0xF, 0xF, true);
+}
+template <int N, int K0, int K = K0>
+__device__ __forceinline__ void row_bc_from(double (&c)[N], const double v) {     // c[k] = row_bc<k>(v), k = K0 .. N - 1
+  if constexpr (K < N) { c[K] = row_bc<K>(v); row_bc_from<N, K0, K + 1>(c, v); }
+}
+
 // The packed kernels' Cholesky sweep H' = L L' fused with the forward substitution L y = rhs (y comes in holding the lane's right-hand side: e_s, or g'
 // on a padding lane), two columns per trip: the raw columns j and j + 1 of every row go through the LDS vectors c0v / c1v together and each lane redoes,
 // for the rows below, the one update that column j + 1 receives from step j — the same operations in the same order as two single steps, one LDS round
@@ -163,6 +177,51 @@ __device__ __forceinline__ double chol_sweep2(double (&h)[N], double (&y)[N], do
     for (int k = j + 2; k < N; ++k) y[k] = fma(-ty2, cm1[k], fma(-ty, cm0[k], y[k]));
     y[j] = fma(-ty2, 0.0, yk); y[j + 1] = yk2;
   }
+  return pmin;
+}
+// The same sweep with its columns taken by DPP row broadcast instead of through LDS: entry k of column j is h[j] of lane k of the
+// same 16-lane row, so trip j takes cm0[k] = row_bc<k>(h[j]), cm1[k] = row_bc<k>(h[j + 1]) for the k >= j the LDS form reads and goes on with the
+// same expressions in the same order — the same bits, without the six store / ds_read_b128 round trips that each stood in front of a pivot's
+// rsqrt chain. row_bc's contract: call it at top level, all 64 lanes active. Lanes s >= N are a source for no k < N and run the same arithmetic
+// on their own h as in the LDS form. The packed sim3 tick alone uses it; the orth and box ticks keep the LDS form.
+template <int N, int J = 0>
+__device__ __forceinline__ void chol_sweep2_bc_trip(double (&h)[N], double (&y)[N], double& pmin) {
+  if constexpr (J < N) {
+    constexpr int j = J;
+    double cm0[N], cm1[N];
+    row_bc_from<N, j>(cm0, h[j]);
+    row_bc_from<N, j>(cm1, h[j + 1]);
+    const double pj = cm0[j];
+    pmin = (pj > 0.0) ? fmin(pmin, pj) : -1.0;
+    const double rinv = rsqrt(pj), ipj = rinv * rinv;
+    // step j on this row
+    const double th = h[j] * ipj, ty = y[j] * ipj, yk = y[j] * rinv;
+    const double h1 = fma(-th, cm0[j + 1], h[j + 1]), y1 = fma(-ty, cm0[j + 1], y[j + 1]);
+    // step j as it acts on column j + 1 of the rows below (what their own lanes compute for themselves)
+    const double a = cm0[j + 1];
+#pragma unroll
+    for (int k = j + 1; k < N; ++k) cm1[k] = fma(-(cm0[k] * ipj), a, cm1[k]);
+    const double pj2 = cm1[j + 1];
+    pmin = (pj2 > 0.0) ? fmin(pmin, pj2) : -1.0;
+    const double rinv2 = rsqrt(pj2), ipj2 = rinv2 * rinv2;
+    const double th2 = h1 * ipj2, ty2 = y1 * ipj2, yk2 = y1 * rinv2;
+#pragma unroll
+    for (int k = j + 2; k < N; ++k) h[k] = fma(-th2, cm1[k], fma(-th, cm0[k], h[k]));
+#pragma unroll
+    for (int k = j + 2; k < N; ++k) y[k] = fma(-ty2, cm1[k], fma(-ty, cm0[k], y[k]));
+    y[j] = fma(-ty2, 0.0, yk); y[j + 1] = yk2;
+    // the trips stay six separate steps: without a fence between them nothing else keeps the scheduler from spreading the unrolled trips over
+    // each other (the pin of qp_core's sweep, wbc_common.h)
+#pragma unroll
+    for (int k = j + 2; k < N; ++k) asm volatile("" : "+v"(h[k]), "+v"(y[k]));
+    chol_sweep2_bc_trip<N, J + 2>(h, y, pmin);
+  }
+}
+template <int N>
+__device__ __forceinline__ double chol_sweep2_bc(double (&h)[N], double (&y)[N]) {
+  static_assert(N % 2 == 0 && N <= 16, "two columns per trip; a row's lanes");
+  double pmin = 1.0;
+  chol_sweep2_bc_trip<N>(h, y, pmin);
   return pmin;
 }
 
