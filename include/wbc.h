@@ -546,7 +546,25 @@ int wbc_batch_set_option(WbcBatch* b, const char* name, int value);
  * elimination, with option "count_pivoted"), "wave_order_slices" (slices of waves whose recorded order the next packed sim3 launch at
  * the last such launch's batch size will read: ceil(ceil(B / 4) / 127) once the order is in effect, 0 without it; waits for `stream`),
  * "last_traj_bad_rows" (bad rows the last wbc_rollout_traj / wbc_rollout_tracks on the handle found; waits for `stream`),
- * "sim3_lds_bytes" / "tick_lds_bytes" / "orthp_lds_bytes" (LDS per workgroup of the tick kernels). */
+ * "sim3_lds_bytes" / "tick_lds_bytes" / "orthp_lds_bytes" (LDS per workgroup of the tick kernels).
+ *
+ * "last_tick_variant" / "last_qp_variant": WHICH instantiation of a kernel family the last launch resolved — the row of the family's variant
+ * table (csrc/wbc_k_<family>.hip, <FAMILY>_VARIANTS), as a five-byte key; -1 before the first such launch. "last_tick_variant" covers wbc_tick*,
+ * every tick of the roll-outs, wbc_assemble* and wbc_fk_jacobians; "last_qp_variant" covers wbc_qp_solve and wbc_qp_solve_ls. The key holds the
+ * row's template arguments in the table's order, first argument in the most significant byte, unused trailing bytes 0:
+ *     key = (((a0 * 256 + a1) * 256 + a2) * 256 + a3) * 256 + a4          a_i = (key >> 8 * (4 - i)) & 255
+ * The family comes from "last_path" (ticks) or "last_qp_path" (QPs: 1 -> qp, 2 / 4 -> qpp); wbc_assemble* and wbc_fk_jacobians always run on the
+ * general family. Arguments per family (flags are 0 / 1):
+ *     general (last_path 0)  MODE, WARM, ORTH, ROT, TP       MODE: 0 = MODE_TICK, 1 = MODE_ASSEMBLE, 2 = MODE_FK
+ *     sim3p   (last_path 2)  WARM, TRUNK, QCON, ROT, TP
+ *     orthp   (last_path 3)  INEQ, WARM, ROT, TP
+ *     boxp    (last_path 4)  WARM, ROT, TP
+ *     qpp     (last_qp_path 2, 4)  G, PV, WARM, HALF         G: lanes per problem (16 / 32), PV: the layout's row capacity (16 / 26)
+ *     qp      (last_qp_path 1)     NM, WARM                  NM: the solver core's size (12, 16, 24, 26)
+ *     compact sim3 (last_path 1; no table, four forms)  WARM, ROT
+ * WARM: working sets are read / written; ORTH: the orthonormal contact presolve; ROT: a model of the handle has a rotated joint placement;
+ * TP: per-instance task rows (wbc_tick_tp); TRUNK: the trunk task; QCON: posture_u / q_con given or computed by the posture kernel;
+ * INEQ: the packed orth kernel's form with inequality rows; HALF: rows of C split over the two halves of a problem. */
 int wbc_batch_get_stat(WbcBatch* b, const char* name, void* stream, int64_t* out);
 
 /* wait for everything queued by this handle on `stream`. */
@@ -560,6 +578,9 @@ int wbc_debug_cycles(WbcBatch* b, uint64_t* out24);
 const char* wbc_last_error(void);
 const char* wbc_version(void);
 int wbc_abi_sizes(int32_t* sizeof_blob, int32_t* sizeof_config); /* ctypes layout self-check */
+/* rows of a kernel family's variant table ("general", "sim3p", "orthp", "boxp", "qpp", "qp"), generated from the table itself: what a census of
+ * the statistics "last_tick_variant" / "last_qp_variant" has to reach. Needs no handle and no device. Unknown family: WBC_E_ARG. */
+int wbc_variant_count(const char* family);
 
 #ifdef __cplusplus
 }

@@ -82,6 +82,7 @@ struct WbcBatch {
   int packed_update, last_update_packed;   // option: wbc_update_packed_kernel where every plan allows it [1]; what the last update ran on
   int last_orth;         // the last general-kernel tick ran the variant with the orthonormal contact presolve
   int last_qp_path;      // problems per wavefront of the last wbc_qp_solve / wbc_qp_solve_ls: 1 (wbc_qp_kernel), 2 or 4 (wbc_qp_packed_kernel)
+  long long last_tick_variant, last_qp_variant;   // variant_key(...) of the row the last tick / assemble / fk launch and the last stand-alone QP launch resolved (-1: none yet)
   int last_path;         // TickPath of the last wbc_tick / wbc_rollout tick: 0 general, 1 sim3 (+ deferred pass), 2 packed sim3, 3 packed orth, 4 packed box
   int max_nj, max_nf;    // FK output strides: the largest model's joint / frame counts
   int rot;               // a model of the handle has a rotated joint placement: the packed kernels run their ROT instantiations
@@ -201,6 +202,7 @@ extern "C" int wbc_batch_create(const WbcModel* const* models, int n_models, int
   if (!b) return fail(WBC_E_ARG, "out of memory");
   memset(b, 0, sizeof *b);
   b->device_id = device_id; b->n_models = n_models; b->max_batch = max_batch; b->presolve = 1; b->presolve_orth = 1; b->packed_update = 1; b->sim3_kernel = 1; b->sing_tol = 1e-7; b->wave_order = 1;
+  b->last_tick_variant = b->last_qp_variant = -1;
   b->jtj_mfma = -1; b->refine = 1; b->packed_min_batch = WBC_SIM3P_MIN_BATCH; b->warm_start = 0; b->packed_kernel = 1; b->packed_orth = 1; b->packed_box = 1; b->posture_par = 1;
   std::vector<DevModel> dm(n_models);
   for (int i = 0; i < n_models; ++i) {
@@ -692,6 +694,8 @@ extern "C" int wbc_batch_get_stat(WbcBatch* b, const char* name, void* stream, i
   HIP_TRY(hipSetDevice(b->device_id));
   if (!strcmp(name, "last_path")) { *out = b->last_path; return WBC_OK; }
   if (!strcmp(name, "last_qp_path")) { *out = b->last_qp_path; return WBC_OK; }
+  if (!strcmp(name, "last_tick_variant")) { *out = b->last_tick_variant; return WBC_OK; }
+  if (!strcmp(name, "last_qp_variant")) { *out = b->last_qp_variant; return WBC_OK; }
   if (!strcmp(name, "last_update_packed")) { *out = b->last_update_packed; return WBC_OK; }
   if (!strcmp(name, "last_posture_par")) { *out = b->last_posture_par; return WBC_OK; }
   if (!strcmp(name, "last_orth")) { *out = (b->last_path == TICK_GENERAL || b->last_path == TICK_ORTHP) ? b->last_orth : 0; return WBC_OK; }
@@ -1025,13 +1029,13 @@ static int launch_tick_auto(WbcBatch* b, KernelArgs& a, int B, void* stream, con
   int rc = prepare_tick(b, a, stream, path);
   if (rc) return rc;
   switch (path) {   // (the packed kernels: ONE kernel per tick, what a packed kernel cannot reduce its own wave redoes on the general path)
-    case TICK_GENERAL: return launch_rc(launch_tick(a, MODE_TICK, grid_tick(b, B), stream, tp), "tick");
-    case TICK_SIM3P: return launch_rc(launch_tick_sim3p(a, stream, tp), "packed sim3 tick");
-    case TICK_ORTHP: return launch_rc(launch_tick_orthp(a, stream, b->plan_host[0].q_ok == 2, tp), "packed orth tick");
-    case TICK_BOXP: return launch_rc(launch_tick_boxp(a, stream, tp), "packed box tick");
+    case TICK_GENERAL: return launch_rc(launch_tick(a, MODE_TICK, grid_tick(b, B), stream, tp, &b->last_tick_variant), "tick");
+    case TICK_SIM3P: return launch_rc(launch_tick_sim3p(a, stream, tp, &b->last_tick_variant), "packed sim3 tick");
+    case TICK_ORTHP: return launch_rc(launch_tick_orthp(a, stream, b->plan_host[0].q_ok == 2, tp, &b->last_tick_variant), "packed orth tick");
+    case TICK_BOXP: return launch_rc(launch_tick_boxp(a, stream, tp, &b->last_tick_variant), "packed box tick");
     case TICK_SIM3: break;   // two kernels, below: the compact one, then the general path over the instances it deferred (singular leg block)
   }
-  if ((rc = launch_rc(launch_tick_sim3(a, B, stream), "sim3 tick"))) return rc;
+  if ((rc = launch_rc(launch_tick_sim3(a, B, stream, &b->last_tick_variant), "sim3 tick"))) return rc;
   if ((rc = launch_rc(launch_tick_deferred(a, stream), "deferred tick")))
     (void)hipMemsetAsync(b->d_defer, 0, sizeof(int32_t), (hipStream_t)stream);   // the list the sim3 kernel may have filled stays behind: empty it, or the next tick appends after a stale count
   return rc;
@@ -1060,7 +1064,7 @@ extern "C" int wbc_fk_jacobians(WbcBatch* b, int B, const double* q, const int32
   st.out(&a.fk.oMi, (size_t)B * nj * 12); st.out(&a.fk.oMf, (size_t)B * nf * 12);
   st.out(&a.fk.J, (size_t)B * 6 * WBC_V_STRIDE); st.out(&a.fk.com, (size_t)B * 3); st.out(&a.fk.Jcom, (size_t)B * 3 * WBC_V_STRIDE);
   if ((rc = st.stage())) return rc;
-  if ((rc = launch_rc(launch_tick(a, MODE_FK, grid_tick(b, B), stream), "fk"))) return rc;
+  if ((rc = launch_rc(launch_tick(a, MODE_FK, grid_tick(b, B), stream, nullptr, &b->last_tick_variant), "fk"))) return rc;
   return st.finish();
 }
 
@@ -1085,7 +1089,7 @@ extern "C" int wbc_assemble_tp(WbcBatch* b, int B, const WbcTickIn* in, const Wb
   st.out(&a.qp.C, n * p * V); st.out(&a.qp.Clb, n * p); st.out(&a.qp.Cub, n * p); st.out(&a.qp.lb, n * V); st.out(&a.qp.ub, n * V);
   if ((rc = st.stage())) return rc;
   if ((rc = auto_posture(b, a, B, stream))) return rc;
-  if ((rc = launch_rc(launch_tick(a, MODE_ASSEMBLE, grid_tick(b, B), stream, tp), "assemble"))) return rc;
+  if ((rc = launch_rc(launch_tick(a, MODE_ASSEMBLE, grid_tick(b, B), stream, tp, &b->last_tick_variant), "assemble"))) return rc;
   return st.finish();
 }
 
@@ -1418,7 +1422,7 @@ static int qp_common(WbcBatch* b, int B, QpArgs& a, int mem, void* stream, const
   // several problems per wavefront (wbc_k_qpp.hip) unless the call carries working sets (hot start) or option packed_kernel is 0
   const int lanes = b->packed_kernel ? qp_packed_lanes(a) : 0;
   b->last_qp_path = lanes ? lanes : 1;
-  if ((rc = launch_rc(lanes ? launch_qp_packed(a, stream) : launch_qp(a, grid_for(b, B), stream), "qp"))) return rc;
+  if ((rc = launch_rc(lanes ? launch_qp_packed(a, stream, &b->last_qp_variant) : launch_qp(a, grid_for(b, B), stream, &b->last_qp_variant), "qp"))) return rc;
   return st.finish();
 }
 
@@ -1486,6 +1490,16 @@ extern "C" const char* wbc_version(void) { return "wbc-hip 0.1 (gfx950, PROFILE 
 #else
 extern "C" const char* wbc_version(void) { return "wbc-hip 0.1 (gfx950)"; }
 #endif
+extern "C" int wbc_variant_count(const char* family) {
+  if (!family) return fail(WBC_E_ARG, "wbc_variant_count: null family");
+  if (!strcmp(family, "general")) return general_variant_count();
+  if (!strcmp(family, "sim3p")) return sim3p_variant_count();
+  if (!strcmp(family, "orthp")) return orthp_variant_count();
+  if (!strcmp(family, "boxp")) return boxp_variant_count();
+  if (!strcmp(family, "qpp")) return qpp_variant_count();
+  if (!strcmp(family, "qp")) return qp_variant_count();
+  return fail(WBC_E_ARG, "wbc_variant_count: unknown kernel family %s", family);
+}
 extern "C" int wbc_abi_sizes(int32_t* sb, int32_t* sc) {
   if (sb) *sb = (int32_t)sizeof(WbcModelBlob);
   if (sc) *sc = (int32_t)sizeof(WbcConfig);

@@ -2603,6 +2603,8 @@ static int check_launch(const char* what) {
 //   WBC_VARIANT_UNIT  explicit instantiation of the rows of part WBC_PART, `extern template` declaration of the others
 //   WBC_VARIANT_FIND  inside `kernel_pointer find(long long key)`: returns the row whose arguments are variant_key(...)'s; the launcher reduces
 //                     its call to the arguments it wants and launches what it finds — no row, no launch (WBC_E_UNSUPPORTED)
+//   WBC_VARIANT_COUNT inside `return 0 FAMILY_VARIANTS(WBC_VARIANT_COUNT);`: the table's row count (wbc_variant_count — the tests' census)
+// A launcher reports the key it launched through its last parameter (`key_out`, may be null): the statistics "last_tick_variant" / "last_qp_variant".
 // ------------------------------------------------------------------------------------------------
 #ifndef WBC_NPARTS
 #define WBC_NPARTS 9      // (the most WBC_PART_IS_ below can tell apart)
@@ -2628,6 +2630,7 @@ static int check_launch(const char* what) {
 #define WBC_VARIANT_UNIT_0 WBC_VARIANT_DECL
 #define WBC_VARIANT_UNIT(p, ...) WBC_CAT(WBC_VARIANT_UNIT_, WBC_PART_IS(p, WBC_PART))(p, __VA_ARGS__)
 #define WBC_VARIANT_FIND(p, ...) if (key == variant_key(__VA_ARGS__)) return WBC_KERNEL<__VA_ARGS__>;
+#define WBC_VARIANT_COUNT(p, ...) + 1
 constexpr long long variant_key(int a, int b = 0, int c = 0, int d = 0, int e = 0) {   // (template arguments: flags, modes, sizes — all below 256)
   return ((((long long)a * 256 + b) * 256 + c) * 256 + d) * 256 + e;
 }

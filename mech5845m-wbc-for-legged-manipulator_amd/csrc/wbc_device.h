@@ -236,23 +236,31 @@ struct UpdateArgs {
 };
 
 // launchers (one per kernel family, wbc_k_*.hip): single-wave workgroups; tick kernels take grid = B, the QP / integrate kernels min(B, resident waves)
-int launch_tick(const KernelArgs& a, int mode, int grid, void* stream, const WbcTaskParams* tp = nullptr);
-int launch_tick_sim3(const KernelArgs& a, int grid, void* stream);
-int launch_tick_sim3p(const KernelArgs& a, void* stream, const WbcTaskParams* tp = nullptr);      // packed: four instances per wavefront, grid = ceil(B / 4)
-int launch_tick_boxp(const KernelArgs& a, void* stream, const WbcTaskParams* tp = nullptr);       // packed box kernel (task problems without constraint rows), grid = ceil(B / 4)
-int launch_tick_orthp(const KernelArgs& a, void* stream, int ineq, const WbcTaskParams* tp = nullptr);      // packed orth kernel (equality-only task problems), grid = ceil(B / 4)
+// key_out (may be null): the variant_key(...) of the row the launcher resolved, written before the launch (wbc_common.h, "Kernel variant tables")
+int launch_tick(const KernelArgs& a, int mode, int grid, void* stream, const WbcTaskParams* tp = nullptr, long long* key_out = nullptr);
+int launch_tick_sim3(const KernelArgs& a, int grid, void* stream, long long* key_out = nullptr);   // (no table: key_out = variant_key(WARM, ROT))
+int launch_tick_sim3p(const KernelArgs& a, void* stream, const WbcTaskParams* tp = nullptr, long long* key_out = nullptr);      // packed: four instances per wavefront, grid = ceil(B / 4)
+int launch_tick_boxp(const KernelArgs& a, void* stream, const WbcTaskParams* tp = nullptr, long long* key_out = nullptr);       // packed box kernel (task problems without constraint rows), grid = ceil(B / 4)
+int launch_tick_orthp(const KernelArgs& a, void* stream, int ineq, const WbcTaskParams* tp = nullptr, long long* key_out = nullptr);      // packed orth kernel (equality-only task problems), grid = ceil(B / 4)
 int orthp_lds_bytes();
 int sim3p_lds_bytes();
 int launch_tick_deferred(const KernelArgs& a, void* stream);   // general path for the instances the sim3 kernel deferred
 int sim3_lds_bytes();
-int launch_qp(const QpArgs& a, int grid, void* stream);
+int launch_qp(const QpArgs& a, int grid, void* stream, long long* key_out = nullptr);
 int qp_packed_lanes(const QpArgs& a);           // wbc_k_qpp.hip: problems per wavefront the packed QP kernel takes this shape with (4 / 2), 0: not taken
-int launch_qp_packed(const QpArgs& a, void* stream);
+int launch_qp_packed(const QpArgs& a, void* stream, long long* key_out = nullptr);
 int launch_integrate(const IntegrateArgs& a, int grid, void* stream);
 int launch_posture(const PostureArgs& a, int grid, void* stream);
 int launch_posture_par(const PostureArgs& a, int grid, void* stream, int three);   // every finite-difference point on its own lane (DevPlan.mp_ok)
 int launch_update(const UpdateArgs& a, int grid, void* stream);
 int launch_update_packed(const UpdateArgs& a, void* stream);   // four instances per wavefront (every plan pk_update_ok)
 int tick_lds_bytes();
+// rows of each family's variant table, generated from the table (WBC_VARIANT_COUNT)
+int general_variant_count();
+int sim3p_variant_count();
+int orthp_variant_count();
+int boxp_variant_count();
+int qpp_variant_count();
+int qp_variant_count();
 
 }  // namespace wbc

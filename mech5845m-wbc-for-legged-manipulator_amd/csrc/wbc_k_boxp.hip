@@ -768,8 +768,11 @@ static TickKernel boxp_variant(long long key) {
   BOXP_VARIANTS(WBC_VARIANT_FIND)
   return nullptr;
 }
-int launch_tick_boxp(const KernelArgs& a, void* stream, const WbcTaskParams* tp) {
-  const TickKernel k = boxp_variant(variant_key(a.ws_in || a.ws_out, a.rot != 0, tp != nullptr));
+int boxp_variant_count() { return 0 BOXP_VARIANTS(WBC_VARIANT_COUNT); }
+int launch_tick_boxp(const KernelArgs& a, void* stream, const WbcTaskParams* tp, long long* key_out) {
+  const long long key = variant_key(a.ws_in || a.ws_out, a.rot != 0, tp != nullptr);
+  if (key_out) *key_out = key;
+  const TickKernel k = boxp_variant(key);
   if (!k) return WBC_E_UNSUPPORTED;
   hipLaunchKernelGGL(k, dim3((a.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
   return check_launch("tick_boxp");

@@ -87,11 +87,14 @@ static TickKernel general_variant(long long key) {
   GENERAL_VARIANTS(WBC_VARIANT_FIND)
   return nullptr;
 }
-int launch_tick(const KernelArgs& a, int mode, int grid, void* stream, const WbcTaskParams* tp) {
+int general_variant_count() { return 0 GENERAL_VARIANTS(WBC_VARIANT_COUNT); }
+int launch_tick(const KernelArgs& a, int mode, int grid, void* stream, const WbcTaskParams* tp, long long* key_out) {
   if (mode == MODE_FK) tp = nullptr;   // (FK reads no weight: no kernel with rows)
   const bool warm = mode == MODE_TICK && (a.ws_in || a.ws_out);                          // working sets and the orthonormal presolve: ticks only,
   const bool orth = mode == MODE_TICK && !warm && a.presolve && a.presolve_orth == 2;   // and a working set wins over presolve_orth == 2
-  const TickKernel k = general_variant(variant_key(mode, warm, orth, a.rot != 0, tp != nullptr));
+  const long long key = variant_key(mode, warm, orth, a.rot != 0, tp != nullptr);
+  if (key_out) *key_out = key;
+  const TickKernel k = general_variant(key);
   if (!k) return WBC_E_UNSUPPORTED;
   hipLaunchKernelGGL(k, dim3(grid), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
   return check_launch("tick");

@@ -164,11 +164,14 @@ static QpKernel qp_variant(long long key) {
   QP_VARIANTS(WBC_VARIANT_FIND)
   return nullptr;
 }
-int launch_qp(const QpArgs& a, int grid, void* stream) {
+int qp_variant_count() { return 0 QP_VARIANTS(WBC_VARIANT_COUNT); }
+int launch_qp(const QpArgs& a, int grid, void* stream, long long* key_out) {
   const bool warm = a.ws_in || a.ws_out;
   // the smallest core that holds the problem; hot start: the core sizes the tick problems come in (a reduced problem fits 16, the full one needs 26)
   const int nm = warm ? (a.n <= 16 ? 16 : NV) : a.n <= 12 ? 12 : a.n <= 16 ? 16 : a.n <= 24 ? 24 : NV;
-  const QpKernel k = qp_variant(variant_key(nm, warm));
+  const long long key = variant_key(nm, warm);
+  if (key_out) *key_out = key;
+  const QpKernel k = qp_variant(key);
   if (!k) return WBC_E_UNSUPPORTED;
   hipLaunchKernelGGL(k, dim3(grid), dim3(64), 0, (hipStream_t)stream, a);
   return check_launch("qp");

@@ -1036,9 +1036,12 @@ static TickKernel orthp_variant(long long key) {
   ORTHP_VARIANTS(WBC_VARIANT_FIND)
   return nullptr;
 }
-int launch_tick_orthp(const KernelArgs& a, void* stream, int ineq, const WbcTaskParams* tp) {
+int orthp_variant_count() { return 0 ORTHP_VARIANTS(WBC_VARIANT_COUNT); }
+int launch_tick_orthp(const KernelArgs& a, void* stream, int ineq, const WbcTaskParams* tp, long long* key_out) {
   const bool warm = ineq && (a.ws_in || a.ws_out);
-  const TickKernel k = orthp_variant(variant_key(ineq != 0, warm, a.rot != 0, tp != nullptr));
+  const long long key = variant_key(ineq != 0, warm, a.rot != 0, tp != nullptr);
+  if (key_out) *key_out = key;
+  const TickKernel k = orthp_variant(key);
   if (!k) return WBC_E_UNSUPPORTED;
   hipLaunchKernelGGL(k, dim3((a.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp);
   return check_launch("tick_orthp");

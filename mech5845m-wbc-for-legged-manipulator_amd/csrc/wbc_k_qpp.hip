@@ -847,10 +847,13 @@ int qp_packed_lanes(const QpArgs& a) {
   if (a.n <= 16 && a.p <= 16) return 4;
   return 2;
 }
-int launch_qp_packed(const QpArgs& a, void* stream) {
+int qpp_variant_count() { return 0 QPP_VARIANTS(WBC_VARIANT_COUNT); }
+int launch_qp_packed(const QpArgs& a, void* stream, long long* key_out) {
   const int nq = qp_packed_lanes(a), g = 64 / nq, pv = nq == 4 ? 16 : NV;   // QppLayout<G, PV>: NQ = 64 / G problems per wavefront
   const bool half = g == 32 && a.p <= 16;                                    // rows of C split over the two halves of a problem
-  const QppKernel k = qpp_variant(variant_key(g, pv, a.ws_in || a.ws_out, half));
+  const long long key = variant_key(g, pv, a.ws_in || a.ws_out, half);
+  if (key_out) *key_out = key;
+  const QppKernel k = qpp_variant(key);
   if (!k) return WBC_E_UNSUPPORTED;
   hipLaunchKernelGGL(k, dim3((a.B + nq - 1) / nq), dim3(64), 0, (hipStream_t)stream, a);
   return check_launch("qp packed");

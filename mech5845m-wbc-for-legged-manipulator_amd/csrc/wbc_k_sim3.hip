@@ -707,7 +707,8 @@ V(0, false)
 V(1, true)
 #undef V
 #if SIM3_PART <= 0
-int launch_tick_sim3(const KernelArgs& a, int grid, void* stream) {
+int launch_tick_sim3(const KernelArgs& a, int grid, void* stream, long long* key_out) {
+  if (key_out) *key_out = variant_key(a.ws_in || a.ws_out, a.rot != 0);
   if (a.rot && (a.ws_in || a.ws_out)) hipLaunchKernelGGL((wbc_tick_sim3_kernel<true, true>), dim3(grid), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
   else if (a.rot) hipLaunchKernelGGL((wbc_tick_sim3_kernel<false, true>), dim3(grid), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
   else if (a.ws_in || a.ws_out) hipLaunchKernelGGL(wbc_tick_sim3_kernel<true>, dim3(grid), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);

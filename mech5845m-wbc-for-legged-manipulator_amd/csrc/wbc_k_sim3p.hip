@@ -1293,10 +1293,13 @@ static Sim3pKernel sim3p_variant(long long key) {
   SIM3P_VARIANTS(WBC_VARIANT_FIND)
   return nullptr;
 }
-int launch_tick_sim3p(const KernelArgs& a, void* stream, const WbcTaskParams* tp) {
+int sim3p_variant_count() { return 0 SIM3P_VARIANTS(WBC_VARIANT_COUNT); }
+int launch_tick_sim3p(const KernelArgs& a, void* stream, const WbcTaskParams* tp, long long* key_out) {
   const bool warm = a.ws_in || a.ws_out, qcon = a.in.q_con || a.in.posture_u;
   const bool trunk = !qcon && a.in.trunk_target && a.packed_trunk;   // (QCON switches TRUNK off)
-  const Sim3pKernel k = sim3p_variant(variant_key(warm, trunk, qcon, a.rot != 0, tp != nullptr));
+  const long long key = variant_key(warm, trunk, qcon, a.rot != 0, tp != nullptr);
+  if (key_out) *key_out = key;
+  const Sim3pKernel k = sim3p_variant(key);
   if (!k) return WBC_E_UNSUPPORTED;
   const uint32_t waves = (uint32_t)((a.B + 3) / 4);
   hipLaunchKernelGGL(k, dim3(waves), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp, wo_geom(waves));

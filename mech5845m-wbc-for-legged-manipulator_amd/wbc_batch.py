@@ -84,8 +84,15 @@ def _task_params(tp, B, keep, device_id):
 
 
 class WbcBatch:
-    def __init__(self, models, max_batch, device_id=0):
+    allocator = None     # the output allocator hook (constructor argument / attribute); None: torch.empty / np.empty where the inputs live
+
+    def __init__(self, models, max_batch, device_id=0, allocator=None):
+        """allocator: a callable (like, shape, numpy dtype) -> array that replaces the default allocation of every output a wrapper
+        allocates itself (everything but tick(out=...)); also settable later as the attribute `allocator` (None: the default). The
+        array must be contiguous, of that shape and dtype, and live where `like` does."""
         self.lib = capi.load_library()
+        if allocator is not None:
+            self.allocator = allocator
         self.models = list(models) if isinstance(models, (list, tuple)) else [models]
         self.max_batch = int(max_batch)
         self._mh = []
@@ -162,7 +169,8 @@ class WbcBatch:
 
     def stat(self, name, stream=None):
         """wbc_batch_get_stat: "last_path" (0 general, 1 compact sim3, 2 packed sim3, 3 packed orth — equality-only or INEQ variant —, 4 packed box), "last_orth", "last_posture_par",
-        "last_update_packed", "last_qp_path" (problems per wavefront of the last stand-alone QP call: 1, 2 or 4), "deferred_last", "pivoted_last", "wave_order_slices", "sim3_lds_bytes", "tick_lds_bytes", "orthp_lds_bytes"."""
+        "last_update_packed", "last_qp_path" (problems per wavefront of the last stand-alone QP call: 1, 2 or 4), "last_tick_variant" /
+        "last_qp_variant" (the variant-table row of the last tick / assemble / fk and stand-alone QP launch: wbc_capi.variant_args), "deferred_last", "pivoted_last", "wave_order_slices", "sim3_lds_bytes", "tick_lds_bytes", "orthp_lds_bytes"."""
         v = C.c_int64()
         capi.check(self.lib.wbc_batch_get_stat(self._h, name.encode(), stream, C.byref(v)), self.lib)
         return int(v.value)
@@ -187,6 +195,8 @@ class WbcBatch:
         return struct
 
     def _alloc(self, like, shape, dtype=np.float64):
+        if self.allocator is not None:
+            return self.allocator(like, shape, dtype)
         if like is not None and _is_torch(like):
             import torch
             return torch.empty(shape, dtype={np.float64: torch.float64, np.int32: torch.int32, np.int64: torch.int64}[dtype], device=like.device)

@@ -167,13 +167,17 @@ SIGNATURES = {
     "wbc_last_error": (C.c_char_p, []),
     "wbc_version": (C.c_char_p, []),
     "wbc_abi_sizes": (_i, [c_int32_p, c_int32_p]),
+    "wbc_variant_count": (_i, [C.c_char_p]),
 }
 
 _lib = None
 
 
+E_ARG, E_HIP, E_UNSUPPORTED, E_STATE = -1, -2, -3, -4      # include/wbc.h
+
+
 class WbcError(RuntimeError):
-    pass
+    code = None      # the library's return code where the error comes from a library call (check), else None
 
 
 def load_library(path=None):
@@ -206,7 +210,26 @@ def load_library(path=None):
     return lib
 
 
+VARIANT_FAMILIES = ("general", "sim3p", "orthp", "boxp", "qpp", "qp")
+
+
+def variant_count(family):
+    """rows of a kernel family's variant table (wbc_variant_count, include/wbc.h); needs no device. Unknown family: WbcError."""
+    lib = load_library()
+    n = lib.wbc_variant_count(family.encode())
+    if n < 0:
+        check(n, lib)
+    return n
+
+
+def variant_args(key, nargs=5):
+    """the template arguments behind a "last_tick_variant" / "last_qp_variant" key (include/wbc.h): first argument in the top byte"""
+    return tuple((int(key) >> (8 * (4 - i))) & 255 for i in range(nargs))
+
+
 def check(rc, lib=None):
     if rc != 0:
         lib = lib or load_library()
-        raise WbcError("wbc call failed (%d): %s" % (rc, (lib.wbc_last_error() or b"").decode()))
+        e = WbcError("wbc call failed (%d): %s" % (rc, (lib.wbc_last_error() or b"").decode()))
+        e.code = rc
+        raise e

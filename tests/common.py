@@ -1,4 +1,6 @@
 """Shared helpers for the tests: models, configurations of BASELINE.json, oracle-backed FK for input generation."""
+import ctypes
+
 import numpy as np
 
 import oracle
@@ -182,3 +184,120 @@ def exact_optimum(H, g, C, lb, ub, Clb, Cub, x_float):
     for k, l in zip(kind, lam):              # H x + g + N'lam = 0: at a lower bound lam <= 0, at an upper bound lam >= 0
         assert not (k == -1 and l > 1e-9 * (1 + abs(l))) and not (k == +1 and l < -1e-9 * (1 + abs(l)))
     return x
+
+
+# ---- tracks (wbc_rollout_tracks): the recipe, the oracle's loop and the scores, shared by test_gpu_rollout_tracks.py and test_gpu_device_inplace.py
+DT_TRACKS = 0.002
+GRIP, TRUNK = 4, capi.TARGET_TRUNK
+
+
+def track_frames(models, q, mid):
+    """positions [B, 6, 3] of the five EE frames and the trunk frame"""
+    oMf = oracle.fk(models, q, mid, want_com=False)["oMf"]
+    return np.concatenate([oMf[:, capi.FR_EE0:capi.FR_EE0 + 5, 9:], oMf[:, capi.FR_TRUNK:capi.FR_TRUNK + 1, 9:]], axis=1)
+
+
+def base_tracks(d, grip_pos, seed):
+    """the base recipe: a trunk track (HERMITE, 2..5 milestones) and a gripper track (LINEAR, 2..4), drawn in this order"""
+    rng = np.random.default_rng(seed)
+    B = len(grip_pos)
+    tp = d["trunk_target"][:, None, :] + rng.normal(0, 0.01, (B, 5, 3))
+    tp[:, 0] = d["trunk_target"]
+    tn = rng.choice([2, 3, 4, 5], B).astype(np.int32)
+    tdu = rng.choice([1 / 8, 1 / 5, 0.3], B)
+    gp = grip_pos[:, None, :] + rng.normal(0, 0.01, (B, 4, 3))
+    gp[:, 0] = grip_pos
+    gn = rng.choice([2, 3, 4], B).astype(np.int32)
+    gdu = rng.choice([1 / 8, 1 / 5, 0.3], B)
+    return [dict(target="trunk", points=tp, kind="hermite", n_points=tn, du=tdu), dict(target=GRIP, points=gp, kind="linear", n_points=gn, du=gdu)]
+
+
+def track_index(t):
+    return TRUNK if t == "trunk" else int(t)
+
+
+def track_at(track, k):
+    return wbc_workload.track_targets(track["points"], track.get("n_points"), track.get("du", 0.002), k, track.get("kind", "linear"), track.get("tangents"))
+
+
+def start_previous_targets(d, tracks):
+    """prev_* of the followed targets = the first milestones (the followed rows of ee_target / trunk_target keep what the generator put there:
+    the call must not read them)"""
+    for t in tracks:
+        if track_index(t["target"]) == TRUNK:
+            d["prev_trunk_target"] = t["points"][:, 0].copy()
+        else:
+            d["prev_ee_target"][:, track_index(t["target"])] = t["points"][:, 0]
+
+
+def per_instance_configs(models, cfgs, mid, rows):
+    """the oracle's form of per-instance task rows: B (model, configuration) pairs, model_id = arange(B)"""
+    off = capi.WbcConfig.ee_W.offset
+    ms, cs = [], []
+    for b in range(len(rows)):
+        i = 0 if mid is None else int(mid[b])
+        c = capi.WbcConfig.from_buffer_copy(cfgs[i])
+        ctypes.memmove(ctypes.addressof(c) + off, rows[b].ctypes.data, 85 * 8)
+        ms.append(models[i])
+        cs.append(c)
+    return ms, cs, np.arange(len(rows), dtype=np.int32)
+
+
+def tracks_reference(p):
+    """oracle.rollout's loop with a target hook per track: -> dict(q, qdot, status (max), iters (sum), ee_target, trunk_target (the targets the
+    next tick would get), tick_status [K, B], frames [K, B, 6, 3] reached, targets [K, B, 6, 3] of the tick). The arrays are read-only."""
+    from scipy.spatial.transform import Rotation as R
+    models, cfgs, mid, B, K = p["models"], p["cfgs"], p["mid"], p["B"], p["K"]
+    ms, cs, d = models, cfgs, {k: np.array(v, copy=True) for k, v in p["d"].items()}
+    if p["rows"] is not None:
+        ms, cs, pid = per_instance_configs(models, cfgs, mid, p["rows"])
+        d["model_id"] = pid
+    assert "ee_ref_rot" not in d                                    # (no EE orientation reference state to carry in this restatement)
+
+    def set_targets(k):
+        for t in p["tracks"]:
+            if track_index(t["target"]) == TRUNK:
+                d["trunk_target"] = track_at(t, k)
+            else:
+                d["ee_target"][:, track_index(t["target"])] = track_at(t, k)
+    status, iters = np.zeros(B, np.int32), np.zeros(B, np.int32)
+    tick_status = np.zeros((K, B), np.int32)
+    frames, targets = np.zeros((K, B, 6, 3)), np.zeros((K, B, 6, 3))
+    out = None
+    for k in range(K):
+        set_targets(k)
+        targets[k, :, :5], targets[k, :, 5] = d["ee_target"], d["trunk_target"]
+        out = oracle.tick(ms, cs, d, DT_TRACKS, B, nthreads=8, want_q_next=True)
+        tick_status[k] = out["status"]
+        status = np.maximum(status, out["status"])
+        iters += out["iters"]
+        d["q"] = oracle.update_state(models, d["q"], out["q_next"], d["ee_target"], p["imu"], mid) if p["running"] else out["q_next"]
+        frames[k] = track_frames(models, d["q"], mid)
+        for i, c in enumerate(cfgs):                                # the reference-state side effects of qpb()
+            sel = slice(None) if mid is None else (mid == i)
+            for e in range(capi.NEE):
+                if c.task_ee[e]:
+                    d["prev_ee_target"][sel, e] = d["ee_target"][sel, e]
+            if c.task_trunk:
+                d["prev_trunk_target"][sel] = d["trunk_target"][sel]
+                d["trunk_prev_rot"][sel] = R.from_euler("xyz", d["trunk_ref_euler"][sel]).as_matrix().reshape(-1, 9)
+    set_targets(K)
+    ref = dict(q=d["q"], qdot=out["qdot"], status=status, iters=iters, ee_target=d["ee_target"], trunk_target=d["trunk_target"],
+               tick_status=tick_status, frames=frames, targets=targets)
+    for v in ref.values():
+        v.setflags(write=False)
+    return ref
+
+
+def numpy_scores(trace, targets, status):
+    """the scores of [K, F, B, 3] positions against [K, F, B, 3] targets and [K, B] statuses, summed in tick order"""
+    K, B = status.shape
+    d = trace - targets
+    e2 = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+    err = np.sqrt(e2)
+    ssum = np.zeros(e2.shape[1:])
+    for k in range(K):
+        ssum = ssum + e2[k]
+    bad = status != 0
+    return dict(err_sq_sum=ssum, err_max=err.max(axis=0), err_max_tick=err.argmax(axis=0).astype(np.int32), err_final=err[-1],
+                first_bad_tick=np.where(bad.any(axis=0), bad.argmax(axis=0), -1).astype(np.int32), bad_ticks=bad.sum(axis=0).astype(np.int32))

@@ -147,3 +147,25 @@ def test_every_option_and_statistic_is_documented_in_the_header():
         missing = [n for n in names if '"%s"' % n not in hdr]
         assert not missing, (fn, missing)
     assert '"refine"' in hdr and "numRefinementSteps" in hdr and '"packed_min_batch"' in hdr
+
+
+def test_device_case_table_covers_every_row_of_the_variant_tables():
+    """The case table of tests/test_gpu_device_inplace.py holds exactly as many distinct rows per kernel family as the family's variant table
+    (wbc_variant_count: generated from the table, needs no device) — a variant added to a table without its case fails here, without a GPU;
+    on the GPU the census of that module shows that each case reaches the row it names. An unknown family is refused."""
+    import test_gpu_device_inplace as dev
+    lib = capi.load_library()
+    assert {fam for fam, _, _ in dev.CASES} == set(capi.VARIANT_FAMILIES)
+    for fam in capi.VARIANT_FAMILIES:
+        n = lib.wbc_variant_count(fam.encode())
+        assert n == capi.variant_count(fam) and n > 0
+        rows = dev.case_rows(fam)
+        assert len(rows) == n, (fam, len(rows), n)
+        assert len([c for c in dev.CASES if c[0] == fam]) == n, fam                      # ... and no row twice
+        assert all(len(r) == len(dev.FLAG_NAMES[fam]) and all(0 <= a < 256 for a in r) for r in rows), fam
+        assert len({dev.key_of(r) for r in rows}) == n
+    assert all(capi.variant_args(dev.key_of(flags), len(flags)) == flags for _, flags, _ in dev.CASES)
+    assert lib.wbc_variant_count(b"sim3") < 0 and b"unknown kernel family" in lib.wbc_last_error()
+    assert lib.wbc_variant_count(None) < 0
+    with pytest.raises(capi.WbcError, match="unknown kernel family"):
+        capi.variant_count("nope")

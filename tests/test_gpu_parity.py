@@ -1373,8 +1373,9 @@ def test_gpu_solution_against_the_exact_optimum(wx200, px100, cfg_name, with_rot
 
 @pytest.mark.parametrize("B", [1, 63, 64, 65, 1000])
 def test_ragged_batch_sizes(wx200, B):
-    """Batch sizes around the 64-status granularity of the deferred pass and a handle larger than the batch: every
-    instance is solved, nothing beyond B is touched."""
+    """Batch sizes around the 64-status granularity of the deferred pass and a handle larger than the batch, on the HOST path: every
+    instance is solved and the copy-back is exactly B rows long (the numpy views' guard rows never reach the device; that the kernels
+    themselves touch nothing beyond B is test_gpu_device_inplace.py's, on caller device memory)."""
     cfg = common.config("c3", wx200)
     d = common.tick_inputs(wx200, cfg, B, seed=90 + B)
     ref = oracle.tick([wx200], [cfg], d, DT, B, nthreads=8)

@@ -34,10 +34,9 @@ def _model(name):
     return wbc_model.load_model(name)
 
 
-def _frames(models, q, mid):
-    """positions [B, 6, 3] of the five EE frames and the trunk frame"""
-    oMf = oracle.fk(models, q, mid, want_com=False)["oMf"]
-    return np.concatenate([oMf[:, capi.FR_EE0:capi.FR_EE0 + 5, 9:], oMf[:, capi.FR_TRUNK:capi.FR_TRUNK + 1, 9:]], axis=1)
+# the track recipe, the oracle loop and the scores' numpy restatement live in tests/common.py (test_gpu_device_inplace.py runs them too)
+_frames, _base_tracks, _index, _at = common.track_frames, common.base_tracks, common.track_index, common.track_at
+_start_previous_targets, _per_instance, _numpy_scores = common.start_previous_targets, common.per_instance_configs, common.numpy_scores
 
 
 def _inputs(names, cfg_name, B, seed, stress):
@@ -55,21 +54,6 @@ def _inputs(names, cfg_name, B, seed, stress):
     return models, cfgs, d, mid
 
 
-def _base_tracks(d, grip_pos, seed):
-    """the base recipe: a trunk track (HERMITE, 2..5 milestones) and a gripper track (LINEAR, 2..4), drawn in this order"""
-    rng = np.random.default_rng(seed)
-    B = len(grip_pos)
-    tp = d["trunk_target"][:, None, :] + rng.normal(0, 0.01, (B, 5, 3))
-    tp[:, 0] = d["trunk_target"]
-    tn = rng.choice([2, 3, 4, 5], B).astype(np.int32)
-    tdu = rng.choice([1 / 8, 1 / 5, 0.3], B)
-    gp = grip_pos[:, None, :] + rng.normal(0, 0.01, (B, 4, 3))
-    gp[:, 0] = grip_pos
-    gn = rng.choice([2, 3, 4], B).astype(np.int32)
-    gdu = rng.choice([1 / 8, 1 / 5, 0.3], B)
-    return [dict(target="trunk", points=tp, kind="hermite", n_points=tn, du=tdu), dict(target=GRIP, points=gp, kind="linear", n_points=gn, du=gdu)]
-
-
 def _six_linear_tracks(d, pos, seed):
     """all six targets on LINEAR tracks from where the frames are"""
     rng = np.random.default_rng(seed)
@@ -84,24 +68,6 @@ def _six_linear_tracks(d, pos, seed):
     return tracks
 
 
-def _index(t):
-    return TRUNK if t == "trunk" else int(t)
-
-
-def _at(track, k):
-    return track_targets(track["points"], track.get("n_points"), track.get("du", 0.002), k, track.get("kind", "linear"), track.get("tangents"))
-
-
-def _start_previous_targets(d, tracks):
-    """prev_* of the followed targets = the first milestones (the followed rows of ee_target / trunk_target keep what the generator put there:
-    the call must not read them)"""
-    for t in tracks:
-        if _index(t["target"]) == TRUNK:
-            d["prev_trunk_target"] = t["points"][:, 0].copy()
-        else:
-            d["prev_ee_target"][:, _index(t["target"])] = t["points"][:, 0]
-
-
 def _task_rows(cfg, B, seed):
     """gains and weights within a factor of two of the preset's (as test_rollout_with_rows_matches_the_oracle)"""
     rng = np.random.default_rng(seed)
@@ -110,19 +76,6 @@ def _task_rows(cfg, B, seed):
     for f in ("ee_W", "ee_w", "ee_gain", "trunk_W", "trunk_w", "trunk_gain", "joint_w"):
         rows[:, sl[f]] *= np.exp(rng.uniform(np.log(0.5), np.log(2.0), (B, sl[f].stop - sl[f].start)))
     return rows
-
-
-def _per_instance(models, cfgs, mid, rows):
-    """the oracle's form of per-instance task rows: B (model, configuration) pairs, model_id = arange(B)"""
-    off = capi.WbcConfig.ee_W.offset
-    ms, cs = [], []
-    for b in range(len(rows)):
-        i = 0 if mid is None else int(mid[b])
-        c = capi.WbcConfig.from_buffer_copy(cfgs[i])
-        C.memmove(C.addressof(c) + off, rows[b].ctypes.data, 85 * 8)
-        ms.append(models[i])
-        cs.append(c)
-    return ms, cs, np.arange(len(rows), dtype=np.int32)
 
 
 # problem -> (models, configuration, B, ticks, input seed, track seed, stress recipe, running, tracks)
@@ -157,50 +110,8 @@ def _problem(name):
 
 @functools.lru_cache(maxsize=None)
 def _reference(name):
-    """oracle.rollout's loop with a target hook per track: -> dict(q, qdot, status (max), iters (sum), ee_target, trunk_target (the targets the
-    next tick would get), tick_status [K, B], frames [K, B, 6, 3] reached, targets [K, B, 6, 3] of the tick). Computed once, never modified."""
-    from scipy.spatial.transform import Rotation as R
-    p = _problem(name)
-    models, cfgs, mid, B, K = p["models"], p["cfgs"], p["mid"], p["B"], p["K"]
-    ms, cs, d = models, cfgs, {k: np.array(v, copy=True) for k, v in p["d"].items()}
-    if p["rows"] is not None:
-        ms, cs, pid = _per_instance(models, cfgs, mid, p["rows"])
-        d["model_id"] = pid
-    assert "ee_ref_rot" not in d                                    # (no EE orientation reference state to carry in this restatement)
-
-    def set_targets(k):
-        for t in p["tracks"]:
-            if _index(t["target"]) == TRUNK:
-                d["trunk_target"] = _at(t, k)
-            else:
-                d["ee_target"][:, _index(t["target"])] = _at(t, k)
-    status, iters = np.zeros(B, np.int32), np.zeros(B, np.int32)
-    tick_status = np.zeros((K, B), np.int32)
-    frames, targets = np.zeros((K, B, 6, 3)), np.zeros((K, B, 6, 3))
-    out = None
-    for k in range(K):
-        set_targets(k)
-        targets[k, :, :5], targets[k, :, 5] = d["ee_target"], d["trunk_target"]
-        out = oracle.tick(ms, cs, d, DT, B, nthreads=8, want_q_next=True)
-        tick_status[k] = out["status"]
-        status = np.maximum(status, out["status"])
-        iters += out["iters"]
-        d["q"] = oracle.update_state(models, d["q"], out["q_next"], d["ee_target"], p["imu"], mid) if p["running"] else out["q_next"]
-        frames[k] = _frames(models, d["q"], mid)
-        for i, c in enumerate(cfgs):                                # the reference-state side effects of qpb()
-            sel = slice(None) if mid is None else (mid == i)
-            for e in range(capi.NEE):
-                if c.task_ee[e]:
-                    d["prev_ee_target"][sel, e] = d["ee_target"][sel, e]
-            if c.task_trunk:
-                d["prev_trunk_target"][sel] = d["trunk_target"][sel]
-                d["trunk_prev_rot"][sel] = R.from_euler("xyz", d["trunk_ref_euler"][sel]).as_matrix().reshape(-1, 9)
-    set_targets(K)
-    ref = dict(q=d["q"], qdot=out["qdot"], status=status, iters=iters, ee_target=d["ee_target"], trunk_target=d["trunk_target"],
-               tick_status=tick_status, frames=frames, targets=targets)
-    for v in ref.values():
-        v.setflags(write=False)
-    return ref
+    """common.tracks_reference of the named problem. Computed once, never modified."""
+    return common.tracks_reference(_problem(name))
 
 
 def _handle(p, options=None, max_batch=None):
@@ -315,20 +226,6 @@ def test_caller_tangents():
 
 
 # ------------------------------------------------------------------------------------------------ 4. chicken head: scores
-def _numpy_scores(trace, targets, status):
-    """the scores of [K, F, B, 3] positions against [K, F, B, 3] targets and [K, B] statuses, summed in tick order"""
-    K, B = status.shape
-    d = trace - targets
-    e2 = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
-    err = np.sqrt(e2)
-    ssum = np.zeros(e2.shape[1:])
-    for k in range(K):
-        ssum = ssum + e2[k]
-    bad = status != 0
-    return dict(err_sq_sum=ssum, err_max=err.max(axis=0), err_max_tick=err.argmax(axis=0).astype(np.int32), err_final=err[-1],
-                first_bad_tick=np.where(bad.any(axis=0), bad.argmax(axis=0), -1).astype(np.int32), bad_ticks=bad.sum(axis=0).astype(np.int32))
-
-
 @functools.lru_cache(maxsize=None)
 def _chicken_runs():
     """the chicken-head problem (only the trunk followed; gripper and trunk scored) with trace + scores, and with the scores alone"""
