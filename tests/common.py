@@ -59,15 +59,128 @@ def config(name, model):
 
 def tick_inputs(model, cfg, B, seed, stress=True, with_rot=False):
     d = wbc_workload.make_tick_inputs(model, cfg, B, seed, OracleFK([model]), stress=stress)
-    if with_rot:   # exercise the orientation feed-forward terms with a moving reference
-        rng = np.random.default_rng(seed + 1000)
-        from scipy.spatial.transform import Rotation as R
-        e = rng.uniform(-0.3, 0.3, (B, 5, 3))
-        de = rng.normal(0, 1e-3, (B, 5, 3))
-        d["ee_ref_rot"] = R.from_euler("xyz", e.reshape(-1, 3)).as_matrix().reshape(B, 5, 9)
-        d["ee_prev_rot"] = R.from_euler("xyz", (e - de).reshape(-1, 3)).as_matrix().reshape(B, 5, 9)
-        d["trunk_ref_euler"] = d["trunk_ref_euler"] + rng.normal(0, 0.02, (B, 3))
-        d["trunk_prev_rot"] = R.from_euler("xyz", d["trunk_ref_euler"] - rng.normal(0, 1e-3, (B, 3))).as_matrix().reshape(B, 9)
+    if with_rot:
+        add_rot_references(d, B, seed)
+    return d
+
+
+def add_rot_references(d, B, seed):
+    """exercise the orientation feed-forward terms with a moving reference (tick_inputs(with_rot=True))"""
+    rng = np.random.default_rng(seed + 1000)
+    from scipy.spatial.transform import Rotation as R
+    e = rng.uniform(-0.3, 0.3, (B, 5, 3))
+    de = rng.normal(0, 1e-3, (B, 5, 3))
+    d["ee_ref_rot"] = R.from_euler("xyz", e.reshape(-1, 3)).as_matrix().reshape(B, 5, 9)
+    d["ee_prev_rot"] = R.from_euler("xyz", (e - de).reshape(-1, 3)).as_matrix().reshape(B, 5, 9)
+    d["trunk_ref_euler"] = d["trunk_ref_euler"] + rng.normal(0, 0.02, (B, 3))
+    d["trunk_prev_rot"] = R.from_euler("xyz", d["trunk_ref_euler"] - rng.normal(0, 1e-3, (B, 3))).as_matrix().reshape(B, 9)
+    return d
+
+
+# ---- poses far from the nominal stance (DESIGN.md §3.28): sample_q keeps the base within 5 cm and 0.1 rad of the origin, where no tick test can see
+# the Euler angles a kernel computes and no kernel leaves the first quadrant of anything
+def _attitude_ok(model, q):
+    """not at the gimbal pole and not on a cut of atan2, judged by the 50-digit reference: there one ulp in R legitimately flips an angle by 2 pi"""
+    import kin_reference
+    e = kin_reference.trunk_euler(model.data, q)
+    return abs(e[1]) <= 1.3 and abs(abs(e[0]) - np.pi) >= 0.02 and abs(abs(e[2]) - np.pi) >= 0.02
+
+
+# roll, pitch, yaw ranges of the narrowed attitudes: inside +-0.3, +-0.3, +-0.5 rad, and on the side where the CoM box (RR and FL foot positions on
+# WORLD axes) keeps the CoM's y between its bounds — at yaw < -0.2 or roll > 0.15 the oracle finds a quarter of the instances infeasible
+NARROW = np.array([[-0.3, 0.15], [-0.3, 0.3], [-0.2, 0.5]])
+
+
+def _far_base(model, q, rng, narrow=False):
+    """base x, y uniform in +-3 m; attitude cycling over four kinds: 0, 1, 2 a rotation by +-(pi - 0.2) about unit(e_k + 0.15 N(0, I)) (tr R < 0
+    with R_kk the largest diagonal entry: the three non-trace quaternion branches), 3 a rotation by +-U(0.5, 2.6) about a random axis; every
+    second quaternion negated (w < 0). narrow: roll, pitch, yaw uniform in NARROW instead (the CoM box stays feasible)."""
+    B = q.shape[0]
+    q[:, 0:2] = rng.uniform(-3.0, 3.0, (B, 2))
+    for b in range(B):
+        while True:
+            if narrow:
+                quat = wbc_workload.euler_xyz_to_quat(rng.uniform(NARROW[:, 0], NARROW[:, 1], (1, 3)))[0]
+            else:
+                kind = b % 4
+                if kind < 3:
+                    axis = np.eye(3)[kind] + 0.15 * rng.normal(size=3)
+                    ang = np.pi - 0.2
+                else:
+                    axis = rng.normal(size=3)
+                    ang = rng.uniform(0.5, 2.6)
+                ang *= 1.0 if rng.random() < 0.5 else -1.0
+                axis /= np.linalg.norm(axis)
+                quat = np.concatenate([axis * np.sin(ang / 2), [np.cos(ang / 2)]])
+            q[b, 3:7] = -quat if b % 2 else quat
+            if _attitude_ok(model, q[b]):
+                break
+    return q
+
+
+def far_q(model, B, rng, narrow=False):
+    """legs and arm of wbc_workload.sample_q, the base far from the origin at a large attitude (_far_base)"""
+    return _far_base(model, wbc_workload.sample_q(model, B, rng), rng, narrow)
+
+
+def far_fk_q(model, B, rng):
+    """FK only: every 1-DoF joint uniform over its full [q_lo, q_hi], four instances exactly on all lower limits and four on all upper limits;
+    the base as far_q"""
+    q = wbc_workload.sample_q(model, B, rng)
+    lo, hi = model.q_lo[7:model.nq], model.q_hi[7:model.nq]
+    q[:, 7:model.nq] = rng.uniform(lo, hi, (B, model.nq - 7))
+    q[:4, 7:model.nq], q[4:8, 7:model.nq] = lo, hi
+    return _far_base(model, q, rng)
+
+
+def edge_trunk_box(d, cfg, rng, f_lo=0.97):
+    """every instance, each of the three angles: the box centre moved by trunk_box_ang * f * s, f ~ U(f_lo, 1.005), s = +-1 — the current angle
+    at the edge of its box, a few just outside (what make_tick_inputs' stress recipe does to the z row alone)"""
+    B = d["q"].shape[0]
+    f = rng.uniform(f_lo, 1.005, (B, 3))
+    s = np.where(rng.random((B, 3)) < 0.5, 1.0, -1.0)
+    d["trunk_box_center"] = d["trunk_box_center"].copy()
+    d["trunk_box_center"][:, 1:] += cfg.trunk_box_ang * f * s
+    return d
+
+
+def far_tick_inputs(model, cfg, B, seed, narrow=False, edge=True, with_rot=False, f_lo=0.97):
+    """wbc_workload.make_tick_inputs(stress=True) restated on far_q poses (that function draws its own sample_q and stays as it is): the same
+    damper and z-box stress, targets on the robot, then edge_trunk_box where the configuration has a trunk box."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    fk = OracleFK([model])
+    q = far_q(model, B, rng, narrow)
+    if cfg.use_bounds:
+        arm_dofs = np.arange(19, model.nv - 3)
+        for b in np.nonzero(rng.random(B) < 0.25)[0]:
+            i = int(rng.choice(arm_dofs))
+            qi = cfg.damper_qidx[i]
+            v = (cfg.damper_lo[i] + rng.uniform(0.0, 0.01)) if rng.random() < 0.5 else (cfg.damper_hi[i] - rng.uniform(0.0, 0.01))
+            if model.q_lo[qi] <= v <= model.q_hi[qi]:
+                q[b, qi] = v
+    oMf = fk(q)
+    pos = oMf[:, :, 9:12]
+    trunk = pos[:, capi.FR_TRUNK, :].copy()
+    ee_target = pos[:, capi.FR_EE0:capi.FR_EE0 + 5, :].copy()
+    ee_target[:, 4, :] += rng.normal(0, 0.01, (B, 3))
+    d = dict(q=q, ee_target=ee_target, prev_ee_target=ee_target - rng.normal(0, 0.0005, (B, 5, 3)),
+             trunk_target=trunk.copy(), prev_trunk_target=trunk - rng.normal(0, 0.0005, (B, 3)))
+    eul = wbc_workload.R_to_euler_xyz(oMf[:, capi.FR_TRUNK, 0:9])
+    box = np.concatenate([trunk[:, 2:3], eul], axis=1)
+    if cfg.con_trunk:
+        pick = rng.random(B) < 0.25
+        frac = rng.uniform(0.245, 0.2505, B) * np.where(rng.random(B) < 0.5, 1.0, -1.0)
+        box[pick, 0] = trunk[pick, 2] / (1.0 + frac[pick])
+    d["trunk_box_center"] = box
+    d["trunk_ref_euler"] = eul.copy()
+    d["trunk_prev_rot"] = oMf[:, capi.FR_TRUNK, 0:9].copy()
+    if cfg.task_com:
+        d["com_target"] = fk.com(q) + rng.normal(0, 0.002, (B, 3))
+        d["com_target_vel"] = rng.normal(0, 0.05, (B, 3))
+    if cfg.con_trunk and edge:
+        edge_trunk_box(d, cfg, rng, f_lo)
+    if with_rot:
+        add_rot_references(d, B, seed)
     return d
 
 
