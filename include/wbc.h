@@ -442,6 +442,63 @@ typedef struct WbcTrackScores {  /* all arrays optional */
 int wbc_rollout_tracks(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
                        const WbcTracks* tracks, const WbcTrackScores* scores /* may be NULL */, int mem, void* stream);
 
+/* ------------------------------------------------------------------ constraint slack: CoM box, trunk box, joint range
+ * How far a configuration is from the reference's constraint limits, whether or not the configuration enforces them: what sim3.py prints
+ * by hand (robot_data.com[0] and the frame positions, sim3.py:237-261, :353-355). Slack >= 0 inside, < 0 outside. All families are evaluated
+ * at a configuration q [27] under instance b's model and configuration; four families in a fixed order, each the minimum of its components,
+ * each component with a code:
+ *   0 WBC_SLACK_COM        r = x, y: lower -(p_RR[r] - com[r]) (code 2 r), upper p_FL[r] - com[r] (2 r + 1); p_FL, p_RR: world positions of EE
+ *                          frames 1 and 2, com: data.com[0] — the operands of CoMConstraint (Robot_Wrapper4.py:669-677) before 1 / dt and
+ *                          com_box_scale.
+ *   1 WBC_SLACK_TRUNK_Z    lower -((c0 - v) - z) (0), upper (c0 + v) - z (1); c0 = trunk_box_center[0], v = c0 * cfg.trunk_box_z_frac, z the
+ *                          trunk frame's world z (trunkConstraint, :719, :735-736).
+ *   2 WBC_SLACK_TRUNK_ANG  a = roll, pitch, yaw: lower -((c[1 + a] - cfg.trunk_box_ang) - e[a]) (2 a), upper (c[1 + a] + cfg.trunk_box_ang) - e[a]
+ *                          (2 a + 1); e from the trunk rotation R as the tick kernels form it: atan2(R21, R22), atan2(-R20, sqrt(R21^2 + R22^2)),
+ *                          atan2(R10, R00).
+ *   3 WBC_SLACK_JOINT      every velocity DoF d with 6 <= d < cfg.lock_from, its joint's q index i: lower q[i] - q_lo[i] (2 d), upper
+ *                          q_hi[i] - q[i] (2 d + 1) — the model's own range of the DoF's own joint (WbcModelBlob.q_lo / q_hi), not the damper's
+ *                          index map (damper_qidx) and not the base. No such DoF: +inf, code -1.
+ * `which` is the code of the component at the minimum: components are scanned in increasing code order with a strict <, so the lowest code wins
+ * a tie. A row whose q holds a non-finite entry (among the model's nq) gives NaN and code -1 in all four families and NaN components; so do
+ * family 1 when trunk_box_center[0] is not finite and family 2 when one of trunk_box_center[1..3] is not. The other instances are unaffected.
+ * One kernel (csrc/wbc_k_slack.hip), four instances per wavefront, FK over the whole tree. WBC_E_UNSUPPORTED (the message names the limit) when
+ * a model of the handle does not fit that kernel's schedule: more than 22 joints, a tree deeper than 7, more than 16 joints at one depth. */
+#define WBC_N_SLACK 4
+enum { WBC_SLACK_COM = 0, WBC_SLACK_TRUNK_Z = 1, WBC_SLACK_TRUNK_ANG = 2, WBC_SLACK_JOINT = 3 };
+typedef struct WbcSlackOut {      /* all optional */
+  double*  slack;       /* [B][4] */
+  int32_t* which;       /* [B][4] */
+  double*  components;  /* [B][12]: family 0's four, family 1's two, family 2's six, in code order */
+} WbcSlackOut;
+/* q [B][27]; trunk_box_center [B][4] or NULL (families 1, 2 and their components come back NaN / -1); model_id [B], required with several
+ * models. Refused with WBC_E_ARG, naming the field: q NULL, out NULL. Needs a configured handle (lock_from, the box constants). */
+int wbc_state_slack(WbcBatch* b, int B, const double* q, const double* trunk_box_center, const int32_t* model_id, int mem,
+                    const WbcSlackOut* out, void* stream);
+
+typedef struct WbcSlackWatch {
+  int32_t mask;          /* bit f: family f is watched; n_w = popcount; rows below in increasing family order */
+  int32_t group_size;    /* as WbcTrackScores */
+  double  *slack_min, *slack_final;                  /* [n_w][B] */
+  int32_t *slack_min_tick, *slack_min_which;         /* [n_w][B]: FIRST tick of the minimum (strictly-smaller rule), its code */
+  int32_t *neg_ticks, *first_neg_tick;               /* [n_w][B]: ticks with slack < 0; the first of them, -1 if none */
+  double  *trace;                                    /* [ticks + hold_ticks][n_w][B], optional */
+  double  *group_min;  int32_t *group_neg_instances; /* [n_w][B / M]: min of slack_min; instances with neg_ticks > 0 */
+} WbcSlackWatch;
+/* The roll-outs above with the slacks watched: after every tick the roll-out runs (hold ticks included) ONE launch of the slack kernel
+ * evaluates the watched families at the state the update kernel just wrote (current_joint_config after tick k: what q_final would hold),
+ * with in0->trunk_box_center as the box centres, and folds them into the per-instance results — no second accumulation launch. All arrays
+ * optional. A tick whose family slack is NaN makes that family's slack_min NaN for good: slack_min_tick is the first such tick, the code -1,
+ * and neg_ticks does not count it. Group results come from one wavefront per group after the last tick (a fixed-shape reduction, no atomics:
+ * two identical calls give identical bits); a NaN slack_min in a group gives a NaN group_min.
+ * watch == NULL: exactly the tracks call when tracks are given, the plain per-instance-rows roll-out otherwise — the same launches, memsets
+ * and outputs bit for bit. With a watch the roll-out's own outputs and scores are unchanged: the watch only reads. tracks may be NULL (then
+ * r->ee_target_step and r->hold_ticks are allowed as in the plain roll-out); scores may be NULL and needs tracks.
+ * Refused with WBC_E_ARG, naming the field: mask 0 or with bits >= 4; scores without tracks; a group_size that does not divide B; family 1
+ * or 2 watched without in0->trunk_box_center; with tracks, the tracks call's own refusals. WBC_E_UNSUPPORTED as in the state call above. */
+int wbc_rollout_watch(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
+                      const WbcTracks* tracks /* may be NULL */, const WbcTrackScores* scores /* may be NULL; needs tracks */,
+                      const WbcSlackWatch* watch /* may be NULL */, int mem, void* stream);
+
 /* Knobs of a handle (none of them changes a result beyond rounding; defaults in brackets):
  *   "jtj_mfma"        [-1] H = A'A of wbc_tick / wbc_assemble (QP_Wrapper.py:17) on the fp64 matrix cores (v_mfma_f64_16x16x4_f64)
  *                          or as the sparse vector-unit contraction. -1: matrix cores when the Cartesian task stack has

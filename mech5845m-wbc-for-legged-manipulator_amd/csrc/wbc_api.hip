@@ -8,6 +8,7 @@
 #include <vector>
 #include "wbc_device.h"
 #include "wbc_traj.h"
+#include "wbc_slack.h"
 
 // d_traj per instance of max_batch: err_sq_sum / err_max / err_final [6] each + the six frames' positions [6][3]; bad, err_max_tick [6],
 // first_bad_tick, bad_ticks, status_max. One int32 (the bad-row count) follows.
@@ -90,6 +91,8 @@ struct WbcBatch {
   double *d_pu, *d_pq;   // qpJointb MANI/HYBRID results: u [max_batch][26], q_after [max_batch][27] (lazy)
   void* d_roll;          // wbc_rollout's mutable controller state for max_batch instances (lazy)
   void* d_traj;          // wbc_rollout_traj / wbc_rollout_tracks: per-instance scores of six frames, their positions of the tick, bad-row flags and their count (lazy)
+  SlackLimits* d_slack_lim;   // wbc_state_slack / wbc_rollout_watch: the models' own joint ranges by DoF (lazy)
+  void* d_slack;         // wbc_rollout_watch: per-instance accumulators of the four families for max_batch instances (lazy)
 };
 
 // ---------------------------------------------------------------------------------------------- model
@@ -247,6 +250,8 @@ extern "C" void wbc_batch_destroy(WbcBatch* b) {
   if (b->d_pq) (void)hipFree(b->d_pq);
   if (b->d_roll) (void)hipFree(b->d_roll);
   if (b->d_traj) (void)hipFree(b->d_traj);
+  if (b->d_slack_lim) (void)hipFree(b->d_slack_lim);
+  if (b->d_slack) (void)hipFree(b->d_slack);
   if (b->d_status) (void)hipFree(b->d_status);
   if (b->d_defer) (void)hipFree(b->d_defer);
   if (b->d_dstat) (void)hipFree(b->d_dstat);
@@ -537,6 +542,8 @@ static void build_boxp_plan(const DevModel& M, const WbcConfig& c, int prows, De
 
 static void build_plan(const DevModel& M, const WbcConfig& c, int prows, DevPlan* P) {
   memset(P, 0, sizeof *P);
+  // the whole-tree tables for every configured model (wbc_slack_kernel); the orth / box plan builders below refill them with the same entries
+  P->slack_ok = build_q_tables(M, P, false) ? 1 : 0;
   build_posture_plan(M, c, P);
   for (int e = 0; e < WBC_NEE; ++e) { if (c.task_ee[e]) P->task_ee_mask |= 1u << e; if (c.con_ee[e]) P->con_ee_mask |= 1u << e; }
   P->flags = (c.con_com ? 1u : 0u) | (c.con_trunk ? 2u : 0u) | (c.task_trunk ? 4u : 0u) | (c.use_bounds ? 8u : 0u) | ((uint32_t)(c.task_joint & 7) << 4);
@@ -1157,9 +1164,67 @@ extern "C" int wbc_update_state(WbcBatch* b, int B, const double* q_cur, const d
   return st.finish();
 }
 
+// wbc_state_slack / wbc_rollout_watch: every model of the handle fits wbc_slack_kernel's whole-tree schedule (DevPlan.slack_ok, else
+// WBC_E_UNSUPPORTED naming the limit build_q_tables found), and the models' own joint ranges by DoF are on the device (first use).
+static int slack_ready(WbcBatch* b, const char* who) {
+  for (int i = 0; i < b->n_models; ++i) {
+    if (b->plan_host[i].slack_ok) continue;
+    const DevModel& M = b->models[i]->dev;
+    if (M.njoints > 22) return fail(WBC_E_UNSUPPORTED, "%s: model %d does not fit the packed whole-tree schedule: %d joints (at most 22)", who, i, M.njoints);
+    if (M.maxdepth > 7) return fail(WBC_E_UNSUPPORTED, "%s: model %d does not fit the packed whole-tree schedule: tree depth %d (at most 7)", who, i, M.maxdepth);
+    return fail(WBC_E_UNSUPPORTED, "%s: model %d does not fit the packed whole-tree schedule: more than 16 joints at one tree depth", who, i);
+  }
+  if (!b->d_slack_lim) {
+    std::vector<SlackLimits> lim(b->n_models);
+    for (int i = 0; i < b->n_models; ++i) {
+      const DevModel& M = b->models[i]->dev;
+      const WbcModelBlob& blob = b->models[i]->blob;
+      memset(&lim[i], 0, sizeof lim[i]);
+      for (int d = 0; d < NL; ++d) {
+        const int qi = (d >= 6 && d < M.nv) ? M.col_q[d] : 7;       // 1-DoF joints live in [7, nq) (wbc_model_create)
+        lim[i].qi[d] = qi; lim[i].lo[d] = blob.q_lo[qi]; lim[i].hi[d] = blob.q_hi[qi];
+      }
+    }
+    SlackLimits* d = nullptr;
+    HIP_TRY(hipMalloc((void**)&d, sizeof(SlackLimits) * b->n_models));
+    if (hipError_t e = hipMemcpy(d, lim.data(), sizeof(SlackLimits) * b->n_models, hipMemcpyHostToDevice)) {
+      (void)hipFree(d);
+      return fail(WBC_E_HIP, "%s: %s", who, hipGetErrorString(e));
+    }
+    b->d_slack_lim = d;
+  }
+  return WBC_OK;
+}
+
+// The four slack families at q for every instance (include/wbc.h): one launch of wbc_slack_kernel.
+extern "C" int wbc_state_slack(WbcBatch* b, int B, const double* q, const double* trunk_box_center, const int32_t* model_id, int mem,
+                               const WbcSlackOut* out, void* stream) {
+  int rc = check_batch(b, B, "wbc_state_slack", true);
+  if (rc) return rc;
+  if (!q) return fail(WBC_E_ARG, "wbc_state_slack: q is required");
+  if (!out) return fail(WBC_E_ARG, "wbc_state_slack: out is required");
+  if (b->n_models > 1 && !model_id) return fail(WBC_E_ARG, "wbc_state_slack: model_id is required with %d models", b->n_models);
+  HIP_TRY(hipSetDevice(b->device_id));
+  if ((rc = slack_ready(b, "wbc_state_slack"))) return rc;
+  SlackArgs a;
+  memset(&a, 0, sizeof a);
+  a.models = b->d_models; a.cfgs = b->d_cfgs; a.plans = b->d_plans; a.lim = b->d_slack_lim;
+  a.B = B; a.n_models = b->n_models; a.rot = b->rot;
+  a.q = q; a.box = trunk_box_center; a.model_id = model_id;
+  a.slack = out->slack; a.which = out->which; a.components = out->components;
+  Stager st{b, mem, (hipStream_t)stream, {}};
+  const size_t n = (size_t)B;
+  st.in(&a.q, n * WBC_Q_STRIDE); st.in(&a.box, n * 4); st.in(&a.model_id, n);
+  st.out(&a.slack, n * SLACK_NF); st.out(&a.which, n * SLACK_NF); st.out(&a.components, n * SLACK_NC);
+  if ((rc = st.stage())) return rc;
+  if (int e = launch_slack(a, stream)) return fail(WBC_E_HIP, "slack kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+  return st.finish();
+}
+
 // K closed-loop ticks: the mutable controller state lives in the handle's rollout workspace; in0 is only read.
 static int rollout_run(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
-                       const WbcTracks* tracks, const WbcTrackScores* scores, bool one_track, int mem, void* stream);
+                       const WbcTracks* tracks, const WbcTrackScores* scores, bool one_track, int mem, void* stream,
+                       const WbcSlackWatch* watch = nullptr);
 extern "C" int wbc_rollout(WbcBatch* b, int B, const WbcTickIn* in0, double dt, const WbcRollout* r, int mem, void* stream) {
   return wbc_rollout_tp(b, B, in0, nullptr, dt, r, mem, stream);
 }
@@ -1172,8 +1237,12 @@ extern "C" int wbc_rollout_tp(WbcBatch* b, int B, const WbcTickIn* in0, const Wb
 // point): the update kernel leaves the targets alone and one wbc_traj_tick_kernel per tick scores the tick and writes every followed target of
 // the next. one_track: wbc_rollout_traj's call — the gripper's position comes from the update kernel's grip_trace row, and a constant trunk
 // step stays with the update kernel; otherwise the update kernel writes the six frames' positions of the tick into the workspace.
+// watch (wbc_rollout_watch, arguments checked by the entry point): one wbc_slack_kernel per tick behind the update kernel, on the state it
+// just wrote; the kernel keeps the per-instance results in the handle's workspace, copied out (and reduced per group) after the last tick.
+// watch == nullptr adds nothing to the sequence above.
 static int rollout_run(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
-                       const WbcTracks* tracks, const WbcTrackScores* scores, bool one_track, int mem, void* stream) {
+                       const WbcTracks* tracks, const WbcTrackScores* scores, bool one_track, int mem, void* stream,
+                       const WbcSlackWatch* watch) {
   int rc = check_batch(b, B, "wbc_rollout", true);
   if (rc) return rc;
   if (!r || r->ticks < 1 || !(dt > 0)) return fail(WBC_E_ARG, "wbc_rollout: ticks >= 1 and dt > 0 required");
@@ -1182,6 +1251,7 @@ static int rollout_run(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskPa
   if ((rc = validate_tick_in(b, in0, "wbc_rollout"))) return rc;
   if (!in0->ee_target || !in0->prev_ee_target) return fail(WBC_E_ARG, "wbc_rollout: ee_target / prev_ee_target are required (the base estimator reads the foot targets)");
   HIP_TRY(hipSetDevice(b->device_id));
+  if (watch && (rc = slack_ready(b, "wbc_rollout_watch"))) return rc;
   hipStream_t s = (hipStream_t)stream;
   const size_t n = (size_t)B, NB = (size_t)b->max_batch;
   // workspace layout (doubles per instance), then two int32 per instance
@@ -1221,6 +1291,17 @@ static int rollout_run(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskPa
     st.out(&so.err_sq_sum, nsc * n); st.out(&so.err_max, nsc * n); st.out(&so.err_max_tick, nsc * n); st.out(&so.err_final, nsc * n);
     st.out(&so.first_bad_tick, n); st.out(&so.bad_ticks, n); st.out(&so.trace, (size_t)r->ticks * nsc * n * 3);
     st.out(&so.group_rms, nsc * ng); st.out(&so.group_err_max, nsc * ng); st.out(&so.group_worst_status, ng); st.out(&so.group_bad_instances, ng);
+  }
+  WbcSlackWatch wo;
+  memset(&wo, 0, sizeof wo);
+  size_t nw = 0;                         // watched families
+  if (watch) {
+    wo = *watch;
+    nw = (size_t)__builtin_popcount((unsigned)wo.mask);
+    const size_t ng = wo.group_size > 0 ? n / (size_t)wo.group_size : 0;
+    st.out(&wo.slack_min, nw * n); st.out(&wo.slack_final, nw * n); st.out(&wo.slack_min_tick, nw * n); st.out(&wo.slack_min_which, nw * n);
+    st.out(&wo.neg_ticks, nw * n); st.out(&wo.first_neg_tick, nw * n); st.out(&wo.trace, (size_t)(r->ticks + r->hold_ticks) * nw * n);
+    st.out(&wo.group_min, nw * ng); st.out(&wo.group_neg_instances, nw * ng);
   }
   if ((rc = st.stage())) return rc;
   // seed the mutable state from in0
@@ -1290,6 +1371,20 @@ static int rollout_run(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskPa
     HIP_TRY(hipMemsetAsync(ta.bad_count, 0, sizeof(int32_t), s));
     if (int e = launch_traj_begin(ta, stream)) return fail(WBC_E_HIP, "trajectory kernel launch failed: %s", hipGetErrorString((hipError_t)e));
   }
+  // the watch's accumulators: [watched family][B] within regions sized for four families of max_batch
+  SlackArgs sa;
+  memset(&sa, 0, sizeof sa);
+  if (watch) {
+    if (!b->d_slack) HIP_TRY(hipMalloc(&b->d_slack, NB * SLACK_NF * (2 * sizeof(double) + 4 * sizeof(int32_t))));
+    double* S = (double*)b->d_slack;
+    const size_t F = SLACK_NF;
+    sa.slack_min = S; sa.slack_final = S + F * NB;
+    int32_t* I = (int32_t*)(S + 2 * F * NB);
+    sa.min_tick = I; sa.min_which = I + F * NB; sa.neg_ticks = I + 2 * F * NB; sa.first_neg = I + 3 * F * NB;
+    sa.models = b->d_models; sa.cfgs = b->d_cfgs; sa.plans = b->d_plans; sa.lim = b->d_slack_lim;
+    sa.B = B; sa.n_models = b->n_models; sa.rot = b->rot; sa.mask = wo.mask;
+    sa.q = blk(O_Q); sa.box = first.trunk_box_center; sa.model_id = first.model_id;
+  }
   const WbcTickIn loop_in = a.in;
   for (int k = 0; k < r->ticks + r->hold_ticks; ++k) {
     if (k == r->ticks) { u.ee_step = nullptr; u.trunk_step = nullptr; }   // hold phase: the targets stay where they are
@@ -1303,6 +1398,27 @@ static int rollout_run(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskPa
       ta.reached = one_track ? u.grip_trace : w_frames;
       ta.trace = so.trace ? so.trace + (size_t)k * nsc * n * 3 : nullptr;
       if (int e = launch_traj_tick(ta, k, stream)) return fail(WBC_E_HIP, "trajectory kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    }
+    if (watch) {
+      sa.k = k;
+      sa.trace = wo.trace ? wo.trace + (size_t)k * nw * n : nullptr;
+      if (int e = launch_slack(sa, stream)) return fail(WBC_E_HIP, "slack kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    }
+  }
+  if (watch) {
+    auto give = [&](void* dst, const void* src, size_t bytes) -> int {
+      if (dst) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s));
+      return WBC_OK;
+    };
+    if ((rc = give(wo.slack_min, sa.slack_min, nw * n * sizeof(double))) || (rc = give(wo.slack_final, sa.slack_final, nw * n * sizeof(double))) ||
+        (rc = give(wo.slack_min_tick, sa.min_tick, nw * n * sizeof(int32_t))) || (rc = give(wo.slack_min_which, sa.min_which, nw * n * sizeof(int32_t))) ||
+        (rc = give(wo.neg_ticks, sa.neg_ticks, nw * n * sizeof(int32_t))) || (rc = give(wo.first_neg_tick, sa.first_neg, nw * n * sizeof(int32_t)))) return rc;
+    if (wo.group_size > 0 && (wo.group_min || wo.group_neg_instances)) {
+      SlackGroupArgs ga;
+      memset(&ga, 0, sizeof ga);
+      ga.G = B / wo.group_size; ga.M = wo.group_size; ga.n_w = (int32_t)nw;
+      ga.slack_min = sa.slack_min; ga.neg_ticks = sa.neg_ticks; ga.group_min = wo.group_min; ga.group_neg_instances = wo.group_neg_instances;
+      if (int e = launch_slack_groups(ga, stream)) return fail(WBC_E_HIP, "slack kernel launch failed: %s", hipGetErrorString((hipError_t)e));
     }
   }
   if (tracks && scores) {
@@ -1366,8 +1482,14 @@ extern "C" int wbc_rollout_traj(WbcBatch* b, int B, const WbcTickIn* in0, const 
 
 // The roll-out with several followed targets (WbcTracks: end effectors and trunk, LINEAR or HERMITE), any frame scored (WbcTrackScores):
 // argument checks, then the shared loop.
+static int rollout_tracks_checked(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
+                                  const WbcTracks* tracks, const WbcTrackScores* scores, int mem, void* stream, const WbcSlackWatch* watch);
 extern "C" int wbc_rollout_tracks(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
                                   const WbcTracks* tracks, const WbcTrackScores* scores, int mem, void* stream) {
+  return rollout_tracks_checked(b, B, in0, tp, dt, r, tracks, scores, mem, stream, nullptr);
+}
+static int rollout_tracks_checked(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
+                                  const WbcTracks* tracks, const WbcTrackScores* scores, int mem, void* stream, const WbcSlackWatch* watch) {
   if (!r || !tracks) return fail(WBC_E_ARG, "wbc_rollout_tracks: r and tracks are required");
   if (r->ee_target_step) return fail(WBC_E_ARG, "wbc_rollout_tracks: ee_target_step must be NULL (tracks move the followed targets; the other EE targets are constant)");
   if (r->hold_ticks != 0) return fail(WBC_E_ARG, "wbc_rollout_tracks: hold_ticks must be 0 (a track holds its last milestone by itself)");
@@ -1399,7 +1521,24 @@ extern "C" int wbc_rollout_tracks(WbcBatch* b, int B, const WbcTickIn* in0, cons
   const bool trunk_scored = scores && ((scores->score_mask >> WBC_TARGET_TRUNK) & 1);
   if ((trunk_track || trunk_scored) && in0 && (!in0->trunk_target || !in0->prev_trunk_target))
     return fail(WBC_E_ARG, "wbc_rollout_tracks: a trunk track or score bit %d needs in0->trunk_target and prev_trunk_target", WBC_TARGET_TRUNK);
-  return rollout_run(b, B, in0, tp, dt, r, tracks, scores, false, mem, stream);
+  return rollout_run(b, B, in0, tp, dt, r, tracks, scores, false, mem, stream, watch);
+}
+
+// The roll-outs with the slack families watched (WbcSlackWatch): the watch's own argument checks, then the tracks call's (with tracks) and
+// the shared loop. watch == NULL: the call without a watch, launch for launch.
+extern "C" int wbc_rollout_watch(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
+                                 const WbcTracks* tracks, const WbcTrackScores* scores, const WbcSlackWatch* watch, int mem, void* stream) {
+  if (scores && !tracks) return fail(WBC_E_ARG, "wbc_rollout_watch: scores needs tracks");
+  if (watch) {
+    if (watch->mask <= 0 || watch->mask >= (1 << WBC_N_SLACK))
+      return fail(WBC_E_ARG, "wbc_rollout_watch: mask = 0x%x must have at least one of the bits 0..%d and none beyond", (unsigned)watch->mask, WBC_N_SLACK - 1);
+    if (watch->group_size < 0 || (watch->group_size > 0 && (B < 1 || B % watch->group_size != 0)))
+      return fail(WBC_E_ARG, "wbc_rollout_watch: group_size = %d does not divide B = %d", watch->group_size, B);
+    if ((watch->mask & ((1 << WBC_SLACK_TRUNK_Z) | (1 << WBC_SLACK_TRUNK_ANG))) && in0 && !in0->trunk_box_center)
+      return fail(WBC_E_ARG, "wbc_rollout_watch: the trunk families (mask bits %d, %d) need in0->trunk_box_center", WBC_SLACK_TRUNK_Z, WBC_SLACK_TRUNK_ANG);
+  }
+  if (tracks) return rollout_tracks_checked(b, B, in0, tp, dt, r, tracks, scores, mem, stream, watch);
+  return rollout_run(b, B, in0, tp, dt, r, nullptr, nullptr, false, mem, stream, watch);
 }
 
 static int qp_common(WbcBatch* b, int B, QpArgs& a, int mem, void* stream, const char* who) {

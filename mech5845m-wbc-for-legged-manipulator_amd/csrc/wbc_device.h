@@ -100,6 +100,8 @@ struct DevPlan {
   uint32_t redsup[WBC_MAX_FRAMES];   // frame f: bit k = reduced variable k moves the frame (frame_support mapped through pos)
   int32_t pos[32];                   // DoF d -> reduced position (-1: eliminated / absent)
   int32_t lidx[32];                  // DoF d -> l (-1: not an eliminated leg DoF)
+  // (appended: the fields above keep their offsets, and the structure its size — it ended in four bytes of padding)
+  int32_t slack_ok;                  // the whole-tree tables q_fk / q_scq / q_jm hold this model (build_q_tables; wbc_slack_kernel reads them whatever q_ok / x_ok say)
 };
 
 enum Mode : int { MODE_TICK = 0, MODE_ASSEMBLE = 1, MODE_FK = 2 };

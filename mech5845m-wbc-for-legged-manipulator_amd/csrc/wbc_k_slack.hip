@@ -1,0 +1,244 @@
+// wbc_k_slack.hip — wbc_state_slack / wbc_rollout_watch: the slack of the reference's constraint quantities at a configuration q, whether or
+// not the configuration enforces them (include/wbc.h). Four families, slack >= 0 inside and < 0 outside:
+//   0 CoM box      the operands of CoMConstraint (Robot_Wrapper4.py:669-677; wbc_common.h, P6) before inv_dt and com_box_scale
+//   1 trunk z box  trunkConstraint's z row (:719, :735-736) before inv_dt and trunk_box_scale
+//   2 trunk angles its three angle rows, the angles by the tick kernels' atan2 formula
+//   3 joint range  the model's own range of each free DoF's OWN joint (not the damper's index map)
+// Two kernels:
+//   wbc_slack_kernel         four instances per wavefront in wbc_update_packed_kernel's lane layout (lane = 16 r + s). FK over the whole-tree
+//                            schedule DevPlan.q_fk (the CoM needs every body). Writes the row (wbc_state_slack) and / or folds the tick into
+//                            the watch's accumulators (lanes s < 4 of a row, one family each): no second accumulation launch.
+//   wbc_slack_groups_kernel  once at the end: one wavefront per group of M consecutive instances, fixed-shape reduction (no atomics)
+// Reads q, the box centres and the tables; writes nothing but its outputs, rows [0, B) only.
+#include <hip/hip_runtime.h>
+#include <limits.h>
+#include <math.h>
+#include "wbc_packed.h"
+#include "wbc_slack.h"
+
+namespace wbc {
+
+struct __attribute__((aligned(16))) SInst {
+  double oMi[24 * 12];
+  double q[32];
+  double sc[64];
+  double pf[12];                            // FL foot, RR foot, trunk frame: world positions (stride 4)
+  double eul[4];                            // roll, pitch, yaw of the trunk rotation
+};
+struct __attribute__((aligned(16))) SSmemP { SInst I[4]; };
+
+__device__ __forceinline__ bool slack_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }   // false for NaN and +-inf
+// (v, c) <- the smaller of (v, c) and (ov, oc): by value, a tie by the lower code — what a scan in increasing code order with a strict < gives
+__device__ __forceinline__ void slack_take(double& v, int& c, const double ov, const int oc) {
+  if (ov < v || (ov == v && oc < c)) { v = ov; c = oc; }
+}
+template <int CTRL>
+__device__ __forceinline__ void slack_take_dpp(double& v, int& c) {
+  const double ov = dpp<CTRL>(v);
+  const int oc = __builtin_amdgcn_update_dpp(c, c, CTRL, 0xF, 0xF, false);
+  slack_take(v, c, ov, oc);
+}
+// minimum of N components scanned in increasing code order with a strict <
+template <int N>
+__device__ __forceinline__ void slack_scan(const double* c, double& v, int& w) {
+  v = c[0]; w = 0;
+#pragma unroll
+  for (int i = 1; i < N; ++i) if (c[i] < v) { v = c[i]; w = i; }
+}
+
+template <bool ROT>   // ROT: rotated joint placements in the batch (wbc_k_sim3p.hip)
+__global__ void __launch_bounds__(64) wbc_slack_kernel(const SlackArgs A, const DevModel* __restrict__ models, const WbcConfig* __restrict__ cfgs,
+                                                       const DevPlan* __restrict__ plans) {
+  __shared__ SSmemP SP;
+  const int lane = threadIdx.x, r = lane >> 4, s = lane & 15, rbase = lane & 48;
+  SInst& U = SP.I[r];
+  const int b_raw = 4 * blockIdx.x + r;
+  const bool valid = b_raw < A.B;
+  const size_t b = valid ? b_raw : A.B - 1;
+  int mid = 0;
+  if (A.model_id) { mid = A.model_id[b]; mid = mid < 0 ? 0 : (mid >= A.n_models ? A.n_models - 1 : mid); }
+  const DevModel& M = models[mid];
+  const WbcConfig& cfg = cfgs[mid];
+  const DevPlan& P = plans[mid];
+  const SlackLimits& Lm = A.lim[mid];
+  const int nq = M.nq, nv = M.nv, nj = M.njoints;
+  const double qnan = __longlong_as_double(0x7FF8000000000000ll), inf = __longlong_as_double(0x7FF0000000000000ll);
+  // ---- every global read first
+  const double* qg = A.q + b * NQ;
+  const double q0 = qg[s], q1 = (16 + s < nq) ? qg[16 + s] : 0.0;
+  double bc[4] = {qnan, qnan, qnan, qnan};
+  if (A.box) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) bc[i] = A.box[b * 4 + i];
+  }
+  DevPlan::PkJoint fkn = P.q_fk[0][s];
+  const int scq0 = P.q_scq[(2 + s) & 31], scq1 = P.q_scq[(18 + s) & 31];
+  // frame of this lane: FL foot, RR foot (EE_frame_pos[1], [2]: the CoM box's corners), trunk
+  const int fr = (s == 0) ? WBC_FR_EE0 + 1 : ((s == 1) ? WBC_FR_EE0 + 2 : WBC_FR_TRUNK);
+  const int fjoint = M.frame_joint[fr];
+  const double f0 = M.frame_p[fr][0], f1 = M.frame_p[fr][1], f2 = M.frame_p[fr][2];
+  const int tjoint = M.frame_joint[WBC_FR_TRUNK];
+  const int j1 = 16 + s;                                          // bodies of this lane: joints s (>= 1) and 16 + s
+  const bool hb0 = s >= 1 && s < nj, hb1 = j1 < nj;
+  const DevPlan::QJnt m0 = P.q_jm[hb0 ? s : 1], m1 = P.q_jm[hb1 ? j1 : 1];
+  const int lock = cfg.lock_from;
+  const bool hd0 = s >= 6 && s < lock && s < nv, hd1 = j1 < lock && j1 < nv;   // free DoF of this lane: d = s and 16 + s
+  const int qi0 = Lm.qi[hd0 ? s : 6], qi1 = Lm.qi[hd1 ? j1 : 6];
+  const double lo0 = Lm.lo[hd0 ? s : 6], hi0 = Lm.hi[hd0 ? s : 6], lo1 = Lm.lo[hd1 ? j1 : 6], hi1 = Lm.hi[hd1 ? j1 : 6];
+  const double z_frac = cfg.trunk_box_z_frac, box_ang = cfg.trunk_box_ang;
+  const bool qbad = (s < nq && !slack_finite(q0)) || (16 + s < nq && !slack_finite(q1));
+  const bool rowbad = ((__ballot(qbad) >> rbase) & 0xFFFFull) != 0ull;
+  U.q[s] = q0; U.q[16 + s] = q1;
+  WSYNC();
+  const double* const qv = U.q;
+  double* const oMi = U.oMi;
+  pk_fk_seed(oMi, U.sc, qv, scq0, scq1, s);
+  WSYNC();
+  pk_fk_sweep<ROT>(oMi, U.sc, qv, M, P.q_fk, fkn, s);               // pin.forwardKinematics over every joint, level by level
+  // ---- frame origins, the trunk's Euler angles (one atan2 per row on lanes 0..2, the tick kernels' formula: wbc_common.h, P6)
+  {
+    const double* Pj = oMi + 12 * fjoint;
+    const double* Pt = oMi + 12 * tjoint;                           // R column-major: R(i, j) = Pt[3 j + i]
+    const double R21 = Pt[5], R22 = Pt[8], R20 = Pt[2], R10 = Pt[1], R00 = Pt[0];
+    const double ay = (s == 0) ? R21 : ((s == 1) ? -R20 : R10);
+    const double ax = (s == 0) ? R22 : ((s == 1) ? sqrt(fma(R21, R21, R22 * R22)) : R00);
+    const double eul = atan2(ay, ax);
+    if (s < 3) {
+#pragma unroll
+      for (int rr = 0; rr < 3; ++rr) U.pf[4 * s + rr] = Pj[9 + rr] + Pj[rr] * f0 + Pj[3 + rr] * f1 + Pj[6 + rr] * f2;
+      U.eul[s] = eul;
+    }
+  }
+  // ---- data.com[0], x and y: lane s sums m_j (R_j c_j + p_j) over joints s and 16 + s in that order, then the row butterfly and one division each
+  double cx = 0.0, cy = 0.0, cm = 0.0;
+  {
+    const double* Pa = oMi + 12 * (hb0 ? s : 1);
+    const double* Pb = oMi + 12 * (hb1 ? j1 : 1);
+    const double xa = Pa[9] + Pa[0] * m0.c0 + Pa[3] * m0.c1 + Pa[6] * m0.c2, ya = Pa[10] + Pa[1] * m0.c0 + Pa[4] * m0.c1 + Pa[7] * m0.c2;
+    const double xb = Pb[9] + Pb[0] * m1.c0 + Pb[3] * m1.c1 + Pb[6] * m1.c2, yb = Pb[10] + Pb[1] * m1.c0 + Pb[4] * m1.c1 + Pb[7] * m1.c2;
+    if (hb0) { cx = m0.m * xa; cy = m0.m * ya; cm = m0.m; }
+    if (hb1) { cx += m1.m * xb; cy += m1.m * yb; cm += m1.m; }
+  }
+  cx = rsum16(cx); cy = rsum16(cy); cm = rsum16(cm);
+  const double com0 = cx / cm, com1 = cy / cm;
+  // ---- joint range: one DoF pair per lane, then a 16-lane minimum that carries the code
+  double jv = inf;
+  int jc = INT_MAX;
+  {
+    const double x0 = qv[qi0], x1 = qv[qi1];
+    if (hd0) { slack_take(jv, jc, x0 - lo0, 2 * s); slack_take(jv, jc, hi0 - x0, 2 * s + 1); }
+    if (hd1) { slack_take(jv, jc, x1 - lo1, 2 * j1); slack_take(jv, jc, hi1 - x1, 2 * j1 + 1); }
+  }
+  slack_take_dpp<DPP_XOR1>(jv, jc); slack_take_dpp<DPP_XOR2>(jv, jc); slack_take_dpp<DPP_HALF_MIRROR>(jv, jc); slack_take_dpp<DPP_MIRROR>(jv, jc);
+  if (jc == INT_MAX) jc = -1;                                       // no free DoF: +inf, no code
+  WSYNC();                                                          // pf, eul are visible
+  // ---- the components of families 0..2 in code order, every lane of the row alike
+  double comp[SLACK_NC];
+  {
+    const double* pFL = U.pf;
+    const double* pRR = U.pf + 4;
+    comp[0] = -(pRR[0] - com0); comp[1] = pFL[0] - com0;
+    comp[2] = -(pRR[1] - com1); comp[3] = pFL[1] - com1;
+    const double z = U.pf[8 + 2], v = bc[0] * z_frac;
+    comp[4] = -((bc[0] - v) - z); comp[5] = (bc[0] + v) - z;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const double e = U.eul[a];
+      comp[6 + 2 * a] = -((bc[1 + a] - box_ang) - e); comp[7 + 2 * a] = (bc[1 + a] + box_ang) - e;
+    }
+  }
+  double sl[SLACK_NF];
+  int wh[SLACK_NF];
+  slack_scan<4>(comp, sl[0], wh[0]);
+  slack_scan<2>(comp + 4, sl[1], wh[1]);
+  slack_scan<6>(comp + 6, sl[2], wh[2]);
+  sl[3] = jv; wh[3] = jc;
+  const bool bad1 = rowbad || !slack_finite(bc[0]);
+  const bool bad2 = rowbad || !slack_finite(bc[1]) || !slack_finite(bc[2]) || !slack_finite(bc[3]);
+  if (rowbad) { sl[0] = qnan; wh[0] = -1; sl[3] = qnan; wh[3] = -1; }
+  if (bad1) { sl[1] = qnan; wh[1] = -1; }
+  if (bad2) { sl[2] = qnan; wh[2] = -1; }
+#pragma unroll
+  for (int i = 0; i < SLACK_NC; ++i) if (i < 4 ? rowbad : (i < 6 ? bad1 : bad2)) comp[i] = qnan;
+  if (!valid) return;
+  // ---- the row (wbc_state_slack): component s on lane s < 12, family s on lane s < 4
+  double cs = comp[0];
+#pragma unroll
+  for (int i = 1; i < SLACK_NC; ++i) cs = (s == i) ? comp[i] : cs;
+  if (A.components && s < SLACK_NC) A.components[b * SLACK_NC + s] = cs;
+  const double fs = (s == 0) ? sl[0] : (s == 1) ? sl[1] : (s == 2) ? sl[2] : sl[3];
+  const int fw = (s == 0) ? wh[0] : (s == 1) ? wh[1] : (s == 2) ? wh[2] : wh[3];
+  if (s < SLACK_NF) {
+    if (A.slack) A.slack[b * SLACK_NF + s] = fs;
+    if (A.which) A.which[b * SLACK_NF + s] = fw;
+  }
+  // ---- the watch: lane s < 4 folds family s of tick k into row w of the accumulators (tick 0 initialises them)
+  if (s < SLACK_NF && ((A.mask >> s) & 1)) {
+    const size_t i = (size_t)__popc((unsigned)A.mask & ((1u << s) - 1u)) * (size_t)A.B + b;
+    const int k = A.k;
+    double mn = fs;
+    int mt = 0, mw = fw, neg = 0, fneg = -1;
+    if (k > 0) {
+      mn = A.slack_min[i]; mt = A.min_tick[i]; mw = A.min_which[i]; neg = A.neg_ticks[i]; fneg = A.first_neg[i];
+      if (mn == mn) {                                               // a NaN minimum stays: the first NaN tick, no code
+        if (fs != fs) { mn = fs; mt = k; mw = -1; }
+        else if (fs < mn) { mn = fs; mt = k; mw = fw; }              // strictly smaller: the FIRST tick of the minimum
+      }
+    }
+    if (fs < 0.0) { neg += 1; if (fneg < 0) fneg = k; }             // (a NaN tick is not counted)
+    A.slack_min[i] = mn; A.min_tick[i] = mt; A.min_which[i] = mw; A.neg_ticks[i] = neg; A.first_neg[i] = fneg;
+    A.slack_final[i] = fs;
+    if (A.trace) A.trace[i] = fs;
+  }
+}
+
+// One wavefront per group: lane l takes instances l, l + 64, ... of the group in that order, then a butterfly over the 64 lanes. The
+// shape of the reduction depends on M alone, so two runs give the same bits. A NaN slack_min in the group gives a NaN group_min.
+__global__ void __launch_bounds__(64) wbc_slack_groups_kernel(const SlackGroupArgs A) {
+  const int g = blockIdx.x, lane = threadIdx.x;
+  if (g >= A.G) return;
+  const size_t base = (size_t)g * A.M, nb = (size_t)A.G * A.M;
+#pragma unroll 1
+  for (int j = 0; j < A.n_w; ++j) {
+    const double* sm = A.slack_min + j * nb + base;
+    const int32_t* ng = A.neg_ticks + j * nb + base;
+    double mn = __longlong_as_double(0x7FF0000000000000ll);
+    int nan = 0, nneg = 0;
+#pragma unroll 1
+    for (int i = lane; i < A.M; i += 64) {
+      const double v = sm[i];
+      nan |= (v != v) ? 1 : 0;
+      mn = fmin(mn, v);
+      nneg += ng[i] > 0;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+      mn = fmin(mn, __shfl_xor(mn, off, 64));
+      nan |= __shfl_xor(nan, off, 64);
+      nneg += __shfl_xor(nneg, off, 64);
+    }
+    if (lane == 0) {
+      if (A.group_min) A.group_min[(size_t)j * A.G + g] = nan ? __longlong_as_double(0x7FF8000000000000ll) : mn;
+      if (A.group_neg_instances) A.group_neg_instances[(size_t)j * A.G + g] = nneg;
+    }
+  }
+}
+
+static int slack_launched() {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : (int)e;
+}
+
+int launch_slack(const SlackArgs& a, void* stream) {
+  const dim3 grid((a.B + 3) / 4), block(64);
+  if (a.rot) hipLaunchKernelGGL(wbc_slack_kernel<true>, grid, block, 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
+  else hipLaunchKernelGGL(wbc_slack_kernel<false>, grid, block, 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans);
+  return slack_launched();
+}
+
+int launch_slack_groups(const SlackGroupArgs& a, void* stream) {
+  hipLaunchKernelGGL(wbc_slack_groups_kernel, dim3(a.G), dim3(64), 0, (hipStream_t)stream, a);
+  return slack_launched();
+}
+
+}  // namespace wbc

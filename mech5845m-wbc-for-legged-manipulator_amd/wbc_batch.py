@@ -465,6 +465,57 @@ class WbcBatch:
             raise capi.WbcError("%s: %r is neither 'trunk' nor an end effector index 0..%d" % (what, t, capi.NEE - 1))
         return int(t)
 
+    _SLACK_FAMILIES = {"com": capi.SLACK_COM, "trunk_z": capi.SLACK_TRUNK_Z, "trunk_ang": capi.SLACK_TRUNK_ANG, "joint": capi.SLACK_JOINT}
+    _WATCH_ROWS = (("slack_min", np.float64), ("slack_final", np.float64), ("slack_min_tick", np.int32), ("slack_min_which", np.int32),
+                   ("neg_ticks", np.int32), ("first_neg_tick", np.int32))
+    _WATCH_GROUPS = (("group_min", np.float64), ("group_neg_instances", np.int32))
+
+    @classmethod
+    def _slack_family(cls, f):
+        if isinstance(f, str):
+            if f not in cls._SLACK_FAMILIES:
+                raise capi.WbcError("watch: %r is none of %s" % (f, ", ".join(cls._SLACK_FAMILIES)))
+            return cls._SLACK_FAMILIES[f]
+        if isinstance(f, bool) or not isinstance(f, (int, np.integer)) or not 0 <= int(f) < capi.N_SLACK:
+            raise capi.WbcError("watch: %r is neither a family name (%s) nor an index 0..%d" % (f, ", ".join(cls._SLACK_FAMILIES), capi.N_SLACK - 1))
+        return int(f)
+
+    def state_slack(self, q, trunk_box_center=None, model_id=None, want_components=False):
+        """Slack of the reference's constraint quantities at q [B, 27] (wbc_state_slack, include/wbc.h; restated in numpy by
+        wbc_workload.state_slack): dict(slack [B, 4] float64, which [B, 4] int32[, components [B, 12]]), families in the order CoM box,
+        trunk z, trunk angles, joint range; >= 0 inside, < 0 outside, evaluated whether or not the configuration enforces the constraint.
+        trunk_box_center [B, 4] (None: the two trunk families come back NaN / -1)."""
+        keep = []
+        mem = _mem_of([q, trunk_box_center, model_id])
+        B = self._batch_of(q)
+        out = dict(slack=self._alloc(q, (B, capi.N_SLACK)), which=self._alloc(q, (B, capi.N_SLACK), np.int32))
+        if want_components:
+            out["components"] = self._alloc(q, (B, capi.N_SLACK_COMPONENTS))
+        o = capi.WbcSlackOut()
+        for k, v in out.items():
+            setattr(o, k, self._p(v, np.int32 if k == "which" else np.float64, keep))
+        f = np.float64
+        capi.check(self.lib.wbc_state_slack(self._h, B, self._p(q, f, keep), self._p(trunk_box_center, f, keep, B, 4, "trunk_box_center"),
+                                            self._p(model_id, np.int32, keep, B, 1, "model_id"), mem, C.byref(o), self._stream(mem)), self.lib)
+        return out
+
+    def rollout_watch(self, inputs, dt, ticks, watch=("com", "trunk_z", "trunk_ang", "joint"), tracks=None, score=(), group_size=0,
+                      want_trace=False, mode=capi.ROLLOUT_RUNNING, task_params=None, trunk_target_step=None, imu=None,
+                      ee_target_step=None, hold_ticks=0):
+        """rollout_tracks (with tracks) or rollout (tracks=None: ee_target_step and hold_ticks as there) with the slack families in `watch`
+        ("com", "trunk_z", "trunk_ang", "joint" or 0..3) evaluated after every tick on the state the tick left (wbc_rollout_watch,
+        include/wbc.h). Returns that call's dict plus, rows in increasing family order, slack_min, slack_final [n_w, B], slack_min_tick,
+        slack_min_which, neg_ticks, first_neg_tick [n_w, B] int32, with want_trace slack_trace [ticks + hold_ticks, n_w, B], and with
+        group_size = M > 0 slack_group_min, slack_group_neg_instances [n_w, B / M] — all reduced on the device
+        (wbc_workload.watch_summary restates the reduction over ticks). An empty `watch` is the call without a watch."""
+        fams = sorted({self._slack_family(f_) for f_ in watch})
+        if len(fams) != len(list(watch)):
+            raise capi.WbcError("watch: a family is listed twice")
+        if tracks is None and len(list(score)):
+            raise capi.WbcError("score: needs tracks")
+        return self._rollout_tracks(inputs, dt, ticks, tracks, score, group_size, want_trace, mode, task_params, trunk_target_step, imu,
+                                    fams, ee_target_step, hold_ticks)
+
     def rollout_tracks(self, inputs, dt, ticks, tracks, score=(), group_size=0, want_trace=False, mode=capi.ROLLOUT_RUNNING,
                        task_params=None, trunk_target_step=None, imu=None):
         """`ticks` closed-loop ticks with several targets following per-instance tracks (wbc_rollout_tracks, include/wbc.h). tracks: a list of
@@ -476,11 +527,17 @@ class WbcBatch:
         err_sq_sum, err_max, err_final, err_max_tick [n_scored, B] (frames in increasing index order, the trunk last), first_bad_tick,
         bad_ticks [B], with want_trace trace [ticks, n_scored, B, 3], and with group_size = M > 0 group_rms, group_err_max
         [n_scored, B / M], group_worst_status, group_bad_instances [B / M] — all reduced on the device."""
+        return self._rollout_tracks(inputs, dt, ticks, tracks, score, group_size, want_trace, mode, task_params, trunk_target_step, imu)
+
+    def _rollout_tracks(self, inputs, dt, ticks, tracks, score, group_size, want_trace, mode, task_params, trunk_target_step, imu,
+                        watch=None, ee_target_step=None, hold_ticks=0):
+        """the body of rollout_tracks and rollout_watch. watch: None (wbc_rollout_tracks) or the sorted family indices (wbc_rollout_watch;
+        tracks may then be None, and ee_target_step / hold_ticks are passed on)"""
         keep = []
-        tracks = list(tracks)
-        if not 1 <= len(tracks) <= capi.MAX_TRACKS:
+        tracks = [] if (tracks is None and watch is not None) else list(tracks)
+        if not (0 if watch is not None else 1) <= len(tracks) <= capi.MAX_TRACKS:
             raise capi.WbcError("tracks: %d given, want 1..%d" % (len(tracks), capi.MAX_TRACKS))
-        arrays = []
+        arrays = [ee_target_step]
         for i, t in enumerate(tracks):
             if not isinstance(t, dict) or set(t) - set(self._TRACK_KEYS) or "target" not in t or "points" not in t:
                 raise capi.WbcError("tracks[%d]: want a dict with target, points and optionally kind, tangents, n_points, du" % i)
@@ -536,17 +593,20 @@ class WbcBatch:
         need_trunk = capi.TARGET_TRUNK in seen or capi.TARGET_TRUNK in frames
         if need_trunk and (inputs.get("trunk_target") is None or inputs.get("prev_trunk_target") is None):
             raise capi.WbcError("a trunk track or a scored trunk needs the inputs trunk_target and prev_trunk_target")
-        K, ns = int(ticks), len(frames)
+        K, ns, H = int(ticks), len(frames), int(hold_ticks)
+        if H < 0:
+            raise capi.WbcError("hold_ticks = %d, want >= 0" % H)
         out = dict(q=self._alloc(q, (B, NQS)), qdot=self._alloc(q, (B, NV)), ee_target=self._alloc(q, (B, 5, 3)),
                    status=self._alloc(q, (B,), np.int32), iters=self._alloc(q, (B,), np.int32))
-        if inputs.get("trunk_target") is not None:
+        if inputs.get("trunk_target") is not None and tracks:
             out["trunk_target"] = self._alloc(q, (B, 3))
             tk.trunk_target_final = P(out["trunk_target"], f, keep)
         if want_trace:
-            out["grip_trace"] = self._alloc(q, (K, B, 3))
+            out["grip_trace"] = self._alloc(q, (K + H, B, 3))
         r = capi.WbcRollout()
-        r.ticks, r.mode, r.hold_ticks = K, int(mode), 0
+        r.ticks, r.mode, r.hold_ticks = K, int(mode), H
         r.trunk_target_step, r.imu = P(trunk_target_step, f, keep, B, 3, "trunk_target_step"), P(imu, f, keep, B, 4, "imu")
+        r.ee_target_step = P(ee_target_step, f, keep, B, 15, "ee_target_step")
         r.q_final, r.qdot_last, r.ee_target_final = P(out["q"], f, keep), P(out["qdot"], f, keep), P(out["ee_target"], f, keep)
         r.status_max, r.iters_sum = P(out["status"], np.int32, keep), P(out["iters"], np.int32, keep)
         if want_trace:
@@ -572,8 +632,30 @@ class WbcBatch:
                     setattr(sc, name, P(out[name], dtypes[name], keep))
         tin = self._tick_in(inputs, keep, B)
         tp = _task_params(task_params, B, keep, self.device_id)
-        capi.check(self.lib.wbc_rollout_tracks(self._h, B, C.byref(tin), tp, float(dt), C.byref(r), C.byref(tk),
-                                               C.byref(sc) if sc is not None else None, mem, self._stream(mem)), self.lib)
+        if watch is None:
+            capi.check(self.lib.wbc_rollout_tracks(self._h, B, C.byref(tin), tp, float(dt), C.byref(r), C.byref(tk),
+                                                   C.byref(sc) if sc is not None else None, mem, self._stream(mem)), self.lib)
+            return out
+        wt = None
+        if watch:
+            wt = capi.WbcSlackWatch()
+            wt.group_size = M
+            nw = len(watch)
+            for fam in watch:
+                wt.mask |= 1 << fam
+            for name, dtype in self._WATCH_ROWS:
+                out[name] = self._alloc(q, (nw, B), dtype)
+                setattr(wt, name, P(out[name], dtype, keep))
+            if want_trace:
+                out["slack_trace"] = self._alloc(q, (K + H, nw, B))
+                wt.trace = P(out["slack_trace"], f, keep)
+            if M > 0:
+                for name, dtype in self._WATCH_GROUPS:
+                    out["slack_" + name] = self._alloc(q, (nw, B // M), dtype)
+                    setattr(wt, name, P(out["slack_" + name], dtype, keep))
+        capi.check(self.lib.wbc_rollout_watch(self._h, B, C.byref(tin), tp, float(dt), C.byref(r), C.byref(tk) if tracks else None,
+                                              C.byref(sc) if sc is not None else None, C.byref(wt) if wt is not None else None, mem,
+                                              self._stream(mem)), self.lib)
         return out
 
     def integrate(self, q, v, dt, model_id=None):

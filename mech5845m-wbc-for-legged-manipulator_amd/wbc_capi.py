@@ -117,6 +117,21 @@ class WbcTrackScores(C.Structure):
         "group_worst_status", "group_bad_instances")]
 
 
+# wbc_state_slack / wbc_rollout_watch: slack of the CoM box, the trunk box (z, angles) and the joint range (include/wbc.h)
+N_SLACK, N_SLACK_COMPONENTS = 4, 12
+SLACK_COM, SLACK_TRUNK_Z, SLACK_TRUNK_ANG, SLACK_JOINT = 0, 1, 2, 3
+
+
+class WbcSlackOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("slack", "which", "components")]
+
+
+class WbcSlackWatch(C.Structure):
+    _fields_ = [("mask", C.c_int32), ("group_size", C.c_int32)] + [(n, C.c_void_p) for n in (
+        "slack_min", "slack_final", "slack_min_tick", "slack_min_which", "neg_ticks", "first_neg_tick", "trace", "group_min",
+        "group_neg_instances")]
+
+
 class WbcFkOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("oMi", "oMf", "J", "com", "Jcom")]
 
@@ -159,6 +174,9 @@ SIGNATURES = {
                               C.POINTER(WbcRolloutSummary), _i, _vp]),
     "wbc_rollout_tracks": (_i, [_vp, _i, C.POINTER(WbcTickIn), _vp, _d, C.POINTER(WbcRollout), C.POINTER(WbcTracks),
                                 C.POINTER(WbcTrackScores), _i, _vp]),
+    "wbc_state_slack": (_i, [_vp, _i, _vp, _vp, _vp, _i, C.POINTER(WbcSlackOut), _vp]),
+    "wbc_rollout_watch": (_i, [_vp, _i, C.POINTER(WbcTickIn), _vp, _d, C.POINTER(WbcRollout), C.POINTER(WbcTracks),
+                               C.POINTER(WbcTrackScores), C.POINTER(WbcSlackWatch), _i, _vp]),
     "wbc_integrate": (_i, [_vp, _i, _vp, _vp, _vp, _d, _i, _vp, _vp]),
     "wbc_batch_set_option": (_i, [_vp, C.c_char_p, _i]),
     "wbc_batch_get_stat": (_i, [_vp, C.c_char_p, _vp, C.POINTER(C.c_int64)]),

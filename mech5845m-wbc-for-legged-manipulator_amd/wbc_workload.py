@@ -189,3 +189,89 @@ def track_targets(points, n_points, du, k, kind="linear", tangents=None):
     last = t >= n - 1
     out[last] = points[last, n[last] - 1]
     return out
+
+
+# ---- constraint slack (wbc_state_slack / wbc_rollout_watch, include/wbc.h): the four families restated in numpy
+def slack_joint_dofs(model, cfg):
+    """(d, i) of every velocity DoF 6 <= d < cfg.lock_from of the model with the q index i of its own joint"""
+    q_of = {j["idx_v"]: j["idx_q"] for j in model.data["joints"][2:model.njoints]}
+    return [(d, q_of[d]) for d in range(6, min(int(cfg.lock_from), model.nv)) if d in q_of]
+
+
+def state_slack(model, cfg, q, trunk_box_center, fk):
+    """wbc_state_slack restated for B instances of ONE model: q [B, 27], trunk_box_center [B, 4] or None, fk a callable with
+    fk(q) -> oMf [B, nframes, 12] and fk.com(q) -> [B, 3] (as wbc_workload.make_tick_inputs takes one). Returns dict(slack [B, 4],
+    which [B, 4] int32, components [B, 12], joint_components [B, 2 n], joint_codes [2 n]): slack >= 0 inside, < 0 outside; families CoM box
+    (RR / FL foot positions against data.com[0], x and y), trunk z box, trunk angle box (angles by the tick kernels' atan2 formula), joint range
+    (the model's own q_lo / q_hi of each DoF's own joint, 6 <= d < cfg.lock_from). `which`: the code of the smallest component, the lowest
+    code on a tie. A row with a non-finite q (or, families 1 and 2, box centre) gives NaN and -1."""
+    q = np.array(q, dtype=np.float64).reshape(-1, capi.Q_STRIDE)
+    B = q.shape[0]
+    rowbad = ~np.isfinite(q[:, :model.nq]).all(axis=1)
+    if rowbad.any():
+        neutral = np.zeros(capi.Q_STRIDE)
+        neutral[6] = 1.0
+        q[rowbad] = neutral                                               # (the kinematics see a valid pose; the row is NaN below)
+    oMf, com = fk(q), fk.com(q)
+    pos = oMf[:, :, 9:12]
+    pFL, pRR = pos[:, capi.FR_EE0 + 1], pos[:, capi.FR_EE0 + 2]
+    comp = np.full((B, capi.N_SLACK_COMPONENTS), np.nan)
+    for r in range(2):
+        comp[:, 2 * r] = -(pRR[:, r] - com[:, r])
+        comp[:, 2 * r + 1] = pFL[:, r] - com[:, r]
+    bad1 = bad2 = np.ones(B, dtype=bool)
+    if trunk_box_center is not None:
+        c = np.asarray(trunk_box_center, dtype=np.float64).reshape(B, 4)
+        bad1, bad2 = ~np.isfinite(c[:, 0]), ~np.isfinite(c[:, 1:]).all(axis=1)
+        R = oMf[:, capi.FR_TRUNK, 0:9]
+        e = np.stack([np.arctan2(R[:, 7], R[:, 8]), np.arctan2(-R[:, 6], np.sqrt(R[:, 7] * R[:, 7] + R[:, 8] * R[:, 8])),
+                      np.arctan2(R[:, 3], R[:, 0])], axis=1)
+        with np.errstate(invalid="ignore"):
+            z, v = pos[:, capi.FR_TRUNK, 2], c[:, 0] * cfg.trunk_box_z_frac
+            comp[:, 4] = -((c[:, 0] - v) - z)
+            comp[:, 5] = (c[:, 0] + v) - z
+            for a in range(3):
+                comp[:, 6 + 2 * a] = -((c[:, 1 + a] - cfg.trunk_box_ang) - e[:, a])
+                comp[:, 7 + 2 * a] = (c[:, 1 + a] + cfg.trunk_box_ang) - e[:, a]
+    bad1, bad2 = bad1 | rowbad, bad2 | rowbad
+    dofs = slack_joint_dofs(model, cfg)
+    jcomp = np.zeros((B, 2 * len(dofs)))
+    jcodes = np.zeros(2 * len(dofs), dtype=np.int32)
+    for n, (d, i) in enumerate(dofs):
+        jcomp[:, 2 * n], jcomp[:, 2 * n + 1] = q[:, i] - model.q_lo[i], model.q_hi[i] - q[:, i]
+        jcodes[2 * n], jcodes[2 * n + 1] = 2 * d, 2 * d + 1
+    slack, which = np.full((B, capi.N_SLACK), np.nan), np.full((B, capi.N_SLACK), -1, dtype=np.int32)
+    for f, (lo, hi, bad) in enumerate(((0, 4, rowbad), (4, 6, bad1), (6, 12, bad2))):
+        comp[bad, lo:hi] = np.nan
+        part = np.where(bad[:, None], 0.0, comp[:, lo:hi])
+        k = part.argmin(axis=1)                                           # the first of equal minima: the lowest code
+        slack[:, f] = np.where(bad, np.nan, part[np.arange(B), k])
+        which[:, f] = np.where(bad, -1, k)
+    if dofs:
+        k = jcomp.argmin(axis=1)
+        slack[:, 3], which[:, 3] = jcomp[np.arange(B), k], jcodes[k]
+    else:
+        slack[:, 3] = np.inf
+    slack[rowbad, 3], which[rowbad, 3] = np.nan, -1
+    jcomp[rowbad] = np.nan
+    return dict(slack=slack, which=which, components=comp, joint_components=jcomp, joint_codes=jcodes)
+
+
+def watch_summary(trace, which=None):
+    """wbc_rollout_watch's reduction over ticks restated: trace [K, ...] per-tick slacks (any trailing shape) -> dict(slack_min,
+    slack_min_tick (the FIRST tick of the minimum), slack_final, neg_ticks (ticks with slack < 0), first_neg_tick (-1: none)[,
+    slack_min_which: with `which` [K, ...], the per-tick codes]). A NaN tick makes the minimum NaN for good: slack_min_tick is the first such
+    tick, the code -1, and neg_ticks does not count it."""
+    t = np.asarray(trace, dtype=np.float64)
+    nan = np.isnan(t)
+    anynan = nan.any(axis=0)
+    filled = np.where(nan, np.inf, t)
+    tick = np.where(anynan, nan.argmax(axis=0), filled.argmin(axis=0)).astype(np.int32)
+    mn = np.where(anynan, np.nan, np.take_along_axis(filled, tick[None].astype(np.int64), axis=0)[0])
+    neg = t < 0
+    out = dict(slack_min=mn, slack_min_tick=tick, slack_final=t[-1].copy(), neg_ticks=neg.sum(axis=0).astype(np.int32),
+               first_neg_tick=np.where(neg.any(axis=0), neg.argmax(axis=0), -1).astype(np.int32))
+    if which is not None:
+        w = np.take_along_axis(np.asarray(which), tick[None].astype(np.int64), axis=0)[0]
+        out["slack_min_which"] = np.where(anynan, -1, w).astype(np.int32)
+    return out

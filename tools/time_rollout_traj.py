@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Closed-loop ticks/s of wbc_rollout_traj (two milestones = one segment, summary on, no trace) and of wbc_rollout_tracks with two tracks
 (the trunk on a four-milestone HERMITE spline, the gripper on the same LINEAR segment, both scored, no trace) against wbc_rollout on the
-same inputs: what the per-tick trajectory kernel costs. Same process, same handle, interleaved rounds, HIP events around each call.
+same inputs: what the per-tick trajectory kernel costs; and of wbc_rollout_watch, the same two-track call with all four slack families watched
+(no trace): what the per-tick slack kernel costs. Same process, same handle, interleaved rounds, HIP events around each call.
     python3 tools/time_rollout_traj.py [B] [ticks] [rounds] [only]      only: run the calls whose label contains one of these comma-separated
                                                                         words (e.g. tracks, for a profiler run of that leg alone)"""
 import json
@@ -51,6 +52,8 @@ calls = {
     "wbc_rollout_traj (summary, no trace)": lambda: bt.rollout_traj(dev, DT, TICKS, pts_d, du=1.0 / TICKS, imu=imu),
     "wbc_rollout_tracks (trunk HERMITE + gripper LINEAR, both scored, no trace)":
         lambda: bt.rollout_tracks(dev, DT, TICKS, two_tracks, score=("trunk", 4), imu=imu),
+    "wbc_rollout_watch (the two-track call, four slack families watched, no trace)":
+        lambda: bt.rollout_watch(dev, DT, TICKS, tracks=two_tracks, score=("trunk", 4), imu=imu),
 }
 calls = {k: v for k, v in calls.items() if any(w in k for w in ONLY.split(","))}
 ms = {k: [] for k in calls}
@@ -69,11 +72,15 @@ for label, t in ms.items():
     print(json.dumps({"call": label, "B": B, "ticks": TICKS, "rounds": ROUNDS, "ms_median": round(med, 3), "ms_min": round(min(t), 3),
                       "ms_max": round(max(t), 3), "M_closed_loop_ticks_per_s": round(B * TICKS / med / 1e3, 2),
                       "last_path": bt.stat("last_path")}))
-if len(calls) == 3:
-    a, b, c = (float(np.median(ms[k])) for k in calls)
+if len(calls) == 4:
+    a, b, c, w = (float(np.median(ms[k])) for k in calls)
     print("# wbc_rollout_traj takes %+.2f %% against wbc_rollout (%.1f us per tick more)" % (100.0 * (b / a - 1.0), 1e3 * (b - a) / TICKS))
     print("# wbc_rollout_tracks (two tracks) takes %+.2f %% against wbc_rollout (%.1f us per tick more)" % (100.0 * (c / a - 1.0), 1e3 * (c - a) / TICKS))
-    old, new, _ = (last[k] for k in calls)
+    print("# wbc_rollout_watch (two tracks, four families) takes %+.2f %% against wbc_rollout_tracks (%.1f us per tick more)" % (100.0 * (w / c - 1.0), 1e3 * (w - c) / TICKS))
+    old, new, tr, wa = (last[k] for k in calls)
+    print("# watched against unwatched: q identical %s; slack minima %s, instances with a negative tick %s" % (
+        bool((tr["q"] == wa["q"]).all().item()), [round(float(v), 4) for v in wa["slack_min"].min(dim=1).values.tolist()],
+        (wa["neg_ticks"] > 0).sum(dim=1).tolist()))
     same = bool((old["status"] == new["status"]).all().item())
     print("# same inputs: status identical %s, q max-abs difference %.3e" % (same, float((old["q"] - new["q"]).abs().max().item())))
 bt.close()
