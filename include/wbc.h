@@ -583,6 +583,11 @@ int wbc_rollout_watch(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskPar
  *                          stacks are well conditioned (1e-8 .. 1e-10 without): the packed orth / box kernels and the orthonormal
  *                          presolve; and the one-instance compact kernel (path 1: no room at 168 VGPRs / 13 KB LDS) — with refine > 0
  *                          what it would take runs on the general kernel instead (refine = 0 brings it back).
+ *   "sim3p_fixd"       [1] a handle with ONE model whose sim3 plan has the a1_wx200 dimensions (26 DoF, 27 coordinates, 11 reduced unknowns,
+ *                          4 stance feet eliminated, 4 kept rows) runs a call without a model_id array on the packed sim3 kernel's FIXD form:
+ *                          those dimensions are compile-time constants there (statistic "last_tick_fixd"). Every other handle and call
+ *                          runs the form that reads them from the plan; 0: always that form (A/B timing, tests). Results are
+ *                          bit-identical either way.
  *   "packed_min_batch" [1] the packed sim3 kernel takes batches from this many instances on. 1: it is the fastest path of the sim3
  *                          family at EVERY batch size (13.6 us at B = 1 against 19 us on either one-instance kernel, 41 vs 53-55 us at
  *                          1024: profiles/r04_small_batch_c3.txt).
@@ -597,6 +602,8 @@ int wbc_batch_set_option(WbcBatch* b, const char* name, int value);
  * compact sim3 — four instances per wavefront, one kernel —, 3 packed orth kernel, 4 packed box kernel), "last_orth" (1: that tick ran with the
  * orthonormal contact presolve, option "presolve_orth": the general kernel's ORTH variant or the packed orth kernel),
  * "last_qp_path" (problems per wavefront of the last wbc_qp_solve / wbc_qp_solve_ls call: 4, 2 or 1),
+ * "last_tick_fixd" (1: the last tick ran the packed sim3 kernel's FIXD form, option "sim3p_fixd" — the same row of the variant table, same
+ * "last_tick_variant"; 0: the form with the plan's dimensions read at run time, or another kernel),
  * "last_update_packed" (1: the last state update ran on the packed kernel), "last_posture_par" (1 / 2: the last MANI / HYBRID posture target
  * ran on the parallel posture kernel, one / three instances per wavefront), "deferred_last" (instances the last tick's kernel could not reduce itself: redone in the packed kernels'
  * tail or left to the one-instance kernel's second pass; waits for `stream`), "pivoted_last" (instances that took the pivoted

@@ -84,6 +84,9 @@ struct WbcBatch {
   int last_orth;         // the last general-kernel tick ran the variant with the orthonormal contact presolve
   int last_qp_path;      // problems per wavefront of the last wbc_qp_solve / wbc_qp_solve_ls: 1 (wbc_qp_kernel), 2 or 4 (wbc_qp_packed_kernel)
   long long last_tick_variant, last_qp_variant;   // variant_key(...) of the row the last tick / assemble / fk launch and the last stand-alone QP launch resolved (-1: none yet)
+  int sim3p_fixd;        // option [1]: the packed sim3 kernel's FIXD form where the handle qualifies (fixd_dims)
+  bool fixd_dims[WBC_MAX_MODELS];   // wbc_batch_configure: the model's plan has exactly the SIM3P_FIXD_* dimensions
+  int last_tick_fixd;    // the last tick ran a FIXD instantiation of the packed sim3 kernel
   int last_path;         // TickPath of the last wbc_tick / wbc_rollout tick: 0 general, 1 sim3 (+ deferred pass), 2 packed sim3, 3 packed orth, 4 packed box
   int max_nj, max_nf;    // FK output strides: the largest model's joint / frame counts
   int rot;               // a model of the handle has a rotated joint placement: the packed kernels run their ROT instantiations
@@ -204,7 +207,7 @@ extern "C" int wbc_batch_create(const WbcModel* const* models, int n_models, int
   WbcBatch* b = new (std::nothrow) WbcBatch;
   if (!b) return fail(WBC_E_ARG, "out of memory");
   memset(b, 0, sizeof *b);
-  b->device_id = device_id; b->n_models = n_models; b->max_batch = max_batch; b->presolve = 1; b->presolve_orth = 1; b->packed_update = 1; b->sim3_kernel = 1; b->sing_tol = 1e-7; b->wave_order = 1;
+  b->device_id = device_id; b->n_models = n_models; b->max_batch = max_batch; b->presolve = 1; b->presolve_orth = 1; b->packed_update = 1; b->sim3_kernel = 1; b->sing_tol = 1e-7; b->wave_order = 1; b->sim3p_fixd = 1;
   b->last_tick_variant = b->last_qp_variant = -1;
   b->jtj_mfma = -1; b->refine = 1; b->packed_min_batch = WBC_SIM3P_MIN_BATCH; b->warm_start = 0; b->packed_kernel = 1; b->packed_orth = 1; b->packed_box = 1; b->posture_par = 1;
   std::vector<DevModel> dm(n_models);
@@ -657,6 +660,7 @@ extern "C" int wbc_batch_configure(WbcBatch* b, int mi, const WbcConfig* cfg) {
   DevPlan plan;
   build_plan(b->models[mi]->dev, *cfg, p, &plan);
   b->plan_host[mi] = plan;
+  b->fixd_dims[mi] = b->models[mi]->dev.nv == SIM3P_FIXD_NV && b->models[mi]->dev.nq == SIM3P_FIXD_NQ && plan.n_red == SIM3P_FIXD_N && plan.nelim == SIM3P_FIXD_NELIM && plan.p_keep == SIM3P_FIXD_PKEEP;
   HIP_TRY(hipMemcpy(b->d_plans + mi, &plan, sizeof plan, hipMemcpyHostToDevice));
   b->worder_reset = 1;                     // the next packed tick runs in the identity order (cleared on that tick's stream)
   return WBC_OK;
@@ -676,6 +680,7 @@ extern "C" int wbc_batch_set_option(WbcBatch* b, const char* name, int value) {
   if (!strcmp(name, "sim3_kernel")) { b->sim3_kernel = value; return WBC_OK; }
   if (!strcmp(name, "packed_kernel")) { b->packed_kernel = value; return WBC_OK; }
   if (!strcmp(name, "wave_order")) { b->wave_order = value < 0 ? 0 : (value > 2 ? 2 : value); return WBC_OK; }
+  if (!strcmp(name, "sim3p_fixd")) { b->sim3p_fixd = value != 0; return WBC_OK; }
   if (!strcmp(name, "packed_min_batch")) { b->packed_min_batch = value < 1 ? 1 : value; return WBC_OK; }
   if (!strcmp(name, "packed_orth")) { b->packed_orth = value; return WBC_OK; }
   if (!strcmp(name, "packed_box")) { b->packed_box = value; return WBC_OK; }
@@ -702,6 +707,7 @@ extern "C" int wbc_batch_get_stat(WbcBatch* b, const char* name, void* stream, i
   if (!strcmp(name, "last_path")) { *out = b->last_path; return WBC_OK; }
   if (!strcmp(name, "last_qp_path")) { *out = b->last_qp_path; return WBC_OK; }
   if (!strcmp(name, "last_tick_variant")) { *out = b->last_tick_variant; return WBC_OK; }
+  if (!strcmp(name, "last_tick_fixd")) { *out = b->last_path == TICK_SIM3P ? b->last_tick_fixd : 0; return WBC_OK; }
   if (!strcmp(name, "last_qp_variant")) { *out = b->last_qp_variant; return WBC_OK; }
   if (!strcmp(name, "last_update_packed")) { *out = b->last_update_packed; return WBC_OK; }
   if (!strcmp(name, "last_posture_par")) { *out = b->last_posture_par; return WBC_OK; }
@@ -1037,7 +1043,8 @@ static int launch_tick_auto(WbcBatch* b, KernelArgs& a, int B, void* stream, con
   if (rc) return rc;
   switch (path) {   // (the packed kernels: ONE kernel per tick, what a packed kernel cannot reduce its own wave redoes on the general path)
     case TICK_GENERAL: return launch_rc(launch_tick(a, MODE_TICK, grid_tick(b, B), stream, tp, &b->last_tick_variant), "tick");
-    case TICK_SIM3P: return launch_rc(launch_tick_sim3p(a, stream, tp, &b->last_tick_variant), "packed sim3 tick");
+    case TICK_SIM3P:   // (FIXD: one model, its plan of the fixed dimensions; the launcher adds: no model_id array, a row that has the form)
+      return launch_rc(launch_tick_sim3p(a, stream, tp, &b->last_tick_variant, b->sim3p_fixd && b->n_models == 1 && b->fixd_dims[0], &b->last_tick_fixd), "packed sim3 tick");
     case TICK_ORTHP: return launch_rc(launch_tick_orthp(a, stream, b->plan_host[0].q_ok == 2, tp, &b->last_tick_variant), "packed orth tick");
     case TICK_BOXP: return launch_rc(launch_tick_boxp(a, stream, tp, &b->last_tick_variant), "packed box tick");
     case TICK_SIM3: break;   // two kernels, below: the compact one, then the general path over the instances it deferred (singular leg block)

@@ -2607,7 +2607,7 @@ static int check_launch(const char* what) {
 // A launcher reports the key it launched through its last parameter (`key_out`, may be null): the statistics "last_tick_variant" / "last_qp_variant".
 // ------------------------------------------------------------------------------------------------
 #ifndef WBC_NPARTS
-#define WBC_NPARTS 9      // (the most WBC_PART_IS_ below can tell apart)
+#define WBC_NPARTS 12     // (the most WBC_PART_IS_ below can tell apart)
 #endif
 #define WBC_CAT_(a, b) a##b
 #define WBC_CAT(a, b) WBC_CAT_(a, b)
@@ -2622,8 +2622,11 @@ static int check_launch(const char* what) {
 #define WBC_PART_IS_6_6 ~, 1
 #define WBC_PART_IS_7_7 ~, 1
 #define WBC_PART_IS_8_8 ~, 1
+#define WBC_PART_IS_9_9 ~, 1
+#define WBC_PART_IS_10_10 ~, 1
+#define WBC_PART_IS_11_11 ~, 1
 #define WBC_PART_IS(p, q) WBC_SECOND(WBC_CAT(WBC_PART_IS_, WBC_CAT(p, WBC_CAT(_, q))), 0)   // 1 where the two numbers are the same token
-#define WBC_VARIANT_ROW(p) static_assert(p >= 0 && p < WBC_NPARTS && p < 9, "variant table: part number outside the family's parts (csrc/Makefile)");
+#define WBC_VARIANT_ROW(p) static_assert(p >= 0 && p < WBC_NPARTS && p < 12, "variant table: part number outside the family's parts (csrc/Makefile)");
 #define WBC_VARIANT_INST(p, ...) WBC_VARIANT_ROW(p) template __global__ void WBC_KERNEL<__VA_ARGS__> WBC_KPARAMS;
 #define WBC_VARIANT_DECL(p, ...) WBC_VARIANT_ROW(p) extern template __global__ void WBC_KERNEL<__VA_ARGS__> WBC_KPARAMS;
 #define WBC_VARIANT_UNIT_1 WBC_VARIANT_INST

@@ -237,11 +237,15 @@ struct UpdateArgs {
   int32_t rot;                         // a model of the handle has a rotated joint placement (wbc_update_packed_kernel<true>)
 };
 
+// The dimensions the packed sim3 kernel's FIXD instantiations are compiled for: the a1_wx200 sim3 plan (DevModel.nv / nq, DevPlan.n_red / nelim /
+// p_keep). wbc_batch_configure compares a plan with them on the host; the kernel never checks.
+constexpr int SIM3P_FIXD_NV = 26, SIM3P_FIXD_NQ = 27, SIM3P_FIXD_N = 11, SIM3P_FIXD_NELIM = 4, SIM3P_FIXD_PKEEP = 4;
+
 // launchers (one per kernel family, wbc_k_*.hip): single-wave workgroups; tick kernels take grid = B, the QP / integrate kernels min(B, resident waves)
 // key_out (may be null): the variant_key(...) of the row the launcher resolved, written before the launch (wbc_common.h, "Kernel variant tables")
 int launch_tick(const KernelArgs& a, int mode, int grid, void* stream, const WbcTaskParams* tp = nullptr, long long* key_out = nullptr);
 int launch_tick_sim3(const KernelArgs& a, int grid, void* stream, long long* key_out = nullptr);   // (no table: key_out = variant_key(WARM, ROT))
-int launch_tick_sim3p(const KernelArgs& a, void* stream, const WbcTaskParams* tp = nullptr, long long* key_out = nullptr);      // packed: four instances per wavefront, grid = ceil(B / 4)
+int launch_tick_sim3p(const KernelArgs& a, void* stream, const WbcTaskParams* tp = nullptr, long long* key_out = nullptr, bool fixd = false, int* fixd_out = nullptr);      // packed: four instances per wavefront, grid = ceil(B / 4)
 int launch_tick_boxp(const KernelArgs& a, void* stream, const WbcTaskParams* tp = nullptr, long long* key_out = nullptr);       // packed box kernel (task problems without constraint rows), grid = ceil(B / 4)
 int launch_tick_orthp(const KernelArgs& a, void* stream, int ineq, const WbcTaskParams* tp = nullptr, long long* key_out = nullptr);      // packed orth kernel (equality-only task problems), grid = ceil(B / 4)
 int orthp_lds_bytes();

@@ -1,4 +1,4 @@
-// wbc_k_sim3p.hip — the packed sim3 kernel wbc_tick_sim3p_kernel<WARM, TRUNK, QCON, ROT, TP>: the benchmark path, four instances per wavefront.
+// wbc_k_sim3p.hip — the packed sim3 kernel wbc_tick_sim3p_kernel<WARM, TRUNK, QCON, ROT, TP, FIXD>: the benchmark path, four instances per wavefront.
 #include "wbc_packed.h"
 
 namespace wbc {
@@ -47,7 +47,13 @@ namespace wbc {
 // TP: per-instance weights and gains (wbc_tick_tp: the kernel's fifth parameter tps [B]): each group reads its instance's row in place of
 // cfgs[mid]'s block and the tail hands the row on; a row that tp_row_bad16 refuses gives its instance WBC_QP_NUMERICAL. Without TP, tps is
 // nullptr and never read.
-template <bool WARM, bool TRUNK = false, bool QCON = false, bool ROT = false, bool TP = false>
+// FIXD: the plan's dimensions nv, nq, n', nelim, p_keep (and with them nl = 3 nelim and p = p_keep + nl) are the compile-time values of the a1_wx200
+// sim3 plan (wbc_device.h SIM3P_FIXD_*) instead of loads from DevModel / DevPlan: the lane guards that compare with them (s < n, s < nl, s < p_keep)
+// become compares with constants, s < p is always true (p = 16 is the row width) and its exec-mask regions go, the G'G loop unrolls (DESIGN.md
+// §3.30). Same operations on the same operands: bit for bit the dynamic variant's results. The launcher takes a FIXD instantiation only for a
+// handle whose single plan has exactly these dimensions and a call without a model_id array (launch_tick_sim3p's `fixd`); the statistic
+// "last_tick_fixd" says which ran. Instantiated for the variants without QCON and ROT. A/B switch: SIM3P_NO_FIXD never selects it.
+template <bool WARM, bool TRUNK = false, bool QCON = false, bool ROT = false, bool TP = false, bool FIXD = false>
 #ifdef SIM3P_NUM_VGPR
 __attribute__((amdgpu_waves_per_eu(SIM3P_NUM_VGPR, SIM3P_NUM_VGPR)))
 #endif
@@ -175,7 +181,8 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
     WSYNC();
     __builtin_amdgcn_sched_barrier(0);    // (the per-lane records below are fetched after this block: live across it they spilled 110 VGPRs)
   }
-  const int nv = M.nv, nq = M.nq, n = P.n_red, nelim = P.nelim, nl = 3 * nelim, p_keep = P.p_keep, p = p_keep + nl;
+  const int nv = FIXD ? SIM3P_FIXD_NV : M.nv, nq = FIXD ? SIM3P_FIXD_NQ : M.nq, n = FIXD ? SIM3P_FIXD_N : P.n_red, nelim = FIXD ? SIM3P_FIXD_NELIM : P.nelim,
+            nl = 3 * nelim, p_keep = FIXD ? SIM3P_FIXD_PKEEP : P.p_keep, p = p_keep + nl;
   const unsigned fl = P.flags;
   const bool c_con_trunk = fl & 2u;
   const int c_task_joint = (fl >> 4) & 7u;
@@ -1283,23 +1290,59 @@ typedef void (*Sim3pKernel) WBC_KPARAMS;
   V(8, true, true, false, true, true)     \
   V(8, false, false, true, true, true)    \
   V(8, true, false, true, true, true)
+// The FIXD instantiations: not rows of their own (the table's census and the "last_tick_variant" key stay those of the five flags) but a second
+// form of the eight rows without QCON and ROT. The part that instantiates it, then WARM, TRUNK, TP. They live in parts of their own (9 .. 11, the
+// benchmark's kernel alone in part 9): a kernel's code depends on what else its unit holds (the inliner's single-caller bonus), and this way
+// every other instantiation compiles to exactly what it was (tools/same_kernels.py, up to the sixth template argument in the names).
+#define SIM3P_FIXD_VARIANTS(V) /* WARM, TRUNK, TP */ \
+  V(9, false, false, false)  \
+  V(10, true, false, false)  \
+  V(10, false, true, false)  \
+  V(10, true, true, false)   \
+  V(11, false, false, true)  \
+  V(11, true, false, true)   \
+  V(11, false, true, true)   \
+  V(11, true, true, true)
+#define SIM3P_FIXD_INST(p, W, T, R) WBC_VARIANT_ROW(p) template __global__ void WBC_KERNEL<W, T, false, false, R, true> WBC_KPARAMS;
+#define SIM3P_FIXD_DECL(p, W, T, R) WBC_VARIANT_ROW(p) extern template __global__ void WBC_KERNEL<W, T, false, false, R, true> WBC_KPARAMS;
+#define SIM3P_FIXD_UNIT_1 SIM3P_FIXD_INST
+#define SIM3P_FIXD_UNIT_0 SIM3P_FIXD_DECL
+#define SIM3P_FIXD_UNIT(p, ...) WBC_CAT(SIM3P_FIXD_UNIT_, WBC_PART_IS(p, WBC_PART))(p, __VA_ARGS__)
+#define SIM3P_FIXD_FIND(p, W, T, R) if (key == variant_key(W, T, false, false, R)) return WBC_KERNEL<W, T, false, false, R, true>;
 #if SIM3P_PART == -1
 SIM3P_VARIANTS(WBC_VARIANT_INST)
+SIM3P_FIXD_VARIANTS(SIM3P_FIXD_INST)
 #else
 SIM3P_VARIANTS(WBC_VARIANT_UNIT)
+SIM3P_FIXD_VARIANTS(SIM3P_FIXD_UNIT)
 #endif
 #if SIM3P_PART <= 0
-static Sim3pKernel sim3p_variant(long long key) {
+static Sim3pKernel sim3p_variant(long long key, bool fixd) {
+#ifndef SIM3P_NO_FIXD
+  if (fixd) { SIM3P_FIXD_VARIANTS(SIM3P_FIXD_FIND) }     // (a row without a FIXD form: its dynamic form)
+#endif
   SIM3P_VARIANTS(WBC_VARIANT_FIND)
   return nullptr;
 }
+static bool sim3p_has_fixd(long long key) {
+#ifndef SIM3P_NO_FIXD
+#define SIM3P_FIXD_HAS(p, W, T, R) if (key == variant_key(W, T, false, false, R)) return true;
+  SIM3P_FIXD_VARIANTS(SIM3P_FIXD_HAS)
+#undef SIM3P_FIXD_HAS
+#endif
+  return false;
+}
 int sim3p_variant_count() { return 0 SIM3P_VARIANTS(WBC_VARIANT_COUNT); }
-int launch_tick_sim3p(const KernelArgs& a, void* stream, const WbcTaskParams* tp, long long* key_out) {
+// fixd: the caller vouches that every instance of the launch runs on ONE plan with the SIM3P_FIXD_* dimensions (wbc_api.hip: one model, no
+// model_id array, the dimensions checked at wbc_batch_configure); fixd_out (may be null): whether a FIXD instantiation was launched
+int launch_tick_sim3p(const KernelArgs& a, void* stream, const WbcTaskParams* tp, long long* key_out, bool fixd, int* fixd_out) {
   const bool warm = a.ws_in || a.ws_out, qcon = a.in.q_con || a.in.posture_u;
   const bool trunk = !qcon && a.in.trunk_target && a.packed_trunk;   // (QCON switches TRUNK off)
   const long long key = variant_key(warm, trunk, qcon, a.rot != 0, tp != nullptr);
   if (key_out) *key_out = key;
-  const Sim3pKernel k = sim3p_variant(key);
+  fixd = fixd && !a.in.model_id && sim3p_has_fixd(key);
+  if (fixd_out) *fixd_out = fixd ? 1 : 0;
+  const Sim3pKernel k = sim3p_variant(key, fixd);
   if (!k) return WBC_E_UNSUPPORTED;
   const uint32_t waves = (uint32_t)((a.B + 3) / 4);
   hipLaunchKernelGGL(k, dim3(waves), dim3(64), 0, (hipStream_t)stream, a, a.models, a.cfgs, a.plans, tp, wo_geom(waves));

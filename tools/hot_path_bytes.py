@@ -23,7 +23,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mech5845m-wbc-for-legged-manipulator_amd", "csrc")
-NPARTS = {"sim3p": 9}
+NPARTS = {"sim3p": 12}
 
 
 def llvm_mc():
