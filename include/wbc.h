@@ -271,6 +271,69 @@ int wbc_qp_solve_ls(WbcBatch* b, int B, int m, int n, int p, const double* A, co
                     double* x, int32_t* status, int32_t* iters, double* H_out, double* g_out,
                     const uint64_t* working_set_in, uint64_t* working_set_out, void* stream);
 
+/* ------------------------------------------------------------------ dual solution, KKT certificate and sensitivities of a solved QP
+ * What qpOASES users read with getDualSolution() / getObjVal(), a certificate of optimality computed from the caller's own data, and the
+ * vector-Jacobian product of the solution — one kernel of its own behind the solve (csrc/wbc_k_cert.hip; no solve kernel takes part).
+ * The problem is wbc_qp_solve's:  min 1/2 x'Hx + g'x  s.t. lb <= x <= ub, Clb <= C x <= Cub,  n <= 26, p <= WBC_MAX_P, C row-major [p][n];
+ * or it is given as (A, b) with m <= WBC_MAX_M rows, H = A'A and g = -A'b. A bound with |value| >= 1e20 is infinite.
+ * Active normals N (k rows), in this order: variables by index, then rows of C by index.
+ *   - a variable with lb == ub, or a row with Clb == Cub, is always active, as an equality;
+ *   - with a working set (format of wbc_qp_solve: word 0 bit i / 32 + i = variable i at its lower / upper bound, word 1 the same for
+ *     the rows): the marked sides; a bit on an equality, on an infinite side, or on both sides at once, is ignored;
+ *   - without one the set is read off x, with v = (x; C x) entry by entry: at the lower side if |v - lo| < 1e-7 max(1, |lo|), else at
+ *     the upper side by the same test.
+ * Duals, in qpOASES' sign convention: grad f(x) = N'y, that is H x + g = y_bounds + C'y_rows; y >= 0 at an active lower side, y <= 0 at
+ *   an active upper side, either sign on an equality, exactly 0 on an inactive entry.
+ * grad f: from (H, g) it is H x + g; from (A, b) it is A'(A x - b) as two products from the unfactored data, never through fl(A'A)
+ *   (the reason option "refine" gives). The objective is 1/2 x'Hx + g'x, in the (A, b) form 1/2 |A x|^2 - b'(A x) (the constant
+ *   1/2 |b|^2 is left out, as in H, g).
+ * Sensitivity, for a caller-given v = dL/dx: with K = [H N'; N 0] solve K (u; w) = (v; 0). Then, e_i being the bound value active
+ *   constraint i sits at:  dL/dg = -u,  dL/de_i = w_i,  dL/dH = -1/2 (u x' + x u'),  dL/dC_j = -w_j x' + y_j u'
+ *   (the host side builds these from the outputs; the gradient of an equality's value belongs to both of its sides).
+ * Method: Cholesky H = L L', Y = L^-1 N' (n x k), Householder QR Y = Q1 R, y = R^-1 Q1' L^-1 grad f, and with z = L^-1 v:
+ *   w = R^-1 Q1' z, u = L^-T (z - Q1 Q1' z). The Schur complement Y'Y is never formed.
+ * cert_status per instance: */
+enum { WBC_CERT_OK = 0         /* the numbers were computed; judging them is the caller's job (no thresholds live in the library)    */,
+       WBC_CERT_UNSOLVED = 1   /* the input status[b] != 0: everything is zero                                                       */,
+       WBC_CERT_DEPENDENT = 2  /* the active normals are dependent: k > n, or a diagonal entry of R with |R_jj| <= 1e-12 x the
+                                  Euclidean norm of column j of Y. kkt[1], objective and n_active are still given; duals, sensitivities
+                                  and kkt[0], [2], [3] are zero                                                                      */,
+       WBC_CERT_NUMERICAL = 3  /* a non-finite input (NaN or +-inf in H, g, A, b, C, x, v; NaN in a bound) or a Cholesky pivot that
+                                  is not positive: everything is zero. Nothing non-finite reaches another instance's outputs         */ };
+typedef struct WbcQpProblem {
+  int32_t n, p, m, pad_;           /* m = 0 with H, g; 1..WBC_MAX_M with A, b                                          */
+  const double* H;                 /* [B][n][n]   \  exactly one pair                                                   */
+  const double* g;                 /* [B][n]      /                                                                     */
+  const double* A;                 /* [B][m][n]   \                                                                     */
+  const double* b;                 /* [B][m]      /                                                                     */
+  const double* C;                 /* [B][p][n]; C, Clb, Cub required when p > 0                                        */
+  const double* lb;                /* [B][n]; lb and ub go together, NULL => no box                                     */
+  const double* ub;
+  const double* Clb;               /* [B][p]                                                                            */
+  const double* Cub;
+  const double* x;                 /* [B][n] the answer to certify (required)                                           */
+  const int32_t* status;           /* [B] the solve's status; NULL => every instance counts as solved                   */
+  const uint64_t* working_set;     /* [B][2] the solve's working_set_out; NULL => the active set is read off x          */
+  const double* v;                 /* [B][n] dL/dx; NULL => no sensitivities                                            */
+} WbcQpProblem;
+typedef struct WbcQpCert {         /* all optional; an output left NULL is not written                                  */
+  double* y_bounds;                /* [B][n]                                                                            */
+  double* y_rows;                  /* [B][p]                                                                            */
+  double* kkt;                     /* [B][4]: [0] |grad f - N'y|_inf; [1] the largest violation of any bound or row, >= 0; [2] the largest
+                                      wrong-signed multiplier magnitude over the inequality actives; [3] max |y_i (v_i - e_i)| over actives */
+  double* objective;               /* [B] getObjVal                                                                     */
+  int32_t* n_active;               /* [B] k                                                                             */
+  double* sens_x;                  /* [B][n] u                                                                          */
+  double* sens_bounds;             /* [B][n] w scattered to the variables' own indices, 0 where inactive                */
+  double* sens_rows;               /* [B][p] w of the rows likewise                                                     */
+  int32_t* cert_status;            /* [B] WBC_CERT_*                                                                    */
+} WbcQpCert;
+/* Works on a QP-only handle. With device pointers the call enqueues exactly one kernel: no allocation, no memset, so it can be captured.
+ * WBC_E_ARG, naming the field: both pairs (H, g and A, b) given, or neither, or half of one; x NULL; n, p or m out of range; C, Clb or
+ * Cub missing with p > 0; lb without ub; sens_x, sens_bounds or sens_rows requested without v. */
+int wbc_qp_certificate(WbcBatch* b, int B, const WbcQpProblem* problem, const WbcQpCert* out, int mem, void* stream);
+int wbc_qp_certificate_sizes(int32_t* sizeof_problem, int32_t* sizeof_cert); /* ctypes layout self-check */
+
 /* replaces qpJointb's "MANI" / "HYBRID" branches (Robot_Wrapper4.py:1220-1260) under the configured task_joint,
  * arm_base_id and posture_literal: u [B][26] = the posture target before scaling (PREV / zeros for the other modes),
  * q_after [B][27] = the configuration the reference's state holds afterwards (optional). wbc_tick / wbc_assemble call

@@ -13,6 +13,8 @@ p x n array, and the solver reads it as p rows of n; ``lb``/``ub
 returned by every ``solveQPHotstart``; misuse of ``solveQPHotstart`` on a bounds-only QP prints and exits.
 Added (the reference drops qpOASES' return codes): ``status`` (0 optimal, 1 iteration cap, 2 infeasible,
 3 numerical) and ``nWSR`` holding the number of working-set changes performed, qpOASES' in/out convention.
+Also qpOASES' ``getDualSolution(yOpt)`` (n + p values, bounds then rows, in its sign convention) and ``getObjVal()``, and the
+attribute ``kkt`` (the four residuals of ``wbc_qp_certificate``, include/wbc.h): computed on demand after a solve by that call.
 """
 import numpy as np
 
@@ -45,6 +47,7 @@ class QP:
         self.status = None
         self.use_mfma = None     # None: the library decides by the row count of A; True / False force the path
         self._ws = None          # the last solve's working set (qpOASES keeps its own between init and hotstart, :45-48, :70)
+        self._last = None        # the last solve's problem, answer and working set, and its certificate once asked for
 
     # H, g are attributes in the reference (computed eagerly with numpy); here the device forms them on demand.
     @property
@@ -90,7 +93,43 @@ class QP:
             self._ws = ws
         self.status = int(st[0])
         self.nWSR = np.array([int(it[0])])
+        self._last = dict(A=A[None], b=b[None], C_=Cr, lb=lb[None], ub=ub[None], Clb=cl, Cub=cu, x=x, status=st, working_set=ws, cert=None)
         return x[0]
+
+    def _certificate(self):
+        """the last solve's certificate (wbc_qp_certificate in the (A, b) form), computed once; None before the first solve"""
+        c = self._last
+        if c is None:
+            return None
+        if c["cert"] is None:
+            c["cert"] = _batch().qp_certificate(c["x"], A=c["A"], b=c["b"], C_=c["C_"], lb=c["lb"], ub=c["ub"], Clb=c["Clb"], Cub=c["Cub"],
+                                                status=c["status"], working_set=c["working_set"])
+        return c["cert"]
+
+    def getDualSolution(self, yOpt=None):
+        """qpOASES' getDualSolution: n + p multipliers, bounds then constraint rows, grad f = y_bounds + C'y_rows (>= 0 at a lower, <= 0 at
+        an upper side). Filled in place when an array is given; zeros for an unsolved QP."""
+        c = self._certificate()
+        if c is None:               # before the first solve: n + p zeros, p from the constraint bounds the object holds
+            bounded_only = self.C is None or self.Clb is None or self.Cub is None
+            y = np.zeros(int(self.no_solutions) + (0 if bounded_only else np.asarray(self.Clb).reshape(-1).shape[0]))
+        else:
+            y = np.concatenate([c["y_bounds"][0], c["y_rows"][0]])
+        if yOpt is None:
+            return y
+        np.asarray(yOpt).reshape(-1)[:len(y)] = y
+        return yOpt
+
+    def getObjVal(self):
+        """qpOASES' getObjVal: 1/2 x'Hx + g'x at the answer (0 for an unsolved QP)"""
+        c = self._certificate()
+        return 0.0 if c is None else float(c["objective"][0])
+
+    @property
+    def kkt(self):
+        """[stationarity, primal violation, wrong-signed multiplier, complementarity] of the last solve (include/wbc.h WbcQpCert.kkt)"""
+        c = self._certificate()
+        return np.zeros(4) if c is None else np.array(c["kkt"][0])
 
     def solveQP(self):
         self._ws = None                 # a cold solve builds a fresh QProblem (QP_Wrapper.py:26-29): no working set is carried into it or past a failed one

@@ -9,6 +9,7 @@
 #include "wbc_device.h"
 #include "wbc_traj.h"
 #include "wbc_slack.h"
+#include "wbc_cert.h"
 
 // d_traj per instance of max_batch: err_sq_sum / err_max / err_final [6] each + the six frames' positions [6][3]; bad, err_max_tick [6],
 // first_bad_tick, bad_ticks, status_max. One int32 (the bad-row count) follows.
@@ -1597,6 +1598,58 @@ extern "C" int wbc_qp_solve_ls(WbcBatch* b, int B, int m, int n, int p, const do
   a.x = x; a.status = status; a.iters = iters; a.H_out = H_out; a.g_out = g_out;
   a.ws_in = (const unsigned long long*)working_set_in; a.ws_out = (unsigned long long*)working_set_out;
   return qp_common(b, B, a, mem, stream, "wbc_qp_solve_ls");
+}
+
+// Dual solution, KKT certificate and sensitivities of solved QPs (include/wbc.h): argument checks, staging of host arrays, ONE launch of
+// wbc_qp_cert_kernel (csrc/wbc_k_cert.hip). No workspace of its own, no memset: with device pointers the call can be captured.
+static_assert(sizeof(WbcQpProblem) == 16 + 13 * sizeof(void*), "WbcQpProblem: four int32 and thirteen pointers (wbc_capi.WbcQpProblem)");
+static_assert(sizeof(WbcQpCert) == 9 * sizeof(void*), "WbcQpCert: nine pointers (wbc_capi.WbcQpCert)");
+extern "C" int wbc_qp_certificate(WbcBatch* b, int B, const WbcQpProblem* q, const WbcQpCert* out, int mem, void* stream) {
+  const char* who = "wbc_qp_certificate";
+  int rc = check_batch(b, B, who, false, false);
+  if (rc) return rc;
+  if (!q || !out) return fail(WBC_E_ARG, "%s: problem and out are required", who);
+  const int n = q->n, p = q->p, m = q->m;
+  const bool hg = q->H || q->g, ab = q->A || q->b;
+  if (hg && ab) return fail(WBC_E_ARG, "%s: both H, g and A, b are given (exactly one pair)", who);
+  if (!hg && !ab) return fail(WBC_E_ARG, "%s: neither H, g nor A, b is given (exactly one pair)", who);
+  if (hg && (!q->H || !q->g)) return fail(WBC_E_ARG, "%s: H and g go together", who);
+  if (ab && (!q->A || !q->b)) return fail(WBC_E_ARG, "%s: A and b go together", who);
+  if (n < 1 || n > WBC_MAX_NV) return fail(WBC_E_ARG, "%s: n = %d outside [1, %d]", who, n, WBC_MAX_NV);
+  if (p < 0 || p > WBC_MAX_P) return fail(WBC_E_ARG, "%s: p = %d outside [0, %d]", who, p, WBC_MAX_P);
+  if (ab ? (m < 1 || m > WBC_MAX_M) : (m != 0)) return fail(WBC_E_ARG, "%s: m = %d (with A, b: 1..%d; with H, g: 0)", who, m, WBC_MAX_M);
+  if (!q->x) return fail(WBC_E_ARG, "%s: x is required", who);
+  if (p > 0 && (!q->C || !q->Clb || !q->Cub)) return fail(WBC_E_ARG, "%s: C, Clb, Cub required when p > 0", who);
+  if ((q->lb != nullptr) != (q->ub != nullptr)) return fail(WBC_E_ARG, "%s: lb and ub go together", who);
+  if (!q->v && out->sens_x) return fail(WBC_E_ARG, "%s: sens_x requested without v", who);
+  if (!q->v && out->sens_bounds) return fail(WBC_E_ARG, "%s: sens_bounds requested without v", who);
+  if (!q->v && out->sens_rows) return fail(WBC_E_ARG, "%s: sens_rows requested without v", who);
+  HIP_TRY(hipSetDevice(b->device_id));
+  CertArgs a;
+  memset(&a, 0, sizeof a);
+  a.B = B; a.n = n; a.p = p; a.m = m;
+  a.H = q->H; a.g = q->g; a.A = q->A; a.bvec = q->b; a.C = p > 0 ? q->C : nullptr; a.lb = q->lb; a.ub = q->ub;
+  a.Clb = p > 0 ? q->Clb : nullptr; a.Cub = p > 0 ? q->Cub : nullptr;
+  a.x = q->x; a.v = q->v; a.status = q->status; a.ws = (const unsigned long long*)q->working_set;
+  a.y_bounds = out->y_bounds; a.y_rows = p > 0 ? out->y_rows : nullptr; a.kkt = out->kkt; a.objective = out->objective;
+  a.sens_x = out->sens_x; a.sens_bounds = out->sens_bounds; a.sens_rows = p > 0 ? out->sens_rows : nullptr;
+  a.n_active = out->n_active; a.cert_status = out->cert_status;
+  Stager st{b, mem, (hipStream_t)stream, {}};
+  const size_t N = (size_t)B;
+  st.in(&a.H, N * n * n); st.in(&a.g, N * n); st.in(&a.A, N * m * n); st.in(&a.bvec, N * m);
+  st.in(&a.C, N * p * n); st.in(&a.lb, N * n); st.in(&a.ub, N * n); st.in(&a.Clb, N * p); st.in(&a.Cub, N * p);
+  st.in(&a.x, N * n); st.in(&a.v, N * n); st.in(&a.status, N); st.in(&a.ws, N * 2);
+  st.out(&a.y_bounds, N * n); st.out(&a.y_rows, N * p); st.out(&a.kkt, N * 4); st.out(&a.objective, N);
+  st.out(&a.sens_x, N * n); st.out(&a.sens_bounds, N * n); st.out(&a.sens_rows, N * p);
+  st.out(&a.n_active, N); st.out(&a.cert_status, N);
+  if ((rc = st.stage())) return rc;
+  if ((rc = launch_rc(launch_cert(a, grid_for(b, B), stream), "qp certificate"))) return rc;
+  return st.finish();
+}
+extern "C" int wbc_qp_certificate_sizes(int32_t* sizeof_problem, int32_t* sizeof_cert) {
+  if (sizeof_problem) *sizeof_problem = (int32_t)sizeof(WbcQpProblem);
+  if (sizeof_cert) *sizeof_cert = (int32_t)sizeof(WbcQpCert);
+  return WBC_OK;
 }
 
 extern "C" int wbc_integrate(WbcBatch* b, int B, const double* q, const double* v, const int32_t* model_id, double dt, int mem,

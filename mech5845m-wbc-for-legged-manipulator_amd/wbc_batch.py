@@ -330,6 +330,56 @@ class WbcBatch:
         out = (x, st, it, Ho, go) if want_Hg else (x, st, it)
         return out + (wso,) if want_working_set else out
 
+    def qp_certificate(self, x, H=None, g=None, A=None, b=None, C_=None, lb=None, ub=None, Clb=None, Cub=None, status=None, working_set=None,
+                       v=None):
+        """wbc_qp_certificate (include/wbc.h): dual solution, KKT certificate and — with v [B,n] = dL/dx — the sensitivities of solved QPs, one
+        kernel launch. Give H [B,n,n], g or A [B,m,n], b. status / working_set: what the solve returned (int32 [B] / int64 [B,2]; optional).
+        Returns dict(y_bounds [B,n], y_rows [B,p], kkt [B,4], objective [B], n_active [B], cert_status [B][, sens_x, sens_bounds, sens_rows])."""
+        keep = []
+        mem = _mem_of([x, H, g, A, b, C_, lb, ub, Clb, Cub, status, working_set, v])
+        if x is None or len(x.shape) != 2:
+            raise capi.WbcError("x must be [B, n], got %s" % (None if x is None else tuple(x.shape),))
+        B, n = int(x.shape[0]), int(x.shape[1])
+        if C_ is not None and (len(C_.shape) != 3 or C_.shape[2] != n):
+            raise capi.WbcError("C must be [B, p, %d], got %s" % (n, tuple(C_.shape)))
+        p = 0 if C_ is None else int(C_.shape[1])
+        if A is not None and (len(A.shape) != 3 or A.shape[2] != n):
+            raise capi.WbcError("A must be [B, m, %d], got %s" % (n, tuple(A.shape)))
+        m = 0 if A is None else int(A.shape[1])
+        f, P = np.float64, self._p
+        q = capi.WbcQpProblem()
+        q.n, q.p, q.m = n, p, m
+        q.H, q.g = P(H, f, keep, B, n * n, "H"), P(g, f, keep, B, n, "g")
+        q.A, q.b = P(A, f, keep, B, m * n, "A"), P(b, f, keep, B, m, "b")
+        q.C, q.lb, q.ub = P(C_, f, keep, B, p * n, "C"), P(lb, f, keep, B, n, "lb"), P(ub, f, keep, B, n, "ub")
+        q.Clb, q.Cub = P(Clb, f, keep, B, p, "Clb"), P(Cub, f, keep, B, p, "Cub")
+        q.x, q.v = P(x, f, keep, B, n, "x"), P(v, f, keep, B, n, "v")
+        q.status, q.working_set = P(status, np.int32, keep, B, 1, "status"), P(working_set, np.int64, keep, B, 2, "working_set")
+        shapes = dict(y_bounds=((B, n), f), y_rows=((B, p), f), kkt=((B, 4), f), objective=((B,), f), n_active=((B,), np.int32),
+                      cert_status=((B,), np.int32))
+        if v is not None:
+            shapes.update(sens_x=((B, n), f), sens_bounds=((B, n), f), sens_rows=((B, p), f))
+        out = {k: self._alloc(x, s, d) for k, (s, d) in shapes.items()}
+        o = capi.WbcQpCert()
+        for k, a in out.items():
+            if a.shape[-1] != 0 or len(a.shape) == 1:          # (p == 0: the row outputs are empty and stay NULL)
+                setattr(o, k, P(a, shapes[k][1], keep))
+        capi.check(self.lib.wbc_qp_certificate(self._h, B, C.byref(q), C.byref(o), mem, self._stream(mem)), self.lib)
+        return out
+
+    def tick_certificate(self, inputs, dt, task_params=None, v=None):
+        """One tick with its certificate, all on the device: wbc_assemble[_tp] (A, b, C, bounds), wbc_tick[_tp] with the working set out, then
+        wbc_qp_certificate in the (A, b) form on the full problem (the tick's working set is in the full problem's indexing on every path).
+        v [B,26]: dL/dqdot for the sensitivities. Returns dict(qdot, status, iters, working_set) plus qp_certificate's entries."""
+        d = self.assemble(inputs, dt, want=("A", "b", "C", "Clb", "Cub", "lb", "ub"), task_params=task_params)
+        t = self.tick(inputs, dt, want_working_set=True, task_params=task_params)
+        has_rows = d["C"].shape[1] > 0
+        # lb / ub as wbc_assemble returns them: +-1e30 (no bound) for an instance whose model's configuration has the velocity box off
+        c = self.qp_certificate(t["qdot"], A=d["A"], b=d["b"], C_=d["C"] if has_rows else None, lb=d["lb"], ub=d["ub"],
+                                Clb=d["Clb"] if has_rows else None, Cub=d["Cub"] if has_rows else None,
+                                status=t["status"], working_set=t["working_set"], v=v)
+        return dict(t, **c)
+
     def posture_target(self, q, model_id=None, want_q_after=True):
         """qpJointb's "MANI" / "HYBRID" posture target u [B,26] under the configured mode (Robot_Wrapper4.py:1220-1260),
         and the configuration the reference's state is left at, q_after [B,27]."""

@@ -132,6 +132,20 @@ class WbcSlackWatch(C.Structure):
         "group_neg_instances")]
 
 
+# wbc_qp_certificate: dual solution, KKT certificate and sensitivities of a solved QP (include/wbc.h)
+CERT_OK, CERT_UNSOLVED, CERT_DEPENDENT, CERT_NUMERICAL = 0, 1, 2, 3
+
+
+class WbcQpProblem(C.Structure):
+    _fields_ = [("n", C.c_int32), ("p", C.c_int32), ("m", C.c_int32), ("pad_", C.c_int32)] + [(n, C.c_void_p) for n in (
+        "H", "g", "A", "b", "C", "lb", "ub", "Clb", "Cub", "x", "status", "working_set", "v")]
+
+
+class WbcQpCert(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("y_bounds", "y_rows", "kkt", "objective", "n_active", "sens_x", "sens_bounds", "sens_rows",
+                                          "cert_status")]
+
+
 class WbcFkOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("oMi", "oMf", "J", "com", "Jcom")]
 
@@ -163,6 +177,8 @@ SIGNATURES = {
     "wbc_assemble": (_i, [_vp, _i, C.POINTER(WbcTickIn), _d, _i, C.POINTER(WbcQpData), _vp]),
     "wbc_qp_solve": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "wbc_qp_solve_ls": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "wbc_qp_certificate": (_i, [_vp, _i, C.POINTER(WbcQpProblem), C.POINTER(WbcQpCert), _i, _vp]),
+    "wbc_qp_certificate_sizes": (_i, [c_int32_p, c_int32_p]),
     "wbc_posture_target": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "wbc_tick": (_i, [_vp, _i, C.POINTER(WbcTickIn), _d, _i, C.POINTER(WbcTickOut), _vp]),
     "wbc_update_state": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
@@ -223,6 +239,10 @@ def load_library(path=None):
     if sb.value != C.sizeof(WbcModelBlob) or sc.value != C.sizeof(WbcConfig):
         raise WbcError("ABI mismatch: library (%d, %d) vs ctypes (%d, %d)" % (
             sb.value, sc.value, C.sizeof(WbcModelBlob), C.sizeof(WbcConfig)))
+    lib.wbc_qp_certificate_sizes(C.byref(sb), C.byref(sc))
+    if sb.value != C.sizeof(WbcQpProblem) or sc.value != C.sizeof(WbcQpCert):
+        raise WbcError("ABI mismatch (certificate structs): library (%d, %d) vs ctypes (%d, %d)" % (
+            sb.value, sc.value, C.sizeof(WbcQpProblem), C.sizeof(WbcQpCert)))
     if path is None:
         _lib = lib
     return lib

@@ -1,0 +1,71 @@
+"""Differentiable batched QP for torch: ``x, status = qp_solve(H, g, C, lb, ub, Clb, Cub, batch)``.
+
+Forward is ``wbc_qp_solve`` with the working set out; backward is ONE ``wbc_qp_certificate`` call with v = grad_output (include/wbc.h:
+K (u; w) = (v; 0) on the factors of the certificate) plus torch outer products:
+
+    dL/dg = -u      dL/dH = -1/2 (u x' + x u')      dL/dC_j = -w_j x' + y_j u'      dL/de_i = w_i
+
+where e_i is the bound value active constraint i sits at: the gradient goes to lb / Clb at a lower side, to ub / Cub at an upper side and
+is split half and half on an equality (lb == ub, Clb == Cub). Instances whose QP was not solved, or whose certificate does not come back
+WBC_CERT_OK (dependent active normals, non-finite data), get zero gradients. All tensors are contiguous float64 on the handle's device;
+C, Clb, Cub (no rows) and lb, ub (no box) may be None. There is no CPU fallback.
+"""
+import torch
+
+import wbc_capi as capi
+
+
+def _c(t):
+    return None if t is None else t.detach().contiguous()
+
+
+class _QpSolve(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, H, g, C, lb, ub, Clb, Cub, batch):
+        args = [_c(t) for t in (H, g, C, lb, ub, Clb, Cub)]
+        x, st, _, ws = batch.qp_solve(*args, want_working_set=True)
+        ctx.batch = batch
+        ctx.present = [a is not None for a in args]
+        # through save_for_backward: an in-place change of an input between forward and backward is an autograd error, not a certificate of other data
+        ctx.save_for_backward(x, st, ws, *[a for a in args if a is not None])
+        ctx.mark_non_differentiable(st)
+        return x, st
+
+    @staticmethod
+    def backward(ctx, gx, _gst):
+        x, st, ws, *given = ctx.saved_tensors
+        it = iter(given)
+        H, g, C, lb, ub, Clb, Cub = [next(it) if have else None for have in ctx.present]
+        if gx is None:              # x took no part in the loss
+            return (None,) * 8
+        B, n = x.shape
+        c = ctx.batch.qp_certificate(x, H=H, g=g, C_=C, lb=lb, ub=ub, Clb=Clb, Cub=Cub, status=st, working_set=ws, v=gx.contiguous())
+        ok = (c["cert_status"] == capi.CERT_OK).to(x.dtype)[:, None]
+        u, wb = c["sens_x"] * ok, c["sens_bounds"] * ok
+        need = ctx.needs_input_grad
+
+        def sides(w, lo, hi, word):
+            """dL/de -> (its lower bound's, its upper bound's) share"""
+            k = w.shape[1]
+            low = ((word[:, None] >> torch.arange(k, device=w.device)) & 1).bool()
+            eq = lo == hi
+            zero = torch.zeros_like(w)
+            return torch.where(eq, 0.5 * w, torch.where(low, w, zero)), torch.where(eq, 0.5 * w, torch.where(low, zero, w))
+        gH = -0.5 * (u[:, :, None] * x[:, None, :] + x[:, :, None] * u[:, None, :]) if need[0] else None
+        gg = -u if need[1] else None
+        gC = glb = gub = gcl = gcu = None
+        if lb is not None and (need[3] or need[4]):
+            glb, gub = sides(wb, lb, ub, ws[:, 0])
+        if C is not None:
+            wr, yr = c["sens_rows"] * ok, c["y_rows"] * ok
+            if need[2]:
+                gC = -wr[:, :, None] * x[:, None, :] + yr[:, :, None] * u[:, None, :]
+            if need[5] or need[6]:
+                gcl, gcu = sides(wr, Clb, Cub, ws[:, 1])
+        return (gH, gg, gC, glb if need[3] else None, gub if need[4] else None, gcl if need[5] else None, gcu if need[6] else None, None)
+
+
+def qp_solve(H, g, C, lb, ub, Clb, Cub, batch):
+    """argmin 1/2 x'Hx + g'x s.t. lb <= x <= ub, Clb <= C x <= Cub for a batch (H [B,n,n], C [B,p,n]) on `batch` (a WbcBatch), differentiable
+    with respect to every tensor argument. Returns (x [B,n], status [B] int32)."""
+    return _QpSolve.apply(H, g, C, lb, ub, Clb, Cub, batch)

@@ -275,3 +275,123 @@ def watch_summary(trace, which=None):
         w = np.take_along_axis(np.asarray(which), tick[None].astype(np.int64), axis=0)[0]
         out["slack_min_which"] = np.where(anynan, -1, w).astype(np.int32)
     return out
+
+
+# ---- dual solution, KKT certificate and sensitivities of a solved QP: the host restatement of wbc_qp_certificate (include/wbc.h), one problem
+# (qp_certificate needs scipy, for solve_triangular — the only function of the package that does; it is imported inside the function)
+QP_INF = 1e20
+CERT_DEP_TOL = 1e-12
+
+
+def _ws_bits(word):
+    w = int(word) & 0xFFFFFFFFFFFFFFFF
+    return [((w >> i) & 1) | (((w >> (32 + i)) & 1) << 1) for i in range(32)]
+
+
+def qp_active_sides(x, C_=None, lb=None, ub=None, Clb=None, Cub=None, working_set=None):
+    """-> (side, lo, hi, val), each [n + p], variables then rows: side 0 inactive, 1 at the lower side, 2 at the upper side, 3 equality; the rule of
+    include/wbc.h (with a working set [2]: its marked sides; without: read off x as tests/common.py exact_optimum does)."""
+    x = np.asarray(x, dtype=np.float64)
+    n = len(x)
+    p = 0 if C_ is None else len(C_)
+    lo = np.concatenate([np.full(n, -1e30) if lb is None else np.asarray(lb, float), np.asarray(Clb, float) if p else np.zeros(0)])
+    hi = np.concatenate([np.full(n, 1e30) if ub is None else np.asarray(ub, float), np.asarray(Cub, float) if p else np.zeros(0)])
+    val = np.concatenate([x, np.asarray(C_, float) @ x if p else np.zeros(0)])
+    bits = None if working_set is None else _ws_bits(working_set[0])[:n] + _ws_bits(working_set[1])[:p]
+    side = np.zeros(n + p, dtype=np.int32)
+    for i in range(n + p):
+        flo, fhi = abs(lo[i]) < QP_INF, abs(hi[i]) < QP_INF
+        if lo[i] == hi[i] and flo:
+            side[i] = 3
+        elif bits is not None:
+            side[i] = 1 if (bits[i] == 1 and flo) else (2 if (bits[i] == 2 and fhi) else 0)
+        elif flo and abs(val[i] - lo[i]) < 1e-7 * max(1.0, abs(lo[i])):
+            side[i] = 1
+        elif fhi and abs(val[i] - hi[i]) < 1e-7 * max(1.0, abs(hi[i])):
+            side[i] = 2
+    return side, lo, hi, val
+
+
+def qp_certificate(x, H=None, g=None, A=None, b=None, C_=None, lb=None, ub=None, Clb=None, Cub=None, status=None, working_set=None, v=None):
+    """wbc_qp_certificate for ONE problem in numpy, the same algebra: Cholesky H = L L', Y = L^-1 N', QR Y = Q1 R, y = R^-1 Q1' L^-1 grad f, and
+    with z = L^-1 v: w = R^-1 Q1' z, u = L^-T (z - Q1 Q1' z). Give H, g or A, b. Returns dict(y_bounds [n], y_rows [p], kkt [4], objective,
+    n_active, sens_x, sens_bounds, sens_rows, cert_status); side [n + p] (qp_active_sides) comes along for qp_gradients."""
+    from scipy.linalg import solve_triangular
+    x = np.asarray(x, dtype=np.float64)
+    n = len(x)
+    p = 0 if C_ is None else len(C_)
+    out = dict(y_bounds=np.zeros(n), y_rows=np.zeros(p), kkt=np.zeros(4), objective=0.0, n_active=0, sens_x=np.zeros(n), sens_bounds=np.zeros(n),
+               sens_rows=np.zeros(p), cert_status=capi.CERT_OK, side=np.zeros(n + p, dtype=np.int32))
+    if status is not None and int(status) != 0:
+        out["cert_status"] = capi.CERT_UNSOLVED
+        return out
+    ls = A is not None
+    data = [x] + ([np.asarray(A, float), np.asarray(b, float)] if ls else [np.asarray(H, float), np.asarray(g, float)])
+    data += [np.asarray(C_, float)] if p else []
+    data += [np.asarray(v, float)] if v is not None else []
+    bounds = [np.asarray(a, float) for a in (lb, ub, Clb if p else None, Cub if p else None) if a is not None]
+    if not all(np.isfinite(a).all() for a in data) or any(np.isnan(a).any() for a in bounds):
+        out["cert_status"] = capi.CERT_NUMERICAL
+        return out
+    side, lo, hi, val = qp_active_sides(x, C_, lb, ub, Clb, Cub, working_set)
+    flo, fhi = np.abs(lo) < QP_INF, np.abs(hi) < QP_INF
+    viol = max(0.0, float(np.where(flo, lo - val, 0.0).max()), float(np.where(fhi, val - hi, 0.0).max()))
+    if ls:
+        A, b = np.asarray(A, float), np.asarray(b, float)
+        Hm = A.T @ A
+        ax = A @ x
+        grad = A.T @ (ax - b)
+        obj = 0.5 * ax @ ax - b @ ax
+    else:
+        Hm, g = np.asarray(H, float), np.asarray(g, float)
+        hx = Hm @ x
+        grad = hx + g
+        obj = x @ (0.5 * hx + g)
+    act = np.nonzero(side)[0]
+    k = len(act)
+    out.update(n_active=k, objective=float(obj), side=side)
+    out["kkt"][1] = viol
+    if k > n:
+        out["cert_status"] = capi.CERT_DEPENDENT
+        return out
+    try:
+        L = np.linalg.cholesky(Hm)
+    except np.linalg.LinAlgError:
+        out.update(cert_status=capi.CERT_NUMERICAL, n_active=0, objective=0.0, kkt=np.zeros(4), side=np.zeros(n + p, dtype=np.int32))
+        return out
+    Nall = np.vstack([np.eye(n)] + ([np.asarray(C_, float)] if p else []))
+    N = Nall[act]
+    Y = solve_triangular(L, N.T, lower=True) if k else np.zeros((n, 0))
+    Q1, R = np.linalg.qr(Y)
+    if k and (np.abs(np.diag(R)) <= CERT_DEP_TOL * np.linalg.norm(Y, axis=0)).any():
+        out["cert_status"] = capi.CERT_DEPENDENT
+        return out
+    y = solve_triangular(R, Q1.T @ solve_triangular(L, grad, lower=True)) if k else np.zeros(0)
+    yall = np.zeros(n + p)
+    yall[act] = y
+    e = np.where(side == 2, hi, lo)
+    out["y_bounds"], out["y_rows"] = yall[:n], yall[n:]
+    out["kkt"][0] = np.abs(grad - Nall.T @ yall).max()
+    out["kkt"][2] = max(0.0, float(np.where(side == 1, -yall, 0.0).max()), float(np.where(side == 2, yall, 0.0).max()))
+    out["kkt"][3] = float(np.abs(yall * (val - e))[side != 0].max()) if k else 0.0
+    if v is not None:
+        z = solve_triangular(L, np.asarray(v, float), lower=True)
+        qz = Q1.T @ z
+        wall = np.zeros(n + p)
+        wall[act] = solve_triangular(R, qz) if k else np.zeros(0)
+        out["sens_x"] = solve_triangular(L.T, z - Q1 @ qz, lower=False)
+        out["sens_bounds"], out["sens_rows"] = wall[:n], wall[n:]
+    return out
+
+
+def qp_gradients(x, y, u, w, side, C_=None):
+    """The gradients of L(x*) for dL/dx = v, from a certificate with sensitivities (include/wbc.h): y, w, side are [n + p], variables then rows
+    (qp_certificate's y_bounds | y_rows, sens_bounds | sens_rows, side), u = sens_x.  dL/dg = -u, dL/dH = -1/2 (u x' + x u'),
+    dL/dC_j = -w_j x' + y_j u', and dL/de_i = w_i goes to the side constraint i sits at: lb / Clb at a lower side, ub / Cub at an upper side,
+    half and half on an equality. Returns dict(g, H, C, lb, ub, Clb, Cub)."""
+    x, y, u, w, side = (np.asarray(a) for a in (x, y, u, w, side))
+    n = len(x)
+    glo = np.where(side == 1, w, 0.0) + np.where(side == 3, 0.5 * w, 0.0)
+    ghi = np.where(side == 2, w, 0.0) + np.where(side == 3, 0.5 * w, 0.0)
+    return dict(g=-u, H=-0.5 * (np.outer(u, x) + np.outer(x, u)), C=-np.outer(w[n:], x) + np.outer(y[n:], u),
+                lb=glo[:n], ub=ghi[:n], Clb=glo[n:], Cub=ghi[n:])
