@@ -1,4 +1,4 @@
-"""Shared by tests/test_qp_certificate_host.py and tests/test_gpu_qp_certificate.py: the problems (random QPs by the recipe of
+"""Shared by tests/test_qp_certificate_host.py, tests/test_gpu_qp_certificate.py and tests/test_gpu_instance_sequences.py: the problems (random QPs by the recipe of
 test_gpu_parity._random_qps, restated; the oracle's tick problems; tests/golden/qp_cases.npz), the host restatement over a batch, and the exact
 rational duals and sensitivities the restatement is measured against. Everything computed here is computed once and read-only."""
 import functools
@@ -60,14 +60,122 @@ def random_problem(n, p, n_eq, B=64):
 
 
 @functools.lru_cache(maxsize=None)
-def ls_problem(B=64, m=32, n=26, p=16, n_eq=12):
-    """the (A, b) form: random_qps' constraints around a least-squares objective of m rows (seed 132)"""
-    rng = np.random.default_rng(132)
+def ls_problem(B=64, m=32, n=26, p=16, n_eq=12, seed=132, box=True):
+    """the (A, b) form: random_qps' constraints around a least-squares objective of m rows. box=False: lb = ub = None (no bounds, so no fixed
+    pair either); p = 0: no rows"""
+    rng = np.random.default_rng(seed)
     _, _, C, lb, ub, cl, cu = random_qps(rng, B, n, p, n_eq)
-    P = dict(A=rng.normal(size=(B, m, n)), b=rng.normal(size=(B, m)) * 2, C=C, lb=lb, ub=ub, Clb=cl, Cub=cu)
+    P = dict(A=rng.normal(size=(B, m, n)), b=rng.normal(size=(B, m)) * 2, C=C if p else None, lb=lb if box else None, ub=ub if box else None,
+             Clb=cl if p else None, Cub=cu if p else None)
     P["x"], P["status"] = oracle_solve(P)
     P["v"] = rng.normal(size=(B, n))
     return _freeze(P)
+
+
+@functools.lru_cache(maxsize=None)
+def ls_problem_free_bounds(B=16, m=1, n=1, seed=211):
+    """the (A, b) form with a box none of whose variables is fixed and no rows: the recipe for n = 1, where random_qps' fixed pair would leave
+    nothing to solve"""
+    rng = np.random.default_rng(seed)
+    P = dict(A=rng.normal(size=(B, m, n)), b=rng.normal(size=(B, m)) * 2, C=None, lb=-rng.uniform(0.02, 0.8, (B, n)), ub=rng.uniform(0.02, 0.8, (B, n)),
+             Clb=None, Cub=None)
+    P["x"], P["status"] = oracle_solve(P)
+    P["v"] = rng.normal(size=(B, n))
+    return _freeze(P)
+
+
+@functools.lru_cache(maxsize=None)
+def vertex_problem(B=16, m=30, n=6, seed=307):
+    """k == n: a tight box (half-widths 0.02 .. 0.05) around a least-squares objective whose b is scaled by 20 — every variable ends at a bound,
+    the active normals span the space and u = 0"""
+    rng = np.random.default_rng(seed)
+    P = dict(A=rng.normal(size=(B, m, n)), b=rng.normal(size=(B, m)) * 20, C=None, lb=-rng.uniform(0.02, 0.05, (B, n)), ub=rng.uniform(0.02, 0.05, (B, n)),
+             Clb=None, Cub=None)
+    P["x"], P["status"] = oracle_solve(P)
+    P["v"] = rng.normal(size=(B, n))
+    return _freeze(P)
+
+
+@functools.lru_cache(maxsize=None)
+def overdetermined_problem(B=16, m=12, n=5, p=8, seed=1258):
+    """k > n: p = 8 equality rows through the origin on n = 5 variables inside the box +-1 — x = 0 is the one feasible point, the oracle solves
+    it, and the eight always-active rows are more normals than variables"""
+    rng = np.random.default_rng(seed)
+    P = dict(A=rng.normal(size=(B, m, n)), b=rng.normal(size=(B, m)) * 2, C=rng.normal(size=(B, p, n)), lb=-np.ones((B, n)), ub=np.ones((B, n)),
+             Clb=np.zeros((B, p)), Cub=np.zeros((B, p)))
+    P["x"], P["status"] = oracle_solve(P)
+    P["v"] = rng.normal(size=(B, n))
+    return _freeze(P)
+
+
+def working_sets(P, x):
+    """[B, 2] int64 in the layout of include/wbc.h (word 0 the variables, word 1 the rows; bit i a lower side, bit 32 + i an upper side) from the
+    sides read off x; an equality is marked at its lower side"""
+    B, n = x.shape
+    ws = np.zeros((B, 2), dtype=np.uint64)
+    for i in range(B):
+        kw_ = instance(P, i)
+        side = wbc_workload.qp_active_sides(x[i], kw_.get("C_"), kw_.get("lb"), kw_.get("ub"), kw_.get("Clb"), kw_.get("Cub"))[0]
+        for j, s in enumerate(side):
+            word, bit = (0, j) if j < n else (1, j - n)
+            if s:
+                ws[i, word] |= np.uint64(1 << (bit + (32 if s == 2 else 0)))
+    return ws.view(np.int64)
+
+
+def ws_bits(ws, i, word, j):
+    """(lower | upper << 1) of constraint j in word `word` of instance i"""
+    w = int(ws.view(np.uint64)[i, word])
+    return ((w >> j) & 1) | (((w >> (32 + j)) & 1) << 1)
+
+
+def ws_set(ws, i, word, j, bits):
+    """set the two bits of constraint j (ws: a writable [B, 2] int64)"""
+    u = ws.view(np.uint64)
+    w = int(u[i, word]) & ~((1 << j) | (1 << (32 + j)))
+    u[i, word] = np.uint64(w | ((bits & 1) << j) | (((bits >> 1) & 1) << (32 + j)))
+
+
+def off_optimum(P, x, ws, way):
+    """x and working set moved off the optimum, one variable per instance among those with lb < ub: "flip" — the first variable the working set
+    has at a bound goes to its other bound, and the working set says so; "outside" — the first variable the working set leaves free goes 1e-3
+    past its upper bound; "shift" — that variable moves by 1e-4 and stays inside. -> (x, ws, moved [B] bool)"""
+    x2, ws2 = np.array(x), np.array(ws)
+    B, n = x.shape
+    moved = np.zeros(B, dtype=bool)
+    for i in range(B):
+        for j in range(n):
+            if P["lb"][i, j] == P["ub"][i, j]:
+                continue
+            bits = ws_bits(ws, i, 0, j)
+            if way == "flip" and bits in (1, 2):
+                x2[i, j] = P["ub"][i, j] if bits == 1 else P["lb"][i, j]
+                ws_set(ws2, i, 0, j, 3 - bits)
+            elif way == "outside" and bits == 0:
+                x2[i, j] = P["ub"][i, j] + 1e-3
+            elif way == "shift" and bits == 0 and P["ub"][i, j] - x[i, j] > 2e-4:
+                x2[i, j] = x[i, j] + 1e-4
+            else:
+                continue
+            moved[i] = True
+            break
+    return x2, ws2, moved
+
+
+def near_bounds(P, x, ws):
+    """for the rule that reads the active set off x (|x - lo| < 1e-7 max(1, |lo|)): per instance two variables with lb < ub — those the working
+    set has at their lower bound first, then the free ones — are placed at lo + 0.5e-7 max(1, |lo|) (active) and lo + 2e-7 max(1, |lo|) (not).
+    -> (x, near [B], far [B])"""
+    x2 = np.array(x)
+    B, n = x.shape
+    near, far = np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.int64)
+    for i in range(B):
+        free = [j for j in range(n) if P["lb"][i, j] < P["ub"][i, j]]
+        order = sorted(free, key=lambda j: {1: 0, 0: 1}.get(ws_bits(ws, i, 0, j), 2))
+        near[i], far[i] = order[0], order[1]
+        for j, f in ((near[i], 0.5e-7), (far[i], 2e-7)):
+            x2[i, j] = P["lb"][i, j] + f * max(1.0, abs(P["lb"][i, j]))
+    return x2, near, far
 
 
 @functools.lru_cache(maxsize=None)
@@ -166,8 +274,8 @@ def exact_solution(P, i, side, v=None, solver=None):
         H, g = kw["H"], kw["g"]
     C = kw.get("C_")
     Nall = np.vstack([np.eye(n)] + ([C] if C is not None else []))
-    lo = np.concatenate([kw["lb"]] + ([kw["Clb"]] if C is not None else []))
-    hi = np.concatenate([kw["ub"]] + ([kw["Cub"]] if C is not None else []))
+    lo = np.concatenate([kw.get("lb", np.full(n, -1e30))] + ([kw["Clb"]] if C is not None else []))     # (no box: no bounds, never active)
+    hi = np.concatenate([kw.get("ub", np.full(n, 1e30))] + ([kw["Cub"]] if C is not None else []))
     act = np.nonzero(side)[0]
     e = np.where(side == 2, hi, lo)[act]
     x, lam = solver(H, g, Nall[act], e)                        # H x + g + N'lam = 0: y = -lam
@@ -201,4 +309,72 @@ def restatement_error(P, cert, idx, v=None, solver=None):
         worst = max(worst, rel_err(np.concatenate([cert["y_bounds"][j], cert["y_rows"][j]]), y))
         if v is not None:
             worst = max(worst, rel_err(cert["sens_x"][j], u, 1.0), rel_err(np.concatenate([cert["sens_bounds"][j], cert["sens_rows"][j]]), w, 1.0))
+    return worst
+
+
+# ---- device against restatement (tests/test_gpu_qp_certificate.py, whose docstring states the tolerance rule; tests/test_gpu_instance_sequences.py)
+EXACT_N = 6
+ULP = 2.220446049250313e-16
+
+
+def kw(P, x, st=None, ws=None, v=None):
+    """the keyword arguments of WbcBatch.qp_certificate for the problems P"""
+    d = dict(C_=P["C"], lb=P["lb"], ub=P["ub"], Clb=P["Clb"], Cub=P["Cub"], status=st, working_set=ws, v=v)
+    d.update(dict(A=P["A"], b=P["b"]) if P.get("A") is not None else dict(H=P["H"], g=P["g"]))
+    return d
+
+
+def grad_terms(P, x, yb, yr):
+    """[B]: the largest entry of what grad f - N'y is summed from"""
+    if P.get("A") is not None:
+        A = np.abs(P["A"])
+        t = np.einsum("bmi,bm->bi", A, np.einsum("bmi,bi->bm", A, np.abs(x)) + np.abs(P["b"]))
+    else:
+        t = np.einsum("bij,bj->bi", np.abs(P["H"]), np.abs(x)) + np.abs(P["g"])
+    t = t + np.abs(yb)
+    if P["C"] is not None:
+        t = t + np.einsum("bpi,bp->bi", np.abs(P["C"]), np.abs(yr))
+    return t.max(axis=1)
+
+
+def tolerance(P, host, v, exact_n=EXACT_N):
+    """(ten times the restatement's error against the exact rationals over the first exact_n certified instances, never below ten ulp; that error)"""
+    idx = [i for i in range(len(host["cert_status"])) if host["cert_status"][i] == capi.CERT_OK][:exact_n]
+    sub = {k: a[idx] for k, a in host.items()}
+    err = restatement_error(P, sub, idx, v)
+    return 10.0 * max(err, ULP), err
+
+
+def compare(dev, host, P, x, tol, what, only_kkt=False):
+    """every output of the device against the restatement (only_kkt: the four residuals alone); returns the largest ratio error / tolerance seen"""
+    assert np.array_equal(dev["n_active"], host["n_active"]), (what, np.nonzero(dev["n_active"] != host["n_active"]))
+    assert np.array_equal(dev["cert_status"], host["cert_status"]), (what, dev["cert_status"], host["cert_status"])
+    B = len(x)
+    cat = lambda d, a, b: np.concatenate([d[a], d[b]], axis=1)
+    yd, yh = cat(dev, "y_bounds", "y_rows"), cat(host, "y_bounds", "y_rows")
+    ymax = np.abs(yh).max(axis=1, initial=0.0)
+    terms = grad_terms(P, x, host["y_bounds"], host["y_rows"])
+    vals = np.abs(x).max(axis=1)
+    if P["C"] is not None:
+        vals = np.maximum(vals, np.abs(np.einsum("bpi,bi->bp", P["C"], x)).max(axis=1))
+    vals = np.maximum(1.0, vals)
+    checks = [("y", np.abs(yd - yh).max(axis=1, initial=0.0), ymax),
+              ("objective", np.abs(dev["objective"] - host["objective"]), np.maximum(1.0, np.abs(host["objective"]))),
+              ("kkt[0] stationarity", np.abs(dev["kkt"][:, 0] - host["kkt"][:, 0]), terms),
+              ("kkt[1] violation", np.abs(dev["kkt"][:, 1] - host["kkt"][:, 1]), vals),
+              ("kkt[2] wrong sign", np.abs(dev["kkt"][:, 2] - host["kkt"][:, 2]), ymax),
+              ("kkt[3] complementarity", np.abs(dev["kkt"][:, 3] - host["kkt"][:, 3]), ymax * vals)]
+    if only_kkt:
+        checks = checks[2:]
+    elif "sens_x" in dev:
+        wd, wh = cat(dev, "sens_bounds", "sens_rows"), cat(host, "sens_bounds", "sens_rows")
+        checks += [("u", np.abs(dev["sens_x"] - host["sens_x"]).max(axis=1), np.maximum(1.0, np.abs(host["sens_x"]).max(axis=1))),
+                   ("w", np.abs(wd - wh).max(axis=1, initial=0.0), np.maximum(1.0, np.abs(wh).max(axis=1, initial=0.0)))]
+    worst = 0.0
+    for name, diff, scale in checks:
+        assert diff.shape == (B,) and scale.shape == (B,)
+        bad = diff > tol * scale
+        assert not bad.any(), "%s: %s: instance %d off by %.3e, allowed %.3e" % (what, name, np.argmax(bad), diff[np.argmax(bad)], tol * scale[np.argmax(bad)])
+        worst = max(worst, float((diff / np.where(scale > 0, scale, 1.0)).max()) / tol)
+    assert (yd[host["side"] == 0] == 0).all(), what                   # inactive entries are exactly zero
     return worst

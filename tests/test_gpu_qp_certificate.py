@@ -1,5 +1,6 @@
-"""GPU: wbc_qp_certificate (csrc/wbc_k_cert.hip) against its host restatement wbc_workload.qp_certificate on every output, the golden QP cases in one
-batch, tick_certificate, in place on guarded device memory, the refusals, the QP mirror's getDualSolution / getObjVal and wbc_torch.qp_solve.
+"""GPU: wbc_qp_certificate (csrc/wbc_k_cert.hip) against its host restatement wbc_workload.qp_certificate on every output — in the middle and at the
+ends of its documented range (EDGE_SHAPES), and where the active set is special (k == n, k > n, an x off the optimum, the working-set and read-off
+rules) —, the golden QP cases in one batch, tick_certificate, in place on guarded device memory, the refusals, the QP mirror's getDualSolution / getObjVal and wbc_torch.qp_solve.
 
 Tolerance of a device-against-restatement comparison: TEN TIMES the restatement's own error against the exact rationals on the same inputs
 (cert_common.restatement_error over the first EXACT_N certified instances: multipliers, and u, w where v is given), never below ten times one
@@ -33,65 +34,11 @@ def bt():
     b.close()
 
 
-def _kw(P, x, st=None, ws=None, v=None):
-    kw = dict(C_=P["C"], lb=P["lb"], ub=P["ub"], Clb=P["Clb"], Cub=P["Cub"], status=st, working_set=ws, v=v)
-    kw.update(dict(A=P["A"], b=P["b"]) if P.get("A") is not None else dict(H=P["H"], g=P["g"]))
-    return kw
+_kw, _grad_terms, _compare = cc.kw, cc.grad_terms, cc.compare          # (shared with tests/test_gpu_instance_sequences.py)
 
 
-def _grad_terms(P, x, yb, yr):
-    """[B]: the largest entry of what grad f - N'y is summed from"""
-    if P.get("A") is not None:
-        A = np.abs(P["A"])
-        t = np.einsum("bmi,bm->bi", A, np.einsum("bmi,bi->bm", A, np.abs(x)) + np.abs(P["b"]))
-    else:
-        t = np.einsum("bij,bj->bi", np.abs(P["H"]), np.abs(x)) + np.abs(P["g"])
-    t = t + np.abs(yb)
-    if P["C"] is not None:
-        t = t + np.einsum("bpi,bp->bi", np.abs(P["C"]), np.abs(yr))
-    return t.max(axis=1)
-
-
-def _tolerance(P, host, v):
-    idx = [i for i in range(len(host["cert_status"])) if host["cert_status"][i] == capi.CERT_OK][:EXACT_N]
-    sub = {k: a[idx] for k, a in host.items()}
-    err = cc.restatement_error(P, sub, idx, v)
-    return 10.0 * max(err, ULP), err
-
-
-def _compare(dev, host, P, x, tol, what, only_kkt=False):
-    """every output of the device against the restatement (only_kkt: the four residuals alone); returns the largest ratio error / tolerance seen"""
-    assert np.array_equal(dev["n_active"], host["n_active"]), (what, np.nonzero(dev["n_active"] != host["n_active"]))
-    assert np.array_equal(dev["cert_status"], host["cert_status"]), (what, dev["cert_status"], host["cert_status"])
-    B = len(x)
-    cat = lambda d, a, b: np.concatenate([d[a], d[b]], axis=1)
-    yd, yh = cat(dev, "y_bounds", "y_rows"), cat(host, "y_bounds", "y_rows")
-    ymax = np.abs(yh).max(axis=1, initial=0.0)
-    terms = _grad_terms(P, x, host["y_bounds"], host["y_rows"])
-    vals = np.abs(x).max(axis=1)
-    if P["C"] is not None:
-        vals = np.maximum(vals, np.abs(np.einsum("bpi,bi->bp", P["C"], x)).max(axis=1))
-    vals = np.maximum(1.0, vals)
-    checks = [("y", np.abs(yd - yh).max(axis=1, initial=0.0), ymax),
-              ("objective", np.abs(dev["objective"] - host["objective"]), np.maximum(1.0, np.abs(host["objective"]))),
-              ("kkt[0] stationarity", np.abs(dev["kkt"][:, 0] - host["kkt"][:, 0]), terms),
-              ("kkt[1] violation", np.abs(dev["kkt"][:, 1] - host["kkt"][:, 1]), vals),
-              ("kkt[2] wrong sign", np.abs(dev["kkt"][:, 2] - host["kkt"][:, 2]), ymax),
-              ("kkt[3] complementarity", np.abs(dev["kkt"][:, 3] - host["kkt"][:, 3]), ymax * vals)]
-    if only_kkt:
-        checks = checks[2:]
-    elif "sens_x" in dev:
-        wd, wh = cat(dev, "sens_bounds", "sens_rows"), cat(host, "sens_bounds", "sens_rows")
-        checks += [("u", np.abs(dev["sens_x"] - host["sens_x"]).max(axis=1), np.maximum(1.0, np.abs(host["sens_x"]).max(axis=1))),
-                   ("w", np.abs(wd - wh).max(axis=1, initial=0.0), np.maximum(1.0, np.abs(wh).max(axis=1, initial=0.0)))]
-    worst = 0.0
-    for name, diff, scale in checks:
-        assert diff.shape == (B,) and scale.shape == (B,)
-        bad = diff > tol * scale
-        assert not bad.any(), "%s: %s: instance %d off by %.3e, allowed %.3e" % (what, name, np.argmax(bad), diff[np.argmax(bad)], tol * scale[np.argmax(bad)])
-        worst = max(worst, float((diff / np.where(scale > 0, scale, 1.0)).max()) / tol)
-    assert (yd[host["side"] == 0] == 0).all(), what                   # inactive entries are exactly zero
-    return worst
+def _tolerance(P, host, v, exact_n=None):
+    return cc.tolerance(P, host, v, EXACT_N if exact_n is None else exact_n)
 
 
 DEFAULTS = {"packed_kernel": 1}          # include/wbc.h: the value a handle has before its first wbc_batch_set_option of that name
@@ -100,12 +47,36 @@ CASES = [("n26_p16", lambda: cc.random_problem(26, 16, 12), {}), ("n25_p10", lam
          ("n3_p2", lambda: cc.random_problem(3, 2, 0), {}), ("n26_p16_B67", lambda: cc.random_problem(26, 16, 12, 67), {}),
          ("n26_p16_B1", lambda: cc.random_problem(26, 16, 12, 1), {}), ("ls_m32", cc.ls_problem, {}),
          ("n26_p16_one_per_wave", lambda: cc.random_problem(26, 16, 12), {"packed_kernel": 0})]
+# the ends of the documented range, B = 16 each, (A, b) form (m, n, p, equalities): two full 48-row chunks with rows on lanes 16..23; a second chunk of
+# one row (odd-row padding); odd m in one chunk with odd n; exactly one chunk with p just past 16; no box (lb = ub = None) without and with rows;
+# the smallest shape with random_qps' fixed pair; n = m = 1; and p = 24 in the (H, g) form. The exact rationals behind their tolerance cost a second per
+# instance at n = 26: the first four certified instances there, and ALL sixteen at n <= 13, where they cost nothing — and where a prefix is no sample:
+# at (3, 3, 0, 0) A is square, cond(A'A) runs from 4.5 to 3.5e4 over the batch and the restatement's own error from 1.1e-16 to 4.6e-12 (instance 8,
+# a vertex: the exact u is 0, the device's is, numpy's z - Q1 Q1'z leaves 4.6e-12 after L^-T)
+EDGE_SHAPES = [(96, 26, 24, 12, True), (49, 26, 16, 12, True), (47, 13, 5, 2, True), (48, 26, 17, 8, True), (95, 26, 0, 0, False), (33, 26, 24, 4, False),
+               (3, 3, 0, 0, True)]
+EDGE_EXACT_N = 4
+
+
+def _exact_n(name, n):
+    return (16 if n <= 13 else EDGE_EXACT_N) if name in EDGE_NAMES else EXACT_N
+
+
+def _edge(m, n, p, n_eq, box, B=16):
+    return cc.ls_problem(B, m, n, p, n_eq, 200 + m, box)
+
+
+EDGE_CASES = [("ls_m%d_n%d_p%d%s" % (s[0], s[1], s[2], "" if s[4] else "_no_box"), (lambda s=s: _edge(*s)), {}) for s in EDGE_SHAPES]
+EDGE_CASES += [("ls_m1_n1_p0", cc.ls_problem_free_bounds, {}), ("n26_p24", lambda: cc.random_problem(26, 24, 12, 16), {})]
+EDGE_NAMES = {c[0] for c in EDGE_CASES}
+CASES += EDGE_CASES
 
 
 @pytest.mark.parametrize("name,make,options", CASES, ids=[c[0] for c in CASES])
 def test_device_against_host_restatement(bt, name, make, options):
     P = make()
     v = P["v"]
+    assert name not in EDGE_NAMES or ((P["status"] == 0).all() and len(P["status"]) == 16)
     before = {k: getattr(bt, "_options", {}).get(k, DEFAULTS[k]) for k in options}
     for k, val in options.items():
         bt.set_option(k, val)
@@ -125,7 +96,7 @@ def test_device_against_host_restatement(bt, name, make, options):
         dev = bt.qp_certificate(x, **_kw(P, x, st, w, v))
         host = cc.host_certificates(P, x=x, status=st, working_set=w, v=v)
         if tol is None:
-            tol, err = _tolerance(P, host, v)
+            tol, err = _tolerance(P, host, v, _exact_n(name, x.shape[1]))
         worst = _compare(dev, host, P, x, tol, "%s, working set %s" % (name, "given" if w is not None else "read off x"))
         print("%s (working set %s): restatement against exact rationals %.2e, device against restatement at most %.2f of the allowed %.2e" % (
             name, "given" if w is not None else "read off x", err, worst, tol))
@@ -134,6 +105,137 @@ def test_device_against_host_restatement(bt, name, make, options):
     assert set(dev0) == set(dev) - {"sens_x", "sens_bounds", "sens_rows"}
     devw = bt.qp_certificate(x, **_kw(P, x, st, ws, v))
     assert all(devguard.same_bytes(dev0[k], devw[k]) for k in dev0)
+
+
+def _solve(bt, P):
+    """the device's answer with its working set, held to the oracle's status"""
+    if P.get("A") is not None:
+        x, st, _, ws = bt.qp_solve_ls(P["A"], P["b"], P["C"], P["lb"], P["ub"], P["Clb"], P["Cub"], want_working_set=True)
+    else:
+        x, st, _, ws = bt.qp_solve(P["H"], P["g"], P["C"], P["lb"], P["ub"], P["Clb"], P["Cub"], want_working_set=True)
+    assert np.array_equal(st, P["status"])
+    return x, st, ws
+
+
+def _both(bt, P, x, st, ws, v):
+    return bt.qp_certificate(x, **_kw(P, x, st, ws, v)), cc.host_certificates(P, x=x, status=st, working_set=ws, v=v)
+
+
+@pytest.mark.parametrize("case", ["vertex", "more_normals_than_variables", "non_optimal_x", "working_set_rules", "read_off_rule"])
+def test_certificate_of_special_active_sets(bt, case):
+    """Device against restatement (the rule and _compare of test_device_against_host_restatement) where the active set is special:
+    vertex — k == n, the normals span the space, u = 0; more_normals_than_variables — k > n, DEPENDENT before the Cholesky; non_optimal_x — an
+    x off the optimum three ways, so that kkt[1], kkt[2] and kkt[3] are NOT zero (the tolerance is the one of the same data at the optimum: the
+    conditioning is the data's); working_set_rules — bits on infinite sides, bits beyond n and p, both bits at once, equalities whatever their
+    bits; read_off_rule — without a working set, a variable 0.5e-7 from its bound counts as active and one 2e-7 from it does not."""
+    if case == "vertex":
+        P = cc.vertex_problem()
+        x, st, ws = _solve(bt, P)
+        for w in (ws, None):
+            dev, host = _both(bt, P, x, st, w, P["v"])
+            assert (st == 0).all() and (host["n_active"] == 6).all() and np.abs(host["sens_x"]).max() <= 5e-17
+            tol, err = _tolerance(P, host, P["v"], EDGE_EXACT_N)
+            worst = _compare(dev, host, P, x, tol, case)                                          # (sens_bounds among the rest)
+            assert (dev["cert_status"] == capi.CERT_OK).all() and np.abs(dev["sens_x"]).max() <= tol * 1.0
+            print("vertex: restatement against exact rationals %.2e, device at most %.2f of the allowed %.2e" % (err, worst, tol))
+    elif case == "more_normals_than_variables":
+        P = cc.overdetermined_problem()
+        x, st, ws = _solve(bt, P)
+        for w in (ws, None):
+            dev, host = _both(bt, P, x, st, w, P["v"])
+            assert (st == 0).all() and (host["cert_status"] == capi.CERT_DEPENDENT).all() and (host["n_active"] == 8).all()
+            tol, _ = _tolerance(P, host, P["v"])                                                   # nothing certified: ten ulp
+            assert tol == 10.0 * ULP
+            _compare(dev, host, P, x, tol, case)                                                   # objective and kkt[1] among the rest
+            assert (dev["cert_status"] == capi.CERT_DEPENDENT).all() and (dev["n_active"] == 8).all()
+            assert (dev["kkt"][:, [0, 2, 3]] == 0).all()
+            assert all((dev[k] == 0).all() for k in ("y_bounds", "y_rows", "sens_x", "sens_bounds", "sens_rows"))
+    elif case == "non_optimal_x":
+        P = cc.random_problem(26, 16, 12)
+        x, st, ws = _solve(bt, P)
+        assert (st == 0).all()
+        tol, err = _tolerance(P, cc.host_certificates(P, x=x, status=st, working_set=ws, v=P["v"]), P["v"])
+        for way in ("flip", "outside", "shift"):
+            x2, ws2, moved = cc.off_optimum(P, x, ws, way)
+            dev, host = _both(bt, P, x2, st, ws2, P["v"])
+            k = host["kkt"][moved]
+            assert moved.sum() >= len(x) // 2 and (host["cert_status"] == capi.CERT_OK).all()
+            assert (k[:, 1] > 0).all() and (k[:, 3] > 0).all()
+            # a multiplier of the wrong sign: at every flipped bound, at some of the variables pushed outside; a shift of 1e-4 changes no sign
+            assert (k[:, 2] > 0).all() if way == "flip" else (k[:, 2] > 0).any() if way == "outside" else True
+            assert way != "outside" or (k[:, 1] >= 1e-3 * (1 - 1e-9)).all()
+            worst = _compare(dev, host, P, x2, tol, "%s, %s" % (case, way))
+            print("non-optimal x (%s): %d moved, kkt[2] > 0 on %d; device at most %.2f of the allowed %.2e" % (way, moved.sum(), (k[:, 2] > 0).sum(), worst, tol))
+    elif case == "working_set_rules":
+        full = np.uint64(0xFFFFFFFFFFFFFFFF)
+        # bits on infinite sides: no box at all, every bit of word 0 set
+        P = _edge(33, 26, 24, 4, False)
+        x, st, ws = _solve(bt, P)
+        plain, host = _both(bt, P, x, st, ws, P["v"])
+        tol, _ = _tolerance(P, host, P["v"], EDGE_EXACT_N)
+        worst = [_compare(plain, host, P, x, tol, case + ", no box")]
+        for word0 in (full, np.uint64(0x00000000FFFFFFFF), np.uint64(0xFFFFFFFF00000000)):
+            w2 = ws.copy().view(np.uint64)
+            w2[:, 0] = word0
+            w2 = w2.view(np.int64)
+            dev, host2 = _both(bt, P, x, st, w2, P["v"])
+            assert devguard.same_bytes(dev, plain) and np.array_equal(host2["n_active"], host["n_active"]), hex(int(word0))
+        # bits at variable positions >= n and row positions >= p
+        P = _edge(47, 13, 5, 2, True)
+        n, p = 13, 5
+        x, st, ws = _solve(bt, P)
+        plain, host = _both(bt, P, x, st, ws, P["v"])
+        tol, _ = _tolerance(P, host, P["v"], 16)
+        worst.append(_compare(plain, host, P, x, tol, case + ", (47, 13, 5)"))
+        w2 = ws.copy().view(np.uint64)
+        low = lambda k: np.uint64(((1 << 32) - (1 << k)) * ((1 << 32) + 1))                          # bits k..31 of both halves
+        for rows, extra in ((slice(0, 16, 2), (low(n), low(p))), (slice(1, 16, 2), (np.uint64(1 << n), np.uint64(1 << (32 + p))))):
+            w2[rows, 0] |= extra[0]
+            w2[rows, 1] |= extra[1]
+        assert (w2 != ws.view(np.uint64)).all()
+        dev, host2 = _both(bt, P, x, st, w2.view(np.int64), P["v"])
+        assert devguard.same_bytes(dev, plain) and np.array_equal(host2["n_active"], host["n_active"])
+        # both bits at once: inactive; an equality: active whatever its bits
+        P = cc.random_problem(26, 16, 12)
+        x, st, ws = _solve(bt, P)
+        plain, host = _both(bt, P, x, st, ws, P["v"])
+        tol, _ = _tolerance(P, host, P["v"])
+        both, none, eq = ws.copy(), ws.copy(), ws.copy()
+        hit = np.zeros(len(x), dtype=bool)
+        for i in range(len(x)):
+            for word, j in [(0, j) for j in range(24)] + [(1, j) for j in range(12, 16)]:        # the inequalities: variables 0..23, rows 12..15
+                if cc.ws_bits(ws, i, word, j) in (1, 2):
+                    cc.ws_set(both, i, word, j, 3)
+                    cc.ws_set(none, i, word, j, 0)
+                    hit[i] = True
+                    break
+            for j in (24, 25):                                                                     # the fixed pair and the twelve equality rows
+                cc.ws_set(eq, i, 0, j, (0, 3)[j - 24])
+            for j in range(12):
+                cc.ws_set(eq, i, 1, j, (0, 2, 3, 1)[(i + j) % 4])
+        assert hit.sum() >= len(x) // 2 and (eq != ws).any(axis=1).all()
+        dev_b, host_b = _both(bt, P, x, st, both, P["v"])
+        dev_n, host_n = _both(bt, P, x, st, none, P["v"])
+        assert devguard.same_bytes(dev_b, dev_n) and np.array_equal(host_b["n_active"], host["n_active"] - hit)
+        worst.append(_compare(dev_b, host_b, P, x, tol, case + ", both bits"))
+        dev_e, host_e = _both(bt, P, x, st, eq, P["v"])
+        assert devguard.same_bytes(dev_e, plain) and np.array_equal(host_e["n_active"], host["n_active"])
+        worst.append(_compare(dev_e, host_e, P, x, tol, case + ", equalities"))
+        print("working-set rules: device at most %.2f of the allowed tolerance" % max(worst))
+    else:
+        P = cc.random_problem(26, 16, 12)
+        x, st, ws = _solve(bt, P)
+        tol, _ = _tolerance(P, cc.host_certificates(P, x=x, status=st, working_set=ws, v=P["v"]), P["v"])
+        x2, near, far = cc.near_bounds(P, x, ws)
+        dev, host = _both(bt, P, x2, st, None, P["v"])
+        rows = np.arange(len(x))
+        assert (host["side"][rows, near] == 1).all() and (host["side"][rows, far] == 0).all()
+        assert np.array_equal(dev["n_active"], host["n_active"]) and np.array_equal(dev["cert_status"], host["cert_status"])
+        yd, yh = np.concatenate([dev["y_bounds"], dev["y_rows"]], axis=1), np.concatenate([host["y_bounds"], host["y_rows"]], axis=1)
+        certified = host["cert_status"] == capi.CERT_OK
+        assert certified.sum() >= len(x) // 2 and np.array_equal(yd[certified] != 0, yh[certified] != 0)
+        assert (yd[rows, far] == 0).all() and (yh[rows, near][certified] != 0).all()
+        print("read-off rule: device at most %.2f of the allowed %.2e" % (_compare(dev, host, P, x2, tol, case), tol))
 
 
 def test_golden_cases_in_one_batch(bt):

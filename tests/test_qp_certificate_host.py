@@ -185,3 +185,119 @@ def test_golden_qp_cases():
     assert wbc_workload.qp_certificate(P["x"][i], **dict(kw, H=Hn))["cert_status"] == capi.CERT_NUMERICAL
     c = wbc_workload.qp_certificate(P["x"][i], **dict(kw, H=-kw["H"]))
     assert c["cert_status"] == capi.CERT_NUMERICAL and c["objective"] == 0 and c["n_active"] == 0 and (c["kkt"] == 0).all()
+
+
+# ---- the ends of the documented range (the shapes tests/test_gpu_qp_certificate.py sends through the device)
+ULP = 2.220446049250313e-16
+# (m, n, p, equalities, box) of cert_common.ls_problem, B = 16, seed 200 + m; then n = m = 1 and p = 24 in the (H, g) form. Largest relative error of
+# y, u and w against the exact rationals over the first four instances, as measured: 1.68e-15, 1.11e-15, 7.03e-16, 1.76e-15, 1.73e-17, 1.44e-15,
+# 3.93e-14 (n = 3: one free variable next to the fixed pair), 1.43e-16, 3.84e-15; the bounds are 10 x those, and 10 ulp where that is less
+EDGE = [("ls_96_26_24", lambda: cc.ls_problem(16, 96, 26, 24, 12, 296, True), 1.68e-14), ("ls_49_26_16", lambda: cc.ls_problem(16, 49, 26, 16, 12, 249, True), 1.11e-14),
+        ("ls_47_13_5", lambda: cc.ls_problem(16, 47, 13, 5, 2, 247, True), 7.03e-15), ("ls_48_26_17", lambda: cc.ls_problem(16, 48, 26, 17, 8, 248, True), 1.76e-14),
+        ("ls_95_26_0_no_box", lambda: cc.ls_problem(16, 95, 26, 0, 0, 295, False), 10 * ULP), ("ls_33_26_24_no_box", lambda: cc.ls_problem(16, 33, 26, 24, 4, 233, False), 1.44e-14),
+        ("ls_3_3_0", lambda: cc.ls_problem(16, 3, 3, 0, 0, 203, True), 3.93e-13), ("ls_1_1_0", cc.ls_problem_free_bounds, 10 * ULP),
+        ("n26_p24", lambda: cc.random_problem(26, 24, 12, 16), 3.84e-14), ("vertex_30_6", cc.vertex_problem, 4.70e-15)]
+
+
+@pytest.mark.parametrize("name,make,bound", EDGE, ids=[e[0] for e in EDGE])
+def test_restatement_against_exact_rationals_at_the_ends_of_the_range(name, make, bound):
+    """every instance solved by the oracle and certified OK with no wrong-signed multiplier, read off x and with the working set given alike; y, u and
+    w of the first four against the exact rationals"""
+    P = make()
+    assert len(P["x"]) == 16 and (P["status"] == 0).all()
+    full = cc.host_certificates(P, status=P["status"], v=P["v"])
+    assert (full["cert_status"] == capi.CERT_OK).all() and (full["kkt"][:, 2] == 0).all()
+    given = cc.host_certificates(P, status=P["status"], working_set=cc.working_sets(P, P["x"]), v=P["v"])
+    assert all(np.array_equal(full[k], given[k]) for k in full)
+    idx = list(range(4))
+    err = cc.restatement_error(P, {k: a[idx] for k, a in full.items()}, idx, P["v"])
+    print("%s: y, u, w against the exact rationals, largest relative error %.3e (bound %.1e); active %d..%d" % (
+        name, err, bound, full["n_active"].min(), full["n_active"].max()))
+    assert err <= bound, err
+    if name == "ls_95_26_0_no_box":
+        assert (full["n_active"] == 0).all() and (full["y_bounds"] == 0).all() and full["y_rows"].shape == (16, 0)
+    if name == "vertex_30_6":                                        # k == n: the normals span the space
+        assert (full["n_active"] == 6).all() and np.abs(full["sens_x"]).max() <= 5e-17
+
+
+def test_more_active_normals_than_variables():
+    """k > n: eight equality rows through the origin on five variables. DEPENDENT before any factorisation; violation, objective and k are given"""
+    P = cc.overdetermined_problem()
+    assert (P["status"] == 0).all()
+    for ws in (None, cc.working_sets(P, P["x"])):
+        cert = cc.host_certificates(P, status=P["status"], working_set=ws, v=P["v"])
+        assert (cert["cert_status"] == capi.CERT_DEPENDENT).all() and (cert["n_active"] == 8).all() and (cert["side"][:, 5:] == 3).all()
+        assert all((cert[k] == 0).all() for k in ("y_bounds", "y_rows", "sens_x", "sens_bounds", "sens_rows")) and (cert["kkt"][:, [0, 2, 3]] == 0).all()
+        assert np.abs(cert["objective"]).max() <= 1e-25 and np.abs(cert["kkt"][:, 1]).max() <= 1e-25      # x = 0 to rounding
+    x = np.full_like(P["x"], 0.1)                                    # away from the feasible point: the two that are still given, at their values
+    cert = cc.host_certificates(P, x=x, v=P["v"])
+    obj = np.array([0.5 * (A @ xi) @ (A @ xi) - b @ (A @ xi) for A, b, xi in zip(P["A"], P["b"], x)])
+    viol = np.abs(np.einsum("bpi,bi->bp", P["C"], x)).max(axis=1)
+    assert (cert["cert_status"] == capi.CERT_DEPENDENT).all() and (cert["n_active"] == 8).all() and (viol > 1e-3).all()
+    assert np.allclose(cert["objective"], obj, rtol=1e-12, atol=0) and np.allclose(cert["kkt"][:, 1], viol, rtol=1e-12, atol=0)
+
+
+def test_working_set_rules_of_the_restatement():
+    """qp_active_sides / qp_certificate: a bit on an infinite side, bits beyond n and p, both bits at once, equalities whatever their bits, and the
+    1e-7 rule that reads the set off x"""
+    full = np.uint64(0xFFFFFFFFFFFFFFFF)
+    P = cc.ls_problem(16, 33, 26, 24, 4, 233, False)                                          # no box: every side of every variable is infinite
+    ws = cc.working_sets(P, P["x"])
+    plain = cc.host_certificates(P, working_set=ws, v=P["v"])
+    w2 = ws.copy().view(np.uint64)
+    w2[:, 0] = full
+    marked = cc.host_certificates(P, working_set=w2.view(np.int64), v=P["v"])
+    assert all(np.array_equal(plain[k], marked[k]) for k in plain) and (plain["side"][:, :26] == 0).all()
+    i = 0
+    kw = cc.instance(P, i)
+    inf = dict(lb=np.full(26, -1e20), ub=np.full(26, np.inf))                                  # +-1e20 and beyond: no bound
+    side = wbc_workload.qp_active_sides(P["x"][i], kw["C_"], inf["lb"], inf["ub"], kw["Clb"], kw["Cub"], w2.view(np.int64)[i])[0]
+    assert np.array_equal(side, plain["side"][i])
+    P = cc.ls_problem(16, 47, 13, 5, 2, 247, True)                                            # bits beyond n = 13 and p = 5
+    ws = cc.working_sets(P, P["x"])
+    plain = cc.host_certificates(P, working_set=ws, v=P["v"])
+    w2 = ws.copy().view(np.uint64)
+    w2[:, 0] |= np.uint64(((1 << 32) - (1 << 13)) * ((1 << 32) + 1))
+    w2[:, 1] |= np.uint64(((1 << 32) - (1 << 5)) * ((1 << 32) + 1))
+    marked = cc.host_certificates(P, working_set=w2.view(np.int64), v=P["v"])
+    assert all(np.array_equal(plain[k], marked[k]) for k in plain)
+    P = cc.random_problem(26, 16, 12)                                                         # both bits; equalities
+    x = P["x"]
+    ws = cc.working_sets(P, x)
+    plain = cc.host_certificates(P, working_set=ws)
+    assert all(np.array_equal(plain[k], a) for k, a in cc.host_certificates(P).items())       # (the set read off x is the set given)
+    both, none, eq = ws.copy(), ws.copy(), ws.copy()
+    hit = np.zeros(len(x), dtype=bool)
+    for i in range(len(x)):
+        for word, j in [(0, j) for j in range(24)] + [(1, j) for j in range(12, 16)]:
+            if cc.ws_bits(ws, i, word, j) in (1, 2):
+                cc.ws_set(both, i, word, j, 3)
+                cc.ws_set(none, i, word, j, 0)
+                hit[i] = True
+                break
+        for j in (24, 25):
+            cc.ws_set(eq, i, 0, j, (0, 3)[j - 24])
+        for j in range(12):
+            cc.ws_set(eq, i, 1, j, (0, 2, 3, 1)[(i + j) % 4])
+    cb, cn, ce = (cc.host_certificates(P, working_set=w) for w in (both, none, eq))
+    assert hit.sum() >= len(x) // 2 and np.array_equal(cb["n_active"], plain["n_active"] - hit)
+    assert all(np.array_equal(cb[k], cn[k]) for k in cb) and all(np.array_equal(ce[k], plain[k]) for k in ce)
+    assert (plain["side"][:, 24:26] == 3).all() and (plain["side"][:, 26:38] == 3).all()
+    x2, near, far = cc.near_bounds(P, x, ws)                                                   # the read-off rule
+    rows = np.arange(len(x))
+    c2 = cc.host_certificates(P, x=x2)
+    assert (c2["side"][rows, near] == 1).all() and (c2["side"][rows, far] == 0).all() and (c2["y_bounds"][rows, far] == 0).all()
+    ok = c2["cert_status"] == capi.CERT_OK
+    assert ok.sum() >= len(x) // 2 and (c2["y_bounds"][rows, near][ok] != 0).all() and np.array_equal(c2["n_active"], (c2["side"] != 0).sum(axis=1))
+
+
+def test_residuals_of_a_non_optimal_x():
+    """x off the optimum three ways (cert_common.off_optimum): the violation and the complementarity product are nonzero on every moved instance, a
+    wrong-signed multiplier at every flipped bound and at some of the variables pushed outside"""
+    P = cc.random_problem(26, 16, 12)
+    ws = cc.working_sets(P, P["x"])
+    for way in ("flip", "outside", "shift"):
+        x2, ws2, moved = cc.off_optimum(P, P["x"], ws, way)
+        k = cc.host_certificates(P, x=x2, working_set=ws2)["kkt"][moved]
+        assert moved.sum() >= len(x2) // 2 and (k[:, 1] > 0).all() and (k[:, 3] > 0).all(), way
+        assert (k[:, 2] > 0).all() if way == "flip" else (k[:, 2] > 0).any() if way == "outside" else (k[:, 2] == 0).all(), way
