@@ -45,7 +45,7 @@ struct XIntegrate { const double* in; const double* xv; };   // what integrate_f
 #else
 #define XSTOP(k, val) do { } while (0)
 #endif
-// WARM: the variant that takes / returns working sets (KernelArgs.ws_in / ws_out, word 0: velocity bounds by DoF) — the packed sim3 kernel's scheme
+// WARM: the variant that takes / returns working sets (KernelArgs.ws_in / ws_out, word 0: velocity bounds by DoF) — wbc_k_sim3p.hip's warm start
 // (seeds through the add step, x / u rebuilt from the factors, restoration) on the kept variables; eliminated and locked DoF carry no seed.
 // ROT: rotated joint placements in the batch (wbc_k_sim3p.hip). TP: per-instance weights and gains (wbc_tick_tp: the kernel's fifth parameter
 // tps [B]) staged into wt in place of the configuration's block; a row with a non-finite entry or joint_w == 0 gives its instance
@@ -384,113 +384,25 @@ __global__ void __launch_bounds__(64, 2) wbc_tick_boxp_kernel(const KernelArgs A
     x = has_b ? xa + xb : 0.0;
   }
   XSTOP(7, x + jf2);
-  // ---- dual active-set iterations (the packed sim3 kernel's, bounds only; per-row state; loops run until every row of the wave is done)
+  // ---- dual active-set iterations (wbc_k_sim3p.hip's loop, bounds only; per-row state; loops run until every row of the wave is done)
   bool act_b = false, overflow = false;
   double u = 0.0;
   int a_code = 0, q = 0, iters = 0;
   const int max_iter = 10 * nv + 20;        // (the full problem's cap: n = nv unknowns, no rows — the oracle's count includes the locked DoF this kernel leaves out)
   bool searching = live;
   const int sT = s < XTC ? s : XTC - 1;      // (lanes beyond T's rows shadow its last row; they never write)
-  // drop slot l of the rows `dr`: Givens sequence read off the removed row of T (rare path)
+  // the working set's factor updates (wbc_packed.h pk_qp_*) on this kernel's J [16][XLD] (every lane carries a row), T [XTC][XTLD] and vectors
+  using Zr = PkZr;
   auto drop_slot = [&](const bool dr, const int l_) {
-    const int l = dr ? l_ : 0;
-    const int lc = bpermi(a_code, rbase + l) & 255;
-    if (dr && s == lc) act_b = false;
-    WSYNC();
-    yv[s] = u; tv[s] = (double)a_code;
-    WSYNC();
-    if (dr && s >= l && s < q - 1) { u = yv[s + 1]; a_code = (int)tv[s + 1]; }
-    if (dr && s == q - 1) { u = 0.0; a_code = 0; }
-    const int srow = (sT >= l) ? ((sT + 1 < XTC) ? sT + 1 : sT) : sT;
-    double tx = T[srow * XTLD + l];
-    double jx = J[s * XLD + l];
-    double hrun = T[l * XTLD + l];
-    const int kend = dr ? q - 1 : 0;    // this row's rotations run k = l .. q - 2
-#pragma unroll 1
-    for (int k0 = 0; k0 < XTC - 1; ++k0) {
-      const bool on = dr && (l + k0 < kend);
-      if (!__ballot(on)) break;
-      const int k = on ? l + k0 : 0;
-      const double tb = T[l * XTLD + k + 1];
-      const double nrm2 = fma(hrun, hrun, tb * tb);
-      double c_ = 1.0, s_ = 0.0, rho = 0.0;
-      if (nrm2 > 0.0) { const double ri = rsqrt(nrm2); c_ = tb * ri; s_ = -hrun * ri; rho = nrm2 * ri; }
-      const double ty_ = T[srow * XTLD + k + 1];
-      const double jy = J[s * XLD + k + 1];
-      WSYNC();
-      if (on) {
-        hrun = rho;
-        if (s < q - 1) T[s * XTLD + k] = fma(c_, tx, s_ * ty_);
-        if (has_b) J[s * XLD + k] = fma(c_, jx, s_ * jy);
-        tx = fma(-s_, tx, c_ * ty_);
-        jx = fma(-s_, jx, c_ * jy);
-      }
-      WSYNC();
-    }
-    WSYNC();
-    if (dr) {
-      if (s < q) T[s * XTLD + q - 1] = 0.0;
-    }
-    WSYNC();
-    if (dr) {
-      if (s < q) T[(q - 1) * XTLD + s] = 0.0;
-      if (has_b) J[s * XLD + q - 1] = jx;
-      --q;
-    }
-    WSYNC();
+    pk_qp_drop_slot<16, XLD, XTC, XTLD>(J, T, yv, tv, s, sT, s, rbase, has_b, dr, l_, u, a_code, q, [&](const int lc) { if (s == lc) act_b = false; });
   };
-  // with d staged (dv = d, yv = d restricted to the slots >= q): z = J2 d2, r = T d1, and the add step's dq = d_q, jq = J[s][q]
-  struct Zr { double z, rv, dq, jq; };
-  auto products = [&](const bool want_r) -> Zr {
-    Zr o;
-    double z = 0.0, zb = 0.0, rv = 0.0, rvb = 0.0;
-    o.dq = dv[q & 15];
-    o.jq = J[s * XLD + (q & 15)];
-#pragma unroll
-    for (int k = 0; k < 16; k += 2) {
-      const double2a j2 = lds2(J + s * XLD + k); const double2a y2 = lds2(yv + k);
-      z = fma(j2.x, y2.x, z); zb = fma(j2.y, y2.y, zb);
-    }
-    z += zb;
-    if (want_r) {                           // r = T d1: nothing to do while no row of the wave holds an active bound
-#pragma unroll
-      for (int k = 0; k < XTC; k += 2) {
-        const double2a t2 = lds2(T + sT * XTLD + k); const double2a d2_ = lds2(dv + k);
-        rv = fma(t2.x, d2_.x, rv); rvb = fma(t2.y, d2_.y, rvb);
-      }
-      rv += rvb;
-    }
-    if (s >= q) rv = 0.0;
-    if (!has_b) z = 0.0;
-    o.z = z; o.rv = rv;
-    return o;
-  };
-  // add: Householder P with P d2 = delta e1; J2 <- J2 P; T gets column (-r/delta, 1/delta); the new slot's multiplier is u_new
+  auto products = [&](const bool want_r) -> Zr { return pk_qp_products<16, XLD, XTC, XTLD>(J, T, dv, yv, s, sT, s, q, has_b, want_r); };
   auto add_step = [&](const bool add, const double zn, const Zr& zr, const int wc, const int ip, const double u_new) {
-    const double rsz = frsq(zn), sz = zn * rsz;
-    const double delta = (zr.dq >= 0.0) ? -sz : sz;
-    const double hv = zn - delta * zr.dq;               // v'v / 2
-    const double vv = 2.0 * hv;
-    const double w = (zr.z - delta * zr.jq) * ((vv > 0.0) ? frcp(hv) : 0.0);
-    if (add && has_b && vv > 0.0) {   // J2 <- J2 - w v', v = d2 - delta e_q (entry q stored with its own term after the sweep on d2)
-#pragma unroll
-      for (int k = 0; k < 16; k += 2) {
-        const double2a j2 = lds2(J + s * XLD + k); const double2a y2 = lds2(yv + k);   // yv = d for k >= q, else 0
-        sts2(J + s * XLD + k, fma(-w, y2.x, j2.x), fma(-w, y2.y, j2.y));
-      }
-      J[s * XLD + q] = fma(-w, zr.dq - delta, zr.jq);
-    }
-    if (add) {
-      const double idel = (zr.dq >= 0.0) ? -rsz : rsz;
-      if (s < q) T[s * XTLD + q] = -zr.rv * idel;
-      if (s == q) { T[s * XTLD + q] = idel; u = u_new; a_code = wc; }
-      if (s == (ip & 15)) act_b = true;
-      ++q;
-    }
+    pk_qp_add_step<16, XLD, XTC, XTLD>(J, T, yv, s, has_b, add, zn, zr, wc, u_new, u, a_code, q, [&] { if (s == (ip & 15)) act_b = true; });
   };
   if (WARM) {
     const unsigned long long ws0 = (unsigned long long)__double_as_longlong(I.in[27]);
-    int sb = has_b ? (int)(((ws0 >> (kv.dof & 31)) & 1ull) | (((ws0 >> (32 + (kv.dof & 31))) & 1ull) << 1)) : 0;
+    int sb = has_b ? pk_ws_bits(ws0, kv.dof) : 0;
     if (sb == 3) sb = 0;
     // a seed is taken only if the unconstrained minimiser x0 violates it or comes close to it (qp_core, solve_v3 `far`)
     const double x0r = x;

@@ -42,9 +42,9 @@ static_assert(offsetof(QInst, xv) - offsetof(QInst, cl) == 80 * sizeof(double), 
 // Robot_Wrapper4.py:707-754), CoM box (CoMConstraint, :669-694), the velocity box of every DoF (:572-637) — and the trunk task (tests/common.py
 // "everything"). In the reduced coordinates y (qd = Z y) the velocity bounds of the base and the stance legs are the ROWS of Z (six columns each),
 // the trunk and CoM boxes six dense rows (formed with the task blocks' own A Z machinery), the arm's bounds stay simple bounds: <= 24 rows, two per
-// lane, and the packed sim3 kernel's dual active-set method on n' <= 12 unknowns. An instance that needs more than 11 active constraints goes to
+// lane, and the packed kernels' dual active-set method (wbc_packed.h pk_qp_*) on n' <= 12 unknowns. An instance that needs more than 11 active constraints goes to
 // the tail with the flagged ones.
-// WARM (INEQ only): working sets in and out — the packed sim3 kernel's scheme (seeds through the add step, x / u rebuilt from the factors, restoration).
+// WARM (INEQ only): working sets in and out — wbc_k_sim3p.hip's warm start (seeds through the add step, x / u rebuilt from the factors, restoration).
 // In FULL-problem indexing a row of Z is the velocity bound of its DoF (word 0), the trunk / CoM box rows are findConstraints' rows (word 1).
 // ROT: rotated joint placements in the batch (wbc_k_sim3p.hip). TP: per-instance weights and gains (wbc_tick_tp: the kernel's fifth parameter
 // tps [B]) staged into wt in place of the configuration's block; a row with a non-finite entry or joint_w == 0 gives its instance
@@ -533,7 +533,7 @@ __global__ void __launch_bounds__(64, 2) wbc_tick_orthp_kernel(const KernelArgs 
   }
   int iters = 0;
   if (INEQ) {
-    // ================================ the QP (INEQ variant): the packed sim3 kernel's dual active-set method =====================================
+    // ================================ the QP (INEQ variant): the dual active-set loop on wbc_packed.h's factor updates (pk_qp_*) ===================
     // unknowns: the n' <= 12 reduced variables (lane s); simple bounds on the arm's; rows 0..5 dense (Cd [6][16]), rows 6 + j = row j of Z (six
     // base-reduced columns): lane s owns rows s and 16 + s (< 24). Codes: bound of variable i = i, row rr = 32 + rr, upper side + 256.
     constexpr int QPV = 12, QLD = 14, QTC = 11;
@@ -626,108 +626,24 @@ __global__ void __launch_bounds__(64, 2) wbc_tick_orthp_kernel(const KernelArgs 
       const bool mine = (code >= 32) ? (s == (rr & 15)) : (s == code);
       if (mine) actm = val ? (actm | bit) : (actm & ~bit);
     };
+    // the working set's factor updates (wbc_packed.h pk_qp_*) on this kernel's J [QPV][QLD], T [QTC][QLD] and vectors
+    using Zr = PkZr;
     auto drop_slot = [&](const bool dr, const int l_) {
-      const int l = dr ? l_ : 0;
-      const int lc = bpermi(a_code, rbase + l) & 255;
-      if (dr) set_act(lc, false);
-      WSYNC();
-      qyv[s] = u; qtv[s] = (double)a_code;
-      WSYNC();
-      if (dr && s >= l && s < q - 1) { u = qyv[s + 1]; a_code = (int)qtv[s + 1]; }
-      if (dr && s == q - 1) { u = 0.0; a_code = 0; }
-      const int srow = (sT >= l) ? ((sT + 1 < QTC) ? sT + 1 : sT) : sT;
-      double tx = T[srow * QLD + l];
-      double jx = J[sJ * QLD + l];
-      double hrun = T[l * QLD + l];
-      const int kend = dr ? q - 1 : 0;
-#pragma unroll 1
-      for (int k0 = 0; k0 < QTC - 1; ++k0) {
-        const bool on = dr && (l + k0 < kend);
-        if (!__ballot(on)) break;
-        const int kk = on ? l + k0 : 0;
-        const double tb = T[l * QLD + kk + 1];
-        const double nrm2 = fma(hrun, hrun, tb * tb);
-        double c_ = 1.0, s_ = 0.0, rho = 0.0;
-        if (nrm2 > 0.0) { const double ri = rsqrt(nrm2); c_ = tb * ri; s_ = -hrun * ri; rho = nrm2 * ri; }
-        const double ty_ = T[srow * QLD + kk + 1];
-        const double jy = J[sJ * QLD + kk + 1];
-        WSYNC();
-        if (on) {
-          hrun = rho;
-          if (s < q - 1) T[s * QLD + kk] = fma(c_, tx, s_ * ty_);
-          if (has_b) J[s * QLD + kk] = fma(c_, jx, s_ * jy);
-          tx = fma(-s_, tx, c_ * ty_);
-          jx = fma(-s_, jx, c_ * jy);
-        }
-        WSYNC();
-      }
-      WSYNC();
-      if (dr) { if (s < q) T[s * QLD + q - 1] = 0.0; }
-      WSYNC();
-      if (dr) {
-        if (s < q) T[(q - 1) * QLD + s] = 0.0;
-        if (has_b) J[s * QLD + q - 1] = jx;
-        --q;
-      }
-      WSYNC();
+      pk_qp_drop_slot<QPV, QLD, QTC, QLD>(J, T, qyv, qtv, sJ, sT, s, rbase, has_b, dr, l_, u, a_code, q, [&](const int lc) { set_act(lc, false); });
     };
-    struct Zr { double z, rv, dq, jq; };
-    auto products = [&](const bool want_r) -> Zr {
-      Zr o;
-      double z = 0.0, zb = 0.0, rv = 0.0, rvb = 0.0;
-      o.dq = qdv[q & 15];
-      o.jq = J[sJ * QLD + (q & 15)];
-#pragma unroll
-      for (int k = 0; k < QPV; k += 2) {
-        const double2a j2 = lds2(J + sJ * QLD + k); const double2a y2 = lds2(qyv + k);
-        z = fma(j2.x, y2.x, z); zb = fma(j2.y, y2.y, zb);
-      }
-      z += zb;
-      if (want_r) {
-#pragma unroll
-        for (int k = 0; k < QPV; k += 2) {
-          const double2a t2 = lds2(T + sT * QLD + k); const double2a d2_ = lds2(qdv + k);
-          rv = fma(t2.x, d2_.x, rv); rvb = fma(t2.y, d2_.y, rvb);
-        }
-        rv += rvb;
-      }
-      if (s >= q) rv = 0.0;
-      if (!has_b) z = 0.0;
-      o.z = z; o.rv = rv;
-      return o;
-    };
+    auto products = [&](const bool want_r) -> Zr { return pk_qp_products<QPV, QLD, QTC, QLD>(J, T, qdv, qyv, sJ, sT, s, q, has_b, want_r); };
     auto add_step = [&](const bool add, const double zn, const Zr& zr, const int wc, const double u_new) {
-      const double rsz = frsq(zn), sz = zn * rsz;
-      const double delta = (zr.dq >= 0.0) ? -sz : sz;
-      const double hv = zn - delta * zr.dq;
-      const double vv = 2.0 * hv;
-      const double w = (zr.z - delta * zr.jq) * ((vv > 0.0) ? frcp(hv) : 0.0);
-      if (add && has_b && vv > 0.0) {
-#pragma unroll
-        for (int k = 0; k < QPV; k += 2) {
-          const double2a j2 = lds2(J + s * QLD + k); const double2a y2 = lds2(qyv + k);
-          sts2(J + s * QLD + k, fma(-w, y2.x, j2.x), fma(-w, y2.y, j2.y));
-        }
-        J[s * QLD + q] = fma(-w, zr.dq - delta, zr.jq);
-      }
-      if (add) {
-        const double idel = (zr.dq >= 0.0) ? -rsz : rsz;
-        if (s < q) T[s * QLD + q] = -zr.rv * idel;
-        if (s == q) { T[s * QLD + q] = idel; u = u_new; a_code = wc; }
-        set_act(wc & 255, true);
-        ++q;
-      }
+      pk_qp_add_step<QPV, QLD, QTC, QLD>(J, T, qyv, s, has_b, add, zn, zr, wc, u_new, u, a_code, q, [&] { set_act(wc & 255, true); });
     };
     if (WARM) {
-      // ================================ warm start (the packed sim3 kernel's scheme) ====================================================
+      // ================================ warm start: seeds, refresh and restoration as in wbc_k_sim3p.hip, on this kernel's three constraint groups =====
       const unsigned long long ws0 = ((unsigned long long)(unsigned)bpermi((int)(ws_mine >> 32), rbase) << 32) | (unsigned)bpermi((int)(unsigned)ws_mine, rbase);
       const unsigned long long ws1 = ((unsigned long long)(unsigned)bpermi((int)(ws_mine >> 32), rbase + 1) << 32) | (unsigned)bpermi((int)(unsigned)ws_mine, rbase + 1);
-      auto bits = [](const unsigned long long w, const int i) -> int { return (int)(((w >> (i & 31)) & 1ull) | (((w >> (32 + (i & 31))) & 1ull) << 1)); };
       const int tbase = c_con_com ? 2 : 0;   // findConstraints' order: CoM rows, then the trunk box
       const int dofv = P.q_red2dof[s & 15], dofr0 = P.q_bl2dof[(s >= 6 ? s - 6 : 0) % 18], dofr1 = P.q_bl2dof[(10 + s) % 18];
-      int sb = (has_b && s >= 6) ? bits(ws0, dofv) : 0;
-      int sr0 = (s < 4) ? (c_con_trunk ? bits(ws1, tbase + s) : 0) : ((s < 6) ? (c_con_com ? bits(ws1, s - 4) : 0) : bits(ws0, dofr0));
-      int sr1 = has_r1 ? bits(ws0, dofr1) : 0;
+      int sb = (has_b && s >= 6) ? pk_ws_bits(ws0, dofv) : 0;
+      int sr0 = (s < 4) ? (c_con_trunk ? pk_ws_bits(ws1, tbase + s) : 0) : ((s < 6) ? (c_con_com ? pk_ws_bits(ws1, s - 4) : 0) : pk_ws_bits(ws0, dofr0));
+      int sr1 = has_r1 ? pk_ws_bits(ws0, dofr1) : 0;
       if (sb == 3) sb = 0;
       if (sr0 == 3) sr0 = 0;
       if (sr1 == 3) sr1 = 0;

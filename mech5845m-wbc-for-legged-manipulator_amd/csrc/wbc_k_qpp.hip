@@ -372,7 +372,7 @@ __global__ void __launch_bounds__(64, 2) wbc_qp_packed_kernel(const QpArgs A) {
     if (k < qm) { const double t0 = TP[tri(k) + s]; rv = fma((s <= k && k < q) ? t0 : 0.0, vec[k], rv); }
     return rv + rvb;
   };
-  // drop slot l of the problems `dr`: Givens sequence read off the removed row of T (rare path)
+  // drop slot l of the problems `dr` (rare path): wbc_packed.h pk_qp_drop_slot's steps on the packed triangle TP
   auto drop_slot = [&](const bool dr, const int l_) {
     const int l = dr ? l_ : 0;
     const int lc = bpermi(a_code, rbase + l) & 255;
@@ -392,10 +392,8 @@ __global__ void __launch_bounds__(64, 2) wbc_qp_packed_kernel(const QpArgs A) {
       const bool on = dr && (l + k0 < kend);
       if (!__ballot(on)) break;
       const int k = on ? l + k0 : 0;
-      const double tb = TP[tri(k + 1) + l];
-      const double nrm2 = fma(hrun, hrun, tb * tb);
-      double c_ = 1.0, s_ = 0.0, rho = 0.0;
-      if (nrm2 > 0.0) { const double ri = rsqrt(nrm2); c_ = tb * ri; s_ = -hrun * ri; rho = nrm2 * ri; }
+      const PkGivens g = pk_givens(hrun, TP[tri(k + 1) + l]);      // (wbc_packed.h)
+      const double c_ = g.c, s_ = g.s, rho = g.rho;
       const double ty_ = (on && srow <= k + 1) ? TP[tri(k + 1) + srow] : 0.0;
       const double jy = J[sv * LD + k + 1];
       WSYNC();
@@ -440,16 +438,12 @@ __global__ void __launch_bounds__(64, 2) wbc_qp_packed_kernel(const QpArgs A) {
     o.z = z; o.rv = rv;
     return o;
   };
-  // add: Householder P with P d2 = delta e1; J2 <- J2 P; T gets column (-r/delta, 1/delta); the new slot's multiplier is u_new
+  // add the constraint as slot q: wbc_packed.h pk_qp_add_step's steps on TP and on J's row in registers (jr, from `products`); returns delta
   auto add_step = [&](const bool add, const double zn, const Zr& zr, const int wc, const bool is_row, const int rr_, const int ip, const double u_new) -> double {
-    const double rsz = frsq(zn), sz = zn * rsz;
-    const double delta = (zr.dq >= 0.0) ? -sz : sz;
-    const double hv = zn - delta * zr.dq;               // v'v / 2
-    const double vv = 2.0 * hv;
     const double jq = zr.jq;
-    const double w = (zr.z - delta * jq) * ((vv > 0.0) ? frcp(hv) : 0.0);
-    if (add && has_b && vv > 0.0) {
-      // J2 <- J2 - w v', v = d2 - delta e_q: the sweep runs on d2 alone (yv = d for k >= q, else 0), entry q is then stored with its own term
+    const PkHouse hh = pk_householder(zn, zr.dq, zr.z, jq);      // (wbc_packed.h)
+    const double delta = hh.delta, w = hh.w;
+    if (add && has_b && hh.ok) {
 #pragma unroll
       for (int k = 0; k < PV; k += 2) {
         double2a v2;
@@ -459,7 +453,7 @@ __global__ void __launch_bounds__(64, 2) wbc_qp_packed_kernel(const QpArgs A) {
       J[s * LD + q] = fma(-w, zr.dq - delta, jq);
     }
     if (add) {
-      const double idel = (zr.dq >= 0.0) ? -rsz : rsz;
+      const double idel = hh.idel;
       if (s < q) TP[tri(q) + s] = -zr.rv * idel;
       if (s == q) { TP[tri(q) + s] = idel; u = u_new; a_code = wc; }
       if (s == (is_row ? rr_ : ip)) actm |= is_row ? (2 | ((wc >> 8) << 3)) : (1 | ((wc >> 8) << 2));
@@ -519,8 +513,7 @@ __global__ void __launch_bounds__(64, 2) wbc_qp_packed_kernel(const QpArgs A) {
   // ================================ warm start ======================================================
   if (WARM && A.ws_in) {
     const unsigned long long w0 = A.ws_in[2 * b], w1 = A.ws_in[2 * b + 1];
-    auto bits = [](const unsigned long long w, const int i) -> int { return (int)(((w >> (i & 31)) & 1ull) | (((w >> (32 + (i & 31))) & 1ull) << 1)); };
-    int sb = has_b ? bits(w0, s) : 0, sr = has_r ? bits(w1, s) : 0;
+    int sb = has_b ? pk_ws_bits(w0, s) : 0, sr = has_r ? pk_ws_bits(w1, s) : 0;
     if (sb == 3) sb = 0;
     if (sr == 3) sr = 0;
     // a seed is taken only if the equalities-only minimiser violates it or comes close to it (within 0.25 max(1, |x|_inf): qp_core, solve_v3 `far`)

@@ -744,7 +744,11 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
     } else d = sgn * J[(ip & 15) * PLD + s];
     return d;
   };
-  // drop slot l of the rows `dr`: Givens sequence read off the removed row of T (rare path)
+  // The working set's factor updates: wbc_packed.h explains them (pk_qp_products, pk_qp_add_step, pk_qp_drop_slot). This kernel shares the Givens
+  // core and the seed decoder; its three steps stay written out, statement for statement the shared functions' on PV / PLD: as calls, the FIXD
+  // instantiations did not compile to the instructions they had. TO BE MIRRORED BY HAND: a change to pk_qp_products,
+  // pk_qp_add_step, pk_qp_drop_slot or pk_householder is made here too, with NJ = NT = PV, LDJ = LDT = PLD, sJ = sT = sv (srd in `products`: one
+  // shadow row serves J and T), J-store predicate s < n (= has_b), yv / tv / dv = V.yv / V.tv / V.dv, and the activity mark in actm
   auto drop_slot = [&](const bool dr, const int l_) {
     COLD_MARK();
     const int l = dr ? l_ : 0;
@@ -766,10 +770,8 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
       const bool on = dr && (l + k0 < kend);
       if (!__ballot(on)) break;
       const int k = on ? l + k0 : 0;
-      const double tb = T[l * PLD + k + 1];
-      const double nrm2 = fma(hrun, hrun, tb * tb);
-      double c_ = 1.0, s_ = 0.0, rho = 0.0;
-      if (nrm2 > 0.0) { const double ri = rsqrt(nrm2); c_ = tb * ri; s_ = -hrun * ri; rho = nrm2 * ri; }
+      const PkGivens g = pk_givens(hrun, T[l * PLD + k + 1]);
+      const double c_ = g.c, s_ = g.s, rho = g.rho;
       const double ty_ = T[srow * PLD + k + 1];
       const double jy = J[sv * PLD + k + 1];
       WSYNC();
@@ -794,21 +796,20 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
     }
     WSYNC();
   };
-  // with d staged (V.dv = d, V.yv = d restricted to the slots >= q): z = J2 d2, r = T d1, and the add step's dq = d_q, jq = J[s][q]
   struct Zr { double z, rv, dq, jq; };
   auto products = [&](const bool want_r) -> Zr {
     Zr o;
     double z = 0.0, zb = 0.0, rv = 0.0, rvb = 0.0;
     const int srd = s < PV ? s : PV - 1;
-    o.dq = V.dv[q & 15];                                                // d of slot q and this row's J entry there (the add step's): read
-    o.jq = J[srd * PLD + (q & 15)];                                     // in the same round as the products below
+    o.dq = V.dv[q & 15];
+    o.jq = J[srd * PLD + (q & 15)];
 #pragma unroll
     for (int k = 0; k < PV; k += 2) {
       const double2a j2 = lds2(J + srd * PLD + k); const double2a y2 = lds2(V.yv + k);
       z = fma(j2.x, y2.x, z); zb = fma(j2.y, y2.y, zb);
     }
     z += zb;
-    if (want_r) {                           // r = T d1: nothing to do while no row of the wave holds an active inequality
+    if (want_r) {
 #pragma unroll
       for (int k = 0; k < PV; k += 2) {
         const double2a t2 = lds2(T + srd * PLD + k); const double2a d2 = lds2(V.dv + k);
@@ -821,7 +822,6 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
     o.z = z; o.rv = rv;
     return o;
   };
-  // add: Householder P with P d2 = delta e1; J2 <- J2 P; T gets column (-r/delta, 1/delta); the new slot's multiplier is u_new
   auto add_step = [&](const bool add, const double zn, const Zr& zr, const int wc, const bool is_row, const int rr_, const int ip, const double u_new) {
     const double rsz = frsq(zn), sz = zn * rsz;
     const double delta = (zr.dq >= 0.0) ? -sz : sz;
@@ -829,8 +829,6 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
     const double vv = 2.0 * hv;
     const double w = (zr.z - delta * zr.jq) * ((vv > 0.0) ? frcp(hv) : 0.0);
     if (add && has_b && vv > 0.0) {
-      // J2 <- J2 - w v', v = d2 - delta e_q: the sweep runs on d2 alone (yv = d for k >= q, else 0) and entry q is then stored with its own term —
-      // the same arithmetic as selecting v_k inside the loop, without two compares and four selects per pair
 #pragma unroll
       for (int k = 0; k < PV; k += 2) {
         const double2a j2 = lds2(J + s * PLD + k); const double2a y2 = lds2(V.yv + k);
@@ -852,11 +850,10 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
   if (WARM) {
     const unsigned long long ws0 = (unsigned long long)__double_as_longlong(V.in[38]), ws1 = (unsigned long long)__double_as_longlong(V.in[39]);
     dofR = bpermi(dofB, rbase + ((s - p_keep) & 15));
-    auto bits = [](const unsigned long long w, const int i) -> int { return (int)(((w >> (i & 31)) & 1ull) | (((w >> (32 + (i & 31))) & 1ull) << 1)); };
     // the seeds seen from the reduced problem: bound of reduced variable s = velocity bound of DoF dofA; row s < p_keep = original
     // constraint row s (the trunk box leads findConstraints' order here); row s >= p_keep = velocity bound of leg DoF dofR
-    int sb = has_b ? bits(ws0, dofA) : 0;
-    int sr = has_r ? ((s < p_keep) ? bits(ws1, s) : bits(ws0, dofR)) : 0;
+    int sb = has_b ? pk_ws_bits(ws0, dofA) : 0;
+    int sr = has_r ? ((s < p_keep) ? pk_ws_bits(ws1, s) : pk_ws_bits(ws0, dofR)) : 0;
     if (sb == 3) sb = 0;
     if (sr == 3) sr = 0;
     // a seed is taken only if the unconstrained minimiser x0 violates it or comes close to it (qp_core, solve_v3 `far`)

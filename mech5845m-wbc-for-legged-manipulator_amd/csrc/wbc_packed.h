@@ -1,6 +1,7 @@
 // wbc_packed.h — what the packed kernels share (four instances per wavefront, lane = 16 r + s): the packed sim3 tick's LDS layout, the DPP
-// row reductions and broadcast, chol_sweep2, the wave order, and the kinematics and input staging every packed tick / update kernel runs — the FK seed and
-// level sweep (pk_fk_seed, pk_fk_sweep), the WORLD Jacobian column of a DoF (pk_jac_col), calcTargetVelTrunk2 (pk_trunk_target_vel) with its
+// row reductions and broadcast, chol_sweep2, the dual active-set's factor updates (pk_qp_products, pk_qp_add_step, pk_qp_drop_slot, with their scalar
+// cores pk_givens / pk_householder and the working-set decoder pk_ws_bits), the wave order, and the kinematics and input staging every packed
+// tick / update kernel runs — the FK seed and level sweep (pk_fk_seed, pk_fk_sweep), the WORLD Jacobian column of a DoF (pk_jac_col), calcTargetVelTrunk2 (pk_trunk_target_vel) with its
 // inputs (pk_trunk_input), the EE orientation feed-forward (pk_ee_omega) and the staged weights image (pk_stage_weights). The per-DoF
 // velocity damper and the Euler matrix, which the one-instance kernels use too, are in wbc_common.h (damper_bounds, euler_to_R).
 #pragma once
@@ -223,6 +224,148 @@ __device__ __forceinline__ double chol_sweep2_bc(double (&h)[N], double (&y)[N])
   double pmin = 1.0;
   chol_sweep2_bc_trip<N>(h, y, pmin);
   return pmin;
+}
+
+// ---- the dual active-set's factor updates: ONE text for the packed ticks. The orth and box ticks call all of it; the sim3 tick
+// calls the Givens core and the seed decoder (its three steps are written out on PV / PLD: §3.33); the packed QP kernel, which keeps T as a packed
+// triangle and J's row in registers (§3.16), takes the scalar cores pk_givens / pk_householder and the seed decoder. The method is
+// qp_core's (Goldfarb-Idnani): with H = L L', J = L^-T Q and the working set's normals N = Q1 R, the kernels carry J [NJ][LDJ] (row s = variable
+// s, column k = slot k; J1 = the first q columns, J2 the rest) and T = R^-1 [NT][LDT] (upper triangular in the first q slots, zero elsewhere).
+// Lane s is row s of both, slot s of u / a_code (the slot's multiplier and its constraint code | side << 8); q is uniform over the 16-lane row.
+// Every function is called by all 64 lanes in wave-uniform control flow; per-instance work is predicated (`dr`, `add`). sJ / sT: lane s, or the last
+// row of J / T on the lanes beyond it (they read that row's shadow and never write). has_b: the lane carries a variable (stores to J).
+// Working-set word w, entry i -> 0 none, 1 lower side, 2 upper side, 3 both (the caller drops those)
+__device__ __forceinline__ int pk_ws_bits(const unsigned long long w, const int i) {
+  return (int)(((w >> (i & 31)) & 1ull) | (((w >> (32 + (i & 31))) & 1ull) << 1));
+}
+// Givens rotation of a drop: the removed row of T leaves the pair (hrun, tb) in columns k, k + 1; (c, s) turns it into (0, rho)
+struct PkGivens { double c, s, rho; };
+__device__ __forceinline__ PkGivens pk_givens(const double hrun, const double tb) {
+  const double nrm2 = fma(hrun, hrun, tb * tb);
+  PkGivens g = {1.0, 0.0, 0.0};
+  if (nrm2 > 0.0) { const double ri = rsqrt(nrm2); g.c = tb * ri; g.s = -hrun * ri; g.rho = nrm2 * ri; }
+  return g;
+}
+// Householder reflection of an add: P = I - v v' / hv with P d2 = delta e_q, v = d2 - delta e_q, zn = |d2|^2, dq = d_q (delta takes the sign that
+// avoids cancellation in v_q), hv = v'v / 2. Row s of J2 P is J2 - w v' with w = (J2 v)_s / hv = (z - delta jq) / hv; idel = 1 / delta. ok: v != 0
+struct PkHouse { double delta, w, idel; bool ok; };
+__device__ __forceinline__ PkHouse pk_householder(const double zn, const double dq, const double z, const double jq) {
+  PkHouse o;
+  const double rsz = frsq(zn), sz = zn * rsz;
+  o.delta = (dq >= 0.0) ? -sz : sz;
+  const double hv = zn - o.delta * dq;
+  const double vv = 2.0 * hv;
+  o.w = (z - o.delta * jq) * ((vv > 0.0) ? frcp(hv) : 0.0);
+  o.idel = (dq >= 0.0) ? -rsz : rsz;
+  o.ok = vv > 0.0;
+  return o;
+}
+// With d = J'n staged (dv = d, yv = d restricted to the slots >= q): z = J2 d2 (the primal step direction, row s), r = T d1 (the dual one, slot s;
+// want_r: some instance of the wave has an active constraint — nothing to do otherwise), and what the add step needs of slot q, read in the same
+// round: dq = d_q, jq = J[s][q]
+struct PkZr { double z, rv, dq, jq; };
+template <int NJ, int LDJ, int NT, int LDT>
+__device__ __forceinline__ PkZr pk_qp_products(const double* const J, const double* const T, const double* const dv, const double* const yv,
+                                               const int sJ, const int sT, const int s, const int q, const bool has_b, const bool want_r) {
+  constexpr int NTE = (NT + 1) & ~1;        // T's slots, two per read
+  static_assert(NJ % 2 == 0 && NJ <= LDJ && NTE <= LDT && NTE <= 16, "rows are read in pairs inside their stride");
+  PkZr o;
+  double z = 0.0, zb = 0.0, rv = 0.0, rvb = 0.0;
+  o.dq = dv[q & 15];
+  o.jq = J[sJ * LDJ + (q & 15)];
+#pragma unroll
+  for (int k = 0; k < NJ; k += 2) {
+    const double2a j2 = lds2(J + sJ * LDJ + k); const double2a y2 = lds2(yv + k);
+    z = fma(j2.x, y2.x, z); zb = fma(j2.y, y2.y, zb);
+  }
+  z += zb;
+  if (want_r) {
+#pragma unroll
+    for (int k = 0; k < NTE; k += 2) {
+      const double2a t2 = lds2(T + sT * LDT + k); const double2a d2 = lds2(dv + k);
+      rv = fma(t2.x, d2.x, rv); rvb = fma(t2.y, d2.y, rvb);
+    }
+    rv += rvb;
+  }
+  if (s >= q) rv = 0.0;
+  if (!has_b) z = 0.0;
+  o.z = z; o.rv = rv;
+  return o;
+}
+// Add the constraint with code wc as slot q of the instances `add`: J2 <- J2 P (pk_householder), T gets the column (-r / delta, 1 / delta), the
+// new slot's multiplier is u_new. The sweep over row s of J runs on d2 alone (yv = d for k >= q, else 0) and entry q is then stored with its own
+// term — the same arithmetic as selecting v_k inside the loop, without two compares and four selects per pair. mark(): the caller's activity
+// flag of the constraint's own lane.
+template <int NJ, int LDJ, int NT, int LDT, class Mark>
+__device__ __forceinline__ void pk_qp_add_step(double* const J, double* const T, const double* const yv, const int s, const bool has_b, const bool add,
+                                               const double zn, const PkZr& zr, const int wc, const double u_new, double& u, int& a_code, int& q,
+                                               Mark&& mark) {
+  const PkHouse hh = pk_householder(zn, zr.dq, zr.z, zr.jq);
+  if (add && has_b && hh.ok) {
+#pragma unroll
+    for (int k = 0; k < NJ; k += 2) {
+      const double2a j2 = lds2(J + s * LDJ + k); const double2a y2 = lds2(yv + k);
+      sts2(J + s * LDJ + k, fma(-hh.w, y2.x, j2.x), fma(-hh.w, y2.y, j2.y));
+    }
+    J[s * LDJ + q] = fma(-hh.w, zr.dq - hh.delta, zr.jq);
+  }
+  if (add) {
+    if (s < q) T[s * LDT + q] = -zr.rv * hh.idel;
+    if (s == q) { T[s * LDT + q] = hh.idel; u = u_new; a_code = wc; }
+    mark();
+    ++q;
+  }
+}
+// Drop slot l_ of the instances `dr` (rare path): u / a_code of the slots behind it move up one (through yv / tv), and the Givens sequence read off
+// the removed row l of T — rotation k = l .. q - 2 on the column pair (k, k + 1), pk_givens — makes T upper triangular again one slot shorter;
+// J's columns take the same rotations (lane s: row s of J, and the row of T that becomes its new row s). The loop runs to the longest sequence
+// of the wave. unmark(code): the caller's activity flag of the dropped constraint.
+template <int NJ, int LDJ, int NT, int LDT, class Unmark>
+__device__ __forceinline__ void pk_qp_drop_slot(double* const J, double* const T, double* const yv, double* const tv, const int sJ, const int sT,
+                                                const int s, const int rbase, const bool has_b, const bool dr, const int l_, double& u, int& a_code,
+                                                int& q, Unmark&& unmark) {
+  const int l = dr ? l_ : 0;
+  const int lc = bpermi(a_code, rbase + l) & 255;
+  if (dr) unmark(lc);
+  WSYNC();
+  yv[s] = u; tv[s] = (double)a_code;
+  WSYNC();
+  if (dr && s >= l && s < q - 1) { u = yv[s + 1]; a_code = (int)tv[s + 1]; }
+  if (dr && s == q - 1) { u = 0.0; a_code = 0; }
+  const int srow = (sT >= l) ? ((sT + 1 < NT) ? sT + 1 : sT) : sT;
+  double tx = T[srow * LDT + l];
+  double jx = J[sJ * LDJ + l];
+  double hrun = T[l * LDT + l];
+  const int kend = dr ? q - 1 : 0;          // this instance's rotations run k = l .. q - 2
+#pragma unroll 1
+  for (int k0 = 0; k0 < NT - 1; ++k0) {
+    const bool on = dr && (l + k0 < kend);
+    if (!__ballot(on)) break;
+    const int k = on ? l + k0 : 0;
+    const PkGivens g = pk_givens(hrun, T[l * LDT + k + 1]);
+    const double ty_ = T[srow * LDT + k + 1];
+    const double jy = J[sJ * LDJ + k + 1];
+    WSYNC();
+    if (on) {
+      hrun = g.rho;
+      if (s < q - 1) T[s * LDT + k] = fma(g.c, tx, g.s * ty_);
+      if (has_b) J[s * LDJ + k] = fma(g.c, jx, g.s * jy);
+      tx = fma(-g.s, tx, g.c * ty_);
+      jx = fma(-g.s, jx, g.c * jy);
+    }
+    WSYNC();
+  }
+  WSYNC();
+  if (dr) {
+    if (s < q) T[s * LDT + q - 1] = 0.0;
+  }
+  WSYNC();
+  if (dr) {
+    if (s < q) T[(q - 1) * LDT + s] = 0.0;
+    if (has_b) J[s * LDJ + q - 1] = jx;
+    --q;
+  }
+  WSYNC();
 }
 
 // ---- the wave order (KernelArgs.worder, wbc_device.h WaveOrder). A wave runs as many dual passes as the slowest of its four rows:

@@ -4,7 +4,10 @@ code object of two libraries (or object files), the set of kernel descriptors (.
 and encodings; the address column is dropped, so a function may sit elsewhere in its code object) and each kernel's metadata note (registers,
 LDS, scratch, spill counts, kernarg layout). Code objects are not compared byte for byte: every compilation names a __hip_cuid_<hash> symbol
 of its own. Prints the verdict; exit status 1 on any difference. Needs no GPU.
-usage: tools/same_kernels.py old/libwbc_hip.so new/libwbc_hip.so"""
+--mnemonics: for a function whose ISA differs, also say whether the multiset of its mnemonics is equal (then the two differ in register names,
+operands and order at most) or which mnemonics it gained and lost.
+usage: tools/same_kernels.py [--mnemonics] old/libwbc_hip.so new/libwbc_hip.so"""
+import collections
 import re
 import subprocess
 import sys
@@ -39,13 +42,29 @@ def kernels(path):
     return {k: "\n".join(v) for k, v in funcs.items()}, meta, kds, len(cos)
 
 
+def mnemonics(text):
+    """-> the multiset of a function's mnemonics: what stays of its ISA when register names, operands and order are set aside"""
+    return collections.Counter(line.split()[0] for line in text.splitlines())
+
+
+def isa_finding(old, new, with_mnemonics):
+    what = "ISA differs (%d vs %d instructions" % (old.count("\n") + 1, new.count("\n") + 1)
+    if with_mnemonics:
+        a, b = mnemonics(old), mnemonics(new)
+        delta = ["%s %+d" % (m, b[m] - a[m]) for m in sorted(set(a) | set(b)) if a[m] != b[m]]
+        what += "; mnemonic multiset " + ("EQUAL" if not delta else "differs: " + ", ".join(delta))
+    return what + ")"
+
+
 def main():
-    if len(sys.argv) != 3:
+    args = [a for a in sys.argv[1:] if a != "--mnemonics"]
+    if len(args) != 2:
         sys.exit(__doc__)
-    (fa, ma, ka, na), (fb, mb, kb, nb) = kernels(sys.argv[1]), kernels(sys.argv[2])
+    with_mnemonics = len(args) != len(sys.argv) - 1
+    (fa, ma, ka, na), (fb, mb, kb, nb) = kernels(args[0]), kernels(args[1])
     bad = [("kernel only in old", n) for n in sorted(ka - kb)] + [("kernel only in new", n) for n in sorted(kb - ka)]
     bad += [("function only in %s" % ("old" if n in fa else "new"), n) for n in sorted(set(fa) ^ set(fb))]
-    bad += [("ISA differs (%d vs %d instructions)" % (fa[n].count("\n") + 1, fb[n].count("\n") + 1), n) for n in sorted(set(fa) & set(fb)) if fa[n] != fb[n]]
+    bad += [(isa_finding(fa[n], fb[n], with_mnemonics), n) for n in sorted(set(fa) & set(fb)) if fa[n] != fb[n]]
     bad += [("metadata note %s" % ("differs" if n in ma and n in mb else "missing on one side"), n) for n in sorted(set(ma) | set(mb)) if ma.get(n) != mb.get(n)]
     if bad:
         for (what, _), nice in zip(bad, kr.demangle([n for _, n in bad])):
