@@ -334,6 +334,48 @@ typedef struct WbcQpCert {         /* all optional; an output left NULL is not w
 int wbc_qp_certificate(WbcBatch* b, int B, const WbcQpProblem* problem, const WbcQpCert* out, int mem, void* stream);
 int wbc_qp_certificate_sizes(int32_t* sizeof_problem, int32_t* sizeof_cert); /* ctypes layout self-check */
 
+/* ------------------------------------------------------------------ the tick as a layer: dL/d(task weights, gains, targets)
+ * For a solved tick x = qdot and the certificate's u = sens_x of a caller's v = dL/dqdot (wbc_qp_certificate on the tick's own A, b, C, bounds):
+ * the gradient of L with respect to what the tick's CALLER owns — the 85 weights and gains (WbcTaskParams) and the task targets. With
+ * r = b - A x and s = A u:  dL/dA = r u' - s x',  dL/db = s;  every task row is (weights) x (an unweighted Jacobian row), so each entry is a
+ * few 26-term products of unweighted rows with x and u. The kernel (csrc/wbc_k_grad.hip, four instances per wavefront) recomputes the
+ * kinematics from q — task rows see q, never q_con — and reads neither A nor H. Per block, with jx = J_r x, ju = J_r u:
+ *   EE e, row r (A = W_r w J_r, b = w vel_r):  s = W_r w ju, rho = w vel_r - W_r w jx;  dW_r = w (rho ju - s jx);
+ *     dw += W_r (rho ju - s jx) + s vel_r;  dvel_r = w s;  r < 3: dgain_r = dvel_r (xt - x_fk) / dt, d ee_target = dvel_r (1 + gain_r) / dt,
+ *     d prev_ee_target = -dvel_r / dt;  ee_gain[e][3..5] never reach b: exactly 0.
+ *   trunk: the same on the WORLD Jacobian; trunk_gain[3..5] multiply the reference's literal quaternion-error components (Robot_Wrapper4.py:974-976).
+ *   CoM (A = com_W_r Jcom_r, b = cv_r + com_gain_r (ct_r - com_r)): com_W, com_gain, com_target, com_target_vel.
+ *   posture (d = joint_w / nv, b_k = d up_k): d joint_w = (2 / nv) sum_k d (up_k - x_k) u_k,  d posture_u_k = d^2 u_k.
+ * Entries of a switched-off task are exactly 0. An instance with status != 0, cert_status != WBC_CERT_OK or a non-finite input gets all-zero
+ * rows; nothing non-finite reaches another instance's rows. grad_status per instance: */
+enum { WBC_GRAD_OK = 0, WBC_GRAD_UNSOLVED = 1 /* status[b] != 0 */, WBC_GRAD_CERT = 2 /* cert_status[b] != WBC_CERT_OK */,
+       WBC_GRAD_NONFINITE = 3 /* NaN or +-inf in q, qdot, sens_x, the weights and gains or a target the configuration reads */ };
+typedef struct WbcTickGrad {         /* all optional; an output left NULL is not written                                  */
+  double* d_task_params;             /* [B][85], WbcTaskParams layout                                                     */
+  double* d_ee_target;               /* [B][5][3]; rows of end effectors without a task are 0                             */
+  double* d_prev_ee_target;          /* [B][5][3]                                                                         */
+  double* d_trunk_target;            /* [B][3]                                                                            */
+  double* d_prev_trunk_target;       /* [B][3]                                                                            */
+  double* d_com_target;              /* [B][3]                                                                            */
+  double* d_com_target_vel;          /* [B][3]                                                                            */
+  double* d_posture_u;               /* [B][26]; posture modes MANI / HYBRID / CUSTOM (the others never read posture_u)   */
+  int32_t* grad_status;              /* [B] WBC_GRAD_*                                                                    */
+} WbcTickGrad;
+/* in: the fields the task rows read (q, ee_target, prev_ee_target, trunk_target, prev_trunk_target, trunk_ref_euler, trunk_prev_rot,
+ * ee_ref_rot, ee_prev_rot, com_target, com_target_vel, posture_u, model_id); tp: per-instance rows or NULL (the configuration's block);
+ * qdot, sens_x [B][26]; status, cert_status [B] (NULL: every instance counts as solved / certified). Host or device buffers. With device
+ * pointers, and posture_u given or the posture mode not MANI / HYBRID, the call enqueues exactly one kernel: no allocation, no memset.
+ * MANI / HYBRID with posture_u NULL: the posture target is computed first, as wbc_assemble does. Needs every model of the handle to fit the
+ * packed whole-tree schedule (as wbc_state_slack: WBC_E_UNSUPPORTED otherwise). WBC_E_ARG, naming the field: qdot or sens_x NULL; an output
+ * requested whose inputs the configuration does not read (d_ee_target without an EE task, d_trunk_target without the trunk task,
+ * d_com_target without the CoM task, d_posture_u outside MANI / HYBRID / CUSTOM).
+ * Not offered: gradients with respect to q (they need kinematic Hessians), ee_ref_rot / ee_prev_rot, trunk_ref_euler / trunk_prev_rot,
+ * trunk_box_center (it enters the constraints, not the task rows), and gradients through roll-outs.
+ * Statistic "last_grad_variant": the row of csrc/wbc_k_grad.hip's table the last call launched (key of ROT), -1 before the first. */
+int wbc_tick_vjp(WbcBatch* b, int B, const WbcTickIn* in, const WbcTaskParams* tp, double dt, const double* qdot, const double* sens_x,
+                 const int32_t* status, const int32_t* cert_status, int mem, const WbcTickGrad* out, void* stream);
+int wbc_tick_grad_sizes(int32_t* sizeof_grad); /* ctypes layout self-check */
+
 /* replaces qpJointb's "MANI" / "HYBRID" branches (Robot_Wrapper4.py:1220-1260) under the configured task_joint,
  * arm_base_id and posture_literal: u [B][26] = the posture target before scaling (PREV / zeros for the other modes),
  * q_after [B][27] = the configuration the reference's state holds afterwards (optional). wbc_tick / wbc_assemble call
@@ -705,7 +747,7 @@ int wbc_debug_cycles(WbcBatch* b, uint64_t* out24);
 const char* wbc_last_error(void);
 const char* wbc_version(void);
 int wbc_abi_sizes(int32_t* sizeof_blob, int32_t* sizeof_config); /* ctypes layout self-check */
-/* rows of a kernel family's variant table ("general", "sim3p", "orthp", "boxp", "qpp", "qp"), generated from the table itself: what a census of
+/* rows of a kernel family's variant table ("general", "sim3p", "orthp", "boxp", "qpp", "qp"; "grad": statistic "last_grad_variant"), generated from the table itself: what a census of
  * the statistics "last_tick_variant" / "last_qp_variant" has to reach. Needs no handle and no device. Unknown family: WBC_E_ARG. */
 int wbc_variant_count(const char* family);
 

@@ -10,6 +10,7 @@
 #include "wbc_traj.h"
 #include "wbc_slack.h"
 #include "wbc_cert.h"
+#include "wbc_grad.h"
 
 // d_traj per instance of max_batch: err_sq_sum / err_max / err_final [6] each + the six frames' positions [6][3]; bad, err_max_tick [6],
 // first_bad_tick, bad_ticks, status_max. One int32 (the bad-row count) follows.
@@ -84,6 +85,7 @@ struct WbcBatch {
   int packed_update, last_update_packed;   // option: wbc_update_packed_kernel where every plan allows it [1]; what the last update ran on
   int last_orth;         // the last general-kernel tick ran the variant with the orthonormal contact presolve
   int last_qp_path;      // problems per wavefront of the last wbc_qp_solve / wbc_qp_solve_ls: 1 (wbc_qp_kernel), 2 or 4 (wbc_qp_packed_kernel)
+  long long last_grad_variant;   // ... and of the last wbc_tick_vjp launch
   long long last_tick_variant, last_qp_variant;   // variant_key(...) of the row the last tick / assemble / fk launch and the last stand-alone QP launch resolved (-1: none yet)
   int sim3p_fixd;        // option [1]: the packed sim3 kernel's FIXD form where the handle qualifies (fixd_dims)
   bool fixd_dims[WBC_MAX_MODELS];   // wbc_batch_configure: the model's plan has exactly the SIM3P_FIXD_* dimensions
@@ -209,7 +211,7 @@ extern "C" int wbc_batch_create(const WbcModel* const* models, int n_models, int
   if (!b) return fail(WBC_E_ARG, "out of memory");
   memset(b, 0, sizeof *b);
   b->device_id = device_id; b->n_models = n_models; b->max_batch = max_batch; b->presolve = 1; b->presolve_orth = 1; b->packed_update = 1; b->sim3_kernel = 1; b->sing_tol = 1e-7; b->wave_order = 1; b->sim3p_fixd = 1;
-  b->last_tick_variant = b->last_qp_variant = -1;
+  b->last_tick_variant = b->last_qp_variant = b->last_grad_variant = -1;
   b->jtj_mfma = -1; b->refine = 1; b->packed_min_batch = WBC_SIM3P_MIN_BATCH; b->warm_start = 0; b->packed_kernel = 1; b->packed_orth = 1; b->packed_box = 1; b->posture_par = 1;
   std::vector<DevModel> dm(n_models);
   for (int i = 0; i < n_models; ++i) {
@@ -710,6 +712,7 @@ extern "C" int wbc_batch_get_stat(WbcBatch* b, const char* name, void* stream, i
   if (!strcmp(name, "last_tick_variant")) { *out = b->last_tick_variant; return WBC_OK; }
   if (!strcmp(name, "last_tick_fixd")) { *out = b->last_path == TICK_SIM3P ? b->last_tick_fixd : 0; return WBC_OK; }
   if (!strcmp(name, "last_qp_variant")) { *out = b->last_qp_variant; return WBC_OK; }
+  if (!strcmp(name, "last_grad_variant")) { *out = b->last_grad_variant; return WBC_OK; }
   if (!strcmp(name, "last_update_packed")) { *out = b->last_update_packed; return WBC_OK; }
   if (!strcmp(name, "last_posture_par")) { *out = b->last_posture_par; return WBC_OK; }
   if (!strcmp(name, "last_orth")) { *out = (b->last_path == TICK_GENERAL || b->last_path == TICK_ORTHP) ? b->last_orth : 0; return WBC_OK; }
@@ -1652,6 +1655,65 @@ extern "C" int wbc_qp_certificate_sizes(int32_t* sizeof_problem, int32_t* sizeof
   return WBC_OK;
 }
 
+// dL/d(task weights, gains, targets) of solved ticks (include/wbc.h): argument checks, staging of host arrays, ONE launch of wbc_grad_kernel
+// (csrc/wbc_k_grad.hip) — after the posture kernel where the mode is MANI / HYBRID, posture_u is not given and a sweep matters, as wbc_assemble.
+// No memset; the kernel writes every row of every output it is given.
+static_assert(sizeof(WbcTickGrad) == 9 * sizeof(void*), "WbcTickGrad: nine pointers (wbc_capi.WbcTickGrad)");
+extern "C" int wbc_tick_vjp(WbcBatch* b, int B, const WbcTickIn* in, const WbcTaskParams* tp, double dt, const double* qdot, const double* sens_x,
+                            const int32_t* status, const int32_t* cert_status, int mem, const WbcTickGrad* out, void* stream) {
+  const char* who = "wbc_tick_vjp";
+  int rc = check_batch(b, B, who, true);
+  if (rc) return rc;
+  if (!out) return fail(WBC_E_ARG, "%s: out is required", who);
+  if (!(dt > 0)) return fail(WBC_E_ARG, "%s: dt <= 0", who);
+  if (!qdot) return fail(WBC_E_ARG, "%s: qdot is required", who);
+  if (!sens_x) return fail(WBC_E_ARG, "%s: sens_x is required", who);
+  if ((rc = validate_tick_in(b, in, who))) return rc;
+  const WbcConfig& c = b->cfg_host[0];
+  bool any_ee = false;
+  for (int i = 0; i < WBC_NEE; ++i) any_ee |= c.task_ee[i] != 0;
+  if (out->d_ee_target && !any_ee) return fail(WBC_E_ARG, "%s: d_ee_target requested, but no EE task reads ee_target", who);
+  if (out->d_prev_ee_target && !any_ee) return fail(WBC_E_ARG, "%s: d_prev_ee_target requested, but no EE task reads prev_ee_target", who);
+  if (out->d_trunk_target && !c.task_trunk) return fail(WBC_E_ARG, "%s: d_trunk_target requested, but the trunk task is off", who);
+  if (out->d_prev_trunk_target && !c.task_trunk) return fail(WBC_E_ARG, "%s: d_prev_trunk_target requested, but the trunk task is off", who);
+  if (out->d_com_target && !c.task_com) return fail(WBC_E_ARG, "%s: d_com_target requested, but the CoM task is off", who);
+  if (out->d_com_target_vel && !c.task_com) return fail(WBC_E_ARG, "%s: d_com_target_vel requested, but the CoM task is off", who);
+  for (int i = 0; i < b->n_models; ++i)
+    if (out->d_posture_u && b->cfg_host[i].task_joint < WBC_JOINT_MANI)
+      return fail(WBC_E_ARG, "%s: d_posture_u requested, but the posture mode of model %d does not read posture_u", who, i);
+  for (int i = 0; i < b->n_models; ++i) {
+    if (b->plan_host[i].slack_ok) continue;
+    const DevModel& M = b->models[i]->dev;
+    return fail(WBC_E_UNSUPPORTED, "%s: model %d does not fit the packed whole-tree schedule (%d joints, at most 22; tree depth %d, at most 7; at most 16 joints at one depth)",
+                who, i, M.njoints, M.maxdepth);
+  }
+  HIP_TRY(hipSetDevice(b->device_id));
+  KernelArgs ka;                       // (auto_posture's view of the call: in, and whether the tick would derive u itself)
+  fill_args(ka, b, B, dt);
+  ka.in = *in;
+  GradArgs a;
+  memset(&a, 0, sizeof a);
+  a.models = b->d_models; a.cfgs = b->d_cfgs; a.plans = b->d_plans; a.B = B; a.n_models = b->n_models; a.rot = b->rot; a.dt = dt;
+  a.tp = tp; a.qdot = qdot; a.sens_x = sens_x; a.status = status; a.cert_status = cert_status; a.out = *out;
+  Stager st{b, mem, (hipStream_t)stream, {}};
+  stage_tick_in(st, ka.in, B, b);
+  const size_t n = (size_t)B;
+  st.in(&a.tp, n); st.in(&a.qdot, n * WBC_V_STRIDE); st.in(&a.sens_x, n * WBC_V_STRIDE); st.in(&a.status, n); st.in(&a.cert_status, n);
+  st.out(&a.out.d_task_params, n * WBC_TASK_PARAMS_DOUBLES); st.out(&a.out.d_ee_target, n * 15); st.out(&a.out.d_prev_ee_target, n * 15);
+  st.out(&a.out.d_trunk_target, n * 3); st.out(&a.out.d_prev_trunk_target, n * 3); st.out(&a.out.d_com_target, n * 3);
+  st.out(&a.out.d_com_target_vel, n * 3); st.out(&a.out.d_posture_u, n * WBC_V_STRIDE); st.out(&a.out.grad_status, n);
+  if ((rc = st.stage())) return rc;
+  ka.in.q_con = nullptr;               // the task rows see q: no leaked configuration is asked for
+  if ((rc = auto_posture(b, ka, B, stream))) return rc;
+  a.in = ka.in;                        // (posture_u still null: every sweep is structurally zero, the kernel reads DevPlan.post_zero)
+  if ((rc = launch_rc(launch_grad(a, stream, &b->last_grad_variant), "tick gradient"))) return rc;
+  return st.finish();
+}
+extern "C" int wbc_tick_grad_sizes(int32_t* sizeof_grad) {
+  if (sizeof_grad) *sizeof_grad = (int32_t)sizeof(WbcTickGrad);
+  return WBC_OK;
+}
+
 extern "C" int wbc_integrate(WbcBatch* b, int B, const double* q, const double* v, const int32_t* model_id, double dt, int mem,
                              double* q_next, void* stream) {
   int rc = check_batch(b, B, "wbc_integrate", false);
@@ -1697,6 +1759,7 @@ extern "C" int wbc_variant_count(const char* family) {
   if (!strcmp(family, "boxp")) return boxp_variant_count();
   if (!strcmp(family, "qpp")) return qpp_variant_count();
   if (!strcmp(family, "qp")) return qp_variant_count();
+  if (!strcmp(family, "grad")) return grad_variant_count();
   return fail(WBC_E_ARG, "wbc_variant_count: unknown kernel family %s", family);
 }
 extern "C" int wbc_abi_sizes(int32_t* sb, int32_t* sc) {

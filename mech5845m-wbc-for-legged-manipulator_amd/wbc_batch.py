@@ -170,7 +170,7 @@ class WbcBatch:
     def stat(self, name, stream=None):
         """wbc_batch_get_stat: "last_path" (0 general, 1 compact sim3, 2 packed sim3, 3 packed orth — equality-only or INEQ variant —, 4 packed box), "last_orth", "last_posture_par",
         "last_update_packed", "last_qp_path" (problems per wavefront of the last stand-alone QP call: 1, 2 or 4), "last_tick_variant" /
-        "last_qp_variant" (the variant-table row of the last tick / assemble / fk and stand-alone QP launch: wbc_capi.variant_args), "last_tick_fixd" (1: the last tick ran the
+        "last_qp_variant" (the variant-table row of the last tick / assemble / fk and stand-alone QP launch: wbc_capi.variant_args), "last_grad_variant" (the same for the last wbc_tick_vjp launch), "last_tick_fixd" (1: the last tick ran the
         packed sim3 kernel's FIXD form, option "sim3p_fixd"), "deferred_last", "pivoted_last", "wave_order_slices", "sim3_lds_bytes", "tick_lds_bytes", "orthp_lds_bytes"."""
         v = C.c_int64()
         capi.check(self.lib.wbc_batch_get_stat(self._h, name.encode(), stream, C.byref(v)), self.lib)
@@ -367,18 +367,99 @@ class WbcBatch:
         capi.check(self.lib.wbc_qp_certificate(self._h, B, C.byref(q), C.byref(o), mem, self._stream(mem)), self.lib)
         return out
 
-    def tick_certificate(self, inputs, dt, task_params=None, v=None):
+    def _padding_rows(self, model_id, B, like):
+        """[B, k, 26] rows e_c, one per column c >= nv of the instance's own model (k = 26 - the smallest nv of the handle; zero rows where an
+        instance's model has fewer padded columns), or None when every model fills the 26 columns. wbc_assemble leaves the padded columns of A
+        zero (H_dd = 1 and bounds 0 in H's form: include/wbc.h), so A'A alone is singular there; with these rows the (A, b) form is the tick's
+        problem for every model."""
+        nvs = [m.nv for m in self.models]
+        k = NV - min(nvs)
+        if k <= 0:
+            return None
+        if _is_torch(like):
+            import torch
+            nv = torch.tensor(nvs, dtype=torch.int64, device=like.device)
+            nv_b = nv[model_id.to(torch.int64).clamp(0, len(nvs) - 1)] if model_id is not None else nv[:1].expand(B)
+            col = nv_b[:, None] + torch.arange(k, device=like.device)[None, :]
+            return (torch.arange(NV, device=like.device)[None, None, :] == col[:, :, None]).to(torch.float64).contiguous()
+        nv = np.asarray(nvs, dtype=np.int64)
+        nv_b = nv[np.clip(np.asarray(model_id, dtype=np.int64), 0, len(nvs) - 1)] if model_id is not None else np.full(B, nv[0])
+        col = nv_b[:, None] + np.arange(k)[None, :]
+        return (np.arange(NV)[None, None, :] == col[:, :, None]).astype(np.float64)
+
+    def tick_certificate(self, inputs, dt, task_params=None, v=None, tick=None):
         """One tick with its certificate, all on the device: wbc_assemble[_tp] (A, b, C, bounds), wbc_tick[_tp] with the working set out, then
         wbc_qp_certificate in the (A, b) form on the full problem (the tick's working set is in the full problem's indexing on every path).
-        v [B,26]: dL/dqdot for the sensitivities. Returns dict(qdot, status, iters, working_set) plus qp_certificate's entries."""
+        v [B,26]: dL/dqdot for the sensitivities. tick: a tick of these inputs already run with the working set out (dict(qdot, status,
+        working_set)); None runs it. A model with fewer than 26 velocity columns gets unit rows on its padded columns (_padding_rows).
+        Returns dict(qdot, status, iters, working_set) plus qp_certificate's entries."""
         d = self.assemble(inputs, dt, want=("A", "b", "C", "Clb", "Cub", "lb", "ub"), task_params=task_params)
-        t = self.tick(inputs, dt, want_working_set=True, task_params=task_params)
+        t = self.tick(inputs, dt, want_working_set=True, task_params=task_params) if tick is None else tick
         has_rows = d["C"].shape[1] > 0
+        A, b = d["A"], d["b"]
+        pad = self._padding_rows(inputs.get("model_id"), A.shape[0], A)
+        if pad is not None:
+            if _is_torch(A):
+                import torch
+                A, b = torch.cat([A, pad], dim=1).contiguous(), torch.cat([b, torch.zeros_like(pad[:, :, 0])], dim=1).contiguous()
+            else:
+                A, b = np.concatenate([A, pad], axis=1), np.concatenate([b, np.zeros(pad.shape[:2])], axis=1)
         # lb / ub as wbc_assemble returns them: +-1e30 (no bound) for an instance whose model's configuration has the velocity box off
-        c = self.qp_certificate(t["qdot"], A=d["A"], b=d["b"], C_=d["C"] if has_rows else None, lb=d["lb"], ub=d["ub"],
+        c = self.qp_certificate(t["qdot"], A=A, b=b, C_=d["C"] if has_rows else None, lb=d["lb"], ub=d["ub"],
                                 Clb=d["Clb"] if has_rows else None, Cub=d["Cub"] if has_rows else None,
                                 status=t["status"], working_set=t["working_set"], v=v)
         return dict(t, **c)
+
+    def default_grad_wants(self):
+        """the gradients wbc_tick_vjp offers under the handle's configuration (names of capi.TICK_GRAD_FIELDS)"""
+        c = self.cfgs[0]
+        want = ["d_task_params"]
+        if any(c.task_ee[e] for e in range(capi.NEE)):
+            want += ["d_ee_target", "d_prev_ee_target"]
+        if c.task_trunk:
+            want += ["d_trunk_target", "d_prev_trunk_target"]
+        if c.task_com:
+            want += ["d_com_target", "d_com_target_vel"]
+        if all(cf is not None and cf.task_joint >= capi.JOINT_MANI for cf in self.cfgs):
+            want += ["d_posture_u"]
+        return tuple(want)
+
+    def tick_vjp(self, inputs, dt, qdot, sens_x, status=None, cert_status=None, task_params=None, want=None, out=None):
+        """wbc_tick_vjp (include/wbc.h): dL/d(task weights, gains, targets) of solved ticks from x = qdot [B,26] and the certificate's
+        u = sens_x [B,26], one kernel launch. want: names of capi.TICK_GRAD_FIELDS (None: default_grad_wants()); out: caller's arrays by
+        those names (and "grad_status") instead. Returns dict(<want>..., grad_status [B] int32)."""
+        keep = []
+        B = self._batch_of(inputs.get("q"))
+        if out is None:
+            names = self.default_grad_wants() if want is None else tuple(want)
+            unknown = set(names) - set(capi.TICK_GRAD_FIELDS)
+            if unknown:
+                raise capi.WbcError("unknown gradients %s (known: %s)" % (sorted(unknown), ", ".join(capi.TICK_GRAD_FIELDS)))
+            out = {k: self._alloc(qdot, (B,) + capi.TICK_GRAD_FIELDS[k]) for k in names}
+            out["grad_status"] = self._alloc(qdot, (B,), np.int32)
+        mem = _mem_of(list(inputs.values()) + list(out.values()) + [task_params, qdot, sens_x, status, cert_status])
+        o = capi.WbcTickGrad()
+        for k, a in out.items():
+            if k == "grad_status":
+                o.grad_status = self._p(a, np.int32, keep, B, 1, k)
+            elif k in capi.TICK_GRAD_FIELDS:
+                setattr(o, k, self._p(a, np.float64, keep, B, int(np.prod(capi.TICK_GRAD_FIELDS[k])), k))
+            else:
+                raise capi.WbcError("unknown output %r" % k)
+        tin = self._tick_in(inputs, keep, B)
+        tp = _task_params(task_params, B, keep, self.device_id)
+        f, P = np.float64, self._p
+        capi.check(self.lib.wbc_tick_vjp(self._h, B, C.byref(tin), tp, float(dt), P(qdot, f, keep, B, NV, "qdot"), P(sens_x, f, keep, B, NV, "sens_x"),
+                                         P(status, np.int32, keep, B, 1, "status"), P(cert_status, np.int32, keep, B, 1, "cert_status"), mem,
+                                         C.byref(o), self._stream(mem)), self.lib)
+        return out
+
+    def tick_grad(self, inputs, dt, v, task_params=None, want=None):
+        """The tick as a layer: tick_certificate(..., v=v) and then wbc_tick_vjp on its qdot and sens_x, on the device throughout when the
+        inputs are. v [B,26] = dL/dqdot. Returns the tick's and the certificate's entries plus the gradients (tick_vjp's names) and grad_status."""
+        c = self.tick_certificate(inputs, dt, task_params=task_params, v=v)
+        g = self.tick_vjp(inputs, dt, c["qdot"], c["sens_x"], status=c["status"], cert_status=c["cert_status"], task_params=task_params, want=want)
+        return dict(c, **g)
 
     def posture_target(self, q, model_id=None, want_q_after=True):
         """qpJointb's "MANI" / "HYBRID" posture target u [B,26] under the configured mode (Robot_Wrapper4.py:1220-1260),

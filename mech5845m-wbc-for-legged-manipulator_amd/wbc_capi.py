@@ -146,6 +146,16 @@ class WbcQpCert(C.Structure):
                                           "cert_status")]
 
 
+# wbc_tick_vjp: dL/d(task weights, gains, targets) of a solved tick (include/wbc.h)
+GRAD_OK, GRAD_UNSOLVED, GRAD_CERT, GRAD_NONFINITE = 0, 1, 2, 3
+TICK_GRAD_FIELDS = dict(d_task_params=(85,), d_ee_target=(NEE, 3), d_prev_ee_target=(NEE, 3), d_trunk_target=(3,), d_prev_trunk_target=(3,),
+                        d_com_target=(3,), d_com_target_vel=(3,), d_posture_u=(V_STRIDE,))     # output name -> per-instance shape
+
+
+class WbcTickGrad(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in tuple(TICK_GRAD_FIELDS) + ("grad_status",)]
+
+
 class WbcFkOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("oMi", "oMf", "J", "com", "Jcom")]
 
@@ -179,6 +189,8 @@ SIGNATURES = {
     "wbc_qp_solve_ls": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "wbc_qp_certificate": (_i, [_vp, _i, C.POINTER(WbcQpProblem), C.POINTER(WbcQpCert), _i, _vp]),
     "wbc_qp_certificate_sizes": (_i, [c_int32_p, c_int32_p]),
+    "wbc_tick_vjp": (_i, [_vp, _i, C.POINTER(WbcTickIn), _vp, _d, _vp, _vp, _vp, _vp, _i, C.POINTER(WbcTickGrad), _vp]),
+    "wbc_tick_grad_sizes": (_i, [c_int32_p]),
     "wbc_posture_target": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "wbc_tick": (_i, [_vp, _i, C.POINTER(WbcTickIn), _d, _i, C.POINTER(WbcTickOut), _vp]),
     "wbc_update_state": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
@@ -243,6 +255,9 @@ def load_library(path=None):
     if sb.value != C.sizeof(WbcQpProblem) or sc.value != C.sizeof(WbcQpCert):
         raise WbcError("ABI mismatch (certificate structs): library (%d, %d) vs ctypes (%d, %d)" % (
             sb.value, sc.value, C.sizeof(WbcQpProblem), C.sizeof(WbcQpCert)))
+    lib.wbc_tick_grad_sizes(C.byref(sb))
+    if sb.value != C.sizeof(WbcTickGrad):
+        raise WbcError("ABI mismatch (WbcTickGrad): library %d vs ctypes %d" % (sb.value, C.sizeof(WbcTickGrad)))
     if path is None:
         _lib = lib
     return lib

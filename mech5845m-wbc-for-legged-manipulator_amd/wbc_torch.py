@@ -9,6 +9,10 @@ where e_i is the bound value active constraint i sits at: the gradient goes to l
 is split half and half on an equality (lb == ub, Clb == Cub). Instances whose QP was not solved, or whose certificate does not come back
 WBC_CERT_OK (dependent active normals, non-finite data), get zero gradients. All tensors are contiguous float64 on the handle's device;
 C, Clb, Cub (no rows) and lb, ub (no box) may be None. There is no CPU fallback.
+
+``qdot, status = wbc_tick(task_params, ee_target, ..., inputs, dt, batch)`` is the same one level up: the whole control tick as a layer over
+what its caller owns — the 85 per-instance weights and gains and the task targets. Forward is ``wbc_tick_tp`` with the working set out;
+backward is one certificate of the tick's own problem with v = grad_output followed by ``wbc_tick_vjp`` (include/wbc.h), all on the device.
 """
 import torch
 
@@ -69,3 +73,57 @@ def qp_solve(H, g, C, lb, ub, Clb, Cub, batch):
     """argmin 1/2 x'Hx + g'x s.t. lb <= x <= ub, Clb <= C x <= Cub for a batch (H [B,n,n], C [B,p,n]) on `batch` (a WbcBatch), differentiable
     with respect to every tensor argument. Returns (x [B,n], status [B] int32)."""
     return _QpSolve.apply(H, g, C, lb, ub, Clb, Cub, batch)
+
+
+_TICK_ARGS = ("task_params", "ee_target", "prev_ee_target", "trunk_target", "prev_trunk_target", "com_target", "com_target_vel", "posture_u")
+
+
+class _WbcTick(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, task_params, ee_target, prev_ee_target, trunk_target, prev_trunk_target, com_target, com_target_vel, posture_u, inputs, dt,
+                batch):
+        args = [_c(t) for t in (task_params, ee_target, prev_ee_target, trunk_target, prev_trunk_target, com_target, com_target_vel, posture_u)]
+        d = dict(inputs)
+        for name, a in zip(_TICK_ARGS[1:], args[1:]):
+            if a is not None:
+                d[name] = a
+        t = batch.tick(d, dt, want_working_set=True, task_params=args[0])
+        ctx.batch, ctx.dt = batch, dt
+        given = {name for name, a in zip(_TICK_ARGS, args) if a is not None}
+        ctx.rest = {k: v for k, v in d.items() if k not in given}          # (what came in `inputs`: not ours to version-check)
+        ctx.present = [a is not None for a in args]
+        ctx.save_for_backward(t["qdot"], t["status"], t["working_set"], *[a for a in args if a is not None])
+        ctx.mark_non_differentiable(t["status"])
+        return t["qdot"], t["status"]
+
+    @staticmethod
+    def backward(ctx, gq, _gst):
+        qdot, st, ws, *given = ctx.saved_tensors
+        n_out = len(_TICK_ARGS) + 3
+        if gq is None:              # qdot took no part in the loss
+            return (None,) * n_out
+        it = iter(given)
+        args = [next(it) if have else None for have in ctx.present]
+        need = ctx.needs_input_grad
+        want = tuple("d_" + name for k, name in enumerate(_TICK_ARGS) if need[k] and args[k] is not None)
+        if not want:
+            return (None,) * n_out
+        bt = ctx.batch
+        d = dict(ctx.rest)
+        for name, a in zip(_TICK_ARGS[1:], args[1:]):
+            if a is not None:
+                d[name] = a
+        c = bt.tick_certificate(d, ctx.dt, task_params=args[0], v=gq.contiguous(), tick=dict(qdot=qdot, status=st, working_set=ws))
+        g = bt.tick_vjp(d, ctx.dt, qdot, c["sens_x"], status=st, cert_status=c["cert_status"], task_params=args[0], want=want)
+        return tuple(g.get("d_" + name) if ("d_" + name) in want else None for name in _TICK_ARGS) + (None, None, None)
+
+
+def wbc_tick(task_params, ee_target, prev_ee_target, trunk_target, prev_trunk_target, com_target, com_target_vel, posture_u, inputs, dt, batch):
+    """One control tick per instance as a differentiable layer on `batch` (a configured WbcBatch): returns (qdot [B,26], status [B] int32).
+    The eight tensor arguments (contiguous float64 on the handle's device; task_params [B,85], the rest shaped as in WbcTickIn) are what
+    gradients flow to; any of them may be None — task_params None is the configuration's block, a target None is taken from `inputs` (a dict
+    keyed like WbcTickIn that holds everything else: q, trunk_box_center, the orientation references, model_id ...) and gets no gradient. An
+    argument the configuration does not read (trunk_target without the trunk task ...) must be None or not require a gradient. Instances
+    whose QP was not solved or whose certificate is not WBC_CERT_OK get zero gradients. No gradient flows to q or anything else in `inputs`."""
+    return _WbcTick.apply(task_params, ee_target, prev_ee_target, trunk_target, prev_trunk_target, com_target, com_target_vel, posture_u, inputs, dt,
+                          batch)

@@ -395,3 +395,173 @@ def qp_gradients(x, y, u, w, side, C_=None):
     ghi = np.where(side == 2, w, 0.0) + np.where(side == 3, 0.5 * w, 0.0)
     return dict(g=-u, H=-0.5 * (np.outer(u, x) + np.outer(x, u)), C=-np.outer(w[n:], x) + np.outer(y[n:], u),
                 lb=glo[:n], ub=ghi[:n], Clb=glo[n:], Cub=ghi[n:])
+
+
+# ---- the tick as a layer (wbc_tick_vjp, include/wbc.h): dL/d(task weights, gains, targets) restated in numpy from UNWEIGHTED Jacobian rows
+def _support_columns(model, joint):
+    """bool [26]: the velocity columns that move a body of `joint` (the joint and its ancestors)"""
+    sup = np.zeros(capi.V_STRIDE, dtype=bool)
+    j = int(joint)
+    while j > 0:
+        jd = model.data["joints"][j]
+        sup[jd["idx_v"]:jd["idx_v"] + (6 if jd["type_id"] == capi.JT["FF"] else 1)] = True
+        j = jd["parent"]
+    return sup
+
+
+def frame_rows(model, J, oMf, role, world):
+    """The six unweighted Jacobian rows [B, 6, 26] of the controller frame `role` (capi.FR_*) from the WORLD joint Jacobians J [B, 6, 26]
+    (pin.computeJointJacobians) and the frame placements oMf: getFrameJacobian in WORLD (world=True) or LOCAL_WORLD_ALIGNED."""
+    Jf = np.where(_support_columns(model, model.blob.frame_joint[role])[None, None, :], J, 0.0)
+    if not world:                                                         # reference point at the frame origin: lin - p x ang
+        p = oMf[:, role, 9:12]
+        Jf = Jf.copy()
+        Jf[:, 0:3, :] -= np.cross(p[:, None, :], Jf[:, 3:6, :].transpose(0, 2, 1)).transpose(0, 2, 1)
+    return Jf
+
+
+def _R_to_quat(R):
+    """scipy Rotation.from_matrix(R).as_quat() branch logic on [B, 9] row-major rotations, (x, y, z, w), no sign canonicalisation
+    (Robot_Wrapper4.py:964-965)"""
+    R = np.asarray(R, dtype=np.float64).reshape(-1, 9)
+    out = np.zeros((len(R), 4))
+    for n, M in enumerate(R):
+        tr = M[0] + M[4] + M[8]
+        dec = [M[0], M[4], M[8], tr]
+        c = 0
+        for i in range(1, 4):
+            if dec[i] > dec[c]:
+                c = i
+        q = np.zeros(4)
+        if c != 3:
+            i, j = c, (c + 1) % 3
+            k = (j + 1) % 3
+            q[i] = 1 - tr + 2 * M[3 * i + i]
+            q[j] = M[3 * j + i] + M[3 * i + j]
+            q[k] = M[3 * k + i] + M[3 * i + k]
+            q[3] = M[3 * k + j] - M[3 * j + k]
+        else:
+            q[:] = M[7] - M[5], M[2] - M[6], M[3] - M[1], 1 + tr
+        out[n] = q / np.sqrt(q @ q)
+    return out
+
+
+def _euler_xyz_to_R(e):
+    """[B, 9] row-major Rz(c) Ry(b) Rx(a)"""
+    sa, ca, sb, cb, sc, cc = np.sin(e[:, 0]), np.cos(e[:, 0]), np.sin(e[:, 1]), np.cos(e[:, 1]), np.sin(e[:, 2]), np.cos(e[:, 2])
+    return np.stack([cc * cb, cc * sb * sa - sc * ca, cc * sb * ca + sc * sa, sc * cb, sc * sb * sa + cc * ca, sc * sb * ca - cc * sa,
+                     -sb, cb * sa, cb * ca], axis=1)
+
+
+def tick_gradients(model, cfg, inputs, x, u, dt, fk, task_params=None):
+    """wbc_tick_vjp restated for B instances of ONE model: x = qdot [B, 26], u = the certificate's sens_x [B, 26] for the caller's
+    v = dL/dqdot, inputs keyed like WbcTickIn, task_params [B, 85] or None (the configuration's block). fk follows state_slack's convention
+    (fk(q) -> oMf [B, nframes, 12], fk.com(q) -> [B, 3]) and also gives the unweighted rows' source, fk.jacobians(q) -> (J [B, 6, 26] the WORLD
+    joint Jacobians of pin.computeJointJacobians, Jcom [B, 3, 26]). Task rows see q (never q_con). MANI / HYBRID need inputs["posture_u"].
+    With r = b - A x and s = A u: dL/dA = r u' - s x', dL/db = s; every row is (weights) x (an unweighted row), and the rules of
+    include/wbc.h follow block by block. Returns dict(d_task_params [B, 85], d_ee_target, d_prev_ee_target [B, 5, 3], d_trunk_target,
+    d_prev_trunk_target, d_com_target, d_com_target_vel [B, 3], d_posture_u [B, 26] — zeros where the configuration does not read the input —
+    and dA [B, m, 26], db [B, m], A [B, m, 26], b [B, m]: the task stack rebuilt from the unweighted rows, and dL/dA, dL/db)."""
+    import wbc_model
+    q = np.asarray(inputs["q"], dtype=np.float64).reshape(-1, capi.Q_STRIDE)
+    B, NVs, nv = q.shape[0], capi.V_STRIDE, model.nv
+    x, u = np.asarray(x, dtype=np.float64).reshape(B, NVs), np.asarray(u, dtype=np.float64).reshape(B, NVs)
+    tp = wbc_model.task_params(cfg, B) if task_params is None else np.asarray(task_params, dtype=np.float64).reshape(B, capi.TASK_PARAMS_DOUBLES)
+    L = wbc_model.TASK_PARAMS_LAYOUT
+    P = {k: tp[:, sl].reshape((B,) + shape) for k, (sl, shape) in L.items()}
+    oMf = fk(q)
+    J, Jcom = fk.jacobians(q)
+    g = {k: np.zeros((B,) + shape) for k, (sl, shape) in L.items()}
+    out = dict(d_ee_target=np.zeros((B, 5, 3)), d_prev_ee_target=np.zeros((B, 5, 3)), d_trunk_target=np.zeros((B, 3)),
+               d_prev_trunk_target=np.zeros((B, 3)), d_com_target=np.zeros((B, 3)), d_com_target_vel=np.zeros((B, 3)),
+               d_posture_u=np.zeros((B, NVs)))
+    A_, b_, dA_, db_ = [], [], [], []
+
+    def block(Jr, c, bv):
+        """rows A = c J_r, b = bv (c, bv [B, R]): -> jx, ju, s, rho [B, R], and the rows are recorded"""
+        jx, ju = np.einsum("brk,bk->br", Jr, x), np.einsum("brk,bk->br", Jr, u)
+        s, rho = c * ju, bv - c * jx
+        A_.append(c[:, :, None] * Jr)
+        b_.append(bv)
+        dA_.append(rho[:, :, None] * u[:, None, :] - s[:, :, None] * x[:, None, :])
+        db_.append(s)
+        return jx, ju, s, rho
+
+    for e in range(capi.NEE):
+        if not cfg.task_ee[e]:
+            continue
+        Jr = frame_rows(model, J, oMf, capi.FR_EE0 + e, world=False)
+        xt = np.asarray(inputs["ee_target"], dtype=np.float64).reshape(B, 5, 3)[:, e]
+        xp = np.asarray(inputs["prev_ee_target"], dtype=np.float64).reshape(B, 5, 3)[:, e]
+        W, w, gain = P["ee_W"][:, e], P["ee_w"][:, e][:, None], P["ee_gain"][:, e]
+        err = (xt - oMf[:, capi.FR_EE0 + e, 9:12]) / dt
+        vel = np.zeros((B, 6))
+        vel[:, :3] = (xt - xp) / dt + gain[:, :3] * err
+        if inputs.get("ee_ref_rot") is not None:
+            Rs = np.asarray(inputs["ee_ref_rot"], dtype=np.float64).reshape(B, 5, 3, 3)[:, e]
+            Rp = np.asarray(inputs["ee_prev_rot"], dtype=np.float64).reshape(B, 5, 3, 3)[:, e]
+            S = np.einsum("bij,bkj->bik", (Rs - Rp) / dt, Rs)               # ((R* - R*_prev) / dt) R*^T
+            vel[:, 3:] = np.stack([S[:, 2, 1], S[:, 0, 2], S[:, 1, 0]], axis=1)
+        jx, ju, s, rho = block(Jr, W * w, w * vel)
+        t = rho * ju - s * jx
+        dvel = w * s
+        g["ee_W"][:, e] = w * t
+        g["ee_w"][:, e] = (W * t + s * vel).sum(axis=1)
+        g["ee_gain"][:, e, :3] = dvel[:, :3] * err
+        out["d_ee_target"][:, e] = dvel[:, :3] * (1.0 + gain[:, :3]) / dt
+        out["d_prev_ee_target"][:, e] = -dvel[:, :3] / dt
+    if cfg.task_trunk:
+        Jr = frame_rows(model, J, oMf, capi.FR_TRUNK, world=True)
+        xt = np.asarray(inputs["trunk_target"], dtype=np.float64).reshape(B, 3)
+        xp = np.asarray(inputs["prev_trunk_target"], dtype=np.float64).reshape(B, 3)
+        W, w, gain = P["trunk_W"], P["trunk_w"].reshape(B, 1), P["trunk_gain"]
+        err = (xt - oMf[:, capi.FR_TRUNK, 9:12]) / dt
+        fq = _R_to_quat(oMf[:, capi.FR_TRUNK, 0:9])
+        er = np.asarray(inputs["trunk_ref_euler"], dtype=np.float64).reshape(B, 3)
+        rq, Rs = euler_xyz_to_quat(er), _euler_xyz_to_R(er).reshape(B, 3, 3)
+        qe = np.stack([fq[:, 3] * rq[:, 0] - fq[:, 0] * rq[:, 3] + fq[:, 1] * rq[:, 2] - fq[:, 2] * rq[:, 1],
+                       fq[:, 3] * rq[:, 1] - fq[:, 1] * rq[:, 3] - fq[:, 0] * rq[:, 2] + fq[:, 2] * rq[:, 0],
+                       fq[:, 3] * rq[:, 2] - fq[:, 3] * rq[:, 2] + fq[:, 0] * rq[:, 1] - fq[:, 1] * rq[:, 0]], axis=1)   # :974-976 (sic)
+        Ro = np.asarray(inputs["trunk_prev_rot"], dtype=np.float64).reshape(B, 3, 3)
+        S = np.einsum("bij,bjk->bik", (Rs - Ro) / dt, Rs)                   # D R* (not R*^T: :984)
+        vel = np.zeros((B, 6))
+        vel[:, :3] = (xt - xp) / dt + gain[:, :3] * err
+        vel[:, 3:] = np.stack([S[:, 2, 1], S[:, 0, 2], S[:, 1, 0]], axis=1) + gain[:, 3:] * qe
+        jx, ju, s, rho = block(Jr, W * w, w * vel)
+        t = rho * ju - s * jx
+        dvel = w * s
+        g["trunk_W"][:] = w * t
+        g["trunk_w"][:] = (W * t + s * vel).sum(axis=1)
+        g["trunk_gain"][:, :3] = dvel[:, :3] * err
+        g["trunk_gain"][:, 3:] = dvel[:, 3:] * qe
+        out["d_trunk_target"][:] = dvel[:, :3] * (1.0 + gain[:, :3]) / dt
+        out["d_prev_trunk_target"][:] = -dvel[:, :3] / dt
+    if cfg.task_com:
+        ct = np.asarray(inputs["com_target"], dtype=np.float64).reshape(B, 3)
+        cv = np.asarray(inputs["com_target_vel"], dtype=np.float64).reshape(B, 3)
+        W, gain = P["com_W"], P["com_gain"]
+        err = ct - fk.com(q)
+        jx, ju, s, rho = block(Jcom, W, cv + gain * err)
+        g["com_W"][:] = rho * ju - s * jx
+        g["com_gain"][:] = s * err
+        out["d_com_target"][:] = s * gain
+        out["d_com_target_vel"][:] = s
+    if cfg.task_joint:
+        d = ((1.0 / nv) * P["joint_w"]).reshape(B, 1)
+        up = np.zeros((B, NVs))
+        if cfg.task_joint == capi.JOINT_PREV:
+            up[:, :nv] = np.delete(q, 6, axis=1)[:, :nv]
+        elif cfg.task_joint >= capi.JOINT_MANI:
+            up[:, :nv] = np.asarray(inputs["posture_u"], dtype=np.float64).reshape(B, NVs)[:, :nv]
+        own = (np.arange(NVs) < nv)[None, :]
+        Jr = np.broadcast_to(np.where(own[0][:, None], np.eye(NVs), 0.0), (B, NVs, NVs))
+        block(Jr, np.broadcast_to(d, (B, NVs)), d * up)
+        g["joint_w"][:] = (2.0 / nv) * np.where(own, d * (up - x) * u, 0.0).sum(axis=1)
+        if cfg.task_joint >= capi.JOINT_MANI:
+            out["d_posture_u"][:] = np.where(own, d * d * u, 0.0)
+    dtp = np.zeros((B, capi.TASK_PARAMS_DOUBLES))
+    for k, (sl, shape) in L.items():
+        dtp[:, sl] = g[k].reshape(B, -1)
+    cat = (lambda a, w: np.concatenate(a, axis=1) if a else np.zeros((B, 0) + w))
+    out.update(d_task_params=dtp, A=cat(A_, (NVs,)), b=cat(b_, ()), dA=cat(dA_, (NVs,)), db=cat(db_, ()))
+    return out
