@@ -12,9 +12,7 @@
 #include "wbc_cert.h"
 #include "wbc_grad.h"
 
-// d_traj per instance of max_batch: err_sq_sum / err_max / err_final [6] each + the six frames' positions [6][3]; bad, err_max_tick [6],
-// first_bad_tick, bad_ticks, status_max. One int32 (the bad-row count) follows.
-enum { TRAJ_WS_DOUBLES = 3 * WBC_MAX_TRACKS + 3 * WBC_MAX_TRACKS, TRAJ_WS_INTS = 4 + WBC_MAX_TRACKS };
+// (the layouts of the handle's roll-out workspaces d_roll, d_traj and d_slack: RollWs, TrajWs and SlackWs below)
 
 using namespace wbc;
 
@@ -100,6 +98,88 @@ struct WbcBatch {
   SlackLimits* d_slack_lim;   // wbc_state_slack / wbc_rollout_watch: the models' own joint ranges by DoF (lazy)
   void* d_slack;         // wbc_rollout_watch: per-instance accumulators of the four families for max_batch instances (lazy)
 };
+
+// ---------------------------------------------------------------------------------------------- workspaces
+// A workspace the handle allocates on first use (wbc_batch_destroy frees what is non-null).
+template <class T> static int ensure(T*& p, size_t bytes) {
+  if (!p) HIP_TRY(hipMalloc((void**)&p, bytes));
+  return WBC_OK;
+}
+// d_defer: the count, the list of up to max_batch instances the compact sim3 kernel leaves to the deferred pass, and four words behind the
+// list (KernelArgs.defer_aux): [0] the pivot counter (statistic "pivoted_last"), [1] the deferred pass's own, [2] the statistic "deferred_last".
+enum { DEFER_TAIL_WORDS = 4, DEFER_TAIL_LAST = 2 };
+static size_t defer_bytes(const WbcBatch* b) { return sizeof(int32_t) * ((size_t)b->max_batch + DEFER_TAIL_WORDS); }
+static int32_t* defer_tail(const WbcBatch* b) { return b->d_defer + 1 + b->max_batch; }
+
+// The roll-out workspaces, each stated once as tables of blocks: a block holds `width` values per instance of max_batch (NB), the blocks follow
+// one another without padding, doubles first. Every block is strided by NB — never by a call's B, which strides the caller's outputs.
+template <class W, class T> struct Block { T* W::*ptr; size_t width; };
+template <class W, class T, size_t N> constexpr size_t block_bytes(const Block<W, T> (&t)[N]) {   // per instance
+  size_t s = 0;
+  for (size_t i = 0; i < N; ++i) s += t[i].width * sizeof(T);
+  return s;
+}
+template <class W, class T, size_t N> static char* carve_blocks(W& w, char* p, size_t NB, const Block<W, T> (&t)[N]) {
+  for (size_t i = 0; i < N; ++i) { w.*t[i].ptr = (T*)p; p += NB * t[i].width * sizeof(T); }
+  return p;
+}
+
+struct RollWs {   // d_roll: wbc_rollout's mutable controller state, the tick's outputs, the working sets carried from tick to tick [NB][2]
+  double *q, *q_next, *qdot, *ee_target, *prev_ee_target, *trunk_target, *prev_trunk_target, *ee_prev_rot, *trunk_prev_rot;
+  int32_t *status, *iters;
+  unsigned long long* working_set;
+  static size_t bytes(size_t NB);
+  static RollWs carve(void* base, size_t NB);
+};
+constexpr Block<RollWs, double> ROLL_D[] = {{&RollWs::q, WBC_Q_STRIDE}, {&RollWs::q_next, WBC_Q_STRIDE}, {&RollWs::qdot, WBC_V_STRIDE},
+    {&RollWs::ee_target, 3 * WBC_NEE}, {&RollWs::prev_ee_target, 3 * WBC_NEE}, {&RollWs::trunk_target, 3}, {&RollWs::prev_trunk_target, 3},
+    {&RollWs::ee_prev_rot, 9 * WBC_NEE}, {&RollWs::trunk_prev_rot, 9}};
+constexpr Block<RollWs, int32_t> ROLL_I[] = {{&RollWs::status, 1}, {&RollWs::iters, 1}};
+constexpr Block<RollWs, unsigned long long> ROLL_U[] = {{&RollWs::working_set, 2}};
+static_assert(block_bytes(ROLL_D) == 170 * sizeof(double) && block_bytes(ROLL_I) == 2 * sizeof(int32_t) && block_bytes(ROLL_U) == 2 * sizeof(unsigned long long),
+              "d_roll: 170 doubles, 2 int32 and 2 64-bit words per instance");
+static_assert(block_bytes(ROLL_I) % 8 == 0, "d_roll: the working sets begin at a multiple of 8 bytes for any max_batch");
+size_t RollWs::bytes(size_t NB) { return NB * (block_bytes(ROLL_D) + block_bytes(ROLL_I) + block_bytes(ROLL_U)); }
+RollWs RollWs::carve(void* base, size_t NB) {
+  RollWs w;
+  carve_blocks(w, carve_blocks(w, carve_blocks(w, (char*)base, NB, ROLL_D), NB, ROLL_I), NB, ROLL_U);
+  return w;
+}
+
+struct TrajWs {   // d_traj: per-instance scores of six frames, the frames' positions of the tick [6][3], bad-row flags; one int32 follows: their count
+  double *err_sq_sum, *err_max, *err_final, *frames;
+  int32_t *bad, *first_bad_tick, *bad_ticks, *status_max, *err_max_tick, *bad_count;
+  static size_t bytes(size_t NB);
+  static TrajWs carve(void* base, size_t NB);
+};
+constexpr Block<TrajWs, double> TRAJ_D[] = {{&TrajWs::err_sq_sum, WBC_MAX_TRACKS}, {&TrajWs::err_max, WBC_MAX_TRACKS}, {&TrajWs::err_final, WBC_MAX_TRACKS},
+    {&TrajWs::frames, 3 * WBC_MAX_TRACKS}};
+constexpr Block<TrajWs, int32_t> TRAJ_I[] = {{&TrajWs::bad, 1}, {&TrajWs::first_bad_tick, 1}, {&TrajWs::bad_ticks, 1}, {&TrajWs::status_max, 1},
+    {&TrajWs::err_max_tick, WBC_MAX_TRACKS}};
+static_assert(block_bytes(TRAJ_D) == 36 * sizeof(double) && block_bytes(TRAJ_I) == 10 * sizeof(int32_t), "d_traj: 36 doubles and 10 int32 per instance (+ one int32)");
+size_t TrajWs::bytes(size_t NB) { return NB * (block_bytes(TRAJ_D) + block_bytes(TRAJ_I)) + sizeof(int32_t); }
+TrajWs TrajWs::carve(void* base, size_t NB) {
+  TrajWs w;
+  w.bad_count = (int32_t*)carve_blocks(w, carve_blocks(w, (char*)base, NB, TRAJ_D), NB, TRAJ_I);
+  return w;
+}
+
+struct SlackWs {   // d_slack: wbc_rollout_watch's per-instance accumulators of the four families
+  double *slack_min, *slack_final;
+  int32_t *min_tick, *min_which, *neg_ticks, *first_neg;
+  static size_t bytes(size_t NB);
+  static SlackWs carve(void* base, size_t NB);
+};
+constexpr Block<SlackWs, double> SLACK_D[] = {{&SlackWs::slack_min, SLACK_NF}, {&SlackWs::slack_final, SLACK_NF}};
+constexpr Block<SlackWs, int32_t> SLACK_I[] = {{&SlackWs::min_tick, SLACK_NF}, {&SlackWs::min_which, SLACK_NF}, {&SlackWs::neg_ticks, SLACK_NF},
+    {&SlackWs::first_neg, SLACK_NF}};
+static_assert(block_bytes(SLACK_D) + block_bytes(SLACK_I) == SLACK_NF * (2 * sizeof(double) + 4 * sizeof(int32_t)), "d_slack: 2 doubles and 4 int32 per family and instance");
+size_t SlackWs::bytes(size_t NB) { return NB * (block_bytes(SLACK_D) + block_bytes(SLACK_I)); }
+SlackWs SlackWs::carve(void* base, size_t NB) {
+  SlackWs w;
+  carve_blocks(w, carve_blocks(w, (char*)base, NB, SLACK_D), NB, SLACK_I);
+  return w;
+}
 
 // ---------------------------------------------------------------------------------------------- model
 static bool is_identity(const double* R) {
@@ -729,7 +809,7 @@ extern "C" int wbc_batch_get_stat(WbcBatch* b, const char* name, void* stream, i
     if (!b->d_defer || b->last_path == TICK_GENERAL) return WBC_OK;
     int32_t c = 0;
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-    HIP_TRY(hipMemcpy(&c, b->d_defer + 1 + b->max_batch + 2, sizeof c, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&c, defer_tail(b) + DEFER_TAIL_LAST, sizeof c, hipMemcpyDeviceToHost));
     *out = c;
     return WBC_OK;
   }
@@ -738,7 +818,7 @@ extern "C" int wbc_batch_get_stat(WbcBatch* b, const char* name, void* stream, i
     if (!b->d_defer || b->last_path == TICK_GENERAL || !b->count_pivoted) return WBC_OK;
     int32_t c = 0;
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-    HIP_TRY(hipMemcpy(&c, b->d_defer + 1 + b->max_batch, sizeof c, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&c, defer_tail(b), sizeof c, hipMemcpyDeviceToHost));
     *out = c;
     return WBC_OK;
   }
@@ -756,7 +836,7 @@ extern "C" int wbc_batch_get_stat(WbcBatch* b, const char* name, void* stream, i
     if (!b->d_traj) return WBC_OK;
     int32_t c = 0;
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-    HIP_TRY(hipMemcpy(&c, (const char*)b->d_traj + (size_t)b->max_batch * (TRAJ_WS_DOUBLES * sizeof(double) + TRAJ_WS_INTS * sizeof(int32_t)), sizeof c, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&c, TrajWs::carve(b->d_traj, (size_t)b->max_batch).bad_count, sizeof c, hipMemcpyDeviceToHost));
     *out = c;
     return WBC_OK;
   }
@@ -900,11 +980,9 @@ static int auto_posture(WbcBatch* b, KernelArgs& a, int B, void* stream) {
     }
     if (all_static && !a.in.q_con) { a.post_static = 1; return WBC_OK; }
   }
-  if (!b->d_pu) {
-    HIP_TRY(hipMalloc((void**)&b->d_pu, sizeof(double) * WBC_V_STRIDE * (size_t)b->max_batch));
-    HIP_TRY(hipMalloc((void**)&b->d_pq, sizeof(double) * WBC_Q_STRIDE * (size_t)b->max_batch));
-  }
-  if (int rc = run_posture(b, B, a.in.q, a.in.model_id, b->d_pu, b->d_pq, stream)) return rc;
+  int rc;
+  if ((rc = ensure(b->d_pu, sizeof(double) * WBC_V_STRIDE * (size_t)b->max_batch)) || (rc = ensure(b->d_pq, sizeof(double) * WBC_Q_STRIDE * (size_t)b->max_batch))) return rc;
+  if ((rc = run_posture(b, B, a.in.q, a.in.model_id, b->d_pu, b->d_pq, stream))) return rc;
   a.in.posture_u = b->d_pu;
   if (literal && !a.in.q_con) a.in.q_con = b->d_pq;
   return WBC_OK;
@@ -993,7 +1071,7 @@ static TickPath select_tick_path(const WbcBatch* b, const KernelArgs& a, const W
 // the "deferred_last" statistic (the instances a packed kernel's tail redid) and this launch's sequence number (0 is the cleared word's).
 static int prepare_tick(WbcBatch* b, KernelArgs& a, void* stream, TickPath path) {
   if (path != TICK_GENERAL && !a.out.status) {
-    if (!b->d_status) HIP_TRY(hipMalloc((void**)&b->d_status, sizeof(int32_t) * (size_t)b->max_batch));
+    if (int rc = ensure(b->d_status, sizeof(int32_t) * (size_t)b->max_batch)) return rc;
     a.out.status = b->d_status;
   }
   if (path >= TICK_SIM3P) {
@@ -1008,13 +1086,13 @@ static int prepare_tick(WbcBatch* b, KernelArgs& a, void* stream, TickPath path)
   if (path == TICK_SIM3 || path == TICK_SIM3P) a.dbg_force_defer = b->force_defer;
   if (path == TICK_SIM3) {    // the list of the instances the compact kernel leaves to the deferred pass, the pivot counter
     if (!b->d_defer) {
-      HIP_TRY(hipMalloc((void**)&b->d_defer, sizeof(int32_t) * ((size_t)b->max_batch + 4)));
-      HIP_TRY(hipMemsetAsync(b->d_defer, 0, sizeof(int32_t) * ((size_t)b->max_batch + 4), (hipStream_t)stream));   // (on the CALL's stream: a null-stream memset is not ordered against a non-blocking caller stream)
+      HIP_TRY(hipMalloc((void**)&b->d_defer, defer_bytes(b)));
+      HIP_TRY(hipMemsetAsync(b->d_defer, 0, defer_bytes(b), (hipStream_t)stream));   // (on the CALL's stream: a null-stream memset is not ordered against a non-blocking caller stream)
     }
     a.defer = b->d_defer;                                  // (count = 0 here: wbc_tick_deferred_kernel leaves the list empty behind it)
-    a.defer_aux = b->d_defer + 1 + b->max_batch;
+    a.defer_aux = defer_tail(b);
     if (b->count_pivoted) {
-      a.pivot_count = b->d_defer + 1 + b->max_batch;
+      a.pivot_count = defer_tail(b);
       HIP_TRY(hipMemsetAsync(a.pivot_count, 0, sizeof(int32_t), (hipStream_t)stream));
     }
   }
@@ -1232,66 +1310,32 @@ extern "C" int wbc_state_slack(WbcBatch* b, int B, const double* q, const double
   return st.finish();
 }
 
-// K closed-loop ticks: the mutable controller state lives in the handle's rollout workspace; in0 is only read.
-static int rollout_run(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
-                       const WbcTracks* tracks, const WbcTrackScores* scores, bool one_track, int mem, void* stream,
-                       const WbcSlackWatch* watch = nullptr);
-extern "C" int wbc_rollout(WbcBatch* b, int B, const WbcTickIn* in0, double dt, const WbcRollout* r, int mem, void* stream) {
-  return wbc_rollout_tp(b, B, in0, nullptr, dt, r, mem, stream);
+// ---- The roll-out pipeline (wbc_rollout / _tp / _traj / _tracks / _watch): rollout_run is the one loop — check, stage,
+// seed, begin extensions, per tick {posture, tick, update, extensions}, gather extensions, gather state, finish. An extension (TracksExt,
+// WatchExt) holds the caller's structs, its kernels' argument struct and its counts, and provides stage (its Stager registrations), begin,
+// after_tick(k) and gather; one the entry point does not pass adds nothing to the stream.
+struct Roll {                // what the stages of one call share
+  WbcBatch* b; int B, ticks, total; size_t n; hipStream_t s;   // total: ticks + hold_ticks
+  WbcRollout ro; RollWs w;   // the caller's struct, its pointers staged; the workspace
+  WbcTickIn first;           // the call's inputs as staged, before the loop points the mutable ones at the workspace
+  UpdateArgs u;
+};
+static int give(hipStream_t s, void* dst, const void* src, size_t bytes) {   // a block to where it is wanted: a result the caller asked for, a state the caller gave
+  if (dst && src) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s));
+  return WBC_OK;
 }
-extern "C" int wbc_rollout_tp(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r, int mem,
-                              void* stream) {
-  return rollout_run(b, B, in0, tp, dt, r, nullptr, nullptr, false, mem, stream);
-}
-// The roll-out loop of wbc_rollout / wbc_rollout_tp / wbc_rollout_traj / wbc_rollout_tracks. tracks == nullptr: one linear segment
-// (WbcRollout.ee_target_step), the launches, memsets and copies of wbc_rollout_tp and nothing else. With tracks (arguments checked by the entry
-// point): the update kernel leaves the targets alone and one wbc_traj_tick_kernel per tick scores the tick and writes every followed target of
-// the next. one_track: wbc_rollout_traj's call — the gripper's position comes from the update kernel's grip_trace row, and a constant trunk
-// step stays with the update kernel; otherwise the update kernel writes the six frames' positions of the tick into the workspace.
-// watch (wbc_rollout_watch, arguments checked by the entry point): one wbc_slack_kernel per tick behind the update kernel, on the state it
-// just wrote; the kernel keeps the per-instance results in the handle's workspace, copied out (and reduced per group) after the last tick.
-// watch == nullptr adds nothing to the sequence above.
-static int rollout_run(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
-                       const WbcTracks* tracks, const WbcTrackScores* scores, bool one_track, int mem, void* stream,
-                       const WbcSlackWatch* watch) {
-  int rc = check_batch(b, B, "wbc_rollout", true);
-  if (rc) return rc;
-  if (!r || r->ticks < 1 || !(dt > 0)) return fail(WBC_E_ARG, "wbc_rollout: ticks >= 1 and dt > 0 required");
-  if (r->hold_ticks < 0 || (r->mode != WBC_ROLLOUT_RUNNING && r->mode != WBC_ROLLOUT_WARMUP))
-    return fail(WBC_E_ARG, "wbc_rollout: hold_ticks >= 0 and mode WBC_ROLLOUT_RUNNING / WBC_ROLLOUT_WARMUP required");
-  if ((rc = validate_tick_in(b, in0, "wbc_rollout"))) return rc;
-  if (!in0->ee_target || !in0->prev_ee_target) return fail(WBC_E_ARG, "wbc_rollout: ee_target / prev_ee_target are required (the base estimator reads the foot targets)");
-  HIP_TRY(hipSetDevice(b->device_id));
-  if (watch && (rc = slack_ready(b, "wbc_rollout_watch"))) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const size_t n = (size_t)B, NB = (size_t)b->max_batch;
-  // workspace layout (doubles per instance), then two int32 per instance
-  enum { O_Q = 0, O_QN = 27, O_QD = 54, O_EET = 80, O_EEP = 95, O_TT = 110, O_TP = 113, O_EPR = 116, O_TPR = 161, O_END = 170 };
-  if (!b->d_roll) HIP_TRY(hipMalloc(&b->d_roll, NB * (O_END * sizeof(double) + 2 * sizeof(int32_t) + 2 * sizeof(unsigned long long))));
-  double* W = (double*)b->d_roll;
-  auto blk = [&](int off) { return W + NB * (size_t)off; };
-  int32_t* w_status = (int32_t*)(W + NB * O_END);
-  int32_t* w_iters = w_status + NB;
-  unsigned long long* w_ws = (unsigned long long*)(w_iters + NB);     // [NB][2] working sets carried from tick to tick (8-byte aligned)
 
-  KernelArgs a;
-  fill_args(a, b, B, dt);
-  a.in = *in0;
-  WbcRollout ro = *r;
-  Stager st{b, mem, s, {}};
-  stage_tick_in(st, a.in, B, b);
-  st.in(&tp, n);                         // (every tick reads the same rows)
-  st.in(&ro.ee_target_step, n * 15); st.in(&ro.trunk_target_step, n * 3); st.in(&ro.imu, n * 4);
-  st.out(&ro.q_final, n * WBC_Q_STRIDE); st.out(&ro.qdot_last, n * WBC_V_STRIDE); st.out(&ro.ee_target_final, n * 15);
-  st.out(&ro.grip_trace, (size_t)(r->ticks + r->hold_ticks) * n * 3); st.out(&ro.status_max, n); st.out(&ro.iters_sum, n);
-  WbcTracks tj;
-  WbcTrackScores so;
-  memset(&tj, 0, sizeof tj); memset(&so, 0, sizeof so);
-  size_t nsc = 0;                        // scored frames
-  if (tracks) {
-    tj = *tracks;
-    if (scores) so = *scores;
-    nsc = (size_t)__builtin_popcount((unsigned)so.score_mask);
+// Tracks (wbc_rollout_traj / wbc_rollout_tracks, arguments checked by the entry point): the update kernel leaves the followed targets alone
+// and one wbc_traj_tick_kernel per tick scores the tick and writes every followed target of the next. one_track: wbc_rollout_traj's call —
+// the gripper's position comes from the update kernel's grip_trace row, and a constant trunk step stays with the update kernel; otherwise
+// the update kernel writes the six frames' positions of the tick into the workspace, beside the scores ([scored frame][B] within regions
+// sized for six frames of max_batch), the bad-row flags and their count.
+struct TracksExt {
+  bool scored, one_track; size_t nsc;   // nsc: scored frames
+  WbcTracks tj; WbcTrackScores so; TrajArgs ta; TrajWs ws;
+  TracksExt(const WbcTracks& tracks, const WbcTrackScores* scores, bool one)
+      : scored(scores != nullptr), one_track(one), nsc(scores ? (size_t)__builtin_popcount((unsigned)scores->score_mask) : 0), tj(tracks), so(scores ? *scores : WbcTrackScores{}), ta{}, ws{} {}
+  void stage(Stager& st, size_t n, int ticks) {
     const size_t ng = so.group_size > 0 ? n / (size_t)so.group_size : 0;
     for (int j = 0; j < tj.n_tracks; ++j) {
       WbcTrack& t = tj.track[j];
@@ -1300,187 +1344,220 @@ static int rollout_run(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskPa
     }
     st.out(&tj.trunk_target_final, n * 3);
     st.out(&so.err_sq_sum, nsc * n); st.out(&so.err_max, nsc * n); st.out(&so.err_max_tick, nsc * n); st.out(&so.err_final, nsc * n);
-    st.out(&so.first_bad_tick, n); st.out(&so.bad_ticks, n); st.out(&so.trace, (size_t)r->ticks * nsc * n * 3);
+    st.out(&so.first_bad_tick, n); st.out(&so.bad_ticks, n); st.out(&so.trace, (size_t)ticks * nsc * n * 3);
     st.out(&so.group_rms, nsc * ng); st.out(&so.group_err_max, nsc * ng); st.out(&so.group_worst_status, ng); st.out(&so.group_bad_instances, ng);
   }
-  WbcSlackWatch wo;
-  memset(&wo, 0, sizeof wo);
-  size_t nw = 0;                         // watched families
-  if (watch) {
-    wo = *watch;
-    nw = (size_t)__builtin_popcount((unsigned)wo.mask);
-    const size_t ng = wo.group_size > 0 ? n / (size_t)wo.group_size : 0;
-    st.out(&wo.slack_min, nw * n); st.out(&wo.slack_final, nw * n); st.out(&wo.slack_min_tick, nw * n); st.out(&wo.slack_min_which, nw * n);
-    st.out(&wo.neg_ticks, nw * n); st.out(&wo.first_neg_tick, nw * n); st.out(&wo.trace, (size_t)(r->ticks + r->hold_ticks) * nw * n);
-    st.out(&wo.group_min, nw * ng); st.out(&wo.group_neg_instances, nw * ng);
-  }
-  if ((rc = st.stage())) return rc;
-  // seed the mutable state from in0
-  auto seed = [&](int off, const double* src, size_t k) -> int {
-    if (src) HIP_TRY(hipMemcpyAsync(blk(off), src, n * k * sizeof(double), hipMemcpyDeviceToDevice, s));
-    return WBC_OK;
-  };
-  if ((rc = seed(O_Q, a.in.q, 27)) || (rc = seed(O_EET, a.in.ee_target, 15)) || (rc = seed(O_EEP, a.in.prev_ee_target, 15)) ||
-      (rc = seed(O_TT, a.in.trunk_target, 3)) || (rc = seed(O_TP, a.in.prev_trunk_target, 3)) ||
-      (rc = seed(O_EPR, a.in.ee_prev_rot, 45)) || (rc = seed(O_TPR, a.in.trunk_prev_rot, 9))) return rc;
-  if (b->warm_start) {   // first tick: the caller's working set if there is one, else cold
-    if (a.in.working_set) HIP_TRY(hipMemcpyAsync(w_ws, a.in.working_set, n * 2 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
-    else HIP_TRY(hipMemsetAsync(w_ws, 0, n * 2 * sizeof(unsigned long long), s));
-    a.ws_in = w_ws; a.ws_out = w_ws;
-  }
-  if (ro.status_max) HIP_TRY(hipMemsetAsync(ro.status_max, 0, n * sizeof(int32_t), s));
-  if (ro.iters_sum) HIP_TRY(hipMemsetAsync(ro.iters_sum, 0, n * sizeof(int32_t), s));
-  const WbcTickIn first = a.in;
-  a.in.q = blk(O_Q); a.in.ee_target = blk(O_EET); a.in.prev_ee_target = blk(O_EEP);
-  if (first.trunk_target) a.in.trunk_target = blk(O_TT);
-  if (first.prev_trunk_target) a.in.prev_trunk_target = blk(O_TP);
-  if (first.ee_prev_rot) a.in.ee_prev_rot = blk(O_EPR);
-  if (first.trunk_prev_rot) a.in.trunk_prev_rot = blk(O_TPR);
-  a.out.qdot = blk(O_QD); a.out.q_next = blk(O_QN); a.out.status = w_status; a.out.iters = w_iters;
-
-  UpdateArgs u;
-  memset(&u, 0, sizeof u);
-  u.models = b->d_models; u.cfgs = b->d_cfgs; u.B = B; u.n_models = b->n_models; u.mode = r->mode; u.rot = b->rot;
-  u.q_cur = blk(O_Q); u.q_next = blk(O_QN); u.imu = ro.imu; u.foot_targets = blk(O_EET); u.model_id = a.in.model_id; u.q_new = blk(O_Q);
-  u.ee_target = blk(O_EET); u.prev_ee_target = blk(O_EEP);
-  u.trunk_target = first.trunk_target ? blk(O_TT) : nullptr; u.prev_trunk_target = first.prev_trunk_target ? blk(O_TP) : nullptr;
-  u.ee_prev_rot = first.ee_prev_rot ? blk(O_EPR) : nullptr; u.trunk_prev_rot = first.trunk_prev_rot ? blk(O_TPR) : nullptr;
-  u.ee_ref_rot = first.ee_ref_rot; u.trunk_ref_euler = first.trunk_ref_euler;
-  u.ee_step = ro.ee_target_step; u.trunk_step = ro.trunk_target_step;   // (a trajectory call has no ee_target_step: wbc_traj_tick_kernel moves those targets)
-  if (tracks && !one_track) u.trunk_step = nullptr;   // ... and wbc_rollout_tracks' constant trunk step is added there too, after the tick was scored
-  u.status = w_status; u.iters = w_iters; u.status_max = ro.status_max; u.iters_sum = ro.iters_sum;
-  // the tracks' own state: per-instance scores ([scored frame][B] within regions sized for six frames of max_batch), the frames' positions of
-  // the tick (the gripper row alone in a one-track call without a trace), the bad-row flags and their count
-  TrajArgs ta;
-  memset(&ta, 0, sizeof ta);
-  double* w_frames = nullptr;
-  if (tracks) {
-    if (!b->d_traj) HIP_TRY(hipMalloc(&b->d_traj, NB * (TRAJ_WS_DOUBLES * sizeof(double) + TRAJ_WS_INTS * sizeof(int32_t)) + sizeof(int32_t)));
-    double* T = (double*)b->d_traj;
-    const size_t F = WBC_MAX_TRACKS;
-    ta.err_sq_sum = T; ta.err_max = T + F * NB; ta.err_final = T + 2 * F * NB; w_frames = T + 3 * F * NB;
-    int32_t* I = (int32_t*)(T + (size_t)TRAJ_WS_DOUBLES * NB);
-    ta.bad = I; ta.first_bad_tick = I + NB; ta.bad_ticks = I + 2 * NB; ta.status_max = I + 3 * NB; ta.err_max_tick = I + 4 * NB;
-    ta.bad_count = I + (size_t)TRAJ_WS_INTS * NB;
-    ta.B = B; ta.ticks = r->ticks; ta.n_tracks = tj.n_tracks; ta.do_sum = scores != nullptr; ta.score_mask = so.score_mask;
+  int begin(Roll& R) {
+    if (int rc = ensure(R.b->d_traj, TrajWs::bytes((size_t)R.b->max_batch))) return rc;
+    ws = TrajWs::carve(R.b->d_traj, (size_t)R.b->max_batch);
+    ta.err_sq_sum = ws.err_sq_sum; ta.err_max = ws.err_max; ta.err_final = ws.err_final; ta.err_max_tick = ws.err_max_tick;
+    ta.bad = ws.bad; ta.first_bad_tick = ws.first_bad_tick; ta.bad_ticks = ws.bad_ticks; ta.status_max = ws.status_max; ta.bad_count = ws.bad_count;
+    ta.B = R.B; ta.ticks = R.ticks; ta.n_tracks = tj.n_tracks; ta.do_sum = scored; ta.score_mask = so.score_mask;
     for (int j = 0; j < tj.n_tracks; ++j) {
       const WbcTrack& t = tj.track[j];
       TrajTrack& d = ta.tr[j];
       d.target = t.target; d.kind = t.kind; d.S = t.max_points;
       d.points = t.points; d.tangents = t.tangents; d.n_points = t.n_points; d.du = t.du; d.du_all = t.du_all;
     }
-    ta.ee_target = blk(O_EET); ta.trunk_target = first.trunk_target ? blk(O_TT) : nullptr;
-    if (!one_track && ta.trunk_target) ta.trunk_step = ro.trunk_target_step;
+    ta.ee_target = R.w.ee_target; ta.trunk_target = R.w.trunk_target;
+    if (!one_track) R.u.trunk_step = nullptr;   // wbc_rollout_tracks' constant trunk step is added by the trajectory kernel, after the tick was scored
+    if (!one_track && ta.trunk_target) ta.trunk_step = R.ro.trunk_target_step;
     ta.one_track = one_track ? 1 : 0;
     if (one_track) ta.reached_stride = 3;                 // reached_off all 0: the gripper row
     else {
       ta.reached_stride = 3 * WBC_MAX_TRACKS;
       for (int f = 0; f < WBC_MAX_TRACKS; ++f) ta.reached_off[f] = 3 * f;
-      if (ta.do_sum && nsc > 0) u.frames_out = w_frames;
+      if (ta.do_sum && nsc > 0) R.u.frames_out = ws.frames;
     }
-    ta.status = w_status; ta.ro_status_max = ro.status_max;
-    HIP_TRY(hipMemsetAsync(ta.bad_count, 0, sizeof(int32_t), s));
-    if (int e = launch_traj_begin(ta, stream)) return fail(WBC_E_HIP, "trajectory kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    ta.status = R.w.status; ta.ro_status_max = R.ro.status_max;
+    HIP_TRY(hipMemsetAsync(ta.bad_count, 0, sizeof(int32_t), R.s));
+    return launch_rc(launch_traj_begin(ta, R.s), "trajectory");
   }
-  // the watch's accumulators: [watched family][B] within regions sized for four families of max_batch
-  SlackArgs sa;
-  memset(&sa, 0, sizeof sa);
-  if (watch) {
-    if (!b->d_slack) HIP_TRY(hipMalloc(&b->d_slack, NB * SLACK_NF * (2 * sizeof(double) + 4 * sizeof(int32_t))));
-    double* S = (double*)b->d_slack;
-    const size_t F = SLACK_NF;
-    sa.slack_min = S; sa.slack_final = S + F * NB;
-    int32_t* I = (int32_t*)(S + 2 * F * NB);
-    sa.min_tick = I; sa.min_which = I + F * NB; sa.neg_ticks = I + 2 * F * NB; sa.first_neg = I + 3 * F * NB;
+  // no trace asked for in a one-track call: the summary reads the tick's gripper row from the workspace
+  double* grip_row() const { return one_track && ta.do_sum ? ws.frames : nullptr; }
+  int after_tick(Roll& R, int k) {
+    ta.reached = one_track ? R.u.grip_trace : ws.frames;
+    ta.trace = so.trace ? so.trace + (size_t)k * nsc * R.n * 3 : nullptr;
+    return launch_rc(launch_traj_tick(ta, k, R.s), "trajectory");
+  }
+  int gather(Roll& R) {
+    if (!scored) return WBC_OK;
+    const size_t fd = nsc * R.n * sizeof(double), fi = nsc * R.n * sizeof(int32_t), ii = R.n * sizeof(int32_t);
+    int rc;
+    if ((rc = give(R.s, so.err_sq_sum, ta.err_sq_sum, fd)) || (rc = give(R.s, so.err_max, ta.err_max, fd)) || (rc = give(R.s, so.err_final, ta.err_final, fd)) ||
+        (rc = give(R.s, so.err_max_tick, ta.err_max_tick, fi)) || (rc = give(R.s, so.first_bad_tick, ta.first_bad_tick, ii)) ||
+        (rc = give(R.s, so.bad_ticks, ta.bad_ticks, ii))) return rc;
+    if (so.group_size <= 0 || !(so.group_rms || so.group_err_max || so.group_worst_status || so.group_bad_instances)) return WBC_OK;
+    TrajGroupArgs ga{};
+    ga.G = R.B / so.group_size; ga.M = so.group_size; ga.ticks = R.ticks; ga.n_scored = (int32_t)nsc;
+    ga.err_sq_sum = ta.err_sq_sum; ga.err_max = ta.err_max; ga.status_max = ta.status_max; ga.bad_ticks = ta.bad_ticks;
+    ga.group_rms = so.group_rms; ga.group_err_max = so.group_err_max; ga.group_worst_status = so.group_worst_status;
+    ga.group_bad_instances = so.group_bad_instances;
+    return launch_rc(launch_traj_groups(ga, R.s), "trajectory");
+  }
+};
+
+// The watch (wbc_rollout_watch, arguments checked by the entry point; slack_ready has run): one wbc_slack_kernel per tick behind the update
+// kernel, on the state it just wrote; the kernel keeps the per-instance results in the handle's workspace ([watched family][B] within regions
+// sized for four families of max_batch), copied out (and reduced per group) after the last tick.
+struct WatchExt {
+  WbcSlackWatch wo; size_t nw; SlackArgs sa;   // nw: watched families
+  explicit WatchExt(const WbcSlackWatch& watch) : wo(watch), nw((size_t)__builtin_popcount((unsigned)wo.mask)), sa{} {}
+  void stage(Stager& st, size_t n, int total) {
+    const size_t ng = wo.group_size > 0 ? n / (size_t)wo.group_size : 0;
+    st.out(&wo.slack_min, nw * n); st.out(&wo.slack_final, nw * n); st.out(&wo.slack_min_tick, nw * n); st.out(&wo.slack_min_which, nw * n);
+    st.out(&wo.neg_ticks, nw * n); st.out(&wo.first_neg_tick, nw * n); st.out(&wo.trace, (size_t)total * nw * n);
+    st.out(&wo.group_min, nw * ng); st.out(&wo.group_neg_instances, nw * ng);
+  }
+  int begin(Roll& R) {
+    WbcBatch* b = R.b;
+    if (int rc = ensure(b->d_slack, SlackWs::bytes((size_t)b->max_batch))) return rc;
+    const SlackWs ws = SlackWs::carve(b->d_slack, (size_t)b->max_batch);
+    sa.slack_min = ws.slack_min; sa.slack_final = ws.slack_final;
+    sa.min_tick = ws.min_tick; sa.min_which = ws.min_which; sa.neg_ticks = ws.neg_ticks; sa.first_neg = ws.first_neg;
     sa.models = b->d_models; sa.cfgs = b->d_cfgs; sa.plans = b->d_plans; sa.lim = b->d_slack_lim;
-    sa.B = B; sa.n_models = b->n_models; sa.rot = b->rot; sa.mask = wo.mask;
-    sa.q = blk(O_Q); sa.box = first.trunk_box_center; sa.model_id = first.model_id;
+    sa.B = R.B; sa.n_models = b->n_models; sa.rot = b->rot; sa.mask = wo.mask;
+    sa.q = R.w.q; sa.box = R.first.trunk_box_center; sa.model_id = R.first.model_id;
+    return WBC_OK;
   }
+  int after_tick(Roll& R, int k) {
+    sa.k = k;
+    sa.trace = wo.trace ? wo.trace + (size_t)k * nw * R.n : nullptr;
+    return launch_rc(launch_slack(sa, R.s), "slack");
+  }
+  int gather(Roll& R) {
+    const size_t fd = nw * R.n * sizeof(double), fi = nw * R.n * sizeof(int32_t);
+    int rc;
+    if ((rc = give(R.s, wo.slack_min, sa.slack_min, fd)) || (rc = give(R.s, wo.slack_final, sa.slack_final, fd)) ||
+        (rc = give(R.s, wo.slack_min_tick, sa.min_tick, fi)) || (rc = give(R.s, wo.slack_min_which, sa.min_which, fi)) ||
+        (rc = give(R.s, wo.neg_ticks, sa.neg_ticks, fi)) || (rc = give(R.s, wo.first_neg_tick, sa.first_neg, fi))) return rc;
+    if (wo.group_size <= 0 || !(wo.group_min || wo.group_neg_instances)) return WBC_OK;
+    SlackGroupArgs ga{};
+    ga.G = R.B / wo.group_size; ga.M = wo.group_size; ga.n_w = (int32_t)nw;
+    ga.slack_min = sa.slack_min; ga.neg_ticks = sa.neg_ticks; ga.group_min = wo.group_min; ga.group_neg_instances = wo.group_neg_instances;
+    return launch_rc(launch_slack_groups(ga, R.s), "slack");
+  }
+};
+
+// K closed-loop ticks: the mutable controller state lives in the handle's rollout workspace; in0 is only read. Without extensions (tk, wx
+// NULL): one linear segment (WbcRollout.ee_target_step), the launches, memsets and copies of wbc_rollout_tp and nothing else.
+static int rollout_run(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r, int mem, void* stream,
+                       TracksExt* tk = nullptr, WatchExt* wx = nullptr) {
+  // check
+  int rc = check_batch(b, B, "wbc_rollout", true);
+  if (rc) return rc;
+  if (!r || r->ticks < 1 || !(dt > 0)) return fail(WBC_E_ARG, "wbc_rollout: ticks >= 1 and dt > 0 required");
+  if (r->hold_ticks < 0 || (r->mode != WBC_ROLLOUT_RUNNING && r->mode != WBC_ROLLOUT_WARMUP))
+    return fail(WBC_E_ARG, "wbc_rollout: hold_ticks >= 0 and mode WBC_ROLLOUT_RUNNING / WBC_ROLLOUT_WARMUP required");
+  if ((rc = validate_tick_in(b, in0, "wbc_rollout"))) return rc;
+  if (!in0->ee_target || !in0->prev_ee_target) return fail(WBC_E_ARG, "wbc_rollout: ee_target / prev_ee_target are required (the base estimator reads the foot targets)");
+  HIP_TRY(hipSetDevice(b->device_id));
+  if (wx && (rc = slack_ready(b, "wbc_rollout_watch"))) return rc;
+  Roll R{};
+  R.b = b; R.B = B; R.ticks = r->ticks; R.total = r->ticks + r->hold_ticks; R.n = (size_t)B; R.s = (hipStream_t)stream; R.ro = *r;
+  const size_t n = R.n;
+  hipStream_t s = R.s;
+  if ((rc = ensure(b->d_roll, RollWs::bytes((size_t)b->max_batch)))) return rc;
+  RollWs& w = R.w = RollWs::carve(b->d_roll, (size_t)b->max_batch);
+  // the blocks of the optional inputs the caller did not give: NULL from here on, like the inputs
+  if (!in0->trunk_target) w.trunk_target = nullptr;
+  if (!in0->prev_trunk_target) w.prev_trunk_target = nullptr;
+  if (!in0->ee_prev_rot) w.ee_prev_rot = nullptr;
+  if (!in0->trunk_prev_rot) w.trunk_prev_rot = nullptr;
+  // stage
+  KernelArgs a;
+  fill_args(a, b, B, dt);
+  a.in = *in0;
+  WbcRollout& ro = R.ro;
+  Stager st{b, mem, s, {}};
+  stage_tick_in(st, a.in, B, b);
+  st.in(&tp, n);                         // (every tick reads the same rows)
+  st.in(&ro.ee_target_step, n * 3 * WBC_NEE); st.in(&ro.trunk_target_step, n * 3); st.in(&ro.imu, n * 4);
+  st.out(&ro.q_final, n * WBC_Q_STRIDE); st.out(&ro.qdot_last, n * WBC_V_STRIDE); st.out(&ro.ee_target_final, n * 3 * WBC_NEE);
+  st.out(&ro.grip_trace, (size_t)R.total * n * 3); st.out(&ro.status_max, n); st.out(&ro.iters_sum, n);
+  if (tk) tk->stage(st, n, R.ticks);
+  if (wx) wx->stage(st, n, R.total);
+  if ((rc = st.stage())) return rc;
+  const size_t d = n * sizeof(double);   // seed the mutable state from in0
+  if ((rc = give(s, w.q, a.in.q, d * WBC_Q_STRIDE)) || (rc = give(s, w.ee_target, a.in.ee_target, d * 3 * WBC_NEE)) ||
+      (rc = give(s, w.prev_ee_target, a.in.prev_ee_target, d * 3 * WBC_NEE)) || (rc = give(s, w.trunk_target, a.in.trunk_target, d * 3)) ||
+      (rc = give(s, w.prev_trunk_target, a.in.prev_trunk_target, d * 3)) || (rc = give(s, w.ee_prev_rot, a.in.ee_prev_rot, d * 9 * WBC_NEE)) ||
+      (rc = give(s, w.trunk_prev_rot, a.in.trunk_prev_rot, d * 9))) return rc;
+  if (b->warm_start) {   // first tick: the caller's working set if there is one, else cold
+    if (a.in.working_set) HIP_TRY(hipMemcpyAsync(w.working_set, a.in.working_set, n * 2 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
+    else HIP_TRY(hipMemsetAsync(w.working_set, 0, n * 2 * sizeof(unsigned long long), s));
+    a.ws_in = w.working_set; a.ws_out = w.working_set;
+  }
+  if (ro.status_max) HIP_TRY(hipMemsetAsync(ro.status_max, 0, n * sizeof(int32_t), s));
+  if (ro.iters_sum) HIP_TRY(hipMemsetAsync(ro.iters_sum, 0, n * sizeof(int32_t), s));
+  R.first = a.in;
+  a.in.q = w.q; a.in.ee_target = w.ee_target; a.in.prev_ee_target = w.prev_ee_target; a.in.trunk_target = w.trunk_target;
+  a.in.prev_trunk_target = w.prev_trunk_target; a.in.ee_prev_rot = w.ee_prev_rot; a.in.trunk_prev_rot = w.trunk_prev_rot;
+  a.out.qdot = w.qdot; a.out.q_next = w.q_next; a.out.status = w.status; a.out.iters = w.iters;
+  UpdateArgs& u = R.u;
+  u.models = b->d_models; u.cfgs = b->d_cfgs; u.B = B; u.n_models = b->n_models; u.mode = r->mode; u.rot = b->rot;
+  u.q_cur = w.q; u.q_next = w.q_next; u.imu = ro.imu; u.foot_targets = w.ee_target; u.model_id = a.in.model_id; u.q_new = w.q;
+  u.ee_target = w.ee_target; u.prev_ee_target = w.prev_ee_target; u.trunk_target = w.trunk_target; u.prev_trunk_target = w.prev_trunk_target;
+  u.ee_prev_rot = w.ee_prev_rot; u.trunk_prev_rot = w.trunk_prev_rot; u.ee_ref_rot = a.in.ee_ref_rot; u.trunk_ref_euler = a.in.trunk_ref_euler;
+  u.ee_step = ro.ee_target_step; u.trunk_step = ro.trunk_target_step;   // (a trajectory call has no ee_target_step: wbc_traj_tick_kernel moves those targets)
+  u.status = w.status; u.iters = w.iters; u.status_max = ro.status_max; u.iters_sum = ro.iters_sum;
+  // begin extensions
+  if ((tk && (rc = tk->begin(R))) || (wx && (rc = wx->begin(R)))) return rc;
   const WbcTickIn loop_in = a.in;
-  for (int k = 0; k < r->ticks + r->hold_ticks; ++k) {
-    if (k == r->ticks) { u.ee_step = nullptr; u.trunk_step = nullptr; }   // hold phase: the targets stay where they are
+  for (int k = 0; k < R.total; ++k) {
+    if (k == R.ticks) { u.ee_step = nullptr; u.trunk_step = nullptr; }   // hold phase: the targets stay where they are
     a.in = loop_in;                       // auto_posture fills posture_u / q_con afresh every tick
     if ((rc = auto_posture(b, a, B, stream))) return rc;
     if ((rc = launch_tick_auto(b, a, B, stream, tp))) return rc;
-    u.grip_trace = ro.grip_trace ? ro.grip_trace + (size_t)k * n * 3 : nullptr;
-    if (one_track && ta.do_sum && !u.grip_trace) u.grip_trace = w_frames;   // no trace asked for: the summary reads the tick's row from the workspace
+    u.grip_trace = ro.grip_trace ? ro.grip_trace + (size_t)k * n * 3 : (tk ? tk->grip_row() : nullptr);
     if (int e = launch_update_auto(b, u, B, stream)) return fail(WBC_E_HIP, "update kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    if (tracks) {
-      ta.reached = one_track ? u.grip_trace : w_frames;
-      ta.trace = so.trace ? so.trace + (size_t)k * nsc * n * 3 : nullptr;
-      if (int e = launch_traj_tick(ta, k, stream)) return fail(WBC_E_HIP, "trajectory kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    }
-    if (watch) {
-      sa.k = k;
-      sa.trace = wo.trace ? wo.trace + (size_t)k * nw * n : nullptr;
-      if (int e = launch_slack(sa, stream)) return fail(WBC_E_HIP, "slack kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    }
+    if ((tk && (rc = tk->after_tick(R, k))) || (wx && (rc = wx->after_tick(R, k)))) return rc;
   }
-  if (watch) {
-    auto give = [&](void* dst, const void* src, size_t bytes) -> int {
-      if (dst) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s));
-      return WBC_OK;
-    };
-    if ((rc = give(wo.slack_min, sa.slack_min, nw * n * sizeof(double))) || (rc = give(wo.slack_final, sa.slack_final, nw * n * sizeof(double))) ||
-        (rc = give(wo.slack_min_tick, sa.min_tick, nw * n * sizeof(int32_t))) || (rc = give(wo.slack_min_which, sa.min_which, nw * n * sizeof(int32_t))) ||
-        (rc = give(wo.neg_ticks, sa.neg_ticks, nw * n * sizeof(int32_t))) || (rc = give(wo.first_neg_tick, sa.first_neg, nw * n * sizeof(int32_t)))) return rc;
-    if (wo.group_size > 0 && (wo.group_min || wo.group_neg_instances)) {
-      SlackGroupArgs ga;
-      memset(&ga, 0, sizeof ga);
-      ga.G = B / wo.group_size; ga.M = wo.group_size; ga.n_w = (int32_t)nw;
-      ga.slack_min = sa.slack_min; ga.neg_ticks = sa.neg_ticks; ga.group_min = wo.group_min; ga.group_neg_instances = wo.group_neg_instances;
-      if (int e = launch_slack_groups(ga, stream)) return fail(WBC_E_HIP, "slack kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    }
-  }
-  if (tracks && scores) {
-    auto give = [&](void* dst, const void* src, size_t bytes) -> int {
-      if (dst) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s));
-      return WBC_OK;
-    };
-    if ((rc = give(so.err_sq_sum, ta.err_sq_sum, nsc * n * sizeof(double))) || (rc = give(so.err_max, ta.err_max, nsc * n * sizeof(double))) ||
-        (rc = give(so.err_final, ta.err_final, nsc * n * sizeof(double))) || (rc = give(so.err_max_tick, ta.err_max_tick, nsc * n * sizeof(int32_t))) ||
-        (rc = give(so.first_bad_tick, ta.first_bad_tick, n * sizeof(int32_t))) || (rc = give(so.bad_ticks, ta.bad_ticks, n * sizeof(int32_t)))) return rc;
-    if (so.group_size > 0 && (so.group_rms || so.group_err_max || so.group_worst_status || so.group_bad_instances)) {
-      TrajGroupArgs ga;
-      memset(&ga, 0, sizeof ga);
-      ga.G = B / so.group_size; ga.M = so.group_size; ga.ticks = r->ticks; ga.n_scored = (int32_t)nsc;
-      ga.err_sq_sum = ta.err_sq_sum; ga.err_max = ta.err_max; ga.status_max = ta.status_max; ga.bad_ticks = ta.bad_ticks;
-      ga.group_rms = so.group_rms; ga.group_err_max = so.group_err_max; ga.group_worst_status = so.group_worst_status;
-      ga.group_bad_instances = so.group_bad_instances;
-      if (int e = launch_traj_groups(ga, stream)) return fail(WBC_E_HIP, "trajectory kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    }
-  }
-  if (ro.q_final) HIP_TRY(hipMemcpyAsync(ro.q_final, blk(O_Q), n * 27 * sizeof(double), hipMemcpyDeviceToDevice, s));
-  if (ro.qdot_last) HIP_TRY(hipMemcpyAsync(ro.qdot_last, blk(O_QD), n * 26 * sizeof(double), hipMemcpyDeviceToDevice, s));
-  if (ro.ee_target_final) HIP_TRY(hipMemcpyAsync(ro.ee_target_final, blk(O_EET), n * 15 * sizeof(double), hipMemcpyDeviceToDevice, s));
-  if (tj.trunk_target_final && first.trunk_target) HIP_TRY(hipMemcpyAsync(tj.trunk_target_final, blk(O_TT), n * 3 * sizeof(double), hipMemcpyDeviceToDevice, s));
+  // gather extensions, then the state
+  if ((wx && (rc = wx->gather(R))) || (tk && (rc = tk->gather(R)))) return rc;
+  if ((rc = give(s, ro.q_final, w.q, d * WBC_Q_STRIDE)) || (rc = give(s, ro.qdot_last, w.qdot, d * WBC_V_STRIDE)) ||
+      (rc = give(s, ro.ee_target_final, w.ee_target, d * 3 * WBC_NEE)) ||
+      (rc = give(s, tk ? tk->tj.trunk_target_final : nullptr, w.trunk_target, d * 3))) return rc;
   return st.finish();
 }
 
+extern "C" int wbc_rollout_tp(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r, int mem, void* stream) {
+  return rollout_run(b, B, in0, tp, dt, r, mem, stream);
+}
+extern "C" int wbc_rollout(WbcBatch* b, int B, const WbcTickIn* in0, double dt, const WbcRollout* r, int mem, void* stream) {
+  return wbc_rollout_tp(b, B, in0, nullptr, dt, r, mem, stream);
+}
+
+// ---- argument checks of the track calls. `who`: the entry point's name; `pre`: "" or "track J: " (the text of every message is the callers')
+static int check_group_size(const char* who, int group_size, int B) {
+  if (group_size < 0 || (group_size > 0 && (B < 1 || B % group_size != 0))) return fail(WBC_E_ARG, "%s: group_size = %d does not divide B = %d", who, group_size, B);
+  return WBC_OK;
+}
+static int check_track(const WbcTrack& t, const char* who, const char* pre) {
+  if (t.max_points < 2 || t.max_points > WBC_MAX_TRAJ_POINTS)
+    return fail(WBC_E_ARG, "%s: %smax_points = %d outside [2, %d]", who, pre, t.max_points, WBC_MAX_TRAJ_POINTS);
+  if (!t.points) return fail(WBC_E_ARG, "%s: %spoints is required", who, pre);
+  if (t.tangents && t.kind == WBC_TRACK_LINEAR) return fail(WBC_E_ARG, "%s: %stangents must be NULL for a LINEAR track", who, pre);
+  if (!t.du && !(std::isfinite(t.du_all) && t.du_all > 0)) return fail(WBC_E_ARG, "%s: %sdu_all must be finite and positive when du is NULL", who, pre);
+  return WBC_OK;
+}
+
 // The roll-out along per-instance milestone trajectories (WbcTrajectory), scored on the device (WbcRolloutSummary): argument checks, then
-// the shared loop.
+// the shared loop on the one-track call: a LINEAR track of end effector ee_index, the gripper scored.
 extern "C" int wbc_rollout_traj(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
                                 const WbcTrajectory* traj, const WbcRolloutSummary* sum, int mem, void* stream) {
   if (!r || !traj) return fail(WBC_E_ARG, "wbc_rollout_traj: r and traj are required");
   if (r->ee_target_step) return fail(WBC_E_ARG, "wbc_rollout_traj: ee_target_step must be NULL (the trajectory moves the followed target; the other EE targets are constant)");
   if (r->hold_ticks != 0) return fail(WBC_E_ARG, "wbc_rollout_traj: hold_ticks must be 0 (a trajectory holds its last milestone by itself)");
-  if (traj->max_points < 2 || traj->max_points > WBC_MAX_TRAJ_POINTS)
-    return fail(WBC_E_ARG, "wbc_rollout_traj: max_points = %d outside [2, %d]", traj->max_points, WBC_MAX_TRAJ_POINTS);
   if (traj->ee_index < 0 || traj->ee_index >= WBC_NEE) return fail(WBC_E_ARG, "wbc_rollout_traj: ee_index = %d outside [0, %d]", traj->ee_index, WBC_NEE - 1);
-  if (!traj->points) return fail(WBC_E_ARG, "wbc_rollout_traj: points is required");
-  if (!traj->du && !(std::isfinite(traj->du_all) && traj->du_all > 0))
-    return fail(WBC_E_ARG, "wbc_rollout_traj: du_all must be finite and positive when du is NULL");
-  if (sum && (sum->group_size < 0 || (sum->group_size > 0 && B % sum->group_size != 0)))
-    return fail(WBC_E_ARG, "wbc_rollout_traj: group_size = %d does not divide B = %d", sum->group_size, B);
-  // the one-track call: a LINEAR track of end effector ee_index, the gripper scored
-  WbcTracks tk;
-  WbcTrackScores sc;
-  memset(&tk, 0, sizeof tk); memset(&sc, 0, sizeof sc);
-  tk.n_tracks = 1;
+  WbcTracks tk{};
+  WbcTrackScores sc{};
   WbcTrack& t = tk.track[0];
+  tk.n_tracks = 1; sc.score_mask = 1 << 4;
   t.target = traj->ee_index; t.kind = WBC_TRACK_LINEAR; t.max_points = traj->max_points;
   t.points = traj->points; t.n_points = traj->n_points; t.du = traj->du; t.du_all = traj->du_all;
-  sc.score_mask = 1 << 4;
+  int rc;
+  if ((rc = check_track(t, "wbc_rollout_traj", "")) || (sum && (rc = check_group_size("wbc_rollout_traj", sum->group_size, B)))) return rc;
   if (sum) {
     sc.group_size = sum->group_size;
     sc.err_sq_sum = sum->err_sq_sum; sc.err_max = sum->err_max; sc.err_final = sum->err_final; sc.err_max_tick = sum->err_max_tick;
@@ -1488,19 +1565,14 @@ extern "C" int wbc_rollout_traj(WbcBatch* b, int B, const WbcTickIn* in0, const 
     sc.group_rms = sum->group_rms; sc.group_err_max = sum->group_err_max;
     sc.group_worst_status = sum->group_worst_status; sc.group_bad_instances = sum->group_bad_instances;
   }
-  return rollout_run(b, B, in0, tp, dt, r, &tk, sum ? &sc : nullptr, true, mem, stream);
+  TracksExt ext(tk, sum ? &sc : nullptr, true);
+  return rollout_run(b, B, in0, tp, dt, r, mem, stream, &ext);
 }
 
-// The roll-out with several followed targets (WbcTracks: end effectors and trunk, LINEAR or HERMITE), any frame scored (WbcTrackScores):
-// argument checks, then the shared loop.
-static int rollout_tracks_checked(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
-                                  const WbcTracks* tracks, const WbcTrackScores* scores, int mem, void* stream, const WbcSlackWatch* watch);
-extern "C" int wbc_rollout_tracks(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
-                                  const WbcTracks* tracks, const WbcTrackScores* scores, int mem, void* stream) {
-  return rollout_tracks_checked(b, B, in0, tp, dt, r, tracks, scores, mem, stream, nullptr);
-}
-static int rollout_tracks_checked(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
-                                  const WbcTracks* tracks, const WbcTrackScores* scores, int mem, void* stream, const WbcSlackWatch* watch) {
+// The argument checks of wbc_rollout_tracks (several followed targets — WbcTracks: end effectors and trunk, LINEAR or HERMITE — any frame
+// scored: WbcTrackScores), also wbc_rollout_watch's with tracks.
+static int check_tracks_call(int B, const WbcTickIn* in0, const WbcRollout* r, const WbcTracks* tracks, const WbcTrackScores* scores) {
+  const char* who = "wbc_rollout_tracks";
   if (!r || !tracks) return fail(WBC_E_ARG, "wbc_rollout_tracks: r and tracks are required");
   if (r->ee_target_step) return fail(WBC_E_ARG, "wbc_rollout_tracks: ee_target_step must be NULL (tracks move the followed targets; the other EE targets are constant)");
   if (r->hold_ticks != 0) return fail(WBC_E_ARG, "wbc_rollout_tracks: hold_ticks must be 0 (a track holds its last milestone by itself)");
@@ -1513,12 +1585,9 @@ static int rollout_tracks_checked(WbcBatch* b, int B, const WbcTickIn* in0, cons
     if (seen & (1u << t.target)) return fail(WBC_E_ARG, "wbc_rollout_tracks: track %d: target = %d is repeated (each target at most once)", j, t.target);
     seen |= 1u << t.target;
     if (t.kind != WBC_TRACK_LINEAR && t.kind != WBC_TRACK_HERMITE) return fail(WBC_E_ARG, "wbc_rollout_tracks: track %d: kind = %d is no WBC_TRACK_*", j, t.kind);
-    if (t.max_points < 2 || t.max_points > WBC_MAX_TRAJ_POINTS)
-      return fail(WBC_E_ARG, "wbc_rollout_tracks: track %d: max_points = %d outside [2, %d]", j, t.max_points, WBC_MAX_TRAJ_POINTS);
-    if (!t.points) return fail(WBC_E_ARG, "wbc_rollout_tracks: track %d: points is required", j);
-    if (t.tangents && t.kind == WBC_TRACK_LINEAR) return fail(WBC_E_ARG, "wbc_rollout_tracks: track %d: tangents must be NULL for a LINEAR track", j);
-    if (!t.du && !(std::isfinite(t.du_all) && t.du_all > 0))
-      return fail(WBC_E_ARG, "wbc_rollout_tracks: track %d: du_all must be finite and positive when du is NULL", j);
+    char pre[24];
+    snprintf(pre, sizeof pre, "track %d: ", j);
+    if (int rc = check_track(t, who, pre)) return rc;
   }
   const bool trunk_track = (seen >> WBC_TARGET_TRUNK) & 1;
   if (trunk_track && r->trunk_target_step)
@@ -1526,30 +1595,37 @@ static int rollout_tracks_checked(WbcBatch* b, int B, const WbcTickIn* in0, cons
   if (scores) {
     if (scores->score_mask < 0 || scores->score_mask >= (1 << WBC_MAX_TRACKS))
       return fail(WBC_E_ARG, "wbc_rollout_tracks: score_mask = 0x%x has bits beyond frame %d", (unsigned)scores->score_mask, WBC_TARGET_TRUNK);
-    if (scores->group_size < 0 || (scores->group_size > 0 && B % scores->group_size != 0))
-      return fail(WBC_E_ARG, "wbc_rollout_tracks: group_size = %d does not divide B = %d", scores->group_size, B);
+    if (int rc = check_group_size(who, scores->group_size, B)) return rc;
   }
   const bool trunk_scored = scores && ((scores->score_mask >> WBC_TARGET_TRUNK) & 1);
   if ((trunk_track || trunk_scored) && in0 && (!in0->trunk_target || !in0->prev_trunk_target))
     return fail(WBC_E_ARG, "wbc_rollout_tracks: a trunk track or score bit %d needs in0->trunk_target and prev_trunk_target", WBC_TARGET_TRUNK);
-  return rollout_run(b, B, in0, tp, dt, r, tracks, scores, false, mem, stream, watch);
+  return WBC_OK;
+}
+extern "C" int wbc_rollout_tracks(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
+                                  const WbcTracks* tracks, const WbcTrackScores* scores, int mem, void* stream) {
+  if (int rc = check_tracks_call(B, in0, r, tracks, scores)) return rc;
+  TracksExt tk(*tracks, scores, false);
+  return rollout_run(b, B, in0, tp, dt, r, mem, stream, &tk);
 }
 
 // The roll-outs with the slack families watched (WbcSlackWatch): the watch's own argument checks, then the tracks call's (with tracks) and
 // the shared loop. watch == NULL: the call without a watch, launch for launch.
 extern "C" int wbc_rollout_watch(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
                                  const WbcTracks* tracks, const WbcTrackScores* scores, const WbcSlackWatch* watch, int mem, void* stream) {
+  int rc;
   if (scores && !tracks) return fail(WBC_E_ARG, "wbc_rollout_watch: scores needs tracks");
   if (watch) {
     if (watch->mask <= 0 || watch->mask >= (1 << WBC_N_SLACK))
       return fail(WBC_E_ARG, "wbc_rollout_watch: mask = 0x%x must have at least one of the bits 0..%d and none beyond", (unsigned)watch->mask, WBC_N_SLACK - 1);
-    if (watch->group_size < 0 || (watch->group_size > 0 && (B < 1 || B % watch->group_size != 0)))
-      return fail(WBC_E_ARG, "wbc_rollout_watch: group_size = %d does not divide B = %d", watch->group_size, B);
+    if ((rc = check_group_size("wbc_rollout_watch", watch->group_size, B))) return rc;
     if ((watch->mask & ((1 << WBC_SLACK_TRUNK_Z) | (1 << WBC_SLACK_TRUNK_ANG))) && in0 && !in0->trunk_box_center)
       return fail(WBC_E_ARG, "wbc_rollout_watch: the trunk families (mask bits %d, %d) need in0->trunk_box_center", WBC_SLACK_TRUNK_Z, WBC_SLACK_TRUNK_ANG);
   }
-  if (tracks) return rollout_tracks_checked(b, B, in0, tp, dt, r, tracks, scores, mem, stream, watch);
-  return rollout_run(b, B, in0, tp, dt, r, nullptr, nullptr, false, mem, stream, watch);
+  if (tracks && (rc = check_tracks_call(B, in0, r, tracks, scores))) return rc;
+  TracksExt tk(tracks ? *tracks : WbcTracks{}, scores, false);
+  WatchExt wx(watch ? *watch : WbcSlackWatch{});
+  return rollout_run(b, B, in0, tp, dt, r, mem, stream, tracks ? &tk : nullptr, watch ? &wx : nullptr);
 }
 
 static int qp_common(WbcBatch* b, int B, QpArgs& a, int mem, void* stream, const char* who) {

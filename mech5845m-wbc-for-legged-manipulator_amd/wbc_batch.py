@@ -488,24 +488,18 @@ class WbcBatch:
                                               P(qn, f, keep), self._stream(mem)), self.lib)
         return qn
 
-    def rollout(self, inputs, dt, ticks, ee_target_step=None, trunk_target_step=None, imu=None, want_trace=True,
-                mode=capi.ROLLOUT_RUNNING, hold_ticks=0, task_params=None):
-        """K closed-loop ticks on the device (SURVEY.md §8 f1): tick -> update_state -> reference-state side effects ->
-        targets advance by their step; then `hold_ticks` more ticks with the targets held. mode: ROLLOUT_RUNNING
-        (updateState(running=True): IMU fed back, base re-estimated from the stance feet) or ROLLOUT_WARMUP
-        (updateState(running=False), the loop of setInitialState). Returns dict(q, qdot, ee_target, status, iters[,
-        grip_trace [K + hold, B, 3]]). task_params: [B, 85] per-instance weights and gains for every tick (wbc_rollout_tp)."""
-        keep = []
-        extra = [ee_target_step, trunk_target_step, imu, task_params]
-        mem = _mem_of(list(inputs.values()) + extra)
-        q = inputs.get("q")
-        B = self._batch_of(q)
+    # ---- roll-outs: every entry point builds its outputs and its WbcRollout with _rollout_base and adds the structs of its own
+    def _rollout_base(self, inputs, B, keep, ticks, mode, hold_ticks=0, ee_target_step=None, trunk_target_step=None, imu=None, want_trace=False):
+        """-> (out, r): the outputs every roll-out returns (q, qdot, ee_target, status, iters[, grip_trace [ticks + hold_ticks, B, 3]]) and the
+        WbcRollout that points at them and at the step / imu inputs"""
+        q = inputs["q"]
+        K, H = int(ticks), int(hold_ticks)
         out = dict(q=self._alloc(q, (B, NQS)), qdot=self._alloc(q, (B, NV)), ee_target=self._alloc(q, (B, 5, 3)),
                    status=self._alloc(q, (B,), np.int32), iters=self._alloc(q, (B,), np.int32))
         if want_trace:
-            out["grip_trace"] = self._alloc(q, (int(ticks) + int(hold_ticks), B, 3))
+            out["grip_trace"] = self._alloc(q, (K + H, B, 3))
         r = capi.WbcRollout()
-        r.ticks, r.mode, r.hold_ticks = int(ticks), int(mode), int(hold_ticks)
+        r.ticks, r.mode, r.hold_ticks = K, int(mode), H
         f = np.float64
         P = self._p
         r.ee_target_step, r.trunk_target_step, r.imu = (P(ee_target_step, f, keep, B, 15, "ee_target_step"),
@@ -514,6 +508,29 @@ class WbcBatch:
         r.status_max, r.iters_sum = P(out["status"], np.int32, keep), P(out["iters"], np.int32, keep)
         if want_trace:
             r.grip_trace = P(out["grip_trace"], f, keep)
+        return out, r
+
+    @staticmethod
+    def _check_ticks_groups(B, ticks, group_size):
+        """the checks the scored roll-outs share -> group_size as an int"""
+        M = int(group_size)
+        if M < 0 or (M > 0 and B % M != 0):
+            raise capi.WbcError("group_size = %d does not divide B = %d" % (M, B))
+        if int(ticks) < 1:
+            raise capi.WbcError("ticks = %d, want >= 1" % ticks)
+        return M
+
+    def rollout(self, inputs, dt, ticks, ee_target_step=None, trunk_target_step=None, imu=None, want_trace=True,
+                mode=capi.ROLLOUT_RUNNING, hold_ticks=0, task_params=None):
+        """K closed-loop ticks on the device (SURVEY.md §8 f1): tick -> update_state -> reference-state side effects ->
+        targets advance by their step; then `hold_ticks` more ticks with the targets held. mode: ROLLOUT_RUNNING
+        (updateState(running=True): IMU fed back, base re-estimated from the stance feet) or ROLLOUT_WARMUP
+        (updateState(running=False), the loop of setInitialState). Returns dict(q, qdot, ee_target, status, iters[,
+        grip_trace [K + hold, B, 3]]). task_params: [B, 85] per-instance weights and gains for every tick (wbc_rollout_tp)."""
+        keep = []
+        mem = _mem_of(list(inputs.values()) + [ee_target_step, trunk_target_step, imu, task_params])
+        B = self._batch_of(inputs.get("q"))
+        out, r = self._rollout_base(inputs, B, keep, ticks, mode, hold_ticks, ee_target_step, trunk_target_step, imu, want_trace)   # (ticks and hold_ticks: the library's own check)
         tin = self._tick_in(inputs, keep, B)
         tp = _task_params(task_params, B, keep, self.device_id)
         capi.check(self.lib.wbc_rollout_tp(self._h, B, C.byref(tin), tp, float(dt), C.byref(r), mem, self._stream(mem)), self.lib)
@@ -543,11 +560,7 @@ class WbcBatch:
         S = int(shape[1])
         if not 0 <= int(ee_index) < capi.NEE:
             raise capi.WbcError("ee_index = %d outside [0, %d]" % (ee_index, capi.NEE - 1))
-        M = int(group_size)
-        if M < 0 or (M > 0 and B % M != 0):
-            raise capi.WbcError("group_size = %d does not divide B = %d" % (M, B))
-        if int(ticks) < 1:
-            raise capi.WbcError("ticks = %d, want >= 1" % ticks)
+        M = self._check_ticks_groups(B, ticks, group_size)
         f = np.float64
         P = self._p
         t = capi.WbcTrajectory()
@@ -558,17 +571,7 @@ class WbcBatch:
             t.du_all = float(du)
         else:
             t.du = P(du_arr, f, keep, B, 1, "du")
-        out = dict(q=self._alloc(q, (B, NQS)), qdot=self._alloc(q, (B, NV)), ee_target=self._alloc(q, (B, 5, 3)),
-                   status=self._alloc(q, (B,), np.int32), iters=self._alloc(q, (B,), np.int32))
-        if want_trace:
-            out["grip_trace"] = self._alloc(q, (int(ticks), B, 3))
-        r = capi.WbcRollout()
-        r.ticks, r.mode, r.hold_ticks = int(ticks), int(mode), 0
-        r.trunk_target_step, r.imu = P(trunk_target_step, f, keep, B, 3, "trunk_target_step"), P(imu, f, keep, B, 4, "imu")
-        r.q_final, r.qdot_last, r.ee_target_final = P(out["q"], f, keep), P(out["qdot"], f, keep), P(out["ee_target"], f, keep)
-        r.status_max, r.iters_sum = P(out["status"], np.int32, keep), P(out["iters"], np.int32, keep)
-        if want_trace:
-            r.grip_trace = P(out["grip_trace"], f, keep)
+        out, r = self._rollout_base(inputs, B, keep, ticks, mode, 0, None, trunk_target_step, imu, want_trace)
         sm = None
         if want_summary:
             sm = capi.WbcRolloutSummary()
@@ -589,11 +592,9 @@ class WbcBatch:
 
     @staticmethod
     def _target_index(t, what):
-        if isinstance(t, str):
-            if t != "trunk":
-                raise capi.WbcError("%s: %r is neither 'trunk' nor an end effector index 0..%d" % (what, t, capi.NEE - 1))
+        if isinstance(t, str) and t == "trunk":
             return capi.TARGET_TRUNK
-        if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or not 0 <= int(t) <= capi.TARGET_TRUNK:
+        if isinstance(t, (str, bool)) or not isinstance(t, (int, np.integer)) or not 0 <= int(t) <= capi.TARGET_TRUNK:
             raise capi.WbcError("%s: %r is neither 'trunk' nor an end effector index 0..%d" % (what, t, capi.NEE - 1))
         return int(t)
 
@@ -661,27 +662,8 @@ class WbcBatch:
         [n_scored, B / M], group_worst_status, group_bad_instances [B / M] — all reduced on the device."""
         return self._rollout_tracks(inputs, dt, ticks, tracks, score, group_size, want_trace, mode, task_params, trunk_target_step, imu)
 
-    def _rollout_tracks(self, inputs, dt, ticks, tracks, score, group_size, want_trace, mode, task_params, trunk_target_step, imu,
-                        watch=None, ee_target_step=None, hold_ticks=0):
-        """the body of rollout_tracks and rollout_watch. watch: None (wbc_rollout_tracks) or the sorted family indices (wbc_rollout_watch;
-        tracks may then be None, and ee_target_step / hold_ticks are passed on)"""
-        keep = []
-        tracks = [] if (tracks is None and watch is not None) else list(tracks)
-        if not (0 if watch is not None else 1) <= len(tracks) <= capi.MAX_TRACKS:
-            raise capi.WbcError("tracks: %d given, want 1..%d" % (len(tracks), capi.MAX_TRACKS))
-        arrays = [ee_target_step]
-        for i, t in enumerate(tracks):
-            if not isinstance(t, dict) or set(t) - set(self._TRACK_KEYS) or "target" not in t or "points" not in t:
-                raise capi.WbcError("tracks[%d]: want a dict with target, points and optionally kind, tangents, n_points, du" % i)
-            arrays += [t["points"], t.get("tangents"), t.get("n_points"), None if np.isscalar(t.get("du", 0.002)) else t.get("du")]
-        mem = _mem_of(list(inputs.values()) + arrays + [trunk_target_step, imu, task_params])
-        q = inputs.get("q")
-        B = self._batch_of(q)
-        M = int(group_size)
-        if M < 0 or (M > 0 and B % M != 0):
-            raise capi.WbcError("group_size = %d does not divide B = %d" % (M, B))
-        if int(ticks) < 1:
-            raise capi.WbcError("ticks = %d, want >= 1" % ticks)
+    def _tracks_struct(self, tracks, B, keep):
+        """-> (WbcTracks of the list of dicts, the set of followed targets)"""
         f = np.float64
         P = self._p
         tk = capi.WbcTracks()
@@ -717,6 +699,66 @@ class WbcBatch:
                 c.du_all = float(du)
             else:
                 c.du = P(du, f, keep, B, 1, who + ".du")
+        return tk, seen
+
+    def _scores_struct(self, out, like, frames, B, K, M, want_trace, keep):
+        """allocates the scores of `frames` into `out` -> the WbcTrackScores that points at them (None: nothing to score)"""
+        ns = len(frames)
+        if not ns:
+            return None
+        sc = capi.WbcTrackScores()
+        sc.group_size = M
+        for fr in frames:
+            sc.score_mask |= 1 << fr
+        spec = [(n, (ns, B), d) for n, d in self._FRAME_SCORES] + [(n, (B,), d) for n, d in self._INSTANCE_SCORES]
+        if want_trace:
+            spec.append(("trace", (K, ns, B, 3), np.float64))
+        if M > 0:
+            spec += [(n, (ns, B // M) if n in ("group_rms", "group_err_max") else (B // M,), d) for n, d in self._GROUP_SUMMARY]
+        for name, shape, dtype in spec:
+            out[name] = self._alloc(like, shape, dtype)
+            setattr(sc, name, self._p(out[name], dtype, keep))
+        return sc
+
+    def _watch_struct(self, out, like, fams, B, total, M, want_trace, keep):
+        """allocates the watch's results of the families `fams` into `out` -> the WbcSlackWatch that points at them (None: no family)"""
+        nw = len(fams)
+        if not nw:
+            return None
+        wt = capi.WbcSlackWatch()
+        wt.group_size = M
+        for fam in fams:
+            wt.mask |= 1 << fam
+        for name, dtype in self._WATCH_ROWS:
+            out[name] = self._alloc(like, (nw, B), dtype)
+            setattr(wt, name, self._p(out[name], dtype, keep))
+        if want_trace:
+            out["slack_trace"] = self._alloc(like, (total, nw, B))
+            wt.trace = self._p(out["slack_trace"], np.float64, keep)
+        if M > 0:
+            for name, dtype in self._WATCH_GROUPS:
+                out["slack_" + name] = self._alloc(like, (nw, B // M), dtype)
+                setattr(wt, name, self._p(out["slack_" + name], dtype, keep))
+        return wt
+
+    def _rollout_tracks(self, inputs, dt, ticks, tracks, score, group_size, want_trace, mode, task_params, trunk_target_step, imu,
+                        watch=None, ee_target_step=None, hold_ticks=0):
+        """the body of rollout_tracks and rollout_watch. watch: None (wbc_rollout_tracks) or the sorted family indices (wbc_rollout_watch;
+        tracks may then be None, and ee_target_step / hold_ticks are passed on)"""
+        keep = []
+        tracks = [] if (tracks is None and watch is not None) else list(tracks)
+        if not (0 if watch is not None else 1) <= len(tracks) <= capi.MAX_TRACKS:
+            raise capi.WbcError("tracks: %d given, want 1..%d" % (len(tracks), capi.MAX_TRACKS))
+        arrays = [ee_target_step]
+        for i, t in enumerate(tracks):
+            if not isinstance(t, dict) or set(t) - set(self._TRACK_KEYS) or "target" not in t or "points" not in t:
+                raise capi.WbcError("tracks[%d]: want a dict with target, points and optionally kind, tangents, n_points, du" % i)
+            arrays += [t["points"], t.get("tangents"), t.get("n_points"), None if np.isscalar(t.get("du", 0.002)) else t.get("du")]
+        mem = _mem_of(list(inputs.values()) + arrays + [trunk_target_step, imu, task_params])
+        q = inputs.get("q")
+        B = self._batch_of(q)
+        M = self._check_ticks_groups(B, ticks, group_size)
+        tk, seen = self._tracks_struct(tracks, B, keep)
         if capi.TARGET_TRUNK in seen and trunk_target_step is not None:
             raise capi.WbcError("trunk_target_step: not together with a trunk track")
         frames = sorted({self._target_index(s_, "score") for s_ in score})
@@ -725,69 +767,23 @@ class WbcBatch:
         need_trunk = capi.TARGET_TRUNK in seen or capi.TARGET_TRUNK in frames
         if need_trunk and (inputs.get("trunk_target") is None or inputs.get("prev_trunk_target") is None):
             raise capi.WbcError("a trunk track or a scored trunk needs the inputs trunk_target and prev_trunk_target")
-        K, ns, H = int(ticks), len(frames), int(hold_ticks)
+        K, H = int(ticks), int(hold_ticks)
         if H < 0:
             raise capi.WbcError("hold_ticks = %d, want >= 0" % H)
-        out = dict(q=self._alloc(q, (B, NQS)), qdot=self._alloc(q, (B, NV)), ee_target=self._alloc(q, (B, 5, 3)),
-                   status=self._alloc(q, (B,), np.int32), iters=self._alloc(q, (B,), np.int32))
+        out, r = self._rollout_base(inputs, B, keep, K, mode, H, ee_target_step, trunk_target_step, imu, want_trace)
         if inputs.get("trunk_target") is not None and tracks:
             out["trunk_target"] = self._alloc(q, (B, 3))
-            tk.trunk_target_final = P(out["trunk_target"], f, keep)
-        if want_trace:
-            out["grip_trace"] = self._alloc(q, (K + H, B, 3))
-        r = capi.WbcRollout()
-        r.ticks, r.mode, r.hold_ticks = K, int(mode), H
-        r.trunk_target_step, r.imu = P(trunk_target_step, f, keep, B, 3, "trunk_target_step"), P(imu, f, keep, B, 4, "imu")
-        r.ee_target_step = P(ee_target_step, f, keep, B, 15, "ee_target_step")
-        r.q_final, r.qdot_last, r.ee_target_final = P(out["q"], f, keep), P(out["qdot"], f, keep), P(out["ee_target"], f, keep)
-        r.status_max, r.iters_sum = P(out["status"], np.int32, keep), P(out["iters"], np.int32, keep)
-        if want_trace:
-            r.grip_trace = P(out["grip_trace"], f, keep)
-        sc = None
-        if ns:
-            sc = capi.WbcTrackScores()
-            sc.group_size = M
-            for fr in frames:
-                sc.score_mask |= 1 << fr
-            for name, dtype in self._FRAME_SCORES:
-                out[name] = self._alloc(q, (ns, B), dtype)
-            for name, dtype in self._INSTANCE_SCORES:
-                out[name] = self._alloc(q, (B,), dtype)
-            if want_trace:
-                out["trace"] = self._alloc(q, (K, ns, B, 3))
-            if M > 0:
-                for name, dtype in self._GROUP_SUMMARY:
-                    out[name] = self._alloc(q, (ns, B // M) if name in ("group_rms", "group_err_max") else (B // M,), dtype)
-            dtypes = dict(self._FRAME_SCORES + self._INSTANCE_SCORES + self._GROUP_SUMMARY, trace=f)
-            for name, _ in capi.WbcTrackScores._fields_[2:]:
-                if name in out:
-                    setattr(sc, name, P(out[name], dtypes[name], keep))
+            tk.trunk_target_final = self._p(out["trunk_target"], np.float64, keep)
+        sc = self._scores_struct(out, q, frames, B, K, M, want_trace, keep)
         tin = self._tick_in(inputs, keep, B)
         tp = _task_params(task_params, B, keep, self.device_id)
+        sc_ref = C.byref(sc) if sc is not None else None
         if watch is None:
-            capi.check(self.lib.wbc_rollout_tracks(self._h, B, C.byref(tin), tp, float(dt), C.byref(r), C.byref(tk),
-                                                   C.byref(sc) if sc is not None else None, mem, self._stream(mem)), self.lib)
+            capi.check(self.lib.wbc_rollout_tracks(self._h, B, C.byref(tin), tp, float(dt), C.byref(r), C.byref(tk), sc_ref, mem, self._stream(mem)), self.lib)
             return out
-        wt = None
-        if watch:
-            wt = capi.WbcSlackWatch()
-            wt.group_size = M
-            nw = len(watch)
-            for fam in watch:
-                wt.mask |= 1 << fam
-            for name, dtype in self._WATCH_ROWS:
-                out[name] = self._alloc(q, (nw, B), dtype)
-                setattr(wt, name, P(out[name], dtype, keep))
-            if want_trace:
-                out["slack_trace"] = self._alloc(q, (K + H, nw, B))
-                wt.trace = P(out["slack_trace"], f, keep)
-            if M > 0:
-                for name, dtype in self._WATCH_GROUPS:
-                    out["slack_" + name] = self._alloc(q, (nw, B // M), dtype)
-                    setattr(wt, name, P(out["slack_" + name], dtype, keep))
-        capi.check(self.lib.wbc_rollout_watch(self._h, B, C.byref(tin), tp, float(dt), C.byref(r), C.byref(tk) if tracks else None,
-                                              C.byref(sc) if sc is not None else None, C.byref(wt) if wt is not None else None, mem,
-                                              self._stream(mem)), self.lib)
+        wt = self._watch_struct(out, q, watch, B, K + H, M, want_trace, keep)
+        capi.check(self.lib.wbc_rollout_watch(self._h, B, C.byref(tin), tp, float(dt), C.byref(r), C.byref(tk) if tracks else None, sc_ref,
+                                              C.byref(wt) if wt is not None else None, mem, self._stream(mem)), self.lib)
         return out
 
     def integrate(self, q, v, dt, model_id=None):
