@@ -230,7 +230,17 @@ int wbc_batch_create(const WbcModel* const* models, int n_models, int max_batch,
 void wbc_batch_destroy(WbcBatch* b);
 
 /* replaces setTasks / setConstraints / staticReachMode and the weight attributes
- * (Robot_Wrapper4.py:176-193, 1415-1464); cfg applies to model `model_index` of the batch. */
+ * (Robot_Wrapper4.py:176-193, 1415-1464); cfg applies to model `model_index` of the batch.
+ * Ordering: the call waits for the device (every stream, the caller's non-blocking ones included) before it overwrites the model's
+ * configuration and plan, and returns when they are in place. A device-mode call enqueued BEFORE it therefore runs to its end under the old
+ * configuration, every call made AFTER it sees the new one; no call ever sees a mixture. It is not for the hot loop and cannot be captured.
+ * State of a handle ("one handle per device/stream"): a handle keeps, between calls, its options, the per-model configurations and plans,
+ * and device workspaces that it allocates on first use and that every later call of the handle writes (the host-staging workspace, the
+ * status / deferred-list / statistic words of the tick kernels, the wave order, the posture targets, the roll-out, score and watch state).
+ * None of it carries a result from one call into the next: a call returns what it returns on a handle created, configured, given the same
+ * options and called once (the wave order and a warm start change which wave runs an instance and how many working-set changes it takes,
+ * never the answer's definition). Because the workspaces are shared by the handle's calls, calls on ONE handle must be enqueued on one
+ * stream, or be ordered by the caller; independent handles may run on different streams concurrently. */
 int wbc_batch_configure(WbcBatch* b, int model_index, const WbcConfig* cfg);
 int wbc_task_rows(const WbcBatch* b);       /* m of qpA() under the current switches        */
 int wbc_constraint_rows(const WbcBatch* b); /* p of findConstraints()                        */

@@ -735,6 +735,10 @@ extern "C" int wbc_batch_configure(WbcBatch* b, int mi, const WbcConfig* cfg) {
   // (all models of a batch must share the task / constraint switches; that is checked when the batch is USED, so that a
   //  configured multi-model batch can be moved to another switch set one model at a time — same_switches below)
   HIP_TRY(hipSetDevice(b->device_id));
+  // The copies below go through the null stream, which is not ordered against a non-blocking caller stream (torch's side streams are): a
+  // device-mode call still in flight there would read the new configuration from some tick on. The call is rare and blocks the host anyway:
+  // wait for the device first (include/wbc.h states this as the contract).
+  HIP_TRY(hipDeviceSynchronize());
   b->cfg_host[mi] = *cfg;
   b->configured[mi] = true;
   b->plan_host[mi] = DevPlan();

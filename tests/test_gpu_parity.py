@@ -17,6 +17,15 @@ pytestmark = pytest.mark.gpu
 DT = 0.002
 QDOT_TOL = 1e-5          # north_star: "within 1e-5 max-abs on identical inputs"
 REFINED_TOL = 1e-7       # what a path with the iterative refinement on (option refine, default 1) is held to against the oracle, which refines too
+# the bounds of the parity tests below, named so that test_gpu_handle_lifetime.py holds its fresh-handle references to the same numbers
+FK_TOL = 1e-12           # test_fk_jacobians_parity
+ASSEMBLE_TOL = 1e-11     # test_assemble_parity (relerr)
+ASSEMBLE_POSTURE_TOL = 1e-9   # test_tick_parity_posture_modes: the assembled arrays under MANI / HYBRID (relerr)
+POSTURE_TOL = 1e-9       # test_posture_target_parity: u
+QP_LS_TOL = 1e-8         # test_qp_ls_packed_refined_matches_oracle: refined answers
+INTEGRATE_TOL = 1e-13    # test_integrate_parity
+UPDATE_TOL = 1e-13       # test_update_state_parity
+ROLLOUT_Q_TOL = 1e-6     # test_rollout_parity, test_batched_warm_up_matches_the_oracle: state and gripper trace after K ticks
 
 
 def relerr(a, b):
@@ -51,7 +60,7 @@ def test_fk_jacobians_parity(name):
     bt = WbcBatch(m, 512)
     got = bt.fk(q)
     for k in ("oMi", "oMf", "J", "com", "Jcom"):
-        assert np.abs(got[k] - ref[k]).max() < 1e-12, k
+        assert np.abs(got[k] - ref[k]).max() < FK_TOL, k
     bt.close()
 
 
@@ -67,7 +76,7 @@ def test_assemble_parity(wx200, cfg_name, with_rot):
     got = bt.assemble(d, DT)
     for k in ("A", "b", "H", "g", "C", "Clb", "Cub", "lb", "ub"):
         assert got[k].shape == ref[k].shape, k
-        assert relerr(got[k], ref[k]) < 1e-11, (k, relerr(got[k], ref[k]))
+        assert relerr(got[k], ref[k]) < ASSEMBLE_TOL, (k, relerr(got[k], ref[k]))
     bt.close()
 
 
@@ -133,7 +142,7 @@ def test_qp_ls_packed_refined_matches_oracle(wx200, m, n, p, lanes, B):
     x, st, it = bt.qp_solve_ls(A, b, C, lb, ub, cl, cu)
     assert bt.stat("last_qp_path") == lanes
     assert (st == sr).all() and (it[ok] == ir[ok]).all()
-    assert np.abs(x - xr)[ok].max() < 1e-8, np.abs(x - xr)[ok].max()
+    assert np.abs(x - xr)[ok].max() < QP_LS_TOL, np.abs(x - xr)[ok].max()
     bt.set_option("refine", 0)
     x0, st0, _ = bt.qp_solve_ls(A, b, C, lb, ub, cl, cu)
     assert (st0 == sr).all() and (2 * p > n or np.abs(x0 - xr)[ok].max() > 1e-6)      # (a vertex solution leaves the objective nothing to decide)
@@ -205,7 +214,7 @@ def test_posture_target_parity(wx200, px100, mode, literal):
     u, qa = bt.posture_target(q, mid)
     assert bt.stat("last_posture_par") == 2       # every sweep on a lane of its own, three instances per wavefront (wbc_posture_par3_kernel: <= 21 sweeps)
     # f = sqrt(det(J J')) is O(1..10) and is differenced over 2e-4: rounding in f (1e-16 relative) shows as ~1e-11 in u
-    assert np.abs(u - ur).max() < 1e-9
+    assert np.abs(u - ur).max() < POSTURE_TOL
     assert (qa == qar).all()                      # same IEEE operations on q: bit-equal
     bt.set_option("posture_par", 3)               # one instance per wavefront, every finite-difference POINT on a lane of its own (wbc_posture_par_kernel):
     u3, qa3 = bt.posture_target(q[:B - 3], mid[:B - 3])     # the same arithmetic per evaluation — bit for bit (and a batch that is not a multiple of three)
@@ -258,7 +267,7 @@ def test_tick_parity_posture_modes(wx200, cfg_name, B):
     assert np.abs(got["q_next"] - ref["q_next"])[ok].max() < 1e-7
     a, ar = bt.assemble(d, DT), oracle.assemble([wx200], [cfg], d, DT, B)
     for k in ("A", "b", "H", "g", "C", "Clb", "Cub", "lb", "ub"):
-        assert relerr(a[k], ar[k]) < 1e-9, (k, relerr(a[k], ar[k]))
+        assert relerr(a[k], ar[k]) < ASSEMBLE_POSTURE_TOL, (k, relerr(a[k], ar[k]))
     if cfg.posture_literal:
         # the leak is visible: integrating from q instead of the perturbed state would be off by the 2e-4 perturbation
         plain = bt.integrate(d["q"], got["qdot"], DT)
@@ -804,7 +813,7 @@ def test_integrate_parity(wx200):
     ref = oracle.integrate([wx200], q, v, DT)
     bt = WbcBatch(wx200, B)
     got = bt.integrate(q, v, DT)
-    assert np.abs(got - ref).max() < 1e-13
+    assert np.abs(got - ref).max() < INTEGRATE_TOL
     big = rng.normal(size=(B, 26)) * 300  # large rotations per step: exercises every quaternion branch
     assert np.abs(bt.integrate(q, big, DT) - oracle.integrate([wx200], q, big, DT)).max() < 1e-12
     bt.close()
@@ -834,7 +843,7 @@ def test_update_state_parity(wx200, px100, B):
             ref = oracle.update_state(models, q_cur, q_next, targets, im, mid)
             got = bt.update_state(q_cur, q_next, targets, im, mid)
             assert bt.stat("last_update_packed") == packed
-            assert np.abs(got - ref).max() < 1e-13
+            assert np.abs(got - ref).max() < UPDATE_TOL
             assert (got[:, 3:] == ref[:, 3:]).all()
     bt.close()
 
@@ -872,10 +881,10 @@ def test_rollout_parity(wx200, cfg_name, K, with_imu):
         assert all((d[k] == before[k]).all() for k in d)            # in0 is only read
         assert (got["status"] == ref["status"]).all(), warm
         # one tick agrees to ~1e-6 in qdot (cond(H) ~ 3e9); K ticks of dt = 2 ms integrate that into ~1e-8 of state
-        assert np.abs(got["q"] - ref["q"])[ok].max() < 1e-6, warm
+        assert np.abs(got["q"] - ref["q"])[ok].max() < ROLLOUT_Q_TOL, warm
         assert np.abs(got["qdot"] - ref["qdot"])[ok].max() < 10 * QDOT_TOL, warm
         assert np.abs(got["ee_target"] - ref["ee_target"]).max() < 1e-15
-        assert np.abs(got["grip_trace"] - ref["grip_trace"])[:, ok].max() < 1e-6, warm
+        assert np.abs(got["grip_trace"] - ref["grip_trace"])[:, ok].max() < ROLLOUT_Q_TOL, warm
         if imu is not None:
             assert (got["q"][:, 3:7] == imu).all()
     assert (res[0]["iters"][ok] - ref["iters"][ok]).__abs__().max() <= 2 * K       # cold: the oracle's working-set changes
@@ -1580,7 +1589,7 @@ def test_batched_warm_up_matches_the_oracle(wx200, px100):
     ref = oracle.warmup(models, q0, DT, 50, foot_radius=fr, model_id=mid, nthreads=8)
     short = bt.warm_up(q0, mid, DT, 50, foot_radius=fr)
     assert (short["status"] == ref["status"]).all()
-    assert np.abs(short["q"] - ref["q"]).max() < 1e-6
+    assert np.abs(short["q"] - ref["q"]).max() < ROLLOUT_Q_TOL
     # working-set changes: equal for wx200; the oracle also counts px100's padded 26th DoF (a locked bound) once per tick
     assert np.abs(short["iters"] - ref["iters"])[mid == 0].max() <= 4
     assert np.abs(short["iters"] + 100 - ref["iters"])[mid == 1].max() <= 4
