@@ -379,12 +379,58 @@ typedef struct WbcTickGrad {         /* all optional; an output left NULL is not
  * packed whole-tree schedule (as wbc_state_slack: WBC_E_UNSUPPORTED otherwise). WBC_E_ARG, naming the field: qdot or sens_x NULL; an output
  * requested whose inputs the configuration does not read (d_ee_target without an EE task, d_trunk_target without the trunk task,
  * d_com_target without the CoM task, d_posture_u outside MANI / HYBRID / CUSTOM).
- * Not offered: gradients with respect to q (they need kinematic Hessians), ee_ref_rot / ee_prev_rot, trunk_ref_euler / trunk_prev_rot,
- * trunk_box_center (it enters the constraints, not the task rows), and gradients through roll-outs.
+ * Gradients with respect to q and trunk_box_center come from wbc_tick_vjp_state below (it contracts what kinematic Hessians would hold with
+ * x and u and never forms them). Not offered: ee_ref_rot / ee_prev_rot, trunk_ref_euler / trunk_prev_rot, and gradients through roll-outs.
  * Statistic "last_grad_variant": the row of csrc/wbc_k_grad.hip's table the last call launched (key of ROT), -1 before the first. */
 int wbc_tick_vjp(WbcBatch* b, int B, const WbcTickIn* in, const WbcTaskParams* tp, double dt, const double* qdot, const double* sens_x,
                  const int32_t* status, const int32_t* cert_status, int mem, const WbcTickGrad* out, void* stream);
 int wbc_tick_grad_sizes(int32_t* sizeof_grad); /* ctypes layout self-check */
+
+/* ------------------------------------------------------------------ the tick as a layer, state side: dL/dq and dL/d trunk_box_center
+ * For a solved tick x = qdot and its certificate for the caller's v = dL/dqdot — u = sens_x, w = sens_bounds / sens_rows, y = y_rows
+ * (wbc_qp_certificate on the tick's own A, b, C, bounds) — the gradient of L with respect to the STATE the tick was solved at. With r = b - A x
+ * and s = A u:
+ *   dL/d delta_k = sum_rows (r_i u - s_i x) . dA_i/d delta_k + s_i db_i/d delta_k + sum_j (y_j u - w_j x) . dC_j/d delta_k + sum_active w_i de_i/d delta_k
+ * Tangent convention: d_q[b][k] = dL/d delta_k at delta = 0 for q(delta) = pin.integrate(q, delta) = wbc_integrate(q, delta, dt = 1); the base
+ * DoF are in the base-local frame; columns >= the model's nv are 0. (wbc_workload.tangent_to_raw turns it into a gradient in raw coordinates.)
+ * Every Jacobian row appears only contracted with x or u, and d(J_W z)/d delta_k = S_k x_m T_k(z) with S_k the WORLD column of DoF k and T_k(z)
+ * the frame body's spatial velocity under z minus that of k's own body: the kernel (csrc/wbc_k_gradq.hip, four instances per wavefront)
+ * recomputes the kinematics from q, keeps one table of body velocities under x and u, and forms no second-order tensor.
+ * Differentiated: every task and constraint row, the position, quaternion and CoM feedback in b, the PREV posture target, the CoM and trunk
+ * boxes (the Euler angles are the three atan2 forms stated under wbc_state_slack), the velocity-damper bounds branch by branch (0 on a
+ * clipped or constant branch; at a kink the branch the tick's own comparisons select).
+ * HELD CONSTANT: posture_u in MANI / HYBRID / CUSTOM (its own dependence on q is not differentiated; wbc_tick_vjp gives d_posture_u), and
+ * the orientation references (ee_ref_rot, ee_prev_rot, trunk_ref_euler, trunk_prev_rot).
+ * Which side a w belongs to: wbc_qp_certificate's rule. With working_set the marked side; without, the lower side if
+ * |value - lo| < 1e-7 max(1, |lo|), else the upper side; half and half where lo == hi. The kernel recomputes the bounds from q.
+ * d_trunk_box_center: z row scale (1 -+ z_frac) / dt, angle rows scale / dt, each times the active side's w. */
+typedef struct WbcTickSens {          /* a solved tick and its certificate for the caller's v = dL/dqdot */
+  const double* qdot;                 /* [B][26] required */
+  const double* sens_x;               /* [B][26] required: u */
+  const double* sens_bounds;          /* [B][26] w of the velocity bounds; NULL => zeros (required with use_bounds) */
+  const double* sens_rows;            /* [B][p]  w of the rows;  required when p > 0 */
+  const double* y_rows;               /* [B][p]  duals of the rows; required when p > 0 */
+  const int32_t* status;              /* [B] NULL => all solved */
+  const int32_t* cert_status;         /* [B] NULL => all certified */
+  const uint64_t* working_set;        /* [B][2] the tick's working_set out; NULL => sides read off qdot */
+} WbcTickSens;
+typedef struct WbcTickStateGrad {     /* all optional */
+  double* d_q;                        /* [B][26] tangent coordinates, see above */
+  double* d_trunk_box_center;         /* [B][4]  needs the trunk constraint */
+  int32_t* grad_status;               /* [B] WBC_GRAD_* (the codes of wbc_tick_vjp) */
+} WbcTickStateGrad;
+/* in: every field the tick reads; tp: per-instance rows or NULL. Host or device buffers. With device pointers the call enqueues exactly one
+ * kernel: no allocation, no memset, so it can be captured. An instance with status != 0, cert_status != WBC_CERT_OK or a non-finite value in
+ * q, qdot, the four sensitivity arrays, the weights and gains, trunk_box_center or a target the configuration reads gets all-zero rows and its
+ * grad_status; nothing non-finite reaches another instance's rows; rows >= B are never written. WBC_E_UNSUPPORTED when a model does not fit
+ * the packed whole-tree schedule (as wbc_state_slack). WBC_E_ARG, naming the field: q_con not NULL (the constraints would see another
+ * configuration); posture mode MANI / HYBRID with posture_u NULL; qdot or sens_x NULL; sens_bounds NULL with use_bounds; sens_rows or y_rows
+ * NULL with p > 0; d_trunk_box_center without the trunk constraint; trunk_box_center NULL with the trunk constraint.
+ * Statistic "last_gradq_variant": the row of csrc/wbc_k_gradq.hip's table the last call launched (key of ROT), -1 before the first;
+ * wbc_variant_count("gradq") == 2. */
+int wbc_tick_vjp_state(WbcBatch* b, int B, const WbcTickIn* in, const WbcTaskParams* tp, double dt, const WbcTickSens* sens, int mem,
+                       const WbcTickStateGrad* out, void* stream);
+int wbc_tick_state_grad_sizes(int32_t* sizeof_sens, int32_t* sizeof_grad); /* ctypes layout self-check */
 
 /* replaces qpJointb's "MANI" / "HYBRID" branches (Robot_Wrapper4.py:1220-1260) under the configured task_joint,
  * arm_base_id and posture_literal: u [B][26] = the posture target before scaling (PREV / zeros for the other modes),

@@ -11,6 +11,7 @@
 #include "wbc_slack.h"
 #include "wbc_cert.h"
 #include "wbc_grad.h"
+#include "wbc_gradq.h"
 
 // (the layouts of the handle's roll-out workspaces d_roll, d_traj and d_slack: RollWs, TrajWs and SlackWs below)
 
@@ -84,6 +85,7 @@ struct WbcBatch {
   int last_orth;         // the last general-kernel tick ran the variant with the orthonormal contact presolve
   int last_qp_path;      // problems per wavefront of the last wbc_qp_solve / wbc_qp_solve_ls: 1 (wbc_qp_kernel), 2 or 4 (wbc_qp_packed_kernel)
   long long last_grad_variant;   // ... and of the last wbc_tick_vjp launch
+  long long last_gradq_variant;  // ... and of the last wbc_tick_vjp_state launch
   long long last_tick_variant, last_qp_variant;   // variant_key(...) of the row the last tick / assemble / fk launch and the last stand-alone QP launch resolved (-1: none yet)
   int sim3p_fixd;        // option [1]: the packed sim3 kernel's FIXD form where the handle qualifies (fixd_dims)
   bool fixd_dims[WBC_MAX_MODELS];   // wbc_batch_configure: the model's plan has exactly the SIM3P_FIXD_* dimensions
@@ -291,7 +293,7 @@ extern "C" int wbc_batch_create(const WbcModel* const* models, int n_models, int
   if (!b) return fail(WBC_E_ARG, "out of memory");
   memset(b, 0, sizeof *b);
   b->device_id = device_id; b->n_models = n_models; b->max_batch = max_batch; b->presolve = 1; b->presolve_orth = 1; b->packed_update = 1; b->sim3_kernel = 1; b->sing_tol = 1e-7; b->wave_order = 1; b->sim3p_fixd = 1;
-  b->last_tick_variant = b->last_qp_variant = b->last_grad_variant = -1;
+  b->last_tick_variant = b->last_qp_variant = b->last_grad_variant = b->last_gradq_variant = -1;
   b->jtj_mfma = -1; b->refine = 1; b->packed_min_batch = WBC_SIM3P_MIN_BATCH; b->warm_start = 0; b->packed_kernel = 1; b->packed_orth = 1; b->packed_box = 1; b->posture_par = 1;
   std::vector<DevModel> dm(n_models);
   for (int i = 0; i < n_models; ++i) {
@@ -797,6 +799,7 @@ extern "C" int wbc_batch_get_stat(WbcBatch* b, const char* name, void* stream, i
   if (!strcmp(name, "last_tick_fixd")) { *out = b->last_path == TICK_SIM3P ? b->last_tick_fixd : 0; return WBC_OK; }
   if (!strcmp(name, "last_qp_variant")) { *out = b->last_qp_variant; return WBC_OK; }
   if (!strcmp(name, "last_grad_variant")) { *out = b->last_grad_variant; return WBC_OK; }
+  if (!strcmp(name, "last_gradq_variant")) { *out = b->last_gradq_variant; return WBC_OK; }
   if (!strcmp(name, "last_update_packed")) { *out = b->last_update_packed; return WBC_OK; }
   if (!strcmp(name, "last_posture_par")) { *out = b->last_posture_par; return WBC_OK; }
   if (!strcmp(name, "last_orth")) { *out = (b->last_path == TICK_GENERAL || b->last_path == TICK_ORTHP) ? b->last_orth : 0; return WBC_OK; }
@@ -1794,6 +1797,63 @@ extern "C" int wbc_tick_grad_sizes(int32_t* sizeof_grad) {
   return WBC_OK;
 }
 
+// dL/dq (tangent coordinates) and dL/d trunk_box_center of solved ticks (include/wbc.h): argument checks, staging of host arrays, ONE launch of
+// wbc_gradq_kernel (csrc/wbc_k_gradq.hip). No posture kernel: MANI / HYBRID need the caller's posture_u, which is held constant. No memset;
+// the kernel writes every row of every output it is given.
+static_assert(sizeof(WbcTickSens) == 8 * sizeof(void*) && sizeof(WbcTickStateGrad) == 3 * sizeof(void*), "wbc_capi.WbcTickSens / WbcTickStateGrad");
+extern "C" int wbc_tick_vjp_state(WbcBatch* b, int B, const WbcTickIn* in, const WbcTaskParams* tp, double dt, const WbcTickSens* sens, int mem,
+                                  const WbcTickStateGrad* out, void* stream) {
+  const char* who = "wbc_tick_vjp_state";
+  int rc = check_batch(b, B, who, true);
+  if (rc) return rc;
+  if (!out) return fail(WBC_E_ARG, "%s: out is required", who);
+  if (!sens) return fail(WBC_E_ARG, "%s: sens is required", who);
+  if (!(dt > 0)) return fail(WBC_E_ARG, "%s: dt <= 0", who);
+  if (!sens->qdot) return fail(WBC_E_ARG, "%s: qdot is required", who);
+  if (!sens->sens_x) return fail(WBC_E_ARG, "%s: sens_x is required", who);
+  if ((rc = validate_tick_in(b, in, who))) return rc;
+  if (in->q_con) return fail(WBC_E_ARG, "%s: q_con is not supported (the constraints would see another configuration than the task rows)", who);
+  const WbcConfig& c = b->cfg_host[0];
+  for (int i = 0; i < b->n_models; ++i) {
+    const int tj = b->cfg_host[i].task_joint;
+    if ((tj == WBC_JOINT_MANI || tj == WBC_JOINT_HYBRID) && !in->posture_u)
+      return fail(WBC_E_ARG, "%s: posture mode MANI / HYBRID of model %d needs posture_u (it is held constant)", who, i);
+  }
+  int p = (c.con_com ? 2 : 0) + (c.con_trunk ? 4 : 0);
+  for (int i = 0; i < WBC_NEE; ++i) p += c.con_ee[i] ? 3 : 0;
+  if (c.use_bounds && !sens->sens_bounds) return fail(WBC_E_ARG, "%s: sens_bounds is required with use_bounds", who);
+  if (p > 0 && !sens->sens_rows) return fail(WBC_E_ARG, "%s: sens_rows is required with %d constraint rows", who, p);
+  if (p > 0 && !sens->y_rows) return fail(WBC_E_ARG, "%s: y_rows is required with %d constraint rows", who, p);
+  if (out->d_trunk_box_center && !c.con_trunk) return fail(WBC_E_ARG, "%s: d_trunk_box_center requested, but the trunk constraint is off", who);
+  for (int i = 0; i < b->n_models; ++i) {
+    if (b->plan_host[i].slack_ok) continue;
+    const DevModel& M = b->models[i]->dev;
+    return fail(WBC_E_UNSUPPORTED, "%s: model %d does not fit the packed whole-tree schedule (%d joints, at most 22; tree depth %d, at most 7; at most 16 joints at one depth)",
+                who, i, M.njoints, M.maxdepth);
+  }
+  HIP_TRY(hipSetDevice(b->device_id));
+  GradQArgs a;
+  memset(&a, 0, sizeof a);
+  a.models = b->d_models; a.cfgs = b->d_cfgs; a.plans = b->d_plans; a.B = B; a.n_models = b->n_models; a.rot = b->rot; a.dt = dt;
+  a.in = *in; a.tp = tp; a.sens = *sens; a.out = *out;
+  if (p == 0) a.sens.sens_rows = a.sens.y_rows = nullptr;
+  Stager st{b, mem, (hipStream_t)stream, {}};
+  stage_tick_in(st, a.in, B, b);
+  const size_t n = (size_t)B;
+  st.in(&a.tp, n); st.in(&a.sens.qdot, n * WBC_V_STRIDE); st.in(&a.sens.sens_x, n * WBC_V_STRIDE); st.in(&a.sens.sens_bounds, n * WBC_V_STRIDE);
+  st.in(&a.sens.sens_rows, n * p); st.in(&a.sens.y_rows, n * p); st.in(&a.sens.status, n); st.in(&a.sens.cert_status, n);
+  st.in(&a.sens.working_set, n * 2);
+  st.out(&a.out.d_q, n * WBC_V_STRIDE); st.out(&a.out.d_trunk_box_center, n * 4); st.out(&a.out.grad_status, n);
+  if ((rc = st.stage())) return rc;
+  if ((rc = launch_rc(launch_gradq(a, stream, &b->last_gradq_variant), "tick state gradient"))) return rc;
+  return st.finish();
+}
+extern "C" int wbc_tick_state_grad_sizes(int32_t* sizeof_sens, int32_t* sizeof_grad) {
+  if (sizeof_sens) *sizeof_sens = (int32_t)sizeof(WbcTickSens);
+  if (sizeof_grad) *sizeof_grad = (int32_t)sizeof(WbcTickStateGrad);
+  return WBC_OK;
+}
+
 extern "C" int wbc_integrate(WbcBatch* b, int B, const double* q, const double* v, const int32_t* model_id, double dt, int mem,
                              double* q_next, void* stream) {
   int rc = check_batch(b, B, "wbc_integrate", false);
@@ -1840,6 +1900,7 @@ extern "C" int wbc_variant_count(const char* family) {
   if (!strcmp(family, "qpp")) return qpp_variant_count();
   if (!strcmp(family, "qp")) return qp_variant_count();
   if (!strcmp(family, "grad")) return grad_variant_count();
+  if (!strcmp(family, "gradq")) return gradq_variant_count();
   return fail(WBC_E_ARG, "wbc_variant_count: unknown kernel family %s", family);
 }
 extern "C" int wbc_abi_sizes(int32_t* sb, int32_t* sc) {

@@ -170,7 +170,7 @@ class WbcBatch:
     def stat(self, name, stream=None):
         """wbc_batch_get_stat: "last_path" (0 general, 1 compact sim3, 2 packed sim3, 3 packed orth — equality-only or INEQ variant —, 4 packed box), "last_orth", "last_posture_par",
         "last_update_packed", "last_qp_path" (problems per wavefront of the last stand-alone QP call: 1, 2 or 4), "last_tick_variant" /
-        "last_qp_variant" (the variant-table row of the last tick / assemble / fk and stand-alone QP launch: wbc_capi.variant_args), "last_grad_variant" (the same for the last wbc_tick_vjp launch), "last_tick_fixd" (1: the last tick ran the
+        "last_qp_variant" (the variant-table row of the last tick / assemble / fk and stand-alone QP launch: wbc_capi.variant_args), "last_grad_variant" / "last_gradq_variant" (the same for the last wbc_tick_vjp / wbc_tick_vjp_state launch), "last_tick_fixd" (1: the last tick ran the
         packed sim3 kernel's FIXD form, option "sim3p_fixd"), "deferred_last", "pivoted_last", "wave_order_slices", "sim3_lds_bytes", "tick_lds_bytes", "orthp_lds_bytes"."""
         v = C.c_int64()
         capi.check(self.lib.wbc_batch_get_stat(self._h, name.encode(), stream, C.byref(v)), self.lib)
@@ -459,6 +459,53 @@ class WbcBatch:
         inputs are. v [B,26] = dL/dqdot. Returns the tick's and the certificate's entries plus the gradients (tick_vjp's names) and grad_status."""
         c = self.tick_certificate(inputs, dt, task_params=task_params, v=v)
         g = self.tick_vjp(inputs, dt, c["qdot"], c["sens_x"], status=c["status"], cert_status=c["cert_status"], task_params=task_params, want=want)
+        return dict(c, **g)
+
+    def tick_vjp_state(self, inputs, dt, qdot, sens_x, sens_bounds=None, sens_rows=None, y_rows=None, status=None, cert_status=None,
+                       working_set=None, task_params=None, want=None, out=None):
+        """wbc_tick_vjp_state (include/wbc.h): dL/dq in tangent coordinates (d_q [B,26]: q (+) delta = pin.integrate(q, delta)) and
+        dL/d trunk_box_center [B,4] of solved ticks from x = qdot and the certificate's u = sens_x, w = sens_bounds / sens_rows, y = y_rows, one
+        kernel launch. want: names of capi.TICK_STATE_GRAD_FIELDS (None: d_q, and d_trunk_box_center with the trunk constraint); out: caller's
+        arrays by those names (and "grad_status") instead. posture_u and the orientation references are held constant; q_con is refused.
+        Returns dict(<want>..., grad_status [B] int32)."""
+        keep = []
+        B = self._batch_of(inputs.get("q"))
+        if out is None:
+            names = (("d_q",) + (("d_trunk_box_center",) if self.cfgs[0].con_trunk else ())) if want is None else tuple(want)
+            unknown = set(names) - set(capi.TICK_STATE_GRAD_FIELDS)
+            if unknown:
+                raise capi.WbcError("unknown gradients %s (known: %s)" % (sorted(unknown), ", ".join(capi.TICK_STATE_GRAD_FIELDS)))
+            out = {k: self._alloc(qdot, (B,) + capi.TICK_STATE_GRAD_FIELDS[k]) for k in names}
+            out["grad_status"] = self._alloc(qdot, (B,), np.int32)
+        mem = _mem_of(list(inputs.values()) + list(out.values()) + [task_params, qdot, sens_x, sens_bounds, sens_rows, y_rows, status, cert_status,
+                                                                    working_set])
+        o = capi.WbcTickStateGrad()
+        for k, a in out.items():
+            if k == "grad_status":
+                o.grad_status = self._p(a, np.int32, keep, B, 1, k)
+            elif k in capi.TICK_STATE_GRAD_FIELDS:
+                setattr(o, k, self._p(a, np.float64, keep, B, int(np.prod(capi.TICK_STATE_GRAD_FIELDS[k])), k))
+            else:
+                raise capi.WbcError("unknown output %r" % k)
+        tin = self._tick_in(inputs, keep, B)
+        tp = _task_params(task_params, B, keep, self.device_id)
+        f, P, p = np.float64, self._p, self.constraint_rows
+        sn = capi.WbcTickSens()
+        sn.qdot, sn.sens_x, sn.sens_bounds = P(qdot, f, keep, B, NV, "qdot"), P(sens_x, f, keep, B, NV, "sens_x"), P(sens_bounds, f, keep, B, NV, "sens_bounds")
+        if p > 0:
+            sn.sens_rows, sn.y_rows = P(sens_rows, f, keep, B, p, "sens_rows"), P(y_rows, f, keep, B, p, "y_rows")
+        sn.status, sn.cert_status = P(status, np.int32, keep, B, 1, "status"), P(cert_status, np.int32, keep, B, 1, "cert_status")
+        sn.working_set = P(working_set, np.int64, keep, B, 2, "working_set")
+        capi.check(self.lib.wbc_tick_vjp_state(self._h, B, C.byref(tin), tp, float(dt), C.byref(sn), mem, C.byref(o), self._stream(mem)), self.lib)
+        return out
+
+    def tick_grad_q(self, inputs, dt, v, task_params=None, want=None):
+        """The tick as a layer over its state: tick_certificate(..., v=v) and then wbc_tick_vjp_state on its qdot, sensitivities, duals and working
+        set, on the device throughout when the inputs are. v [B,26] = dL/dqdot. Returns the tick's and the certificate's entries plus d_q [B,26]
+        (tangent coordinates; wbc_workload.tangent_to_raw for raw ones), d_trunk_box_center [B,4] with the trunk constraint, and grad_status."""
+        c = self.tick_certificate(inputs, dt, task_params=task_params, v=v)
+        g = self.tick_vjp_state(inputs, dt, c["qdot"], c["sens_x"], sens_bounds=c["sens_bounds"], sens_rows=c["sens_rows"], y_rows=c["y_rows"],
+                                status=c["status"], cert_status=c["cert_status"], working_set=c["working_set"], task_params=task_params, want=want)
         return dict(c, **g)
 
     def posture_target(self, q, model_id=None, want_q_after=True):

@@ -156,6 +156,19 @@ class WbcTickGrad(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in tuple(TICK_GRAD_FIELDS) + ("grad_status",)]
 
 
+# wbc_tick_vjp_state: dL/dq (tangent coordinates) and dL/d trunk_box_center of a solved tick (include/wbc.h)
+TICK_SENS_FIELDS = ("qdot", "sens_x", "sens_bounds", "sens_rows", "y_rows", "status", "cert_status", "working_set")
+TICK_STATE_GRAD_FIELDS = dict(d_q=(V_STRIDE,), d_trunk_box_center=(4,))     # output name -> per-instance shape
+
+
+class WbcTickSens(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in TICK_SENS_FIELDS]
+
+
+class WbcTickStateGrad(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in tuple(TICK_STATE_GRAD_FIELDS) + ("grad_status",)]
+
+
 class WbcFkOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("oMi", "oMf", "J", "com", "Jcom")]
 
@@ -191,6 +204,8 @@ SIGNATURES = {
     "wbc_qp_certificate_sizes": (_i, [c_int32_p, c_int32_p]),
     "wbc_tick_vjp": (_i, [_vp, _i, C.POINTER(WbcTickIn), _vp, _d, _vp, _vp, _vp, _vp, _i, C.POINTER(WbcTickGrad), _vp]),
     "wbc_tick_grad_sizes": (_i, [c_int32_p]),
+    "wbc_tick_vjp_state": (_i, [_vp, _i, C.POINTER(WbcTickIn), _vp, _d, C.POINTER(WbcTickSens), _i, C.POINTER(WbcTickStateGrad), _vp]),
+    "wbc_tick_state_grad_sizes": (_i, [c_int32_p, c_int32_p]),
     "wbc_posture_target": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "wbc_tick": (_i, [_vp, _i, C.POINTER(WbcTickIn), _d, _i, C.POINTER(WbcTickOut), _vp]),
     "wbc_update_state": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
@@ -258,6 +273,10 @@ def load_library(path=None):
     lib.wbc_tick_grad_sizes(C.byref(sb))
     if sb.value != C.sizeof(WbcTickGrad):
         raise WbcError("ABI mismatch (WbcTickGrad): library %d vs ctypes %d" % (sb.value, C.sizeof(WbcTickGrad)))
+    lib.wbc_tick_state_grad_sizes(C.byref(sb), C.byref(sc))
+    if sb.value != C.sizeof(WbcTickSens) or sc.value != C.sizeof(WbcTickStateGrad):
+        raise WbcError("ABI mismatch (WbcTickSens / WbcTickStateGrad): library (%d, %d) vs ctypes (%d, %d)" % (
+            sb.value, sc.value, C.sizeof(WbcTickSens), C.sizeof(WbcTickStateGrad)))
     if path is None:
         _lib = lib
     return lib

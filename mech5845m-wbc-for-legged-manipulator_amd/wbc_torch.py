@@ -13,6 +13,10 @@ C, Clb, Cub (no rows) and lb, ub (no box) may be None. There is no CPU fallback.
 ``qdot, status = wbc_tick(task_params, ee_target, ..., inputs, dt, batch)`` is the same one level up: the whole control tick as a layer over
 what its caller owns — the 85 per-instance weights and gains and the task targets. Forward is ``wbc_tick_tp`` with the working set out;
 backward is one certificate of the tick's own problem with v = grad_output followed by ``wbc_tick_vjp`` (include/wbc.h), all on the device.
+
+``qdot, status = wbc_tick_state(q, task_params, ee_target, ..., inputs, dt, batch)`` adds the state: the same forward with q a tensor argument;
+backward is one certificate, ``wbc_tick_vjp`` when a gradient other than q's is wanted, and ``wbc_tick_vjp_state``, whose tangent-coordinate
+d_q goes to raw coordinates through ``wbc_workload.tangent_to_raw``.
 """
 import torch
 
@@ -127,3 +131,60 @@ def wbc_tick(task_params, ee_target, prev_ee_target, trunk_target, prev_trunk_ta
     whose QP was not solved or whose certificate is not WBC_CERT_OK get zero gradients. No gradient flows to q or anything else in `inputs`."""
     return _WbcTick.apply(task_params, ee_target, prev_ee_target, trunk_target, prev_trunk_target, com_target, com_target_vel, posture_u, inputs, dt,
                           batch)
+
+
+class _WbcTickState(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, task_params, ee_target, prev_ee_target, trunk_target, prev_trunk_target, com_target, com_target_vel, posture_u, inputs, dt,
+                batch):
+        args = [_c(t) for t in (task_params, ee_target, prev_ee_target, trunk_target, prev_trunk_target, com_target, com_target_vel, posture_u)]
+        d = dict(inputs)
+        d["q"] = _c(q)
+        for name, a in zip(_TICK_ARGS[1:], args[1:]):
+            if a is not None:
+                d[name] = a
+        t = batch.tick(d, dt, want_working_set=True, task_params=args[0])
+        ctx.batch, ctx.dt = batch, dt
+        given = {name for name, a in zip(_TICK_ARGS, args) if a is not None} | {"q"}
+        ctx.rest = {k: v for k, v in d.items() if k not in given}          # (what came in `inputs`: not ours to version-check)
+        ctx.present = [a is not None for a in args]
+        ctx.save_for_backward(t["qdot"], t["status"], t["working_set"], d["q"], *[a for a in args if a is not None])
+        ctx.mark_non_differentiable(t["status"])
+        return t["qdot"], t["status"]
+
+    @staticmethod
+    def backward(ctx, gq, _gst):
+        import wbc_workload
+        qdot, st, ws, q, *given = ctx.saved_tensors
+        n_out = 1 + len(_TICK_ARGS) + 3
+        if gq is None:              # qdot took no part in the loss
+            return (None,) * n_out
+        it = iter(given)
+        args = [next(it) if have else None for have in ctx.present]
+        need = ctx.needs_input_grad
+        want = tuple("d_" + name for k, name in enumerate(_TICK_ARGS) if need[1 + k] and args[k] is not None)
+        if not want and not need[0]:
+            return (None,) * n_out
+        bt = ctx.batch
+        d = dict(ctx.rest, q=q)
+        for name, a in zip(_TICK_ARGS[1:], args[1:]):
+            if a is not None:
+                d[name] = a
+        c = bt.tick_certificate(d, ctx.dt, task_params=args[0], v=gq.contiguous(), tick=dict(qdot=qdot, status=st, working_set=ws))
+        g = bt.tick_vjp(d, ctx.dt, qdot, c["sens_x"], status=st, cert_status=c["cert_status"], task_params=args[0], want=want) if want else {}
+        gq_raw = None
+        if need[0]:
+            s = bt.tick_vjp_state(d, ctx.dt, qdot, c["sens_x"], sens_bounds=c["sens_bounds"], sens_rows=c["sens_rows"], y_rows=c["y_rows"], status=st,
+                                  cert_status=c["cert_status"], working_set=ws, task_params=args[0], want=("d_q",))
+            gq_raw = wbc_workload.tangent_to_raw(q, s["d_q"])
+        return (gq_raw,) + tuple(g.get("d_" + name) if ("d_" + name) in want else None for name in _TICK_ARGS) + (None, None, None)
+
+
+def wbc_tick_state(q, task_params, ee_target, prev_ee_target, trunk_target, prev_trunk_target, com_target, com_target_vel, posture_u, inputs, dt,
+                   batch):
+    """wbc_tick with the state as a differentiable argument: q [B,27] (contiguous float64 on the handle's device) replaces inputs["q"], and its
+    gradient is that of the tick composed with the normalisation of q's quaternion, in raw coordinates (wbc_workload.tangent_to_raw of
+    wbc_tick_vjp_state's d_q). The other eight arguments and their gradients are wbc_tick's. posture_u (MANI / HYBRID / CUSTOM: it must be
+    given) and the orientation references are held constant; inputs must not hold q_con. No gradient flows to anything else in `inputs`."""
+    return _WbcTickState.apply(q, task_params, ee_target, prev_ee_target, trunk_target, prev_trunk_target, com_target, com_target_vel, posture_u,
+                               inputs, dt, batch)

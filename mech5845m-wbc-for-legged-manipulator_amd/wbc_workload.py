@@ -565,3 +565,322 @@ def tick_gradients(model, cfg, inputs, x, u, dt, fk, task_params=None):
     cat = (lambda a, w: np.concatenate(a, axis=1) if a else np.zeros((B, 0) + w))
     out.update(d_task_params=dtp, A=cat(A_, (NVs,)), b=cat(b_, ()), dA=cat(dA_, (NVs,)), db=cat(db_, ()))
     return out
+
+
+# ---- the tick as a layer, state side (wbc_tick_vjp_state, include/wbc.h): dL/dq in tangent coordinates, restated in numpy
+def _dof_tree(model):
+    """(joint [26] of every velocity column (-1: none), after [26, 26] bool): after[k, d] — column d's WORLD Jacobian column moves with the
+    tangent coordinate k: k's joint is a strict ancestor of d's joint, or k and d are two free-flyer columns (M <- M exp(delta))."""
+    NVs = capi.V_STRIDE
+    joints = model.data["joints"]
+    jof = np.full(NVs, -1, dtype=np.int64)
+    ff = np.zeros(NVs, dtype=bool)
+    for j in range(1, model.njoints):
+        jd = joints[j]
+        n = 6 if jd["type_id"] == capi.JT["FF"] else 1
+        jof[jd["idx_v"]:jd["idx_v"] + n] = j
+        ff[jd["idx_v"]:jd["idx_v"] + n] = n == 6
+    after = np.zeros((NVs, NVs), dtype=bool)
+    for d in range(NVs):
+        if jof[d] < 0:
+            continue
+        a = joints[int(jof[d])]["parent"]
+        while a > 0:
+            after[jof == a, d] = True
+            a = joints[a]["parent"]
+        if ff[d]:
+            after[ff, d] = True
+    return jof, after
+
+
+def _point_rows_dq(J, sup, after, p, world, z):
+    """d(J_r z)/d delta [B, 6, 26] of the six rows of a frame with support `sup` [26] at the point p [B, 3] (LOCAL_WORLD_ALIGNED) or at the
+    world origin (world=True), from the WORLD joint Jacobians J [B, 6, 26]:  S_k x_m T_k(z),  T_k(z) = sum of S_d z_d over the support columns
+    d after k; LOCAL_WORLD_ALIGNED adds (d ang) x p + ang x (l_k + a_k x p) to the linear rows."""
+    Jz = np.where(sup[None, None, :], J, 0.0) * z[:, None, :]
+    T = np.einsum("bcd,kd->bkc", Jz, after.astype(np.float64))           # [B, k, 6]
+    S = J.transpose(0, 2, 1)                                             # [B, k, 6]
+    lk, ak = S[:, :, 0:3], S[:, :, 3:6]
+    D = np.concatenate([np.cross(ak, T[:, :, 0:3]) + np.cross(lk, T[:, :, 3:6]), np.cross(ak, T[:, :, 3:6])], axis=2)
+    if not world:
+        ang = Jz[:, 3:6, :].sum(axis=2)[:, None, :]
+        dp = lk + np.cross(ak, p[:, None, :])
+        D[:, :, 0:3] += np.cross(D[:, :, 3:6], p[:, None, :]) + np.cross(ang, dp)
+    return np.where(sup[None, :, None], D, 0.0).transpose(0, 2, 1)
+
+
+def frame_rows_dq(model, J, oMf, role, world, z):
+    """d(J_r z)/d delta_k [B, 6, 26] (row, k) of frame_rows(model, J, oMf, role, world) contracted with a fixed z [B, 26]; delta: the tangent
+    coordinates of q (+) delta = pin.integrate(q, delta), base columns in the base-local frame. No 26 x 26 x 6 tensor is formed."""
+    sup = _support_columns(model, model.blob.frame_joint[role])
+    return _point_rows_dq(J, sup, _dof_tree(model)[1], oMf[:, role, 9:12], world, np.asarray(z, dtype=np.float64))
+
+
+def com_rows_dq(model, J, oMi, z):
+    """d(Jcom z)/d delta_k [B, 3, 26]: the mass-weighted mean over the bodies of the LOCAL_WORLD_ALIGNED linear rows at the bodies' centres of
+    mass. oMi [B, >= njoints, 12]: the joint placements (rotation row-major, then the translation)."""
+    z = np.asarray(z, dtype=np.float64)
+    after = _dof_tree(model)[1]
+    out, mtot = np.zeros((J.shape[0], 3, capi.V_STRIDE)), 0.0
+    for j in range(1, model.njoints):
+        m = float(model.blob.mass[j])
+        if m == 0.0:
+            continue
+        c = np.einsum("bij,j->bi", oMi[:, j, 0:9].reshape(-1, 3, 3), np.array(model.blob.com[j][:])) + oMi[:, j, 9:12]
+        out += m * _point_rows_dq(J, _support_columns(model, j), after, c, False, z)[:, 0:3]
+        mtot += m
+    return out / mtot
+
+
+def _quat_right(q4, e):
+    """q (x) (e, 0), Hamilton, (x, y, z, w): [B, 4]"""
+    v, w = q4[:, 0:3], q4[:, 3:4]
+    e = np.broadcast_to(e, v.shape)
+    return np.concatenate([w * e + np.cross(v, e), -(v * e).sum(axis=1, keepdims=True)], axis=1)
+
+
+def _quat_to_R(q4):
+    x, y, z, w = q4[:, 0], q4[:, 1], q4[:, 2], q4[:, 3]
+    return np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w), 2 * (x * y + z * w), 1 - 2 * (x * x + z * z),
+                     2 * (y * z - x * w), 2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)], axis=1).reshape(-1, 3, 3)
+
+
+def raw_tangent_map(model, q):
+    """G = d q_raw / d delta [B, 27, 26] at delta = 0 of q (+) delta: xyz rows R (the base rotation), quaternion rows 1/2 q (x) (e_k, 0), joint
+    rows the identity (q index of the joint's own angle)."""
+    q = np.asarray(q, dtype=np.float64).reshape(-1, capi.Q_STRIDE)
+    G = np.zeros((q.shape[0], capi.Q_STRIDE, capi.V_STRIDE))
+    G[:, 0:3, 0:3] = _quat_to_R(q[:, 3:7])
+    for k in range(3):
+        G[:, 3:7, 3 + k] = 0.5 * _quat_right(q[:, 3:7], np.eye(3)[k])
+    for jd in model.data["joints"][2:model.njoints]:
+        G[:, jd["idx_q"], jd["idx_v"]] = 1.0
+    return G
+
+
+def tangent_to_raw(q, d):
+    """The gradient [B, 27] in raw coordinates of L(tick(q_raw with its quaternion normalised)) from d = dL/d delta [B, 26] (wbc_tick_vjp_state's
+    d_q). With the unit quaternion qn = quat / |quat| = (x, y, z, w), R = R(qn) the base rotation, d_lin = d[0:3], d_ang = d[3:6]:
+      xyz        <- R d_lin
+      quaternion <- 2 qn (x) (d_ang, 0) / |quat|  =  2 (w d_ang + (x, y, z) x d_ang ; -(x, y, z) . d_ang) / |quat|
+      joints     <- d[6:]  (raw index one higher; entries beyond a model's nq get what d holds beyond its nv: 0)
+    The quaternion rows are the pull-back of the tangent through the normalisation: delta_ang = 2 Im(conj(qn) (x) dq) / |quat| for a raw
+    perturbation dq, so the gradient has no component along the quaternion itself. numpy arrays or torch tensors; written in elementwise
+    operations in one fixed order, so that both give the same bits."""
+    if hasattr(q, "detach"):
+        import torch as xp
+        cat = lambda parts: xp.stack(parts, dim=1)      # noqa: E731
+    else:
+        xp = np
+        q, d = np.asarray(q, dtype=np.float64).reshape(-1, capi.Q_STRIDE), np.asarray(d, dtype=np.float64).reshape(-1, capi.V_STRIDE)
+        cat = lambda parts: np.stack(parts, axis=1)     # noqa: E731
+    nrm = xp.sqrt(q[:, 3] * q[:, 3] + q[:, 4] * q[:, 4] + q[:, 5] * q[:, 5] + q[:, 6] * q[:, 6])
+    x, y, z, w = q[:, 3] / nrm, q[:, 4] / nrm, q[:, 5] / nrm, q[:, 6] / nrm
+    l0, l1, l2, a0, a1, a2 = d[:, 0], d[:, 1], d[:, 2], d[:, 3], d[:, 4], d[:, 5]
+    cols = [(1 - 2 * (y * y + z * z)) * l0 + (2 * (x * y - z * w)) * l1 + (2 * (x * z + y * w)) * l2,
+            (2 * (x * y + z * w)) * l0 + (1 - 2 * (x * x + z * z)) * l1 + (2 * (y * z - x * w)) * l2,
+            (2 * (x * z - y * w)) * l0 + (2 * (y * z + x * w)) * l1 + (1 - 2 * (x * x + y * y)) * l2,
+            2 * (w * a0 + (y * a2 - z * a1)) / nrm,
+            2 * (w * a1 + (z * a0 - x * a2)) / nrm,
+            2 * (w * a2 + (x * a1 - y * a0)) / nrm,
+            2 * (-(x * a0 + y * a1 + z * a2)) / nrm]
+    return cat(cols + [d[:, k] for k in range(6, capi.V_STRIDE)])
+
+
+def damper_bounds(cfg, nv, q):
+    """velDamperJointConstraints as the oracle states it (oracle/wbc_oracle.c): -> lb, ub, dlb, dub [B, 26]; dlb, dub the derivative with
+    respect to q[damper_qidx[i]], branch by branch: 0 on a constant branch, at a kink the branch the oracle's comparisons select."""
+    q = np.asarray(q, dtype=np.float64).reshape(-1, capi.Q_STRIDE)
+    B, NVs = q.shape[0], capi.V_STRIDE
+    lb, ub, dlb, dub = np.zeros((B, NVs)), np.zeros((B, NVs)), np.zeros((B, NVs)), np.zeros((B, NVs))
+    if not cfg.use_bounds:
+        lb[:, :nv], ub[:, :nv] = -1e30, 1e30
+        return lb, ub, dlb, dub
+    slope = cfg.damper_coef / (cfg.damper_qi - cfg.damper_qs)
+    for i in range(min(nv, int(cfg.lock_from))):
+        qi, lo, hi, vm = q[:, cfg.damper_qidx[i]], cfg.damper_lo[i], cfg.damper_hi[i], cfg.damper_vmax[i]
+        zone = qi <= lo + cfg.damper_qi
+        lraw = -cfg.damper_coef * (qi - lo - cfg.damper_qs) / (cfg.damper_qi - cfg.damper_qs)
+        lin = zone & ~(lraw > vm) & ~(lraw < -vm)
+        l = np.where(zone, np.clip(lraw, -vm, vm), -vm)
+        dl = np.where(lin, -slope, 0.0)
+        zone = qi >= hi - cfg.damper_qi
+        uraw = cfg.damper_coef * (hi - qi - cfg.damper_qs) / (cfg.damper_qi - cfg.damper_qs)
+        lin = zone & ~(uraw < -vm) & ~(uraw > vm)
+        uu = np.where(zone, np.clip(uraw, -vm, vm), vm)
+        du = np.where(lin, -slope, 0.0)
+        lb[:, i], dlb[:, i] = np.where(l > 0, -l, l), np.where(l > 0, -dl, dl)
+        ub[:, i], dub[:, i] = np.where(uu < 0, -uu, uu), np.where(uu < 0, -du, du)
+    return lb, ub, dlb, dub
+
+
+def _side_split(w, val, lo, hi, bits):
+    """(dL/d lower, dL/d upper) of the constraints with values val between lo and hi and sensitivities w: wbc_qp_certificate's rule — with a
+    working set its marked side (bits: 1 lower, 2 upper), without one the lower side if |val - lo| < 1e-7 max(1, |lo|), else the upper; half and
+    half where lo == hi."""
+    if bits is None:
+        low = np.abs(val - lo) < 1e-7 * np.maximum(1.0, np.abs(lo))
+        up = ~low
+    else:
+        low, up = bits == 1, bits == 2
+    eq = lo == hi
+    return np.where(eq, 0.5 * w, np.where(low, w, 0.0)), np.where(eq, 0.5 * w, np.where(up, w, 0.0))
+
+
+def tick_state_gradients(model, cfg, inputs, x, u, dt, fk, sens_bounds=None, sens_rows=None, y_rows=None, task_params=None, working_set=None):
+    """wbc_tick_vjp_state restated for B instances of ONE model, from unweighted rows: x = qdot, u = sens_x, w = sens_bounds [B, 26] /
+    sens_rows [B, p], y = y_rows [B, p] of the certificate for the caller's v = dL/dqdot; working_set [B, 2] uint64 or None. Conventions of
+    tick_gradients; fk also gives fk.joints(q) -> oMi [B, njoints, 12]. q_con is not supported; posture_u and the orientation references are
+    held constant. With r = b - A x and s = A u:
+      dL/d delta_k = sum_rows (r_i u - s_i x) . dA_i/d delta_k + s_i db_i/d delta_k + sum_j (y_j u - w_j x) . dC_j/d delta_k + sum_active w_i de_i/d delta_k
+    Returns dict(d_q [B, 26] (tangent coordinates: q (+) delta = pin.integrate(q, delta)), d_trunk_box_center [B, 4], and what the algebra
+    contracts: dA, db (tick_gradients'), dC [B, p, 26], dClb, dCub [B, p], dlb, dub [B, 26])."""
+    q = np.asarray(inputs["q"], dtype=np.float64).reshape(-1, capi.Q_STRIDE)
+    B, NVs, nv = q.shape[0], capi.V_STRIDE, model.nv
+    x, u = np.asarray(x, dtype=np.float64).reshape(B, NVs), np.asarray(u, dtype=np.float64).reshape(B, NVs)
+    tg = tick_gradients(model, cfg, inputs, x, u, dt, fk, task_params)
+    import wbc_model
+    tp = wbc_model.task_params(cfg, B) if task_params is None else np.asarray(task_params, dtype=np.float64).reshape(B, capi.TASK_PARAMS_DOUBLES)
+    P = {k: tp[:, sl].reshape((B,) + shape) for k, (sl, shape) in wbc_model.TASK_PARAMS_LAYOUT.items()}
+    oMf, oMi = fk(q), fk.joints(q)
+    J, Jcom = fk.jacobians(q)
+    G = raw_tangent_map(model, q)
+    dq = np.zeros((B, NVs))
+    A, b = tg["A"], tg["b"]
+    rr, ss = b - np.einsum("bmk,bk->bm", A, x), np.einsum("bmk,bk->bm", A, u)
+    row = 0
+
+    def rows_term(alpha, beta, Dx, Du):
+        return np.einsum("br,brk->bk", alpha, Du) - np.einsum("br,brk->bk", beta, Dx)
+
+    def lwa_lin(role):
+        return frame_rows(model, J, oMf, role, world=False)[:, 0:3]
+    # ---- task rows
+    for e in range(capi.NEE):
+        if not cfg.task_ee[e]:
+            continue
+        c = P["ee_W"][:, e] * P["ee_w"][:, e][:, None]
+        r6, s6 = rr[:, row:row + 6], ss[:, row:row + 6]
+        dq += rows_term(c * r6, c * s6, frame_rows_dq(model, J, oMf, capi.FR_EE0 + e, False, x), frame_rows_dq(model, J, oMf, capi.FR_EE0 + e, False, u))
+        db = -(P["ee_w"][:, e][:, None] * P["ee_gain"][:, e, :3] / dt)          # b_i = w (.. + gain_i (xt_i - p_i) / dt)
+        dq += np.einsum("br,brk->bk", s6[:, :3] * db, lwa_lin(capi.FR_EE0 + e))
+        row += 6
+    if cfg.task_trunk:
+        c = P["trunk_W"] * P["trunk_w"].reshape(B, 1)
+        r6, s6 = rr[:, row:row + 6], ss[:, row:row + 6]
+        dq += rows_term(c * r6, c * s6, frame_rows_dq(model, J, oMf, capi.FR_TRUNK, True, x), frame_rows_dq(model, J, oMf, capi.FR_TRUNK, True, u))
+        w = P["trunk_w"].reshape(B, 1)
+        dq += np.einsum("br,brk->bk", s6[:, :3] * (-(w * P["trunk_gain"][:, :3] / dt)), lwa_lin(capi.FR_TRUNK))
+        # quaternion feedback: qe is linear in fq, d fq / d delta_k = 1/2 fq (x) (R_f' a_k, 0) for the columns that move the frame
+        Rf = oMf[:, capi.FR_TRUNK, 0:9].reshape(B, 3, 3)
+        fq = _R_to_quat(oMf[:, capi.FR_TRUNK, 0:9])
+        rq = euler_xyz_to_quat(np.asarray(inputs["trunk_ref_euler"], dtype=np.float64).reshape(B, 3))
+
+        def qe_of(f):
+            return np.stack([f[:, 3] * rq[:, 0] - f[:, 0] * rq[:, 3] + f[:, 1] * rq[:, 2] - f[:, 2] * rq[:, 1],
+                             f[:, 3] * rq[:, 1] - f[:, 1] * rq[:, 3] - f[:, 0] * rq[:, 2] + f[:, 2] * rq[:, 0],
+                             f[:, 3] * rq[:, 2] - f[:, 3] * rq[:, 2] + f[:, 0] * rq[:, 1] - f[:, 1] * rq[:, 0]], axis=1)
+        Jang = frame_rows(model, J, oMf, capi.FR_TRUNK, world=True)[:, 3:6]     # a_k of the support columns
+        loc = np.einsum("bji,bjk->bik", Rf, Jang)                             # R_f' a_k
+        coef = s6[:, 3:] * w * P["trunk_gain"][:, 3:]
+        for m in range(3):
+            dq += (coef * qe_of(0.5 * _quat_right(fq, np.eye(3)[m]))).sum(axis=1)[:, None] * loc[:, m, :]
+        row += 6
+    if cfg.task_com:
+        c = P["com_W"]
+        r3, s3 = rr[:, row:row + 3], ss[:, row:row + 3]
+        dq += rows_term(c * r3, c * s3, com_rows_dq(model, J, oMi, x), com_rows_dq(model, J, oMi, u))
+        dq += np.einsum("br,brk->bk", s3 * (-P["com_gain"]), Jcom)
+        row += 3
+    if cfg.task_joint:
+        if cfg.task_joint == capi.JOINT_PREV:                                 # b_k = d up_k, up = np.delete(q, 6)[:nv]
+            d = ((1.0 / nv) * P["joint_w"]).reshape(B, 1)
+            Gd = np.delete(G, 6, axis=1)[:, :NVs]
+            dq += np.einsum("bi,bik->bk", np.where(np.arange(NVs)[None, :] < nv, ss[:, row:row + NVs] * d, 0.0), Gd)
+        row += NVs
+    # ---- constraint rows, in findConstraints' order
+    rows_, cl_, cu_, dcur_ = [], [], [], []                                    # unweighted rows, bounds, and d(bounds)/d delta [B, 26] per row (lower, upper)
+    com = fk.com(q) if (cfg.con_com or cfg.task_com) else None
+    bc = None
+    if cfg.con_com:
+        pFL, pRR = oMf[:, capi.FR_EE0 + 1, 9:12], oMf[:, capi.FR_EE0 + 2, 9:12]
+        JFL, JRR = lwa_lin(capi.FR_EE0 + 1), lwa_lin(capi.FR_EE0 + 2)
+        k = cfg.com_box_scale / dt
+        for r in range(2):
+            rows_.append(("com", r))
+            cl_.append((pRR[:, r] - com[:, r]) / dt * cfg.com_box_scale)
+            cu_.append((pFL[:, r] - com[:, r]) / dt * cfg.com_box_scale)
+            dcur_.append((k * (JRR[:, r] - Jcom[:, r]), k * (JFL[:, r] - Jcom[:, r])))
+    if cfg.con_trunk:
+        bc = np.asarray(inputs["trunk_box_center"], dtype=np.float64).reshape(B, 4)
+        R = oMf[:, capi.FR_TRUNK, 0:9]
+        Jt = frame_rows(model, J, oMf, capi.FR_TRUNK, world=False)
+        om = Jt[:, 3:6]                                                       # world angular velocity per column: dR = [om] R
+        dR = lambda i, j: np.cross(om.transpose(0, 2, 1), R.reshape(B, 3, 3)[:, None, :, j])[:, :, i]   # noqa: E731  d R_ij / d delta_k [B, 26]
+        R00, R10, R20, R21, R22 = (R[:, i][:, None] for i in (0, 3, 6, 7, 8))
+        cxy = np.sqrt(R21 * R21 + R22 * R22)
+        de = [(R22 * dR(2, 1) - R21 * dR(2, 2)) / (R21 * R21 + R22 * R22),
+              (-cxy * dR(2, 0) + R20 * ((R21 * dR(2, 1) + R22 * dR(2, 2)) / cxy)) / (R20 * R20 + cxy * cxy),
+              (R00 * dR(1, 0) - R10 * dR(0, 0)) / (R00 * R00 + R10 * R10)]
+        cur = np.stack([oMf[:, capi.FR_TRUNK, 11], np.arctan2(R[:, 7], R[:, 8]), np.arctan2(-R[:, 6], cxy[:, 0]), np.arctan2(R[:, 3], R[:, 0])], axis=1)
+        dcur = [Jt[:, 2]] + de
+        var = np.stack([bc[:, 0] * cfg.trunk_box_z_frac] + [np.full(B, cfg.trunk_box_ang)] * 3, axis=1)
+        k = cfg.trunk_box_scale / dt
+        for r in range(4):
+            rows_.append(("trunk", r))
+            cl_.append(((bc[:, r] - var[:, r]) - cur[:, r]) / dt * cfg.trunk_box_scale)
+            cu_.append(((bc[:, r] + var[:, r]) - cur[:, r]) / dt * cfg.trunk_box_scale)
+            dcur_.append((-k * dcur[r], -k * dcur[r]))
+    for e in range(capi.NEE):
+        if cfg.con_ee[e]:
+            for r in range(3):
+                rows_.append(("ee", e, r))
+                cl_.append(np.zeros(B))
+                cu_.append(np.zeros(B))
+                dcur_.append((np.zeros((B, NVs)), np.zeros((B, NVs))))
+    p = len(rows_)
+    out = dict(dA=tg["dA"], db=tg["db"], dC=np.zeros((B, p, NVs)), dClb=np.zeros((B, p)), dCub=np.zeros((B, p)), d_trunk_box_center=np.zeros((B, 4)))
+    ws = None if working_set is None else np.asarray(working_set, dtype=np.uint64).reshape(B, 2)
+
+    def bits_of(word, n):
+        i = np.arange(n, dtype=np.uint64)[None, :]
+        return (((word[:, None] >> i) & np.uint64(1)) | (((word[:, None] >> (i + np.uint64(32))) & np.uint64(1)) << np.uint64(1))).astype(np.int64)
+    if p:
+        w = np.asarray(sens_rows, dtype=np.float64).reshape(B, p)
+        y = np.asarray(y_rows, dtype=np.float64).reshape(B, p)
+        out["dC"] = y[:, :, None] * u[:, None, :] - w[:, :, None] * x[:, None, :]
+        Dcx = Dcu = None
+        Dfx, Dfu = {}, {}
+        Cx = np.zeros((B, p))
+        for i, rdesc in enumerate(rows_):
+            if rdesc[0] == "com":
+                if Dcx is None:
+                    Dcx, Dcu = com_rows_dq(model, J, oMi, x), com_rows_dq(model, J, oMi, u)
+                Dx, Du, Crow = Dcx[:, rdesc[1]], Dcu[:, rdesc[1]], Jcom[:, rdesc[1]]
+            else:
+                role, world, r = (capi.FR_TRUNK, False, 2 + rdesc[1]) if rdesc[0] == "trunk" else (capi.FR_EE0 + rdesc[1], True, rdesc[2])
+                if (role, world) not in Dfx:
+                    Dfx[role, world] = frame_rows_dq(model, J, oMf, role, world, x)
+                    Dfu[role, world] = frame_rows_dq(model, J, oMf, role, world, u)
+                Dx, Du, Crow = Dfx[role, world][:, r], Dfu[role, world][:, r], frame_rows(model, J, oMf, role, world)[:, r]
+            dq += y[:, i:i + 1] * Du - w[:, i:i + 1] * Dx
+            Cx[:, i] = np.einsum("bk,bk->b", Crow, x)
+        cl, cu = np.stack(cl_, axis=1), np.stack(cu_, axis=1)
+        out["dClb"], out["dCub"] = _side_split(w, Cx, cl, cu, None if ws is None else bits_of(ws[:, 1], p))
+        for i in range(p):
+            dq += out["dClb"][:, i:i + 1] * dcur_[i][0] + out["dCub"][:, i:i + 1] * dcur_[i][1]
+        if cfg.con_trunk:
+            i0 = 2 if cfg.con_com else 0
+            k = cfg.trunk_box_scale / dt
+            out["d_trunk_box_center"][:, 0] = k * (out["dClb"][:, i0] * (1.0 - cfg.trunk_box_z_frac) + out["dCub"][:, i0] * (1.0 + cfg.trunk_box_z_frac))
+            out["d_trunk_box_center"][:, 1:] = k * (out["dClb"][:, i0 + 1:i0 + 4] + out["dCub"][:, i0 + 1:i0 + 4])
+    # ---- the velocity bounds
+    lb, ub, dlb, dub = damper_bounds(cfg, nv, q)
+    wb = np.zeros((B, NVs)) if sens_bounds is None else np.asarray(sens_bounds, dtype=np.float64).reshape(B, NVs)
+    out["dlb"], out["dub"] = _side_split(wb, x, lb, ub, None if ws is None else bits_of(ws[:, 0], NVs))
+    if cfg.use_bounds:
+        qidx = np.array([cfg.damper_qidx[i] for i in range(NVs)])
+        dq += np.einsum("bi,bik->bk", out["dlb"] * dlb + out["dub"] * dub, G[:, qidx, :])
+    dq[:, nv:] = 0.0
+    out["d_q"] = dq
+    return out
