@@ -1,5 +1,6 @@
 // wbc_k_sim3p.hip — the packed sim3 kernel wbc_tick_sim3p_kernel<WARM, TRUNK, QCON, ROT, TP, FIXD>: the benchmark path, four instances per wavefront.
 #include "wbc_packed.h"
+#include "wbc_entry_in.h"
 
 namespace wbc {
 
@@ -53,6 +54,50 @@ namespace wbc {
 // §3.30). Same operations on the same operands: bit for bit the dynamic variant's results. The launcher takes a FIXD instantiation only for a
 // handle whose single plan has exactly these dimensions and a call without a model_id array (launch_tick_sim3p's `fixd`); the statistic
 // "last_tick_fixd" says which ran. Instantiated for the variants without QCON and ROT. A/B switch: SIM3P_NO_FIXD never selects it.
+// The entry's tables: lane s's records (reduced variable s, eliminated leg DoF s, first FK level, two sine / cosine indices) and
+// the constants of the model, its configuration and its plan that the packed path reads — one load level behind the inputs, nothing waits for an
+// index; with it the entries the kernel used to fetch where it needed them, each a round trip of its own: the trunk frame's joint and the posture
+// rows' masks (A/B switch: SIM3P_ENTRY_OLD_LATE). With TP the weights and gains come from the instance's row instead (read where the row is known).
+template <bool TP, bool FIXD>
+struct PkTab {
+  DevPlan::PkCol cv, cg;
+  DevPlan::PkJoint fkn;
+  int scq0, scq1, gj, tj, nv, nq, n_red, nelim, p_keep;
+  unsigned flags, task_ee_mask, gsup, post_zero, post_pert;
+  double dcoef, dqi, dqs, gp[3], tb_z, tb_a, tb_s, ee_w, eW[6], eG[3], joint_w;
+};
+template <bool TP, bool FIXD>
+__device__ __forceinline__ PkTab<TP, FIXD> pk_tab_load(const DevModel& M, const WbcConfig& cfg, const DevPlan& P, const int s) {
+  PkTab<TP, FIXD> t;
+  t.cv = P.pk_var[s]; t.cg = P.pk_leg[s];
+  t.fkn = P.pk_fk[0][s];
+  t.scq0 = P.pk_scq[(2 + s) & 31]; t.scq1 = P.pk_scq[(18 + s) & 31];
+  t.gj = M.frame_joint[WBC_FR_EE0 + 4];
+#ifdef SIM3P_ENTRY_OLD_LATE
+  t.tj = 0;
+#else
+  t.tj = M.frame_joint[WBC_FR_TRUNK];       // (read after the FK sweep: fetched there it was a round trip of its own)
+#endif
+  t.nv = FIXD ? SIM3P_FIXD_NV : M.nv; t.nq = FIXD ? SIM3P_FIXD_NQ : M.nq; t.n_red = FIXD ? SIM3P_FIXD_N : P.n_red;
+  t.nelim = FIXD ? SIM3P_FIXD_NELIM : P.nelim; t.p_keep = FIXD ? SIM3P_FIXD_PKEEP : P.p_keep;
+  t.flags = P.flags; t.task_ee_mask = P.task_ee_mask; t.gsup = P.redsup[WBC_FR_EE0 + 4];
+#ifdef SIM3P_ENTRY_OLD_LATE
+  t.post_zero = t.post_pert = 0u;
+#else
+  t.post_zero = P.post_zero; t.post_pert = P.post_pert;   // (the posture rows' masks: fetched where they are used they were waited for on the spot)
+#endif
+  t.dcoef = cfg.damper_coef; t.dqi = cfg.damper_qi; t.dqs = cfg.damper_qs;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) t.gp[i] = M.frame_p[WBC_FR_EE0 + 4][i];
+  t.tb_z = cfg.trunk_box_z_frac; t.tb_a = cfg.trunk_box_ang; t.tb_s = cfg.trunk_box_scale;
+  t.ee_w = TP ? 0.0 : (double)cfg.ee_w[4];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) t.eW[i] = TP ? 0.0 : (double)cfg.ee_W[4][i];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) t.eG[i] = TP ? 0.0 : (double)cfg.ee_gain[4][i];
+  t.joint_w = TP ? 0.0 : (double)cfg.joint_w;
+  return t;
+}
 template <bool WARM, bool TRUNK = false, bool QCON = false, bool ROT = false, bool TP = false, bool FIXD = false>
 #ifdef SIM3P_NUM_VGPR
 __attribute__((amdgpu_waves_per_eu(SIM3P_NUM_VGPR, SIM3P_NUM_VGPR)))
@@ -77,26 +122,89 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
   // (no loop over groups: a wave that takes two groups of four one after the other — half the workgroups, twice as long each — measured 6 % SLOWER
   //  even with a clean register allocation (opaque lane index + -mllvm -disable-machine-licm; without them the hoisted invariants spill 139 loads /
   //  91 stores into the packed path): profiles/r04_ab_licm_iters.txt. The first round of a launch costs twice a steady-state round — all waves
-  //  stall on their inputs at once — and fewer, longer waves do not change that.)
+  //  stall on their inputs at once — and fewer, longer waves do not change that. What does: fewer memory levels in series before the first
+  //  arithmetic. The entry below has four — slice block, list entry, inputs, tables — where it had nine: DESIGN.md §3.38.)
   // row r of group grp takes instance 4 grp + r, or the one the handle's wave order puts there (wbc_packed.h wo_instance)
   const int grp = (int)blockIdx.x;
   const int pos = 4 * grp + r;
   const bool valid = pos < A.B;
-  const int b = valid ? wo_instance(A.worder, wg, A.B, grp, r, pos) : A.B - 1;
+  // ---- the entry's memory levels: [kernel arguments] -> the wave order's slice block -> its list entry -> every input of the
+  // instance at once -> the per-lane tables. Loads are ISSUED in this order and waited for once per level; nothing about the arithmetic changes.
+  // (The tables ahead of the wave order's chain, which the FIXD form allows — no model_id array, model 0 — measured nothing at B = 65536 and
+  //  +0.3 us on a lone wave: dropped, §3.38.) The FIXD form's model index goes through an opaque VGPR: with a constant the uniform table entries
+  //  would become scalar loads, and the kernel has no SGPRs to keep them in.
+  const bool mid_known = FIXD || !A.in.model_id;          // wave-uniform
   int mid = 0;
+  asm("" : "+v"(mid));                      // (not volatile: behind an asm with side effects the slice block's loads are no longer scalar loads)
+#ifdef SIM3P_ENTRY_OLD_SLICE
+  const int b = valid ? wo_instance(A.worder, wg, A.B, grp, r, pos) : A.B - 1;
+#else
+  const int bw = wo_instance(A.worder, wg, A.B, grp, r, pos);   // (every row: a row without an instance reads a clamped list entry and drops it)
+  const int b = valid ? bw : A.B - 1;
+#endif
+  const double dt = A.dt, inv_dt = 1.0 / A.dt;
+  const WbcTaskParams* tpr = nullptr;       // TP: the row the weights and gains come from (a refused row: the model's own block)
+  bool tpbad = false;
+#ifndef SIM3P_ENTRY_OLD_INPUTS
+  // ---- loads: every input of instance b in ONE level — one address per lane (wbc_entry_in.h), one predicated load each, issued back to back
+  double tw = 0.0;                          // TRUNK: entry s of trunk_W [6], trunk_w, trunk_gain [6]
+  bool tw_late = TRUNK;
+  {
+    const double* qg = A.in.q + (size_t)b * NQ;
+    const unsigned present = (A.in.ee_target ? 1u << EIN_EE_TARGET : 0u) | (A.in.prev_ee_target ? 1u << EIN_PREV_EE_TARGET : 0u) |
+                             (A.in.trunk_box_center ? 1u << EIN_TRUNK_BOX_CENTER : 0u) | (A.in.ee_ref_rot ? 1u << EIN_EE_REF_ROT : 0u);
+    const EntryIn ie = entry_in_ex(s, b, present), ir = entry_in_rot(s, b, present);
+    const double* const eb = ie.arr == EIN_EE_TARGET ? A.in.ee_target : (ie.arr == EIN_PREV_EE_TARGET ? A.in.prev_ee_target : A.in.trunk_box_center);
+    const double q0 = qg[s];
+    double q1 = 0.0, ex = 0.0, rs = 0.0, rp = 0.0, t0 = 0.0, t1 = 0.0;
+    unsigned long long wsw = 0ull;
+    int midv = 0;
+    if (16 + s < NQ) q1 = qg[16 + s];
+    if (ie.on) ex = eb[ie.off];
+    if (ir.on) { rs = A.in.ee_ref_rot[ir.off]; rp = A.in.ee_prev_rot[ir.off]; }
+    if (WARM && s < 2 && A.ws_in && valid) wsw = A.ws_in[2 * (size_t)b + s];      // the carried working set: two words per instance
+    if (!FIXD && A.in.model_id) midv = A.in.model_id[b];
+    if (TRUNK) {
+      t0 = *pk_trunk_input_at(A.in, b, s);
+      if (s < 2) t1 = *pk_trunk_input_at(A.in, b, 16 + s);
+      if (!TP && mid_known) { tw_late = false; if (s < 13) tw = (&cfgs[mid].trunk_W[0])[s]; }
+    }
+    __builtin_amdgcn_sched_barrier(0);      // (everything above is in flight before anything below waits for it)
+    if (!FIXD && A.in.model_id) mid = midv < 0 ? 0 : (midv >= A.n_models ? A.n_models - 1 : midv);
+    if (TP) {
+      tpbad = tp_row_bad16(tps + b, s, rbase);
+      tpr = tpbad ? reinterpret_cast<const WbcTaskParams*>(&cfgs[mid].ee_W[0][0]) : tps + b;
+    }
+    V.in[s] = q0;
+    if (16 + s < 28) V.in[16 + s] = q1;
+    if (s < 10) V.in[28 + s] = ex;
+    V.cl[s] = 0.0; V.cl[16 + s] = 0.0;
+    if (TRUNK) {   // trunk_target [3], prev_trunk_target [3], trunk_ref_euler [3], trunk_prev_rot [9] -> V.yv [14..15] | V.tv [16], contiguous; the
+                   // configuration's trunk_W [6], trunk_w, trunk_gain [6] -> V.xv [2..14] (these vectors are free until the contact stage)
+      static_assert(offsetof(PVec, tv) - offsetof(PVec, yv) == 16 * sizeof(double), "yv [14..15] runs on into tv");
+      double* const tin = V.yv + 14;
+      if (tw_late && s < 13) tw = TP ? (&tpr->trunk_W[0])[s] : (&cfgs[mid].trunk_W[0])[s];
+      tin[s] = t0;
+      if (s < 2) tin[16 + s] = t1;
+      if (s < 13) V.xv[2 + s] = tw;
+    }
+    if (WARM && s < 2) V.in[38 + s] = __longlong_as_double((long long)wsw);   // parked (as bit patterns) in V.in[38..39]
+    if (ir.on) { V.dv[s] = rs; V.yv[s] = rp; }   // the gripper's orientation reference and its previous value (free vectors until the QP)
+  }
+  const DevModel& M = models[mid];
+  const WbcConfig& cfg = cfgs[mid];
+  const DevPlan& P = plans[mid];
+#else
   if (A.in.model_id) { mid = A.in.model_id[b]; mid = mid < 0 ? 0 : (mid >= A.n_models ? A.n_models - 1 : mid); }
   const DevModel& M = models[mid];
   const WbcConfig& cfg = cfgs[mid];
   const DevPlan& P = plans[mid];
-  const double dt = A.dt, inv_dt = 1.0 / A.dt;
-  const WbcTaskParams* tpr = nullptr;       // TP: the row the weights and gains come from (a refused row: the model's own block)
-  bool tpbad = false;
   if (TP) {
     tpbad = tp_row_bad16(tps + b, s, rbase);
     tpr = tpbad ? reinterpret_cast<const WbcTaskParams*>(&cfg.ee_W[0][0]) : tps + b;
   }
 
-  // ---- loads: inputs (coalesced per instance), then the per-lane tables
+  // ---- loads: inputs (coalesced per instance), then the per-lane tables (A/B: the nested arms, a load in each)
   {
     const double* qg = A.in.q + (size_t)b * NQ;
     const double q0 = qg[s], q1 = (16 + s < NQ) ? qg[16 + s] : 0.0;
@@ -126,6 +234,7 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
       if (s < 9) { V.dv[s] = A.in.ee_ref_rot[(size_t)b * 45 + 36 + s]; V.yv[s] = A.in.ee_prev_rot[(size_t)b * 45 + 36 + s]; }
     }
   }
+#endif
   double at6[6] = {0, 0, 0, 0, 0, 0};      // TRUNK: the trunk task's image of base variable s (kept for the refinement's residual; its targets in V.pad_)
   if (TRUNK) {
     WSYNC();                               // (the staged inputs are visible)
@@ -181,31 +290,32 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
     WSYNC();
     __builtin_amdgcn_sched_barrier(0);    // (the per-lane records below are fetched after this block: live across it they spilled 110 VGPRs)
   }
-  const int nv = FIXD ? SIM3P_FIXD_NV : M.nv, nq = FIXD ? SIM3P_FIXD_NQ : M.nq, n = FIXD ? SIM3P_FIXD_N : P.n_red, nelim = FIXD ? SIM3P_FIXD_NELIM : P.nelim,
-            nl = 3 * nelim, p_keep = FIXD ? SIM3P_FIXD_PKEEP : P.p_keep, p = p_keep + nl;
-  const unsigned fl = P.flags;
+  // the per-lane records and the model's constants (pk_tab_load)
+  const PkTab<TP, FIXD> tab = pk_tab_load<TP, FIXD>(M, cfg, P, s);
+  const int nv = FIXD ? SIM3P_FIXD_NV : tab.nv, nq = FIXD ? SIM3P_FIXD_NQ : tab.nq, n = FIXD ? SIM3P_FIXD_N : tab.n_red, nelim = FIXD ? SIM3P_FIXD_NELIM : tab.nelim,
+            nl = 3 * nelim, p_keep = FIXD ? SIM3P_FIXD_PKEEP : tab.p_keep, p = p_keep + nl;
+  const unsigned fl = tab.flags;
   const bool c_con_trunk = fl & 2u;
   const int c_task_joint = (fl >> 4) & 7u;
-  const bool has_grip = (P.task_ee_mask >> 4) & 1u;
-  // per-lane records (one load level: nothing waits for an index): reduced variable s, eliminated leg DoF s, first FK level
-  const DevPlan::PkCol cv = P.pk_var[s], cg = P.pk_leg[s];
-  DevPlan::PkJoint fkn = P.pk_fk[0][s];
-  const int scq0 = P.pk_scq[(2 + s) & 31], scq1 = P.pk_scq[(18 + s) & 31];
+  const bool has_grip = (tab.task_ee_mask >> 4) & 1u;
+  const DevPlan::PkCol cv = tab.cv, cg = tab.cg;
+  DevPlan::PkJoint fkn = tab.fkn;
+  const int scq0 = tab.scq0, scq1 = tab.scq1;
   const int dof0 = cv.dof, dof1 = cg.dof;
   const int c0_joint = cv.joint, c0_lin = cv.lin, c0_ang = cv.ang, c1_joint = cg.joint, c1_lin = cg.lin, c1_ang = cg.ang;
   const int dq0 = cv.dq_idx, dq1 = cg.dq_idx;
   const double dlo0 = cv.d_lo, dhi0 = cv.d_hi, dvm0 = cv.d_vm, dlo1 = cg.d_lo, dhi1 = cg.d_hi, dvm1 = cg.d_vm;
-  const double dcoef = cfg.damper_coef, dqi = cfg.damper_qi, dqs = cfg.damper_qs;
-  const int gj = M.frame_joint[WBC_FR_EE0 + 4];
-  const double gp0 = M.frame_p[WBC_FR_EE0 + 4][0], gp1 = M.frame_p[WBC_FR_EE0 + 4][1], gp2 = M.frame_p[WBC_FR_EE0 + 4][2];
-  const unsigned gsup = P.redsup[WBC_FR_EE0 + 4];
-  const double ee_w = TPW(ee_w[4]);
+  const double dcoef = tab.dcoef, dqi = tab.dqi, dqs = tab.dqs;
+  const int gj = tab.gj;
+  const double gp0 = tab.gp[0], gp1 = tab.gp[1], gp2 = tab.gp[2];
+  const unsigned gsup = tab.gsup;
+  const double ee_w = TP ? (double)tpr->ee_w[4] : tab.ee_w;
   double eW[6], eG[3];
 #pragma unroll
-  for (int i = 0; i < 6; ++i) eW[i] = TPW(ee_W[4][i]);
+  for (int i = 0; i < 6; ++i) eW[i] = TP ? (double)tpr->ee_W[4][i] : tab.eW[i];
 #pragma unroll
-  for (int i = 0; i < 3; ++i) eG[i] = TPW(ee_gain[4][i]);
-  const double joint_w = TPW(joint_w), tb_z = cfg.trunk_box_z_frac, tb_a = cfg.trunk_box_ang, tb_s = cfg.trunk_box_scale;
+  for (int i = 0; i < 3; ++i) eG[i] = TP ? (double)tpr->ee_gain[4][i] : tab.eG[i];
+  const double joint_w = TP ? (double)tpr->joint_w : tab.joint_w, tb_z = tab.tb_z, tb_a = tab.tb_a, tb_s = tab.tb_s;
   WSYNC();
   const double* const qv = V.in;
   PSTOP(6, qv[s] + dlo0 + dlo1 + eW[0] + (double)(fkn.joint + scq0 + scq1));
@@ -225,7 +335,11 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
   // trunk frame = the root joint's placement (imu frame: identity offset); gripper_bar origin
   double Rtr[9], ptr[3], pfe[3];
   {
+#ifdef SIM3P_ENTRY_OLD_LATE
     const double* Pr = oMi + 12 * M.frame_joint[WBC_FR_TRUNK];
+#else
+    const double* Pr = oMi + 12 * tab.tj;
+#endif
 #pragma unroll
     for (int c = 0; c < 3; ++c)
 #pragma unroll
@@ -286,8 +400,13 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
   double g1 = 0.0;                          // posture term of leg DoF s in g
   double bp0 = 0.0, bp1 = 0.0;              // posture rows' targets (b of qpJointb) of reduced variable s / of leg DoF s: the refinement's residual
   {
-    const bool prev0 = (c_task_joint == WBC_JOINT_PREV) || (c_task_joint >= WBC_JOINT_MANI && !((P.post_zero >> dof0) & 1u));
-    const bool prev1 = (c_task_joint == WBC_JOINT_PREV) || (c_task_joint >= WBC_JOINT_MANI && !((P.post_zero >> dof1) & 1u));
+#ifdef SIM3P_ENTRY_OLD_LATE
+    const unsigned post_zero = P.post_zero;
+#else
+    const unsigned post_zero = tab.post_zero;
+#endif
+    const bool prev0 = (c_task_joint == WBC_JOINT_PREV) || (c_task_joint >= WBC_JOINT_MANI && !((post_zero >> dof0) & 1u));
+    const bool prev1 = (c_task_joint == WBC_JOINT_PREV) || (c_task_joint >= WBC_JOINT_MANI && !((post_zero >> dof1) & 1u));
     double u0 = (prev0 && s < n) ? qv[dof0 < 6 ? dof0 : dof0 + 1] : 0.0;
     double u1 = (prev1 && s < nl) ? qv[dof1 < 6 ? dof1 : dof1 + 1] : 0.0;
     if (QCON && A.in.posture_u) {           // the posture kernel's (or the caller's) target, by DoF
@@ -300,11 +419,16 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
     bp1 = (s < nl) ? (1.0 / nv) * u1 * joint_w : 0.0;
   }
   if (s >= n) g = 0.0;
-  if (RARE(A.post_static && P.post_pert)) {     // the state qpJointb leaves behind: bounds and integrate see it
+#ifdef SIM3P_ENTRY_OLD_LATE
+  const unsigned post_pert = P.post_pert;
+#else
+  const unsigned post_pert = tab.post_pert;
+#endif
+  if (RARE(A.post_static && post_pert)) {     // the state qpJointb leaves behind: bounds and integrate see it
     COLD_MARK();
     WSYNC();
-    if (((P.post_pert >> s) & 1u)) V.in[s] = (qv[s] + 0.0002) - (0.0002 * 2);
-    if (16 + s < NQ && ((P.post_pert >> (16 + s)) & 1u)) V.in[16 + s] = (qv[16 + s] + 0.0002) - (0.0002 * 2);
+    if (((post_pert >> s) & 1u)) V.in[s] = (qv[s] + 0.0002) - (0.0002 * 2);
+    if (16 + s < NQ && ((post_pert >> (16 + s)) & 1u)) V.in[16 + s] = (qv[16 + s] + 0.0002) - (0.0002 * 2);
   }
   WSYNC();
   if (s < 6) {                              // (every lane has read the Grip targets: their slots take the rows' b)
@@ -1059,6 +1183,15 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
   WoPost wop = {0ull, 0ull, 0u, 0u, (uint32_t)WO_NS + 1u, 0u};
   if (A.worder) wop = wo_post(A.worder, wg, grp, valid, wocls, r, s);
 #endif
+#ifndef SIM3P_ENTRY_OLD_LATE
+  // the table entries the outputs need (the locked DoF's count for `iters`, the q index of DoF 6 + s and 22 + s for q_next): issued here, so that
+  // their round trips run behind the refinement and x = Z y too; the opaque uses further down keep them from being sunk again
+  int nlock = P.nlock, cq0 = 0, cq1 = 0;
+  if (A.out.q_next) {
+    if (6 + s < nv) cq0 = M.col_q[6 + s];
+    if (22 + s < nv) cq1 = M.col_q[22 + s];
+  }
+#endif
   // ================================ iterative refinement ==========================================
   // One step at the final working set (QP_Wrapper.py:37 asks qpOASES for numRefinementSteps = 100; oracle: qp_refine). With the slots' normals
   // n_k, right-hand sides b_k and multipliers u_k:   r1 = -(grad f(y) - sum u_k n_k),  r2_k = b_k - n_k'y,   dy = J1 T' r2 + J2 J2' r1.
@@ -1202,13 +1335,18 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
   if (s < n) V.cl[dofA] = x;
   WSYNC();
   const bool wr = valid && !flagged;
+#ifdef SIM3P_ENTRY_OLD_LATE
+  const int nlock = P.nlock;
+#else
+  asm volatile("" : "+v"(nlock));
+#endif
   if (wr) {
     double* qo = A.out.qdot + (size_t)b * NV;
     qo[s] = V.cl[s];
     if (16 + s < NV) qo[16 + s] = V.cl[16 + s];
     if (s == 0) {
       A.out.status[b] = status;
-      if (A.out.iters) A.out.iters[b] = iters + nl + P.nlock;
+      if (A.out.iters) A.out.iters[b] = iters + nl + nlock;
     }
   }
   // ---- jointVelocitiestoConfig (Robot_Wrapper4.py:440-441)
@@ -1217,13 +1355,20 @@ __global__ void __launch_bounds__(64, SIM3P_WAVES) wbc_tick_sim3p_kernel(const K
     V.xv[s] = (s < 6) ? V.cl[s] * dt : 0.0;
     WSYNC();
     double* qn = A.out.q_next + (size_t)b * NQ;
+#ifndef SIM3P_ENTRY_OLD_LATE
+    asm volatile("" : "+v"(cq0), "+v"(cq1));
+#endif
     if (wr) {
       integrate_ff(V, s, qn);
       // 1-DoF joints: q + v dt, DoF by DoF (two per lane; a locked DoF's velocity is 0, the padding of a smaller model stays 0)
 #pragma unroll
       for (int hh = 0; hh < 2; ++hh) {
         const int d = 6 + s + 16 * hh;
+#ifdef SIM3P_ENTRY_OLD_LATE
         if (d < nv) { const int qi = M.col_q[d]; qn[qi] = qv[qi] + V.cl[d] * dt; }
+#else
+        if (d < nv) { const int qi = hh ? cq1 : cq0; qn[qi] = qv[qi] + V.cl[d] * dt; }
+#endif
       }
       if (s < NQ - nq) qn[nq + s] = 0.0;
     }

@@ -400,6 +400,7 @@ __device__ __forceinline__ int wo_instance(WaveOrder* __restrict__ wo, const WoG
   if (!wo || wg.ns > (uint32_t)WO_NS) return pos;
   const uint32_t k = wo_divk(wg, (uint32_t)grp), g = wo_mod(wg, (uint32_t)grp, k);
   const WaveOrder& sl = wo[g];
+#ifdef SIM3P_ENTRY_OLD_SLICE   // (A/B: B in a scalar round of its own, cur and the offsets in a second one behind the early return)
   if (sl.B != (uint32_t)B) return pos;
   const uint32_t cur = sl.cur & 1u, j = 4u * k + (uint32_t)r;
   uint32_t d = 0;
@@ -408,6 +409,25 @@ __device__ __forceinline__ int wo_instance(WaveOrder* __restrict__ wo, const WoG
     const uint32_t o = sl.off[c];
     if (j >= o) d = (uint32_t)(c * WO_CAP) - o;
   }
+#else
+  // cur, B and off[0..5] are bytes 16..47 of the block: ONE scalar load group, read before B is looked at — the same line either
+  // way, and nothing is read through them unless B matches
+  static_assert(offsetof(WaveOrder, cur) == 16 && offsetof(WaveOrder, B) == 20 && offsetof(WaveOrder, off) == 24, "cur, B, off[0..5]: eight words from byte 16");
+  uint32_t w[8];
+  const uint32_t* const wp = reinterpret_cast<const uint32_t*>(&sl) + 4;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) w[i] = wp[i];
+  // (opaque: left alone the compiler sinks all but B behind the early return again, a second round to the same line)
+  asm volatile("" : "+s"(w[0]), "+s"(w[1]), "+s"(w[2]), "+s"(w[3]), "+s"(w[4]), "+s"(w[5]), "+s"(w[6]), "+s"(w[7]));
+  if (w[1] != (uint32_t)B) return pos;
+  const uint32_t cur = w[0] & 1u, j = 4u * k + (uint32_t)r;
+  uint32_t d = 0;
+#pragma unroll
+  for (int c = 1; c < WO_NCLS; ++c) {
+    const uint32_t o = w[2 + c];
+    if (j >= o) d = (uint32_t)(c * WO_CAP) - o;
+  }
+#endif
   const uint32_t i = wo_list(wo, cur, g, 0)[min(j + d, (uint32_t)(WO_NCLS * WO_CAP) - 1u)];
   return i < (uint32_t)B ? (int)i : B - 1;
 }
@@ -563,6 +583,12 @@ __device__ __forceinline__ void pk_jac_col(const double* const oMi, const int jo
 __device__ __forceinline__ double pk_trunk_input(const WbcTickIn& in, const int b, const int k) {
   return (k < 3) ? in.trunk_target[(size_t)b * 3 + k] : (k < 6) ? in.prev_trunk_target[(size_t)b * 3 + (k - 3)]
        : (k < 9) ? in.trunk_ref_euler[(size_t)b * 3 + (k - 6)] : in.trunk_prev_rot[(size_t)b * 9 + (k - 9)];
+}
+// the same entry's address: one load per lane whatever the array (the packed sim3 kernel's single input level)
+__device__ __forceinline__ const double* pk_trunk_input_at(const WbcTickIn& in, const int b, const int k) {
+  const double* const base = (k < 3) ? in.trunk_target : (k < 6) ? in.prev_trunk_target : (k < 9) ? in.trunk_ref_euler : in.trunk_prev_rot;
+  const size_t off = (k < 3) ? (size_t)b * 3 + k : (k < 6) ? (size_t)b * 3 + (k - 3) : (k < 9) ? (size_t)b * 3 + (k - 6) : (size_t)b * 9 + (k - 9);
+  return base + off;
 }
 // calcTargetVelEE3's orientation feed-forward (Robot_Wrapper4.py:1125-1133): omega = vee(((R* - R*_prev) / dt) R*^T), one component per lane
 // (EE s / 3, component s % 3), straight from the caller's [B][5][9] references; zero when none are passed
