@@ -250,6 +250,11 @@ int wbc_constraint_rows(const WbcBatch* b); /* p of findConstraints()           
 int wbc_fk_jacobians(WbcBatch* b, int B, const double* q, const int32_t* model_id, int mem,
                      const WbcFkOut* out, void* stream);
 
+/* The time step. Every entry point below that takes `dt` (wbc_assemble, wbc_tick, wbc_rollout and their _tp / _traj / _tracks / _watch forms,
+ * wbc_tick_vjp, wbc_tick_vjp_state) requires dt > 0 with dt and 1 / dt both finite: the kernels form x * (1 / dt) and qdot * dt, so NaN, 0,
+ * a negative step, +inf (1 / dt = 0, qdot * dt = 0 * inf) and a subnormal step (1 / dt = inf) are refused with WBC_E_ARG before any launch.
+ * wbc_integrate requires dt and 1 / dt finite only: dt < 0 there is a step back. Nothing else about dt is assumed (no nominal 2 ms). */
+
 /* replaces qpA/qpb/findConstraints/velDamperJointConstraints + QP.__init__'s H, g
  * (Robot_Wrapper4.py:1348-1361, QP_Wrapper.py:17-18). */
 int wbc_assemble(WbcBatch* b, int B, const WbcTickIn* in, double dt, int mem, const WbcQpData* out, void* stream);

@@ -25,6 +25,14 @@ static int fail(int code, const char* fmt, ...) {
   va_end(ap);
   return code;
 }
+// The time step of every entry point that takes one (include/wbc.h): dt and 1 / dt both finite and positive. +inf (1 / dt = 0, qdot * dt =
+// 0 * inf) and a subnormal dt (1 / dt = inf) pass a bare "dt > 0". backward: wbc_integrate alone, where dt < 0 is a step back.
+static int check_dt(double dt, const char* who, bool backward = false) {
+  const double inv = 1.0 / dt;
+  if (std::isfinite(dt) && std::isfinite(inv) && (backward || dt > 0)) return WBC_OK;
+  if (backward) return fail(WBC_E_ARG, "%s: dt = %g: dt and 1 / dt finite required", who, dt);
+  return fail(WBC_E_ARG, "%s: dt = %g: dt > 0 with dt and 1 / dt finite required", who, dt);
+}
 #define HIP_TRY(expr)                                                                       \
   do {                                                                                      \
     hipError_t e_ = (expr);                                                                 \
@@ -1178,7 +1186,8 @@ extern "C" int wbc_assemble_tp(WbcBatch* b, int B, const WbcTickIn* in, const Wb
                                void* stream) {
   int rc = check_batch(b, B, "wbc_assemble", true);
   if (rc) return rc;
-  if (!out || !(dt > 0)) return fail(WBC_E_ARG, "wbc_assemble: null output or dt <= 0");
+  if (!out) return fail(WBC_E_ARG, "wbc_assemble: null output");
+  if ((rc = check_dt(dt, "wbc_assemble"))) return rc;
   if ((rc = validate_tick_in(b, in, "wbc_assemble"))) return rc;
   HIP_TRY(hipSetDevice(b->device_id));
   KernelArgs a;
@@ -1203,7 +1212,8 @@ extern "C" int wbc_tick_tp(WbcBatch* b, int B, const WbcTickIn* in, const WbcTas
                            void* stream) {
   int rc = check_batch(b, B, "wbc_tick", true);
   if (rc) return rc;
-  if (!out || !out->qdot || !(dt > 0)) return fail(WBC_E_ARG, "wbc_tick: qdot output required and dt > 0");
+  if (!out || !out->qdot) return fail(WBC_E_ARG, "wbc_tick: qdot output required");
+  if ((rc = check_dt(dt, "wbc_tick"))) return rc;
   if ((rc = validate_tick_in(b, in, "wbc_tick"))) return rc;
   HIP_TRY(hipSetDevice(b->device_id));
   KernelArgs a;
@@ -1453,7 +1463,8 @@ static int rollout_run(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskPa
   // check
   int rc = check_batch(b, B, "wbc_rollout", true);
   if (rc) return rc;
-  if (!r || r->ticks < 1 || !(dt > 0)) return fail(WBC_E_ARG, "wbc_rollout: ticks >= 1 and dt > 0 required");
+  if (!r || r->ticks < 1) return fail(WBC_E_ARG, "wbc_rollout: ticks >= 1 required");
+  if ((rc = check_dt(dt, "wbc_rollout"))) return rc;
   if (r->hold_ticks < 0 || (r->mode != WBC_ROLLOUT_RUNNING && r->mode != WBC_ROLLOUT_WARMUP))
     return fail(WBC_E_ARG, "wbc_rollout: hold_ticks >= 0 and mode WBC_ROLLOUT_RUNNING / WBC_ROLLOUT_WARMUP required");
   if ((rc = validate_tick_in(b, in0, "wbc_rollout"))) return rc;
@@ -1748,7 +1759,7 @@ extern "C" int wbc_tick_vjp(WbcBatch* b, int B, const WbcTickIn* in, const WbcTa
   int rc = check_batch(b, B, who, true);
   if (rc) return rc;
   if (!out) return fail(WBC_E_ARG, "%s: out is required", who);
-  if (!(dt > 0)) return fail(WBC_E_ARG, "%s: dt <= 0", who);
+  if ((rc = check_dt(dt, who))) return rc;
   if (!qdot) return fail(WBC_E_ARG, "%s: qdot is required", who);
   if (!sens_x) return fail(WBC_E_ARG, "%s: sens_x is required", who);
   if ((rc = validate_tick_in(b, in, who))) return rc;
@@ -1808,7 +1819,7 @@ extern "C" int wbc_tick_vjp_state(WbcBatch* b, int B, const WbcTickIn* in, const
   if (rc) return rc;
   if (!out) return fail(WBC_E_ARG, "%s: out is required", who);
   if (!sens) return fail(WBC_E_ARG, "%s: sens is required", who);
-  if (!(dt > 0)) return fail(WBC_E_ARG, "%s: dt <= 0", who);
+  if ((rc = check_dt(dt, who))) return rc;
   if (!sens->qdot) return fail(WBC_E_ARG, "%s: qdot is required", who);
   if (!sens->sens_x) return fail(WBC_E_ARG, "%s: sens_x is required", who);
   if ((rc = validate_tick_in(b, in, who))) return rc;
@@ -1859,6 +1870,7 @@ extern "C" int wbc_integrate(WbcBatch* b, int B, const double* q, const double* 
   int rc = check_batch(b, B, "wbc_integrate", false);
   if (rc) return rc;
   if (!q || !v || !q_next) return fail(WBC_E_ARG, "wbc_integrate: null argument");
+  if ((rc = check_dt(dt, "wbc_integrate", true))) return rc;      // (dt < 0: a step back)
   if (b->n_models > 1 && !model_id) return fail(WBC_E_ARG, "wbc_integrate: model_id is required with %d models", b->n_models);
   HIP_TRY(hipSetDevice(b->device_id));
   IntegrateArgs a;

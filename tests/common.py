@@ -356,7 +356,7 @@ def per_instance_configs(models, cfgs, mid, rows):
     return ms, cs, np.arange(len(rows), dtype=np.int32)
 
 
-def tracks_reference(p):
+def tracks_reference(p, dt=DT_TRACKS):
     """oracle.rollout's loop with a target hook per track: -> dict(q, qdot, status (max), iters (sum), ee_target, trunk_target (the targets the
     next tick would get), tick_status [K, B], frames [K, B, 6, 3] reached, targets [K, B, 6, 3] of the tick). The arrays are read-only."""
     from scipy.spatial.transform import Rotation as R
@@ -380,7 +380,7 @@ def tracks_reference(p):
     for k in range(K):
         set_targets(k)
         targets[k, :, :5], targets[k, :, 5] = d["ee_target"], d["trunk_target"]
-        out = oracle.tick(ms, cs, d, DT_TRACKS, B, nthreads=8, want_q_next=True)
+        out = oracle.tick(ms, cs, d, dt, B, nthreads=8, want_q_next=True)
         tick_status[k] = out["status"]
         status = np.maximum(status, out["status"])
         iters += out["iters"]

@@ -34,7 +34,7 @@ def fields_read(cfg):
     return out
 
 
-def restate(models, cfgs, mid, d, x, u, rows=None):
+def restate(models, cfgs, mid, d, x, u, rows=None, dt=DT):
     """wbc_workload.tick_gradients for a batch of several models interleaved by model_id: each model's instances through the one-model
     restatement, scattered back. -> dict of the eight output arrays [B, ...]"""
     B = len(d["q"])
@@ -44,7 +44,7 @@ def restate(models, cfgs, mid, d, x, u, rows=None):
         if not sel.any():
             continue
         di = {k: v[sel] for k, v in d.items() if k != "model_id"}
-        r = wbc_workload.tick_gradients(m, c, di, x[sel], u[sel], DT, GradFK([m]), None if rows is None else rows[sel])
+        r = wbc_workload.tick_gradients(m, c, di, x[sel], u[sel], dt, GradFK([m]), None if rows is None else rows[sel])
         for k in out:
             out[k][sel] = r[k]
     return out

@@ -22,7 +22,7 @@ def step(models, q, delta, mid=None):
     return oracle.integrate(models, q, delta, 1.0, mid)
 
 
-def restate(models, cfgs, mid, d, cert, rows=None, working_set=None):
+def restate(models, cfgs, mid, d, cert, rows=None, working_set=None, dt=DT):
     """wbc_workload.tick_state_gradients for a batch of several models interleaved by model_id -> dict(d_q [B, 26], d_trunk_box_center [B, 4]);
     cert: dict(qdot, sens_x, sens_bounds, sens_rows, y_rows)"""
     B = len(d["q"])
@@ -32,7 +32,7 @@ def restate(models, cfgs, mid, d, cert, rows=None, working_set=None):
         if not sel.any():
             continue
         di = {k: v[sel] for k, v in d.items() if k != "model_id"}
-        r = wbc_workload.tick_state_gradients(m, c, di, cert["qdot"][sel], cert["sens_x"][sel], DT, StateFK([m]),
+        r = wbc_workload.tick_state_gradients(m, c, di, cert["qdot"][sel], cert["sens_x"][sel], dt, StateFK([m]),
                                               sens_bounds=cert["sens_bounds"][sel], sens_rows=cert["sens_rows"][sel], y_rows=cert["y_rows"][sel],
                                               task_params=None if rows is None else rows[sel],
                                               working_set=None if working_set is None else working_set[sel])

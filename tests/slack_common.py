@@ -106,7 +106,7 @@ def watch_problem(name, B=67, K=12):
 
 
 @functools.lru_cache(maxsize=None)
-def watch_reference(name, B=67, K=12):
+def watch_reference(name, B=67, K=12, dt=DT):
     """The oracle's closed loop of the named recipe with the configuration kept per tick: dict(q [K, B, 27] after each tick's update,
     tick_status [K, B], status, trace [K, 4, B] and which [K, 4, B] (the restatement at q[k]), gap [K, 4, B] (two smallest components), bycode
     [K, 4, B, NCODE] (every component by its code)).
@@ -125,7 +125,7 @@ def watch_reference(name, B=67, K=12):
                 d["trunk_target"] = common.track_at(t, k)
             else:
                 d["ee_target"][:, common.track_index(t["target"])] = common.track_at(t, k)
-        out = oracle.tick(models, cfgs, d, DT, B, nthreads=8, want_q_next=True)
+        out = oracle.tick(models, cfgs, d, dt, B, nthreads=8, want_q_next=True)
         tick_status[k] = out["status"]
         d["q"] = oracle.update_state(models, d["q"], out["q_next"], d["ee_target"], p["imu"], mid) if p["running"] else out["q_next"]
         qs[k] = d["q"]

@@ -50,9 +50,9 @@ def _problem(cfg_name, model_name, B, seed):
     return m, cfg, d, rows, rng
 
 
-def _assemble(m, cfg, d, rows):
+def _assemble(m, cfg, d, rows, dt=DT):
     ms, cs, pid = common.per_instance_configs([m], [cfg], None, rows)
-    a = oracle.assemble(ms, cs, dict(d, model_id=pid), DT, len(rows))
+    a = oracle.assemble(ms, cs, dict(d, model_id=pid), dt, len(rows))
     return a["A"], a["b"]
 
 
@@ -66,12 +66,17 @@ K_BOUND = 16.0
 @pytest.mark.parametrize("model_name", ["a1_wx200", "a1_px100_pin_ver", "laikago_vx300"])
 @pytest.mark.parametrize("cfg_name", ["everything", "c3_trunk_task", "c2", "c3_custom"])
 def test_algebra_against_central_differences_of_the_assembly(cfg_name, model_name):
+    algebra_check(cfg_name, model_name)
+
+
+def algebra_check(cfg_name, model_name, dt=DT):
+    """the check at step dt (test_dt_host.py runs it at steps other than 2 ms)"""
     B = 4
     m, cfg, d, rows, rng = _problem(cfg_name, model_name, B, seed=31)
     x, u = np.zeros((B, 26)), np.zeros((B, 26))
     x[:, :m.nv], u[:, :m.nv] = rng.normal(0, 0.5, (B, m.nv)), rng.normal(0, 0.5, (B, m.nv))
-    res = wbc_workload.tick_gradients(m, cfg, d, x, u, DT, gc.GradFK([m]), rows)
-    A0, b0 = _assemble(m, cfg, d, rows)
+    res = wbc_workload.tick_gradients(m, cfg, d, x, u, dt, gc.GradFK([m]), rows)
+    A0, b0 = _assemble(m, cfg, d, rows, dt)
     # the restatement's rows ARE the oracle's task stack
     scale = max(np.abs(A0).max(), np.abs(b0).max())
     assert res["A"].shape == A0.shape and np.abs(res["A"] - A0).max() <= 1e-12 * scale and np.abs(res["b"] - b0).max() <= 1e-12 * scale
@@ -99,7 +104,7 @@ def test_algebra_against_central_differences_of_the_assembly(cfg_name, model_nam
         def fd_of(t, i=i):
             r2 = rows.copy()
             r2[:, i] = t
-            return _assemble(m, cfg, d, r2)
+            return _assemble(m, cfg, d, r2, dt)
         check(rows[:, i].copy(), "d_task_params", i, fd_of)
     for f in gc.FIELDS:
         if f not in d:
@@ -109,10 +114,10 @@ def test_algebra_against_central_differences_of_the_assembly(cfg_name, model_nam
             def fd_of(t, f=f, i=i, flat=flat):
                 a2 = flat.copy()
                 a2[:, i] = t
-                return _assemble(m, cfg, dict(d, **{f: a2.reshape(d[f].shape)}), rows)
+                return _assemble(m, cfg, dict(d, **{f: a2.reshape(d[f].shape)}), rows, dt)
             check(flat[:, i].copy(), "d_" + f, i, fd_of)
-    print("%s / %s: %d coordinates x %d instances, worst |analytic - central difference| = %.2f eps (max|A| + max|b|) (|dL/dA|_1 + |dL/db|_1) / h  (bound %g)" % (
-        cfg_name, model_name, n_coord, B, worst, K_BOUND))
+    print("%s / %s / dt %.7g: %d coordinates x %d instances, worst |analytic - central difference| = %.2f eps (max|A| + max|b|) (|dL/dA|_1 + |dL/db|_1) / h  (bound %g)" % (
+        cfg_name, model_name, dt, n_coord, B, worst, K_BOUND))
     # what never reaches b is exactly 0; a switched-off task's entries are exactly 0
     S = wbc_model.TASK_PARAMS_SLICES
     g = res["d_task_params"]

@@ -104,7 +104,7 @@ def _random_sides(rng, B, n):
     return ((1 << (np.arange(n)[None, :] + 32 * up)).sum(axis=1)).astype(np.uint64)
 
 
-def _algebra_problem(cfg_name, model_name, B, seed):
+def _algebra_problem(cfg_name, model_name, B, seed, dt=DT):
     m = tgp._model(model_name)
     cfg = common.config(cfg_name, m)
     d = common.tick_inputs(m, cfg, B, seed=seed, with_rot=True)
@@ -117,9 +117,9 @@ def _algebra_problem(cfg_name, model_name, B, seed):
     x[:, :m.nv], u[:, :m.nv] = rng.normal(0, 0.5, (B, m.nv)), rng.normal(0, 0.5, (B, m.nv))
     w, y, wb = rng.normal(0, 1, (B, p)), rng.normal(0, 1, (B, p)), rng.normal(0, 1, (B, 26))
     ws = np.stack([_random_sides(rng, B, 26), _random_sides(rng, B, p) if p else np.zeros(B, np.uint64)], axis=1)
-    res = wbc_workload.tick_state_gradients(m, cfg, d, x, u, DT, gq.StateFK([m]), wb, w, y, rows, ws)
+    res = wbc_workload.tick_state_gradients(m, cfg, d, x, u, dt, gq.StateFK([m]), wb, w, y, rows, ws)
     ms, cs, pid = common.per_instance_configs([m], [cfg], None, rows)
-    return m, cfg, d, res, (lambda dd: oracle.assemble(ms, cs, dict(dd, model_id=pid), DT, B)), ms, pid
+    return m, cfg, d, res, (lambda dd: oracle.assemble(ms, cs, dict(dd, model_id=pid), dt, B)), ms, pid
 
 
 def _finite(a):
@@ -136,8 +136,13 @@ def _contract(res, ap, am, B):
 @pytest.mark.parametrize("model_name", MODELS)
 @pytest.mark.parametrize("cfg_name", ["everything", "c3_trunk_task", "c2", "c3_custom", "c3_nobounds"])
 def test_algebra_against_central_differences_of_the_assembly(cfg_name, model_name):
+    algebra_check(cfg_name, model_name)
+
+
+def algebra_check(cfg_name, model_name, dt=DT):
+    """the check at step dt (test_dt_host.py runs it at steps other than 2 ms)"""
     B = 4
-    m, cfg, d, res, asm, ms, pid = _algebra_problem(cfg_name, model_name, B, seed=31)
+    m, cfg, d, res, asm, ms, pid = _algebra_problem(cfg_name, model_name, B, seed=31, dt=dt)
     a0 = asm(d)
     size = sum(np.abs(_finite(a0[k])).reshape(B, -1).max(axis=1, initial=0.0) for k in QP_KEYS)
     l1 = sum(np.abs(res[GRAD_OF[k]]).reshape(B, -1).sum(axis=1) for k in QP_KEYS)
@@ -153,7 +158,7 @@ def test_algebra_against_central_differences_of_the_assembly(cfg_name, model_nam
         worst = max(worst, (err / tol).max())
         assert (err <= tol).all(), "d_q[%d]: analytic %s, central difference %s, tolerance %s" % (k, res["d_q"][:, k], fd[1], tol)
     assert (res["d_q"][:, m.nv:] == 0).all() and np.abs(res["d_q"]).max() > 0
-    print("%s / %s: %d tangent coordinates x %d instances, worst |analytic - FD(h/2)| / tolerance %.3f" % (cfg_name, model_name, m.nv, B, worst))
+    print("%s / %s / dt %.7g: %d tangent coordinates x %d instances, worst |analytic - FD(h/2)| / tolerance %.3f" % (cfg_name, model_name, dt, m.nv, B, worst))
     if cfg.con_trunk:                                                    # linear in the centre: the computed bound alone
         c = np.asarray(d["trunk_box_center"], dtype=np.float64)
         for i in range(4):
