@@ -385,7 +385,8 @@ typedef struct WbcTickGrad {         /* all optional; an output left NULL is not
  * requested whose inputs the configuration does not read (d_ee_target without an EE task, d_trunk_target without the trunk task,
  * d_com_target without the CoM task, d_posture_u outside MANI / HYBRID / CUSTOM).
  * Gradients with respect to q and trunk_box_center come from wbc_tick_vjp_state below (it contracts what kinematic Hessians would hold with
- * x and u and never forms them). Not offered: ee_ref_rot / ee_prev_rot, trunk_ref_euler / trunk_prev_rot, and gradients through roll-outs.
+ * x and u and never forms them). Not offered: ee_ref_rot / ee_prev_rot, trunk_ref_euler / trunk_prev_rot. Gradients through roll-outs are offered as
+ * chained layers (this call, wbc_tick_vjp_state and wbc_step_vjp below, composed per tick: wbc_torch.wbc_rollout); a fused reverse sweep is not.
  * Statistic "last_grad_variant": the row of csrc/wbc_k_grad.hip's table the last call launched (key of ROT), -1 before the first. */
 int wbc_tick_vjp(WbcBatch* b, int B, const WbcTickIn* in, const WbcTaskParams* tp, double dt, const double* qdot, const double* sens_x,
                  const int32_t* status, const int32_t* cert_status, int mem, const WbcTickGrad* out, void* stream);
@@ -460,6 +461,46 @@ int wbc_integrate(WbcBatch* b, int B, const double* q, const double* v, const in
  * q_new may alias q_cur. */
 int wbc_update_state(WbcBatch* b, int B, const double* q_cur, const double* q_next, const double* imu,
                      const double* foot_targets, const int32_t* model_id, int mem, double* q_new, void* stream);
+
+/* ------------------------------------------------------------------ the state step as a layer: dL/d(q, qdot, foot targets)
+ * The link between tick k and tick k + 1:  q_next = wbc_integrate(q, qdot, dt),  q_new = wbc_update_state(q, q_next, imu, foot_targets)
+ * (mode WBC_ROLLOUT_WARMUP: q_new = q_next). For g = dL/d delta_new [B][26], the gradient of a loss in the tangent coordinates at q_new, one
+ * kernel launch (csrc/wbc_k_stepvjp.hip, four instances per wavefront) gives the gradient with respect to q (d_q, tangent
+ * coordinates at q), qdot and foot_targets. Tangent convention of wbc_tick_vjp_state: q (+) delta = wbc_integrate with dt = 1, base DoF in the
+ * base-local frame, linear before angular; columns >= the model's nv are 0.
+ * Update part (RUNNING). R_b: the rotation of the quaternion q_new carries (the IMU's if given, else q_next's); p_e (e = 0..3), p_t: the world
+ * positions of the foot frames and the trunk frame at [q xyz, that quaternion, the joints of q_next]; BPA = mean_e (p_e - p_t); rbar = R_b' BPA;
+ * Jbar = mean_e of the LOCAL_WORLD_ALIGNED linear rows of foot frame e. With g_p = g[0:3], g_phi = g[3:6], g_theta = g[6:]:
+ *   d_foot_targets[e] = R_b g_p / 4  (e = 0..3; row 4 = 0)
+ *   c_theta = g_theta - Jbar[:, 6:]' g_p
+ *   c_phi   = g_phi - BPA x g_p - rbar x (R_b' g_p)
+ *   c_p     = 0   (q's xyz cancels in the estimator; q_next's is not read)
+ * In WARMUP c = g and d_foot_targets = 0.
+ * Integrate part. xi = dt qdot[0:6], (Re, pe) = exp6(xi), c6 = (c_p, c_phi):
+ *   d_q[0:6]    = Ad' c6,  Ad = [[Re', -Re' [pe]x], [0, Re']]  (the adjoint of the inverse of exp6(xi))
+ *   d_qdot[0:6] = dt Jr(xi)' c6,  Jr the right Jacobian of SE(3) = sum_k (-ad_xi)^k / (k + 1)!
+ *   d_q[6:]     = c_theta,   d_qdot[6:] = dt c_theta
+ * HELD CONSTANT: the IMU quaternion (no d_imu is offered; with an IMU c_phi = 0).
+ * EXACT ZEROS: d_q[0:3] and d_qdot[0:3] in RUNNING; d_q[3:6] and d_qdot[3:6] with an IMU; row 4 of d_foot_targets; columns >= nv.
+ * The quaternion's sign continuity and first-order renormalisation do not appear in tangent coordinates. */
+typedef struct WbcStepGrad {          /* all optional */
+  double* d_q;                        /* [B][26] tangent coordinates at q_cur */
+  double* d_qdot;                     /* [B][26] */
+  double* d_foot_targets;             /* [B][5][3] */
+  int32_t* grad_status;               /* [B] WBC_GRAD_OK or WBC_GRAD_NONFINITE */
+} WbcStepGrad;
+/* q_cur [B][27], qdot [B][26], foot_targets [B][5][3], g_q_new [B][26] required; imu [B][4] or NULL; mode WBC_ROLLOUT_*. Host or device
+ * buffers. With device pointers the call enqueues exactly one kernel: no allocation, no memset, so it can be captured. An instance with a
+ * non-finite value among its model's own entries of q_cur, qdot or g_q_new, in the foot targets read (rows 0..3, RUNNING) or in its IMU row
+ * gets all-zero rows and WBC_GRAD_NONFINITE; nothing non-finite reaches another instance's rows; rows >= B are never written. dt: the rule of
+ * a forward step (dt > 0, dt and 1 / dt finite). WBC_E_ARG, naming the field: q_cur, qdot, foot_targets, g_q_new or out NULL; a mode other
+ * than WBC_ROLLOUT_RUNNING / WBC_ROLLOUT_WARMUP; model_id NULL with several models. WBC_E_UNSUPPORTED when a model does not fit the packed
+ * whole-tree schedule (as wbc_state_slack).
+ * Statistic "last_stepvjp_variant": the row of csrc/wbc_k_stepvjp.hip's table the last call launched (key of ROT), -1 before the first;
+ * wbc_variant_count("stepvjp") == 2. */
+int wbc_step_vjp(WbcBatch* b, int B, const double* q_cur, const double* qdot, const double* foot_targets, const double* imu,
+                 const int32_t* model_id, double dt, int mode, const double* g_q_new, int mem, const WbcStepGrad* out, void* stream);
+int wbc_step_grad_sizes(int32_t* sizeof_grad); /* ctypes layout self-check */
 
 /* K closed-loop ticks without leaving the device (the 2000 QPs of setInitialState for B robots in one
  * call with mode = WBC_ROLLOUT_WARMUP, ticks = hold_ticks = 1000): per tick wbc_tick -> wbc_update_state -> the

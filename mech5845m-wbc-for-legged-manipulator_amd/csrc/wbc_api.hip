@@ -12,6 +12,7 @@
 #include "wbc_cert.h"
 #include "wbc_grad.h"
 #include "wbc_gradq.h"
+#include "wbc_stepvjp.h"
 
 // (the layouts of the handle's roll-out workspaces d_roll, d_traj and d_slack: RollWs, TrajWs and SlackWs below)
 
@@ -94,6 +95,7 @@ struct WbcBatch {
   int last_qp_path;      // problems per wavefront of the last wbc_qp_solve / wbc_qp_solve_ls: 1 (wbc_qp_kernel), 2 or 4 (wbc_qp_packed_kernel)
   long long last_grad_variant;   // ... and of the last wbc_tick_vjp launch
   long long last_gradq_variant;  // ... and of the last wbc_tick_vjp_state launch
+  long long last_stepvjp_variant;   // ... and of the last wbc_step_vjp launch
   long long last_tick_variant, last_qp_variant;   // variant_key(...) of the row the last tick / assemble / fk launch and the last stand-alone QP launch resolved (-1: none yet)
   int sim3p_fixd;        // option [1]: the packed sim3 kernel's FIXD form where the handle qualifies (fixd_dims)
   bool fixd_dims[WBC_MAX_MODELS];   // wbc_batch_configure: the model's plan has exactly the SIM3P_FIXD_* dimensions
@@ -301,7 +303,7 @@ extern "C" int wbc_batch_create(const WbcModel* const* models, int n_models, int
   if (!b) return fail(WBC_E_ARG, "out of memory");
   memset(b, 0, sizeof *b);
   b->device_id = device_id; b->n_models = n_models; b->max_batch = max_batch; b->presolve = 1; b->presolve_orth = 1; b->packed_update = 1; b->sim3_kernel = 1; b->sing_tol = 1e-7; b->wave_order = 1; b->sim3p_fixd = 1;
-  b->last_tick_variant = b->last_qp_variant = b->last_grad_variant = b->last_gradq_variant = -1;
+  b->last_tick_variant = b->last_qp_variant = b->last_grad_variant = b->last_gradq_variant = b->last_stepvjp_variant = -1;
   b->jtj_mfma = -1; b->refine = 1; b->packed_min_batch = WBC_SIM3P_MIN_BATCH; b->warm_start = 0; b->packed_kernel = 1; b->packed_orth = 1; b->packed_box = 1; b->posture_par = 1;
   std::vector<DevModel> dm(n_models);
   for (int i = 0; i < n_models; ++i) {
@@ -808,6 +810,7 @@ extern "C" int wbc_batch_get_stat(WbcBatch* b, const char* name, void* stream, i
   if (!strcmp(name, "last_qp_variant")) { *out = b->last_qp_variant; return WBC_OK; }
   if (!strcmp(name, "last_grad_variant")) { *out = b->last_grad_variant; return WBC_OK; }
   if (!strcmp(name, "last_gradq_variant")) { *out = b->last_gradq_variant; return WBC_OK; }
+  if (!strcmp(name, "last_stepvjp_variant")) { *out = b->last_stepvjp_variant; return WBC_OK; }
   if (!strcmp(name, "last_update_packed")) { *out = b->last_update_packed; return WBC_OK; }
   if (!strcmp(name, "last_posture_par")) { *out = b->last_posture_par; return WBC_OK; }
   if (!strcmp(name, "last_orth")) { *out = (b->last_path == TICK_GENERAL || b->last_path == TICK_ORTHP) ? b->last_orth : 0; return WBC_OK; }
@@ -1865,6 +1868,48 @@ extern "C" int wbc_tick_state_grad_sizes(int32_t* sizeof_sens, int32_t* sizeof_g
   return WBC_OK;
 }
 
+// dL/d(q, qdot, foot_targets) of the state step between two ticks (include/wbc.h): argument checks, staging of host arrays, ONE launch of
+// wbc_stepvjp_kernel (csrc/wbc_k_stepvjp.hip). No memset; the kernel writes every row of every output it is given.
+static_assert(sizeof(WbcStepGrad) == 4 * sizeof(void*), "wbc_capi.WbcStepGrad");
+extern "C" int wbc_step_vjp(WbcBatch* b, int B, const double* q_cur, const double* qdot, const double* foot_targets, const double* imu,
+                            const int32_t* model_id, double dt, int mode, const double* g_q_new, int mem, const WbcStepGrad* out, void* stream) {
+  const char* who = "wbc_step_vjp";
+  int rc = check_batch(b, B, who, true);
+  if (rc) return rc;
+  if (!out) return fail(WBC_E_ARG, "%s: out is required", who);
+  if (!q_cur) return fail(WBC_E_ARG, "%s: q_cur is required", who);
+  if (!qdot) return fail(WBC_E_ARG, "%s: qdot is required", who);
+  if (!foot_targets) return fail(WBC_E_ARG, "%s: foot_targets is required", who);
+  if (!g_q_new) return fail(WBC_E_ARG, "%s: g_q_new is required", who);
+  if (mode != WBC_ROLLOUT_RUNNING && mode != WBC_ROLLOUT_WARMUP)
+    return fail(WBC_E_ARG, "%s: mode = %d, want WBC_ROLLOUT_RUNNING (%d) or WBC_ROLLOUT_WARMUP (%d)", who, mode, WBC_ROLLOUT_RUNNING, WBC_ROLLOUT_WARMUP);
+  if ((rc = check_dt(dt, who))) return rc;
+  if (b->n_models > 1 && !model_id) return fail(WBC_E_ARG, "%s: model_id is required with %d models", who, b->n_models);
+  for (int i = 0; i < b->n_models; ++i) {
+    if (b->plan_host[i].slack_ok) continue;
+    const DevModel& M = b->models[i]->dev;
+    return fail(WBC_E_UNSUPPORTED, "%s: model %d does not fit the packed whole-tree schedule (%d joints, at most 22; tree depth %d, at most 7; at most 16 joints at one depth)",
+                who, i, M.njoints, M.maxdepth);
+  }
+  HIP_TRY(hipSetDevice(b->device_id));
+  StepVjpArgs a;
+  memset(&a, 0, sizeof a);
+  a.models = b->d_models; a.plans = b->d_plans; a.B = B; a.n_models = b->n_models; a.rot = b->rot; a.mode = mode; a.dt = dt;
+  a.q_cur = q_cur; a.qdot = qdot; a.foot_targets = foot_targets; a.imu = imu; a.model_id = model_id; a.g = g_q_new; a.out = *out;
+  Stager st{b, mem, (hipStream_t)stream, {}};
+  const size_t n = (size_t)B;
+  st.in(&a.q_cur, n * WBC_Q_STRIDE); st.in(&a.qdot, n * WBC_V_STRIDE); st.in(&a.foot_targets, n * 15); st.in(&a.imu, n * 4);
+  st.in(&a.model_id, n); st.in(&a.g, n * WBC_V_STRIDE);
+  st.out(&a.out.d_q, n * WBC_V_STRIDE); st.out(&a.out.d_qdot, n * WBC_V_STRIDE); st.out(&a.out.d_foot_targets, n * 15); st.out(&a.out.grad_status, n);
+  if ((rc = st.stage())) return rc;
+  if ((rc = launch_rc(launch_stepvjp(a, stream, &b->last_stepvjp_variant), "state step gradient"))) return rc;
+  return st.finish();
+}
+extern "C" int wbc_step_grad_sizes(int32_t* sizeof_grad) {
+  if (sizeof_grad) *sizeof_grad = (int32_t)sizeof(WbcStepGrad);
+  return WBC_OK;
+}
+
 extern "C" int wbc_integrate(WbcBatch* b, int B, const double* q, const double* v, const int32_t* model_id, double dt, int mem,
                              double* q_next, void* stream) {
   int rc = check_batch(b, B, "wbc_integrate", false);
@@ -1913,6 +1958,7 @@ extern "C" int wbc_variant_count(const char* family) {
   if (!strcmp(family, "qp")) return qp_variant_count();
   if (!strcmp(family, "grad")) return grad_variant_count();
   if (!strcmp(family, "gradq")) return gradq_variant_count();
+  if (!strcmp(family, "stepvjp")) return stepvjp_variant_count();
   return fail(WBC_E_ARG, "wbc_variant_count: unknown kernel family %s", family);
 }
 extern "C" int wbc_abi_sizes(int32_t* sb, int32_t* sc) {

@@ -170,7 +170,7 @@ class WbcBatch:
     def stat(self, name, stream=None):
         """wbc_batch_get_stat: "last_path" (0 general, 1 compact sim3, 2 packed sim3, 3 packed orth — equality-only or INEQ variant —, 4 packed box), "last_orth", "last_posture_par",
         "last_update_packed", "last_qp_path" (problems per wavefront of the last stand-alone QP call: 1, 2 or 4), "last_tick_variant" /
-        "last_qp_variant" (the variant-table row of the last tick / assemble / fk and stand-alone QP launch: wbc_capi.variant_args), "last_grad_variant" / "last_gradq_variant" (the same for the last wbc_tick_vjp / wbc_tick_vjp_state launch), "last_tick_fixd" (1: the last tick ran the
+        "last_qp_variant" (the variant-table row of the last tick / assemble / fk and stand-alone QP launch: wbc_capi.variant_args), "last_grad_variant" / "last_gradq_variant" / "last_stepvjp_variant" (the same for the last wbc_tick_vjp / wbc_tick_vjp_state / wbc_step_vjp launch), "last_tick_fixd" (1: the last tick ran the
         packed sim3 kernel's FIXD form, option "sim3p_fixd"), "deferred_last", "pivoted_last", "wave_order_slices", "sim3_lds_bytes", "tick_lds_bytes", "orthp_lds_bytes"."""
         v = C.c_int64()
         capi.check(self.lib.wbc_batch_get_stat(self._h, name.encode(), stream, C.byref(v)), self.lib)
@@ -534,6 +534,36 @@ class WbcBatch:
                                               P(foot_targets, f, keep, B, 15, "foot_targets"), P(model_id, np.int32, keep, B, 1, "model_id"), mem,
                                               P(qn, f, keep), self._stream(mem)), self.lib)
         return qn
+
+    def step_vjp(self, q_cur, qdot, foot_targets, g, dt, imu=None, model_id=None, mode=capi.ROLLOUT_RUNNING, want=None, out=None):
+        """wbc_step_vjp (include/wbc.h): the state step between two ticks as a layer. For q_new = update_state(q_cur, integrate(q_cur, qdot, dt),
+        foot_targets, imu) (mode ROLLOUT_WARMUP: q_new = integrate(q_cur, qdot, dt)) and g [B,26] = dL/d delta_new in the tangent coordinates at
+        q_new: d_q [B,26] (tangent coordinates at q_cur; wbc_workload.tangent_to_raw for raw ones), d_qdot [B,26], d_foot_targets [B,5,3], one
+        kernel launch. want: names of capi.STEP_GRAD_FIELDS (None: all three); out: caller's arrays by those names (and "grad_status") instead.
+        The IMU quaternion is held constant. Returns dict(<want>..., grad_status [B] int32)."""
+        keep = []
+        B = self._batch_of(q_cur, "q_cur")
+        if out is None:
+            names = tuple(capi.STEP_GRAD_FIELDS) if want is None else tuple(want)
+            unknown = set(names) - set(capi.STEP_GRAD_FIELDS)
+            if unknown:
+                raise capi.WbcError("unknown gradients %s (known: %s)" % (sorted(unknown), ", ".join(capi.STEP_GRAD_FIELDS)))
+            out = {k: self._alloc(q_cur, (B,) + capi.STEP_GRAD_FIELDS[k]) for k in names}
+            out["grad_status"] = self._alloc(q_cur, (B,), np.int32)
+        mem = _mem_of([q_cur, qdot, foot_targets, g, imu, model_id] + list(out.values()))
+        o = capi.WbcStepGrad()
+        for k, a in out.items():
+            if k == "grad_status":
+                o.grad_status = self._p(a, np.int32, keep, B, 1, k)
+            elif k in capi.STEP_GRAD_FIELDS:
+                setattr(o, k, self._p(a, np.float64, keep, B, int(np.prod(capi.STEP_GRAD_FIELDS[k])), k))
+            else:
+                raise capi.WbcError("unknown output %r" % k)
+        f, P = np.float64, self._p
+        capi.check(self.lib.wbc_step_vjp(self._h, B, P(q_cur, f, keep), P(qdot, f, keep, B, NV, "qdot"), P(foot_targets, f, keep, B, 15, "foot_targets"),
+                                          P(imu, f, keep, B, 4, "imu"), P(model_id, np.int32, keep, B, 1, "model_id"), float(dt), int(mode),
+                                          P(g, f, keep, B, NV, "g"), mem, C.byref(o), self._stream(mem)), self.lib)
+        return out
 
     # ---- roll-outs: every entry point builds its outputs and its WbcRollout with _rollout_base and adds the structs of its own
     def _rollout_base(self, inputs, B, keep, ticks, mode, hold_ticks=0, ee_target_step=None, trunk_target_step=None, imu=None, want_trace=False):

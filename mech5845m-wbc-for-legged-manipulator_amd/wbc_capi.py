@@ -169,6 +169,14 @@ class WbcTickStateGrad(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in tuple(TICK_STATE_GRAD_FIELDS) + ("grad_status",)]
 
 
+# wbc_step_vjp: dL/d(q, qdot, foot targets) of the state step between two ticks (include/wbc.h)
+STEP_GRAD_FIELDS = dict(d_q=(V_STRIDE,), d_qdot=(V_STRIDE,), d_foot_targets=(5, 3))     # output name -> per-instance shape
+
+
+class WbcStepGrad(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in tuple(STEP_GRAD_FIELDS) + ("grad_status",)]
+
+
 class WbcFkOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("oMi", "oMf", "J", "com", "Jcom")]
 
@@ -206,6 +214,8 @@ SIGNATURES = {
     "wbc_tick_grad_sizes": (_i, [c_int32_p]),
     "wbc_tick_vjp_state": (_i, [_vp, _i, C.POINTER(WbcTickIn), _vp, _d, C.POINTER(WbcTickSens), _i, C.POINTER(WbcTickStateGrad), _vp]),
     "wbc_tick_state_grad_sizes": (_i, [c_int32_p, c_int32_p]),
+    "wbc_step_vjp": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _d, _i, _vp, _i, C.POINTER(WbcStepGrad), _vp]),
+    "wbc_step_grad_sizes": (_i, [c_int32_p]),
     "wbc_posture_target": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "wbc_tick": (_i, [_vp, _i, C.POINTER(WbcTickIn), _d, _i, C.POINTER(WbcTickOut), _vp]),
     "wbc_update_state": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
@@ -277,6 +287,9 @@ def load_library(path=None):
     if sb.value != C.sizeof(WbcTickSens) or sc.value != C.sizeof(WbcTickStateGrad):
         raise WbcError("ABI mismatch (WbcTickSens / WbcTickStateGrad): library (%d, %d) vs ctypes (%d, %d)" % (
             sb.value, sc.value, C.sizeof(WbcTickSens), C.sizeof(WbcTickStateGrad)))
+    lib.wbc_step_grad_sizes(C.byref(sb))
+    if sb.value != C.sizeof(WbcStepGrad):
+        raise WbcError("ABI mismatch (WbcStepGrad): library %d vs ctypes %d" % (sb.value, C.sizeof(WbcStepGrad)))
     if path is None:
         _lib = lib
     return lib

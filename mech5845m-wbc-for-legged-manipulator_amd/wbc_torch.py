@@ -17,6 +17,9 @@ backward is one certificate of the tick's own problem with v = grad_output follo
 ``qdot, status = wbc_tick_state(q, task_params, ee_target, ..., inputs, dt, batch)`` adds the state: the same forward with q a tensor argument;
 backward is one certificate, ``wbc_tick_vjp`` when a gradient other than q's is wanted, and ``wbc_tick_vjp_state``, whose tangent-coordinate
 d_q goes to raw coordinates through ``wbc_workload.tangent_to_raw``.
+
+``q_new = wbc_step(q, qdot, foot_targets, imu, dt, batch, mode)`` is the state step between two ticks (integrate, then the estimator) with
+``wbc_step_vjp`` behind it, and ``wbc_rollout(q0, task_params, ee_target, ..., inputs, dt, ticks, batch)`` chains K ticks out of the two layers.
 """
 import torch
 
@@ -188,3 +191,90 @@ def wbc_tick_state(q, task_params, ee_target, prev_ee_target, trunk_target, prev
     given) and the orientation references are held constant; inputs must not hold q_con. No gradient flows to anything else in `inputs`."""
     return _WbcTickState.apply(q, task_params, ee_target, prev_ee_target, trunk_target, prev_trunk_target, com_target, com_target_vel, posture_u,
                                inputs, dt, batch)
+
+
+class _WbcStep(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, qdot, foot_targets, imu, dt, batch, mode, model_id):
+        q, qdot, ft, imu = _c(q), _c(qdot), _c(foot_targets), _c(imu)
+        q_new = batch.integrate(q, qdot, dt, model_id=model_id)
+        if mode == capi.ROLLOUT_RUNNING:
+            q_new = batch.update_state(q, q_new, ft, imu=imu, model_id=model_id)
+        ctx.batch, ctx.dt, ctx.mode, ctx.model_id, ctx.have_imu = batch, dt, mode, model_id, imu is not None
+        ctx.save_for_backward(q, qdot, ft, q_new, *([imu] if imu is not None else []))
+        return q_new
+
+    @staticmethod
+    def backward(ctx, g_raw):
+        import wbc_workload
+        q, qdot, ft, q_new, *rest = ctx.saved_tensors
+        if g_raw is None:
+            return (None,) * 8
+        g = wbc_workload.raw_to_tangent(q_new, g_raw.contiguous())
+        s = ctx.batch.step_vjp(q, qdot, ft, g, ctx.dt, imu=rest[0] if ctx.have_imu else None, model_id=ctx.model_id, mode=ctx.mode)
+        need = ctx.needs_input_grad
+        return (wbc_workload.tangent_to_raw(q, s["d_q"]) if need[0] else None, s["d_qdot"] if need[1] else None,
+                s["d_foot_targets"].reshape(ft.shape) if need[2] else None, None, None, None, None, None)
+
+
+def wbc_step(q, qdot, foot_targets, imu, dt, batch, mode=capi.ROLLOUT_RUNNING, model_id=None):
+    """The state step between two ticks as a differentiable layer on `batch`: q_new [B,27] = update_state(q, integrate(q, qdot, dt), foot_targets,
+    imu) (mode ROLLOUT_WARMUP: integrate alone). Gradients flow to q (raw coordinates: the step composed with the normalisation of q's
+    quaternion), qdot and foot_targets [B,5,3]; backward is wbc_workload.raw_to_tangent at q_new, ONE wbc_step_vjp (include/wbc.h) and
+    wbc_workload.tangent_to_raw at q. imu ([B,4] or None) is held constant. Contiguous float64 tensors on the handle's device."""
+    return _WbcStep.apply(q, qdot, foot_targets, imu, dt, batch, mode, model_id)
+
+
+def _euler_xyz_to_R(e):
+    """[B, 9] row-major Rz(c) Ry(b) Rx(a) (wbc_workload._euler_xyz_to_R)"""
+    sa, ca, sb, cb, sc, cc = torch.sin(e[:, 0]), torch.cos(e[:, 0]), torch.sin(e[:, 1]), torch.cos(e[:, 1]), torch.sin(e[:, 2]), torch.cos(e[:, 2])
+    return torch.stack([cc * cb, cc * sb * sa - sc * ca, cc * sb * ca + sc * sa, sc * cb, sc * sb * sa + cc * ca, sc * sb * ca - cc * sa,
+                        -sb, cb * sa, cb * ca], dim=1)
+
+
+def wbc_rollout(q0, task_params, ee_target, prev_ee_target, trunk_target, prev_trunk_target, com_target, com_target_vel, posture_u, inputs, dt,
+                ticks, batch, ee_target_step=None, trunk_target_step=None, mode=capi.ROLLOUT_RUNNING, imu=None):
+    """`ticks` closed-loop ticks as chained differentiable layers, written in torch operations: per tick wbc_tick_state -> wbc_step, then the
+    reference-state side effects of the update kernel (prev_ee_target <- ee_target and ee_prev_rot <- ee_ref_rot for the end effectors whose
+    task is on; prev_trunk_target <- trunk_target and trunk_prev_rot <- R(trunk_ref_euler) with the trunk task on), then the targets advance
+    by their steps as a running sum, as the kernel does. The arguments are wbc_tick_state's (q0 for q; a target None is taken from `inputs` and
+    gets no gradient) plus the steps ([B,5,3] / [B,3] or None), the mode and the IMU quaternion ([B,4] or None, held constant). Gradients flow
+    to q0 and to whichever of the eight tensor arguments the configuration reads; ee_target also receives the estimator's d_foot_targets.
+    Returns (q_final [B,27], qdot of the last tick [B,26], status [B] int32 the worst over the ticks, states: per tick dict(q, qdot, status)).
+    An instance with an unsolved or uncertified tick gets zero gradient from that tick's layer on (wbc_tick_state's rule): what reaches q0
+    and the arguments from such an instance is what flows around that tick, through the step alone. This is the forward of WbcBatch.rollout
+    (no hold ticks) as separate launches; a fused reverse sweep is not offered.
+    On the sim3 switch set (c3) the cotangent that arrives from the next tick's state is no task-space direction (grad_common.task_space_v in
+    the tests says why): sens_x reaches 1e6, the chain's gradient is right to about 7 digits and cannot be held to tighter bounds."""
+    cfg = batch.cfgs[0]
+    on = [bool(cfg.task_ee[e]) for e in range(capi.NEE)]
+    d = dict(inputs)
+    pick = lambda t, name: d.get(name) if t is None else t      # noqa: E731
+    ee, pee = pick(ee_target, "ee_target"), pick(prev_ee_target, "prev_ee_target")
+    tt, ptt = pick(trunk_target, "trunk_target"), pick(prev_trunk_target, "prev_trunk_target")
+    for name in ("ee_target", "prev_ee_target", "trunk_target", "prev_trunk_target"):
+        d.pop(name, None)
+    read = lambda t, yes: t if (yes or t is None) else t.detach()      # noqa: E731  (an argument the configuration does not read gets no gradient)
+    on_t = torch.tensor(on, device=q0.device)[None, :, None]
+    mid = d.get("model_id")
+    q, status, states, qdot = q0, None, [], None
+    for _ in range(int(ticks)):
+        qdot, st = wbc_tick_state(q, task_params, read(ee, any(on)), read(pee, any(on)), read(tt, cfg.task_trunk), read(ptt, cfg.task_trunk),
+                                  com_target, com_target_vel, posture_u, d, dt, batch)
+        states.append(dict(q=q, qdot=qdot, status=st))
+        status = st if status is None else torch.maximum(status, st)
+        q = wbc_step(q, qdot, ee, imu, dt, batch, mode, mid)
+        if any(on):
+            pee = torch.where(on_t, ee.reshape(-1, capi.NEE, 3), pee.reshape(-1, capi.NEE, 3)).reshape(pee.shape) if pee is not None else None
+            if d.get("ee_ref_rot") is not None and d.get("ee_prev_rot") is not None:
+                d["ee_prev_rot"] = torch.where(on_t, d["ee_ref_rot"].reshape(-1, capi.NEE, 9), d["ee_prev_rot"].reshape(-1, capi.NEE, 9)).reshape(
+                    d["ee_prev_rot"].shape).contiguous()
+        if cfg.task_trunk:
+            ptt = tt if ptt is not None else None
+            if d.get("trunk_ref_euler") is not None and d.get("trunk_prev_rot") is not None:
+                d["trunk_prev_rot"] = _euler_xyz_to_R(d["trunk_ref_euler"].reshape(-1, 3)).reshape(d["trunk_prev_rot"].shape).contiguous()
+        if ee_target_step is not None:
+            ee = ee + ee_target_step.reshape(ee.shape)
+        if trunk_target_step is not None and tt is not None:
+            tt = tt + trunk_target_step.reshape(tt.shape)
+    return q, qdot, status, states

@@ -884,3 +884,114 @@ def tick_state_gradients(model, cfg, inputs, x, u, dt, fk, sens_bounds=None, sen
     dq[:, nv:] = 0.0
     out["d_q"] = dq
     return out
+
+
+# ---- the state step as a layer (wbc_step_vjp, include/wbc.h): integrate, then the estimator, in tangent coordinates
+def raw_to_tangent(q, c_raw):
+    """raw_tangent_map(q)' c_raw: the gradient [B, 26] in tangent coordinates at q of a loss whose gradient in raw coordinates is c_raw [B, 27].
+    With (x, y, z, w) = q[3:7] as it stands, R = R(x, y, z, w), c_p = c_raw[0:3], (c_v, c_w) = c_raw[3:7]:
+      linear  <- R' c_p
+      angular <- (w c_v + c_v x (x, y, z) - c_w (x, y, z)) / 2
+      joints  <- c_raw[7:]  (tangent index one lower)
+    numpy arrays or torch tensors; elementwise operations in one fixed order, so that both give the same bits (as tangent_to_raw)."""
+    if hasattr(q, "detach"):
+        import torch as xp
+        cat = lambda parts: xp.stack(parts, dim=1)      # noqa: E731
+    else:
+        xp = np
+        q, c_raw = np.asarray(q, dtype=np.float64).reshape(-1, capi.Q_STRIDE), np.asarray(c_raw, dtype=np.float64).reshape(-1, capi.Q_STRIDE)
+        cat = lambda parts: np.stack(parts, axis=1)     # noqa: E731
+    x, y, z, w = q[:, 3], q[:, 4], q[:, 5], q[:, 6]
+    p0, p1, p2, v0, v1, v2, cw = c_raw[:, 0], c_raw[:, 1], c_raw[:, 2], c_raw[:, 3], c_raw[:, 4], c_raw[:, 5], c_raw[:, 6]
+    cols = [(1 - 2 * (y * y + z * z)) * p0 + (2 * (x * y + z * w)) * p1 + (2 * (x * z - y * w)) * p2,
+            (2 * (x * y - z * w)) * p0 + (1 - 2 * (x * x + z * z)) * p1 + (2 * (y * z + x * w)) * p2,
+            (2 * (x * z + y * w)) * p0 + (2 * (y * z - x * w)) * p1 + (1 - 2 * (x * x + y * y)) * p2,
+            0.5 * (w * v0 + (v1 * z - v2 * y) - cw * x),
+            0.5 * (w * v1 + (v2 * x - v0 * z) - cw * y),
+            0.5 * (w * v2 + (v0 * y - v1 * x) - cw * z)]
+    return cat(cols + [c_raw[:, k] for k in range(7, capi.Q_STRIDE)])
+
+
+def _hat(v):
+    """[B, 3] -> the cross-product matrices [B, 3, 3]"""
+    o = np.zeros(len(v))
+    return np.stack([o, -v[:, 2], v[:, 1], v[:, 2], o, -v[:, 0], -v[:, 1], v[:, 0], o], axis=1).reshape(-1, 3, 3)
+
+
+def _series(X, first_div, sign):
+    """I + (sign X) / first_div + (sign X)^2 / (first_div (first_div + 1)) + ...: first_div = 1 the exponential, first_div = 2
+    sum_k (sign X)^k / (k + 1)!. The plain power series of [B, n, n] matrices, run until a term no longer changes the sum."""
+    n = X.shape[1]
+    term = np.broadcast_to(np.eye(n), X.shape).copy()
+    total = term.copy()
+    for k in range(1, 400):
+        term = sign * np.einsum("bij,bjk->bik", term, X) / (k + first_div - 1)
+        new = total + term
+        if (new == total).all():
+            break
+        total = new
+    return total
+
+
+def step_gradients(model, q_cur, qdot, foot_targets, dt, g, fk, imu=None, mode=capi.ROLLOUT_RUNNING):
+    """wbc_step_vjp restated for B instances of ONE model: the gradient of a loss on q_new = update_state(q_cur, integrate(q_cur, qdot dt),
+    foot_targets, imu) (mode ROLLOUT_WARMUP: q_new = integrate(q_cur, qdot dt)) from g = dL/d delta_new [B, 26], the tangent coordinates at
+    q_new, with respect to q_cur (tangent coordinates at q_cur), qdot and foot_targets. fk follows tick_state_gradients' convention (fk(q) ->
+    oMf, fk.joints(q) -> oMi, fk.jacobians(q) -> (J, Jcom)). The exponential and the right Jacobian of SE(3) are the plain power series of
+    the 4 x 4 twist matrix and of -ad_xi, run to convergence. The IMU quaternion is held constant.
+    Returns dict(d_q [B, 26], d_qdot [B, 26], d_foot_targets [B, 5, 3])."""
+    q = np.asarray(q_cur, dtype=np.float64).reshape(-1, capi.Q_STRIDE)
+    B, NVs, nv = q.shape[0], capi.V_STRIDE, model.nv
+    x = np.asarray(qdot, dtype=np.float64).reshape(B, NVs)
+    g = np.asarray(g, dtype=np.float64).reshape(B, NVs).copy()
+    g[:, nv:] = 0.0
+    xi = dt * x[:, 0:6]
+    W, V = _hat(xi[:, 3:6]), _hat(xi[:, 0:3])
+    X4 = np.zeros((B, 4, 4))
+    X4[:, 0:3, 0:3], X4[:, 0:3, 3] = W, xi[:, 0:3]
+    E4 = _series(X4, 1, 1.0)                                              # exp6(xi)
+    Re, pe = E4[:, 0:3, 0:3], E4[:, 0:3, 3]
+    c = g.copy()
+    dft = np.zeros((B, 5, 3))
+    if mode == capi.ROLLOUT_RUNNING:
+        # the configuration the estimator's kinematics run at: [q_cur xyz, the quaternion q_new carries, the joints of q_next]
+        cq = q.copy()
+        for jd in model.data["joints"][2:model.njoints]:
+            cq[:, jd["idx_q"]] = q[:, jd["idx_q"]] + dt * x[:, jd["idx_v"]]
+        if imu is not None:
+            cq[:, 3:7] = np.asarray(imu, dtype=np.float64).reshape(B, 4)
+        else:
+            Rn = np.einsum("bij,bjk->bik", _quat_to_R(q[:, 3:7]), Re)
+            cq[:, 3:7] = _R_to_quat(Rn.reshape(B, 9))
+        oMf, oMi = fk(cq), fk.joints(cq)
+        J, _ = fk.jacobians(cq)
+        Rb = oMi[:, 1, 0:9].reshape(B, 3, 3)
+        pt = oMf[:, capi.FR_TRUNK, 9:12]
+        BPA = sum(oMf[:, capi.FR_EE0 + e, 9:12] - pt for e in range(4)) / 4
+        rbar = np.einsum("bji,bj->bi", Rb, BPA)
+        Jbar = sum(frame_rows(model, J, oMf, capi.FR_EE0 + e, world=False)[:, 0:3] for e in range(4)) / 4
+        gp = g[:, 0:3]
+        dft[:, 0:4] = (np.einsum("bij,bj->bi", Rb, gp) / 4)[:, None, :]
+        c[:, 6:] = g[:, 6:] - np.einsum("bik,bi->bk", Jbar[:, :, 6:], gp)
+        if imu is None:
+            c[:, 3:6] = g[:, 3:6] - np.cross(BPA, gp) - np.cross(rbar, np.einsum("bji,bj->bi", Rb, gp))
+        else:
+            c[:, 3:6] = 0.0
+        c[:, 0:3] = 0.0
+    c[:, nv:] = 0.0
+    # ---- integrate: q_next = q (+) dt qdot
+    Ad = np.zeros((B, 6, 6))                                             # Ad of exp(-xi)
+    Ret = Re.transpose(0, 2, 1)
+    Ad[:, 0:3, 0:3] = Ad[:, 3:6, 3:6] = Ret
+    Ad[:, 0:3, 3:6] = -np.einsum("bij,bjk->bik", Ret, _hat(pe))
+    ad = np.zeros((B, 6, 6))
+    ad[:, 0:3, 0:3] = ad[:, 3:6, 3:6] = W
+    ad[:, 0:3, 3:6] = V
+    Jr = _series(ad, 2, -1.0)                                             # sum_k (-ad)^k / (k + 1)!
+    dq, dx = np.zeros((B, NVs)), np.zeros((B, NVs))
+    dq[:, 0:6] = np.einsum("bji,bj->bi", Ad, c[:, 0:6])
+    dx[:, 0:6] = dt * np.einsum("bji,bj->bi", Jr, c[:, 0:6])
+    dq[:, 6:], dx[:, 6:] = c[:, 6:], dt * c[:, 6:]
+    if mode == capi.ROLLOUT_RUNNING:
+        dq[:, 0:3] = dx[:, 0:3] = 0.0                                     # (c_p = 0: exactly)
+    return dict(d_q=dq, d_qdot=dx, d_foot_targets=dft)
