@@ -933,12 +933,34 @@ def _series(X, first_div, sign):
     return total
 
 
+def _exp_and_phi(X, want_phi):
+    """exp(X) and (want_phi) phi(X) = sum_k X^k / (k + 1)! of [B, n, n] matrices by scaling and doubling: X is halved s times, per instance,
+    until its largest absolute row sum is 1 or below; there the plain power series (_series) converge in some twenty terms, none larger than
+    the sum itself; then s times exp(2 x) = exp(x)^2 and phi(2 x) = (I + exp(x)) phi(x) / 2. (Summed as
+    they stand, the series of a twist of |omega| dt = 30 pass through terms of 1e11 on their way to a sum of order 1.) s = 0 leaves the plain
+    series as it was."""
+    B, n = X.shape[0], X.shape[1]
+    norm = np.abs(X).sum(axis=2).max(axis=1)
+    s = np.where(norm > 1.0, np.ceil(np.log2(np.maximum(norm, 1.0))), 0.0).astype(np.int64)
+    x = X / (2.0 ** s)[:, None, None]
+    E = _series(x, 1, 1.0)
+    P = _series(x, 2, 1.0) if want_phi else None
+    I = np.eye(n)
+    for j in range(int(s.max()) if B else 0):
+        on = s > j
+        if want_phi:
+            P[on] = 0.5 * np.einsum("bij,bjk->bik", I + E[on], P[on])
+        E[on] = np.einsum("bij,bjk->bik", E[on], E[on])
+    return E, P
+
+
 def step_gradients(model, q_cur, qdot, foot_targets, dt, g, fk, imu=None, mode=capi.ROLLOUT_RUNNING):
     """wbc_step_vjp restated for B instances of ONE model: the gradient of a loss on q_new = update_state(q_cur, integrate(q_cur, qdot dt),
     foot_targets, imu) (mode ROLLOUT_WARMUP: q_new = integrate(q_cur, qdot dt)) from g = dL/d delta_new [B, 26], the tangent coordinates at
     q_new, with respect to q_cur (tangent coordinates at q_cur), qdot and foot_targets. fk follows tick_state_gradients' convention (fk(q) ->
     oMf, fk.joints(q) -> oMi, fk.jacobians(q) -> (J, Jcom)). The exponential and the right Jacobian of SE(3) are the plain power series of
-    the 4 x 4 twist matrix and of -ad_xi, run to convergence. The IMU quaternion is held constant.
+    the 4 x 4 twist matrix and of -ad_xi, run to convergence on the argument halved until its norm is 1 or below, then doubled back
+    (_exp_and_phi): held to a 50-digit reference up to |omega| dt = 30 (tests/test_step_se3_host.py). The IMU quaternion is held constant.
     Returns dict(d_q [B, 26], d_qdot [B, 26], d_foot_targets [B, 5, 3])."""
     q = np.asarray(q_cur, dtype=np.float64).reshape(-1, capi.Q_STRIDE)
     B, NVs, nv = q.shape[0], capi.V_STRIDE, model.nv
@@ -949,7 +971,7 @@ def step_gradients(model, q_cur, qdot, foot_targets, dt, g, fk, imu=None, mode=c
     W, V = _hat(xi[:, 3:6]), _hat(xi[:, 0:3])
     X4 = np.zeros((B, 4, 4))
     X4[:, 0:3, 0:3], X4[:, 0:3, 3] = W, xi[:, 0:3]
-    E4 = _series(X4, 1, 1.0)                                              # exp6(xi)
+    E4, _ = _exp_and_phi(X4, False)                                       # exp6(xi)
     Re, pe = E4[:, 0:3, 0:3], E4[:, 0:3, 3]
     c = g.copy()
     dft = np.zeros((B, 5, 3))
@@ -987,7 +1009,7 @@ def step_gradients(model, q_cur, qdot, foot_targets, dt, g, fk, imu=None, mode=c
     ad = np.zeros((B, 6, 6))
     ad[:, 0:3, 0:3] = ad[:, 3:6, 3:6] = W
     ad[:, 0:3, 3:6] = V
-    Jr = _series(ad, 2, -1.0)                                             # sum_k (-ad)^k / (k + 1)!
+    _, Jr = _exp_and_phi(-ad, True)                                       # sum_k (-ad)^k / (k + 1)!
     dq, dx = np.zeros((B, NVs)), np.zeros((B, NVs))
     dq[:, 0:6] = np.einsum("bji,bj->bi", Ad, c[:, 0:6])
     dx[:, 0:6] = dt * np.einsum("bji,bj->bi", Jr, c[:, 0:6])

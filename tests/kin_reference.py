@@ -20,7 +20,7 @@ TRUNK = 5
 
 
 def _f(x):
-    return mp.mpf(float(x))
+    return x if isinstance(x, mp.mpf) else mp.mpf(float(x))      # (se3_reference.py feeds _tree values that are mpmath's already)
 
 
 def _mat(rows):
@@ -112,9 +112,9 @@ def role_frame_ids(data):
     return ids
 
 
-def _tree(data, q):
+def _tree(data, q, base_R=None):
     """world rotation R[j], origin p[j] of every joint, and per joint the list of (velocity column, kind, world axis): kind "rev" turns about the
-    axis through p[j], "lin" slides along it"""
+    axis through p[j], "lin" slides along it. base_R: the free-flyer's rotation as a 3 x 3 of mpmath values, in place of the quaternion's"""
     js = data["joints"]
     R, p, cols = [_eye()], [[mp.mpf(0)] * 3], [[]]
     for j in js[1:]:
@@ -123,7 +123,7 @@ def _tree(data, q):
         Rl, pl = _eye(), [mp.mpf(0)] * 3
         if kind == "FF":
             i = j["idx_q"]
-            Rl = _quat_matrix(*[_f(v) for v in q[i + 3:i + 7]])
+            Rl = _quat_matrix(*[_f(v) for v in q[i + 3:i + 7]]) if base_R is None else base_R
             pl = [_f(v) for v in q[i:i + 3]]
         else:
             e = [mp.mpf(int(k == "XYZ".index(kind[1]))) for k in range(3)]
