@@ -386,7 +386,8 @@ typedef struct WbcTickGrad {         /* all optional; an output left NULL is not
  * d_com_target without the CoM task, d_posture_u outside MANI / HYBRID / CUSTOM).
  * Gradients with respect to q and trunk_box_center come from wbc_tick_vjp_state below (it contracts what kinematic Hessians would hold with
  * x and u and never forms them). Not offered: ee_ref_rot / ee_prev_rot, trunk_ref_euler / trunk_prev_rot. Gradients through roll-outs are offered as
- * chained layers (this call, wbc_tick_vjp_state and wbc_step_vjp below, composed per tick: wbc_torch.wbc_rollout); a fused reverse sweep is not.
+ * chained layers (this call, wbc_tick_vjp_state and wbc_step_vjp below, composed per tick: wbc_torch.wbc_rollout) and as a fused reverse sweep
+ * over a recorded roll-out (wbc_rollout_record / wbc_rollout_vjp below).
  * Statistic "last_grad_variant": the row of csrc/wbc_k_grad.hip's table the last call launched (key of ROT), -1 before the first. */
 int wbc_tick_vjp(WbcBatch* b, int B, const WbcTickIn* in, const WbcTaskParams* tp, double dt, const double* qdot, const double* sens_x,
                  const int32_t* status, const int32_t* cert_status, int mem, const WbcTickGrad* out, void* stream);
@@ -538,6 +539,76 @@ int wbc_rollout(WbcBatch* b, int B, const WbcTickIn* in0, double dt, const WbcRo
 int wbc_tick_tp(WbcBatch* b, int B, const WbcTickIn* in, const WbcTaskParams* tp, double dt, int mem, const WbcTickOut* out, void* stream);
 int wbc_assemble_tp(WbcBatch* b, int B, const WbcTickIn* in, const WbcTaskParams* tp, double dt, int mem, const WbcQpData* out, void* stream);
 int wbc_rollout_tp(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r, int mem, void* stream);
+
+/* ------------------------------------------------------------------ roll-out gradients in two calls: recorded forward, device reverse sweep
+ * wbc_rollout_record is wbc_rollout_tp that also writes a TAPE; wbc_rollout_vjp sweeps the tape from the last tick to the first and gives
+ * dL/d(q_0, weights and gains, targets, target steps) of a loss seeded at q_K, at the last tick's qdot and / or at the state after every tick
+ * (DESIGN.md §3.42). The sweep composes, per tick and unchanged, the kernels of wbc_step_vjp, wbc_assemble_tp, wbc_qp_certificate (the
+ * (A, b) form), wbc_tick_vjp and wbc_tick_vjp_state above, plus one link kernel of its own (csrc/wbc_k_rollvjp.hip, four instances per
+ * wavefront) for the algebra between them. It is the reverse of the forward users run, not of a restatement of it.
+ * THE TAPE is device memory the caller owns (several may coexist; the handle keeps no pointer to one): wbc_rollout_tape_bytes(B, ticks) =
+ * 432 B + 736 B ticks bytes. Per instance and tick, 736 bytes: q_k [27], qdot_k [26], ee_target, prev_ee_target [5][3] each, trunk_target,
+ * prev_trunk_target [3] each as the tick SAW them (the running sums: never k * step), all doubles (89); the tick's status (int32, + one int32
+ * of padding); the tick's working set (2 x uint64: written under option "warm_start" alone — a cold tick returns none). Per instance, once, 432
+ * bytes: ee_prev_rot [5][9] and trunk_prev_rot [9] as every tick after the first saw them (tick 0 saw in0's). Blocks are strided by B.
+ * wbc_rollout_record: the arguments of wbc_rollout_tp, the tape, and q_trace [ticks][B][27] (optional, host or device as `mem` says): the
+ * state after every tick; q_trace[ticks - 1] is q_final. Every output is bit-identical to wbc_rollout_tp's on the same inputs and handle
+ * state: the ticks are launched exactly as wbc_rollout_tp launches them. WBC_E_ARG, naming the field, before any launch: hold_ticks > 0; q_con;
+ * posture mode MANI / HYBRID with posture_u NULL (wbc_tick_vjp_state's rule: the posture target would change per tick); tape NULL or
+ * tape_bytes too small. WBC_E_UNSUPPORTED: a model that does not fit the packed whole-tree schedule (as the layers). */
+size_t wbc_rollout_tape_bytes(int B, int ticks);
+int wbc_rollout_record(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r, void* tape,
+                       size_t tape_bytes, double* q_trace, int mem, void* stream);
+/* Seeds: cotangents in the tangent coordinates of wbc_tick_vjp_state (q (+) delta = wbc_integrate with dt = 1); at least one is required. */
+typedef struct WbcRolloutSeed {
+  const double* g_q_final;            /* [B][26] tangent at q_K                                                            */
+  const double* g_qdot_last;          /* [B][26] dL/d(qdot of the last tick)                                               */
+  const double* g_q_trace;            /* [ticks][B][26] tangent at the state after each tick (row ticks - 1 adds to g_q_final) */
+} WbcRolloutSeed;
+typedef struct WbcRolloutGrad {       /* all optional; an output left NULL is not written                                  */
+  double* d_q0;                       /* [B][26] tangent at q_0                                                            */
+  double* d_task_params;              /* [B][85] summed over the ticks, as the five below                                  */
+  double* d_ee_target;                /* [B][5][3] with respect to in0's ee_target                                         */
+  double* d_prev_ee_target;           /* [B][5][3] with respect to in0's prev_ee_target                                    */
+  double* d_trunk_target;             /* [B][3]                                                                            */
+  double* d_prev_trunk_target;        /* [B][3]                                                                            */
+  double* d_com_target;               /* [B][3]                                                                            */
+  double* d_com_target_vel;           /* [B][3]                                                                            */
+  double* d_posture_u;                /* [B][26]                                                                           */
+  double* d_trunk_box_center;         /* [B][4]                                                                            */
+  double* d_ee_target_step;           /* [B][5][3] with respect to WbcRollout.ee_target_step                               */
+  double* d_trunk_target_step;        /* [B][3]                                                                            */
+  int32_t* grad_status;               /* [B] the worst WBC_GRAD_* of any layer over the ticks                              */
+  int32_t* ticks_dropped;             /* [B] ticks whose tick layer gave zero for the instance                             */
+} WbcRolloutGrad;
+/* in0, tp, dt, r: what wbc_rollout_record was called with (r's outputs and steps are not read: the tape holds the targets; mode and imu are).
+ * Per tick k = K - 1 .. 0, everything on `stream`, no host round trip and no synchronisation (device buffers):
+ *   1. wbc_step_vjp's kernel at the taped (q_k, qdot_k, ee_target_k) with g = the carried cotangent of q_(k+1) (+ g_q_trace[k]; k = K - 1: g_q_final)
+ *   2. v = the step's d_qdot (k = K - 1: + g_qdot_last)
+ *   3. wbc_assemble_tp's kernel at the taped inputs (A, b, C, bounds; a model with nv < 26 gets unit rows on its padded columns behind A's task
+ *      rows, written on the device), then wbc_qp_certificate's kernel with v, the taped status and, under option "warm_start", the taped
+ *      working set (without: the active sides are read off qdot, wbc_qp_certificate's rule; the option must be what it was at the record)
+ *   4. wbc_tick_vjp's and wbc_tick_vjp_state's kernels from the certificate's outputs
+ *   5. the link kernel: g <- step.d_q + tickstate.d_q (both tangent at q_k: no raw coordinates anywhere in the sweep); the summed outputs +=
+ *      this tick's; the adjoint of the target bookkeeping.
+ * TARGET BOOKKEEPING. Forward, with s = ee_target_step: E_(k+1) = E_k + s, and P_(k+1) = E_k where the end effector's task is on, else P_k
+ * (E: ee_target, P: prev_ee_target). With Ebar, Pbar the cotangents of E_(k+1), P_(k+1) (both 0 behind the last tick), a_k = tick.d_ee_target
+ * + step.d_foot_targets and p_k = tick.d_prev_ee_target:
+ *     d_ee_target_step += Ebar;   Ebar <- Ebar + a_k + on o Pbar;   Pbar <- p_k + (1 - on) o Pbar
+ * and after tick 0 d_ee_target = Ebar, d_prev_ee_target = Pbar. The trunk pair follows the same rule under task_trunk (a_k = tick.d_trunk_target).
+ * HELD CONSTANT, as in the layers: the orientation references, the IMU quaternion, posture_u's own dependence on q.
+ * UNSOLVED TICKS: an instance whose tick k is unsolved, uncertified or non-finite gets zero from that tick's layer (wbc_tick_vjp's rule) and
+ * ticks_dropped += 1; what flows through the step alone continues. An instance with WBC_GRAD_NONFINITE from any layer gets all-zero rows.
+ * Nothing non-finite reaches another instance; rows >= B are never written. The workspaces live in the handle and grow on demand: once they
+ * have their size a call allocates nothing, and with device buffers both calls can be captured into a HIP graph.
+ * WBC_E_ARG, naming the field, before any launch: no seed; what wbc_rollout_record refuses; an output whose inputs the configuration does
+ * not read (the rules of wbc_tick_vjp and wbc_tick_vjp_state; d_*_target_step as d_*_target). WBC_E_UNSUPPORTED as wbc_rollout_record.
+ * Not offered: hold_ticks, the trajectory / tracks / watch roll-outs, checkpoint-and-recompute (the tape holds every tick).
+ * Statistic "last_rollvjp_variant": the row of csrc/wbc_k_rollvjp.hip's table the last call launched last (key of the stage: 0 BEGIN, 1 ADDV,
+ * 2 LINK), -1 before the first; wbc_variant_count("rollvjp") == 3. */
+int wbc_rollout_vjp(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r, const void* tape,
+                    size_t tape_bytes, const WbcRolloutSeed* seed, int mem, const WbcRolloutGrad* out, void* stream);
+int wbc_rollout_grad_sizes(int32_t* sizeof_seed, int32_t* sizeof_grad); /* ctypes layout self-check */
 
 /* ------------------------------------------------------------------ roll-outs along per-instance milestone trajectories, scored on device
  * The experiment of sim3.py as one call: the target of one end effector follows a piecewise-linear trajectory through the instance's own

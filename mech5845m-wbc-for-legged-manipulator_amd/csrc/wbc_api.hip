@@ -13,6 +13,7 @@
 #include "wbc_grad.h"
 #include "wbc_gradq.h"
 #include "wbc_stepvjp.h"
+#include "wbc_rollvjp.h"
 
 // (the layouts of the handle's roll-out workspaces d_roll, d_traj and d_slack: RollWs, TrajWs and SlackWs below)
 
@@ -96,6 +97,7 @@ struct WbcBatch {
   long long last_grad_variant;   // ... and of the last wbc_tick_vjp launch
   long long last_gradq_variant;  // ... and of the last wbc_tick_vjp_state launch
   long long last_stepvjp_variant;   // ... and of the last wbc_step_vjp launch
+  long long last_rollvjp_variant;   // ... and of the last link-kernel launch of wbc_rollout_vjp
   long long last_tick_variant, last_qp_variant;   // variant_key(...) of the row the last tick / assemble / fk launch and the last stand-alone QP launch resolved (-1: none yet)
   int sim3p_fixd;        // option [1]: the packed sim3 kernel's FIXD form where the handle qualifies (fixd_dims)
   bool fixd_dims[WBC_MAX_MODELS];   // wbc_batch_configure: the model's plan has exactly the SIM3P_FIXD_* dimensions
@@ -109,6 +111,8 @@ struct WbcBatch {
   void* d_traj;          // wbc_rollout_traj / wbc_rollout_tracks: per-instance scores of six frames, their positions of the tick, bad-row flags and their count (lazy)
   SlackLimits* d_slack_lim;   // wbc_state_slack / wbc_rollout_watch: the models' own joint ranges by DoF (lazy)
   void* d_slack;         // wbc_rollout_watch: per-instance accumulators of the four families for max_batch instances (lazy)
+  void* d_rvjp;          // wbc_rollout_vjp: one tick's QP image, certificate, layer outputs and the sweep's accumulators for max_batch instances (lazy, grown)
+  size_t rvjp_bytes;
 };
 
 // ---------------------------------------------------------------------------------------------- workspaces
@@ -190,6 +194,72 @@ size_t SlackWs::bytes(size_t NB) { return NB * (block_bytes(SLACK_D) + block_byt
 SlackWs SlackWs::carve(void* base, size_t NB) {
   SlackWs w;
   carve_blocks(w, carve_blocks(w, (char*)base, NB, SLACK_D), NB, SLACK_I);
+  return w;
+}
+
+// The tape of wbc_rollout_record (the CALLER's device memory; include/wbc.h states the layout): a head of the previous rotations every tick
+// after the first saw, then one TapeWs per tick. Unlike the handle's workspaces the blocks are strided by the call's B: the tape is sized by it.
+struct TapeHead {
+  double *ee_prev_rot, *trunk_prev_rot;
+  static TapeHead carve(void* tape, size_t B);
+};
+constexpr Block<TapeHead, double> TAPE_HEAD_D[] = {{&TapeHead::ee_prev_rot, 9 * WBC_NEE}, {&TapeHead::trunk_prev_rot, 9}};
+struct TapeWs {   // tick k: the state and the targets the tick saw, its answer, status and working set
+  double *q, *qdot, *ee_target, *prev_ee_target, *trunk_target, *prev_trunk_target;
+  int32_t *status, *pad;
+  unsigned long long* working_set;
+  static TapeWs carve(void* tape, size_t B, int k);
+};
+constexpr Block<TapeWs, double> TAPE_D[] = {{&TapeWs::q, WBC_Q_STRIDE}, {&TapeWs::qdot, WBC_V_STRIDE}, {&TapeWs::ee_target, 3 * WBC_NEE},
+    {&TapeWs::prev_ee_target, 3 * WBC_NEE}, {&TapeWs::trunk_target, 3}, {&TapeWs::prev_trunk_target, 3}};
+constexpr Block<TapeWs, int32_t> TAPE_I[] = {{&TapeWs::status, 1}, {&TapeWs::pad, 1}};
+constexpr Block<TapeWs, unsigned long long> TAPE_U[] = {{&TapeWs::working_set, 2}};
+constexpr size_t TAPE_HEAD_BYTES = block_bytes(TAPE_HEAD_D), TAPE_TICK_BYTES = block_bytes(TAPE_D) + block_bytes(TAPE_I) + block_bytes(TAPE_U);
+static_assert(TAPE_HEAD_BYTES == 432 && TAPE_TICK_BYTES == 736, "the tape: 432 bytes per instance, 736 bytes per instance and tick (include/wbc.h)");
+static_assert(block_bytes(TAPE_D) % 8 == 0 && block_bytes(TAPE_I) % 8 == 0, "the tape: the working sets begin at a multiple of 8 bytes for any B");
+TapeHead TapeHead::carve(void* tape, size_t B) {
+  TapeHead h;
+  carve_blocks(h, (char*)tape, B, TAPE_HEAD_D);
+  return h;
+}
+TapeWs TapeWs::carve(void* tape, size_t B, int k) {
+  TapeWs w;
+  carve_blocks(w, carve_blocks(w, carve_blocks(w, (char*)tape + B * (TAPE_HEAD_BYTES + (size_t)k * TAPE_TICK_BYTES), B, TAPE_D), B, TAPE_I), B, TAPE_U);
+  return w;
+}
+
+struct RollVjpWs {   // d_rvjp: wbc_rollout_vjp's workspace — one tick's QP image and certificate, the layers' outputs of the tick, the sweep's accumulators
+  double *lb, *ub, *v, *g, *s_dq, *s_dft, *sens_x, *sens_bounds, *t_dq, *t_box, *t_tp, *t_ee, *t_pee, *t_tt, *t_ptt, *t_com, *t_comv, *t_pu;
+  double *Ebar, *Pbar, *TEbar, *TPbar, *d_estep, *d_tstep, *acc_tp, *acc_com, *acc_comv, *acc_pu, *acc_box;
+  int32_t *cert_status, *gs_step, *gs_tick, *gs_tickq, *worst, *dropped;
+  double *A, *b, *C, *Clb, *Cub, *y_rows, *sens_rows;   // [NB][M][26], [NB][M], [NB][p][26], [NB][p] x 4: M = task rows + padding rows, p = constraint rows
+  static size_t bytes(size_t NB, size_t M, size_t p);
+  static RollVjpWs carve(void* base, size_t NB, size_t M, size_t p);
+};
+constexpr Block<RollVjpWs, double> RVJP_D[] = {{&RollVjpWs::lb, WBC_V_STRIDE}, {&RollVjpWs::ub, WBC_V_STRIDE}, {&RollVjpWs::v, WBC_V_STRIDE},
+    {&RollVjpWs::g, WBC_V_STRIDE}, {&RollVjpWs::s_dq, WBC_V_STRIDE}, {&RollVjpWs::s_dft, 3 * WBC_NEE}, {&RollVjpWs::sens_x, WBC_V_STRIDE},
+    {&RollVjpWs::sens_bounds, WBC_V_STRIDE}, {&RollVjpWs::t_dq, WBC_V_STRIDE}, {&RollVjpWs::t_box, 4}, {&RollVjpWs::t_tp, WBC_TASK_PARAMS_DOUBLES},
+    {&RollVjpWs::t_ee, 3 * WBC_NEE}, {&RollVjpWs::t_pee, 3 * WBC_NEE}, {&RollVjpWs::t_tt, 3}, {&RollVjpWs::t_ptt, 3}, {&RollVjpWs::t_com, 3},
+    {&RollVjpWs::t_comv, 3}, {&RollVjpWs::t_pu, WBC_V_STRIDE}, {&RollVjpWs::Ebar, 3 * WBC_NEE}, {&RollVjpWs::Pbar, 3 * WBC_NEE}, {&RollVjpWs::TEbar, 3},
+    {&RollVjpWs::TPbar, 3}, {&RollVjpWs::d_estep, 3 * WBC_NEE}, {&RollVjpWs::d_tstep, 3}, {&RollVjpWs::acc_tp, WBC_TASK_PARAMS_DOUBLES},
+    {&RollVjpWs::acc_com, 3}, {&RollVjpWs::acc_comv, 3}, {&RollVjpWs::acc_pu, WBC_V_STRIDE}, {&RollVjpWs::acc_box, 4}};
+constexpr Block<RollVjpWs, int32_t> RVJP_I[] = {{&RollVjpWs::cert_status, 1}, {&RollVjpWs::gs_step, 1}, {&RollVjpWs::gs_tick, 1}, {&RollVjpWs::gs_tickq, 1},
+    {&RollVjpWs::worst, 1}, {&RollVjpWs::dropped, 1}};
+static_assert(block_bytes(RVJP_D) == 555 * sizeof(double) && block_bytes(RVJP_I) == 6 * sizeof(int32_t), "d_rvjp: 555 doubles and 6 int32 per instance (+ the QP image)");
+static_assert(block_bytes(RVJP_I) % 8 == 0, "d_rvjp: the QP image begins at a multiple of 8 bytes for any max_batch");
+size_t RollVjpWs::bytes(size_t NB, size_t M, size_t p) {
+  return NB * (block_bytes(RVJP_D) + block_bytes(RVJP_I) + sizeof(double) * (M * (WBC_V_STRIDE + 1) + p * (WBC_V_STRIDE + 4)));
+}
+RollVjpWs RollVjpWs::carve(void* base, size_t NB, size_t M, size_t p) {
+  RollVjpWs w;
+  double* d = (double*)carve_blocks(w, carve_blocks(w, (char*)base, NB, RVJP_D), NB, RVJP_I);
+  w.A = d; d += NB * M * WBC_V_STRIDE;
+  w.b = d; d += NB * M;
+  w.C = d; d += NB * p * WBC_V_STRIDE;
+  w.Clb = d; d += NB * p;
+  w.Cub = d; d += NB * p;
+  w.y_rows = d; d += NB * p;
+  w.sens_rows = d;
   return w;
 }
 
@@ -303,7 +373,7 @@ extern "C" int wbc_batch_create(const WbcModel* const* models, int n_models, int
   if (!b) return fail(WBC_E_ARG, "out of memory");
   memset(b, 0, sizeof *b);
   b->device_id = device_id; b->n_models = n_models; b->max_batch = max_batch; b->presolve = 1; b->presolve_orth = 1; b->packed_update = 1; b->sim3_kernel = 1; b->sing_tol = 1e-7; b->wave_order = 1; b->sim3p_fixd = 1;
-  b->last_tick_variant = b->last_qp_variant = b->last_grad_variant = b->last_gradq_variant = b->last_stepvjp_variant = -1;
+  b->last_tick_variant = b->last_qp_variant = b->last_grad_variant = b->last_gradq_variant = b->last_stepvjp_variant = b->last_rollvjp_variant = -1;
   b->jtj_mfma = -1; b->refine = 1; b->packed_min_batch = WBC_SIM3P_MIN_BATCH; b->warm_start = 0; b->packed_kernel = 1; b->packed_orth = 1; b->packed_box = 1; b->posture_par = 1;
   std::vector<DevModel> dm(n_models);
   for (int i = 0; i < n_models; ++i) {
@@ -350,6 +420,7 @@ extern "C" void wbc_batch_destroy(WbcBatch* b) {
   if (b->d_traj) (void)hipFree(b->d_traj);
   if (b->d_slack_lim) (void)hipFree(b->d_slack_lim);
   if (b->d_slack) (void)hipFree(b->d_slack);
+  if (b->d_rvjp) (void)hipFree(b->d_rvjp);
   if (b->d_status) (void)hipFree(b->d_status);
   if (b->d_defer) (void)hipFree(b->d_defer);
   if (b->d_dstat) (void)hipFree(b->d_dstat);
@@ -811,6 +882,7 @@ extern "C" int wbc_batch_get_stat(WbcBatch* b, const char* name, void* stream, i
   if (!strcmp(name, "last_grad_variant")) { *out = b->last_grad_variant; return WBC_OK; }
   if (!strcmp(name, "last_gradq_variant")) { *out = b->last_gradq_variant; return WBC_OK; }
   if (!strcmp(name, "last_stepvjp_variant")) { *out = b->last_stepvjp_variant; return WBC_OK; }
+  if (!strcmp(name, "last_rollvjp_variant")) { *out = b->last_rollvjp_variant; return WBC_OK; }
   if (!strcmp(name, "last_update_packed")) { *out = b->last_update_packed; return WBC_OK; }
   if (!strcmp(name, "last_posture_par")) { *out = b->last_posture_par; return WBC_OK; }
   if (!strcmp(name, "last_orth")) { *out = (b->last_path == TICK_GENERAL || b->last_path == TICK_ORTHP) ? b->last_orth : 0; return WBC_OK; }
@@ -1459,10 +1531,53 @@ struct WatchExt {
   }
 };
 
-// K closed-loop ticks: the mutable controller state lives in the handle's rollout workspace; in0 is only read. Without extensions (tk, wx
+// The record (wbc_rollout_record, arguments checked by the entry point): one wbc_tape_copy_kernel per tick behind the update kernel. Tick k's
+// part of the tape holds what the tick saw — written by begin (k = 0) or behind tick k - 1's update — and what it answered. The loop is
+// wbc_rollout_tp's, launch for launch: the ticks return working sets under option "warm_start" and then the tape holds them; a cold
+// roll-out's ticks return none (asking for one selects other kernel variants, whose answers differ in the last bits: DESIGN.md §3.42), and
+// the sweep reads the active sides off qdot, as wbc_qp_certificate and wbc_tick_vjp_state do without a working set.
+struct RecordExt {
+  void* tape; double* q_trace;
+  RecordExt(void* t, double* qt) : tape(t), q_trace(qt) {}
+  void stage(Stager& st, size_t n, int ticks) { st.out(&q_trace, (size_t)ticks * n * WBC_Q_STRIDE); }
+  static void seg(TapeCopyArgs& c, const void* src, void* dst, size_t bytes_per_row) {
+    if (src && dst) c.seg[c.n_seg++] = TapeSeg{src, dst, (int32_t)(bytes_per_row / 4), 0};
+  }
+  static void seen(TapeCopyArgs& c, const RollWs& w, const TapeWs& t) {   // the state and the targets the next tick sees
+    const size_t d = sizeof(double);
+    seg(c, w.q, t.q, d * WBC_Q_STRIDE); seg(c, w.ee_target, t.ee_target, d * 3 * WBC_NEE); seg(c, w.prev_ee_target, t.prev_ee_target, d * 3 * WBC_NEE);
+    seg(c, w.trunk_target, t.trunk_target, d * 3); seg(c, w.prev_trunk_target, t.prev_trunk_target, d * 3);
+  }
+  int begin(Roll& R) {
+    TapeCopyArgs c{};
+    c.B = R.B;
+    seen(c, R.w, TapeWs::carve(tape, R.n, 0));
+    return launch_rc(launch_tape_copy(c, R.s), "tape");
+  }
+  int after_tick(Roll& R, int k) {
+    TapeCopyArgs c{};
+    c.B = R.B;
+    const TapeWs t = TapeWs::carve(tape, R.n, k);
+    seg(c, R.w.qdot, t.qdot, sizeof(double) * WBC_V_STRIDE); seg(c, R.w.status, t.status, sizeof(int32_t));
+    if (R.b->warm_start) seg(c, R.w.working_set, t.working_set, 2 * sizeof(unsigned long long));   // (a cold tick returns none)
+    if (q_trace) seg(c, R.w.q, q_trace + (size_t)k * R.n * WBC_Q_STRIDE, sizeof(double) * WBC_Q_STRIDE);
+    if (k + 1 < R.ticks) seen(c, R.w, TapeWs::carve(tape, R.n, k + 1));
+    return launch_rc(launch_tape_copy(c, R.s), "tape");
+  }
+  int gather(Roll& R) {   // the previous rotations every tick after the first saw: constant from the first update on
+    if (R.ticks < 2 || !(R.w.ee_prev_rot || R.w.trunk_prev_rot)) return WBC_OK;
+    TapeCopyArgs c{};
+    c.B = R.B;
+    const TapeHead h = TapeHead::carve(tape, R.n);
+    seg(c, R.w.ee_prev_rot, h.ee_prev_rot, sizeof(double) * 9 * WBC_NEE); seg(c, R.w.trunk_prev_rot, h.trunk_prev_rot, sizeof(double) * 9);
+    return launch_rc(launch_tape_copy(c, R.s), "tape");
+  }
+};
+
+// K closed-loop ticks: the mutable controller state lives in the handle's rollout workspace; in0 is only read. Without extensions (tk, wx, rx
 // NULL): one linear segment (WbcRollout.ee_target_step), the launches, memsets and copies of wbc_rollout_tp and nothing else.
 static int rollout_run(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r, int mem, void* stream,
-                       TracksExt* tk = nullptr, WatchExt* wx = nullptr) {
+                       TracksExt* tk = nullptr, WatchExt* wx = nullptr, RecordExt* rx = nullptr) {
   // check
   int rc = check_batch(b, B, "wbc_rollout", true);
   if (rc) return rc;
@@ -1498,6 +1613,7 @@ static int rollout_run(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskPa
   st.out(&ro.grip_trace, (size_t)R.total * n * 3); st.out(&ro.status_max, n); st.out(&ro.iters_sum, n);
   if (tk) tk->stage(st, n, R.ticks);
   if (wx) wx->stage(st, n, R.total);
+  if (rx) rx->stage(st, n, R.ticks);
   if ((rc = st.stage())) return rc;
   const size_t d = n * sizeof(double);   // seed the mutable state from in0
   if ((rc = give(s, w.q, a.in.q, d * WBC_Q_STRIDE)) || (rc = give(s, w.ee_target, a.in.ee_target, d * 3 * WBC_NEE)) ||
@@ -1523,7 +1639,7 @@ static int rollout_run(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskPa
   u.ee_step = ro.ee_target_step; u.trunk_step = ro.trunk_target_step;   // (a trajectory call has no ee_target_step: wbc_traj_tick_kernel moves those targets)
   u.status = w.status; u.iters = w.iters; u.status_max = ro.status_max; u.iters_sum = ro.iters_sum;
   // begin extensions
-  if ((tk && (rc = tk->begin(R))) || (wx && (rc = wx->begin(R)))) return rc;
+  if ((tk && (rc = tk->begin(R))) || (wx && (rc = wx->begin(R))) || (rx && (rc = rx->begin(R)))) return rc;
   const WbcTickIn loop_in = a.in;
   for (int k = 0; k < R.total; ++k) {
     if (k == R.ticks) { u.ee_step = nullptr; u.trunk_step = nullptr; }   // hold phase: the targets stay where they are
@@ -1532,10 +1648,10 @@ static int rollout_run(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskPa
     if ((rc = launch_tick_auto(b, a, B, stream, tp))) return rc;
     u.grip_trace = ro.grip_trace ? ro.grip_trace + (size_t)k * n * 3 : (tk ? tk->grip_row() : nullptr);
     if (int e = launch_update_auto(b, u, B, stream)) return fail(WBC_E_HIP, "update kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    if ((tk && (rc = tk->after_tick(R, k))) || (wx && (rc = wx->after_tick(R, k)))) return rc;
+    if ((tk && (rc = tk->after_tick(R, k))) || (wx && (rc = wx->after_tick(R, k))) || (rx && (rc = rx->after_tick(R, k)))) return rc;
   }
   // gather extensions, then the state
-  if ((wx && (rc = wx->gather(R))) || (tk && (rc = tk->gather(R)))) return rc;
+  if ((wx && (rc = wx->gather(R))) || (tk && (rc = tk->gather(R))) || (rx && (rc = rx->gather(R)))) return rc;
   if ((rc = give(s, ro.q_final, w.q, d * WBC_Q_STRIDE)) || (rc = give(s, ro.qdot_last, w.qdot, d * WBC_V_STRIDE)) ||
       (rc = give(s, ro.ee_target_final, w.ee_target, d * 3 * WBC_NEE)) ||
       (rc = give(s, tk ? tk->tj.trunk_target_final : nullptr, w.trunk_target, d * 3))) return rc;
@@ -1547,6 +1663,197 @@ extern "C" int wbc_rollout_tp(WbcBatch* b, int B, const WbcTickIn* in0, const Wb
 }
 extern "C" int wbc_rollout(WbcBatch* b, int B, const WbcTickIn* in0, double dt, const WbcRollout* r, int mem, void* stream) {
   return wbc_rollout_tp(b, B, in0, nullptr, dt, r, mem, stream);
+}
+
+// ---- Roll-out gradients in two calls (include/wbc.h): wbc_rollout_record is rollout_run with the RecordExt extension;
+// wbc_rollout_vjp walks the tape from the last tick to the first and launches, per tick, the layers' own kernels on the taped inputs
+// (wbc_stepvjp_kernel, the general kernel's assemble mode, wbc_qp_cert_kernel, wbc_grad_kernel, wbc_gradq_kernel) and the link kernel.
+static_assert(sizeof(WbcRolloutSeed) == 3 * sizeof(void*) && sizeof(WbcRolloutGrad) == 14 * sizeof(void*), "wbc_capi.WbcRolloutSeed / WbcRolloutGrad");
+extern "C" size_t wbc_rollout_tape_bytes(int B, int ticks) {
+  return (B < 1 || ticks < 1) ? 0 : (size_t)B * (TAPE_HEAD_BYTES + (size_t)ticks * TAPE_TICK_BYTES);
+}
+// what both calls refuse, before any launch
+static int check_record_call(WbcBatch* b, int B, const WbcTickIn* in0, const WbcRollout* r, const void* tape, size_t tape_bytes, const char* who) {
+  int rc = check_batch(b, B, who, true);
+  if (rc) return rc;
+  if (!r || r->ticks < 1) return fail(WBC_E_ARG, "%s: ticks >= 1 required", who);
+  if (r->hold_ticks != 0) return fail(WBC_E_ARG, "%s: hold_ticks = %d: a recorded roll-out has no hold phase", who, r->hold_ticks);
+  if (!in0) return fail(WBC_E_ARG, "%s: q is required", who);
+  if (in0->q_con) return fail(WBC_E_ARG, "%s: q_con is not supported (the constraints would see another configuration than the task rows)", who);
+  for (int i = 0; i < b->n_models; ++i) {
+    const int tj = b->cfg_host[i].task_joint;
+    if ((tj == WBC_JOINT_MANI || tj == WBC_JOINT_HYBRID) && !in0->posture_u)
+      return fail(WBC_E_ARG, "%s: posture mode MANI / HYBRID of model %d needs posture_u (it is held constant over the ticks)", who, i);
+  }
+  if (!tape) return fail(WBC_E_ARG, "%s: tape is required (device memory of wbc_rollout_tape_bytes(B, ticks) bytes)", who);
+  const size_t want = wbc_rollout_tape_bytes(B, r->ticks);
+  if (tape_bytes < want) return fail(WBC_E_ARG, "%s: tape_bytes = %zu, wbc_rollout_tape_bytes(%d, %d) = %zu", who, tape_bytes, B, r->ticks, want);
+  for (int i = 0; i < b->n_models; ++i) {
+    if (b->plan_host[i].slack_ok) continue;
+    const DevModel& M = b->models[i]->dev;
+    return fail(WBC_E_UNSUPPORTED, "%s: model %d does not fit the packed whole-tree schedule (%d joints, at most 22; tree depth %d, at most 7; at most 16 joints at one depth)",
+                who, i, M.njoints, M.maxdepth);
+  }
+  return WBC_OK;
+}
+extern "C" int wbc_rollout_record(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r, void* tape,
+                                  size_t tape_bytes, double* q_trace, int mem, void* stream) {
+  if (int rc = check_record_call(b, B, in0, r, tape, tape_bytes, "wbc_rollout_record")) return rc;
+  RecordExt rx(tape, q_trace);
+  return rollout_run(b, B, in0, tp, dt, r, mem, stream, nullptr, nullptr, &rx);
+}
+
+template <class T> static int ensure_size(T*& p, size_t& have, size_t want) {   // a workspace that grows with the configuration's row counts
+  if (want <= have) return WBC_OK;
+  if (p) HIP_TRY(hipFree(p));
+  p = nullptr; have = 0;
+  HIP_TRY(hipMalloc((void**)&p, want));
+  have = want;
+  return WBC_OK;
+}
+extern "C" int wbc_rollout_vjp(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r, const void* tape,
+                               size_t tape_bytes, const WbcRolloutSeed* seed, int mem, const WbcRolloutGrad* out, void* stream) {
+  const char* who = "wbc_rollout_vjp";
+  int rc = check_record_call(b, B, in0, r, tape, tape_bytes, who);
+  if (rc) return rc;
+  if (!out) return fail(WBC_E_ARG, "%s: out is required", who);
+  if (!seed || !(seed->g_q_final || seed->g_qdot_last || seed->g_q_trace))
+    return fail(WBC_E_ARG, "%s: a seed is required (g_q_final, g_qdot_last or g_q_trace)", who);
+  if ((rc = check_dt(dt, who))) return rc;
+  if (r->mode != WBC_ROLLOUT_RUNNING && r->mode != WBC_ROLLOUT_WARMUP)
+    return fail(WBC_E_ARG, "%s: mode = %d, want WBC_ROLLOUT_RUNNING (%d) or WBC_ROLLOUT_WARMUP (%d)", who, r->mode, WBC_ROLLOUT_RUNNING, WBC_ROLLOUT_WARMUP);
+  if ((rc = validate_tick_in(b, in0, who))) return rc;
+  if (!in0->ee_target || !in0->prev_ee_target) return fail(WBC_E_ARG, "%s: ee_target / prev_ee_target are required (the base estimator reads the foot targets)", who);
+  const WbcConfig& c = b->cfg_host[0];
+  bool any_ee = false;
+  uint32_t ee_on = 0;
+  for (int i = 0; i < WBC_NEE; ++i) if (c.task_ee[i]) { any_ee = true; ee_on |= 1u << i; }
+  const bool est = r->mode == WBC_ROLLOUT_RUNNING;   // the estimator reads ee_target: the step's d_foot_targets reaches it without an EE task
+  if (out->d_ee_target && !any_ee && !est) return fail(WBC_E_ARG, "%s: d_ee_target requested, but no EE task and no estimator reads ee_target", who);
+  if (out->d_ee_target_step && !any_ee && !est) return fail(WBC_E_ARG, "%s: d_ee_target_step requested, but no EE task and no estimator reads ee_target", who);
+  if (out->d_prev_ee_target && !any_ee) return fail(WBC_E_ARG, "%s: d_prev_ee_target requested, but no EE task reads prev_ee_target", who);
+  if (out->d_trunk_target && !c.task_trunk) return fail(WBC_E_ARG, "%s: d_trunk_target requested, but the trunk task is off", who);
+  if (out->d_prev_trunk_target && !c.task_trunk) return fail(WBC_E_ARG, "%s: d_prev_trunk_target requested, but the trunk task is off", who);
+  if (out->d_trunk_target_step && !c.task_trunk) return fail(WBC_E_ARG, "%s: d_trunk_target_step requested, but the trunk task is off", who);
+  if (out->d_com_target && !c.task_com) return fail(WBC_E_ARG, "%s: d_com_target requested, but the CoM task is off", who);
+  if (out->d_com_target_vel && !c.task_com) return fail(WBC_E_ARG, "%s: d_com_target_vel requested, but the CoM task is off", who);
+  bool reads_pu = true;
+  for (int i = 0; i < b->n_models; ++i) reads_pu = reads_pu && b->cfg_host[i].task_joint >= WBC_JOINT_MANI;
+  if (out->d_posture_u && !reads_pu) return fail(WBC_E_ARG, "%s: d_posture_u requested, but the posture mode of a model does not read posture_u", who);
+  if (out->d_trunk_box_center && !c.con_trunk) return fail(WBC_E_ARG, "%s: d_trunk_box_center requested, but the trunk constraint is off", who);
+  HIP_TRY(hipSetDevice(b->device_id));
+  // sizes: the task rows of wbc_assemble, the unit rows on the padded columns of the handle's smallest model, the constraint rows
+  int min_nv = WBC_V_STRIDE;
+  for (int i = 0; i < b->n_models; ++i) if (b->models[i]->dev.nv < min_nv) min_nv = b->models[i]->dev.nv;
+  const int m = b->mrows, pad_rows = WBC_V_STRIDE - min_nv, M = m + pad_rows, p = b->prows, K = r->ticks;
+  if (M > WBC_MAX_M) return fail(WBC_E_UNSUPPORTED, "%s: %d task rows + %d padding rows exceed the certificate's %d", who, m, pad_rows, WBC_MAX_M);
+  const size_t NB = (size_t)b->max_batch, n = (size_t)B;
+  if ((rc = ensure_size(b->d_rvjp, b->rvjp_bytes, RollVjpWs::bytes(NB, (size_t)M, (size_t)p)))) return rc;
+  const RollVjpWs w = RollVjpWs::carve(b->d_rvjp, NB, (size_t)M, (size_t)p);
+  // stage
+  KernelArgs a;
+  fill_args(a, b, B, dt);
+  a.in = *in0;
+  a.in.working_set = nullptr;
+  WbcRolloutSeed sd = *seed;
+  WbcRolloutGrad og = *out;
+  const double* imu = r->imu;
+  hipStream_t s = (hipStream_t)stream;
+  Stager st{b, mem, s, {}};
+  stage_tick_in(st, a.in, B, b);
+  st.in(&tp, n); st.in(&imu, n * 4);
+  st.in(&sd.g_q_final, n * WBC_V_STRIDE); st.in(&sd.g_qdot_last, n * WBC_V_STRIDE); st.in(&sd.g_q_trace, (size_t)K * n * WBC_V_STRIDE);
+  st.out(&og.d_q0, n * WBC_V_STRIDE); st.out(&og.d_task_params, n * WBC_TASK_PARAMS_DOUBLES); st.out(&og.d_ee_target, n * 15);
+  st.out(&og.d_prev_ee_target, n * 15); st.out(&og.d_trunk_target, n * 3); st.out(&og.d_prev_trunk_target, n * 3); st.out(&og.d_com_target, n * 3);
+  st.out(&og.d_com_target_vel, n * 3); st.out(&og.d_posture_u, n * WBC_V_STRIDE); st.out(&og.d_trunk_box_center, n * 4);
+  st.out(&og.d_ee_target_step, n * 15); st.out(&og.d_trunk_target_step, n * 3); st.out(&og.grad_status, n); st.out(&og.ticks_dropped, n);
+  if ((rc = st.stage())) return rc;
+  const WbcTickIn first = a.in;
+  const bool have_ws = b->warm_start != 0;   // the tape holds working sets (the option as it was when the tape was recorded: include/wbc.h)
+  void* const tp_mut = const_cast<void*>(tape);   // (read only: TapeWs carves non-const pointers)
+  const TapeHead head = TapeHead::carve(tp_mut, n);
+  // the tick gradient's kernel runs where one of its outputs is asked for (the state side runs on every tick: g needs it)
+  const bool want_tick = og.d_task_params || og.d_ee_target || og.d_prev_ee_target || og.d_trunk_target || og.d_prev_trunk_target || og.d_com_target ||
+                         og.d_com_target_vel || og.d_posture_u || og.d_ee_target_step || og.d_trunk_target_step;
+  RollVjpArgs L;
+  memset(&L, 0, sizeof L);
+  L.models = b->d_models; L.model_id = first.model_id; L.B = B; L.n_models = b->n_models; L.K = K; L.m = m; L.pad_rows = pad_rows;
+  L.ee_on = ee_on; L.trunk_on = c.task_trunk != 0;
+  L.g_q_final = sd.g_q_final; L.g_qdot_last = sd.g_qdot_last; L.g_q_trace = sd.g_q_trace;
+  L.A = w.A; L.b = w.b; L.g = w.g; L.v = w.v;
+  L.s_dq = w.s_dq; L.s_dft = est ? w.s_dft : nullptr; L.t_dq = w.t_dq; L.t_box = c.con_trunk ? w.t_box : nullptr;
+  if (want_tick) {
+    L.t.d_task_params = w.t_tp; L.t.grad_status = w.gs_tick;
+    if (any_ee) { L.t.d_ee_target = w.t_ee; L.t.d_prev_ee_target = w.t_pee; }
+    if (c.task_trunk) { L.t.d_trunk_target = w.t_tt; L.t.d_prev_trunk_target = w.t_ptt; }
+    if (c.task_com) { L.t.d_com_target = w.t_com; L.t.d_com_target_vel = w.t_comv; }
+    if (reads_pu) L.t.d_posture_u = w.t_pu;
+  }
+  L.gs_step = w.gs_step; L.gs_tickq = w.gs_tickq;
+  L.Ebar = w.Ebar; L.Pbar = w.Pbar; L.TEbar = w.TEbar; L.TPbar = w.TPbar; L.d_estep = w.d_estep; L.d_tstep = w.d_tstep; L.acc_tp = w.acc_tp;
+  L.acc_com = w.acc_com; L.acc_comv = w.acc_comv; L.acc_pu = w.acc_pu; L.acc_box = w.acc_box; L.worst = w.worst; L.dropped = w.dropped;
+  L.out = og;
+  L.k = K - 1;
+  if ((rc = launch_rc(launch_rollvjp(L, ROLLVJP_BEGIN, stream, &b->last_rollvjp_variant), "roll-out gradient link"))) return rc;
+  for (int k = K - 1; k >= 0; --k) {
+    const TapeWs T = TapeWs::carve(tp_mut, n, k);
+    WbcTickIn in = first;   // the inputs tick k saw
+    in.q = T.q; in.ee_target = T.ee_target; in.prev_ee_target = T.prev_ee_target;
+    if (first.trunk_target) in.trunk_target = T.trunk_target;
+    if (first.prev_trunk_target) in.prev_trunk_target = T.prev_trunk_target;
+    if (k > 0 && first.ee_prev_rot) in.ee_prev_rot = head.ee_prev_rot;
+    if (k > 0 && first.trunk_prev_rot) in.trunk_prev_rot = head.trunk_prev_rot;
+    // 1., 2. the step: g -> d_q, v = d_qdot, d_foot_targets
+    StepVjpArgs sa;
+    memset(&sa, 0, sizeof sa);
+    sa.models = b->d_models; sa.plans = b->d_plans; sa.B = B; sa.n_models = b->n_models; sa.rot = b->rot; sa.mode = r->mode; sa.dt = dt;
+    sa.q_cur = T.q; sa.qdot = T.qdot; sa.foot_targets = T.ee_target; sa.imu = imu; sa.model_id = first.model_id; sa.g = w.g;
+    sa.out.d_q = w.s_dq; sa.out.d_qdot = w.v; sa.out.d_foot_targets = w.s_dft; sa.out.grad_status = w.gs_step;
+    if ((rc = launch_rc(launch_stepvjp(sa, stream, &b->last_stepvjp_variant), "state step gradient"))) return rc;
+    if (k == K - 1 && sd.g_qdot_last && (rc = launch_rc(launch_rollvjp(L, ROLLVJP_ADDV, stream, &b->last_rollvjp_variant), "roll-out gradient link"))) return rc;
+    // 3. the tick's problem at the taped inputs (A's rows strided by M: the padding rows stay where BEGIN wrote them), its certificate with v
+    a.in = in;
+    a.mrows = M;
+    a.qp = WbcQpData{};
+    a.qp.A = w.A; a.qp.b = w.b; a.qp.lb = w.lb; a.qp.ub = w.ub;
+    if (p > 0) { a.qp.C = w.C; a.qp.Clb = w.Clb; a.qp.Cub = w.Cub; }
+    if ((rc = auto_posture(b, a, B, stream))) return rc;
+    if ((rc = launch_rc(launch_tick(a, MODE_ASSEMBLE, grid_tick(b, B), stream, tp, &b->last_tick_variant), "assemble"))) return rc;
+    CertArgs ca;
+    memset(&ca, 0, sizeof ca);
+    ca.B = B; ca.n = WBC_V_STRIDE; ca.p = p; ca.m = M;
+    ca.A = w.A; ca.bvec = w.b; ca.lb = w.lb; ca.ub = w.ub;
+    if (p > 0) { ca.C = w.C; ca.Clb = w.Clb; ca.Cub = w.Cub; ca.y_rows = w.y_rows; ca.sens_rows = w.sens_rows; }
+    ca.x = T.qdot; ca.v = w.v; ca.status = T.status; ca.ws = have_ws ? T.working_set : nullptr;
+    ca.sens_x = w.sens_x; ca.sens_bounds = w.sens_bounds; ca.cert_status = w.cert_status;
+    if ((rc = launch_rc(launch_cert(ca, grid_for(b, B), stream), "qp certificate"))) return rc;
+    // 4. the tick's two layers
+    if (want_tick) {
+      GradArgs ga;
+      memset(&ga, 0, sizeof ga);
+      ga.models = b->d_models; ga.cfgs = b->d_cfgs; ga.plans = b->d_plans; ga.B = B; ga.n_models = b->n_models; ga.rot = b->rot; ga.dt = dt;
+      ga.in = a.in; ga.tp = tp; ga.qdot = T.qdot; ga.sens_x = w.sens_x; ga.status = T.status; ga.cert_status = w.cert_status; ga.out = L.t;
+      if ((rc = launch_rc(launch_grad(ga, stream, &b->last_grad_variant), "tick gradient"))) return rc;
+    }
+    GradQArgs qa;
+    memset(&qa, 0, sizeof qa);
+    qa.models = b->d_models; qa.cfgs = b->d_cfgs; qa.plans = b->d_plans; qa.B = B; qa.n_models = b->n_models; qa.rot = b->rot; qa.dt = dt;
+    qa.in = in; qa.tp = tp;
+    qa.sens.qdot = T.qdot; qa.sens.sens_x = w.sens_x; qa.sens.sens_bounds = w.sens_bounds;
+    if (p > 0) { qa.sens.sens_rows = w.sens_rows; qa.sens.y_rows = w.y_rows; }
+    qa.sens.status = T.status; qa.sens.cert_status = w.cert_status; qa.sens.working_set = have_ws ? (const uint64_t*)T.working_set : nullptr;
+    qa.out.d_q = w.t_dq; qa.out.d_trunk_box_center = c.con_trunk ? w.t_box : nullptr; qa.out.grad_status = w.gs_tickq;
+    if ((rc = launch_rc(launch_gradq(qa, stream, &b->last_gradq_variant), "tick state gradient"))) return rc;
+    // 5. the link
+    L.k = k;
+    if ((rc = launch_rc(launch_rollvjp(L, ROLLVJP_LINK, stream, &b->last_rollvjp_variant), "roll-out gradient link"))) return rc;
+  }
+  return st.finish();
+}
+extern "C" int wbc_rollout_grad_sizes(int32_t* sizeof_seed, int32_t* sizeof_grad) {
+  if (sizeof_seed) *sizeof_seed = (int32_t)sizeof(WbcRolloutSeed);
+  if (sizeof_grad) *sizeof_grad = (int32_t)sizeof(WbcRolloutGrad);
+  return WBC_OK;
 }
 
 // ---- argument checks of the track calls. `who`: the entry point's name; `pre`: "" or "track J: " (the text of every message is the callers')
@@ -1959,6 +2266,7 @@ extern "C" int wbc_variant_count(const char* family) {
   if (!strcmp(family, "grad")) return grad_variant_count();
   if (!strcmp(family, "gradq")) return gradq_variant_count();
   if (!strcmp(family, "stepvjp")) return stepvjp_variant_count();
+  if (!strcmp(family, "rollvjp")) return rollvjp_variant_count();
   return fail(WBC_E_ARG, "wbc_variant_count: unknown kernel family %s", family);
 }
 extern "C" int wbc_abi_sizes(int32_t* sb, int32_t* sc) {

@@ -83,8 +83,36 @@ def _task_params(tp, B, keep, device_id):
     return arr.ctypes.data
 
 
+class RolloutTape:
+    """The tape of WbcBatch.rollout_record: `buf`, a torch uint8 tensor on the handle's device in the layout include/wbc.h states (a head of
+    432 bytes per instance, then 736 bytes per instance and tick, every block strided by B), and `call`, the arguments of the recorded call."""
+    _BLOCKS = (("q", np.float64, NQS), ("qdot", np.float64, NV), ("ee_target", np.float64, 15), ("prev_ee_target", np.float64, 15),
+               ("trunk_target", np.float64, 3), ("prev_trunk_target", np.float64, 3), ("status", np.int32, 1), ("pad", np.int32, 1),
+               ("working_set", np.int64, 2))
+
+    def __init__(self, buf, B, ticks):
+        self.buf, self.B, self.ticks, self.call = buf, int(B), int(ticks), None
+
+    def tick(self, k):
+        """-> dict of tick k's blocks as torch views into the tape: q [B,27], qdot [B,26], ee_target, prev_ee_target [B,15], trunk_target,
+        prev_trunk_target [B,3], status [B] int32, working_set [B,2] int64 (blocks of inputs the call did not have hold no data; the working
+        sets are recorded under option "warm_start" alone)"""
+        import torch
+        if not 0 <= k < self.ticks:
+            raise capi.WbcError("tick %d outside [0, %d)" % (k, self.ticks))
+        off = self.B * (capi.TAPE_HEAD_BYTES + k * capi.TAPE_TICK_BYTES)
+        out = {}
+        for name, dt, width in self._BLOCKS:
+            size = self.B * width * np.dtype(dt).itemsize
+            if name != "pad":
+                t = self.buf[off:off + size].view({np.float64: torch.float64, np.int32: torch.int32, np.int64: torch.int64}[dt])
+                out[name] = t.reshape(self.B) if width == 1 else t.reshape(self.B, width)
+            off += size
+        return out
+
+
 class WbcBatch:
-    allocator = None     # the output allocator hook (constructor argument / attribute); None: torch.empty / np.empty where the inputs live
+    allocator = None    # the output allocator hook (constructor argument / attribute); None: torch.empty / np.empty where the inputs live
 
     def __init__(self, models, max_batch, device_id=0, allocator=None):
         """allocator: a callable (like, shape, numpy dtype) -> array that replaces the default allocation of every output a wrapper
@@ -612,6 +640,97 @@ class WbcBatch:
         tp = _task_params(task_params, B, keep, self.device_id)
         capi.check(self.lib.wbc_rollout_tp(self._h, B, C.byref(tin), tp, float(dt), C.byref(r), mem, self._stream(mem)), self.lib)
         return out
+
+    def rollout_record(self, inputs, dt, ticks, ee_target_step=None, trunk_target_step=None, imu=None, mode=capi.ROLLOUT_RUNNING,
+                       task_params=None, want_trace=True, tape=None):
+        """wbc_rollout_record (include/wbc.h): rollout(..., want_trace=False) that also writes a tape for rollout_vjp. Returns (out, tape): out
+        is rollout's dict plus q_trace [K, B, 27] (the state after every tick; want_trace); tape is a RolloutTape — device memory of
+        wbc_rollout_tape_bytes(B, K) bytes (a torch uint8 tensor on the handle's device, allocated here or the caller's `tape.buf` when a
+        RolloutTape of the same B and K is passed back in) together with the call's arguments, which rollout_vjp needs again. The ticks run
+        exactly as rollout's do: under option "warm_start" they return working sets and the tape holds them. No hold ticks;
+        inputs must not hold q_con; posture modes MANI / HYBRID need inputs["posture_u"]."""
+        import torch
+        keep = []
+        mem = _mem_of(list(inputs.values()) + [ee_target_step, trunk_target_step, imu, task_params])
+        B = self._batch_of(inputs.get("q"))
+        K = int(ticks)
+        out, r = self._rollout_base(inputs, B, keep, K, mode, 0, ee_target_step, trunk_target_step, imu, False)
+        if want_trace and K >= 1:
+            out["q_trace"] = self._alloc(inputs["q"], (K, B, NQS))
+        nbytes = int(self.lib.wbc_rollout_tape_bytes(B, K))
+        if tape is None or tape.B != B or tape.ticks != K:
+            tape = RolloutTape(torch.empty(max(nbytes, 1), dtype=torch.uint8, device="cuda:%d" % self.device_id), B, K)
+        tape.call = dict(inputs=dict(inputs), dt=float(dt), imu=imu, mode=int(mode), task_params=task_params,
+                         warm_start=getattr(self, "_options", {}).get("warm_start", 0))
+        tin = self._tick_in(inputs, keep, B)
+        tp = _task_params(task_params, B, keep, self.device_id)
+        capi.check(self.lib.wbc_rollout_record(self._h, B, C.byref(tin), tp, float(dt), C.byref(r), tape.buf.data_ptr(), nbytes,
+                                                self._p(out.get("q_trace"), np.float64, keep), mem, self._stream(mem)), self.lib)
+        return out, tape
+
+    def rollout_vjp(self, tape, g_q_final=None, g_qdot_last=None, g_q_trace=None, want=None, out=None):
+        """wbc_rollout_vjp (include/wbc.h): the reverse sweep over a recorded roll-out, everything on the device. tape: rollout_record's.
+        Seeds (numpy or torch, at least one; tangent coordinates — wbc_workload.raw_to_tangent turns a raw gradient into one): g_q_final
+        [B,26] at q_K, g_qdot_last [B,26], g_q_trace [K,B,26] at the state after each tick. want: names of capi.ROLLOUT_GRAD_FIELDS (None:
+        d_q0 and what the configuration reads); out: caller's arrays by those names (and "grad_status", "ticks_dropped") instead.
+        Returns dict(<want>..., grad_status [B] int32, ticks_dropped [B] int32); d_q0 is tangent at q_0 (wbc_workload.tangent_to_raw)."""
+        keep = []
+        c = tape.call
+        inputs, B, K = c["inputs"], tape.B, tape.ticks
+        if getattr(self, "_options", {}).get("warm_start", 0) != c["warm_start"]:
+            raise capi.WbcError("rollout_vjp: option warm_start changed since the tape was recorded (the tape holds working sets only with it)")
+        like = next((a for a in (g_q_final, g_qdot_last, g_q_trace) if a is not None), inputs["q"])
+        if out is None:
+            names = self.default_rollout_grad_wants(c["mode"]) if want is None else tuple(want)
+            unknown = set(names) - set(capi.ROLLOUT_GRAD_FIELDS)
+            if unknown:
+                raise capi.WbcError("unknown gradients %s (known: %s)" % (sorted(unknown), ", ".join(capi.ROLLOUT_GRAD_FIELDS)))
+            out = {k: self._alloc(like, (B,) + capi.ROLLOUT_GRAD_FIELDS[k]) for k in names}
+            out["grad_status"] = self._alloc(like, (B,), np.int32)
+            out["ticks_dropped"] = self._alloc(like, (B,), np.int32)
+        mem = _mem_of(list(inputs.values()) + list(out.values()) + [c["imu"], c["task_params"], g_q_final, g_qdot_last, g_q_trace])
+        o = capi.WbcRolloutGrad()
+        for k, a in out.items():
+            if k in ("grad_status", "ticks_dropped"):
+                setattr(o, k, self._p(a, np.int32, keep, B, 1, k))
+            elif k in capi.ROLLOUT_GRAD_FIELDS:
+                setattr(o, k, self._p(a, np.float64, keep, B, int(np.prod(capi.ROLLOUT_GRAD_FIELDS[k])), k))
+            else:
+                raise capi.WbcError("unknown output %r" % k)
+        f, P = np.float64, self._p
+        sd = capi.WbcRolloutSeed()
+        sd.g_q_final, sd.g_qdot_last = P(g_q_final, f, keep, B, NV, "g_q_final"), P(g_qdot_last, f, keep, B, NV, "g_qdot_last")
+        if g_q_trace is not None:
+            if tuple(g_q_trace.shape) != (K, B, NV):
+                raise capi.WbcError("g_q_trace: shape %s, want (%d, %d, %d)" % (tuple(g_q_trace.shape), K, B, NV))
+            sd.g_q_trace = P(g_q_trace, f, keep)
+        r = capi.WbcRollout()
+        r.ticks, r.mode, r.hold_ticks = K, c["mode"], 0
+        r.imu = P(c["imu"], f, keep, B, 4, "imu")
+        tin = self._tick_in(inputs, keep, B)
+        tp = _task_params(c["task_params"], B, keep, self.device_id)
+        capi.check(self.lib.wbc_rollout_vjp(self._h, B, C.byref(tin), tp, c["dt"], C.byref(r), tape.buf.data_ptr(), tape.buf.numel(),
+                                             C.byref(sd), mem, C.byref(o), self._stream(mem)), self.lib)
+        return out
+
+    def default_rollout_grad_wants(self, mode=capi.ROLLOUT_RUNNING):
+        """the gradients wbc_rollout_vjp offers under the handle's configuration (names of capi.ROLLOUT_GRAD_FIELDS)"""
+        c = self.cfgs[0]
+        want = ["d_q0", "d_task_params"]
+        any_ee = any(c.task_ee[e] for e in range(capi.NEE))
+        if any_ee or mode == capi.ROLLOUT_RUNNING:
+            want += ["d_ee_target", "d_ee_target_step"]
+        if any_ee:
+            want += ["d_prev_ee_target"]
+        if c.task_trunk:
+            want += ["d_trunk_target", "d_prev_trunk_target", "d_trunk_target_step"]
+        if c.task_com:
+            want += ["d_com_target", "d_com_target_vel"]
+        if all(cf is not None and cf.task_joint >= capi.JOINT_MANI for cf in self.cfgs):
+            want += ["d_posture_u"]
+        if c.con_trunk:
+            want += ["d_trunk_box_center"]
+        return tuple(want)
 
     _SUMMARY = (("err_sq_sum", np.float64), ("err_max", np.float64), ("err_max_tick", np.int32), ("err_final", np.float64),
                 ("first_bad_tick", np.int32), ("bad_ticks", np.int32))

@@ -177,6 +177,22 @@ class WbcStepGrad(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in tuple(STEP_GRAD_FIELDS) + ("grad_status",)]
 
 
+# wbc_rollout_record / wbc_rollout_vjp: the reverse sweep over a recorded roll-out (include/wbc.h)
+ROLLOUT_SEED_FIELDS = ("g_q_final", "g_qdot_last", "g_q_trace")
+ROLLOUT_GRAD_FIELDS = dict(d_q0=(V_STRIDE,), d_task_params=(85,), d_ee_target=(NEE, 3), d_prev_ee_target=(NEE, 3), d_trunk_target=(3,),
+                           d_prev_trunk_target=(3,), d_com_target=(3,), d_com_target_vel=(3,), d_posture_u=(V_STRIDE,), d_trunk_box_center=(4,),
+                           d_ee_target_step=(NEE, 3), d_trunk_target_step=(3,))     # output name -> per-instance shape
+TAPE_HEAD_BYTES, TAPE_TICK_BYTES = 432, 736     # per instance; per instance and tick (wbc_rollout_tape_bytes)
+
+
+class WbcRolloutSeed(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ROLLOUT_SEED_FIELDS]
+
+
+class WbcRolloutGrad(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in tuple(ROLLOUT_GRAD_FIELDS) + ("grad_status", "ticks_dropped")]
+
+
 class WbcFkOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("oMi", "oMf", "J", "com", "Jcom")]
 
@@ -223,6 +239,11 @@ SIGNATURES = {
     "wbc_tick_tp": (_i, [_vp, _i, C.POINTER(WbcTickIn), _vp, _d, _i, C.POINTER(WbcTickOut), _vp]),
     "wbc_assemble_tp": (_i, [_vp, _i, C.POINTER(WbcTickIn), _vp, _d, _i, C.POINTER(WbcQpData), _vp]),
     "wbc_rollout_tp": (_i, [_vp, _i, C.POINTER(WbcTickIn), _vp, _d, C.POINTER(WbcRollout), _i, _vp]),
+    "wbc_rollout_tape_bytes": (C.c_size_t, [_i, _i]),
+    "wbc_rollout_record": (_i, [_vp, _i, C.POINTER(WbcTickIn), _vp, _d, C.POINTER(WbcRollout), _vp, C.c_size_t, _vp, _i, _vp]),
+    "wbc_rollout_vjp": (_i, [_vp, _i, C.POINTER(WbcTickIn), _vp, _d, C.POINTER(WbcRollout), _vp, C.c_size_t, C.POINTER(WbcRolloutSeed), _i,
+                             C.POINTER(WbcRolloutGrad), _vp]),
+    "wbc_rollout_grad_sizes": (_i, [c_int32_p, c_int32_p]),
     "wbc_rollout_traj": (_i, [_vp, _i, C.POINTER(WbcTickIn), _vp, _d, C.POINTER(WbcRollout), C.POINTER(WbcTrajectory),
                               C.POINTER(WbcRolloutSummary), _i, _vp]),
     "wbc_rollout_tracks": (_i, [_vp, _i, C.POINTER(WbcTickIn), _vp, _d, C.POINTER(WbcRollout), C.POINTER(WbcTracks),
@@ -290,6 +311,10 @@ def load_library(path=None):
     lib.wbc_step_grad_sizes(C.byref(sb))
     if sb.value != C.sizeof(WbcStepGrad):
         raise WbcError("ABI mismatch (WbcStepGrad): library %d vs ctypes %d" % (sb.value, C.sizeof(WbcStepGrad)))
+    lib.wbc_rollout_grad_sizes(C.byref(sb), C.byref(sc))
+    if sb.value != C.sizeof(WbcRolloutSeed) or sc.value != C.sizeof(WbcRolloutGrad):
+        raise WbcError("ABI mismatch (WbcRolloutSeed / WbcRolloutGrad): library (%d, %d) vs ctypes (%d, %d)" % (
+            sb.value, sc.value, C.sizeof(WbcRolloutSeed), C.sizeof(WbcRolloutGrad)))
     if path is None:
         _lib = lib
     return lib

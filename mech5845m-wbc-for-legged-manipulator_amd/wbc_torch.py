@@ -20,6 +20,7 @@ d_q goes to raw coordinates through ``wbc_workload.tangent_to_raw``.
 
 ``q_new = wbc_step(q, qdot, foot_targets, imu, dt, batch, mode)`` is the state step between two ticks (integrate, then the estimator) with
 ``wbc_step_vjp`` behind it, and ``wbc_rollout(q0, task_params, ee_target, ..., inputs, dt, ticks, batch)`` chains K ticks out of the two layers.
+``wbc_rollout_fused`` takes the same arguments and is one layer: forward ``wbc_rollout_record``, backward ``wbc_rollout_vjp``.
 """
 import torch
 
@@ -243,7 +244,7 @@ def wbc_rollout(q0, task_params, ee_target, prev_ee_target, trunk_target, prev_t
     Returns (q_final [B,27], qdot of the last tick [B,26], status [B] int32 the worst over the ticks, states: per tick dict(q, qdot, status)).
     An instance with an unsolved or uncertified tick gets zero gradient from that tick's layer on (wbc_tick_state's rule): what reaches q0
     and the arguments from such an instance is what flows around that tick, through the step alone. This is the forward of WbcBatch.rollout
-    (no hold ticks) as separate launches; a fused reverse sweep is not offered.
+    (no hold ticks) as separate launches; wbc_rollout_fused below is the same layer over the recorded roll-out and the device's reverse sweep.
     On the sim3 switch set (c3) the cotangent that arrives from the next tick's state is no task-space direction (grad_common.task_space_v in
     the tests says why): sens_x reaches 1e6, the chain's gradient is right to about 7 digits and cannot be held to tighter bounds."""
     cfg = batch.cfgs[0]
@@ -278,3 +279,83 @@ def wbc_rollout(q0, task_params, ee_target, prev_ee_target, trunk_target, prev_t
         if trunk_target_step is not None and tt is not None:
             tt = tt + trunk_target_step.reshape(tt.shape)
     return q, qdot, status, states
+
+
+_FUSED_ARGS = ("q0",) + _TICK_ARGS + ("ee_target_step", "trunk_target_step")
+
+
+class _WbcRolloutFused(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q0, task_params, ee_target, prev_ee_target, trunk_target, prev_trunk_target, com_target, com_target_vel, posture_u,
+                ee_target_step, trunk_target_step, inputs, dt, ticks, batch, mode, imu):
+        args = [_c(t) for t in (q0, task_params, ee_target, prev_ee_target, trunk_target, prev_trunk_target, com_target, com_target_vel, posture_u,
+                                ee_target_step, trunk_target_step)]
+        d = dict(inputs)
+        d["q"] = args[0]
+        for name, a in zip(_TICK_ARGS[1:], args[2:9]):
+            if a is not None:
+                d[name] = a
+        es = None if args[9] is None else args[9].reshape(-1, capi.NEE, 3)
+        out, tape = batch.rollout_record(d, dt, ticks, ee_target_step=es, trunk_target_step=args[10], imu=_c(imu), mode=mode, task_params=args[1])
+        ctx.batch, ctx.tape = batch, tape
+        ctx.present = [a is not None for a in args]
+        # through save_for_backward: an in-place change of an argument between forward and backward is an autograd error, not a sweep over other data
+        ctx.save_for_backward(out["q"], out["q_trace"], *[a for a in args if a is not None])
+        ctx.mark_non_differentiable(out["status"])
+        return out["q"], out["qdot"], out["status"], out["q_trace"]
+
+    @staticmethod
+    def backward(ctx, g_q, g_qdot, _gst, g_trace):
+        import wbc_workload
+        q_final, q_trace, *given = ctx.saved_tensors
+        n_out = len(_FUSED_ARGS) + 6
+        if g_q is None and g_qdot is None and g_trace is None:
+            return (None,) * n_out
+        it = iter(given)
+        args = [next(it) if have else None for have in ctx.present]
+        need = ctx.needs_input_grad
+        bt, tape = ctx.batch, ctx.tape
+        K, B = tape.ticks, tape.B
+        offered = set(bt.default_rollout_grad_wants(tape.call["mode"]))
+        names = ("d_q0", "d_task_params", "d_ee_target", "d_prev_ee_target", "d_trunk_target", "d_prev_trunk_target", "d_com_target",
+                 "d_com_target_vel", "d_posture_u", "d_ee_target_step", "d_trunk_target_step")
+        want = tuple(n for k, n in enumerate(names) if need[k] and args[k] is not None and n in offered)
+        if not want:
+            return (None,) * n_out
+        # the seeds: raw -> tangent coordinates, q_K's and the trace's in one call
+        raw, at = [], []
+        if g_q is not None:
+            raw.append(g_q.reshape(B, -1))
+            at.append(q_final)
+        if g_trace is not None:
+            raw.append(g_trace.reshape(K * B, -1))
+            at.append(q_trace.reshape(K * B, -1))
+        gq_f = gq_t = None
+        if raw:
+            tang = wbc_workload.raw_to_tangent(torch.cat(at), torch.cat(raw).contiguous())
+            if g_q is not None:
+                gq_f = tang[:B].contiguous()
+            if g_trace is not None:
+                gq_t = tang[-K * B:].reshape(K, B, -1).contiguous()
+        r = bt.rollout_vjp(tape, g_q_final=gq_f, g_qdot_last=None if g_qdot is None else g_qdot.contiguous(), g_q_trace=gq_t, want=want)
+        res = []
+        for k, n in enumerate(names):
+            if n not in want:
+                res.append(None)
+            elif n == "d_q0":
+                res.append(wbc_workload.tangent_to_raw(args[0], r[n]))
+            else:
+                res.append(r[n].reshape(args[k].shape))
+        return tuple(res) + (None,) * 6
+
+
+def wbc_rollout_fused(q0, task_params, ee_target, prev_ee_target, trunk_target, prev_trunk_target, com_target, com_target_vel, posture_u, inputs, dt,
+                      ticks, batch, ee_target_step=None, trunk_target_step=None, mode=capi.ROLLOUT_RUNNING, imu=None):
+    """wbc_rollout as ONE layer: the arguments of wbc_rollout; the forward is one WbcBatch.rollout_record (the forward users run, with a tape),
+    the backward converts the seeds with wbc_workload.raw_to_tangent once, makes one WbcBatch.rollout_vjp call (include/wbc.h: the reverse
+    sweep on the device) and runs wbc_workload.tangent_to_raw on d_q0 once. Gradients flow to q0, to whichever of the eight tensor arguments
+    the configuration reads, and to ee_target_step / trunk_target_step. Returns (q_final [B,27], qdot of the last tick [B,26], status [B]
+    int32 the worst over the ticks, q_trace [ticks,B,27]: the state after every tick); a loss may use q_final, qdot and q_trace.
+    Unsolved ticks: wbc_rollout's rule. inputs must not hold q_con; posture modes MANI / HYBRID need posture_u."""
+    return _WbcRolloutFused.apply(q0, task_params, ee_target, prev_ee_target, trunk_target, prev_trunk_target, com_target, com_target_vel,
+                                  posture_u, ee_target_step, trunk_target_step, inputs, dt, ticks, batch, mode, imu)

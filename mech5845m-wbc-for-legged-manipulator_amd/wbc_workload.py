@@ -1017,3 +1017,75 @@ def step_gradients(model, q_cur, qdot, foot_targets, dt, g, fk, imu=None, mode=c
     if mode == capi.ROLLOUT_RUNNING:
         dq[:, 0:3] = dx[:, 0:3] = 0.0                                     # (c_p = 0: exactly)
     return dict(d_q=dq, d_qdot=dx, d_foot_targets=dft)
+
+
+# ---- K ticks as one reverse sweep (wbc_rollout_vjp, include/wbc.h)
+_ROLLOUT_SUMS = ("d_task_params", "d_com_target", "d_com_target_vel", "d_posture_u")
+
+
+def rollout_gradients(model, cfg, ticks_in, x, dt, fk, assemble, g_q_final=None, g_qdot_last=None, g_q_trace=None, task_params=None, imu=None,
+                      mode=capi.ROLLOUT_RUNNING, status=None, working_set=None):
+    """wbc_rollout_vjp restated for B instances of ONE model over step_gradients, qp_certificate, tick_gradients and tick_state_gradients,
+    tick by tick from the last. ticks_in: K dicts, the inputs tick k SAW (q, the targets as running sums, the previous rotations); x [K, B, 26]:
+    the ticks' qdot; assemble(inputs) -> dict(A, b, C, Clb, Cub, lb, ub) of a tick's problem (a model with nv < 26 gets unit rows on its padded
+    columns here). Seeds in tangent coordinates: g_q_final [B, 26] at q_K, g_qdot_last [B, 26], g_q_trace [K, B, 26] at the state after each
+    tick. status [K, B] / working_set [K, B, 2]: the ticks' own, or None (every tick solved; the active sets read off x).
+    Target bookkeeping (E ee_target, P prev_ee_target, s the step; forward E' = E + s, P' = E where the task is on, else P), with Ebar, Pbar
+    the cotangents of E', P', a = tick.d_ee_target + step.d_foot_targets, p = tick.d_prev_ee_target:
+        d_step += Ebar;  Ebar <- Ebar + a + on Pbar;  Pbar <- p + (1 - on) Pbar          (the trunk pair: the same under task_trunk)
+    A tick that is unsolved, uncertified or non-finite for an instance gives that instance zero from the tick's layer (ticks_dropped += 1);
+    the step's part flows on. Returns dict(d_q0 (tangent at q_0), d_task_params, d_ee_target, d_prev_ee_target, d_trunk_target,
+    d_prev_trunk_target, d_com_target, d_com_target_vel, d_posture_u, d_trunk_box_center, d_ee_target_step, d_trunk_target_step,
+    ticks_dropped [B], sens_max [B]: the largest |sens_x| entry over the ticks)."""
+    K = len(ticks_in)
+    x = np.asarray(x, dtype=np.float64).reshape(K, -1, capi.V_STRIDE)
+    B, NVs, nv = x.shape[1], capi.V_STRIDE, model.nv
+    on = np.array([bool(cfg.task_ee[e]) for e in range(capi.NEE)])[None, :, None]
+    on_t = bool(cfg.task_trunk)
+    g = np.zeros((B, NVs)) if g_q_final is None else np.array(g_q_final, dtype=np.float64).reshape(B, NVs)
+    if g_q_trace is not None:
+        g_q_trace = np.asarray(g_q_trace, dtype=np.float64).reshape(K, B, NVs)
+        g = g + g_q_trace[K - 1]
+    Eb, Pb, TEb, TPb = np.zeros((B, 5, 3)), np.zeros((B, 5, 3)), np.zeros((B, 3)), np.zeros((B, 3))
+    d_es, d_ts = np.zeros((B, 5, 3)), np.zeros((B, 3))
+    acc = dict(d_task_params=np.zeros((B, capi.TASK_PARAMS_DOUBLES)), d_com_target=np.zeros((B, 3)), d_com_target_vel=np.zeros((B, 3)),
+               d_posture_u=np.zeros((B, NVs)), d_trunk_box_center=np.zeros((B, 4)))
+    dropped, sens_max = np.zeros(B, dtype=np.int32), np.zeros(B)
+    for k in range(K - 1, -1, -1):
+        d = ticks_in[k]
+        sg = step_gradients(model, d["q"], x[k], d["ee_target"], dt, g, fk, imu=imu, mode=mode)
+        v = sg["d_qdot"]
+        if k == K - 1 and g_qdot_last is not None:
+            v = v + np.asarray(g_qdot_last, dtype=np.float64).reshape(B, NVs)
+        a = assemble(d)
+        A, b = np.asarray(a["A"], dtype=np.float64), np.asarray(a["b"], dtype=np.float64)
+        if nv < NVs:
+            A = np.concatenate([A, np.broadcast_to(np.eye(NVs)[nv:], (B, NVs - nv, NVs))], axis=1)
+            b = np.concatenate([b, np.zeros((B, NVs - nv))], axis=1)
+        rows = a["C"].shape[1] > 0
+        cert = [qp_certificate(x[k][i], A=A[i], b=b[i], C_=a["C"][i] if rows else None, lb=a["lb"][i], ub=a["ub"][i],
+                               Clb=a["Clb"][i] if rows else None, Cub=a["Cub"][i] if rows else None,
+                               status=None if status is None else status[k][i], working_set=None if working_set is None else working_set[k][i],
+                               v=v[i]) for i in range(B)]
+        st = lambda name: np.stack([c[name] for c in cert])      # noqa: E731
+        ok = np.array([c["cert_status"] == capi.CERT_OK for c in cert]) & np.isfinite(d["q"]).all(axis=1) & np.isfinite(x[k]).all(axis=1)
+        u = st("sens_x")
+        sens_max = np.maximum(sens_max, np.abs(u).max(axis=1))
+        res = tick_state_gradients(model, cfg, d, x[k], u, dt, fk, st("sens_bounds"), st("sens_rows"), st("y_rows"), task_params=task_params,
+                                   working_set=None if working_set is None else working_set[k])
+        tg = tick_gradients(model, cfg, d, x[k], u, dt, fk, task_params)
+        take = lambda t: np.where(ok.reshape((B,) + (1,) * (t.ndim - 1)), t, 0.0)      # noqa: E731
+        dropped += ~ok
+        g = sg["d_q"] + take(res["d_q"])
+        if k > 0 and g_q_trace is not None:
+            g = g + g_q_trace[k - 1]
+        for name in _ROLLOUT_SUMS:
+            acc[name] = acc[name] + take(tg[name])
+        acc["d_trunk_box_center"] = acc["d_trunk_box_center"] + take(res["d_trunk_box_center"])
+        a_k, p_k = take(tg["d_ee_target"]) + sg["d_foot_targets"], take(tg["d_prev_ee_target"])
+        d_es = d_es + Eb
+        Eb, Pb = Eb + a_k + np.where(on, Pb, 0.0), p_k + np.where(on, 0.0, Pb)
+        d_ts = d_ts + TEb
+        TEb, TPb = TEb + take(tg["d_trunk_target"]) + (TPb if on_t else 0.0), take(tg["d_prev_trunk_target"]) + (0.0 if on_t else TPb)
+    return dict(acc, d_q0=g, d_ee_target=Eb, d_prev_ee_target=Pb, d_trunk_target=TEb, d_prev_trunk_target=TPb, d_ee_target_step=d_es,
+                d_trunk_target_step=d_ts, ticks_dropped=dropped, sens_max=sens_max)

@@ -1,0 +1,93 @@
+#!/usr/bin/env python3
+"""What a roll-out gradient costs in two calls against the chained layers (recorded, not gated): on the benchmark's c3 inputs, K = 16 ticks,
+B = 256, 4096 and 65536 in one process, device tensors in place, forward + backward of the loss rho . q_K with gradients to q0, ee_target
+and the task rows,
+    fused     wbc_torch.wbc_rollout_fused: one wbc_rollout_record, one wbc_rollout_vjp
+    chain     wbc_torch.wbc_rollout: per tick wbc_tick_state -> wbc_step, autograd through the layers
+    record    WbcBatch.rollout_record alone            rollout   WbcBatch.rollout alone (what the record adds to the forward)
+    vjp       WbcBatch.rollout_vjp alone               tick      wbc_tick alone (the unit the per-reverse-tick cost is stated in)
+tools/time_step_vjp.py's protocol: warm-up, then ROUNDS rounds that alternate the runs, each REPS repeats between two device events; the
+median over rounds and the spread (min .. max). Writes profiles/r24_rollout_vjp.txt (or argv[1]).
+    python3 tools/time_rollout_vjp.py [out.txt] [K]"""
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "mech5845m-wbc-for-legged-manipulator_amd"))
+import numpy as np
+import torch
+
+import wbc_capi as capi
+import wbc_model
+import wbc_torch
+import wbc_workload
+from wbc_batch import WbcBatch
+
+OUT = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "r24_rollout_vjp.txt")
+K = int(sys.argv[2]) if len(sys.argv) > 2 else 16
+BATCHES = (256, 4096, 65536)
+DT, ROUNDS, REPS, WARM = 0.002, 5, 3, 2
+
+assert torch.cuda.is_available(), "time_rollout_vjp.py measures on the GPU; there is nothing to report without one"
+model = wbc_model.load_model("a1_wx200")
+cfg = wbc_model.sim3_config(model)
+lines = ["# tools/time_rollout_vjp.py: a1_wx200, c3 (sim3 switch set), benchmark inputs (seed 0), K = %d ticks, loss rho . q_K, gradients to q0, ee_target"
+         " and the task rows" % K,
+         "# device tensors in place; %d rounds alternating the runs, %d calls between two device events each, %d warm-up calls; ms per call"
+         % (ROUNDS, REPS, WARM),
+         "# tape: %d bytes per instance + %d bytes per instance and tick" % (capi.TAPE_HEAD_BYTES, capi.TAPE_TICK_BYTES)]
+for B in BATCHES:
+    bt = WbcBatch(model, B)
+    bt.configure(cfg)
+    d = wbc_workload.make_tick_inputs(model, cfg, B, 0, lambda q: bt.fk(q, want=("oMf",))["oMf"])
+    dev = {k: torch.from_numpy(np.ascontiguousarray(v)).cuda() for k, v in d.items()}
+    rest = {k: v for k, v in dev.items() if k not in ("q", "ee_target")}
+    rho = torch.from_numpy(np.random.default_rng(1).normal(0, 1.0, (B, 27))).cuda()
+    rows = torch.from_numpy(wbc_model.task_params(cfg, B)).cuda()
+    g_final = wbc_workload.raw_to_tangent(dev["q"], rho).contiguous()
+    state = {}
+
+    def layer(fn):
+        q0, ee, tp = dev["q"].clone().requires_grad_(True), dev["ee_target"].clone().requires_grad_(True), rows.clone().requires_grad_(True)
+        q = fn(q0, tp, ee, None, None, None, None, None, None, rest, DT, K, bt)[0]
+        (q * rho).sum().backward()
+        return q0.grad
+
+    def run_record():
+        state["rec"], state["tape"] = bt.rollout_record(dev, DT, K, task_params=rows, tape=state.get("tape"))
+
+    run_record()
+    vjp_out = bt.rollout_vjp(state["tape"], g_q_final=g_final)
+    runs = dict(fused=lambda: layer(wbc_torch.wbc_rollout_fused), chain=lambda: layer(wbc_torch.wbc_rollout), record=run_record,
+                rollout=lambda: bt.rollout(dev, DT, K, want_trace=False, task_params=rows),
+                vjp=lambda: bt.rollout_vjp(state["tape"], g_q_final=g_final, out=vjp_out), tick=lambda: bt.tick(dev, DT, task_params=rows))
+    for fn in runs.values():
+        for _ in range(WARM):
+            fn()
+    torch.cuda.synchronize()
+    same = float((layer(wbc_torch.wbc_rollout_fused) - layer(wbc_torch.wbc_rollout)).abs().max())
+    dropped = int((vjp_out["ticks_dropped"] > 0).sum())
+    ms = {k: [] for k in runs}
+    for _ in range(ROUNDS):
+        for k, fn in runs.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(REPS):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / REPS)
+    lines.append("# B = %d: %d instances with a dropped tick; max|fused dL/dq0 - chain dL/dq0| %.3e" % (B, dropped, same))
+    for k in runs:
+        a = np.array(ms[k])
+        lines.append(json.dumps(dict(B=B, what=k, median_ms=round(float(np.median(a)), 4), min_ms=round(float(a.min()), 4), max_ms=round(float(a.max()), 4))))
+    med = {k: float(np.median(ms[k])) for k in runs}
+    lines.append("# B = %d: chain / fused = %.2f; record / rollout = %.3f; one reverse tick = vjp / K = %.4f ms = %.2f ticks" % (
+        B, med["chain"] / med["fused"], med["record"] / med["rollout"], med["vjp"] / K, med["vjp"] / K / med["tick"]))
+    bt.close()
+text = "\n".join(lines) + "\n"
+print(text, end="")
+os.makedirs(os.path.dirname(os.path.abspath(OUT)), exist_ok=True)
+with open(OUT, "w") as f:
+    f.write(text)
