@@ -228,6 +228,35 @@ TapeWs TapeWs::carve(void* tape, size_t B, int k) {
   return w;
 }
 
+// The gradient layers' outputs, each struct stated once as a table: the member, its doubles per instance, its name, which
+// input of the configuration it is the gradient of (Read: the "requested, but ..." refusals, the wiring of the sweep's tick outputs) and that
+// input's name in the refusal. The rows stand in the struct's order, which is the order the entry points stage them in.
+enum Read { R_ALWAYS, R_EE, R_EE_EST, R_TRUNK, R_COM, R_PU, R_BOX };
+template <class G> struct OutRow { double* G::*ptr; size_t width; const char* name; Read need; const char* src; };
+constexpr OutRow<WbcTickGrad> TICK_OUT[] = {{&WbcTickGrad::d_task_params, WBC_TASK_PARAMS_DOUBLES, "d_task_params", R_ALWAYS, nullptr},
+    {&WbcTickGrad::d_ee_target, 3 * WBC_NEE, "d_ee_target", R_EE, "ee_target"}, {&WbcTickGrad::d_prev_ee_target, 3 * WBC_NEE, "d_prev_ee_target", R_EE, "prev_ee_target"},
+    {&WbcTickGrad::d_trunk_target, 3, "d_trunk_target", R_TRUNK, nullptr}, {&WbcTickGrad::d_prev_trunk_target, 3, "d_prev_trunk_target", R_TRUNK, nullptr},
+    {&WbcTickGrad::d_com_target, 3, "d_com_target", R_COM, nullptr}, {&WbcTickGrad::d_com_target_vel, 3, "d_com_target_vel", R_COM, nullptr},
+    {&WbcTickGrad::d_posture_u, WBC_V_STRIDE, "d_posture_u", R_PU, nullptr}};
+constexpr OutRow<WbcTickStateGrad> TICKQ_OUT[] = {{&WbcTickStateGrad::d_q, WBC_V_STRIDE, "d_q", R_ALWAYS, nullptr},
+    {&WbcTickStateGrad::d_trunk_box_center, 4, "d_trunk_box_center", R_BOX, nullptr}};
+constexpr OutRow<WbcStepGrad> STEP_OUT[] = {{&WbcStepGrad::d_q, WBC_V_STRIDE, "d_q", R_ALWAYS, nullptr}, {&WbcStepGrad::d_qdot, WBC_V_STRIDE, "d_qdot", R_ALWAYS, nullptr},
+    {&WbcStepGrad::d_foot_targets, 3 * WBC_NEE, "d_foot_targets", R_ALWAYS, nullptr}};
+template <class G, size_t N> constexpr size_t out_width(const OutRow<G> (&t)[N], double* G::*ptr) {
+  for (size_t i = 0; i < N; ++i) if (t[i].ptr == ptr) return t[i].width;
+  return 0;
+}
+// (the roll-out's outputs: the tick's and the tick-state's at their widths there, the steps as the targets they advance)
+constexpr size_t tw(double* WbcTickGrad::*p) { return out_width(TICK_OUT, p); }
+constexpr size_t qw(double* WbcTickStateGrad::*p) { return out_width(TICKQ_OUT, p); }
+constexpr OutRow<WbcRolloutGrad> ROLL_OUT[] = {{&WbcRolloutGrad::d_q0, qw(&WbcTickStateGrad::d_q), "d_q0", R_ALWAYS, nullptr},
+    {&WbcRolloutGrad::d_task_params, tw(&WbcTickGrad::d_task_params), "d_task_params", R_ALWAYS, nullptr}, {&WbcRolloutGrad::d_ee_target, tw(&WbcTickGrad::d_ee_target), "d_ee_target", R_EE_EST, "ee_target"},
+    {&WbcRolloutGrad::d_prev_ee_target, tw(&WbcTickGrad::d_prev_ee_target), "d_prev_ee_target", R_EE, "prev_ee_target"}, {&WbcRolloutGrad::d_trunk_target, tw(&WbcTickGrad::d_trunk_target), "d_trunk_target", R_TRUNK, nullptr},
+    {&WbcRolloutGrad::d_prev_trunk_target, tw(&WbcTickGrad::d_prev_trunk_target), "d_prev_trunk_target", R_TRUNK, nullptr}, {&WbcRolloutGrad::d_com_target, tw(&WbcTickGrad::d_com_target), "d_com_target", R_COM, nullptr},
+    {&WbcRolloutGrad::d_com_target_vel, tw(&WbcTickGrad::d_com_target_vel), "d_com_target_vel", R_COM, nullptr}, {&WbcRolloutGrad::d_posture_u, tw(&WbcTickGrad::d_posture_u), "d_posture_u", R_PU, nullptr},
+    {&WbcRolloutGrad::d_trunk_box_center, qw(&WbcTickStateGrad::d_trunk_box_center), "d_trunk_box_center", R_BOX, nullptr},
+    {&WbcRolloutGrad::d_ee_target_step, tw(&WbcTickGrad::d_ee_target), "d_ee_target_step", R_EE_EST, "ee_target"}, {&WbcRolloutGrad::d_trunk_target_step, tw(&WbcTickGrad::d_trunk_target), "d_trunk_target_step", R_TRUNK, nullptr}};
+
 struct RollVjpWs {   // d_rvjp: wbc_rollout_vjp's workspace — one tick's QP image and certificate, the layers' outputs of the tick, the sweep's accumulators
   double *lb, *ub, *v, *g, *s_dq, *s_dft, *sens_x, *sens_bounds, *t_dq, *t_box, *t_tp, *t_ee, *t_pee, *t_tt, *t_ptt, *t_com, *t_comv, *t_pu;
   double *Ebar, *Pbar, *TEbar, *TPbar, *d_estep, *d_tstep, *acc_tp, *acc_com, *acc_comv, *acc_pu, *acc_box;
@@ -236,13 +265,20 @@ struct RollVjpWs {   // d_rvjp: wbc_rollout_vjp's workspace — one tick's QP im
   static size_t bytes(size_t NB, size_t M, size_t p);
   static RollVjpWs carve(void* base, size_t NB, size_t M, size_t p);
 };
+// where the sweep keeps one tick's outputs of the tick layer: the block's width is the output's
+constexpr struct TickWire { double* WbcTickGrad::*out; double* RollVjpWs::*ws; } TICK_WS[] = {{&WbcTickGrad::d_task_params, &RollVjpWs::t_tp},
+    {&WbcTickGrad::d_ee_target, &RollVjpWs::t_ee}, {&WbcTickGrad::d_prev_ee_target, &RollVjpWs::t_pee}, {&WbcTickGrad::d_trunk_target, &RollVjpWs::t_tt},
+    {&WbcTickGrad::d_prev_trunk_target, &RollVjpWs::t_ptt}, {&WbcTickGrad::d_com_target, &RollVjpWs::t_com}, {&WbcTickGrad::d_com_target_vel, &RollVjpWs::t_comv},
+    {&WbcTickGrad::d_posture_u, &RollVjpWs::t_pu}};
+constexpr Block<RollVjpWs, double> tick_block(int i) { return {TICK_WS[i].ws, tw(TICK_WS[i].out)}; }
 constexpr Block<RollVjpWs, double> RVJP_D[] = {{&RollVjpWs::lb, WBC_V_STRIDE}, {&RollVjpWs::ub, WBC_V_STRIDE}, {&RollVjpWs::v, WBC_V_STRIDE},
-    {&RollVjpWs::g, WBC_V_STRIDE}, {&RollVjpWs::s_dq, WBC_V_STRIDE}, {&RollVjpWs::s_dft, 3 * WBC_NEE}, {&RollVjpWs::sens_x, WBC_V_STRIDE},
-    {&RollVjpWs::sens_bounds, WBC_V_STRIDE}, {&RollVjpWs::t_dq, WBC_V_STRIDE}, {&RollVjpWs::t_box, 4}, {&RollVjpWs::t_tp, WBC_TASK_PARAMS_DOUBLES},
-    {&RollVjpWs::t_ee, 3 * WBC_NEE}, {&RollVjpWs::t_pee, 3 * WBC_NEE}, {&RollVjpWs::t_tt, 3}, {&RollVjpWs::t_ptt, 3}, {&RollVjpWs::t_com, 3},
-    {&RollVjpWs::t_comv, 3}, {&RollVjpWs::t_pu, WBC_V_STRIDE}, {&RollVjpWs::Ebar, 3 * WBC_NEE}, {&RollVjpWs::Pbar, 3 * WBC_NEE}, {&RollVjpWs::TEbar, 3},
+    {&RollVjpWs::g, WBC_V_STRIDE}, {&RollVjpWs::s_dq, out_width(STEP_OUT, &WbcStepGrad::d_q)}, {&RollVjpWs::s_dft, out_width(STEP_OUT, &WbcStepGrad::d_foot_targets)},
+    {&RollVjpWs::sens_x, WBC_V_STRIDE}, {&RollVjpWs::sens_bounds, WBC_V_STRIDE}, {&RollVjpWs::t_dq, qw(&WbcTickStateGrad::d_q)},
+    {&RollVjpWs::t_box, qw(&WbcTickStateGrad::d_trunk_box_center)}, tick_block(0), tick_block(1), tick_block(2), tick_block(3),
+    tick_block(4), tick_block(5), tick_block(6), tick_block(7), {&RollVjpWs::Ebar, 3 * WBC_NEE}, {&RollVjpWs::Pbar, 3 * WBC_NEE}, {&RollVjpWs::TEbar, 3},
     {&RollVjpWs::TPbar, 3}, {&RollVjpWs::d_estep, 3 * WBC_NEE}, {&RollVjpWs::d_tstep, 3}, {&RollVjpWs::acc_tp, WBC_TASK_PARAMS_DOUBLES},
     {&RollVjpWs::acc_com, 3}, {&RollVjpWs::acc_comv, 3}, {&RollVjpWs::acc_pu, WBC_V_STRIDE}, {&RollVjpWs::acc_box, 4}};
+static_assert(sizeof(TICK_WS) / sizeof(TICK_WS[0]) == sizeof(TICK_OUT) / sizeof(TICK_OUT[0]) && sizeof(TICK_WS) / sizeof(TICK_WS[0]) == 8, "one block of d_rvjp per output of the tick layer");
 constexpr Block<RollVjpWs, int32_t> RVJP_I[] = {{&RollVjpWs::cert_status, 1}, {&RollVjpWs::gs_step, 1}, {&RollVjpWs::gs_tick, 1}, {&RollVjpWs::gs_tickq, 1},
     {&RollVjpWs::worst, 1}, {&RollVjpWs::dropped, 1}};
 static_assert(block_bytes(RVJP_D) == 555 * sizeof(double) && block_bytes(RVJP_I) == 6 * sizeof(int32_t), "d_rvjp: 555 doubles and 6 int32 per instance (+ the QP image)");
@@ -1665,6 +1701,113 @@ extern "C" int wbc_rollout(WbcBatch* b, int B, const WbcTickIn* in0, double dt, 
   return wbc_rollout_tp(b, B, in0, nullptr, dt, r, mem, stream);
 }
 
+// ---- The gradient layers: what every entry point and the roll-out's sweep share. One refusal of a model the packed whole-tree
+// schedule cannot hold, one answer to "what does the configuration read", the refusals and the staging driven by the output tables (OutRow),
+// and ONE function per layer that fills the layer's kernel arguments from what the layer consumes and launches: an entry point is check,
+// stage, that function, finish; the sweep calls the same functions with pointers into the tape and RollVjpWs.
+static int layers_fit(const WbcBatch* b, const char* who) {
+  for (int i = 0; i < b->n_models; ++i) {
+    if (b->plan_host[i].slack_ok) continue;
+    const DevModel& M = b->models[i]->dev;
+    return fail(WBC_E_UNSUPPORTED, "%s: model %d does not fit the packed whole-tree schedule (%d joints, at most 22; tree depth %d, at most 7; at most 16 joints at one depth)",
+                who, i, M.njoints, M.maxdepth);
+  }
+  return WBC_OK;
+}
+struct Reads {   // of a handle check_batch passed (the switches are every model's); est: the base estimator runs (roll-outs in RUNNING mode) and reads ee_target
+  bool any_ee, est, trunk, com, reads_pu, con_trunk;
+  uint32_t ee_on;
+  int p, no_pu;   // constraint rows (b->prows: rows_con of switches every model shares); the first model whose posture mode does not read posture_u
+  Reads(const WbcBatch* b, bool est_) : est(est_), ee_on(0), p(b->prows), no_pu(-1) {
+    const WbcConfig& c = b->cfg_host[0];
+    for (int i = 0; i < WBC_NEE; ++i) if (c.task_ee[i]) ee_on |= 1u << i;
+    any_ee = ee_on != 0; trunk = c.task_trunk != 0; com = c.task_com != 0; con_trunk = c.con_trunk != 0;
+    for (int i = b->n_models - 1; i >= 0; --i) if (b->cfg_host[i].task_joint < WBC_JOINT_MANI) no_pu = i;
+    reads_pu = no_pu < 0;
+  }
+  bool operator()(Read what) const {
+    switch (what) {
+      case R_EE: return any_ee;
+      case R_EE_EST: return any_ee || est;
+      case R_TRUNK: return trunk;
+      case R_COM: return com;
+      case R_PU: return reads_pu;
+      case R_BOX: return con_trunk;
+      default: return true;
+    }
+  }
+};
+// "<name> requested, but ...": the first output of the table that is asked for and is the gradient of nothing the configuration reads.
+// name_model: wbc_tick_vjp names the model whose posture mode does not read posture_u, wbc_rollout_vjp does not (each caller's wording is kept).
+template <class G, size_t N> static int check_outs(const G& out, const OutRow<G> (&t)[N], const Reads& rd, const char* who, bool name_model) {
+  for (const OutRow<G>& r : t) {
+    if (!(out.*r.ptr) || rd(r.need)) continue;
+    switch (r.need) {
+      case R_EE: return fail(WBC_E_ARG, "%s: %s requested, but no EE task reads %s", who, r.name, r.src);
+      case R_EE_EST: return fail(WBC_E_ARG, "%s: %s requested, but no EE task and no estimator reads %s", who, r.name, r.src);
+      case R_TRUNK: return fail(WBC_E_ARG, "%s: %s requested, but the trunk task is off", who, r.name);
+      case R_COM: return fail(WBC_E_ARG, "%s: %s requested, but the CoM task is off", who, r.name);
+      case R_BOX: return fail(WBC_E_ARG, "%s: %s requested, but the trunk constraint is off", who, r.name);
+      default:
+        if (name_model) return fail(WBC_E_ARG, "%s: %s requested, but the posture mode of model %d does not read posture_u", who, r.name, rd.no_pu);
+        return fail(WBC_E_ARG, "%s: %s requested, but the posture mode of a model does not read posture_u", who, r.name);
+    }
+  }
+  return WBC_OK;
+}
+template <class G, size_t N> static void stage_outs(Stager& st, G& out, const OutRow<G> (&t)[N], size_t n) {
+  for (const OutRow<G>& r : t) st.out(&(out.*r.ptr), n * r.width);
+}
+
+// the state step: g -> d_q, d_qdot, d_foot_targets (wbc_stepvjp_kernel)
+static int step_layer(WbcBatch* b, int B, double dt, int mode, const double* q_cur, const double* qdot, const double* foot_targets, const double* imu,
+                      const int32_t* model_id, const double* g, const WbcStepGrad& out, void* stream) {
+  StepVjpArgs a;
+  memset(&a, 0, sizeof a);
+  a.models = b->d_models; a.plans = b->d_plans; a.B = B; a.n_models = b->n_models; a.rot = b->rot; a.mode = mode; a.dt = dt;
+  a.q_cur = q_cur; a.qdot = qdot; a.foot_targets = foot_targets; a.imu = imu; a.model_id = model_id; a.g = g; a.out = out;
+  return launch_rc(launch_stepvjp(a, stream, &b->last_stepvjp_variant), "state step gradient");
+}
+// the certificate of solved QPs (wbc_qp_cert_kernel). Without constraint rows the row blocks are not read or written, whatever the pointers are.
+static int cert_layer(WbcBatch* b, int B, const WbcQpProblem& q, const WbcQpCert& out, void* stream) {
+  const bool rows = q.p > 0;
+  CertArgs a;
+  memset(&a, 0, sizeof a);
+  a.B = B; a.n = q.n; a.p = q.p; a.m = q.m;
+  a.H = q.H; a.g = q.g; a.A = q.A; a.bvec = q.b; a.C = rows ? q.C : nullptr; a.lb = q.lb; a.ub = q.ub;
+  a.Clb = rows ? q.Clb : nullptr; a.Cub = rows ? q.Cub : nullptr;
+  a.x = q.x; a.v = q.v; a.status = q.status; a.ws = (const unsigned long long*)q.working_set;
+  a.y_bounds = out.y_bounds; a.y_rows = rows ? out.y_rows : nullptr; a.kkt = out.kkt; a.objective = out.objective;
+  a.sens_x = out.sens_x; a.sens_bounds = out.sens_bounds; a.sens_rows = rows ? out.sens_rows : nullptr;
+  a.n_active = out.n_active; a.cert_status = out.cert_status;
+  return launch_rc(launch_cert(a, grid_for(b, B), stream), "qp certificate");
+}
+// the tick over its weights, gains and targets (wbc_grad_kernel), after the posture kernel where the tick itself would run it
+static int tick_layer(WbcBatch* b, int B, double dt, const WbcTickIn& in, const WbcTaskParams* tp, const double* qdot, const double* sens_x,
+                      const int32_t* status, const int32_t* cert_status, const WbcTickGrad& out, void* stream) {
+  KernelArgs ka;                       // (auto_posture's view of the call: in, and whether the tick would derive u itself)
+  fill_args(ka, b, B, dt);
+  ka.in = in;
+  ka.in.q_con = nullptr;               // cleared after staging: the task rows see q, no leaked configuration is asked for
+  if (int rc = auto_posture(b, ka, B, stream)) return rc;
+  GradArgs a;
+  memset(&a, 0, sizeof a);
+  a.models = b->d_models; a.cfgs = b->d_cfgs; a.plans = b->d_plans; a.B = B; a.n_models = b->n_models; a.rot = b->rot; a.dt = dt;
+  a.in = ka.in;                        // posture_u AFTER auto_posture (still null: every sweep is structurally zero, the kernel reads DevPlan.post_zero)
+  a.tp = tp; a.qdot = qdot; a.sens_x = sens_x; a.status = status; a.cert_status = cert_status; a.out = out;
+  return launch_rc(launch_grad(a, stream, &b->last_grad_variant), "tick gradient");
+}
+// the tick over its state (wbc_gradq_kernel). No posture kernel: the layer sees the CALLER's posture_u, which is held constant.
+static int tickq_layer(WbcBatch* b, int B, double dt, const WbcTickIn& in, const WbcTaskParams* tp, const WbcTickSens& sens, const WbcTickStateGrad& out,
+                       void* stream) {
+  GradQArgs a;
+  memset(&a, 0, sizeof a);
+  a.models = b->d_models; a.cfgs = b->d_cfgs; a.plans = b->d_plans; a.B = B; a.n_models = b->n_models; a.rot = b->rot; a.dt = dt;
+  a.in = in; a.tp = tp; a.sens = sens; a.out = out;
+  if (b->prows == 0) a.sens.sens_rows = a.sens.y_rows = nullptr;
+  return launch_rc(launch_gradq(a, stream, &b->last_gradq_variant), "tick state gradient");
+}
+
 // ---- Roll-out gradients in two calls (include/wbc.h): wbc_rollout_record is rollout_run with the RecordExt extension;
 // wbc_rollout_vjp walks the tape from the last tick to the first and launches, per tick, the layers' own kernels on the taped inputs
 // (wbc_stepvjp_kernel, the general kernel's assemble mode, wbc_qp_cert_kernel, wbc_grad_kernel, wbc_gradq_kernel) and the link kernel.
@@ -1688,13 +1831,7 @@ static int check_record_call(WbcBatch* b, int B, const WbcTickIn* in0, const Wbc
   if (!tape) return fail(WBC_E_ARG, "%s: tape is required (device memory of wbc_rollout_tape_bytes(B, ticks) bytes)", who);
   const size_t want = wbc_rollout_tape_bytes(B, r->ticks);
   if (tape_bytes < want) return fail(WBC_E_ARG, "%s: tape_bytes = %zu, wbc_rollout_tape_bytes(%d, %d) = %zu", who, tape_bytes, B, r->ticks, want);
-  for (int i = 0; i < b->n_models; ++i) {
-    if (b->plan_host[i].slack_ok) continue;
-    const DevModel& M = b->models[i]->dev;
-    return fail(WBC_E_UNSUPPORTED, "%s: model %d does not fit the packed whole-tree schedule (%d joints, at most 22; tree depth %d, at most 7; at most 16 joints at one depth)",
-                who, i, M.njoints, M.maxdepth);
-  }
-  return WBC_OK;
+  return layers_fit(b, who);
 }
 extern "C" int wbc_rollout_record(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r, void* tape,
                                   size_t tape_bytes, double* q_trace, int mem, void* stream) {
@@ -1724,31 +1861,16 @@ extern "C" int wbc_rollout_vjp(WbcBatch* b, int B, const WbcTickIn* in0, const W
     return fail(WBC_E_ARG, "%s: mode = %d, want WBC_ROLLOUT_RUNNING (%d) or WBC_ROLLOUT_WARMUP (%d)", who, r->mode, WBC_ROLLOUT_RUNNING, WBC_ROLLOUT_WARMUP);
   if ((rc = validate_tick_in(b, in0, who))) return rc;
   if (!in0->ee_target || !in0->prev_ee_target) return fail(WBC_E_ARG, "%s: ee_target / prev_ee_target are required (the base estimator reads the foot targets)", who);
-  const WbcConfig& c = b->cfg_host[0];
-  bool any_ee = false;
-  uint32_t ee_on = 0;
-  for (int i = 0; i < WBC_NEE; ++i) if (c.task_ee[i]) { any_ee = true; ee_on |= 1u << i; }
-  const bool est = r->mode == WBC_ROLLOUT_RUNNING;   // the estimator reads ee_target: the step's d_foot_targets reaches it without an EE task
-  if (out->d_ee_target && !any_ee && !est) return fail(WBC_E_ARG, "%s: d_ee_target requested, but no EE task and no estimator reads ee_target", who);
-  if (out->d_ee_target_step && !any_ee && !est) return fail(WBC_E_ARG, "%s: d_ee_target_step requested, but no EE task and no estimator reads ee_target", who);
-  if (out->d_prev_ee_target && !any_ee) return fail(WBC_E_ARG, "%s: d_prev_ee_target requested, but no EE task reads prev_ee_target", who);
-  if (out->d_trunk_target && !c.task_trunk) return fail(WBC_E_ARG, "%s: d_trunk_target requested, but the trunk task is off", who);
-  if (out->d_prev_trunk_target && !c.task_trunk) return fail(WBC_E_ARG, "%s: d_prev_trunk_target requested, but the trunk task is off", who);
-  if (out->d_trunk_target_step && !c.task_trunk) return fail(WBC_E_ARG, "%s: d_trunk_target_step requested, but the trunk task is off", who);
-  if (out->d_com_target && !c.task_com) return fail(WBC_E_ARG, "%s: d_com_target requested, but the CoM task is off", who);
-  if (out->d_com_target_vel && !c.task_com) return fail(WBC_E_ARG, "%s: d_com_target_vel requested, but the CoM task is off", who);
-  bool reads_pu = true;
-  for (int i = 0; i < b->n_models; ++i) reads_pu = reads_pu && b->cfg_host[i].task_joint >= WBC_JOINT_MANI;
-  if (out->d_posture_u && !reads_pu) return fail(WBC_E_ARG, "%s: d_posture_u requested, but the posture mode of a model does not read posture_u", who);
-  if (out->d_trunk_box_center && !c.con_trunk) return fail(WBC_E_ARG, "%s: d_trunk_box_center requested, but the trunk constraint is off", who);
+  const Reads rd(b, r->mode == WBC_ROLLOUT_RUNNING);   // the estimator reads ee_target: the step's d_foot_targets reaches it without an EE task
+  if ((rc = check_outs(*out, ROLL_OUT, rd, who, false))) return rc;
   HIP_TRY(hipSetDevice(b->device_id));
-  // sizes: the task rows of wbc_assemble, the unit rows on the padded columns of the handle's smallest model, the constraint rows
+  // size the workspace: the task rows of wbc_assemble, the unit rows on the padded columns of the handle's smallest model, the constraint rows
   int min_nv = WBC_V_STRIDE;
   for (int i = 0; i < b->n_models; ++i) if (b->models[i]->dev.nv < min_nv) min_nv = b->models[i]->dev.nv;
-  const int m = b->mrows, pad_rows = WBC_V_STRIDE - min_nv, M = m + pad_rows, p = b->prows, K = r->ticks;
+  const int m = b->mrows, pad_rows = WBC_V_STRIDE - min_nv, M = m + pad_rows, p = rd.p, K = r->ticks;
   if (M > WBC_MAX_M) return fail(WBC_E_UNSUPPORTED, "%s: %d task rows + %d padding rows exceed the certificate's %d", who, m, pad_rows, WBC_MAX_M);
   const size_t NB = (size_t)b->max_batch, n = (size_t)B;
-  if ((rc = ensure_size(b->d_rvjp, b->rvjp_bytes, RollVjpWs::bytes(NB, (size_t)M, (size_t)p)))) return rc;
+  if ((rc = ensure_size(b->d_rvjp, b->rvjp_bytes, RollVjpWs::bytes(NB, (size_t)M, (size_t)p)))) return rc;   // (after one call of these row counts: no allocation)
   const RollVjpWs w = RollVjpWs::carve(b->d_rvjp, NB, (size_t)M, (size_t)p);
   // stage
   KernelArgs a;
@@ -1758,43 +1880,46 @@ extern "C" int wbc_rollout_vjp(WbcBatch* b, int B, const WbcTickIn* in0, const W
   WbcRolloutSeed sd = *seed;
   WbcRolloutGrad og = *out;
   const double* imu = r->imu;
-  hipStream_t s = (hipStream_t)stream;
-  Stager st{b, mem, s, {}};
+  Stager st{b, mem, (hipStream_t)stream, {}};
   stage_tick_in(st, a.in, B, b);
   st.in(&tp, n); st.in(&imu, n * 4);
   st.in(&sd.g_q_final, n * WBC_V_STRIDE); st.in(&sd.g_qdot_last, n * WBC_V_STRIDE); st.in(&sd.g_q_trace, (size_t)K * n * WBC_V_STRIDE);
-  st.out(&og.d_q0, n * WBC_V_STRIDE); st.out(&og.d_task_params, n * WBC_TASK_PARAMS_DOUBLES); st.out(&og.d_ee_target, n * 15);
-  st.out(&og.d_prev_ee_target, n * 15); st.out(&og.d_trunk_target, n * 3); st.out(&og.d_prev_trunk_target, n * 3); st.out(&og.d_com_target, n * 3);
-  st.out(&og.d_com_target_vel, n * 3); st.out(&og.d_posture_u, n * WBC_V_STRIDE); st.out(&og.d_trunk_box_center, n * 4);
-  st.out(&og.d_ee_target_step, n * 15); st.out(&og.d_trunk_target_step, n * 3); st.out(&og.grad_status, n); st.out(&og.ticks_dropped, n);
+  stage_outs(st, og, ROLL_OUT, n);
+  st.out(&og.grad_status, n); st.out(&og.ticks_dropped, n);
   if ((rc = st.stage())) return rc;
   const WbcTickIn first = a.in;
   const bool have_ws = b->warm_start != 0;   // the tape holds working sets (the option as it was when the tape was recorded: include/wbc.h)
   void* const tp_mut = const_cast<void*>(tape);   // (read only: TapeWs carves non-const pointers)
   const TapeHead head = TapeHead::carve(tp_mut, n);
-  // the tick gradient's kernel runs where one of its outputs is asked for (the state side runs on every tick: g needs it)
-  const bool want_tick = og.d_task_params || og.d_ee_target || og.d_prev_ee_target || og.d_trunk_target || og.d_prev_trunk_target || og.d_com_target ||
-                         og.d_com_target_vel || og.d_posture_u || og.d_ee_target_step || og.d_trunk_target_step;
+  // the outputs of the layers, in the workspace. The tick layer runs where an output of the sweep needs one of its (the state side runs on
+  // every tick: g needs it); each of its outputs is wired where the configuration reads what it is the gradient of
+  bool want_tick = false;
+  for (const OutRow<WbcRolloutGrad>& row : ROLL_OUT) want_tick |= og.*row.ptr && row.ptr != &WbcRolloutGrad::d_q0 && row.ptr != &WbcRolloutGrad::d_trunk_box_center;
+  const WbcStepGrad s_out{w.s_dq, w.v, w.s_dft, w.gs_step};
+  const WbcTickStateGrad q_out{w.t_dq, rd.con_trunk ? w.t_box : nullptr, w.gs_tickq};
+  WbcQpCert c_out{};
+  c_out.y_rows = w.y_rows; c_out.sens_x = w.sens_x; c_out.sens_bounds = w.sens_bounds; c_out.sens_rows = w.sens_rows; c_out.cert_status = w.cert_status;
   RollVjpArgs L;
   memset(&L, 0, sizeof L);
+  if (want_tick) {
+    L.t.grad_status = w.gs_tick;
+    for (size_t i = 0; i < sizeof(TICK_WS) / sizeof(TICK_WS[0]); ++i)
+      if (rd(TICK_OUT[i].need)) L.t.*TICK_WS[i].out = w.*TICK_WS[i].ws;
+  }
   L.models = b->d_models; L.model_id = first.model_id; L.B = B; L.n_models = b->n_models; L.K = K; L.m = m; L.pad_rows = pad_rows;
-  L.ee_on = ee_on; L.trunk_on = c.task_trunk != 0;
+  L.ee_on = rd.ee_on; L.trunk_on = rd.trunk;
   L.g_q_final = sd.g_q_final; L.g_qdot_last = sd.g_qdot_last; L.g_q_trace = sd.g_q_trace;
   L.A = w.A; L.b = w.b; L.g = w.g; L.v = w.v;
-  L.s_dq = w.s_dq; L.s_dft = est ? w.s_dft : nullptr; L.t_dq = w.t_dq; L.t_box = c.con_trunk ? w.t_box : nullptr;
-  if (want_tick) {
-    L.t.d_task_params = w.t_tp; L.t.grad_status = w.gs_tick;
-    if (any_ee) { L.t.d_ee_target = w.t_ee; L.t.d_prev_ee_target = w.t_pee; }
-    if (c.task_trunk) { L.t.d_trunk_target = w.t_tt; L.t.d_prev_trunk_target = w.t_ptt; }
-    if (c.task_com) { L.t.d_com_target = w.t_com; L.t.d_com_target_vel = w.t_comv; }
-    if (reads_pu) L.t.d_posture_u = w.t_pu;
-  }
+  L.s_dq = s_out.d_q; L.s_dft = rd.est ? s_out.d_foot_targets : nullptr; L.t_dq = q_out.d_q; L.t_box = q_out.d_trunk_box_center;
   L.gs_step = w.gs_step; L.gs_tickq = w.gs_tickq;
   L.Ebar = w.Ebar; L.Pbar = w.Pbar; L.TEbar = w.TEbar; L.TPbar = w.TPbar; L.d_estep = w.d_estep; L.d_tstep = w.d_tstep; L.acc_tp = w.acc_tp;
   L.acc_com = w.acc_com; L.acc_comv = w.acc_comv; L.acc_pu = w.acc_pu; L.acc_box = w.acc_box; L.worst = w.worst; L.dropped = w.dropped;
   L.out = og;
-  L.k = K - 1;
-  if ((rc = launch_rc(launch_rollvjp(L, ROLLVJP_BEGIN, stream, &b->last_rollvjp_variant), "roll-out gradient link"))) return rc;
+  auto link = [&](int stage, int k) {   // (the launch chain is linear: every stage waits for the one before it on the stream)
+    L.k = k;
+    return launch_rc(launch_rollvjp(L, stage, stream, &b->last_rollvjp_variant), "roll-out gradient link");
+  };
+  if ((rc = link(ROLLVJP_BEGIN, K - 1))) return rc;
   for (int k = K - 1; k >= 0; --k) {
     const TapeWs T = TapeWs::carve(tp_mut, n, k);
     WbcTickIn in = first;   // the inputs tick k saw
@@ -1803,15 +1928,10 @@ extern "C" int wbc_rollout_vjp(WbcBatch* b, int B, const WbcTickIn* in0, const W
     if (first.prev_trunk_target) in.prev_trunk_target = T.prev_trunk_target;
     if (k > 0 && first.ee_prev_rot) in.ee_prev_rot = head.ee_prev_rot;
     if (k > 0 && first.trunk_prev_rot) in.trunk_prev_rot = head.trunk_prev_rot;
-    // 1., 2. the step: g -> d_q, v = d_qdot, d_foot_targets
-    StepVjpArgs sa;
-    memset(&sa, 0, sizeof sa);
-    sa.models = b->d_models; sa.plans = b->d_plans; sa.B = B; sa.n_models = b->n_models; sa.rot = b->rot; sa.mode = r->mode; sa.dt = dt;
-    sa.q_cur = T.q; sa.qdot = T.qdot; sa.foot_targets = T.ee_target; sa.imu = imu; sa.model_id = first.model_id; sa.g = w.g;
-    sa.out.d_q = w.s_dq; sa.out.d_qdot = w.v; sa.out.d_foot_targets = w.s_dft; sa.out.grad_status = w.gs_step;
-    if ((rc = launch_rc(launch_stepvjp(sa, stream, &b->last_stepvjp_variant), "state step gradient"))) return rc;
-    if (k == K - 1 && sd.g_qdot_last && (rc = launch_rc(launch_rollvjp(L, ROLLVJP_ADDV, stream, &b->last_rollvjp_variant), "roll-out gradient link"))) return rc;
-    // 3. the tick's problem at the taped inputs (A's rows strided by M: the padding rows stay where BEGIN wrote them), its certificate with v
+    // the step: g -> d_q, v = d_qdot, d_foot_targets; on the last tick v += g_qdot_last
+    if ((rc = step_layer(b, B, dt, r->mode, T.q, T.qdot, T.ee_target, imu, first.model_id, w.g, s_out, stream))) return rc;
+    if (k == K - 1 && sd.g_qdot_last && (rc = link(ROLLVJP_ADDV, K - 1))) return rc;
+    // the tick's problem at the taped inputs. mrows = M is the stride of A: the padding rows stay where BEGIN wrote them
     a.in = in;
     a.mrows = M;
     a.qp = WbcQpData{};
@@ -1819,34 +1939,19 @@ extern "C" int wbc_rollout_vjp(WbcBatch* b, int B, const WbcTickIn* in0, const W
     if (p > 0) { a.qp.C = w.C; a.qp.Clb = w.Clb; a.qp.Cub = w.Cub; }
     if ((rc = auto_posture(b, a, B, stream))) return rc;
     if ((rc = launch_rc(launch_tick(a, MODE_ASSEMBLE, grid_tick(b, B), stream, tp, &b->last_tick_variant), "assemble"))) return rc;
-    CertArgs ca;
-    memset(&ca, 0, sizeof ca);
-    ca.B = B; ca.n = WBC_V_STRIDE; ca.p = p; ca.m = M;
-    ca.A = w.A; ca.bvec = w.b; ca.lb = w.lb; ca.ub = w.ub;
-    if (p > 0) { ca.C = w.C; ca.Clb = w.Clb; ca.Cub = w.Cub; ca.y_rows = w.y_rows; ca.sens_rows = w.sens_rows; }
-    ca.x = T.qdot; ca.v = w.v; ca.status = T.status; ca.ws = have_ws ? T.working_set : nullptr;
-    ca.sens_x = w.sens_x; ca.sens_bounds = w.sens_bounds; ca.cert_status = w.cert_status;
-    if ((rc = launch_rc(launch_cert(ca, grid_for(b, B), stream), "qp certificate"))) return rc;
-    // 4. the tick's two layers
-    if (want_tick) {
-      GradArgs ga;
-      memset(&ga, 0, sizeof ga);
-      ga.models = b->d_models; ga.cfgs = b->d_cfgs; ga.plans = b->d_plans; ga.B = B; ga.n_models = b->n_models; ga.rot = b->rot; ga.dt = dt;
-      ga.in = a.in; ga.tp = tp; ga.qdot = T.qdot; ga.sens_x = w.sens_x; ga.status = T.status; ga.cert_status = w.cert_status; ga.out = L.t;
-      if ((rc = launch_rc(launch_grad(ga, stream, &b->last_grad_variant), "tick gradient"))) return rc;
-    }
-    GradQArgs qa;
-    memset(&qa, 0, sizeof qa);
-    qa.models = b->d_models; qa.cfgs = b->d_cfgs; qa.plans = b->d_plans; qa.B = B; qa.n_models = b->n_models; qa.rot = b->rot; qa.dt = dt;
-    qa.in = in; qa.tp = tp;
-    qa.sens.qdot = T.qdot; qa.sens.sens_x = w.sens_x; qa.sens.sens_bounds = w.sens_bounds;
-    if (p > 0) { qa.sens.sens_rows = w.sens_rows; qa.sens.y_rows = w.y_rows; }
-    qa.sens.status = T.status; qa.sens.cert_status = w.cert_status; qa.sens.working_set = have_ws ? (const uint64_t*)T.working_set : nullptr;
-    qa.out.d_q = w.t_dq; qa.out.d_trunk_box_center = c.con_trunk ? w.t_box : nullptr; qa.out.grad_status = w.gs_tickq;
-    if ((rc = launch_rc(launch_gradq(qa, stream, &b->last_gradq_variant), "tick state gradient"))) return rc;
-    // 5. the link
-    L.k = k;
-    if ((rc = launch_rc(launch_rollvjp(L, ROLLVJP_LINK, stream, &b->last_rollvjp_variant), "roll-out gradient link"))) return rc;
+    // its certificate with v. The working set reaches the certificate and the tick-state layer under warm_start alone: only then the tape holds it
+    WbcQpProblem qp{};
+    qp.n = WBC_V_STRIDE; qp.p = p; qp.m = M;
+    qp.A = w.A; qp.b = w.b; qp.C = w.C; qp.lb = w.lb; qp.ub = w.ub; qp.Clb = w.Clb; qp.Cub = w.Cub;
+    qp.x = T.qdot; qp.v = w.v; qp.status = T.status; qp.working_set = have_ws ? (const uint64_t*)T.working_set : nullptr;
+    if ((rc = cert_layer(b, B, qp, c_out, stream))) return rc;
+    // the tick's two layers: the first is skipped when none of its outputs is asked for
+    if (want_tick && (rc = tick_layer(b, B, dt, a.in, tp, T.qdot, w.sens_x, T.status, w.cert_status, L.t, stream))) return rc;
+    WbcTickSens sn{};
+    sn.qdot = T.qdot; sn.sens_x = w.sens_x; sn.sens_bounds = w.sens_bounds; sn.sens_rows = w.sens_rows; sn.y_rows = w.y_rows;
+    sn.status = T.status; sn.cert_status = w.cert_status; sn.working_set = qp.working_set;
+    if ((rc = tickq_layer(b, B, dt, in, tp, sn, q_out, stream))) return rc;
+    if ((rc = link(ROLLVJP_LINK, k))) return rc;
   }
   return st.finish();
 }
@@ -2032,25 +2137,18 @@ extern "C" int wbc_qp_certificate(WbcBatch* b, int B, const WbcQpProblem* q, con
   if (!q->v && out->sens_bounds) return fail(WBC_E_ARG, "%s: sens_bounds requested without v", who);
   if (!q->v && out->sens_rows) return fail(WBC_E_ARG, "%s: sens_rows requested without v", who);
   HIP_TRY(hipSetDevice(b->device_id));
-  CertArgs a;
-  memset(&a, 0, sizeof a);
-  a.B = B; a.n = n; a.p = p; a.m = m;
-  a.H = q->H; a.g = q->g; a.A = q->A; a.bvec = q->b; a.C = p > 0 ? q->C : nullptr; a.lb = q->lb; a.ub = q->ub;
-  a.Clb = p > 0 ? q->Clb : nullptr; a.Cub = p > 0 ? q->Cub : nullptr;
-  a.x = q->x; a.v = q->v; a.status = q->status; a.ws = (const unsigned long long*)q->working_set;
-  a.y_bounds = out->y_bounds; a.y_rows = p > 0 ? out->y_rows : nullptr; a.kkt = out->kkt; a.objective = out->objective;
-  a.sens_x = out->sens_x; a.sens_bounds = out->sens_bounds; a.sens_rows = p > 0 ? out->sens_rows : nullptr;
-  a.n_active = out->n_active; a.cert_status = out->cert_status;
+  WbcQpProblem a = *q;
+  WbcQpCert o = *out;
   Stager st{b, mem, (hipStream_t)stream, {}};
   const size_t N = (size_t)B;
-  st.in(&a.H, N * n * n); st.in(&a.g, N * n); st.in(&a.A, N * m * n); st.in(&a.bvec, N * m);
+  st.in(&a.H, N * n * n); st.in(&a.g, N * n); st.in(&a.A, N * m * n); st.in(&a.b, N * m);
   st.in(&a.C, N * p * n); st.in(&a.lb, N * n); st.in(&a.ub, N * n); st.in(&a.Clb, N * p); st.in(&a.Cub, N * p);
-  st.in(&a.x, N * n); st.in(&a.v, N * n); st.in(&a.status, N); st.in(&a.ws, N * 2);
-  st.out(&a.y_bounds, N * n); st.out(&a.y_rows, N * p); st.out(&a.kkt, N * 4); st.out(&a.objective, N);
-  st.out(&a.sens_x, N * n); st.out(&a.sens_bounds, N * n); st.out(&a.sens_rows, N * p);
-  st.out(&a.n_active, N); st.out(&a.cert_status, N);
+  st.in(&a.x, N * n); st.in(&a.v, N * n); st.in(&a.status, N); st.in(&a.working_set, N * 2);
+  st.out(&o.y_bounds, N * n); st.out(&o.y_rows, N * p); st.out(&o.kkt, N * 4); st.out(&o.objective, N);
+  st.out(&o.sens_x, N * n); st.out(&o.sens_bounds, N * n); st.out(&o.sens_rows, N * p);
+  st.out(&o.n_active, N); st.out(&o.cert_status, N);
   if ((rc = st.stage())) return rc;
-  if ((rc = launch_rc(launch_cert(a, grid_for(b, B), stream), "qp certificate"))) return rc;
+  if ((rc = cert_layer(b, B, a, o, stream))) return rc;
   return st.finish();
 }
 extern "C" int wbc_qp_certificate_sizes(int32_t* sizeof_problem, int32_t* sizeof_cert) {
@@ -2073,44 +2171,19 @@ extern "C" int wbc_tick_vjp(WbcBatch* b, int B, const WbcTickIn* in, const WbcTa
   if (!qdot) return fail(WBC_E_ARG, "%s: qdot is required", who);
   if (!sens_x) return fail(WBC_E_ARG, "%s: sens_x is required", who);
   if ((rc = validate_tick_in(b, in, who))) return rc;
-  const WbcConfig& c = b->cfg_host[0];
-  bool any_ee = false;
-  for (int i = 0; i < WBC_NEE; ++i) any_ee |= c.task_ee[i] != 0;
-  if (out->d_ee_target && !any_ee) return fail(WBC_E_ARG, "%s: d_ee_target requested, but no EE task reads ee_target", who);
-  if (out->d_prev_ee_target && !any_ee) return fail(WBC_E_ARG, "%s: d_prev_ee_target requested, but no EE task reads prev_ee_target", who);
-  if (out->d_trunk_target && !c.task_trunk) return fail(WBC_E_ARG, "%s: d_trunk_target requested, but the trunk task is off", who);
-  if (out->d_prev_trunk_target && !c.task_trunk) return fail(WBC_E_ARG, "%s: d_prev_trunk_target requested, but the trunk task is off", who);
-  if (out->d_com_target && !c.task_com) return fail(WBC_E_ARG, "%s: d_com_target requested, but the CoM task is off", who);
-  if (out->d_com_target_vel && !c.task_com) return fail(WBC_E_ARG, "%s: d_com_target_vel requested, but the CoM task is off", who);
-  for (int i = 0; i < b->n_models; ++i)
-    if (out->d_posture_u && b->cfg_host[i].task_joint < WBC_JOINT_MANI)
-      return fail(WBC_E_ARG, "%s: d_posture_u requested, but the posture mode of model %d does not read posture_u", who, i);
-  for (int i = 0; i < b->n_models; ++i) {
-    if (b->plan_host[i].slack_ok) continue;
-    const DevModel& M = b->models[i]->dev;
-    return fail(WBC_E_UNSUPPORTED, "%s: model %d does not fit the packed whole-tree schedule (%d joints, at most 22; tree depth %d, at most 7; at most 16 joints at one depth)",
-                who, i, M.njoints, M.maxdepth);
-  }
+  if ((rc = check_outs(*out, TICK_OUT, Reads(b, false), who, true))) return rc;
+  if ((rc = layers_fit(b, who))) return rc;
   HIP_TRY(hipSetDevice(b->device_id));
-  KernelArgs ka;                       // (auto_posture's view of the call: in, and whether the tick would derive u itself)
-  fill_args(ka, b, B, dt);
-  ka.in = *in;
-  GradArgs a;
-  memset(&a, 0, sizeof a);
-  a.models = b->d_models; a.cfgs = b->d_cfgs; a.plans = b->d_plans; a.B = B; a.n_models = b->n_models; a.rot = b->rot; a.dt = dt;
-  a.tp = tp; a.qdot = qdot; a.sens_x = sens_x; a.status = status; a.cert_status = cert_status; a.out = *out;
+  WbcTickIn ti = *in;
+  WbcTickGrad og = *out;
   Stager st{b, mem, (hipStream_t)stream, {}};
-  stage_tick_in(st, ka.in, B, b);
+  stage_tick_in(st, ti, B, b);
   const size_t n = (size_t)B;
-  st.in(&a.tp, n); st.in(&a.qdot, n * WBC_V_STRIDE); st.in(&a.sens_x, n * WBC_V_STRIDE); st.in(&a.status, n); st.in(&a.cert_status, n);
-  st.out(&a.out.d_task_params, n * WBC_TASK_PARAMS_DOUBLES); st.out(&a.out.d_ee_target, n * 15); st.out(&a.out.d_prev_ee_target, n * 15);
-  st.out(&a.out.d_trunk_target, n * 3); st.out(&a.out.d_prev_trunk_target, n * 3); st.out(&a.out.d_com_target, n * 3);
-  st.out(&a.out.d_com_target_vel, n * 3); st.out(&a.out.d_posture_u, n * WBC_V_STRIDE); st.out(&a.out.grad_status, n);
+  st.in(&tp, n); st.in(&qdot, n * WBC_V_STRIDE); st.in(&sens_x, n * WBC_V_STRIDE); st.in(&status, n); st.in(&cert_status, n);
+  stage_outs(st, og, TICK_OUT, n);
+  st.out(&og.grad_status, n);
   if ((rc = st.stage())) return rc;
-  ka.in.q_con = nullptr;               // the task rows see q: no leaked configuration is asked for
-  if ((rc = auto_posture(b, ka, B, stream))) return rc;
-  a.in = ka.in;                        // (posture_u still null: every sweep is structurally zero, the kernel reads DevPlan.post_zero)
-  if ((rc = launch_rc(launch_grad(a, stream, &b->last_grad_variant), "tick gradient"))) return rc;
+  if ((rc = tick_layer(b, B, dt, ti, tp, qdot, sens_x, status, cert_status, og, stream))) return rc;
   return st.finish();
 }
 extern "C" int wbc_tick_grad_sizes(int32_t* sizeof_grad) {
@@ -2134,39 +2207,32 @@ extern "C" int wbc_tick_vjp_state(WbcBatch* b, int B, const WbcTickIn* in, const
   if (!sens->sens_x) return fail(WBC_E_ARG, "%s: sens_x is required", who);
   if ((rc = validate_tick_in(b, in, who))) return rc;
   if (in->q_con) return fail(WBC_E_ARG, "%s: q_con is not supported (the constraints would see another configuration than the task rows)", who);
-  const WbcConfig& c = b->cfg_host[0];
   for (int i = 0; i < b->n_models; ++i) {
     const int tj = b->cfg_host[i].task_joint;
     if ((tj == WBC_JOINT_MANI || tj == WBC_JOINT_HYBRID) && !in->posture_u)
       return fail(WBC_E_ARG, "%s: posture mode MANI / HYBRID of model %d needs posture_u (it is held constant)", who, i);
   }
-  int p = (c.con_com ? 2 : 0) + (c.con_trunk ? 4 : 0);
-  for (int i = 0; i < WBC_NEE; ++i) p += c.con_ee[i] ? 3 : 0;
-  if (c.use_bounds && !sens->sens_bounds) return fail(WBC_E_ARG, "%s: sens_bounds is required with use_bounds", who);
+  const Reads rd(b, false);
+  const int p = rd.p;
+  if (b->cfg_host[0].use_bounds && !sens->sens_bounds) return fail(WBC_E_ARG, "%s: sens_bounds is required with use_bounds", who);
   if (p > 0 && !sens->sens_rows) return fail(WBC_E_ARG, "%s: sens_rows is required with %d constraint rows", who, p);
   if (p > 0 && !sens->y_rows) return fail(WBC_E_ARG, "%s: y_rows is required with %d constraint rows", who, p);
-  if (out->d_trunk_box_center && !c.con_trunk) return fail(WBC_E_ARG, "%s: d_trunk_box_center requested, but the trunk constraint is off", who);
-  for (int i = 0; i < b->n_models; ++i) {
-    if (b->plan_host[i].slack_ok) continue;
-    const DevModel& M = b->models[i]->dev;
-    return fail(WBC_E_UNSUPPORTED, "%s: model %d does not fit the packed whole-tree schedule (%d joints, at most 22; tree depth %d, at most 7; at most 16 joints at one depth)",
-                who, i, M.njoints, M.maxdepth);
-  }
+  if ((rc = check_outs(*out, TICKQ_OUT, rd, who, true))) return rc;
+  if ((rc = layers_fit(b, who))) return rc;
   HIP_TRY(hipSetDevice(b->device_id));
-  GradQArgs a;
-  memset(&a, 0, sizeof a);
-  a.models = b->d_models; a.cfgs = b->d_cfgs; a.plans = b->d_plans; a.B = B; a.n_models = b->n_models; a.rot = b->rot; a.dt = dt;
-  a.in = *in; a.tp = tp; a.sens = *sens; a.out = *out;
-  if (p == 0) a.sens.sens_rows = a.sens.y_rows = nullptr;
+  WbcTickIn ti = *in;
+  WbcTickSens sn = *sens;
+  WbcTickStateGrad og = *out;
   Stager st{b, mem, (hipStream_t)stream, {}};
-  stage_tick_in(st, a.in, B, b);
+  stage_tick_in(st, ti, B, b);
   const size_t n = (size_t)B;
-  st.in(&a.tp, n); st.in(&a.sens.qdot, n * WBC_V_STRIDE); st.in(&a.sens.sens_x, n * WBC_V_STRIDE); st.in(&a.sens.sens_bounds, n * WBC_V_STRIDE);
-  st.in(&a.sens.sens_rows, n * p); st.in(&a.sens.y_rows, n * p); st.in(&a.sens.status, n); st.in(&a.sens.cert_status, n);
-  st.in(&a.sens.working_set, n * 2);
-  st.out(&a.out.d_q, n * WBC_V_STRIDE); st.out(&a.out.d_trunk_box_center, n * 4); st.out(&a.out.grad_status, n);
+  st.in(&tp, n); st.in(&sn.qdot, n * WBC_V_STRIDE); st.in(&sn.sens_x, n * WBC_V_STRIDE); st.in(&sn.sens_bounds, n * WBC_V_STRIDE);
+  st.in(&sn.sens_rows, n * p); st.in(&sn.y_rows, n * p); st.in(&sn.status, n); st.in(&sn.cert_status, n);
+  st.in(&sn.working_set, n * 2);
+  stage_outs(st, og, TICKQ_OUT, n);
+  st.out(&og.grad_status, n);
   if ((rc = st.stage())) return rc;
-  if ((rc = launch_rc(launch_gradq(a, stream, &b->last_gradq_variant), "tick state gradient"))) return rc;
+  if ((rc = tickq_layer(b, B, dt, ti, tp, sn, og, stream))) return rc;
   return st.finish();
 }
 extern "C" int wbc_tick_state_grad_sizes(int32_t* sizeof_sens, int32_t* sizeof_grad) {
@@ -2192,24 +2258,17 @@ extern "C" int wbc_step_vjp(WbcBatch* b, int B, const double* q_cur, const doubl
     return fail(WBC_E_ARG, "%s: mode = %d, want WBC_ROLLOUT_RUNNING (%d) or WBC_ROLLOUT_WARMUP (%d)", who, mode, WBC_ROLLOUT_RUNNING, WBC_ROLLOUT_WARMUP);
   if ((rc = check_dt(dt, who))) return rc;
   if (b->n_models > 1 && !model_id) return fail(WBC_E_ARG, "%s: model_id is required with %d models", who, b->n_models);
-  for (int i = 0; i < b->n_models; ++i) {
-    if (b->plan_host[i].slack_ok) continue;
-    const DevModel& M = b->models[i]->dev;
-    return fail(WBC_E_UNSUPPORTED, "%s: model %d does not fit the packed whole-tree schedule (%d joints, at most 22; tree depth %d, at most 7; at most 16 joints at one depth)",
-                who, i, M.njoints, M.maxdepth);
-  }
+  if ((rc = layers_fit(b, who))) return rc;
   HIP_TRY(hipSetDevice(b->device_id));
-  StepVjpArgs a;
-  memset(&a, 0, sizeof a);
-  a.models = b->d_models; a.plans = b->d_plans; a.B = B; a.n_models = b->n_models; a.rot = b->rot; a.mode = mode; a.dt = dt;
-  a.q_cur = q_cur; a.qdot = qdot; a.foot_targets = foot_targets; a.imu = imu; a.model_id = model_id; a.g = g_q_new; a.out = *out;
+  WbcStepGrad og = *out;
   Stager st{b, mem, (hipStream_t)stream, {}};
   const size_t n = (size_t)B;
-  st.in(&a.q_cur, n * WBC_Q_STRIDE); st.in(&a.qdot, n * WBC_V_STRIDE); st.in(&a.foot_targets, n * 15); st.in(&a.imu, n * 4);
-  st.in(&a.model_id, n); st.in(&a.g, n * WBC_V_STRIDE);
-  st.out(&a.out.d_q, n * WBC_V_STRIDE); st.out(&a.out.d_qdot, n * WBC_V_STRIDE); st.out(&a.out.d_foot_targets, n * 15); st.out(&a.out.grad_status, n);
+  st.in(&q_cur, n * WBC_Q_STRIDE); st.in(&qdot, n * WBC_V_STRIDE); st.in(&foot_targets, n * 15); st.in(&imu, n * 4);
+  st.in(&model_id, n); st.in(&g_q_new, n * WBC_V_STRIDE);
+  stage_outs(st, og, STEP_OUT, n);
+  st.out(&og.grad_status, n);
   if ((rc = st.stage())) return rc;
-  if ((rc = launch_rc(launch_stepvjp(a, stream, &b->last_stepvjp_variant), "state step gradient"))) return rc;
+  if ((rc = step_layer(b, B, dt, mode, q_cur, qdot, foot_targets, imu, model_id, g_q_new, og, stream))) return rc;
   return st.finish();
 }
 extern "C" int wbc_step_grad_sizes(int32_t* sizeof_grad) {

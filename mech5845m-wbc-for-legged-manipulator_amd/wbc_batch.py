@@ -223,6 +223,39 @@ class WbcBatch:
             setattr(struct, k, self._p(v, _dtype_of(k), keep, B, widths[k], k))
         return struct
 
+    # which input of the configuration a gradient output belongs to (the library's OutRow tables; an output not named here is always offered)
+    _NEEDS = dict(d_ee_target="ee", d_prev_ee_target="ee", d_trunk_target="trunk", d_prev_trunk_target="trunk", d_trunk_target_step="trunk",
+                  d_com_target="com", d_com_target_vel="com", d_posture_u="posture_u", d_trunk_box_center="con_trunk")
+    _ROLLOUT_NEEDS = dict(_NEEDS, d_ee_target="ee_est", d_ee_target_step="ee_est")     # the estimator of RUNNING mode reads ee_target too
+
+    def _offered(self, fields, needs=_NEEDS, mode=None):
+        """the names of `fields` whose input the handle's configuration reads (mode: the roll-out's; RUNNING has the estimator)"""
+        c = self.cfgs[0]
+        ee = any(c.task_ee[e] for e in range(capi.NEE))
+        reads = dict(ee=ee, ee_est=ee or mode == capi.ROLLOUT_RUNNING, trunk=c.task_trunk, com=c.task_com, con_trunk=c.con_trunk,
+                     posture_u=all(cf is not None and cf.task_joint >= capi.JOINT_MANI for cf in self.cfgs))
+        return tuple(k for k in fields if k not in needs or reads[needs[k]])
+
+    def _grad_outs(self, fields, struct, like, B, keep, want, default, out, extras=("grad_status",)):
+        """-> (out, o): the outputs of a *_vjp method and the struct that points at them. fields: name -> per-instance shape. out None: the
+        arrays of `want` (None: default()) are allocated where `like` lives, and the int32 [B] `extras`; else the caller's arrays by name."""
+        if out is None:
+            names = default() if want is None else tuple(want)
+            unknown = set(names) - set(fields)
+            if unknown:
+                raise capi.WbcError("unknown gradients %s (known: %s)" % (sorted(unknown), ", ".join(fields)))
+            out = {k: self._alloc(like, (B,) + fields[k]) for k in names}
+            out.update({k: self._alloc(like, (B,), np.int32) for k in extras})
+        o = struct()
+        for k, a in out.items():
+            if k in extras:
+                setattr(o, k, self._p(a, np.int32, keep, B, 1, k))
+            elif k in fields:
+                setattr(o, k, self._p(a, np.float64, keep, B, int(np.prod(fields[k])), k))
+            else:
+                raise capi.WbcError("unknown output %r" % k)
+        return out, o
+
     def _alloc(self, like, shape, dtype=np.float64):
         if self.allocator is not None:
             return self.allocator(like, shape, dtype)
@@ -440,17 +473,7 @@ class WbcBatch:
 
     def default_grad_wants(self):
         """the gradients wbc_tick_vjp offers under the handle's configuration (names of capi.TICK_GRAD_FIELDS)"""
-        c = self.cfgs[0]
-        want = ["d_task_params"]
-        if any(c.task_ee[e] for e in range(capi.NEE)):
-            want += ["d_ee_target", "d_prev_ee_target"]
-        if c.task_trunk:
-            want += ["d_trunk_target", "d_prev_trunk_target"]
-        if c.task_com:
-            want += ["d_com_target", "d_com_target_vel"]
-        if all(cf is not None and cf.task_joint >= capi.JOINT_MANI for cf in self.cfgs):
-            want += ["d_posture_u"]
-        return tuple(want)
+        return self._offered(capi.TICK_GRAD_FIELDS)
 
     def tick_vjp(self, inputs, dt, qdot, sens_x, status=None, cert_status=None, task_params=None, want=None, out=None):
         """wbc_tick_vjp (include/wbc.h): dL/d(task weights, gains, targets) of solved ticks from x = qdot [B,26] and the certificate's
@@ -458,22 +481,8 @@ class WbcBatch:
         those names (and "grad_status") instead. Returns dict(<want>..., grad_status [B] int32)."""
         keep = []
         B = self._batch_of(inputs.get("q"))
-        if out is None:
-            names = self.default_grad_wants() if want is None else tuple(want)
-            unknown = set(names) - set(capi.TICK_GRAD_FIELDS)
-            if unknown:
-                raise capi.WbcError("unknown gradients %s (known: %s)" % (sorted(unknown), ", ".join(capi.TICK_GRAD_FIELDS)))
-            out = {k: self._alloc(qdot, (B,) + capi.TICK_GRAD_FIELDS[k]) for k in names}
-            out["grad_status"] = self._alloc(qdot, (B,), np.int32)
+        out, o = self._grad_outs(capi.TICK_GRAD_FIELDS, capi.WbcTickGrad, qdot, B, keep, want, self.default_grad_wants, out)
         mem = _mem_of(list(inputs.values()) + list(out.values()) + [task_params, qdot, sens_x, status, cert_status])
-        o = capi.WbcTickGrad()
-        for k, a in out.items():
-            if k == "grad_status":
-                o.grad_status = self._p(a, np.int32, keep, B, 1, k)
-            elif k in capi.TICK_GRAD_FIELDS:
-                setattr(o, k, self._p(a, np.float64, keep, B, int(np.prod(capi.TICK_GRAD_FIELDS[k])), k))
-            else:
-                raise capi.WbcError("unknown output %r" % k)
         tin = self._tick_in(inputs, keep, B)
         tp = _task_params(task_params, B, keep, self.device_id)
         f, P = np.float64, self._p
@@ -498,23 +507,10 @@ class WbcBatch:
         Returns dict(<want>..., grad_status [B] int32)."""
         keep = []
         B = self._batch_of(inputs.get("q"))
-        if out is None:
-            names = (("d_q",) + (("d_trunk_box_center",) if self.cfgs[0].con_trunk else ())) if want is None else tuple(want)
-            unknown = set(names) - set(capi.TICK_STATE_GRAD_FIELDS)
-            if unknown:
-                raise capi.WbcError("unknown gradients %s (known: %s)" % (sorted(unknown), ", ".join(capi.TICK_STATE_GRAD_FIELDS)))
-            out = {k: self._alloc(qdot, (B,) + capi.TICK_STATE_GRAD_FIELDS[k]) for k in names}
-            out["grad_status"] = self._alloc(qdot, (B,), np.int32)
+        out, o = self._grad_outs(capi.TICK_STATE_GRAD_FIELDS, capi.WbcTickStateGrad, qdot, B, keep, want,
+                                 lambda: self._offered(capi.TICK_STATE_GRAD_FIELDS), out)
         mem = _mem_of(list(inputs.values()) + list(out.values()) + [task_params, qdot, sens_x, sens_bounds, sens_rows, y_rows, status, cert_status,
                                                                     working_set])
-        o = capi.WbcTickStateGrad()
-        for k, a in out.items():
-            if k == "grad_status":
-                o.grad_status = self._p(a, np.int32, keep, B, 1, k)
-            elif k in capi.TICK_STATE_GRAD_FIELDS:
-                setattr(o, k, self._p(a, np.float64, keep, B, int(np.prod(capi.TICK_STATE_GRAD_FIELDS[k])), k))
-            else:
-                raise capi.WbcError("unknown output %r" % k)
         tin = self._tick_in(inputs, keep, B)
         tp = _task_params(task_params, B, keep, self.device_id)
         f, P, p = np.float64, self._p, self.constraint_rows
@@ -571,22 +567,8 @@ class WbcBatch:
         The IMU quaternion is held constant. Returns dict(<want>..., grad_status [B] int32)."""
         keep = []
         B = self._batch_of(q_cur, "q_cur")
-        if out is None:
-            names = tuple(capi.STEP_GRAD_FIELDS) if want is None else tuple(want)
-            unknown = set(names) - set(capi.STEP_GRAD_FIELDS)
-            if unknown:
-                raise capi.WbcError("unknown gradients %s (known: %s)" % (sorted(unknown), ", ".join(capi.STEP_GRAD_FIELDS)))
-            out = {k: self._alloc(q_cur, (B,) + capi.STEP_GRAD_FIELDS[k]) for k in names}
-            out["grad_status"] = self._alloc(q_cur, (B,), np.int32)
+        out, o = self._grad_outs(capi.STEP_GRAD_FIELDS, capi.WbcStepGrad, q_cur, B, keep, want, lambda: tuple(capi.STEP_GRAD_FIELDS), out)
         mem = _mem_of([q_cur, qdot, foot_targets, g, imu, model_id] + list(out.values()))
-        o = capi.WbcStepGrad()
-        for k, a in out.items():
-            if k == "grad_status":
-                o.grad_status = self._p(a, np.int32, keep, B, 1, k)
-            elif k in capi.STEP_GRAD_FIELDS:
-                setattr(o, k, self._p(a, np.float64, keep, B, int(np.prod(capi.STEP_GRAD_FIELDS[k])), k))
-            else:
-                raise capi.WbcError("unknown output %r" % k)
         f, P = np.float64, self._p
         capi.check(self.lib.wbc_step_vjp(self._h, B, P(q_cur, f, keep), P(qdot, f, keep, B, NV, "qdot"), P(foot_targets, f, keep, B, 15, "foot_targets"),
                                           P(imu, f, keep, B, 4, "imu"), P(model_id, np.int32, keep, B, 1, "model_id"), float(dt), int(mode),
@@ -680,23 +662,9 @@ class WbcBatch:
         if getattr(self, "_options", {}).get("warm_start", 0) != c["warm_start"]:
             raise capi.WbcError("rollout_vjp: option warm_start changed since the tape was recorded (the tape holds working sets only with it)")
         like = next((a for a in (g_q_final, g_qdot_last, g_q_trace) if a is not None), inputs["q"])
-        if out is None:
-            names = self.default_rollout_grad_wants(c["mode"]) if want is None else tuple(want)
-            unknown = set(names) - set(capi.ROLLOUT_GRAD_FIELDS)
-            if unknown:
-                raise capi.WbcError("unknown gradients %s (known: %s)" % (sorted(unknown), ", ".join(capi.ROLLOUT_GRAD_FIELDS)))
-            out = {k: self._alloc(like, (B,) + capi.ROLLOUT_GRAD_FIELDS[k]) for k in names}
-            out["grad_status"] = self._alloc(like, (B,), np.int32)
-            out["ticks_dropped"] = self._alloc(like, (B,), np.int32)
+        out, o = self._grad_outs(capi.ROLLOUT_GRAD_FIELDS, capi.WbcRolloutGrad, like, B, keep, want, lambda: self.default_rollout_grad_wants(c["mode"]),
+                                 out, extras=("grad_status", "ticks_dropped"))
         mem = _mem_of(list(inputs.values()) + list(out.values()) + [c["imu"], c["task_params"], g_q_final, g_qdot_last, g_q_trace])
-        o = capi.WbcRolloutGrad()
-        for k, a in out.items():
-            if k in ("grad_status", "ticks_dropped"):
-                setattr(o, k, self._p(a, np.int32, keep, B, 1, k))
-            elif k in capi.ROLLOUT_GRAD_FIELDS:
-                setattr(o, k, self._p(a, np.float64, keep, B, int(np.prod(capi.ROLLOUT_GRAD_FIELDS[k])), k))
-            else:
-                raise capi.WbcError("unknown output %r" % k)
         f, P = np.float64, self._p
         sd = capi.WbcRolloutSeed()
         sd.g_q_final, sd.g_qdot_last = P(g_q_final, f, keep, B, NV, "g_q_final"), P(g_qdot_last, f, keep, B, NV, "g_qdot_last")
@@ -715,22 +683,7 @@ class WbcBatch:
 
     def default_rollout_grad_wants(self, mode=capi.ROLLOUT_RUNNING):
         """the gradients wbc_rollout_vjp offers under the handle's configuration (names of capi.ROLLOUT_GRAD_FIELDS)"""
-        c = self.cfgs[0]
-        want = ["d_q0", "d_task_params"]
-        any_ee = any(c.task_ee[e] for e in range(capi.NEE))
-        if any_ee or mode == capi.ROLLOUT_RUNNING:
-            want += ["d_ee_target", "d_ee_target_step"]
-        if any_ee:
-            want += ["d_prev_ee_target"]
-        if c.task_trunk:
-            want += ["d_trunk_target", "d_prev_trunk_target", "d_trunk_target_step"]
-        if c.task_com:
-            want += ["d_com_target", "d_com_target_vel"]
-        if all(cf is not None and cf.task_joint >= capi.JOINT_MANI for cf in self.cfgs):
-            want += ["d_posture_u"]
-        if c.con_trunk:
-            want += ["d_trunk_box_center"]
-        return tuple(want)
+        return self._offered(capi.ROLLOUT_GRAD_FIELDS, self._ROLLOUT_NEEDS, mode)
 
     _SUMMARY = (("err_sq_sum", np.float64), ("err_max", np.float64), ("err_max_tick", np.int32), ("err_final", np.float64),
                 ("first_bad_tick", np.int32), ("bad_ticks", np.int32))

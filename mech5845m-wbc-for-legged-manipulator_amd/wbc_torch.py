@@ -84,46 +84,71 @@ def qp_solve(H, g, C, lb, ub, Clb, Cub, batch):
 
 
 _TICK_ARGS = ("task_params", "ee_target", "prev_ee_target", "trunk_target", "prev_trunk_target", "com_target", "com_target_vel", "posture_u")
+_STATE_ARGS = ("q",) + _TICK_ARGS
+_FUSED_ARGS = ("q0",) + _TICK_ARGS + ("ee_target_step", "trunk_target_step")
+_IN_NAME = dict({n: n for n in _TICK_ARGS[1:]}, q="q", q0="q")      # tensor argument -> the WbcTickIn field it stands for (the others are none)
+
+
+# ---- the bookkeeping the layers over a tick share: tensor arguments that may be None, merged into `inputs`, saved, and asked for by name
+def _merged(inputs, names, args):
+    """-> dict(inputs) with every tensor argument that is given in under its WbcTickIn name"""
+    d = dict(inputs)
+    d.update({_IN_NAME[n]: a for n, a in zip(names, args) if a is not None and n in _IN_NAME})
+    return d
+
+
+def _save(ctx, head, args):
+    """through save_for_backward: an in-place change of an argument between forward and backward is an autograd error, not a gradient of other data"""
+    ctx.present = [a is not None for a in args]
+    ctx.save_for_backward(*head, *[a for a in args if a is not None])
+
+
+def _saved(ctx, n_head):
+    """-> (the head tensors, the arguments with None where none was given)"""
+    t = ctx.saved_tensors
+    it = iter(t[n_head:])
+    return t[:n_head], [next(it) if have else None for have in ctx.present]
+
+
+def _wanted(names, args, need, offered=None):
+    """the gradient names ("d_" + argument) that are needed, of arguments that were given (and that the configuration offers)"""
+    return tuple("d_" + n for k, n in enumerate(names) if need[k] and args[k] is not None and (offered is None or "d_" + n in offered))
 
 
 class _WbcTick(torch.autograd.Function):
+    """wbc_tick (q None: the state is inputs["q"] and gets no gradient) and wbc_tick_state"""
     @staticmethod
-    def forward(ctx, task_params, ee_target, prev_ee_target, trunk_target, prev_trunk_target, com_target, com_target_vel, posture_u, inputs, dt,
+    def forward(ctx, q, task_params, ee_target, prev_ee_target, trunk_target, prev_trunk_target, com_target, com_target_vel, posture_u, inputs, dt,
                 batch):
-        args = [_c(t) for t in (task_params, ee_target, prev_ee_target, trunk_target, prev_trunk_target, com_target, com_target_vel, posture_u)]
-        d = dict(inputs)
-        for name, a in zip(_TICK_ARGS[1:], args[1:]):
-            if a is not None:
-                d[name] = a
-        t = batch.tick(d, dt, want_working_set=True, task_params=args[0])
+        args = [_c(t) for t in (q, task_params, ee_target, prev_ee_target, trunk_target, prev_trunk_target, com_target, com_target_vel, posture_u)]
+        d = _merged(inputs, _STATE_ARGS, args)
+        t = batch.tick(d, dt, want_working_set=True, task_params=args[1])
         ctx.batch, ctx.dt = batch, dt
-        given = {name for name, a in zip(_TICK_ARGS, args) if a is not None}
+        given = {_IN_NAME[n] for n, a in zip(_STATE_ARGS, args) if a is not None and n in _IN_NAME}
         ctx.rest = {k: v for k, v in d.items() if k not in given}          # (what came in `inputs`: not ours to version-check)
-        ctx.present = [a is not None for a in args]
-        ctx.save_for_backward(t["qdot"], t["status"], t["working_set"], *[a for a in args if a is not None])
+        _save(ctx, (t["qdot"], t["status"], t["working_set"]), args)
         ctx.mark_non_differentiable(t["status"])
         return t["qdot"], t["status"]
 
     @staticmethod
     def backward(ctx, gq, _gst):
-        qdot, st, ws, *given = ctx.saved_tensors
-        n_out = len(_TICK_ARGS) + 3
-        if gq is None:              # qdot took no part in the loss
+        import wbc_workload
+        (qdot, st, ws), args = _saved(ctx, 3)
+        n_out = len(_STATE_ARGS) + 3
+        want = _wanted(_STATE_ARGS, args, ctx.needs_input_grad)
+        need_q, want = "d_q" in want, tuple(n for n in want if n != "d_q")
+        if gq is None or not (want or need_q):              # qdot took no part in the loss, or nothing is asked for
             return (None,) * n_out
-        it = iter(given)
-        args = [next(it) if have else None for have in ctx.present]
-        need = ctx.needs_input_grad
-        want = tuple("d_" + name for k, name in enumerate(_TICK_ARGS) if need[k] and args[k] is not None)
-        if not want:
-            return (None,) * n_out
-        bt = ctx.batch
-        d = dict(ctx.rest)
-        for name, a in zip(_TICK_ARGS[1:], args[1:]):
-            if a is not None:
-                d[name] = a
-        c = bt.tick_certificate(d, ctx.dt, task_params=args[0], v=gq.contiguous(), tick=dict(qdot=qdot, status=st, working_set=ws))
-        g = bt.tick_vjp(d, ctx.dt, qdot, c["sens_x"], status=st, cert_status=c["cert_status"], task_params=args[0], want=want)
-        return tuple(g.get("d_" + name) if ("d_" + name) in want else None for name in _TICK_ARGS) + (None, None, None)
+        bt, tp = ctx.batch, args[1]
+        d = _merged(ctx.rest, _STATE_ARGS, args)
+        c = bt.tick_certificate(d, ctx.dt, task_params=tp, v=gq.contiguous(), tick=dict(qdot=qdot, status=st, working_set=ws))
+        # one launch per layer that is asked for: no wbc_tick_vjp without one of its gradients, no wbc_tick_vjp_state without q's
+        g = bt.tick_vjp(d, ctx.dt, qdot, c["sens_x"], status=st, cert_status=c["cert_status"], task_params=tp, want=want) if want else {}
+        if need_q:
+            s = bt.tick_vjp_state(d, ctx.dt, qdot, c["sens_x"], sens_bounds=c["sens_bounds"], sens_rows=c["sens_rows"], y_rows=c["y_rows"], status=st,
+                                  cert_status=c["cert_status"], working_set=ws, task_params=tp, want=("d_q",))
+            g["d_q"] = wbc_workload.tangent_to_raw(args[0], s["d_q"])
+        return tuple(g.get("d_" + n) for n in _STATE_ARGS) + (None, None, None)
 
 
 def wbc_tick(task_params, ee_target, prev_ee_target, trunk_target, prev_trunk_target, com_target, com_target_vel, posture_u, inputs, dt, batch):
@@ -133,55 +158,8 @@ def wbc_tick(task_params, ee_target, prev_ee_target, trunk_target, prev_trunk_ta
     keyed like WbcTickIn that holds everything else: q, trunk_box_center, the orientation references, model_id ...) and gets no gradient. An
     argument the configuration does not read (trunk_target without the trunk task ...) must be None or not require a gradient. Instances
     whose QP was not solved or whose certificate is not WBC_CERT_OK get zero gradients. No gradient flows to q or anything else in `inputs`."""
-    return _WbcTick.apply(task_params, ee_target, prev_ee_target, trunk_target, prev_trunk_target, com_target, com_target_vel, posture_u, inputs, dt,
-                          batch)
-
-
-class _WbcTickState(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, q, task_params, ee_target, prev_ee_target, trunk_target, prev_trunk_target, com_target, com_target_vel, posture_u, inputs, dt,
-                batch):
-        args = [_c(t) for t in (task_params, ee_target, prev_ee_target, trunk_target, prev_trunk_target, com_target, com_target_vel, posture_u)]
-        d = dict(inputs)
-        d["q"] = _c(q)
-        for name, a in zip(_TICK_ARGS[1:], args[1:]):
-            if a is not None:
-                d[name] = a
-        t = batch.tick(d, dt, want_working_set=True, task_params=args[0])
-        ctx.batch, ctx.dt = batch, dt
-        given = {name for name, a in zip(_TICK_ARGS, args) if a is not None} | {"q"}
-        ctx.rest = {k: v for k, v in d.items() if k not in given}          # (what came in `inputs`: not ours to version-check)
-        ctx.present = [a is not None for a in args]
-        ctx.save_for_backward(t["qdot"], t["status"], t["working_set"], d["q"], *[a for a in args if a is not None])
-        ctx.mark_non_differentiable(t["status"])
-        return t["qdot"], t["status"]
-
-    @staticmethod
-    def backward(ctx, gq, _gst):
-        import wbc_workload
-        qdot, st, ws, q, *given = ctx.saved_tensors
-        n_out = 1 + len(_TICK_ARGS) + 3
-        if gq is None:              # qdot took no part in the loss
-            return (None,) * n_out
-        it = iter(given)
-        args = [next(it) if have else None for have in ctx.present]
-        need = ctx.needs_input_grad
-        want = tuple("d_" + name for k, name in enumerate(_TICK_ARGS) if need[1 + k] and args[k] is not None)
-        if not want and not need[0]:
-            return (None,) * n_out
-        bt = ctx.batch
-        d = dict(ctx.rest, q=q)
-        for name, a in zip(_TICK_ARGS[1:], args[1:]):
-            if a is not None:
-                d[name] = a
-        c = bt.tick_certificate(d, ctx.dt, task_params=args[0], v=gq.contiguous(), tick=dict(qdot=qdot, status=st, working_set=ws))
-        g = bt.tick_vjp(d, ctx.dt, qdot, c["sens_x"], status=st, cert_status=c["cert_status"], task_params=args[0], want=want) if want else {}
-        gq_raw = None
-        if need[0]:
-            s = bt.tick_vjp_state(d, ctx.dt, qdot, c["sens_x"], sens_bounds=c["sens_bounds"], sens_rows=c["sens_rows"], y_rows=c["y_rows"], status=st,
-                                  cert_status=c["cert_status"], working_set=ws, task_params=args[0], want=("d_q",))
-            gq_raw = wbc_workload.tangent_to_raw(q, s["d_q"])
-        return (gq_raw,) + tuple(g.get("d_" + name) if ("d_" + name) in want else None for name in _TICK_ARGS) + (None, None, None)
+    return _WbcTick.apply(None, task_params, ee_target, prev_ee_target, trunk_target, prev_trunk_target, com_target, com_target_vel, posture_u, inputs,
+                          dt, batch)
 
 
 def wbc_tick_state(q, task_params, ee_target, prev_ee_target, trunk_target, prev_trunk_target, com_target, com_target_vel, posture_u, inputs, dt,
@@ -190,8 +168,8 @@ def wbc_tick_state(q, task_params, ee_target, prev_ee_target, trunk_target, prev
     gradient is that of the tick composed with the normalisation of q's quaternion, in raw coordinates (wbc_workload.tangent_to_raw of
     wbc_tick_vjp_state's d_q). The other eight arguments and their gradients are wbc_tick's. posture_u (MANI / HYBRID / CUSTOM: it must be
     given) and the orientation references are held constant; inputs must not hold q_con. No gradient flows to anything else in `inputs`."""
-    return _WbcTickState.apply(q, task_params, ee_target, prev_ee_target, trunk_target, prev_trunk_target, com_target, com_target_vel, posture_u,
-                               inputs, dt, batch)
+    return _WbcTick.apply(q, task_params, ee_target, prev_ee_target, trunk_target, prev_trunk_target, com_target, com_target_vel, posture_u,
+                          inputs, dt, batch)
 
 
 class _WbcStep(torch.autograd.Function):
@@ -281,46 +259,29 @@ def wbc_rollout(q0, task_params, ee_target, prev_ee_target, trunk_target, prev_t
     return q, qdot, status, states
 
 
-_FUSED_ARGS = ("q0",) + _TICK_ARGS + ("ee_target_step", "trunk_target_step")
-
-
 class _WbcRolloutFused(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q0, task_params, ee_target, prev_ee_target, trunk_target, prev_trunk_target, com_target, com_target_vel, posture_u,
                 ee_target_step, trunk_target_step, inputs, dt, ticks, batch, mode, imu):
         args = [_c(t) for t in (q0, task_params, ee_target, prev_ee_target, trunk_target, prev_trunk_target, com_target, com_target_vel, posture_u,
                                 ee_target_step, trunk_target_step)]
-        d = dict(inputs)
-        d["q"] = args[0]
-        for name, a in zip(_TICK_ARGS[1:], args[2:9]):
-            if a is not None:
-                d[name] = a
+        d = _merged(inputs, _FUSED_ARGS, args)
         es = None if args[9] is None else args[9].reshape(-1, capi.NEE, 3)
         out, tape = batch.rollout_record(d, dt, ticks, ee_target_step=es, trunk_target_step=args[10], imu=_c(imu), mode=mode, task_params=args[1])
         ctx.batch, ctx.tape = batch, tape
-        ctx.present = [a is not None for a in args]
-        # through save_for_backward: an in-place change of an argument between forward and backward is an autograd error, not a sweep over other data
-        ctx.save_for_backward(out["q"], out["q_trace"], *[a for a in args if a is not None])
+        _save(ctx, (out["q"], out["q_trace"]), args)
         ctx.mark_non_differentiable(out["status"])
         return out["q"], out["qdot"], out["status"], out["q_trace"]
 
     @staticmethod
     def backward(ctx, g_q, g_qdot, _gst, g_trace):
         import wbc_workload
-        q_final, q_trace, *given = ctx.saved_tensors
+        (q_final, q_trace), args = _saved(ctx, 2)
         n_out = len(_FUSED_ARGS) + 6
-        if g_q is None and g_qdot is None and g_trace is None:
-            return (None,) * n_out
-        it = iter(given)
-        args = [next(it) if have else None for have in ctx.present]
-        need = ctx.needs_input_grad
         bt, tape = ctx.batch, ctx.tape
         K, B = tape.ticks, tape.B
-        offered = set(bt.default_rollout_grad_wants(tape.call["mode"]))
-        names = ("d_q0", "d_task_params", "d_ee_target", "d_prev_ee_target", "d_trunk_target", "d_prev_trunk_target", "d_com_target",
-                 "d_com_target_vel", "d_posture_u", "d_ee_target_step", "d_trunk_target_step")
-        want = tuple(n for k, n in enumerate(names) if need[k] and args[k] is not None and n in offered)
-        if not want:
+        want = _wanted(_FUSED_ARGS, args, ctx.needs_input_grad, set(bt.default_rollout_grad_wants(tape.call["mode"])))
+        if (g_q is None and g_qdot is None and g_trace is None) or not want:
             return (None,) * n_out
         # the seeds: raw -> tangent coordinates, q_K's and the trace's in one call
         raw, at = [], []
@@ -338,14 +299,8 @@ class _WbcRolloutFused(torch.autograd.Function):
             if g_trace is not None:
                 gq_t = tang[-K * B:].reshape(K, B, -1).contiguous()
         r = bt.rollout_vjp(tape, g_q_final=gq_f, g_qdot_last=None if g_qdot is None else g_qdot.contiguous(), g_q_trace=gq_t, want=want)
-        res = []
-        for k, n in enumerate(names):
-            if n not in want:
-                res.append(None)
-            elif n == "d_q0":
-                res.append(wbc_workload.tangent_to_raw(args[0], r[n]))
-            else:
-                res.append(r[n].reshape(args[k].shape))
+        res = [None if "d_" + n not in want else r["d_" + n].reshape(a.shape) if n != "q0" else wbc_workload.tangent_to_raw(a, r["d_q0"])
+               for n, a in zip(_FUSED_ARGS, args)]
         return tuple(res) + (None,) * 6
 
 

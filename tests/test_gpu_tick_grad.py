@@ -261,7 +261,7 @@ def test_torch_layer_backward_is_tick_grad():
 
     class Ctx:
         saved_tensors, batch, dt, rest, present = node.saved_tensors, node.batch, node.dt, node.rest, node.present
-        needs_input_grad = (True, False, False, False, True, False, False, False, False, False, False)
+        needs_input_grad = (False, True, False, False, False, True, False, False, False, False, False, False)      # (q, which wbc_tick leaves None, first)
     out = wbc_torch._WbcTick.backward(Ctx, torch.from_numpy(v).cuda(), None)
-    assert len(out) == 11 and [o is not None for o in out] == [True, False, False, False, True] + [False] * 6
+    assert len(out) == 12 and [o is not None for o in out] == [False, True, False, False, False, True] + [False] * 6
     bt.close()

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """What a roll-out gradient costs in two calls against the chained layers (recorded, not gated): on the benchmark's c3 inputs, K = 16 ticks,
-B = 256, 4096 and 65536 in one process, device tensors in place, forward + backward of the loss rho . q_K with gradients to q0, ee_target
+B = 256, 4096 and 65536 (or the batches of argv[3]) in one process, device tensors in place, forward + backward of the loss rho . q_K with gradients to q0, ee_target
 and the task rows,
     fused     wbc_torch.wbc_rollout_fused: one wbc_rollout_record, one wbc_rollout_vjp
     chain     wbc_torch.wbc_rollout: per tick wbc_tick_state -> wbc_step, autograd through the layers
@@ -8,7 +8,7 @@ and the task rows,
     vjp       WbcBatch.rollout_vjp alone               tick      wbc_tick alone (the unit the per-reverse-tick cost is stated in)
 tools/time_step_vjp.py's protocol: warm-up, then ROUNDS rounds that alternate the runs, each REPS repeats between two device events; the
 median over rounds and the spread (min .. max). Writes profiles/r24_rollout_vjp.txt (or argv[1]).
-    python3 tools/time_rollout_vjp.py [out.txt] [K]"""
+    python3 tools/time_rollout_vjp.py [out.txt] [K] [B,B,...]"""
 import json
 import os
 import sys
@@ -26,7 +26,7 @@ from wbc_batch import WbcBatch
 
 OUT = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "r24_rollout_vjp.txt")
 K = int(sys.argv[2]) if len(sys.argv) > 2 else 16
-BATCHES = (256, 4096, 65536)
+BATCHES = tuple(int(x) for x in sys.argv[3].split(",")) if len(sys.argv) > 3 else (256, 4096, 65536)
 DT, ROUNDS, REPS, WARM = 0.002, 5, 3, 2
 
 assert torch.cuda.is_available(), "time_rollout_vjp.py measures on the GPU; there is nothing to report without one"
