@@ -603,7 +603,8 @@ typedef struct WbcRolloutGrad {       /* all optional; an output left NULL is no
  * have their size a call allocates nothing, and with device buffers both calls can be captured into a HIP graph.
  * WBC_E_ARG, naming the field, before any launch: no seed; what wbc_rollout_record refuses; an output whose inputs the configuration does
  * not read (the rules of wbc_tick_vjp and wbc_tick_vjp_state; d_*_target_step as d_*_target). WBC_E_UNSUPPORTED as wbc_rollout_record.
- * Not offered: hold_ticks, the trajectory / tracks / watch roll-outs, checkpoint-and-recompute (the tape holds every tick).
+ * Not offered: hold_ticks, the one-track trajectory call and the watch roll-outs (roll-outs along tracks: wbc_rollout_record_tracks /
+ * wbc_rollout_vjp_tracks below), checkpoint-and-recompute (the tape holds every tick).
  * Statistic "last_rollvjp_variant": the row of csrc/wbc_k_rollvjp.hip's table the last call launched last (key of the stage: 0 BEGIN, 1 ADDV,
  * 2 LINK), -1 before the first; wbc_variant_count("rollvjp") == 3. */
 int wbc_rollout_vjp(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r, const void* tape,
@@ -719,6 +720,54 @@ typedef struct WbcTrackScores {  /* all arrays optional */
  * floating-point atomics. Per tick: the tick and update kernels of wbc_rollout plus ONE launch of the trajectory kernel however many tracks. */
 int wbc_rollout_tracks(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
                        const WbcTracks* tracks, const WbcTrackScores* scores /* may be NULL */, int mem, void* stream);
+
+/* ------------------------------------------------------------------ roll-out gradients along tracks: dL/d(milestones, tangents, speed)
+ * wbc_rollout_record_tracks is wbc_rollout_tracks that also writes wbc_rollout_record's tape (same layout, same wbc_rollout_tape_bytes: the
+ * tape holds every target as the tick saw it, followed or not); wbc_rollout_vjp_tracks is wbc_rollout_vjp's sweep with the target
+ * bookkeeping of a followed target replaced by the adjoint of the track evaluation. Every output of the record call, the
+ * scores included, is bit-identical to wbc_rollout_tracks' on the same inputs and handle state. It refuses what wbc_rollout_tracks refuses,
+ * what wbc_rollout_record refuses, and tracks == NULL (the plain call exists for that).
+ * THE SWEEP. Forward, a followed target is E_k = eval_b(k * du_b) on every tick (the PRODUCT; tick 0 gets eval(0), in0's followed row is not
+ * read), and P_(k+1) = E_k where the task is on, as before. So for a followed end effector at tick k the whole cotangent of E_k is
+ *     e_k = a_k + on o Pbar        (a_k = tick.d_ee_target + step.d_foot_targets; the trunk track: the same under task_trunk)
+ * it goes into the track and nothing is carried: Ebar of a followed row is 0 in front of every tick; Pbar updates as in wbc_rollout_vjp.
+ * Adjoint of the evaluation, with t = (double)k * du, n = n_points and the forward's own comparisons:
+ *   t <= 0: d_points[0] += e.   t >= n - 1: d_points[n - 1] += e (neither gives anything to d_du).   Otherwise i = floor(t), u = t - i (at an
+ *   exact knot the forward selects segment i with u = 0, and d_du uses that segment's derivative) and
+ *   LINEAR   d_points[i] += (1 - u) e; d_points[i + 1] += u e; d_du += k ((x + y) + z), x, y, z = (m[i + 1][c] - m[i][c]) e[c].
+ *   HERMITE  d_points[i] += cx1 e; d_points[i + 1] += cx2 e; vbar_i = cv1 e, vbar_(i+1) = cv2 e; d_du += k ((x + y) + z) with, per component,
+ *            ((((6 u2 - 6 u) m[i] + (-6 u2 + 6 u) m[i + 1]) + ((3 u2 - 4 u) + 1) v[i]) + (3 u2 - 2 u) v[i + 1]) e. Caller tangents:
+ *            d_tangents[i] += vbar_i, d_tangents[i + 1] += vbar_(i+1). Default tangents: vbar goes through the branch the rule took for that
+ *            milestone and component (first milestone i, then i + 1; the plus term first): n = 2: +vbar to m[1], -vbar to m[0]; end
+ *            milestones and case (1): nothing; (2) +3 vbar to m[i], -3 vbar to m[i - 1]; (3) +3 vbar to m[i + 1], -3 vbar to m[i];
+ *            (4) +vbar / 2 to m[i + 1], -vbar / 2 to m[i - 1].
+ * Every entry is summed in reverse tick order by one lane, without atomics or contraction: two identical calls give identical bits and the
+ * host restatement (wbc_workload.track_target_gradients) runs the same operations in the same order.
+ * EXACT ZEROS AND BAD ROWS. The followed rows of d_ee_target / d_trunk_target are exactly 0; rows of d_points / d_tangents at or beyond
+ * n_points[b] are exactly 0. A bad row (wbc_rollout_tracks' definition) gets all-zero rows in every output of the call and grad_status
+ * WBC_GRAD_NONFINITE, as an instance with WBC_GRAD_NONFINITE from any layer; the other instances keep their bits; rows >= B are never
+ * written. Unsolved ticks are dropped by wbc_rollout_vjp's rule; what reaches a dropped tick's targets through the step still flows into the track.
+ * WBC_E_ARG, naming the field, before any launch: d_ee_target_step (no step exists under tracks); d_trunk_target_step together with a trunk
+ * track (without one trunk_target_step stays allowed and d_trunk_target_step is wbc_rollout_vjp's); d_tangents on a LINEAR track or a
+ * HERMITE track with tangents == NULL; tracks_out NULL; a tracks_out->track[j] member set for j >= n_tracks; what wbc_rollout_tracks and
+ * what wbc_rollout_vjp refuse.
+ * Not offered: hold ticks, the watch, the scores as a loss, gradients with respect to n_points, checkpoint-and-recompute.
+ * Neither call allocates once the workspaces have their size; with device buffers both can be captured into a HIP graph.
+ * Statistic "last_trackvjp_variant": the row of csrc/wbc_k_trackvjp.hip's table the last call launched last (key of the stage: 0 BEGIN,
+ * 1 TICK), -1 before the first; wbc_variant_count("trackvjp") == 2. */
+typedef struct WbcTrackGrad {          /* all optional; an output left NULL is not written */
+  double* d_points;                    /* [B][S][3], S = the track's max_points; rows >= n_points[b] exactly 0 */
+  double* d_tangents;                  /* [B][S][3]; HERMITE with caller tangents only */
+  double* d_du;                        /* [B] (also when the track uses du_all: the caller sums) */
+} WbcTrackGrad;
+typedef struct WbcTracksGrad { WbcTrackGrad track[WBC_MAX_TRACKS]; } WbcTracksGrad;   /* track[j] belongs to tracks->track[j] */
+int wbc_rollout_record_tracks(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
+                              const WbcTracks* tracks, const WbcTrackScores* scores /* may be NULL */, void* tape, size_t tape_bytes,
+                              double* q_trace, int mem, void* stream);
+int wbc_rollout_vjp_tracks(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
+                           const WbcTracks* tracks, const void* tape, size_t tape_bytes, const WbcRolloutSeed* seed, int mem,
+                           const WbcRolloutGrad* out, const WbcTracksGrad* tracks_out, void* stream);
+int wbc_rollout_tracks_grad_sizes(int32_t* sizeof_track_grad, int32_t* sizeof_tracks_grad); /* ctypes layout self-check */
 
 /* ------------------------------------------------------------------ constraint slack: CoM box, trunk box, joint range
  * How far a configuration is from the reference's constraint limits, whether or not the configuration enforces them: what sim3.py prints

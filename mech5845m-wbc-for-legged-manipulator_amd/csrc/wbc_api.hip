@@ -14,6 +14,7 @@
 #include "wbc_gradq.h"
 #include "wbc_stepvjp.h"
 #include "wbc_rollvjp.h"
+#include "wbc_trackvjp.h"
 
 // (the layouts of the handle's roll-out workspaces d_roll, d_traj and d_slack: RollWs, TrajWs and SlackWs below)
 
@@ -98,6 +99,7 @@ struct WbcBatch {
   long long last_gradq_variant;  // ... and of the last wbc_tick_vjp_state launch
   long long last_stepvjp_variant;   // ... and of the last wbc_step_vjp launch
   long long last_rollvjp_variant;   // ... and of the last link-kernel launch of wbc_rollout_vjp
+  long long last_trackvjp_variant;  // ... and of the last track-adjoint launch of wbc_rollout_vjp_tracks
   long long last_tick_variant, last_qp_variant;   // variant_key(...) of the row the last tick / assemble / fk launch and the last stand-alone QP launch resolved (-1: none yet)
   int sim3p_fixd;        // option [1]: the packed sim3 kernel's FIXD form where the handle qualifies (fixd_dims)
   bool fixd_dims[WBC_MAX_MODELS];   // wbc_batch_configure: the model's plan has exactly the SIM3P_FIXD_* dimensions
@@ -409,7 +411,7 @@ extern "C" int wbc_batch_create(const WbcModel* const* models, int n_models, int
   if (!b) return fail(WBC_E_ARG, "out of memory");
   memset(b, 0, sizeof *b);
   b->device_id = device_id; b->n_models = n_models; b->max_batch = max_batch; b->presolve = 1; b->presolve_orth = 1; b->packed_update = 1; b->sim3_kernel = 1; b->sing_tol = 1e-7; b->wave_order = 1; b->sim3p_fixd = 1;
-  b->last_tick_variant = b->last_qp_variant = b->last_grad_variant = b->last_gradq_variant = b->last_stepvjp_variant = b->last_rollvjp_variant = -1;
+  b->last_tick_variant = b->last_qp_variant = b->last_grad_variant = b->last_gradq_variant = b->last_stepvjp_variant = b->last_rollvjp_variant = b->last_trackvjp_variant = -1;
   b->jtj_mfma = -1; b->refine = 1; b->packed_min_batch = WBC_SIM3P_MIN_BATCH; b->warm_start = 0; b->packed_kernel = 1; b->packed_orth = 1; b->packed_box = 1; b->posture_par = 1;
   std::vector<DevModel> dm(n_models);
   for (int i = 0; i < n_models; ++i) {
@@ -919,6 +921,7 @@ extern "C" int wbc_batch_get_stat(WbcBatch* b, const char* name, void* stream, i
   if (!strcmp(name, "last_gradq_variant")) { *out = b->last_gradq_variant; return WBC_OK; }
   if (!strcmp(name, "last_stepvjp_variant")) { *out = b->last_stepvjp_variant; return WBC_OK; }
   if (!strcmp(name, "last_rollvjp_variant")) { *out = b->last_rollvjp_variant; return WBC_OK; }
+  if (!strcmp(name, "last_trackvjp_variant")) { *out = b->last_trackvjp_variant; return WBC_OK; }
   if (!strcmp(name, "last_update_packed")) { *out = b->last_update_packed; return WBC_OK; }
   if (!strcmp(name, "last_posture_par")) { *out = b->last_posture_par; return WBC_OK; }
   if (!strcmp(name, "last_orth")) { *out = (b->last_path == TICK_GENERAL || b->last_path == TICK_ORTHP) ? b->last_orth : 0; return WBC_OK; }
@@ -1848,12 +1851,37 @@ template <class T> static int ensure_size(T*& p, size_t& have, size_t want) {   
   have = want;
   return WBC_OK;
 }
-extern "C" int wbc_rollout_vjp(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r, const void* tape,
-                               size_t tape_bytes, const WbcRolloutSeed* seed, int mem, const WbcRolloutGrad* out, void* stream) {
-  const char* who = "wbc_rollout_vjp";
-  int rc = check_record_call(b, B, in0, r, tape, tape_bytes, who);
-  if (rc) return rc;
+static int check_tracks_call(int B, const WbcTickIn* in0, const WbcRollout* r, const WbcTracks* tracks, const WbcTrackScores* scores);
+// what wbc_rollout_vjp_tracks refuses beyond both calls' own refusals, before any launch
+static int check_tracks_grad(const WbcTracks& tk, const WbcRolloutGrad* out, const WbcTracksGrad* tg, const char* who) {
+  if (!tg) return fail(WBC_E_ARG, "%s: tracks_out is required", who);
+  if (out && out->d_ee_target_step) return fail(WBC_E_ARG, "%s: d_ee_target_step requested, but a roll-out along tracks has no ee_target_step", who);
+  for (int j = 0; j < WBC_MAX_TRACKS; ++j) {
+    const WbcTrackGrad& g = tg->track[j];
+    if (j >= tk.n_tracks) {
+      if (g.d_points || g.d_tangents || g.d_du)
+        return fail(WBC_E_ARG, "%s: tracks_out->track[%d] has an output set, but n_tracks = %d", who, j, tk.n_tracks);
+      continue;
+    }
+    const WbcTrack& t = tk.track[j];
+    if (t.target == WBC_TARGET_TRUNK && out && out->d_trunk_target_step)
+      return fail(WBC_E_ARG, "%s: d_trunk_target_step requested, but track %d moves the trunk target (there is no trunk_target_step)", who, j);
+    if (g.d_tangents && (t.kind != WBC_TRACK_HERMITE || !t.tangents))
+      return fail(WBC_E_ARG, "%s: tracks_out->track[%d].d_tangents requested, but the track is %s", who, j,
+                  t.kind != WBC_TRACK_HERMITE ? "LINEAR" : "HERMITE with tangents == NULL (the default rule: its gradient is part of d_points)");
+  }
+  return WBC_OK;
+}
+// The sweep of wbc_rollout_vjp and, with tracks, of wbc_rollout_vjp_tracks: the same launches, plus one stage of the track-adjoint kernel behind
+// the link kernel's BEGIN and behind every LINK.
+static int rollout_vjp_run(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r, const void* tape,
+                           size_t tape_bytes, const WbcRolloutSeed* seed, int mem, const WbcRolloutGrad* out, void* stream, const char* who,
+                           bool with_tracks, const WbcTracks* tracks, const WbcTracksGrad* tracks_out) {
+  int rc;
+  if (with_tracks && (rc = check_tracks_call(B, in0, r, tracks, nullptr))) return rc;   // (first: tracks == NULL is refused before a field of it is read)
+  if ((rc = check_record_call(b, B, in0, r, tape, tape_bytes, who))) return rc;
   if (!out) return fail(WBC_E_ARG, "%s: out is required", who);
+  if (with_tracks && (rc = check_tracks_grad(*tracks, out, tracks_out, who))) return rc;
   if (!seed || !(seed->g_q_final || seed->g_qdot_last || seed->g_q_trace))
     return fail(WBC_E_ARG, "%s: a seed is required (g_q_final, g_qdot_last or g_q_trace)", who);
   if ((rc = check_dt(dt, who))) return rc;
@@ -1886,6 +1914,14 @@ extern "C" int wbc_rollout_vjp(WbcBatch* b, int B, const WbcTickIn* in0, const W
   st.in(&sd.g_q_final, n * WBC_V_STRIDE); st.in(&sd.g_qdot_last, n * WBC_V_STRIDE); st.in(&sd.g_q_trace, (size_t)K * n * WBC_V_STRIDE);
   stage_outs(st, og, ROLL_OUT, n);
   st.out(&og.grad_status, n); st.out(&og.ticks_dropped, n);
+  WbcTracks tj = with_tracks ? *tracks : WbcTracks{};
+  WbcTracksGrad tg = with_tracks ? *tracks_out : WbcTracksGrad{};
+  for (int j = 0; j < tj.n_tracks; ++j) {
+    WbcTrack& t = tj.track[j];
+    const size_t np = n * (size_t)t.max_points * 3;
+    st.in(&t.points, np); st.in(&t.tangents, np); st.in(&t.n_points, n); st.in(&t.du, n);
+    st.out(&tg.track[j].d_points, np); st.out(&tg.track[j].d_tangents, np); st.out(&tg.track[j].d_du, n);
+  }
   if ((rc = st.stage())) return rc;
   const WbcTickIn first = a.in;
   const bool have_ws = b->warm_start != 0;   // the tape holds working sets (the option as it was when the tape was recorded: include/wbc.h)
@@ -1895,6 +1931,7 @@ extern "C" int wbc_rollout_vjp(WbcBatch* b, int B, const WbcTickIn* in0, const W
   // every tick: g needs it); each of its outputs is wired where the configuration reads what it is the gradient of
   bool want_tick = false;
   for (const OutRow<WbcRolloutGrad>& row : ROLL_OUT) want_tick |= og.*row.ptr && row.ptr != &WbcRolloutGrad::d_q0 && row.ptr != &WbcRolloutGrad::d_trunk_box_center;
+  for (int j = 0; j < tj.n_tracks; ++j) want_tick |= tg.track[j].d_points || tg.track[j].d_tangents || tg.track[j].d_du;   // (a track's cotangent is the tick layer's d_*_target)
   const WbcStepGrad s_out{w.s_dq, w.v, w.s_dft, w.gs_step};
   const WbcTickStateGrad q_out{w.t_dq, rd.con_trunk ? w.t_box : nullptr, w.gs_tickq};
   WbcQpCert c_out{};
@@ -1919,7 +1956,23 @@ extern "C" int wbc_rollout_vjp(WbcBatch* b, int B, const WbcTickIn* in0, const W
     L.k = k;
     return launch_rc(launch_rollvjp(L, stage, stream, &b->last_rollvjp_variant), "roll-out gradient link");
   };
+  TrackVjpArgs V;
+  memset(&V, 0, sizeof V);
+  V.B = B; V.n_tracks = tj.n_tracks; V.Ebar = w.Ebar; V.TEbar = w.TEbar; V.worst = w.worst;
+  V.d_ee_target = og.d_ee_target; V.d_trunk_target = og.d_trunk_target;
+  for (int j = 0; j < tj.n_tracks; ++j) {
+    const WbcTrack& t = tj.track[j];
+    TrackVjpTrack& d = V.tr[j];
+    d.target = t.target; d.kind = t.kind; d.S = t.max_points;
+    d.points = t.points; d.tangents = t.tangents; d.n_points = t.n_points; d.du = t.du; d.du_all = t.du_all;
+    d.d_points = tg.track[j].d_points; d.d_tangents = tg.track[j].d_tangents; d.d_du = tg.track[j].d_du;
+  }
+  auto track = [&](int stage, int k) {   // (with tracks alone: the plain sweep launches what it launched)
+    V.k = k;
+    return launch_rc(launch_trackvjp(V, stage, stream, &b->last_trackvjp_variant), "roll-out gradient track adjoint");
+  };
   if ((rc = link(ROLLVJP_BEGIN, K - 1))) return rc;
+  if (with_tracks && (rc = track(TRACKVJP_BEGIN, K - 1))) return rc;
   for (int k = K - 1; k >= 0; --k) {
     const TapeWs T = TapeWs::carve(tp_mut, n, k);
     WbcTickIn in = first;   // the inputs tick k saw
@@ -1952,8 +2005,13 @@ extern "C" int wbc_rollout_vjp(WbcBatch* b, int B, const WbcTickIn* in0, const W
     sn.status = T.status; sn.cert_status = w.cert_status; sn.working_set = qp.working_set;
     if ((rc = tickq_layer(b, B, dt, in, tp, sn, q_out, stream))) return rc;
     if ((rc = link(ROLLVJP_LINK, k))) return rc;
+    if (with_tracks && (rc = track(TRACKVJP_TICK, k))) return rc;
   }
   return st.finish();
+}
+extern "C" int wbc_rollout_vjp(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r, const void* tape,
+                               size_t tape_bytes, const WbcRolloutSeed* seed, int mem, const WbcRolloutGrad* out, void* stream) {
+  return rollout_vjp_run(b, B, in0, tp, dt, r, tape, tape_bytes, seed, mem, out, stream, "wbc_rollout_vjp", false, nullptr, nullptr);
 }
 extern "C" int wbc_rollout_grad_sizes(int32_t* sizeof_seed, int32_t* sizeof_grad) {
   if (sizeof_seed) *sizeof_seed = (int32_t)sizeof(WbcRolloutSeed);
@@ -2004,7 +2062,7 @@ extern "C" int wbc_rollout_traj(WbcBatch* b, int B, const WbcTickIn* in0, const 
 
 // The argument checks of wbc_rollout_tracks (several followed targets — WbcTracks: end effectors and trunk, LINEAR or HERMITE — any frame
 // scored: WbcTrackScores), also wbc_rollout_watch's with tracks.
-static int check_tracks_call(int B, const WbcTickIn* in0, const WbcRollout* r, const WbcTracks* tracks, const WbcTrackScores* scores) {
+static int check_tracks_call(int B, const WbcTickIn* in0, const WbcRollout* r, const WbcTracks* tracks, const WbcTrackScores* scores) {   // (declared above the sweep)
   const char* who = "wbc_rollout_tracks";
   if (!r || !tracks) return fail(WBC_E_ARG, "wbc_rollout_tracks: r and tracks are required");
   if (r->ee_target_step) return fail(WBC_E_ARG, "wbc_rollout_tracks: ee_target_step must be NULL (tracks move the followed targets; the other EE targets are constant)");
@@ -2040,6 +2098,30 @@ extern "C" int wbc_rollout_tracks(WbcBatch* b, int B, const WbcTickIn* in0, cons
   if (int rc = check_tracks_call(B, in0, r, tracks, scores)) return rc;
   TracksExt tk(*tracks, scores, false);
   return rollout_run(b, B, in0, tp, dt, r, mem, stream, &tk);
+}
+
+// The recorded roll-out along tracks and its sweep (include/wbc.h): wbc_rollout_tracks' loop with the record extension behind
+// the tracks extension (tick k's part of the tape holds the followed targets the tick saw), then wbc_rollout_vjp's sweep with the adjoint of
+// the track evaluation behind every link stage.
+static_assert(sizeof(WbcTrackGrad) == 3 * sizeof(void*) && sizeof(WbcTracksGrad) == WBC_MAX_TRACKS * sizeof(WbcTrackGrad), "wbc_capi.WbcTrackGrad / WbcTracksGrad");
+extern "C" int wbc_rollout_record_tracks(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
+                                         const WbcTracks* tracks, const WbcTrackScores* scores, void* tape, size_t tape_bytes, double* q_trace,
+                                         int mem, void* stream) {
+  int rc;
+  if ((rc = check_tracks_call(B, in0, r, tracks, scores)) || (rc = check_record_call(b, B, in0, r, tape, tape_bytes, "wbc_rollout_record_tracks"))) return rc;
+  TracksExt tk(*tracks, scores, false);
+  RecordExt rx(tape, q_trace);
+  return rollout_run(b, B, in0, tp, dt, r, mem, stream, &tk, nullptr, &rx);
+}
+extern "C" int wbc_rollout_vjp_tracks(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
+                                      const WbcTracks* tracks, const void* tape, size_t tape_bytes, const WbcRolloutSeed* seed, int mem,
+                                      const WbcRolloutGrad* out, const WbcTracksGrad* tracks_out, void* stream) {
+  return rollout_vjp_run(b, B, in0, tp, dt, r, tape, tape_bytes, seed, mem, out, stream, "wbc_rollout_vjp_tracks", true, tracks, tracks_out);
+}
+extern "C" int wbc_rollout_tracks_grad_sizes(int32_t* sizeof_track_grad, int32_t* sizeof_tracks_grad) {
+  if (sizeof_track_grad) *sizeof_track_grad = (int32_t)sizeof(WbcTrackGrad);
+  if (sizeof_tracks_grad) *sizeof_tracks_grad = (int32_t)sizeof(WbcTracksGrad);
+  return WBC_OK;
 }
 
 // The roll-outs with the slack families watched (WbcSlackWatch): the watch's own argument checks, then the tracks call's (with tracks) and
@@ -2326,6 +2408,7 @@ extern "C" int wbc_variant_count(const char* family) {
   if (!strcmp(family, "gradq")) return gradq_variant_count();
   if (!strcmp(family, "stepvjp")) return stepvjp_variant_count();
   if (!strcmp(family, "rollvjp")) return rollvjp_variant_count();
+  if (!strcmp(family, "trackvjp")) return trackvjp_variant_count();
   return fail(WBC_E_ARG, "wbc_variant_count: unknown kernel family %s", family);
 }
 extern "C" int wbc_abi_sizes(int32_t* sb, int32_t* sc) {

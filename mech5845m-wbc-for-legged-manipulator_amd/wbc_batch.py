@@ -198,7 +198,7 @@ class WbcBatch:
     def stat(self, name, stream=None):
         """wbc_batch_get_stat: "last_path" (0 general, 1 compact sim3, 2 packed sim3, 3 packed orth — equality-only or INEQ variant —, 4 packed box), "last_orth", "last_posture_par",
         "last_update_packed", "last_qp_path" (problems per wavefront of the last stand-alone QP call: 1, 2 or 4), "last_tick_variant" /
-        "last_qp_variant" (the variant-table row of the last tick / assemble / fk and stand-alone QP launch: wbc_capi.variant_args), "last_grad_variant" / "last_gradq_variant" / "last_stepvjp_variant" (the same for the last wbc_tick_vjp / wbc_tick_vjp_state / wbc_step_vjp launch), "last_tick_fixd" (1: the last tick ran the
+        "last_qp_variant" (the variant-table row of the last tick / assemble / fk and stand-alone QP launch: wbc_capi.variant_args), "last_grad_variant" / "last_gradq_variant" / "last_stepvjp_variant" / "last_rollvjp_variant" / "last_trackvjp_variant" (the same for the last wbc_tick_vjp / wbc_tick_vjp_state / wbc_step_vjp launch, the last link-kernel launch of wbc_rollout_vjp and the last track-adjoint launch of wbc_rollout_vjp_tracks), "last_tick_fixd" (1: the last tick ran the
         packed sim3 kernel's FIXD form, option "sim3p_fixd"), "deferred_last", "pivoted_last", "wave_order_slices", "sim3_lds_bytes", "tick_lds_bytes", "orthp_lds_bytes"."""
         v = C.c_int64()
         capi.check(self.lib.wbc_batch_get_stat(self._h, name.encode(), stream, C.byref(v)), self.lib)
@@ -624,28 +624,56 @@ class WbcBatch:
         return out
 
     def rollout_record(self, inputs, dt, ticks, ee_target_step=None, trunk_target_step=None, imu=None, mode=capi.ROLLOUT_RUNNING,
-                       task_params=None, want_trace=True, tape=None):
+                       task_params=None, want_trace=True, tape=None, tracks=None, score=(), group_size=0):
         """wbc_rollout_record (include/wbc.h): rollout(..., want_trace=False) that also writes a tape for rollout_vjp. Returns (out, tape): out
         is rollout's dict plus q_trace [K, B, 27] (the state after every tick; want_trace); tape is a RolloutTape — device memory of
         wbc_rollout_tape_bytes(B, K) bytes (a torch uint8 tensor on the handle's device, allocated here or the caller's `tape.buf` when a
         RolloutTape of the same B and K is passed back in) together with the call's arguments, which rollout_vjp needs again. The ticks run
         exactly as rollout's do: under option "warm_start" they return working sets and the tape holds them. No hold ticks;
-        inputs must not hold q_con; posture modes MANI / HYBRID need inputs["posture_u"]."""
+        inputs must not hold q_con; posture modes MANI / HYBRID need inputs["posture_u"].
+        tracks (rollout_tracks' list of dicts; None: the call above, argument for argument): wbc_rollout_record_tracks — rollout_tracks(...,
+        score, group_size) that also writes the tape; out then holds rollout_tracks' results too, and rollout_vjp returns the gradients
+        with respect to every track's points, tangents and du. Not together with ee_target_step."""
         import torch
         keep = []
-        mem = _mem_of(list(inputs.values()) + [ee_target_step, trunk_target_step, imu, task_params])
+        arrays = []
+        if tracks is not None:
+            tracks = list(tracks)
+            if not 1 <= len(tracks) <= capi.MAX_TRACKS:
+                raise capi.WbcError("tracks: %d given, want 1..%d" % (len(tracks), capi.MAX_TRACKS))
+            arrays = self._track_arrays(tracks)
+        elif len(list(score)):
+            raise capi.WbcError("score: needs tracks")
+        mem = _mem_of(list(inputs.values()) + arrays + [ee_target_step, trunk_target_step, imu, task_params])
         B = self._batch_of(inputs.get("q"))
         K = int(ticks)
         out, r = self._rollout_base(inputs, B, keep, K, mode, 0, ee_target_step, trunk_target_step, imu, False)
+        tk = sc = None
+        if tracks is not None:
+            M = self._check_ticks_groups(B, K, group_size)
+            tk, _ = self._tracks_struct(tracks, B, keep)
+            frames = sorted({self._target_index(s_, "score") for s_ in score})
+            if len(frames) != len(list(score)):
+                raise capi.WbcError("score: a frame is listed twice")
+            if inputs.get("trunk_target") is not None:
+                out["trunk_target"] = self._alloc(inputs["q"], (B, 3))
+                tk.trunk_target_final = self._p(out["trunk_target"], np.float64, keep)
+            sc = self._scores_struct(out, inputs["q"], frames, B, K, M, False, keep)
         if want_trace and K >= 1:
             out["q_trace"] = self._alloc(inputs["q"], (K, B, NQS))
         nbytes = int(self.lib.wbc_rollout_tape_bytes(B, K))
         if tape is None or tape.B != B or tape.ticks != K:
             tape = RolloutTape(torch.empty(max(nbytes, 1), dtype=torch.uint8, device="cuda:%d" % self.device_id), B, K)
         tape.call = dict(inputs=dict(inputs), dt=float(dt), imu=imu, mode=int(mode), task_params=task_params,
-                         warm_start=getattr(self, "_options", {}).get("warm_start", 0))
+                         warm_start=getattr(self, "_options", {}).get("warm_start", 0),
+                         tracks=None if tracks is None else [dict(t) for t in tracks])
         tin = self._tick_in(inputs, keep, B)
         tp = _task_params(task_params, B, keep, self.device_id)
+        if tk is not None:
+            capi.check(self.lib.wbc_rollout_record_tracks(self._h, B, C.byref(tin), tp, float(dt), C.byref(r), C.byref(tk),
+                                                          C.byref(sc) if sc is not None else None, tape.buf.data_ptr(), nbytes,
+                                                          self._p(out.get("q_trace"), np.float64, keep), mem, self._stream(mem)), self.lib)
+            return out, tape
         capi.check(self.lib.wbc_rollout_record(self._h, B, C.byref(tin), tp, float(dt), C.byref(r), tape.buf.data_ptr(), nbytes,
                                                 self._p(out.get("q_trace"), np.float64, keep), mem, self._stream(mem)), self.lib)
         return out, tape
@@ -655,16 +683,41 @@ class WbcBatch:
         Seeds (numpy or torch, at least one; tangent coordinates — wbc_workload.raw_to_tangent turns a raw gradient into one): g_q_final
         [B,26] at q_K, g_qdot_last [B,26], g_q_trace [K,B,26] at the state after each tick. want: names of capi.ROLLOUT_GRAD_FIELDS (None:
         d_q0 and what the configuration reads); out: caller's arrays by those names (and "grad_status", "ticks_dropped") instead.
-        Returns dict(<want>..., grad_status [B] int32, ticks_dropped [B] int32); d_q0 is tangent at q_0 (wbc_workload.tangent_to_raw)."""
+        Returns dict(<want>..., grad_status [B] int32, ticks_dropped [B] int32); d_q0 is tangent at q_0 (wbc_workload.tangent_to_raw).
+        A tape recorded with tracks (wbc_rollout_vjp_tracks): the dict also holds tracks = [dict(d_points [B,S,3], d_tangents [B,S,3],
+        d_du [B]), ...], one per track in the call's order; want accepts those three names too (None: each where the track offers it —
+        d_tangents for a hermite track with caller tangents alone), and out may hold "tracks": a list of dicts of the caller's arrays."""
         keep = []
         c = tape.call
         inputs, B, K = c["inputs"], tape.B, tape.ticks
+        tracks = c.get("tracks")
         if getattr(self, "_options", {}).get("warm_start", 0) != c["warm_start"]:
             raise capi.WbcError("rollout_vjp: option warm_start changed since the tape was recorded (the tape holds working sets only with it)")
         like = next((a for a in (g_q_final, g_qdot_last, g_q_trace) if a is not None), inputs["q"])
-        out, o = self._grad_outs(capi.ROLLOUT_GRAD_FIELDS, capi.WbcRolloutGrad, like, B, keep, want, lambda: self.default_rollout_grad_wants(c["mode"]),
-                                 out, extras=("grad_status", "ticks_dropped"))
-        mem = _mem_of(list(inputs.values()) + list(out.values()) + [c["imu"], c["task_params"], g_q_final, g_qdot_last, g_q_trace])
+        default = lambda: self.default_rollout_grad_wants(c["mode"])
+        tk = tg = None
+        t_outs, arrays = [], []
+        if tracks is not None:     # the names of the track outputs leave `want` / `out`; what a roll-out along tracks has no step for leaves the default
+            tk, seen = self._tracks_struct(tracks, B, keep)
+            tg = capi.WbcTracksGrad()
+            no_step = {"d_ee_target_step"} | ({"d_trunk_target_step"} if capi.TARGET_TRUNK in seen else set())
+            default = lambda: tuple(k for k in self.default_rollout_grad_wants(c["mode"]) if k not in no_step)
+            track_want = None if want is None else tuple(k for k in want if k in capi.TRACK_GRAD_FIELDS)
+            want = None if want is None else tuple(k for k in want if k not in capi.TRACK_GRAD_FIELDS)
+            caller_tracks = None if out is None else out.get("tracks", [{}] * len(tracks))
+            out = None if out is None else {k: v for k, v in out.items() if k != "tracks"}
+            for j, t in enumerate(tracks):
+                fields = {k: tuple(int(t["points"].shape[1]) if d == "S" else d for d in shp) for k, shp in capi.TRACK_GRAD_FIELDS.items()}
+                offered = tuple(k for k in fields if k != "d_tangents" or (tk.track[j].kind == capi.TRACK_HERMITE and t.get("tangents") is not None))
+                t_out, t_struct = self._grad_outs(fields, capi.WbcTrackGrad, like, B, keep,
+                                                  offered if track_want is None else tuple(k for k in track_want if k in offered),
+                                                  lambda: offered, None if caller_tracks is None else caller_tracks[j], extras=())
+                tg.track[j] = t_struct
+                t_outs.append(t_out)
+                arrays += list(t_out.values())
+            arrays += self._track_arrays(tracks)
+        out, o = self._grad_outs(capi.ROLLOUT_GRAD_FIELDS, capi.WbcRolloutGrad, like, B, keep, want, default, out, extras=("grad_status", "ticks_dropped"))
+        mem = _mem_of(list(inputs.values()) + list(out.values()) + arrays + [c["imu"], c["task_params"], g_q_final, g_qdot_last, g_q_trace])
         f, P = np.float64, self._p
         sd = capi.WbcRolloutSeed()
         sd.g_q_final, sd.g_qdot_last = P(g_q_final, f, keep, B, NV, "g_q_final"), P(g_qdot_last, f, keep, B, NV, "g_qdot_last")
@@ -677,9 +730,13 @@ class WbcBatch:
         r.imu = P(c["imu"], f, keep, B, 4, "imu")
         tin = self._tick_in(inputs, keep, B)
         tp = _task_params(c["task_params"], B, keep, self.device_id)
-        capi.check(self.lib.wbc_rollout_vjp(self._h, B, C.byref(tin), tp, c["dt"], C.byref(r), tape.buf.data_ptr(), tape.buf.numel(),
-                                             C.byref(sd), mem, C.byref(o), self._stream(mem)), self.lib)
-        return out
+        if tk is None:
+            capi.check(self.lib.wbc_rollout_vjp(self._h, B, C.byref(tin), tp, c["dt"], C.byref(r), tape.buf.data_ptr(), tape.buf.numel(),
+                                                 C.byref(sd), mem, C.byref(o), self._stream(mem)), self.lib)
+            return out
+        capi.check(self.lib.wbc_rollout_vjp_tracks(self._h, B, C.byref(tin), tp, c["dt"], C.byref(r), C.byref(tk), tape.buf.data_ptr(),
+                                                   tape.buf.numel(), C.byref(sd), mem, C.byref(o), C.byref(tg), self._stream(mem)), self.lib)
+        return dict(out, tracks=t_outs)
 
     def default_rollout_grad_wants(self, mode=capi.ROLLOUT_RUNNING):
         """the gradients wbc_rollout_vjp offers under the handle's configuration (names of capi.ROLLOUT_GRAD_FIELDS)"""
@@ -811,6 +868,15 @@ class WbcBatch:
         [n_scored, B / M], group_worst_status, group_bad_instances [B / M] — all reduced on the device."""
         return self._rollout_tracks(inputs, dt, ticks, tracks, score, group_size, want_trace, mode, task_params, trunk_target_step, imu)
 
+    def _track_arrays(self, tracks):
+        """the arrays of a list of track dicts (for _mem_of), after the check of each dict's keys"""
+        arrays = []
+        for i, t in enumerate(tracks):
+            if not isinstance(t, dict) or set(t) - set(self._TRACK_KEYS) or "target" not in t or "points" not in t:
+                raise capi.WbcError("tracks[%d]: want a dict with target, points and optionally kind, tangents, n_points, du" % i)
+            arrays += [t["points"], t.get("tangents"), t.get("n_points"), None if np.isscalar(t.get("du", 0.002)) else t.get("du")]
+        return arrays
+
     def _tracks_struct(self, tracks, B, keep):
         """-> (WbcTracks of the list of dicts, the set of followed targets)"""
         f = np.float64
@@ -898,11 +964,7 @@ class WbcBatch:
         tracks = [] if (tracks is None and watch is not None) else list(tracks)
         if not (0 if watch is not None else 1) <= len(tracks) <= capi.MAX_TRACKS:
             raise capi.WbcError("tracks: %d given, want 1..%d" % (len(tracks), capi.MAX_TRACKS))
-        arrays = [ee_target_step]
-        for i, t in enumerate(tracks):
-            if not isinstance(t, dict) or set(t) - set(self._TRACK_KEYS) or "target" not in t or "points" not in t:
-                raise capi.WbcError("tracks[%d]: want a dict with target, points and optionally kind, tangents, n_points, du" % i)
-            arrays += [t["points"], t.get("tangents"), t.get("n_points"), None if np.isscalar(t.get("du", 0.002)) else t.get("du")]
+        arrays = [ee_target_step] + self._track_arrays(tracks)
         mem = _mem_of(list(inputs.values()) + arrays + [trunk_target_step, imu, task_params])
         q = inputs.get("q")
         B = self._batch_of(q)

@@ -193,6 +193,18 @@ class WbcRolloutGrad(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in tuple(ROLLOUT_GRAD_FIELDS) + ("grad_status", "ticks_dropped")]
 
 
+# wbc_rollout_record_tracks / wbc_rollout_vjp_tracks: the sweep's outputs per track (include/wbc.h); the shapes are per instance, S = max_points
+TRACK_GRAD_FIELDS = dict(d_points=("S", 3), d_tangents=("S", 3), d_du=())
+
+
+class WbcTrackGrad(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in TRACK_GRAD_FIELDS]
+
+
+class WbcTracksGrad(C.Structure):
+    _fields_ = [("track", WbcTrackGrad * MAX_TRACKS)]
+
+
 class WbcFkOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("oMi", "oMf", "J", "com", "Jcom")]
 
@@ -244,6 +256,11 @@ SIGNATURES = {
     "wbc_rollout_vjp": (_i, [_vp, _i, C.POINTER(WbcTickIn), _vp, _d, C.POINTER(WbcRollout), _vp, C.c_size_t, C.POINTER(WbcRolloutSeed), _i,
                              C.POINTER(WbcRolloutGrad), _vp]),
     "wbc_rollout_grad_sizes": (_i, [c_int32_p, c_int32_p]),
+    "wbc_rollout_record_tracks": (_i, [_vp, _i, C.POINTER(WbcTickIn), _vp, _d, C.POINTER(WbcRollout), C.POINTER(WbcTracks),
+                                       C.POINTER(WbcTrackScores), _vp, C.c_size_t, _vp, _i, _vp]),
+    "wbc_rollout_vjp_tracks": (_i, [_vp, _i, C.POINTER(WbcTickIn), _vp, _d, C.POINTER(WbcRollout), C.POINTER(WbcTracks), _vp, C.c_size_t,
+                                    C.POINTER(WbcRolloutSeed), _i, C.POINTER(WbcRolloutGrad), C.POINTER(WbcTracksGrad), _vp]),
+    "wbc_rollout_tracks_grad_sizes": (_i, [c_int32_p, c_int32_p]),
     "wbc_rollout_traj": (_i, [_vp, _i, C.POINTER(WbcTickIn), _vp, _d, C.POINTER(WbcRollout), C.POINTER(WbcTrajectory),
                               C.POINTER(WbcRolloutSummary), _i, _vp]),
     "wbc_rollout_tracks": (_i, [_vp, _i, C.POINTER(WbcTickIn), _vp, _d, C.POINTER(WbcRollout), C.POINTER(WbcTracks),
@@ -315,6 +332,10 @@ def load_library(path=None):
     if sb.value != C.sizeof(WbcRolloutSeed) or sc.value != C.sizeof(WbcRolloutGrad):
         raise WbcError("ABI mismatch (WbcRolloutSeed / WbcRolloutGrad): library (%d, %d) vs ctypes (%d, %d)" % (
             sb.value, sc.value, C.sizeof(WbcRolloutSeed), C.sizeof(WbcRolloutGrad)))
+    lib.wbc_rollout_tracks_grad_sizes(C.byref(sb), C.byref(sc))
+    if sb.value != C.sizeof(WbcTrackGrad) or sc.value != C.sizeof(WbcTracksGrad):
+        raise WbcError("ABI mismatch (WbcTrackGrad / WbcTracksGrad): library (%d, %d) vs ctypes (%d, %d)" % (
+            sb.value, sc.value, C.sizeof(WbcTrackGrad), C.sizeof(WbcTracksGrad)))
     if path is None:
         _lib = lib
     return lib

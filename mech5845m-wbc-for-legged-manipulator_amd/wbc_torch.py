@@ -314,3 +314,80 @@ def wbc_rollout_fused(q0, task_params, ee_target, prev_ee_target, trunk_target, 
     Unsolved ticks: wbc_rollout's rule. inputs must not hold q_con; posture modes MANI / HYBRID need posture_u."""
     return _WbcRolloutFused.apply(q0, task_params, ee_target, prev_ee_target, trunk_target, prev_trunk_target, com_target, com_target_vel,
                                   posture_u, ee_target_step, trunk_target_step, inputs, dt, ticks, batch, mode, imu)
+
+
+class _WbcRolloutTracksFused(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q0, task_params, inputs, dt, ticks, batch, mode, imu, trunk_target_step, specs, *flat):
+        args = [_c(q0), _c(task_params)] + [_c(t) for t in flat]
+        d = dict(inputs)
+        d["q"] = args[0]
+        tracks = []
+        for j, spec in enumerate(specs):     # flat: (points, tangents, du) per track; a du that is no tensor stays in the spec
+            t = dict(spec, points=args[2 + 3 * j])
+            if args[3 + 3 * j] is not None:
+                t["tangents"] = args[3 + 3 * j]
+            if args[4 + 3 * j] is not None:
+                t["du"] = args[4 + 3 * j]
+            tracks.append(t)
+        out, tape = batch.rollout_record(d, dt, ticks, trunk_target_step=_c(trunk_target_step), imu=_c(imu), mode=mode, task_params=args[1],
+                                         tracks=tracks)
+        ctx.batch, ctx.tape = batch, tape
+        _save(ctx, (out["q"], out["q_trace"]), args)
+        ctx.mark_non_differentiable(out["status"])
+        return out["q"], out["qdot"], out["status"], out["q_trace"]
+
+    @staticmethod
+    def backward(ctx, g_q, g_qdot, _gst, g_trace):
+        import wbc_workload
+        (q_final, q_trace), args = _saved(ctx, 2)
+        n_flat = len(args) - 2
+        bt, tape = ctx.batch, ctx.tape
+        K, B = tape.ticks, tape.B
+        need = ctx.needs_input_grad
+        want = [n for n, k in (("d_q0", 0), ("d_task_params", 1)) if need[k] and args[k] is not None]
+        names = ("d_points", "d_tangents", "d_du")
+        need_flat = [bool(need[10 + i]) and args[2 + i] is not None for i in range(n_flat)]
+        want += [n for c, n in enumerate(names) if any(need_flat[c::3])]
+        if (g_q is None and g_qdot is None and g_trace is None) or not want:
+            return (None,) * (10 + n_flat)
+        raw, at = [], []
+        if g_q is not None:
+            raw.append(g_q.reshape(B, -1))
+            at.append(q_final)
+        if g_trace is not None:
+            raw.append(g_trace.reshape(K * B, -1))
+            at.append(q_trace.reshape(K * B, -1))
+        gq_f = gq_t = None
+        if raw:
+            tang = wbc_workload.raw_to_tangent(torch.cat(at), torch.cat(raw).contiguous())
+            if g_q is not None:
+                gq_f = tang[:B].contiguous()
+            if g_trace is not None:
+                gq_t = tang[-K * B:].reshape(K, B, -1).contiguous()
+        r = bt.rollout_vjp(tape, g_q_final=gq_f, g_qdot_last=None if g_qdot is None else g_qdot.contiguous(), g_q_trace=gq_t, want=want)
+        res = [wbc_workload.tangent_to_raw(args[0], r["d_q0"]) if "d_q0" in want else None,
+               r["d_task_params"].reshape(args[1].shape) if "d_task_params" in want else None]
+        for i in range(n_flat):
+            got = r["tracks"][i // 3].get(names[i % 3]) if need_flat[i] else None
+            res.append(None if got is None else got.reshape(args[2 + i].shape))
+        return tuple(res[:2]) + (None,) * 8 + tuple(res[2:])
+
+
+def wbc_rollout_tracks_fused(q0, task_params, tracks, inputs, dt, ticks, batch, mode=capi.ROLLOUT_RUNNING, imu=None, trunk_target_step=None):
+    """WbcBatch.rollout_tracks as ONE differentiable layer (trajectory optimisation through the controller): the forward is one
+    WbcBatch.rollout_record(..., tracks=tracks) (wbc_rollout_record_tracks, include/wbc.h), the backward one WbcBatch.rollout_vjp
+    (wbc_rollout_vjp_tracks: the reverse sweep and the adjoint of the track evaluation on the device). tracks: rollout_tracks' list of dicts;
+    each track's points [B,S,3], tangents [B,S,3] (hermite with caller tangents) and du [B] may be tensors that require a gradient (a du
+    given as a number is shared by the instances and gets none; n_points gets none). Gradients also flow to q0 (raw coordinates) and
+    task_params; the constant targets come from `inputs` and get none here (wbc_rollout_fused is the layer for those). Returns what
+    wbc_rollout_fused returns: (q_final [B,27], qdot of the last tick [B,26], status [B] int32, q_trace [ticks,B,27]). A bad row (include/wbc.h)
+    gets zero gradients everywhere. Contiguous float64 tensors on the handle's device."""
+    specs, flat = [], []
+    for t in tracks:
+        du = t.get("du", 0.002)
+        specs.append({k: v for k, v in t.items() if k not in ("points", "tangents", "du")})
+        if not torch.is_tensor(du):
+            specs[-1]["du"] = du
+        flat += [t["points"], t.get("tangents"), du if torch.is_tensor(du) else None]
+    return _WbcRolloutTracksFused.apply(q0, task_params, inputs, dt, ticks, batch, mode, imu, trunk_target_step, specs, *flat)

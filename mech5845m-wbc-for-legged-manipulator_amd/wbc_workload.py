@@ -191,6 +191,103 @@ def track_targets(points, n_points, du, k, kind="linear", tangents=None):
     return out
 
 
+def _tangent_case(a, x, b):
+    """the case (1..4, include/wbc.h) the default-tangent rule takes for one component at an interior milestone"""
+    w, third = (b - a) * 0.5, 1.0 / 3.0
+    if x <= min(a, b) or x >= max(a, b):
+        return 1
+    if (w < 0 and x - w * third >= a) or (w > 0 and x - w * third <= a):
+        return 2
+    if (w < 0 and x + w * third < b) or (w > 0 and x + w * third > b):
+        return 3
+    return 4
+
+
+def _tangent_adjoint(m, d, n, i, vb):
+    """vb, the cotangent of the default tangent at milestone i, into d (both one instance's [S, 3]); per component, the plus term first"""
+    if n == 2:
+        d[1] = d[1] + vb
+        d[0] = d[0] - vb
+        return
+    if i == 0 or i == n - 1:
+        return
+    for c in range(3):
+        case = _tangent_case(m[i - 1, c], m[i, c], m[i + 1, c])
+        if case == 2:
+            d[i, c] = d[i, c] + 3.0 * vb[c]
+            d[i - 1, c] = d[i - 1, c] - 3.0 * vb[c]
+        elif case == 3:
+            d[i + 1, c] = d[i + 1, c] + 3.0 * vb[c]
+            d[i, c] = d[i, c] - 3.0 * vb[c]
+        elif case == 4:
+            d[i + 1, c] = d[i + 1, c] + 0.5 * vb[c]
+            d[i - 1, c] = d[i - 1, c] - 0.5 * vb[c]
+
+
+def track_target_gradients(points, n_points, du, ticks, kind="linear", tangents=None, e=None):
+    """The adjoint of track_targets over ticks k = 0 .. ticks - 1: wbc_rollout_vjp_tracks' track kernel restated, the same operations in the
+    same order (include/wbc.h), so the sums round alike. e [ticks, B, 3]: the cotangent of the target of each tick. Returns (d_points
+    [B, S, 3], d_tangents [B, S, 3] — None unless kind is "hermite" with caller tangents —, d_du [B]). Per instance, from the last tick to
+    the first, with t = float(k) * du and the forward's comparisons: t <= 0 -> d_points[0] += e; t >= n - 1 -> d_points[n - 1] += e;
+    otherwise i = floor(t), u = t - i (an exact knot: segment i with u = 0), the segment's coefficients times e into milestones i and i + 1,
+    the tangent cotangents cv1 e, cv2 e into d_tangents or, default tangents, through the rule's branch into the neighbouring milestones,
+    and d_du += k ((x + y) + z) with x, y, z the components of d(target)/dt times e. A bad row (a non-finite point or tangent among the
+    first n_points, du not finite and positive, n_points outside 2..S) gets zeros."""
+    if kind not in ("linear", "hermite"):
+        raise ValueError("kind %r is neither 'linear' nor 'hermite'" % (kind,))
+    if kind == "linear" and tangents is not None:
+        raise ValueError("a linear track has no tangents")
+    points = np.asarray(points, dtype=np.float64)
+    B, S = points.shape[0], points.shape[1]
+    K = int(ticks)
+    e = np.asarray(e, dtype=np.float64).reshape(K, B, 3)
+    n_all = np.full(B, S, dtype=np.int64) if n_points is None else np.asarray(n_points, dtype=np.int64).reshape(B)
+    du_all = np.broadcast_to(np.asarray(du, dtype=np.float64), (B,))
+    vel = None if tangents is None else np.asarray(tangents, dtype=np.float64).reshape(B, S, 3)
+    dflt = spline_tangents(points, np.clip(n_all, 2, S)) if (kind == "hermite" and vel is None) else None
+    d_points, d_du = np.zeros((B, S, 3)), np.zeros(B)
+    d_tangents = np.zeros((B, S, 3)) if vel is not None else None
+    for b in range(B):
+        n, dub, m = int(n_all[b]), float(du_all[b]), points[b]
+        if n < 2 or n > S or not np.isfinite(dub) or not dub > 0.0 or not np.isfinite(m[:n]).all() or (vel is not None and not np.isfinite(vel[b, :n]).all()):
+            continue
+        v = vel[b] if vel is not None else (dflt[b] if dflt is not None else None)
+        dp = d_points[b]
+        for k in range(K - 1, -1, -1):
+            eb = e[k, b]
+            t = float(k) * dub
+            if t <= 0.0:
+                dp[0] = dp[0] + eb
+                continue
+            if t >= float(n - 1):
+                dp[n - 1] = dp[n - 1] + eb
+                continue
+            fi = np.floor(t)
+            i = int(fi)
+            u = t - fi
+            if kind == "linear":
+                dp[i] = dp[i] + (1.0 - u) * eb
+                dp[i + 1] = dp[i + 1] + u * eb
+                x = (m[i + 1] - m[i]) * eb
+            else:
+                u2 = u * u
+                u3 = u * u2
+                cx1, cx2, cv1, cv2 = (2.0 * u3 - 3.0 * u2) + 1.0, (-2.0 * u3) + 3.0 * u2, (u3 - 2.0 * u2) + u, u3 - u2
+                dx1, dx2, dv1, dv2 = 6.0 * u2 - 6.0 * u, (-6.0 * u2) + 6.0 * u, (3.0 * u2 - 4.0 * u) + 1.0, 3.0 * u2 - 2.0 * u
+                x = (((dx1 * m[i] + dx2 * m[i + 1]) + dv1 * v[i]) + dv2 * v[i + 1]) * eb
+                dp[i] = dp[i] + cx1 * eb
+                dp[i + 1] = dp[i + 1] + cx2 * eb
+                vb0, vb1 = cv1 * eb, cv2 * eb
+                if vel is not None:
+                    d_tangents[b, i] = d_tangents[b, i] + vb0
+                    d_tangents[b, i + 1] = d_tangents[b, i + 1] + vb1
+                else:
+                    _tangent_adjoint(m, dp, n, i, vb0)
+                    _tangent_adjoint(m, dp, n, i + 1, vb1)
+            d_du[b] = d_du[b] + float(k) * ((x[0] + x[1]) + x[2])
+    return d_points, d_tangents, d_du
+
+
 # ---- constraint slack (wbc_state_slack / wbc_rollout_watch, include/wbc.h): the four families restated in numpy
 def slack_joint_dofs(model, cfg):
     """(d, i) of every velocity DoF 6 <= d < cfg.lock_from of the model with the q index i of its own joint"""
@@ -1024,7 +1121,7 @@ _ROLLOUT_SUMS = ("d_task_params", "d_com_target", "d_com_target_vel", "d_posture
 
 
 def rollout_gradients(model, cfg, ticks_in, x, dt, fk, assemble, g_q_final=None, g_qdot_last=None, g_q_trace=None, task_params=None, imu=None,
-                      mode=capi.ROLLOUT_RUNNING, status=None, working_set=None):
+                      mode=capi.ROLLOUT_RUNNING, status=None, working_set=None, tracks=None):
     """wbc_rollout_vjp restated for B instances of ONE model over step_gradients, qp_certificate, tick_gradients and tick_state_gradients,
     tick by tick from the last. ticks_in: K dicts, the inputs tick k SAW (q, the targets as running sums, the previous rotations); x [K, B, 26]:
     the ticks' qdot; assemble(inputs) -> dict(A, b, C, Clb, Cub, lb, ub) of a tick's problem (a model with nv < 26 gets unit rows on its padded
@@ -1036,8 +1133,14 @@ def rollout_gradients(model, cfg, ticks_in, x, dt, fk, assemble, g_q_final=None,
     A tick that is unsolved, uncertified or non-finite for an instance gives that instance zero from the tick's layer (ticks_dropped += 1);
     the step's part flows on. Returns dict(d_q0 (tangent at q_0), d_task_params, d_ee_target, d_prev_ee_target, d_trunk_target,
     d_prev_trunk_target, d_com_target, d_com_target_vel, d_posture_u, d_trunk_box_center, d_ee_target_step, d_trunk_target_step,
-    ticks_dropped [B], sens_max [B]: the largest |sens_x| entry over the ticks)."""
+    ticks_dropped [B], sens_max [B]: the largest |sens_x| entry over the ticks).
+    tracks (wbc_rollout_vjp_tracks): a list of dicts(target: 0..4 or 5 / "trunk", points, n_points, du, kind, tangents) as track_targets takes
+    them. A followed target is eval(k * du) on every tick, so its whole cotangent e_k = a + on Pbar goes into the track and nothing is
+    carried (Ebar of a followed row is 0 in front of every tick; Pbar updates as above). The dict then also holds tracks = [dict(d_points,
+    d_tangents, d_du), ...] from track_target_gradients; the followed rows of d_ee_target / d_trunk_target are 0 and the steps mean nothing."""
     K = len(ticks_in)
+    followed = [capi.TARGET_TRUNK if t["target"] == "trunk" else int(t["target"]) for t in (tracks or [])]
+    e_tracks = [np.zeros((K, np.asarray(x).reshape(K, -1, capi.V_STRIDE).shape[1], 3)) for _ in followed]
     x = np.asarray(x, dtype=np.float64).reshape(K, -1, capi.V_STRIDE)
     B, NVs, nv = x.shape[1], capi.V_STRIDE, model.nv
     on = np.array([bool(cfg.task_ee[e]) for e in range(capi.NEE)])[None, :, None]
@@ -1087,5 +1190,16 @@ def rollout_gradients(model, cfg, ticks_in, x, dt, fk, assemble, g_q_final=None,
         Eb, Pb = Eb + a_k + np.where(on, Pb, 0.0), p_k + np.where(on, 0.0, Pb)
         d_ts = d_ts + TEb
         TEb, TPb = TEb + take(tg["d_trunk_target"]) + (TPb if on_t else 0.0), take(tg["d_prev_trunk_target"]) + (0.0 if on_t else TPb)
+        for j, f in enumerate(followed):       # the followed rows: into the track, nothing carried
+            if f == capi.TARGET_TRUNK:
+                e_tracks[j][k] = TEb
+                TEb = np.zeros((B, 3))
+            else:
+                e_tracks[j][k] = Eb[:, f]
+                Eb[:, f] = 0.0
+    if tracks:
+        names = ("d_points", "d_tangents", "d_du")
+        acc["tracks"] = [dict(zip(names, track_target_gradients(t["points"], t.get("n_points"), t.get("du", 0.002), K, t.get("kind", "linear"),
+                                                                 t.get("tangents"), e_tracks[j]))) for j, t in enumerate(tracks)]
     return dict(acc, d_q0=g, d_ee_target=Eb, d_prev_ee_target=Pb, d_trunk_target=TEb, d_prev_trunk_target=TPb, d_ee_target_step=d_es,
                 d_trunk_target_step=d_ts, ticks_dropped=dropped, sens_max=sens_max)
