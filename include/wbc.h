@@ -751,7 +751,8 @@ int wbc_rollout_tracks(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskPa
  * track (without one trunk_target_step stays allowed and d_trunk_target_step is wbc_rollout_vjp's); d_tangents on a LINEAR track or a
  * HERMITE track with tangents == NULL; tracks_out NULL; a tracks_out->track[j] member set for j >= n_tracks; what wbc_rollout_tracks and
  * what wbc_rollout_vjp refuse.
- * Not offered: hold ticks, the watch, the scores as a loss, gradients with respect to n_points, checkpoint-and-recompute.
+ * Not offered: hold ticks, the watch, gradients with respect to n_points, checkpoint-and-recompute (the scores as a loss:
+ * wbc_rollout_vjp_scored below).
  * Neither call allocates once the workspaces have their size; with device buffers both can be captured into a HIP graph.
  * Statistic "last_trackvjp_variant": the row of csrc/wbc_k_trackvjp.hip's table the last call launched last (key of the stage: 0 BEGIN,
  * 1 TICK), -1 before the first; wbc_variant_count("trackvjp") == 2. */
@@ -768,6 +769,54 @@ int wbc_rollout_vjp_tracks(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTa
                            const WbcTracks* tracks, const void* tape, size_t tape_bytes, const WbcRolloutSeed* seed, int mem,
                            const WbcRolloutGrad* out, const WbcTracksGrad* tracks_out, void* stream);
 int wbc_rollout_tracks_grad_sizes(int32_t* sizeof_track_grad, int32_t* sizeof_tracks_grad); /* ctypes layout self-check */
+
+/* ------------------------------------------------------------------ roll-out scores as a loss: dL/d(err_sq_sum, err_final, err_max)
+ * wbc_rollout_vjp_scored is wbc_rollout_vjp_tracks' sweep seeded (also, or alone) with the cotangents of the scores the record call returned
+ * (WbcTrackScores.err_sq_sum, err_final, err_max), formed on the device: one launch in front of every reverse tick's step layer and one
+ * behind its link stage. wbc_rollout_vjp and wbc_rollout_vjp_tracks launch what they launched and return the same bits.
+ * FORWARD (wbc_rollout_tracks): for a scored frame f (0..4 the end effectors, 5 the trunk) on tick k, d = reached_f(after tick k) -
+ * target_f(of tick k), e2 = (dx dx + dy dy) + dz dz, e = sqrt(e2); err_sq_sum += e2, err_final = e, err_max with its FIRST tick. reached_f
+ * is the frame's position at the integrated configuration shifted rigidly by (estimated base - integrated base); without an IMU quaternion
+ * the state after the tick keeps the integrated orientation and joints and takes the estimated base, so reached_f = FK_f(q_(k+1)) up to
+ * rounding in both modes. The sweep recomputes d from the FK at q_(k+1) (the tape's q of tick k + 1; q_final for k = K - 1: the tape ends
+ * at q_(K-1)) and the taped target of tick k. The recomputed e differs from the forward's by the rounding of the FK, which moves the
+ * gradient's value at rounding level and no branch: the one branch, err_max's tick, is the caller's err_max_tick.
+ * THE COTANGENT of d on tick k, with the caller's g_sq, g_fin, g_max [n_scored][B]:
+ *     c = ((2 g_sq + [k == K - 1] g_fin / e) + [k == err_max_tick] g_max / e) d          (both 1 / e terms are 0 where e == 0)
+ * To the state: g(q_(k+1)) += J_f(q_(k+1))' c, J_f the frame's translational Jacobian in the sweep's tangent coordinates (base DoF in the
+ * base-local frame; a column is lin + ang x p_f of the WORLD joint Jacobian), summed over the scored frames in increasing order, added
+ * BEFORE the step layer of tick k runs: where g_q_trace[k] enters. To the target: -c joins the cotangent of E_k (the trunk target for f = 5)
+ * AFTER the link stage of tick k and before the track stage: LINK's d_*_target_step += Ebar must see the cotangent of E_(k+1) alone. A
+ * followed row then reaches the track adjoint with e_k containing -c; a row no track follows ends in d_ee_target / d_trunk_target
+ * (- sum_k c_k); a trunk target under trunk_target_step without a trunk track gives d_trunk_target_step - sum_k k c_k; at k = 0 LINK has
+ * written the caller's d_*_target rows, which take -c_0 as well. The score's cotangent flows whatever the tick's QP status was (the forward
+ * sums e2 on every tick); ticks_dropped keeps its meaning. An exact zero is never added (all-zero cotangents with a state seed give
+ * wbc_rollout_vjp_tracks' bits). Nothing is contracted into fused multiply-adds and there are no atomics: identical calls, identical bits.
+ * PER-INSTANCE FAULTS: a g_err_* value of a scored frame or a q_final entry (among the model's nq) that is not finite, or an err_max_tick
+ * outside [0, K) while g_err_max != 0, gives the instance all-zero rows in every output and WBC_GRAD_NONFINITE, as a bad track row does; the
+ * other instances keep their bits; rows >= B are never written.
+ * WBC_E_ARG, naming the field, before any launch: score NULL (the other entry points exist for that); no g_err_* at all; g_err_max without
+ * err_max_tick; q_final NULL; score_mask 0 or with bits >= 6; bit 5 without in0->trunk_target; r->imu not NULL (the state then discards the
+ * orientation the scored position was formed with); whatever wbc_rollout_vjp_tracks refuses — except that `seed` may be NULL or empty here:
+ * with both seeds the gradients are those of the summed loss. WBC_E_UNSUPPORTED as wbc_rollout_record (the packed whole-tree schedule).
+ * Not offered: an IMU quaternion fed back under a score seed, hold ticks, the watch as a loss, wbc_rollout_traj's one-track summary, the
+ * group scores (group RMS is an expression of err_sq_sum), gradients with respect to n_points, checkpoint-and-recompute.
+ * The workspace lives in the handle with wbc_rollout_vjp's: no allocation after the first call of a size; with device buffers the call
+ * can be captured into a HIP graph.
+ * Statistic "last_scorevjp_variant": the SEED row of csrc/wbc_k_scorevjp.hip's table the last call launched (key of (STAGE, ROT) = (0, 0) or
+ * (0, 1): the stage with the kinematics; the TARGET stage has the one row (1, 0)), -1 before the first; wbc_variant_count("scorevjp") == 3. */
+typedef struct WbcScoreSeed {
+  int32_t score_mask, pad_;        /* as the record call's WbcTrackScores.score_mask; n_scored = popcount */
+  const double*  g_err_sq_sum;     /* [n_scored][B] dL/d err_sq_sum; optional */
+  const double*  g_err_final;      /* [n_scored][B] dL/d err_final;  optional */
+  const double*  g_err_max;        /* [n_scored][B] dL/d err_max;    optional, needs err_max_tick */
+  const int32_t* err_max_tick;     /* [n_scored][B] as the record call returned it */
+  const double*  q_final;          /* [B][27] the state after the last tick (record's q_final): the tape ends at q_(K-1) */
+} WbcScoreSeed;
+int wbc_rollout_vjp_scored(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
+                           const WbcTracks* tracks, const void* tape, size_t tape_bytes, const WbcRolloutSeed* seed /* may be NULL */,
+                           const WbcScoreSeed* score, int mem, const WbcRolloutGrad* out, const WbcTracksGrad* tracks_out, void* stream);
+int wbc_rollout_scored_sizes(int32_t* sizeof_score_seed); /* ctypes layout self-check */
 
 /* ------------------------------------------------------------------ constraint slack: CoM box, trunk box, joint range
  * How far a configuration is from the reference's constraint limits, whether or not the configuration enforces them: what sim3.py prints

@@ -15,6 +15,7 @@
 #include "wbc_stepvjp.h"
 #include "wbc_rollvjp.h"
 #include "wbc_trackvjp.h"
+#include "wbc_scorevjp.h"
 
 // (the layouts of the handle's roll-out workspaces d_roll, d_traj and d_slack: RollWs, TrajWs and SlackWs below)
 
@@ -100,6 +101,7 @@ struct WbcBatch {
   long long last_stepvjp_variant;   // ... and of the last wbc_step_vjp launch
   long long last_rollvjp_variant;   // ... and of the last link-kernel launch of wbc_rollout_vjp
   long long last_trackvjp_variant;  // ... and of the last track-adjoint launch of wbc_rollout_vjp_tracks
+  long long last_scorevjp_variant;  // ... and of the last score-cotangent launch of wbc_rollout_vjp_scored
   long long last_tick_variant, last_qp_variant;   // variant_key(...) of the row the last tick / assemble / fk launch and the last stand-alone QP launch resolved (-1: none yet)
   int sim3p_fixd;        // option [1]: the packed sim3 kernel's FIXD form where the handle qualifies (fixd_dims)
   bool fixd_dims[WBC_MAX_MODELS];   // wbc_batch_configure: the model's plan has exactly the SIM3P_FIXD_* dimensions
@@ -262,6 +264,7 @@ constexpr OutRow<WbcRolloutGrad> ROLL_OUT[] = {{&WbcRolloutGrad::d_q0, qw(&WbcTi
 struct RollVjpWs {   // d_rvjp: wbc_rollout_vjp's workspace — one tick's QP image and certificate, the layers' outputs of the tick, the sweep's accumulators
   double *lb, *ub, *v, *g, *s_dq, *s_dft, *sens_x, *sens_bounds, *t_dq, *t_box, *t_tp, *t_ee, *t_pee, *t_tt, *t_ptt, *t_com, *t_comv, *t_pu;
   double *Ebar, *Pbar, *TEbar, *TPbar, *d_estep, *d_tstep, *acc_tp, *acc_com, *acc_comv, *acc_pu, *acc_box;
+  double* stash;   // wbc_rollout_vjp_scored: -c of the tick's six scored frames [NB][6][3]
   int32_t *cert_status, *gs_step, *gs_tick, *gs_tickq, *worst, *dropped;
   double *A, *b, *C, *Clb, *Cub, *y_rows, *sens_rows;   // [NB][M][26], [NB][M], [NB][p][26], [NB][p] x 4: M = task rows + padding rows, p = constraint rows
   static size_t bytes(size_t NB, size_t M, size_t p);
@@ -279,11 +282,11 @@ constexpr Block<RollVjpWs, double> RVJP_D[] = {{&RollVjpWs::lb, WBC_V_STRIDE}, {
     {&RollVjpWs::t_box, qw(&WbcTickStateGrad::d_trunk_box_center)}, tick_block(0), tick_block(1), tick_block(2), tick_block(3),
     tick_block(4), tick_block(5), tick_block(6), tick_block(7), {&RollVjpWs::Ebar, 3 * WBC_NEE}, {&RollVjpWs::Pbar, 3 * WBC_NEE}, {&RollVjpWs::TEbar, 3},
     {&RollVjpWs::TPbar, 3}, {&RollVjpWs::d_estep, 3 * WBC_NEE}, {&RollVjpWs::d_tstep, 3}, {&RollVjpWs::acc_tp, WBC_TASK_PARAMS_DOUBLES},
-    {&RollVjpWs::acc_com, 3}, {&RollVjpWs::acc_comv, 3}, {&RollVjpWs::acc_pu, WBC_V_STRIDE}, {&RollVjpWs::acc_box, 4}};
+    {&RollVjpWs::acc_com, 3}, {&RollVjpWs::acc_comv, 3}, {&RollVjpWs::acc_pu, WBC_V_STRIDE}, {&RollVjpWs::acc_box, 4}, {&RollVjpWs::stash, 3 * WBC_MAX_TRACKS}};
 static_assert(sizeof(TICK_WS) / sizeof(TICK_WS[0]) == sizeof(TICK_OUT) / sizeof(TICK_OUT[0]) && sizeof(TICK_WS) / sizeof(TICK_WS[0]) == 8, "one block of d_rvjp per output of the tick layer");
 constexpr Block<RollVjpWs, int32_t> RVJP_I[] = {{&RollVjpWs::cert_status, 1}, {&RollVjpWs::gs_step, 1}, {&RollVjpWs::gs_tick, 1}, {&RollVjpWs::gs_tickq, 1},
     {&RollVjpWs::worst, 1}, {&RollVjpWs::dropped, 1}};
-static_assert(block_bytes(RVJP_D) == 555 * sizeof(double) && block_bytes(RVJP_I) == 6 * sizeof(int32_t), "d_rvjp: 555 doubles and 6 int32 per instance (+ the QP image)");
+static_assert(block_bytes(RVJP_D) == 573 * sizeof(double) && block_bytes(RVJP_I) == 6 * sizeof(int32_t), "d_rvjp: 573 doubles and 6 int32 per instance (+ the QP image)");
 static_assert(block_bytes(RVJP_I) % 8 == 0, "d_rvjp: the QP image begins at a multiple of 8 bytes for any max_batch");
 size_t RollVjpWs::bytes(size_t NB, size_t M, size_t p) {
   return NB * (block_bytes(RVJP_D) + block_bytes(RVJP_I) + sizeof(double) * (M * (WBC_V_STRIDE + 1) + p * (WBC_V_STRIDE + 4)));
@@ -411,7 +414,7 @@ extern "C" int wbc_batch_create(const WbcModel* const* models, int n_models, int
   if (!b) return fail(WBC_E_ARG, "out of memory");
   memset(b, 0, sizeof *b);
   b->device_id = device_id; b->n_models = n_models; b->max_batch = max_batch; b->presolve = 1; b->presolve_orth = 1; b->packed_update = 1; b->sim3_kernel = 1; b->sing_tol = 1e-7; b->wave_order = 1; b->sim3p_fixd = 1;
-  b->last_tick_variant = b->last_qp_variant = b->last_grad_variant = b->last_gradq_variant = b->last_stepvjp_variant = b->last_rollvjp_variant = b->last_trackvjp_variant = -1;
+  b->last_tick_variant = b->last_qp_variant = b->last_grad_variant = b->last_gradq_variant = b->last_stepvjp_variant = b->last_rollvjp_variant = b->last_trackvjp_variant = b->last_scorevjp_variant = -1;
   b->jtj_mfma = -1; b->refine = 1; b->packed_min_batch = WBC_SIM3P_MIN_BATCH; b->warm_start = 0; b->packed_kernel = 1; b->packed_orth = 1; b->packed_box = 1; b->posture_par = 1;
   std::vector<DevModel> dm(n_models);
   for (int i = 0; i < n_models; ++i) {
@@ -922,6 +925,7 @@ extern "C" int wbc_batch_get_stat(WbcBatch* b, const char* name, void* stream, i
   if (!strcmp(name, "last_stepvjp_variant")) { *out = b->last_stepvjp_variant; return WBC_OK; }
   if (!strcmp(name, "last_rollvjp_variant")) { *out = b->last_rollvjp_variant; return WBC_OK; }
   if (!strcmp(name, "last_trackvjp_variant")) { *out = b->last_trackvjp_variant; return WBC_OK; }
+  if (!strcmp(name, "last_scorevjp_variant")) { *out = b->last_scorevjp_variant; return WBC_OK; }
   if (!strcmp(name, "last_update_packed")) { *out = b->last_update_packed; return WBC_OK; }
   if (!strcmp(name, "last_posture_par")) { *out = b->last_posture_par; return WBC_OK; }
   if (!strcmp(name, "last_orth")) { *out = (b->last_path == TICK_GENERAL || b->last_path == TICK_ORTHP) ? b->last_orth : 0; return WBC_OK; }
@@ -1872,18 +1876,35 @@ static int check_tracks_grad(const WbcTracks& tk, const WbcRolloutGrad* out, con
   }
   return WBC_OK;
 }
+// what wbc_rollout_vjp_scored refuses beyond wbc_rollout_vjp_tracks' refusals, before any launch
+static int check_score_seed(const WbcScoreSeed& sc, const WbcTickIn* in0, const WbcRollout* r, const char* who) {
+  if (!sc.g_err_sq_sum && !sc.g_err_final && !sc.g_err_max)
+    return fail(WBC_E_ARG, "%s: a score cotangent is required (g_err_sq_sum, g_err_final or g_err_max)", who);
+  if (sc.g_err_max && !sc.err_max_tick) return fail(WBC_E_ARG, "%s: g_err_max needs err_max_tick (as the record call returned it)", who);
+  if (!sc.q_final) return fail(WBC_E_ARG, "%s: q_final is required (the state after the last tick: the tape ends one state earlier)", who);
+  if (sc.score_mask <= 0 || sc.score_mask >= (1 << WBC_MAX_TRACKS))
+    return fail(WBC_E_ARG, "%s: score_mask = 0x%x, want a bit of the frames 0..%d and none beyond", who, (unsigned)sc.score_mask, WBC_TARGET_TRUNK);
+  if (((sc.score_mask >> WBC_TARGET_TRUNK) & 1) && !in0->trunk_target)
+    return fail(WBC_E_ARG, "%s: score_mask bit %d needs in0->trunk_target", who, WBC_TARGET_TRUNK);
+  if (r->imu) return fail(WBC_E_ARG, "%s: imu must be NULL (with an IMU quaternion fed back the state discards the orientation the scored position was formed with)", who);
+  return WBC_OK;
+}
 // The sweep of wbc_rollout_vjp and, with tracks, of wbc_rollout_vjp_tracks: the same launches, plus one stage of the track-adjoint kernel behind
-// the link kernel's BEGIN and behind every LINK.
+// the link kernel's BEGIN and behind every LINK. With a score seed (wbc_rollout_vjp_scored) also one stage of the score-cotangent kernel in
+// front of every tick's step layer and one between LINK and the track stage.
 static int rollout_vjp_run(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r, const void* tape,
                            size_t tape_bytes, const WbcRolloutSeed* seed, int mem, const WbcRolloutGrad* out, void* stream, const char* who,
-                           bool with_tracks, const WbcTracks* tracks, const WbcTracksGrad* tracks_out) {
+                           bool with_tracks, const WbcTracks* tracks, const WbcTracksGrad* tracks_out, bool with_score = false,
+                           const WbcScoreSeed* score = nullptr) {
   int rc;
+  if (with_score && !score) return fail(WBC_E_ARG, "%s: score is required (wbc_rollout_vjp_tracks is the call without one)", who);
   if (with_tracks && (rc = check_tracks_call(B, in0, r, tracks, nullptr))) return rc;   // (first: tracks == NULL is refused before a field of it is read)
   if ((rc = check_record_call(b, B, in0, r, tape, tape_bytes, who))) return rc;
   if (!out) return fail(WBC_E_ARG, "%s: out is required", who);
   if (with_tracks && (rc = check_tracks_grad(*tracks, out, tracks_out, who))) return rc;
-  if (!seed || !(seed->g_q_final || seed->g_qdot_last || seed->g_q_trace))
+  if (!with_score && (!seed || !(seed->g_q_final || seed->g_qdot_last || seed->g_q_trace)))
     return fail(WBC_E_ARG, "%s: a seed is required (g_q_final, g_qdot_last or g_q_trace)", who);
+  if (with_score && (rc = check_score_seed(*score, in0, r, who))) return rc;
   if ((rc = check_dt(dt, who))) return rc;
   if (r->mode != WBC_ROLLOUT_RUNNING && r->mode != WBC_ROLLOUT_WARMUP)
     return fail(WBC_E_ARG, "%s: mode = %d, want WBC_ROLLOUT_RUNNING (%d) or WBC_ROLLOUT_WARMUP (%d)", who, r->mode, WBC_ROLLOUT_RUNNING, WBC_ROLLOUT_WARMUP);
@@ -1905,13 +1926,18 @@ static int rollout_vjp_run(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTa
   fill_args(a, b, B, dt);
   a.in = *in0;
   a.in.working_set = nullptr;
-  WbcRolloutSeed sd = *seed;
+  WbcRolloutSeed sd = seed ? *seed : WbcRolloutSeed{};
+  WbcScoreSeed ss = with_score ? *score : WbcScoreSeed{};
   WbcRolloutGrad og = *out;
   const double* imu = r->imu;
   Stager st{b, mem, (hipStream_t)stream, {}};
   stage_tick_in(st, a.in, B, b);
   st.in(&tp, n); st.in(&imu, n * 4);
   st.in(&sd.g_q_final, n * WBC_V_STRIDE); st.in(&sd.g_qdot_last, n * WBC_V_STRIDE); st.in(&sd.g_q_trace, (size_t)K * n * WBC_V_STRIDE);
+  if (with_score) {
+    const size_t ns = (size_t)__builtin_popcount((unsigned)ss.score_mask) * n;
+    st.in(&ss.g_err_sq_sum, ns); st.in(&ss.g_err_final, ns); st.in(&ss.g_err_max, ns); st.in(&ss.err_max_tick, ns); st.in(&ss.q_final, n * WBC_Q_STRIDE);
+  }
   stage_outs(st, og, ROLL_OUT, n);
   st.out(&og.grad_status, n); st.out(&og.ticks_dropped, n);
   WbcTracks tj = with_tracks ? *tracks : WbcTracks{};
@@ -1971,6 +1997,17 @@ static int rollout_vjp_run(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTa
     V.k = k;
     return launch_rc(launch_trackvjp(V, stage, stream, &b->last_trackvjp_variant), "roll-out gradient track adjoint");
   };
+  ScoreVjpArgs S;
+  memset(&S, 0, sizeof S);
+  S.models = b->d_models; S.plans = b->d_plans; S.model_id = first.model_id; S.B = B; S.n_models = b->n_models; S.K = K; S.rot = b->rot;
+  S.score_mask = ss.score_mask; S.g_sq = ss.g_err_sq_sum; S.g_fin = ss.g_err_final; S.g_max = ss.g_err_max; S.err_max_tick = ss.err_max_tick;
+  S.g = w.g; S.stash = w.stash; S.worst = w.worst; S.Ebar = w.Ebar; S.TEbar = w.TEbar;
+  S.d_ee_target = og.d_ee_target; S.d_trunk_target = og.d_trunk_target;
+  auto score_stage = [&](int stage, int k) {
+    S.k = k;
+    // (the statistic names the SEED row, the stage with kinematics and a ROT form; TARGET has one row)
+    return launch_rc(launch_scorevjp(S, stage, stream, stage == SCOREVJP_SEED ? &b->last_scorevjp_variant : nullptr), "roll-out gradient score cotangent");
+  };
   if ((rc = link(ROLLVJP_BEGIN, K - 1))) return rc;
   if (with_tracks && (rc = track(TRACKVJP_BEGIN, K - 1))) return rc;
   for (int k = K - 1; k >= 0; --k) {
@@ -1981,6 +2018,11 @@ static int rollout_vjp_run(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTa
     if (first.prev_trunk_target) in.prev_trunk_target = T.prev_trunk_target;
     if (k > 0 && first.ee_prev_rot) in.ee_prev_rot = head.ee_prev_rot;
     if (k > 0 && first.trunk_prev_rot) in.trunk_prev_rot = head.trunk_prev_rot;
+    if (with_score) {   // g += J' c at q_(k+1): the tape's q of tick k + 1, the caller's q_final behind the last tick; -c into the stash
+      S.q = k == K - 1 ? ss.q_final : TapeWs::carve(tp_mut, n, k + 1).q;
+      S.ee_target = T.ee_target; S.trunk_target = first.trunk_target ? T.trunk_target : nullptr;
+      if ((rc = score_stage(SCOREVJP_SEED, k))) return rc;
+    }
     // the step: g -> d_q, v = d_qdot, d_foot_targets; on the last tick v += g_qdot_last
     if ((rc = step_layer(b, B, dt, r->mode, T.q, T.qdot, T.ee_target, imu, first.model_id, w.g, s_out, stream))) return rc;
     if (k == K - 1 && sd.g_qdot_last && (rc = link(ROLLVJP_ADDV, K - 1))) return rc;
@@ -2005,6 +2047,7 @@ static int rollout_vjp_run(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTa
     sn.status = T.status; sn.cert_status = w.cert_status; sn.working_set = qp.working_set;
     if ((rc = tickq_layer(b, B, dt, in, tp, sn, q_out, stream))) return rc;
     if ((rc = link(ROLLVJP_LINK, k))) return rc;
+    if (with_score && (rc = score_stage(SCOREVJP_TARGET, k))) return rc;
     if (with_tracks && (rc = track(TRACKVJP_TICK, k))) return rc;
   }
   return st.finish();
@@ -2117,6 +2160,16 @@ extern "C" int wbc_rollout_vjp_tracks(WbcBatch* b, int B, const WbcTickIn* in0, 
                                       const WbcTracks* tracks, const void* tape, size_t tape_bytes, const WbcRolloutSeed* seed, int mem,
                                       const WbcRolloutGrad* out, const WbcTracksGrad* tracks_out, void* stream) {
   return rollout_vjp_run(b, B, in0, tp, dt, r, tape, tape_bytes, seed, mem, out, stream, "wbc_rollout_vjp_tracks", true, tracks, tracks_out);
+}
+extern "C" int wbc_rollout_vjp_scored(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
+                                      const WbcTracks* tracks, const void* tape, size_t tape_bytes, const WbcRolloutSeed* seed,
+                                      const WbcScoreSeed* score, int mem, const WbcRolloutGrad* out, const WbcTracksGrad* tracks_out, void* stream) {
+  return rollout_vjp_run(b, B, in0, tp, dt, r, tape, tape_bytes, seed, mem, out, stream, "wbc_rollout_vjp_scored", true, tracks, tracks_out, true, score);
+}
+static_assert(sizeof(WbcScoreSeed) == 8 + 5 * sizeof(void*), "wbc_capi.WbcScoreSeed");
+extern "C" int wbc_rollout_scored_sizes(int32_t* sizeof_score_seed) {
+  if (sizeof_score_seed) *sizeof_score_seed = (int32_t)sizeof(WbcScoreSeed);
+  return WBC_OK;
 }
 extern "C" int wbc_rollout_tracks_grad_sizes(int32_t* sizeof_track_grad, int32_t* sizeof_tracks_grad) {
   if (sizeof_track_grad) *sizeof_track_grad = (int32_t)sizeof(WbcTrackGrad);
@@ -2409,6 +2462,7 @@ extern "C" int wbc_variant_count(const char* family) {
   if (!strcmp(family, "stepvjp")) return stepvjp_variant_count();
   if (!strcmp(family, "rollvjp")) return rollvjp_variant_count();
   if (!strcmp(family, "trackvjp")) return trackvjp_variant_count();
+  if (!strcmp(family, "scorevjp")) return scorevjp_variant_count();
   return fail(WBC_E_ARG, "wbc_variant_count: unknown kernel family %s", family);
 }
 extern "C" int wbc_abi_sizes(int32_t* sb, int32_t* sc) {

@@ -678,7 +678,7 @@ class WbcBatch:
                                                 self._p(out.get("q_trace"), np.float64, keep), mem, self._stream(mem)), self.lib)
         return out, tape
 
-    def rollout_vjp(self, tape, g_q_final=None, g_qdot_last=None, g_q_trace=None, want=None, out=None):
+    def rollout_vjp(self, tape, g_q_final=None, g_qdot_last=None, g_q_trace=None, want=None, out=None, score_seed=None):
         """wbc_rollout_vjp (include/wbc.h): the reverse sweep over a recorded roll-out, everything on the device. tape: rollout_record's.
         Seeds (numpy or torch, at least one; tangent coordinates — wbc_workload.raw_to_tangent turns a raw gradient into one): g_q_final
         [B,26] at q_K, g_qdot_last [B,26], g_q_trace [K,B,26] at the state after each tick. want: names of capi.ROLLOUT_GRAD_FIELDS (None:
@@ -686,14 +686,23 @@ class WbcBatch:
         Returns dict(<want>..., grad_status [B] int32, ticks_dropped [B] int32); d_q0 is tangent at q_0 (wbc_workload.tangent_to_raw).
         A tape recorded with tracks (wbc_rollout_vjp_tracks): the dict also holds tracks = [dict(d_points [B,S,3], d_tangents [B,S,3],
         d_du [B]), ...], one per track in the call's order; want accepts those three names too (None: each where the track offers it —
-        d_tangents for a hermite track with caller tangents alone), and out may hold "tracks": a list of dicts of the caller's arrays."""
+        d_tangents for a hermite track with caller tangents alone), and out may hold "tracks": a list of dicts of the caller's arrays.
+        score_seed (None: exactly the calls above; a tape recorded with tracks): wbc_rollout_vjp_scored — dict(mask: the score mask or the
+        scored frames as rollout_record's `score` lists them, g_err_sq_sum, g_err_final, g_err_max [n_scored,B] (at least one), err_max_tick
+        [n_scored,B] int32 (with g_err_max), q_final [B,27]: the record call's outputs). The cotangents of the scores are formed on the
+        device; the state seeds become optional and, where given, the gradients are those of the summed loss."""
         keep = []
         c = tape.call
         inputs, B, K = c["inputs"], tape.B, tape.ticks
         tracks = c.get("tracks")
         if getattr(self, "_options", {}).get("warm_start", 0) != c["warm_start"]:
             raise capi.WbcError("rollout_vjp: option warm_start changed since the tape was recorded (the tape holds working sets only with it)")
-        like = next((a for a in (g_q_final, g_qdot_last, g_q_trace) if a is not None), inputs["q"])
+        sseed = None
+        if score_seed is not None:
+            if tracks is None:
+                raise capi.WbcError("score_seed: needs a tape recorded with tracks")
+            sseed = {k: score_seed.get(k) for k in capi.SCORE_SEED_FIELDS}
+        like = next((a for a in (g_q_final, g_qdot_last, g_q_trace) + tuple((sseed or {}).values()) if a is not None), inputs["q"])
         default = lambda: self.default_rollout_grad_wants(c["mode"])
         tk = tg = None
         t_outs, arrays = [], []
@@ -717,7 +726,8 @@ class WbcBatch:
                 arrays += list(t_out.values())
             arrays += self._track_arrays(tracks)
         out, o = self._grad_outs(capi.ROLLOUT_GRAD_FIELDS, capi.WbcRolloutGrad, like, B, keep, want, default, out, extras=("grad_status", "ticks_dropped"))
-        mem = _mem_of(list(inputs.values()) + list(out.values()) + arrays + [c["imu"], c["task_params"], g_q_final, g_qdot_last, g_q_trace])
+        mem = _mem_of(list(inputs.values()) + list(out.values()) + arrays + [c["imu"], c["task_params"], g_q_final, g_qdot_last, g_q_trace] +
+                      list((sseed or {}).values()))
         f, P = np.float64, self._p
         sd = capi.WbcRolloutSeed()
         sd.g_q_final, sd.g_qdot_last = P(g_q_final, f, keep, B, NV, "g_q_final"), P(g_qdot_last, f, keep, B, NV, "g_qdot_last")
@@ -734,6 +744,19 @@ class WbcBatch:
             capi.check(self.lib.wbc_rollout_vjp(self._h, B, C.byref(tin), tp, c["dt"], C.byref(r), tape.buf.data_ptr(), tape.buf.numel(),
                                                  C.byref(sd), mem, C.byref(o), self._stream(mem)), self.lib)
             return out
+        if sseed is not None:
+            ss = capi.WbcScoreSeed()
+            m_ = score_seed.get("mask")
+            ss.score_mask = int(m_) if isinstance(m_, (int, np.integer)) else sum(1 << self._target_index(f_, "score") for f_ in set(m_ or ()))
+            ns = bin(ss.score_mask & 0xFFFFFFFF).count("1")
+            for k_ in ("g_err_sq_sum", "g_err_final", "g_err_max"):
+                setattr(ss, k_, P(sseed[k_], f, keep, ns, B, k_))
+            ss.err_max_tick = P(sseed["err_max_tick"], np.int32, keep, ns, B, "err_max_tick")
+            ss.q_final = P(sseed["q_final"], f, keep, B, NQS, "q_final")
+            capi.check(self.lib.wbc_rollout_vjp_scored(self._h, B, C.byref(tin), tp, c["dt"], C.byref(r), C.byref(tk), tape.buf.data_ptr(),
+                                                       tape.buf.numel(), C.byref(sd), C.byref(ss), mem, C.byref(o), C.byref(tg),
+                                                       self._stream(mem)), self.lib)
+            return dict(out, tracks=t_outs)
         capi.check(self.lib.wbc_rollout_vjp_tracks(self._h, B, C.byref(tin), tp, c["dt"], C.byref(r), C.byref(tk), tape.buf.data_ptr(),
                                                    tape.buf.numel(), C.byref(sd), mem, C.byref(o), C.byref(tg), self._stream(mem)), self.lib)
         return dict(out, tracks=t_outs)

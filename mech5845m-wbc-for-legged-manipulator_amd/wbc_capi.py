@@ -205,6 +205,14 @@ class WbcTracksGrad(C.Structure):
     _fields_ = [("track", WbcTrackGrad * MAX_TRACKS)]
 
 
+# wbc_rollout_vjp_scored: the cotangents of the track scores as a seed of the sweep (include/wbc.h)
+SCORE_SEED_FIELDS = ("g_err_sq_sum", "g_err_final", "g_err_max", "err_max_tick", "q_final")
+
+
+class WbcScoreSeed(C.Structure):
+    _fields_ = [("score_mask", C.c_int32), ("pad_", C.c_int32)] + [(n, C.c_void_p) for n in SCORE_SEED_FIELDS]
+
+
 class WbcFkOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("oMi", "oMf", "J", "com", "Jcom")]
 
@@ -261,6 +269,10 @@ SIGNATURES = {
     "wbc_rollout_vjp_tracks": (_i, [_vp, _i, C.POINTER(WbcTickIn), _vp, _d, C.POINTER(WbcRollout), C.POINTER(WbcTracks), _vp, C.c_size_t,
                                     C.POINTER(WbcRolloutSeed), _i, C.POINTER(WbcRolloutGrad), C.POINTER(WbcTracksGrad), _vp]),
     "wbc_rollout_tracks_grad_sizes": (_i, [c_int32_p, c_int32_p]),
+    "wbc_rollout_vjp_scored": (_i, [_vp, _i, C.POINTER(WbcTickIn), _vp, _d, C.POINTER(WbcRollout), C.POINTER(WbcTracks), _vp, C.c_size_t,
+                                    C.POINTER(WbcRolloutSeed), C.POINTER(WbcScoreSeed), _i, C.POINTER(WbcRolloutGrad),
+                                    C.POINTER(WbcTracksGrad), _vp]),
+    "wbc_rollout_scored_sizes": (_i, [c_int32_p]),
     "wbc_rollout_traj": (_i, [_vp, _i, C.POINTER(WbcTickIn), _vp, _d, C.POINTER(WbcRollout), C.POINTER(WbcTrajectory),
                               C.POINTER(WbcRolloutSummary), _i, _vp]),
     "wbc_rollout_tracks": (_i, [_vp, _i, C.POINTER(WbcTickIn), _vp, _d, C.POINTER(WbcRollout), C.POINTER(WbcTracks),
@@ -336,6 +348,9 @@ def load_library(path=None):
     if sb.value != C.sizeof(WbcTrackGrad) or sc.value != C.sizeof(WbcTracksGrad):
         raise WbcError("ABI mismatch (WbcTrackGrad / WbcTracksGrad): library (%d, %d) vs ctypes (%d, %d)" % (
             sb.value, sc.value, C.sizeof(WbcTrackGrad), C.sizeof(WbcTracksGrad)))
+    lib.wbc_rollout_scored_sizes(C.byref(sb))
+    if sb.value != C.sizeof(WbcScoreSeed):
+        raise WbcError("ABI mismatch (WbcScoreSeed): library %d vs ctypes %d" % (sb.value, C.sizeof(WbcScoreSeed)))
     if path is None:
         _lib = lib
     return lib

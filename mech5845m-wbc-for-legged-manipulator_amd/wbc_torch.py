@@ -391,3 +391,87 @@ def wbc_rollout_tracks_fused(q0, task_params, tracks, inputs, dt, ticks, batch, 
             specs[-1]["du"] = du
         flat += [t["points"], t.get("tangents"), du if torch.is_tensor(du) else None]
     return _WbcRolloutTracksFused.apply(q0, task_params, inputs, dt, ticks, batch, mode, imu, trunk_target_step, specs, *flat)
+
+
+class _WbcRolloutTracksScored(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q0, task_params, inputs, dt, ticks, batch, mode, trunk_target_step, score, specs, *flat):
+        args = [_c(q0), _c(task_params)] + [_c(t) for t in flat]
+        d = dict(inputs)
+        d["q"] = args[0]
+        tracks = []
+        for j, spec in enumerate(specs):     # flat: (points, tangents, du) per track; a du that is no tensor stays in the spec
+            t = dict(spec, points=args[2 + 3 * j])
+            if args[3 + 3 * j] is not None:
+                t["tangents"] = args[3 + 3 * j]
+            if args[4 + 3 * j] is not None:
+                t["du"] = args[4 + 3 * j]
+            tracks.append(t)
+        out, tape = batch.rollout_record(d, dt, ticks, trunk_target_step=_c(trunk_target_step), mode=mode, task_params=args[1], tracks=tracks,
+                                         score=score)
+        ctx.batch, ctx.tape, ctx.score = batch, tape, tuple(score)
+        ctx.set_materialize_grads(False)     # an output the loss does not use gives None, not zeros: its seed is left out of the call
+        _save(ctx, (out["q"], out["q_trace"], out["err_max_tick"]), args)
+        ctx.mark_non_differentiable(out["status"], out["err_max_tick"])
+        return out["q"], out["qdot"], out["status"], out["q_trace"], out["err_sq_sum"], out["err_final"], out["err_max"], out["err_max_tick"]
+
+    @staticmethod
+    def backward(ctx, g_q, g_qdot, _gst, g_trace, g_sq, g_fin, g_max, _gtick):
+        import wbc_workload
+        (q_final, q_trace, err_max_tick), args = _saved(ctx, 3)
+        n_flat = len(args) - 2
+        bt, tape = ctx.batch, ctx.tape
+        K, B = tape.ticks, tape.B
+        need = ctx.needs_input_grad
+        want = [n for n, k in (("d_q0", 0), ("d_task_params", 1)) if need[k] and args[k] is not None]
+        names = ("d_points", "d_tangents", "d_du")
+        need_flat = [bool(need[10 + i]) and args[2 + i] is not None for i in range(n_flat)]
+        want += [n for c, n in enumerate(names) if any(need_flat[c::3])]
+        scored = not (g_sq is None and g_fin is None and g_max is None)
+        if (g_q is None and g_qdot is None and g_trace is None and not scored) or not want:
+            return (None,) * (10 + n_flat)
+        raw, at = [], []
+        if g_q is not None:
+            raw.append(g_q.reshape(B, -1))
+            at.append(q_final)
+        if g_trace is not None:
+            raw.append(g_trace.reshape(K * B, -1))
+            at.append(q_trace.reshape(K * B, -1))
+        gq_f = gq_t = None
+        if raw:
+            tang = wbc_workload.raw_to_tangent(torch.cat(at), torch.cat(raw).contiguous())
+            if g_q is not None:
+                gq_f = tang[:B].contiguous()
+            if g_trace is not None:
+                gq_t = tang[-K * B:].reshape(K, B, -1).contiguous()
+        seed = None
+        if scored:
+            cg = lambda t: None if t is None else t.contiguous()      # noqa: E731
+            seed = dict(mask=ctx.score, g_err_sq_sum=cg(g_sq), g_err_final=cg(g_fin), g_err_max=cg(g_max),
+                        err_max_tick=None if g_max is None else err_max_tick, q_final=q_final)
+        r = bt.rollout_vjp(tape, g_q_final=gq_f, g_qdot_last=None if g_qdot is None else g_qdot.contiguous(), g_q_trace=gq_t, want=want,
+                           score_seed=seed)
+        res = [wbc_workload.tangent_to_raw(args[0], r["d_q0"]) if "d_q0" in want else None,
+               r["d_task_params"].reshape(args[1].shape) if "d_task_params" in want else None]
+        for i in range(n_flat):
+            got = r["tracks"][i // 3].get(names[i % 3]) if need_flat[i] else None
+            res.append(None if got is None else got.reshape(args[2 + i].shape))
+        return tuple(res[:2]) + (None,) * 8 + tuple(res[2:])
+
+
+def wbc_rollout_tracks_scored(q0, task_params, tracks, inputs, dt, ticks, batch, score=(4,), mode=capi.ROLLOUT_RUNNING, trunk_target_step=None):
+    """wbc_rollout_tracks_fused with the tracking scores as differentiable outputs (the loss the roll-out computes on the device): the forward
+    is one WbcBatch.rollout_record(..., tracks=tracks, score=score), the backward one WbcBatch.rollout_vjp(..., score_seed=...)
+    (wbc_rollout_vjp_scored, include/wbc.h: the scores' cotangents are formed where the sweep runs, nothing crosses to the host). score: the
+    scored frames, end effector indices 0..4 and / or "trunk". Returns wbc_rollout_tracks_fused's (q_final, qdot, status, q_trace) and then
+    err_sq_sum, err_final, err_max [n_scored,B] (rows in increasing frame order; differentiable) and err_max_tick [n_scored,B] int32 (not
+    differentiable). A loss may mix the scores with q_final, qdot and q_trace: the gradients are those of the sum. The group RMS is
+    torch.sqrt(err_sq_sum.reshape(n, G, M).sum(-1) / (M * ticks)). No IMU quaternion is fed back under a score (include/wbc.h)."""
+    specs, flat = [], []
+    for t in tracks:
+        du = t.get("du", 0.002)
+        specs.append({k: v for k, v in t.items() if k not in ("points", "tangents", "du")})
+        if not torch.is_tensor(du):
+            specs[-1]["du"] = du
+        flat += [t["points"], t.get("tangents"), du if torch.is_tensor(du) else None]
+    return _WbcRolloutTracksScored.apply(q0, task_params, inputs, dt, ticks, batch, mode, trunk_target_step, tuple(score), specs, *flat)

@@ -1116,12 +1116,54 @@ def step_gradients(model, q_cur, qdot, foot_targets, dt, g, fk, imu=None, mode=c
     return dict(d_q=dq, d_qdot=dx, d_foot_targets=dft)
 
 
+# ---- the track scores as a loss (wbc_rollout_vjp_scored, include/wbc.h)
+def score_seed_gradients(model, q_after, ee_target, trunk_target, fk, mask, g_err_sq_sum=None, g_err_final=None, g_err_max=None,
+                         err_max_tick=None):
+    """The cotangent of the track scores restated for B instances of ONE model. q_after [K, B, 27]: the state after every tick (q_(k+1));
+    ee_target [K, B, 5, 3] / trunk_target [K, B, 3] (None without score bit 5): the targets tick k saw; fk as tick_state_gradients takes it
+    (fk(q) -> oMf, fk.jacobians(q) -> (J, Jcom)); mask: the score mask (bit f: 0..4 the end effectors, 5 the trunk); g_err_* [n_scored, B]
+    the cotangents of err_sq_sum, err_final and err_max, each optional; err_max_tick [n_scored, B] as the record call returned it.
+    With d = FK_f(q_(k+1)) - target_f(k), e = |d|:  c = ((2 g_sq + [k == K - 1] g_fin / e) + [k == err_max_tick] g_max / e) d, the 1 / e
+    terms taken as 0 where e == 0. Returns dict(g_q_trace [K, B, 26]: sum_f J_f' c_f, tangent at q_(k+1) — J_f the [:, :3] block of
+    frame_rows(..., world=False); c [K, B, 6, 3]: the cotangent of d, 0 for an unscored frame (the target of tick k gets -c); e [K, B, 6])."""
+    q_after = np.asarray(q_after, dtype=np.float64)
+    K, B = q_after.shape[:2]
+    frames = [f for f in range(capi.TARGET_TRUNK + 1) if (int(mask) >> f) & 1]
+    take = lambda a: None if a is None else np.asarray(a, dtype=np.float64).reshape(len(frames), B)      # noqa: E731
+    g_sq, g_fin, g_max = take(g_err_sq_sum), take(g_err_final), take(g_err_max)
+    tick = None if err_max_tick is None else np.asarray(err_max_tick).reshape(len(frames), B)
+    if g_max is not None and tick is None:
+        raise ValueError("g_err_max needs err_max_tick")
+    g = np.zeros((K, B, capi.V_STRIDE))
+    c_all, e_all = np.zeros((K, B, capi.TARGET_TRUNK + 1, 3)), np.zeros((K, B, capi.TARGET_TRUNK + 1))
+    for k in range(K):
+        oMf = fk(q_after[k])
+        J, _ = fk.jacobians(q_after[k])
+        for i, f in enumerate(frames):
+            role = capi.FR_TRUNK if f == capi.TARGET_TRUNK else capi.FR_EE0 + f
+            tg = (np.asarray(trunk_target[k], dtype=np.float64).reshape(B, 3) if f == capi.TARGET_TRUNK
+                  else np.asarray(ee_target[k], dtype=np.float64).reshape(B, capi.NEE, 3)[:, f])
+            d = oMf[:, role, 9:12] - tg
+            e = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
+            inv = np.divide(1.0, e, out=np.zeros(B), where=e > 0.0)
+            coef = np.zeros(B) if g_sq is None else 2.0 * g_sq[i]
+            if g_fin is not None and k == K - 1:
+                coef = coef + np.where(e > 0.0, g_fin[i] * inv, 0.0)
+            if g_max is not None:
+                coef = coef + np.where((tick[i] == k) & (e > 0.0), g_max[i] * inv, 0.0)
+            c = coef[:, None] * d
+            Jf = frame_rows(model, J, oMf, role, world=False)[:, :3]
+            g[k] += np.einsum("brk,br->bk", Jf, c)
+            c_all[k, :, f], e_all[k, :, f] = c, e
+    return dict(g_q_trace=g, c=c_all, e=e_all)
+
+
 # ---- K ticks as one reverse sweep (wbc_rollout_vjp, include/wbc.h; DESIGN.md §3.42)
 _ROLLOUT_SUMS = ("d_task_params", "d_com_target", "d_com_target_vel", "d_posture_u")
 
 
 def rollout_gradients(model, cfg, ticks_in, x, dt, fk, assemble, g_q_final=None, g_qdot_last=None, g_q_trace=None, task_params=None, imu=None,
-                      mode=capi.ROLLOUT_RUNNING, status=None, working_set=None, tracks=None):
+                      mode=capi.ROLLOUT_RUNNING, status=None, working_set=None, tracks=None, score_seed=None):
     """wbc_rollout_vjp restated for B instances of ONE model over step_gradients, qp_certificate, tick_gradients and tick_state_gradients,
     tick by tick from the last. ticks_in: K dicts, the inputs tick k SAW (q, the targets as running sums, the previous rotations); x [K, B, 26]:
     the ticks' qdot; assemble(inputs) -> dict(A, b, C, Clb, Cub, lb, ub) of a tick's problem (a model with nv < 26 gets unit rows on its padded
@@ -1137,8 +1179,20 @@ def rollout_gradients(model, cfg, ticks_in, x, dt, fk, assemble, g_q_final=None,
     tracks (wbc_rollout_vjp_tracks): a list of dicts(target: 0..4 or 5 / "trunk", points, n_points, du, kind, tangents) as track_targets takes
     them. A followed target is eval(k * du) on every tick, so its whole cotangent e_k = a + on Pbar goes into the track and nothing is
     carried (Ebar of a followed row is 0 in front of every tick; Pbar updates as above). The dict then also holds tracks = [dict(d_points,
-    d_tangents, d_du), ...] from track_target_gradients; the followed rows of d_ee_target / d_trunk_target are 0 and the steps mean nothing."""
+    d_tangents, d_du), ...] from track_target_gradients; the followed rows of d_ee_target / d_trunk_target are 0 and the steps mean nothing.
+    score_seed (wbc_rollout_vjp_scored): dict(mask, q_final [B, 27], g_err_sq_sum, g_err_final, g_err_max, err_max_tick) — the cotangents of
+    the track scores through score_seed_gradients: its g_q_trace rows join the state seed where g_q_trace enters, and -c_k joins the
+    cotangent of tick k's targets BEHIND that tick's bookkeeping (so the step sums see the later ticks' alone) and in front of the tracks."""
     K = len(ticks_in)
+    sc_c = None
+    if score_seed is not None:
+        q_after = np.stack([np.asarray(ticks_in[k + 1]["q"], dtype=np.float64) for k in range(K - 1)] + [np.asarray(score_seed["q_final"], dtype=np.float64)])
+        want_t = (int(score_seed["mask"]) >> capi.TARGET_TRUNK) & 1
+        ss = score_seed_gradients(model, q_after, [t["ee_target"] for t in ticks_in], [t["trunk_target"] for t in ticks_in] if want_t else None, fk,
+                                  score_seed["mask"], score_seed.get("g_err_sq_sum"), score_seed.get("g_err_final"), score_seed.get("g_err_max"),
+                                  score_seed.get("err_max_tick"))
+        g_q_trace = ss["g_q_trace"] if g_q_trace is None else np.asarray(g_q_trace, dtype=np.float64).reshape(ss["g_q_trace"].shape) + ss["g_q_trace"]
+        sc_c = ss["c"]
     followed = [capi.TARGET_TRUNK if t["target"] == "trunk" else int(t["target"]) for t in (tracks or [])]
     e_tracks = [np.zeros((K, np.asarray(x).reshape(K, -1, capi.V_STRIDE).shape[1], 3)) for _ in followed]
     x = np.asarray(x, dtype=np.float64).reshape(K, -1, capi.V_STRIDE)
@@ -1190,6 +1244,9 @@ def rollout_gradients(model, cfg, ticks_in, x, dt, fk, assemble, g_q_final=None,
         Eb, Pb = Eb + a_k + np.where(on, Pb, 0.0), p_k + np.where(on, 0.0, Pb)
         d_ts = d_ts + TEb
         TEb, TPb = TEb + take(tg["d_trunk_target"]) + (TPb if on_t else 0.0), take(tg["d_prev_trunk_target"]) + (0.0 if on_t else TPb)
+        if sc_c is not None:                   # the scores' own dependence on the targets of tick k
+            Eb = Eb - sc_c[k][:, :capi.NEE]
+            TEb = TEb - sc_c[k][:, capi.TARGET_TRUNK]
         for j, f in enumerate(followed):       # the followed rows: into the track, nothing carried
             if f == capi.TARGET_TRUNK:
                 e_tracks[j][k] = TEb

@@ -1,12 +1,16 @@
 #!/usr/bin/env python3
-"""Trajectory optimisation through the controller (wbc_torch.wbc_rollout_tracks_fused: a roll-out along tracks as one torch layer).
+"""Trajectory optimisation through the controller (wbc_torch.wbc_rollout_tracks_scored: a roll-out along tracks as one torch layer whose
+tracking scores are differentiable outputs).
 
 Every instance of a batch of sampled stances has its gripper follow a HERMITE track of four milestones for K closed-loop ticks, with the
 contacts, the trunk box and the velocity dampers enforced by every tick's QP. Adam descends on the two interior milestones and on du (the
-track's speed) of every instance, so that the gripper of q_K — where the robot actually is after the roll-out, not where the track points —
-reaches a goal 2 cm from where it starts. The first and the last milestone stay put: the start, and the goal itself. The gripper's position
-at q_K comes from the library's kinematics, linearised at the reached state (p + J (q_K (-) stop-gradient q_K) has the value p and the gradient J).
-It prints the loss per iteration; a demonstration, no assertion.
+track's speed) of every instance. The first and the last milestone stay put: the start, and a goal 2 cm from where the gripper starts. The
+loss is the roll-out's own score of the gripper against its target of the tick, formed on the device (include/wbc.h,
+wbc_rollout_vjp_scored) and masked by the roll-out's status: nothing crosses to the host inside the loop. Two variants, one after the other:
+    final   err_final ** 2: the gripper after the last tick against the track's target of that tick
+    sum     err_sq_sum: the squared tracking error summed over every tick
+It prints the loss per iteration and, for both variants, the gripper's distance to the goal after the last tick (from the library's
+kinematics, once, outside the loop); a demonstration, no assertion.
     python3 tools/fit_track.py [B] [K] [steps]"""
 import os
 import sys
@@ -40,33 +44,31 @@ dev = {k: torch.from_numpy(np.ascontiguousarray(v)).cuda() for k, v in d.items()
 rest = {k: v for k, v in dev.items() if k != "q"}
 ends = torch.from_numpy(points0).cuda()
 goal_t = torch.from_numpy(goal).cuda()
-inner = ends[:, 1:3].clone().requires_grad_(True)                         # the two interior milestones
-log_du = torch.full((B,), float(np.log(3.0 / K)), dtype=torch.float64, device="cuda").requires_grad_(True)   # du > 0; the track ends at tick K
-opt = torch.optim.Adam([inner, log_du], lr=2e-3)
 
 
-def gripper_of(q):
-    """the gripper's position at q [B,27] as a function of q: the library's kinematics, first order around q itself"""
-    qh = q.detach()
-    f = bt.fk(qh, want=("oMf", "J"))
-    J = torch.as_tensor(wbc_workload.frame_rows(model, f["J"].cpu().numpy(), f["oMf"].cpu().numpy(), capi.FR_EE0 + 4, world=False)[:, :3]).cuda()
-    tang = torch.as_tensor(wbc_workload.raw_tangent_map(model, qh.cpu().numpy())).cuda()      # [B, 27, 26]: d(raw q) / d(tangent)
-    # least-squares tangent of the raw difference (zero in value): its gradient with respect to q is pinv(tang)' J'
-    delta = torch.linalg.lstsq(tang, (q - qh).unsqueeze(-1)).solution.squeeze(-1)
-    return f["oMf"][:, capi.FR_EE0 + 4, 9:] + torch.einsum("brk,bk->br", J, delta)
+def fit(variant):
+    inner = ends[:, 1:3].clone().requires_grad_(True)                     # the two interior milestones
+    log_du = torch.full((B,), float(np.log(3.0 / K)), dtype=torch.float64, device="cuda").requires_grad_(True)   # du > 0; the track ends at tick K
+    opt = torch.optim.Adam([inner, log_du], lr=2e-3)
+    q = None
+    for step in range(STEPS):
+        points = torch.cat([ends[:, :1], inner, ends[:, 3:]], dim=1).contiguous()
+        track = dict(target=4, kind="hermite", points=points, du=torch.exp(log_du))
+        q, qdot, status, _, err_sq_sum, err_final, err_max, _ = wbc_torch.wbc_rollout_tracks_scored(dev["q"], None, [track], rest, DT, K, bt, score=(4,))
+        solved = (status == 0).to(q.dtype)
+        per = (err_final[0] ** 2 if variant == "final" else err_sq_sum[0]) * solved
+        loss = per.sum()
+        opt.zero_grad()
+        loss.backward()
+        opt.step()
+        print("%s, iteration %3d: loss %.6e   tracking error, mm: final mean %.4f  max over the ticks %.4f   du: median %.4f  (solved %d / %d)" % (
+            variant, step, float(loss.detach()), 1e3 * float(err_final.detach().mean()), 1e3 * float(err_max.detach().max()),
+            float(torch.exp(log_du).detach().median()), int(solved.sum()), B))
+    return q.detach()
 
 
-for step in range(STEPS):
-    points = torch.cat([ends[:, :1], inner, ends[:, 3:]], dim=1).contiguous()
-    track = dict(target=4, kind="hermite", points=points, du=torch.exp(log_du))
-    q, qdot, status, _ = wbc_torch.wbc_rollout_tracks_fused(dev["q"], None, [track], rest, DT, K, bt)
-    solved = (status == 0).to(q.dtype)
-    per = ((gripper_of(q) - goal_t) ** 2).sum(dim=1) * solved
-    loss = per.sum()
-    opt.zero_grad()
-    loss.backward()
-    opt.step()
-    e = 1e3 * torch.sqrt(per.detach())
-    print("iteration %3d: loss %.6e   gripper to goal after %d ticks, mm: mean %.4f  max %.4f   du: median %.4f  (solved %d / %d)" % (
-        step, float(loss.detach()), K, float(e.mean()), float(e.max()), float(torch.exp(log_du).detach().median()), int(solved.sum()), B))
+for variant in ("final", "sum"):
+    q_end = fit(variant)
+    dist = 1e3 * torch.linalg.norm(bt.fk(q_end, want=("oMf",))["oMf"][:, capi.FR_EE0 + 4, 9:] - goal_t, dim=1)
+    print("%s: gripper to goal after %d ticks, mm: mean %.4f  max %.4f" % (variant, K, float(dist.mean()), float(dist.max())))
 bt.close()
