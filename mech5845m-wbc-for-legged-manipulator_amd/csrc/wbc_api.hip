@@ -7,7 +7,8 @@
 #include <new>
 #include <vector>
 #include "wbc_device.h"
-#include "wbc_traj.h"
+#include "wbc_traj.h"        // (brings in wbc_track.h, whose file-scope `#pragma clang fp contract(off)` holds for the rest of this unit: host code
+                             //  only, no device code, and the x86 build contracts nothing either way)
 #include "wbc_slack.h"
 #include "wbc_cert.h"
 #include "wbc_grad.h"
@@ -1460,6 +1461,16 @@ static int give(hipStream_t s, void* dst, const void* src, size_t bytes) {   // 
   return WBC_OK;
 }
 
+// every track's inputs and, in the sweep (tg), behind each track's inputs its outputs
+static void stage_tracks(Stager& st, WbcTracks& tj, size_t n, WbcTracksGrad* tg = nullptr) {
+  for (int j = 0; j < tj.n_tracks; ++j) {
+    WbcTrack& t = tj.track[j];
+    const size_t np = n * (size_t)t.max_points * 3;
+    st.in(&t.points, np); st.in(&t.tangents, np); st.in(&t.n_points, n); st.in(&t.du, n);
+    if (tg) { st.out(&tg->track[j].d_points, np); st.out(&tg->track[j].d_tangents, np); st.out(&tg->track[j].d_du, n); }
+  }
+}
+
 // Tracks (wbc_rollout_traj / wbc_rollout_tracks, arguments checked by the entry point): the update kernel leaves the followed targets alone
 // and one wbc_traj_tick_kernel per tick scores the tick and writes every followed target of the next. one_track: wbc_rollout_traj's call —
 // the gripper's position comes from the update kernel's grip_trace row, and a constant trunk step stays with the update kernel; otherwise
@@ -1472,11 +1483,7 @@ struct TracksExt {
       : scored(scores != nullptr), one_track(one), nsc(scores ? (size_t)__builtin_popcount((unsigned)scores->score_mask) : 0), tj(tracks), so(scores ? *scores : WbcTrackScores{}), ta{}, ws{} {}
   void stage(Stager& st, size_t n, int ticks) {
     const size_t ng = so.group_size > 0 ? n / (size_t)so.group_size : 0;
-    for (int j = 0; j < tj.n_tracks; ++j) {
-      WbcTrack& t = tj.track[j];
-      const size_t np = n * (size_t)t.max_points * 3;
-      st.in(&t.points, np); st.in(&t.tangents, np); st.in(&t.n_points, n); st.in(&t.du, n);
-    }
+    stage_tracks(st, tj, n);
     st.out(&tj.trunk_target_final, n * 3);
     st.out(&so.err_sq_sum, nsc * n); st.out(&so.err_max, nsc * n); st.out(&so.err_max_tick, nsc * n); st.out(&so.err_final, nsc * n);
     st.out(&so.first_bad_tick, n); st.out(&so.bad_ticks, n); st.out(&so.trace, (size_t)ticks * nsc * n * 3);
@@ -1488,12 +1495,7 @@ struct TracksExt {
     ta.err_sq_sum = ws.err_sq_sum; ta.err_max = ws.err_max; ta.err_final = ws.err_final; ta.err_max_tick = ws.err_max_tick;
     ta.bad = ws.bad; ta.first_bad_tick = ws.first_bad_tick; ta.bad_ticks = ws.bad_ticks; ta.status_max = ws.status_max; ta.bad_count = ws.bad_count;
     ta.B = R.B; ta.ticks = R.ticks; ta.n_tracks = tj.n_tracks; ta.do_sum = scored; ta.score_mask = so.score_mask;
-    for (int j = 0; j < tj.n_tracks; ++j) {
-      const WbcTrack& t = tj.track[j];
-      TrajTrack& d = ta.tr[j];
-      d.target = t.target; d.kind = t.kind; d.S = t.max_points;
-      d.points = t.points; d.tangents = t.tangents; d.n_points = t.n_points; d.du = t.du; d.du_all = t.du_all;
-    }
+    for (int j = 0; j < tj.n_tracks; ++j) fill_track(ta.tr[j], tj.track[j]);
     ta.ee_target = R.w.ee_target; ta.trunk_target = R.w.trunk_target;
     if (!one_track) R.u.trunk_step = nullptr;   // wbc_rollout_tracks' constant trunk step is added by the trajectory kernel, after the tick was scored
     if (!one_track && ta.trunk_target) ta.trunk_step = R.ro.trunk_target_step;
@@ -1855,213 +1857,6 @@ template <class T> static int ensure_size(T*& p, size_t& have, size_t want) {   
   have = want;
   return WBC_OK;
 }
-static int check_tracks_call(int B, const WbcTickIn* in0, const WbcRollout* r, const WbcTracks* tracks, const WbcTrackScores* scores);
-// what wbc_rollout_vjp_tracks refuses beyond both calls' own refusals, before any launch
-static int check_tracks_grad(const WbcTracks& tk, const WbcRolloutGrad* out, const WbcTracksGrad* tg, const char* who) {
-  if (!tg) return fail(WBC_E_ARG, "%s: tracks_out is required", who);
-  if (out && out->d_ee_target_step) return fail(WBC_E_ARG, "%s: d_ee_target_step requested, but a roll-out along tracks has no ee_target_step", who);
-  for (int j = 0; j < WBC_MAX_TRACKS; ++j) {
-    const WbcTrackGrad& g = tg->track[j];
-    if (j >= tk.n_tracks) {
-      if (g.d_points || g.d_tangents || g.d_du)
-        return fail(WBC_E_ARG, "%s: tracks_out->track[%d] has an output set, but n_tracks = %d", who, j, tk.n_tracks);
-      continue;
-    }
-    const WbcTrack& t = tk.track[j];
-    if (t.target == WBC_TARGET_TRUNK && out && out->d_trunk_target_step)
-      return fail(WBC_E_ARG, "%s: d_trunk_target_step requested, but track %d moves the trunk target (there is no trunk_target_step)", who, j);
-    if (g.d_tangents && (t.kind != WBC_TRACK_HERMITE || !t.tangents))
-      return fail(WBC_E_ARG, "%s: tracks_out->track[%d].d_tangents requested, but the track is %s", who, j,
-                  t.kind != WBC_TRACK_HERMITE ? "LINEAR" : "HERMITE with tangents == NULL (the default rule: its gradient is part of d_points)");
-  }
-  return WBC_OK;
-}
-// what wbc_rollout_vjp_scored refuses beyond wbc_rollout_vjp_tracks' refusals, before any launch
-static int check_score_seed(const WbcScoreSeed& sc, const WbcTickIn* in0, const WbcRollout* r, const char* who) {
-  if (!sc.g_err_sq_sum && !sc.g_err_final && !sc.g_err_max)
-    return fail(WBC_E_ARG, "%s: a score cotangent is required (g_err_sq_sum, g_err_final or g_err_max)", who);
-  if (sc.g_err_max && !sc.err_max_tick) return fail(WBC_E_ARG, "%s: g_err_max needs err_max_tick (as the record call returned it)", who);
-  if (!sc.q_final) return fail(WBC_E_ARG, "%s: q_final is required (the state after the last tick: the tape ends one state earlier)", who);
-  if (sc.score_mask <= 0 || sc.score_mask >= (1 << WBC_MAX_TRACKS))
-    return fail(WBC_E_ARG, "%s: score_mask = 0x%x, want a bit of the frames 0..%d and none beyond", who, (unsigned)sc.score_mask, WBC_TARGET_TRUNK);
-  if (((sc.score_mask >> WBC_TARGET_TRUNK) & 1) && !in0->trunk_target)
-    return fail(WBC_E_ARG, "%s: score_mask bit %d needs in0->trunk_target", who, WBC_TARGET_TRUNK);
-  if (r->imu) return fail(WBC_E_ARG, "%s: imu must be NULL (with an IMU quaternion fed back the state discards the orientation the scored position was formed with)", who);
-  return WBC_OK;
-}
-// The sweep of wbc_rollout_vjp and, with tracks, of wbc_rollout_vjp_tracks: the same launches, plus one stage of the track-adjoint kernel behind
-// the link kernel's BEGIN and behind every LINK. With a score seed (wbc_rollout_vjp_scored) also one stage of the score-cotangent kernel in
-// front of every tick's step layer and one between LINK and the track stage.
-static int rollout_vjp_run(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r, const void* tape,
-                           size_t tape_bytes, const WbcRolloutSeed* seed, int mem, const WbcRolloutGrad* out, void* stream, const char* who,
-                           bool with_tracks, const WbcTracks* tracks, const WbcTracksGrad* tracks_out, bool with_score = false,
-                           const WbcScoreSeed* score = nullptr) {
-  int rc;
-  if (with_score && !score) return fail(WBC_E_ARG, "%s: score is required (wbc_rollout_vjp_tracks is the call without one)", who);
-  if (with_tracks && (rc = check_tracks_call(B, in0, r, tracks, nullptr))) return rc;   // (first: tracks == NULL is refused before a field of it is read)
-  if ((rc = check_record_call(b, B, in0, r, tape, tape_bytes, who))) return rc;
-  if (!out) return fail(WBC_E_ARG, "%s: out is required", who);
-  if (with_tracks && (rc = check_tracks_grad(*tracks, out, tracks_out, who))) return rc;
-  if (!with_score && (!seed || !(seed->g_q_final || seed->g_qdot_last || seed->g_q_trace)))
-    return fail(WBC_E_ARG, "%s: a seed is required (g_q_final, g_qdot_last or g_q_trace)", who);
-  if (with_score && (rc = check_score_seed(*score, in0, r, who))) return rc;
-  if ((rc = check_dt(dt, who))) return rc;
-  if (r->mode != WBC_ROLLOUT_RUNNING && r->mode != WBC_ROLLOUT_WARMUP)
-    return fail(WBC_E_ARG, "%s: mode = %d, want WBC_ROLLOUT_RUNNING (%d) or WBC_ROLLOUT_WARMUP (%d)", who, r->mode, WBC_ROLLOUT_RUNNING, WBC_ROLLOUT_WARMUP);
-  if ((rc = validate_tick_in(b, in0, who))) return rc;
-  if (!in0->ee_target || !in0->prev_ee_target) return fail(WBC_E_ARG, "%s: ee_target / prev_ee_target are required (the base estimator reads the foot targets)", who);
-  const Reads rd(b, r->mode == WBC_ROLLOUT_RUNNING);   // the estimator reads ee_target: the step's d_foot_targets reaches it without an EE task
-  if ((rc = check_outs(*out, ROLL_OUT, rd, who, false))) return rc;
-  HIP_TRY(hipSetDevice(b->device_id));
-  // size the workspace: the task rows of wbc_assemble, the unit rows on the padded columns of the handle's smallest model, the constraint rows
-  int min_nv = WBC_V_STRIDE;
-  for (int i = 0; i < b->n_models; ++i) if (b->models[i]->dev.nv < min_nv) min_nv = b->models[i]->dev.nv;
-  const int m = b->mrows, pad_rows = WBC_V_STRIDE - min_nv, M = m + pad_rows, p = rd.p, K = r->ticks;
-  if (M > WBC_MAX_M) return fail(WBC_E_UNSUPPORTED, "%s: %d task rows + %d padding rows exceed the certificate's %d", who, m, pad_rows, WBC_MAX_M);
-  const size_t NB = (size_t)b->max_batch, n = (size_t)B;
-  if ((rc = ensure_size(b->d_rvjp, b->rvjp_bytes, RollVjpWs::bytes(NB, (size_t)M, (size_t)p)))) return rc;   // (after one call of these row counts: no allocation)
-  const RollVjpWs w = RollVjpWs::carve(b->d_rvjp, NB, (size_t)M, (size_t)p);
-  // stage
-  KernelArgs a;
-  fill_args(a, b, B, dt);
-  a.in = *in0;
-  a.in.working_set = nullptr;
-  WbcRolloutSeed sd = seed ? *seed : WbcRolloutSeed{};
-  WbcScoreSeed ss = with_score ? *score : WbcScoreSeed{};
-  WbcRolloutGrad og = *out;
-  const double* imu = r->imu;
-  Stager st{b, mem, (hipStream_t)stream, {}};
-  stage_tick_in(st, a.in, B, b);
-  st.in(&tp, n); st.in(&imu, n * 4);
-  st.in(&sd.g_q_final, n * WBC_V_STRIDE); st.in(&sd.g_qdot_last, n * WBC_V_STRIDE); st.in(&sd.g_q_trace, (size_t)K * n * WBC_V_STRIDE);
-  if (with_score) {
-    const size_t ns = (size_t)__builtin_popcount((unsigned)ss.score_mask) * n;
-    st.in(&ss.g_err_sq_sum, ns); st.in(&ss.g_err_final, ns); st.in(&ss.g_err_max, ns); st.in(&ss.err_max_tick, ns); st.in(&ss.q_final, n * WBC_Q_STRIDE);
-  }
-  stage_outs(st, og, ROLL_OUT, n);
-  st.out(&og.grad_status, n); st.out(&og.ticks_dropped, n);
-  WbcTracks tj = with_tracks ? *tracks : WbcTracks{};
-  WbcTracksGrad tg = with_tracks ? *tracks_out : WbcTracksGrad{};
-  for (int j = 0; j < tj.n_tracks; ++j) {
-    WbcTrack& t = tj.track[j];
-    const size_t np = n * (size_t)t.max_points * 3;
-    st.in(&t.points, np); st.in(&t.tangents, np); st.in(&t.n_points, n); st.in(&t.du, n);
-    st.out(&tg.track[j].d_points, np); st.out(&tg.track[j].d_tangents, np); st.out(&tg.track[j].d_du, n);
-  }
-  if ((rc = st.stage())) return rc;
-  const WbcTickIn first = a.in;
-  const bool have_ws = b->warm_start != 0;   // the tape holds working sets (the option as it was when the tape was recorded: include/wbc.h)
-  void* const tp_mut = const_cast<void*>(tape);   // (read only: TapeWs carves non-const pointers)
-  const TapeHead head = TapeHead::carve(tp_mut, n);
-  // the outputs of the layers, in the workspace. The tick layer runs where an output of the sweep needs one of its (the state side runs on
-  // every tick: g needs it); each of its outputs is wired where the configuration reads what it is the gradient of
-  bool want_tick = false;
-  for (const OutRow<WbcRolloutGrad>& row : ROLL_OUT) want_tick |= og.*row.ptr && row.ptr != &WbcRolloutGrad::d_q0 && row.ptr != &WbcRolloutGrad::d_trunk_box_center;
-  for (int j = 0; j < tj.n_tracks; ++j) want_tick |= tg.track[j].d_points || tg.track[j].d_tangents || tg.track[j].d_du;   // (a track's cotangent is the tick layer's d_*_target)
-  const WbcStepGrad s_out{w.s_dq, w.v, w.s_dft, w.gs_step};
-  const WbcTickStateGrad q_out{w.t_dq, rd.con_trunk ? w.t_box : nullptr, w.gs_tickq};
-  WbcQpCert c_out{};
-  c_out.y_rows = w.y_rows; c_out.sens_x = w.sens_x; c_out.sens_bounds = w.sens_bounds; c_out.sens_rows = w.sens_rows; c_out.cert_status = w.cert_status;
-  RollVjpArgs L;
-  memset(&L, 0, sizeof L);
-  if (want_tick) {
-    L.t.grad_status = w.gs_tick;
-    for (size_t i = 0; i < sizeof(TICK_WS) / sizeof(TICK_WS[0]); ++i)
-      if (rd(TICK_OUT[i].need)) L.t.*TICK_WS[i].out = w.*TICK_WS[i].ws;
-  }
-  L.models = b->d_models; L.model_id = first.model_id; L.B = B; L.n_models = b->n_models; L.K = K; L.m = m; L.pad_rows = pad_rows;
-  L.ee_on = rd.ee_on; L.trunk_on = rd.trunk;
-  L.g_q_final = sd.g_q_final; L.g_qdot_last = sd.g_qdot_last; L.g_q_trace = sd.g_q_trace;
-  L.A = w.A; L.b = w.b; L.g = w.g; L.v = w.v;
-  L.s_dq = s_out.d_q; L.s_dft = rd.est ? s_out.d_foot_targets : nullptr; L.t_dq = q_out.d_q; L.t_box = q_out.d_trunk_box_center;
-  L.gs_step = w.gs_step; L.gs_tickq = w.gs_tickq;
-  L.Ebar = w.Ebar; L.Pbar = w.Pbar; L.TEbar = w.TEbar; L.TPbar = w.TPbar; L.d_estep = w.d_estep; L.d_tstep = w.d_tstep; L.acc_tp = w.acc_tp;
-  L.acc_com = w.acc_com; L.acc_comv = w.acc_comv; L.acc_pu = w.acc_pu; L.acc_box = w.acc_box; L.worst = w.worst; L.dropped = w.dropped;
-  L.out = og;
-  auto link = [&](int stage, int k) {   // (the launch chain is linear: every stage waits for the one before it on the stream)
-    L.k = k;
-    return launch_rc(launch_rollvjp(L, stage, stream, &b->last_rollvjp_variant), "roll-out gradient link");
-  };
-  TrackVjpArgs V;
-  memset(&V, 0, sizeof V);
-  V.B = B; V.n_tracks = tj.n_tracks; V.Ebar = w.Ebar; V.TEbar = w.TEbar; V.worst = w.worst;
-  V.d_ee_target = og.d_ee_target; V.d_trunk_target = og.d_trunk_target;
-  for (int j = 0; j < tj.n_tracks; ++j) {
-    const WbcTrack& t = tj.track[j];
-    TrackVjpTrack& d = V.tr[j];
-    d.target = t.target; d.kind = t.kind; d.S = t.max_points;
-    d.points = t.points; d.tangents = t.tangents; d.n_points = t.n_points; d.du = t.du; d.du_all = t.du_all;
-    d.d_points = tg.track[j].d_points; d.d_tangents = tg.track[j].d_tangents; d.d_du = tg.track[j].d_du;
-  }
-  auto track = [&](int stage, int k) {   // (with tracks alone: the plain sweep launches what it launched)
-    V.k = k;
-    return launch_rc(launch_trackvjp(V, stage, stream, &b->last_trackvjp_variant), "roll-out gradient track adjoint");
-  };
-  ScoreVjpArgs S;
-  memset(&S, 0, sizeof S);
-  S.models = b->d_models; S.plans = b->d_plans; S.model_id = first.model_id; S.B = B; S.n_models = b->n_models; S.K = K; S.rot = b->rot;
-  S.score_mask = ss.score_mask; S.g_sq = ss.g_err_sq_sum; S.g_fin = ss.g_err_final; S.g_max = ss.g_err_max; S.err_max_tick = ss.err_max_tick;
-  S.g = w.g; S.stash = w.stash; S.worst = w.worst; S.Ebar = w.Ebar; S.TEbar = w.TEbar;
-  S.d_ee_target = og.d_ee_target; S.d_trunk_target = og.d_trunk_target;
-  auto score_stage = [&](int stage, int k) {
-    S.k = k;
-    // (the statistic names the SEED row, the stage with kinematics and a ROT form; TARGET has one row)
-    return launch_rc(launch_scorevjp(S, stage, stream, stage == SCOREVJP_SEED ? &b->last_scorevjp_variant : nullptr), "roll-out gradient score cotangent");
-  };
-  if ((rc = link(ROLLVJP_BEGIN, K - 1))) return rc;
-  if (with_tracks && (rc = track(TRACKVJP_BEGIN, K - 1))) return rc;
-  for (int k = K - 1; k >= 0; --k) {
-    const TapeWs T = TapeWs::carve(tp_mut, n, k);
-    WbcTickIn in = first;   // the inputs tick k saw
-    in.q = T.q; in.ee_target = T.ee_target; in.prev_ee_target = T.prev_ee_target;
-    if (first.trunk_target) in.trunk_target = T.trunk_target;
-    if (first.prev_trunk_target) in.prev_trunk_target = T.prev_trunk_target;
-    if (k > 0 && first.ee_prev_rot) in.ee_prev_rot = head.ee_prev_rot;
-    if (k > 0 && first.trunk_prev_rot) in.trunk_prev_rot = head.trunk_prev_rot;
-    if (with_score) {   // g += J' c at q_(k+1): the tape's q of tick k + 1, the caller's q_final behind the last tick; -c into the stash
-      S.q = k == K - 1 ? ss.q_final : TapeWs::carve(tp_mut, n, k + 1).q;
-      S.ee_target = T.ee_target; S.trunk_target = first.trunk_target ? T.trunk_target : nullptr;
-      if ((rc = score_stage(SCOREVJP_SEED, k))) return rc;
-    }
-    // the step: g -> d_q, v = d_qdot, d_foot_targets; on the last tick v += g_qdot_last
-    if ((rc = step_layer(b, B, dt, r->mode, T.q, T.qdot, T.ee_target, imu, first.model_id, w.g, s_out, stream))) return rc;
-    if (k == K - 1 && sd.g_qdot_last && (rc = link(ROLLVJP_ADDV, K - 1))) return rc;
-    // the tick's problem at the taped inputs. mrows = M is the stride of A: the padding rows stay where BEGIN wrote them
-    a.in = in;
-    a.mrows = M;
-    a.qp = WbcQpData{};
-    a.qp.A = w.A; a.qp.b = w.b; a.qp.lb = w.lb; a.qp.ub = w.ub;
-    if (p > 0) { a.qp.C = w.C; a.qp.Clb = w.Clb; a.qp.Cub = w.Cub; }
-    if ((rc = auto_posture(b, a, B, stream))) return rc;
-    if ((rc = launch_rc(launch_tick(a, MODE_ASSEMBLE, grid_tick(b, B), stream, tp, &b->last_tick_variant), "assemble"))) return rc;
-    // its certificate with v. The working set reaches the certificate and the tick-state layer under warm_start alone: only then the tape holds it
-    WbcQpProblem qp{};
-    qp.n = WBC_V_STRIDE; qp.p = p; qp.m = M;
-    qp.A = w.A; qp.b = w.b; qp.C = w.C; qp.lb = w.lb; qp.ub = w.ub; qp.Clb = w.Clb; qp.Cub = w.Cub;
-    qp.x = T.qdot; qp.v = w.v; qp.status = T.status; qp.working_set = have_ws ? (const uint64_t*)T.working_set : nullptr;
-    if ((rc = cert_layer(b, B, qp, c_out, stream))) return rc;
-    // the tick's two layers: the first is skipped when none of its outputs is asked for
-    if (want_tick && (rc = tick_layer(b, B, dt, a.in, tp, T.qdot, w.sens_x, T.status, w.cert_status, L.t, stream))) return rc;
-    WbcTickSens sn{};
-    sn.qdot = T.qdot; sn.sens_x = w.sens_x; sn.sens_bounds = w.sens_bounds; sn.sens_rows = w.sens_rows; sn.y_rows = w.y_rows;
-    sn.status = T.status; sn.cert_status = w.cert_status; sn.working_set = qp.working_set;
-    if ((rc = tickq_layer(b, B, dt, in, tp, sn, q_out, stream))) return rc;
-    if ((rc = link(ROLLVJP_LINK, k))) return rc;
-    if (with_score && (rc = score_stage(SCOREVJP_TARGET, k))) return rc;
-    if (with_tracks && (rc = track(TRACKVJP_TICK, k))) return rc;
-  }
-  return st.finish();
-}
-extern "C" int wbc_rollout_vjp(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r, const void* tape,
-                               size_t tape_bytes, const WbcRolloutSeed* seed, int mem, const WbcRolloutGrad* out, void* stream) {
-  return rollout_vjp_run(b, B, in0, tp, dt, r, tape, tape_bytes, seed, mem, out, stream, "wbc_rollout_vjp", false, nullptr, nullptr);
-}
-extern "C" int wbc_rollout_grad_sizes(int32_t* sizeof_seed, int32_t* sizeof_grad) {
-  if (sizeof_seed) *sizeof_seed = (int32_t)sizeof(WbcRolloutSeed);
-  if (sizeof_grad) *sizeof_grad = (int32_t)sizeof(WbcRolloutGrad);
-  return WBC_OK;
-}
-
 // ---- argument checks of the track calls. `who`: the entry point's name; `pre`: "" or "track J: " (the text of every message is the callers')
 static int check_group_size(const char* who, int group_size, int B) {
   if (group_size < 0 || (group_size > 0 && (B < 1 || B % group_size != 0))) return fail(WBC_E_ARG, "%s: group_size = %d does not divide B = %d", who, group_size, B);
@@ -2076,36 +1871,9 @@ static int check_track(const WbcTrack& t, const char* who, const char* pre) {
   return WBC_OK;
 }
 
-// The roll-out along per-instance milestone trajectories (WbcTrajectory), scored on the device (WbcRolloutSummary): argument checks, then
-// the shared loop on the one-track call: a LINEAR track of end effector ee_index, the gripper scored.
-extern "C" int wbc_rollout_traj(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
-                                const WbcTrajectory* traj, const WbcRolloutSummary* sum, int mem, void* stream) {
-  if (!r || !traj) return fail(WBC_E_ARG, "wbc_rollout_traj: r and traj are required");
-  if (r->ee_target_step) return fail(WBC_E_ARG, "wbc_rollout_traj: ee_target_step must be NULL (the trajectory moves the followed target; the other EE targets are constant)");
-  if (r->hold_ticks != 0) return fail(WBC_E_ARG, "wbc_rollout_traj: hold_ticks must be 0 (a trajectory holds its last milestone by itself)");
-  if (traj->ee_index < 0 || traj->ee_index >= WBC_NEE) return fail(WBC_E_ARG, "wbc_rollout_traj: ee_index = %d outside [0, %d]", traj->ee_index, WBC_NEE - 1);
-  WbcTracks tk{};
-  WbcTrackScores sc{};
-  WbcTrack& t = tk.track[0];
-  tk.n_tracks = 1; sc.score_mask = 1 << 4;
-  t.target = traj->ee_index; t.kind = WBC_TRACK_LINEAR; t.max_points = traj->max_points;
-  t.points = traj->points; t.n_points = traj->n_points; t.du = traj->du; t.du_all = traj->du_all;
-  int rc;
-  if ((rc = check_track(t, "wbc_rollout_traj", "")) || (sum && (rc = check_group_size("wbc_rollout_traj", sum->group_size, B)))) return rc;
-  if (sum) {
-    sc.group_size = sum->group_size;
-    sc.err_sq_sum = sum->err_sq_sum; sc.err_max = sum->err_max; sc.err_final = sum->err_final; sc.err_max_tick = sum->err_max_tick;
-    sc.first_bad_tick = sum->first_bad_tick; sc.bad_ticks = sum->bad_ticks;
-    sc.group_rms = sum->group_rms; sc.group_err_max = sum->group_err_max;
-    sc.group_worst_status = sum->group_worst_status; sc.group_bad_instances = sum->group_bad_instances;
-  }
-  TracksExt ext(tk, sum ? &sc : nullptr, true);
-  return rollout_run(b, B, in0, tp, dt, r, mem, stream, &ext);
-}
-
 // The argument checks of wbc_rollout_tracks (several followed targets — WbcTracks: end effectors and trunk, LINEAR or HERMITE — any frame
 // scored: WbcTrackScores), also wbc_rollout_watch's with tracks.
-static int check_tracks_call(int B, const WbcTickIn* in0, const WbcRollout* r, const WbcTracks* tracks, const WbcTrackScores* scores) {   // (declared above the sweep)
+static int check_tracks_call(int B, const WbcTickIn* in0, const WbcRollout* r, const WbcTracks* tracks, const WbcTrackScores* scores) {
   const char* who = "wbc_rollout_tracks";
   if (!r || !tracks) return fail(WBC_E_ARG, "wbc_rollout_tracks: r and tracks are required");
   if (r->ee_target_step) return fail(WBC_E_ARG, "wbc_rollout_tracks: ee_target_step must be NULL (tracks move the followed targets; the other EE targets are constant)");
@@ -2136,6 +1904,265 @@ static int check_tracks_call(int B, const WbcTickIn* in0, const WbcRollout* r, c
     return fail(WBC_E_ARG, "wbc_rollout_tracks: a trunk track or score bit %d needs in0->trunk_target and prev_trunk_target", WBC_TARGET_TRUNK);
   return WBC_OK;
 }
+
+// ---- The reverse sweep (wbc_rollout_vjp / _tracks / _scored): rollout_vjp_run is the one sweep, as rollout_run is the one
+// loop — check, stage, link BEGIN, begin extensions, per tick from K - 1 down to 0 {before_step, step, [ADDV], posture, assemble, certificate,
+// [tick layer], tick-state layer, LINK, after_link}, finish. An extension (TrackAdjExt, ScoreSeedExt) holds the caller's structs and its
+// kernel's argument struct and provides check (what its call refuses beyond the sweep's own refusals, before any launch), stage (its Stager
+// registrations), begin, before_step(k) and after_link(k); one the entry point does not pass adds nothing to the stream.
+struct Sweep {               // what the stages of one sweep share
+  WbcBatch* b; int B, K; size_t n; void* stream; void* tape;
+  RollVjpWs w; WbcRolloutGrad og; WbcTickIn first;   // the workspace; the caller's outputs and inputs, their pointers staged
+};
+
+// The track adjoint (wbc_rollout_vjp_tracks): one stage of wbc_trackvjp_kernel behind the link kernel's BEGIN and behind every LINK.
+struct TrackAdjExt {
+  const WbcTracks* in; const WbcTracksGrad* out;   // as the caller gave them: either may be NULL until the sweep's checks are through
+  WbcTracks tj; WbcTracksGrad tg; TrackVjpArgs va;
+  TrackAdjExt(const WbcTracks* tracks, const WbcTracksGrad* tracks_out) : in(tracks), out(tracks_out), tj{}, tg{} { memset(&va, 0, sizeof va); }
+  // what wbc_rollout_vjp_tracks refuses beyond both calls' own refusals, before any launch (og: the sweep's outputs as the caller gave them)
+  int check(const WbcRolloutGrad* og, const char* who) const {
+    if (!out) return fail(WBC_E_ARG, "%s: tracks_out is required", who);
+    if (og && og->d_ee_target_step) return fail(WBC_E_ARG, "%s: d_ee_target_step requested, but a roll-out along tracks has no ee_target_step", who);
+    for (int j = 0; j < WBC_MAX_TRACKS; ++j) {
+      const WbcTrackGrad& g = out->track[j];
+      if (j >= in->n_tracks) {
+        if (g.d_points || g.d_tangents || g.d_du)
+          return fail(WBC_E_ARG, "%s: tracks_out->track[%d] has an output set, but n_tracks = %d", who, j, in->n_tracks);
+        continue;
+      }
+      const WbcTrack& t = in->track[j];
+      if (t.target == WBC_TARGET_TRUNK && og && og->d_trunk_target_step)
+        return fail(WBC_E_ARG, "%s: d_trunk_target_step requested, but track %d moves the trunk target (there is no trunk_target_step)", who, j);
+      if (g.d_tangents && (t.kind != WBC_TRACK_HERMITE || !t.tangents))
+        return fail(WBC_E_ARG, "%s: tracks_out->track[%d].d_tangents requested, but the track is %s", who, j,
+                    t.kind != WBC_TRACK_HERMITE ? "LINEAR" : "HERMITE with tangents == NULL (the default rule: its gradient is part of d_points)");
+    }
+    return WBC_OK;
+  }
+  void stage(Stager& st, size_t n) { tj = *in; tg = *out; stage_tracks(st, tj, n, &tg); }
+  bool wanted() const {   // an output is asked for (a track's cotangent is the tick layer's d_*_target)
+    for (int j = 0; j < tj.n_tracks; ++j) if (tg.track[j].d_points || tg.track[j].d_tangents || tg.track[j].d_du) return true;
+    return false;
+  }
+  int launch(const Sweep& W, int stage, int k) {
+    va.k = k;
+    return launch_rc(launch_trackvjp(va, stage, W.stream, &W.b->last_trackvjp_variant), "roll-out gradient track adjoint");
+  }
+  int begin(const Sweep& W) {
+    va.B = W.B; va.n_tracks = tj.n_tracks; va.Ebar = W.w.Ebar; va.TEbar = W.w.TEbar; va.worst = W.w.worst;
+    va.d_ee_target = W.og.d_ee_target; va.d_trunk_target = W.og.d_trunk_target;
+    for (int j = 0; j < tj.n_tracks; ++j) {
+      TrackVjpTrack& d = va.tr[j];
+      fill_track(d, tj.track[j]);
+      d.d_points = tg.track[j].d_points; d.d_tangents = tg.track[j].d_tangents; d.d_du = tg.track[j].d_du;
+    }
+    return launch(W, TRACKVJP_BEGIN, W.K - 1);
+  }
+  int after_link(const Sweep& W, int k) { return launch(W, TRACKVJP_TICK, k); }
+};
+
+// The score seed (wbc_rollout_vjp_scored): one stage of wbc_scorevjp_kernel in front of every tick's step layer (SEED: g += J' c at q_(k+1),
+// -c into the stash) and one between LINK and the track stage (TARGET).
+struct ScoreSeedExt {
+  const WbcScoreSeed* in;   // as the caller gave it: NULL is the sweep's first refusal
+  WbcScoreSeed ss; ScoreVjpArgs sa;
+  explicit ScoreSeedExt(const WbcScoreSeed* score) : in(score), ss{} { memset(&sa, 0, sizeof sa); }
+  // what wbc_rollout_vjp_scored refuses beyond wbc_rollout_vjp_tracks' refusals, before any launch
+  int check(const WbcTickIn* in0, const WbcRollout* r, const char* who) const {
+    const WbcScoreSeed& sc = *in;
+    if (!sc.g_err_sq_sum && !sc.g_err_final && !sc.g_err_max)
+      return fail(WBC_E_ARG, "%s: a score cotangent is required (g_err_sq_sum, g_err_final or g_err_max)", who);
+    if (sc.g_err_max && !sc.err_max_tick) return fail(WBC_E_ARG, "%s: g_err_max needs err_max_tick (as the record call returned it)", who);
+    if (!sc.q_final) return fail(WBC_E_ARG, "%s: q_final is required (the state after the last tick: the tape ends one state earlier)", who);
+    if (sc.score_mask <= 0 || sc.score_mask >= (1 << WBC_MAX_TRACKS))
+      return fail(WBC_E_ARG, "%s: score_mask = 0x%x, want a bit of the frames 0..%d and none beyond", who, (unsigned)sc.score_mask, WBC_TARGET_TRUNK);
+    if (((sc.score_mask >> WBC_TARGET_TRUNK) & 1) && !in0->trunk_target)
+      return fail(WBC_E_ARG, "%s: score_mask bit %d needs in0->trunk_target", who, WBC_TARGET_TRUNK);
+    if (r->imu) return fail(WBC_E_ARG, "%s: imu must be NULL (with an IMU quaternion fed back the state discards the orientation the scored position was formed with)", who);
+    return WBC_OK;
+  }
+  void stage(Stager& st, size_t n) {
+    ss = *in;
+    const size_t ns = (size_t)__builtin_popcount((unsigned)ss.score_mask) * n;
+    st.in(&ss.g_err_sq_sum, ns); st.in(&ss.g_err_final, ns); st.in(&ss.g_err_max, ns); st.in(&ss.err_max_tick, ns); st.in(&ss.q_final, n * WBC_Q_STRIDE);
+  }
+  int launch(const Sweep& W, int stage, int k) {
+    sa.k = k;
+    // (the statistic names the SEED row, the stage with kinematics and a ROT form; TARGET has one row)
+    return launch_rc(launch_scorevjp(sa, stage, W.stream, stage == SCOREVJP_SEED ? &W.b->last_scorevjp_variant : nullptr), "roll-out gradient score cotangent");
+  }
+  int begin(const Sweep& W) {
+    WbcBatch* b = W.b;
+    sa.models = b->d_models; sa.plans = b->d_plans; sa.model_id = W.first.model_id; sa.B = W.B; sa.n_models = b->n_models; sa.K = W.K; sa.rot = b->rot;
+    sa.score_mask = ss.score_mask; sa.g_sq = ss.g_err_sq_sum; sa.g_fin = ss.g_err_final; sa.g_max = ss.g_err_max; sa.err_max_tick = ss.err_max_tick;
+    sa.g = W.w.g; sa.stash = W.w.stash; sa.worst = W.w.worst; sa.Ebar = W.w.Ebar; sa.TEbar = W.w.TEbar;
+    sa.d_ee_target = W.og.d_ee_target; sa.d_trunk_target = W.og.d_trunk_target;
+    return WBC_OK;
+  }
+  int before_step(const Sweep& W, int k, const TapeWs& T) {   // q_(k+1): the tape's q of tick k + 1, the caller's q_final behind the last tick
+    sa.q = k == W.K - 1 ? ss.q_final : TapeWs::carve(W.tape, W.n, k + 1).q;
+    sa.ee_target = T.ee_target; sa.trunk_target = W.first.trunk_target ? T.trunk_target : nullptr;
+    return launch(W, SCOREVJP_SEED, k);
+  }
+  int after_link(const Sweep& W, int k) { return launch(W, SCOREVJP_TARGET, k); }
+};
+
+static int rollout_vjp_run(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r, const void* tape,
+                           size_t tape_bytes, const WbcRolloutSeed* seed, int mem, const WbcRolloutGrad* out, void* stream, const char* who,
+                           TrackAdjExt* tx = nullptr, ScoreSeedExt* sx = nullptr) {
+  int rc;
+  if (sx && !sx->in) return fail(WBC_E_ARG, "%s: score is required (wbc_rollout_vjp_tracks is the call without one)", who);
+  if (tx && (rc = check_tracks_call(B, in0, r, tx->in, nullptr))) return rc;   // (first: tracks == NULL is refused before a field of it is read)
+  if ((rc = check_record_call(b, B, in0, r, tape, tape_bytes, who))) return rc;
+  if (!out) return fail(WBC_E_ARG, "%s: out is required", who);
+  if (tx && (rc = tx->check(out, who))) return rc;
+  if (!sx && (!seed || !(seed->g_q_final || seed->g_qdot_last || seed->g_q_trace)))
+    return fail(WBC_E_ARG, "%s: a seed is required (g_q_final, g_qdot_last or g_q_trace)", who);
+  if (sx && (rc = sx->check(in0, r, who))) return rc;
+  if ((rc = check_dt(dt, who))) return rc;
+  if (r->mode != WBC_ROLLOUT_RUNNING && r->mode != WBC_ROLLOUT_WARMUP)
+    return fail(WBC_E_ARG, "%s: mode = %d, want WBC_ROLLOUT_RUNNING (%d) or WBC_ROLLOUT_WARMUP (%d)", who, r->mode, WBC_ROLLOUT_RUNNING, WBC_ROLLOUT_WARMUP);
+  if ((rc = validate_tick_in(b, in0, who))) return rc;
+  if (!in0->ee_target || !in0->prev_ee_target) return fail(WBC_E_ARG, "%s: ee_target / prev_ee_target are required (the base estimator reads the foot targets)", who);
+  const Reads rd(b, r->mode == WBC_ROLLOUT_RUNNING);   // the estimator reads ee_target: the step's d_foot_targets reaches it without an EE task
+  if ((rc = check_outs(*out, ROLL_OUT, rd, who, false))) return rc;
+  HIP_TRY(hipSetDevice(b->device_id));
+  // size the workspace: the task rows of wbc_assemble, the unit rows on the padded columns of the handle's smallest model, the constraint rows
+  int min_nv = WBC_V_STRIDE;
+  for (int i = 0; i < b->n_models; ++i) if (b->models[i]->dev.nv < min_nv) min_nv = b->models[i]->dev.nv;
+  const int m = b->mrows, pad_rows = WBC_V_STRIDE - min_nv, M = m + pad_rows, p = rd.p, K = r->ticks;
+  if (M > WBC_MAX_M) return fail(WBC_E_UNSUPPORTED, "%s: %d task rows + %d padding rows exceed the certificate's %d", who, m, pad_rows, WBC_MAX_M);
+  const size_t NB = (size_t)b->max_batch, n = (size_t)B;
+  if ((rc = ensure_size(b->d_rvjp, b->rvjp_bytes, RollVjpWs::bytes(NB, (size_t)M, (size_t)p)))) return rc;   // (after one call of these row counts: no allocation)
+  Sweep W{};
+  W.b = b; W.B = B; W.K = K; W.n = n; W.stream = stream; W.tape = const_cast<void*>(tape);   // (read only: TapeWs carves non-const pointers)
+  const RollVjpWs& w = W.w = RollVjpWs::carve(b->d_rvjp, NB, (size_t)M, (size_t)p);
+  // stage
+  KernelArgs a;
+  fill_args(a, b, B, dt);
+  a.in = *in0;
+  a.in.working_set = nullptr;
+  WbcRolloutSeed sd = seed ? *seed : WbcRolloutSeed{};
+  WbcRolloutGrad& og = W.og = *out;
+  const double* imu = r->imu;
+  Stager st{b, mem, (hipStream_t)stream, {}};
+  stage_tick_in(st, a.in, B, b);
+  st.in(&tp, n); st.in(&imu, n * 4);
+  st.in(&sd.g_q_final, n * WBC_V_STRIDE); st.in(&sd.g_qdot_last, n * WBC_V_STRIDE); st.in(&sd.g_q_trace, (size_t)K * n * WBC_V_STRIDE);
+  if (sx) sx->stage(st, n);
+  stage_outs(st, og, ROLL_OUT, n);
+  st.out(&og.grad_status, n); st.out(&og.ticks_dropped, n);
+  if (tx) tx->stage(st, n);
+  if ((rc = st.stage())) return rc;
+  const WbcTickIn& first = W.first = a.in;
+  const bool have_ws = b->warm_start != 0;   // the tape holds working sets (the option as it was when the tape was recorded: include/wbc.h)
+  const TapeHead head = TapeHead::carve(W.tape, n);
+  // the outputs of the layers, in the workspace. The tick layer runs where an output of the sweep needs one of its (the state side runs on
+  // every tick: g needs it); each of its outputs is wired where the configuration reads what it is the gradient of
+  bool want_tick = false;
+  for (const OutRow<WbcRolloutGrad>& row : ROLL_OUT) want_tick |= og.*row.ptr && row.ptr != &WbcRolloutGrad::d_q0 && row.ptr != &WbcRolloutGrad::d_trunk_box_center;
+  if (tx) want_tick |= tx->wanted();
+  const WbcStepGrad s_out{w.s_dq, w.v, w.s_dft, w.gs_step};
+  const WbcTickStateGrad q_out{w.t_dq, rd.con_trunk ? w.t_box : nullptr, w.gs_tickq};
+  WbcQpCert c_out{};
+  c_out.y_rows = w.y_rows; c_out.sens_x = w.sens_x; c_out.sens_bounds = w.sens_bounds; c_out.sens_rows = w.sens_rows; c_out.cert_status = w.cert_status;
+  RollVjpArgs L;
+  memset(&L, 0, sizeof L);
+  if (want_tick) {
+    L.t.grad_status = w.gs_tick;
+    for (size_t i = 0; i < sizeof(TICK_WS) / sizeof(TICK_WS[0]); ++i)
+      if (rd(TICK_OUT[i].need)) L.t.*TICK_WS[i].out = w.*TICK_WS[i].ws;
+  }
+  L.models = b->d_models; L.model_id = first.model_id; L.B = B; L.n_models = b->n_models; L.K = K; L.m = m; L.pad_rows = pad_rows;
+  L.ee_on = rd.ee_on; L.trunk_on = rd.trunk;
+  L.g_q_final = sd.g_q_final; L.g_qdot_last = sd.g_qdot_last; L.g_q_trace = sd.g_q_trace;
+  L.A = w.A; L.b = w.b; L.g = w.g; L.v = w.v;
+  L.s_dq = s_out.d_q; L.s_dft = rd.est ? s_out.d_foot_targets : nullptr; L.t_dq = q_out.d_q; L.t_box = q_out.d_trunk_box_center;
+  L.gs_step = w.gs_step; L.gs_tickq = w.gs_tickq;
+  L.Ebar = w.Ebar; L.Pbar = w.Pbar; L.TEbar = w.TEbar; L.TPbar = w.TPbar; L.d_estep = w.d_estep; L.d_tstep = w.d_tstep; L.acc_tp = w.acc_tp;
+  L.acc_com = w.acc_com; L.acc_comv = w.acc_comv; L.acc_pu = w.acc_pu; L.acc_box = w.acc_box; L.worst = w.worst; L.dropped = w.dropped;
+  L.out = og;
+  auto link = [&](int stage, int k) {   // (the launch chain is linear: every stage waits for the one before it on the stream)
+    L.k = k;
+    return launch_rc(launch_rollvjp(L, stage, stream, &b->last_rollvjp_variant), "roll-out gradient link");
+  };
+  if ((rc = link(ROLLVJP_BEGIN, K - 1))) return rc;
+  if ((tx && (rc = tx->begin(W))) || (sx && (rc = sx->begin(W)))) return rc;
+  for (int k = K - 1; k >= 0; --k) {
+    const TapeWs T = TapeWs::carve(W.tape, n, k);
+    WbcTickIn in = first;   // the inputs tick k saw
+    in.q = T.q; in.ee_target = T.ee_target; in.prev_ee_target = T.prev_ee_target;
+    if (first.trunk_target) in.trunk_target = T.trunk_target;
+    if (first.prev_trunk_target) in.prev_trunk_target = T.prev_trunk_target;
+    if (k > 0 && first.ee_prev_rot) in.ee_prev_rot = head.ee_prev_rot;
+    if (k > 0 && first.trunk_prev_rot) in.trunk_prev_rot = head.trunk_prev_rot;
+    if (sx && (rc = sx->before_step(W, k, T))) return rc;
+    // the step: g -> d_q, v = d_qdot, d_foot_targets; on the last tick v += g_qdot_last
+    if ((rc = step_layer(b, B, dt, r->mode, T.q, T.qdot, T.ee_target, imu, first.model_id, w.g, s_out, stream))) return rc;
+    if (k == K - 1 && sd.g_qdot_last && (rc = link(ROLLVJP_ADDV, K - 1))) return rc;
+    // the tick's problem at the taped inputs. mrows = M is the stride of A: the padding rows stay where BEGIN wrote them
+    a.in = in;
+    a.mrows = M;
+    a.qp = WbcQpData{};
+    a.qp.A = w.A; a.qp.b = w.b; a.qp.lb = w.lb; a.qp.ub = w.ub;
+    if (p > 0) { a.qp.C = w.C; a.qp.Clb = w.Clb; a.qp.Cub = w.Cub; }
+    if ((rc = auto_posture(b, a, B, stream))) return rc;
+    if ((rc = launch_rc(launch_tick(a, MODE_ASSEMBLE, grid_tick(b, B), stream, tp, &b->last_tick_variant), "assemble"))) return rc;
+    // its certificate with v. The working set reaches the certificate and the tick-state layer under warm_start alone: only then the tape holds it
+    WbcQpProblem qp{};
+    qp.n = WBC_V_STRIDE; qp.p = p; qp.m = M;
+    qp.A = w.A; qp.b = w.b; qp.C = w.C; qp.lb = w.lb; qp.ub = w.ub; qp.Clb = w.Clb; qp.Cub = w.Cub;
+    qp.x = T.qdot; qp.v = w.v; qp.status = T.status; qp.working_set = have_ws ? (const uint64_t*)T.working_set : nullptr;
+    if ((rc = cert_layer(b, B, qp, c_out, stream))) return rc;
+    // the tick's two layers: the first is skipped when none of its outputs is asked for
+    if (want_tick && (rc = tick_layer(b, B, dt, a.in, tp, T.qdot, w.sens_x, T.status, w.cert_status, L.t, stream))) return rc;
+    WbcTickSens sn{};
+    sn.qdot = T.qdot; sn.sens_x = w.sens_x; sn.sens_bounds = w.sens_bounds; sn.sens_rows = w.sens_rows; sn.y_rows = w.y_rows;
+    sn.status = T.status; sn.cert_status = w.cert_status; sn.working_set = qp.working_set;
+    if ((rc = tickq_layer(b, B, dt, in, tp, sn, q_out, stream))) return rc;
+    if ((rc = link(ROLLVJP_LINK, k))) return rc;
+    if ((sx && (rc = sx->after_link(W, k))) || (tx && (rc = tx->after_link(W, k)))) return rc;
+  }
+  return st.finish();
+}
+extern "C" int wbc_rollout_vjp(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r, const void* tape,
+                               size_t tape_bytes, const WbcRolloutSeed* seed, int mem, const WbcRolloutGrad* out, void* stream) {
+  return rollout_vjp_run(b, B, in0, tp, dt, r, tape, tape_bytes, seed, mem, out, stream, "wbc_rollout_vjp");
+}
+extern "C" int wbc_rollout_grad_sizes(int32_t* sizeof_seed, int32_t* sizeof_grad) {
+  if (sizeof_seed) *sizeof_seed = (int32_t)sizeof(WbcRolloutSeed);
+  if (sizeof_grad) *sizeof_grad = (int32_t)sizeof(WbcRolloutGrad);
+  return WBC_OK;
+}
+
+// The roll-out along per-instance milestone trajectories (WbcTrajectory), scored on the device (WbcRolloutSummary): argument checks, then
+// the shared loop on the one-track call: a LINEAR track of end effector ee_index, the gripper scored.
+extern "C" int wbc_rollout_traj(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
+                                const WbcTrajectory* traj, const WbcRolloutSummary* sum, int mem, void* stream) {
+  if (!r || !traj) return fail(WBC_E_ARG, "wbc_rollout_traj: r and traj are required");
+  if (r->ee_target_step) return fail(WBC_E_ARG, "wbc_rollout_traj: ee_target_step must be NULL (the trajectory moves the followed target; the other EE targets are constant)");
+  if (r->hold_ticks != 0) return fail(WBC_E_ARG, "wbc_rollout_traj: hold_ticks must be 0 (a trajectory holds its last milestone by itself)");
+  if (traj->ee_index < 0 || traj->ee_index >= WBC_NEE) return fail(WBC_E_ARG, "wbc_rollout_traj: ee_index = %d outside [0, %d]", traj->ee_index, WBC_NEE - 1);
+  WbcTracks tk{};
+  WbcTrackScores sc{};
+  WbcTrack& t = tk.track[0];
+  tk.n_tracks = 1; sc.score_mask = 1 << 4;
+  t.target = traj->ee_index; t.kind = WBC_TRACK_LINEAR; t.max_points = traj->max_points;
+  t.points = traj->points; t.n_points = traj->n_points; t.du = traj->du; t.du_all = traj->du_all;
+  int rc;
+  if ((rc = check_track(t, "wbc_rollout_traj", "")) || (sum && (rc = check_group_size("wbc_rollout_traj", sum->group_size, B)))) return rc;
+  if (sum) {
+    sc.group_size = sum->group_size;
+    sc.err_sq_sum = sum->err_sq_sum; sc.err_max = sum->err_max; sc.err_final = sum->err_final; sc.err_max_tick = sum->err_max_tick;
+    sc.first_bad_tick = sum->first_bad_tick; sc.bad_ticks = sum->bad_ticks;
+    sc.group_rms = sum->group_rms; sc.group_err_max = sum->group_err_max;
+    sc.group_worst_status = sum->group_worst_status; sc.group_bad_instances = sum->group_bad_instances;
+  }
+  TracksExt ext(tk, sum ? &sc : nullptr, true);
+  return rollout_run(b, B, in0, tp, dt, r, mem, stream, &ext);
+}
+
 extern "C" int wbc_rollout_tracks(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
                                   const WbcTracks* tracks, const WbcTrackScores* scores, int mem, void* stream) {
   if (int rc = check_tracks_call(B, in0, r, tracks, scores)) return rc;
@@ -2159,12 +2186,15 @@ extern "C" int wbc_rollout_record_tracks(WbcBatch* b, int B, const WbcTickIn* in
 extern "C" int wbc_rollout_vjp_tracks(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
                                       const WbcTracks* tracks, const void* tape, size_t tape_bytes, const WbcRolloutSeed* seed, int mem,
                                       const WbcRolloutGrad* out, const WbcTracksGrad* tracks_out, void* stream) {
-  return rollout_vjp_run(b, B, in0, tp, dt, r, tape, tape_bytes, seed, mem, out, stream, "wbc_rollout_vjp_tracks", true, tracks, tracks_out);
+  TrackAdjExt tx(tracks, tracks_out);
+  return rollout_vjp_run(b, B, in0, tp, dt, r, tape, tape_bytes, seed, mem, out, stream, "wbc_rollout_vjp_tracks", &tx);
 }
 extern "C" int wbc_rollout_vjp_scored(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
                                       const WbcTracks* tracks, const void* tape, size_t tape_bytes, const WbcRolloutSeed* seed,
                                       const WbcScoreSeed* score, int mem, const WbcRolloutGrad* out, const WbcTracksGrad* tracks_out, void* stream) {
-  return rollout_vjp_run(b, B, in0, tp, dt, r, tape, tape_bytes, seed, mem, out, stream, "wbc_rollout_vjp_scored", true, tracks, tracks_out, true, score);
+  TrackAdjExt tx(tracks, tracks_out);
+  ScoreSeedExt sx(score);
+  return rollout_vjp_run(b, B, in0, tp, dt, r, tape, tape_bytes, seed, mem, out, stream, "wbc_rollout_vjp_scored", &tx, &sx);
 }
 static_assert(sizeof(WbcScoreSeed) == 8 + 5 * sizeof(void*), "wbc_capi.WbcScoreSeed");
 extern "C" int wbc_rollout_scored_sizes(int32_t* sizeof_score_seed) {

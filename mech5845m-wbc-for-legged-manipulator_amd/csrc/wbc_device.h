@@ -1,5 +1,6 @@
 // wbc_device.h — host-visible description of what the gfx950 kernels consume (internal, C++).
 #pragma once
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 #include "../../include/wbc.h"
@@ -9,6 +10,9 @@ namespace wbc {
 constexpr int NV = WBC_V_STRIDE;   // 26: QP size, lanes 0..25 of the wavefront carry one DoF each
 constexpr int NQ = WBC_Q_STRIDE;   // 27
 constexpr int NL = 32;             // per-lane model tables are padded to 32 entries
+
+// the finite test of every kernel that refuses non-finite inputs: false for NaN and +-inf
+__device__ __forceinline__ bool is_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }
 
 // One kinematic model, flattened for "lane j = joint j" and "lane k = velocity column k" access.
 // Built by wbc_model_create from WbcModelBlob; lives in device global memory (tiny, L2 resident).

@@ -32,7 +32,6 @@ static_assert(sizeof(CertSmem) <= sizeof(Smem), "the certificate kernel's LDS fo
 static_assert(offsetof(CertSmem, Cm) == offsetof(CertSmem, Yt) + sizeof(double) * CERT_COLS * LDJ, "Yt and Cm are one staging area");
 static_assert((CERT_COLS + PMAX) * LDJ >= NV * CERT_MT, "A by DoF fits Yt + Cm");
 
-__device__ __forceinline__ bool cert_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }   // false for NaN and +-inf
 __device__ __forceinline__ bool cert_bounded(double x) { return fabs(x) < QP_INF; }                    // a bound the problem really has
 // sum / max over all 64 lanes, wave-uniform result: butterfly inside each 16-lane row, the four rows joined by readlane
 __device__ __forceinline__ double cert_sum(double v) {
@@ -75,7 +74,7 @@ __global__ void __launch_bounds__(64, 2) wbc_qp_cert_kernel(const CertArgs A) {
       double lo = -1e30, hi = 1e30, clo = 0.0, chi = 0.0;
       if (A.lb && isv) { lo = A.lb[bn + lane]; hi = A.ub[bn + lane]; }
       if (isr) { clo = A.Clb[bp + lane]; chi = A.Cub[bp + lane]; }
-      bool bad = !cert_finite(xk) || !cert_finite(vk) || lo != lo || hi != hi || clo != clo || chi != chi;   // (an infinite bound is no bound)
+      bool bad = !is_finite(xk) || !is_finite(vk) || lo != lo || hi != hi || clo != clo || chi != chi;   // (an infinite bound is no bound)
       double gk = 0.0, grad = 0.0;
       if (lane < 32) S.xv[lane] = isv ? xk : 0.0;
       if (m > 0) {
@@ -93,12 +92,12 @@ __global__ void __launch_bounds__(64, 2) wbc_qp_cert_kernel(const CertArgs A) {
           for (int idx = lane; idx < mc * n; idx += 64) {
             const int r = idx / n, c = idx - r * n;
             const double a = Ac[idx];
-            bad |= !cert_finite(a);
+            bad |= !is_finite(a);
             At[c * CERT_MT + r] = a;
           }
           if (isv && mc2 > mc) At[lane * CERT_MT + mc] = 0.0;       // (the products below go two rows at a time)
           const double br = (lane < mc) ? bb[r0 + lane] : 0.0;
-          bad |= !cert_finite(br);
+          bad |= !is_finite(br);
           WSYNC();
           if (lane < mc) {
             double ax = 0.0;
@@ -132,18 +131,18 @@ __global__ void __launch_bounds__(64, 2) wbc_qp_cert_kernel(const CertArgs A) {
         for (int idx = lane; idx < n * n; idx += 64) {
           const int r = idx / n, c = idx - r * n;
           const double h = Hb[idx];
-          bad |= !cert_finite(h);
+          bad |= !is_finite(h);
           S.Hm[r * LDJ + c] = h;
         }
         gk = isv ? A.g[bn + lane] : 0.0;
-        bad |= !cert_finite(gk);
+        bad |= !is_finite(gk);
       }
       {
         const double* Cb = A.C + bp * n;
         for (int idx = lane; idx < p * n; idx += 64) {
           const int r = idx / n, c = idx - r * n;
           const double cv = Cb[idx];
-          bad |= !cert_finite(cv);
+          bad |= !is_finite(cv);
           S.Cm[r * LDJ + c] = cv;
         }
       }
@@ -189,7 +188,7 @@ __global__ void __launch_bounds__(64, 2) wbc_qp_cert_kernel(const CertArgs A) {
           for (int t = 0; t < j; ++t) s = fma(-S.Hm[lane * LDJ + t], S.Hm[j * LDJ + t], s);
         }
         const double d = rdl(s, j);
-        if (!(d > 0.0) || !cert_finite(d)) { chol_bad = true; break; }
+        if (!(d > 0.0) || !is_finite(d)) { chol_bad = true; break; }
         const double sq = sqrt(d);
         if (isv && lane >= j) S.Hm[lane * LDJ + j] = (lane == j) ? sq : s / sq;
         WSYNC();

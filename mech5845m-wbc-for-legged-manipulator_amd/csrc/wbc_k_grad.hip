@@ -38,8 +38,6 @@ struct __attribute__((aligned(16))) GInst {
 };
 struct __attribute__((aligned(16))) GSmemP { GInst I[4]; };
 
-__device__ __forceinline__ bool grad_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }   // false for NaN and +-inf
-
 // Entry k of the staged inputs; an input the configuration does not read is 0 and is never loaded
 __device__ __forceinline__ double grad_input(const WbcTickIn& in, const size_t b, const int k, const unsigned eemask, const bool trunk, const bool com,
                                              const bool pu) {
@@ -95,8 +93,8 @@ __global__ void __launch_bounds__(64) wbc_grad_kernel(const GradArgs A, const De
   const int j1 = 16 + s;                                            // bodies of this lane: joints s (>= 1) and 16 + s
   const bool hb0 = s >= 1 && s < nj, hb1 = j1 < nj;
   const DevPlan::QJnt m0 = P.q_jm[hb0 ? s : 1], m1 = P.q_jm[hb1 ? j1 : 1];
-  bool bad = (s < nq && !grad_finite(q0)) || (16 + s < nq && !grad_finite(q1)) || !grad_finite(xd0) || !grad_finite(xd1) || !grad_finite(ud0) ||
-             !grad_finite(ud1);
+  bool bad = (s < nq && !is_finite(q0)) || (16 + s < nq && !is_finite(q1)) || !is_finite(xd0) || !is_finite(xd1) || !is_finite(ud0) ||
+             !is_finite(ud1);
   {
     const double* cw = &cfg.ee_W[0][0];
     const double* rw = A.tp ? reinterpret_cast<const double*>(A.tp + b) : cw;
@@ -104,7 +102,7 @@ __global__ void __launch_bounds__(64) wbc_grad_kernel(const GradArgs A, const De
     for (int i = 0; i < 6; ++i) {
       const int k = s + 16 * i;
       const double v = (k < WBC_TASK_PARAMS_DOUBLES) ? rw[k] : 0.0;
-      bad = bad || !grad_finite(v);
+      bad = bad || !is_finite(v);
       U.wt[k] = v;
       U.gout[k] = 0.0;
     }
@@ -112,11 +110,11 @@ __global__ void __launch_bounds__(64) wbc_grad_kernel(const GradArgs A, const De
     for (int i = 0; i < 5; ++i) {
       const int k = s + 16 * i;
       const double v = grad_input(A.in, b, k, eemask, t_trunk, t_com, pu_read);
-      bad = bad || !grad_finite(v);
+      bad = bad || !is_finite(v);
       U.tin[k] = v;
     }
     const double om = (eemask >> ((s < 15 ? s : 0) / 3) & 1u) ? pk_ee_omega(A.in, (int)b, s, inv_dt) : 0.0;   // calcTargetVelEE3's feed-forward, one component per lane
-    bad = bad || !grad_finite(om);
+    bad = bad || !is_finite(om);
     U.tin[GI_OM + s] = om;
 #pragma unroll
     for (int i = 0; i < 3; ++i) U.tout[s + 16 * i] = 0.0;
@@ -305,11 +303,11 @@ __global__ void __launch_bounds__(64) wbc_grad_kernel(const GradArgs A, const De
   WSYNC();
   // ---- out: zero rows for an unsolved / uncertified / non-finite instance; nothing non-finite leaves the instance
   double go[6], to[3];
-  bool obad = !grad_finite(pu0) || !grad_finite(pu1);
+  bool obad = !is_finite(pu0) || !is_finite(pu1);
 #pragma unroll
-  for (int i = 0; i < 6; ++i) { go[i] = U.gout[s + 16 * i]; obad = obad || !grad_finite(go[i]); }
+  for (int i = 0; i < 6; ++i) { go[i] = U.gout[s + 16 * i]; obad = obad || !is_finite(go[i]); }
 #pragma unroll
-  for (int i = 0; i < 3; ++i) { to[i] = U.tout[s + 16 * i]; obad = obad || !grad_finite(to[i]); }
+  for (int i = 0; i < 3; ++i) { to[i] = U.tout[s + 16 * i]; obad = obad || !is_finite(to[i]); }
   const bool nonfin = ((__ballot(bad || obad) >> rbase) & 0xFFFFull) != 0ull;
   const int gs = st != 0 ? GRAD_UNSOLVED : (cst != 0 ? GRAD_CERT : (nonfin ? GRAD_NONFINITE : GRAD_OK));
   if (!valid) return;

@@ -39,8 +39,6 @@ struct __attribute__((aligned(16))) QInst {
 };
 struct __attribute__((aligned(16))) QSmemP { QInst I[4]; };
 
-__device__ __forceinline__ bool gq_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }   // false for NaN and +-inf
-
 // Entry k of the staged inputs; an input the configuration does not read is 0 and is never loaded
 __device__ __forceinline__ double gq_input(const WbcTickIn& in, const size_t b, const int k, const unsigned eemask, const bool trunk, const bool com) {
   if (k < QI_TR) {
@@ -201,8 +199,8 @@ __global__ void __launch_bounds__(64) wbc_gradq_kernel(const GradQArgs A, const 
 #pragma unroll
     for (int i = 0; i < 4; ++i) bc[i] = A.in.trunk_box_center[b * 4 + i];
   }
-  bool bad = (s < nq && !gq_finite(q0)) || (16 + s < nq && !gq_finite(q1)) || !gq_finite(xd0) || !gq_finite(xd1) || !gq_finite(ud0) ||
-             !gq_finite(ud1) || !gq_finite(wb0) || !gq_finite(wb1) || !gq_finite(bc[0]) || !gq_finite(bc[1]) || !gq_finite(bc[2]) || !gq_finite(bc[3]);
+  bool bad = (s < nq && !is_finite(q0)) || (16 + s < nq && !is_finite(q1)) || !is_finite(xd0) || !is_finite(xd1) || !is_finite(ud0) ||
+             !is_finite(ud1) || !is_finite(wb0) || !is_finite(wb1) || !is_finite(bc[0]) || !is_finite(bc[1]) || !is_finite(bc[2]) || !is_finite(bc[3]);
   {
     const double* cw = &cfg.ee_W[0][0];
     const double* rw = A.tp ? reinterpret_cast<const double*>(A.tp + b) : cw;
@@ -210,24 +208,24 @@ __global__ void __launch_bounds__(64) wbc_gradq_kernel(const GradQArgs A, const 
     for (int i = 0; i < 6; ++i) {
       const int k = s + 16 * i;
       const double v = (k < WBC_TASK_PARAMS_DOUBLES) ? rw[k] : 0.0;
-      bad = bad || !gq_finite(v);
+      bad = bad || !is_finite(v);
       U.wt[k] = v;
     }
 #pragma unroll
     for (int i = 0; i < 5; ++i) {
       const int k = s + 16 * i;
       const double v = gq_input(A.in, b, k, eemask, t_trunk, t_com);
-      bad = bad || !gq_finite(v);
+      bad = bad || !is_finite(v);
       U.tin[k] = v;
     }
     const double om = (eemask >> ((s < 15 ? s : 0) / 3) & 1u) ? pk_ee_omega(A.in, (int)b, s, inv_dt) : 0.0;   // calcTargetVelEE3's feed-forward, one component per lane
-    bad = bad || !gq_finite(om);
+    bad = bad || !is_finite(om);
     U.tin[QI_OM + s] = om;
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
       const int k = s + 16 * i, kk = (k < 24) ? k : k - 24;
       const double v = (kk < p) ? ((k < 24) ? A.sens.sens_rows[b * p + kk] : A.sens.y_rows[b * p + kk]) : 0.0;
-      bad = bad || !gq_finite(v);
+      bad = bad || !is_finite(v);
       U.wy[k] = v;
     }
 #pragma unroll
@@ -564,7 +562,7 @@ __global__ void __launch_bounds__(64) wbc_gradq_kernel(const GradQArgs A, const 
     if (h1) res1 += cr[cq1];
   }
   // ---- out: zero rows for an unsolved / uncertified / non-finite instance; nothing non-finite leaves the instance
-  const bool obad = !gq_finite(res0) || !gq_finite(res1) || !gq_finite(tbc);
+  const bool obad = !is_finite(res0) || !is_finite(res1) || !is_finite(tbc);
   const bool nonfin = ((__ballot(bad || obad) >> rbase) & 0xFFFFull) != 0ull;
   const int gs = st != 0 ? GRAD_UNSOLVED : (cst != 0 ? GRAD_CERT : (nonfin ? GRAD_NONFINITE : GRAD_OK));
   if (!valid) return;

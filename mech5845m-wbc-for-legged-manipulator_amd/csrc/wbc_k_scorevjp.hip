@@ -33,8 +33,6 @@ struct __attribute__((aligned(16))) VInst {
 };
 struct __attribute__((aligned(16))) VSmemP { VInst I[4]; };
 
-__device__ __forceinline__ bool sv_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }   // false for NaN and +-inf
-
 // this DoF's term: sum over the scored frames the column moves of (lin + ang x p_f) . c_f, the frames in increasing order
 __device__ __forceinline__ double sv_contract(const double* const pf, const double* const c, const DevModel& M, const int mask, const int d,
                                               const double (&lin)[3], const double (&ang)[3]) {
@@ -108,8 +106,8 @@ __global__ void __launch_bounds__(64) wbc_scorevjp_kernel(const ScoreVjpArgs A) 
   const bool h0 = d0 < nv, h1 = d1 < nv;
   const int cj0 = M.col_joint[h0 ? d0 : 0], cl0 = M.col_lin[h0 ? d0 : 0], ca0 = M.col_ang[h0 ? d0 : 0];
   const int cj1 = M.col_joint[h1 ? d1 : 0], cl1 = M.col_lin[h1 ? d1 : 0], ca1 = M.col_ang[h1 ? d1 : 0];
-  const bool bad = lastk && ((s < nq && !sv_finite(q0)) || (16 + s < nq && !sv_finite(q1)) || !sv_finite(gsq) || !sv_finite(gfin) ||
-                             !sv_finite(gmax) || (gmax != 0.0 && (tk < 0 || tk >= A.K)));
+  const bool bad = lastk && ((s < nq && !is_finite(q0)) || (16 + s < nq && !is_finite(q1)) || !is_finite(gsq) || !is_finite(gfin) ||
+                             !is_finite(gmax) || (gmax != 0.0 && (tk < 0 || tk >= A.K)));
   const bool rowbad = ((__ballot(bad) >> rbase) & 0xFFFFull) != 0ull;
   const bool dead = rowbad || A.worst[b] == GRAD_NONFINITE;
   U.q[s] = q0; U.q[16 + s] = q1;

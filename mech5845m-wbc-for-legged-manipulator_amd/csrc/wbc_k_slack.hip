@@ -27,7 +27,6 @@ struct __attribute__((aligned(16))) SInst {
 };
 struct __attribute__((aligned(16))) SSmemP { SInst I[4]; };
 
-__device__ __forceinline__ bool slack_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }   // false for NaN and +-inf
 // (v, c) <- the smaller of (v, c) and (ov, oc): by value, a tie by the lower code — what a scan in increasing code order with a strict < gives
 __device__ __forceinline__ void slack_take(double& v, int& c, const double ov, const int oc) {
   if (ov < v || (ov == v && oc < c)) { v = ov; c = oc; }
@@ -86,7 +85,7 @@ __global__ void __launch_bounds__(64) wbc_slack_kernel(const SlackArgs A, const 
   const int qi0 = Lm.qi[hd0 ? s : 6], qi1 = Lm.qi[hd1 ? j1 : 6];
   const double lo0 = Lm.lo[hd0 ? s : 6], hi0 = Lm.hi[hd0 ? s : 6], lo1 = Lm.lo[hd1 ? j1 : 6], hi1 = Lm.hi[hd1 ? j1 : 6];
   const double z_frac = cfg.trunk_box_z_frac, box_ang = cfg.trunk_box_ang;
-  const bool qbad = (s < nq && !slack_finite(q0)) || (16 + s < nq && !slack_finite(q1));
+  const bool qbad = (s < nq && !is_finite(q0)) || (16 + s < nq && !is_finite(q1));
   const bool rowbad = ((__ballot(qbad) >> rbase) & 0xFFFFull) != 0ull;
   U.q[s] = q0; U.q[16 + s] = q1;
   WSYNC();
@@ -153,8 +152,8 @@ __global__ void __launch_bounds__(64) wbc_slack_kernel(const SlackArgs A, const 
   slack_scan<2>(comp + 4, sl[1], wh[1]);
   slack_scan<6>(comp + 6, sl[2], wh[2]);
   sl[3] = jv; wh[3] = jc;
-  const bool bad1 = rowbad || !slack_finite(bc[0]);
-  const bool bad2 = rowbad || !slack_finite(bc[1]) || !slack_finite(bc[2]) || !slack_finite(bc[3]);
+  const bool bad1 = rowbad || !is_finite(bc[0]);
+  const bool bad2 = rowbad || !is_finite(bc[1]) || !is_finite(bc[2]) || !is_finite(bc[3]);
   if (rowbad) { sl[0] = qnan; wh[0] = -1; sl[3] = qnan; wh[3] = -1; }
   if (bad1) { sl[1] = qnan; wh[1] = -1; }
   if (bad2) { sl[2] = qnan; wh[2] = -1; }

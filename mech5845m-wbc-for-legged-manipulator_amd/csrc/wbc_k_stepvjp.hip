@@ -33,8 +33,6 @@ struct __attribute__((aligned(16))) VInst {
 };
 struct __attribute__((aligned(16))) VSmemP { VInst I[4]; };
 
-__device__ __forceinline__ bool sv_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }   // false for NaN and +-inf
-
 // sum_k (-t2)^k c_k with c_0 = 1 and c_k / c_(k-1) = NUM(k) / ((2 k + OFF - 1) (2 k + OFF)), nested from k = N down: every partial sum is
 // within [1 - t2 / 6, 1], so nothing cancels
 template <int OFF, bool C3, int N>
@@ -137,8 +135,8 @@ __global__ void __launch_bounds__(64) wbc_stepvjp_kernel(const StepVjpArgs A, co
   const int fr = (s < 4) ? WBC_FR_EE0 + s : WBC_FR_TRUNK;           // frame of this lane: feet 0..3, trunk
   const int fjoint = M.frame_joint[fr];
   const double f0 = M.frame_p[fr][0], f1 = M.frame_p[fr][1], f2 = M.frame_p[fr][2];
-  const bool bad = (s < nq && !sv_finite(q0)) || (16 + s < nq && !sv_finite(q1)) || !sv_finite(xd0) || !sv_finite(xd1) || !sv_finite(gd0) ||
-                   !sv_finite(gd1) || !sv_finite(ft) || !sv_finite(im);
+  const bool bad = (s < nq && !is_finite(q0)) || (16 + s < nq && !is_finite(q1)) || !is_finite(xd0) || !is_finite(xd1) || !is_finite(gd0) ||
+                   !is_finite(gd1) || !is_finite(ft) || !is_finite(im);
   U.qc[s] = q0; U.qc[16 + s] = q1;
   U.q[s] = 0.0; U.q[16 + s] = 0.0;
   if (s < 6) { U.xi[s] = dt * xd0; U.g6[s] = gd0; }
@@ -240,7 +238,7 @@ __global__ void __launch_bounds__(64) wbc_stepvjp_kernel(const StepVjpArgs A, co
   const int fe = s / 3, fi = s - 3 * fe;
   const double rf = (running && fe < 4) ? ((fi == 0) ? Rg[0] : (fi == 1) ? Rg[1] : Rg[2]) / 4 : 0.0;
   // ---- out: zero rows for a non-finite instance; nothing non-finite leaves the instance
-  const bool obad = (h0 && (!sv_finite(rq0) || !sv_finite(rx0))) || (h1 && (!sv_finite(rq1) || !sv_finite(rx1))) || !sv_finite(rf);
+  const bool obad = (h0 && (!is_finite(rq0) || !is_finite(rx0))) || (h1 && (!is_finite(rq1) || !is_finite(rx1))) || !is_finite(rf);
   const bool zero = ((__ballot(bad || obad) >> rbase) & 0xFFFFull) != 0ull;
   if (!valid) return;
   if (A.out.d_q) {

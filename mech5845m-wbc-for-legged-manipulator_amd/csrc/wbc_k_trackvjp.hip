@@ -2,14 +2,15 @@
 // the algebra). The sweep is wbc_rollout_vjp's, kernel for kernel; behind the link kernel's BEGIN and behind every LINK it launches one stage of
 //   wbc_trackvjp_kernel    four instances per wavefront (lane = 16 r + s), one lane per (instance, track, component): s = 3 j + c for the
 //                          tracks j = 0..4 in a first pass, s = c for track 5 in a second
-//     BEGIN  the bad-row test of wbc_traj_begin_kernel (lane s == 0): a bad row's worst[b] <- WBC_GRAD_NONFINITE, so the unchanged LINK zeroes
-//            that instance's outputs at k == 0; the track outputs <- 0
+//     BEGIN  the bad-row test wbc_traj_begin_kernel runs (wbc_track.h's; lane s == 0): a bad row's worst[b] <- WBC_GRAD_NONFINITE, so the
+//            unchanged LINK zeroes that instance's outputs at k == 0; the track outputs <- 0
 //     TICK   e <- the followed row of Ebar / TEbar (LINK has just made it e_k = a_k + on o Pbar), that row <- 0 (nothing is carried: the
 //            target of every tick comes from the track); the adjoint of eval_b(k * du_b) applied to e; at k == 0 the followed rows of the
 //            caller's d_ee_target / d_trunk_target <- 0 and all-zero track outputs for an instance with WBC_GRAD_NONFINITE
 // The accumulators are the outputs themselves. Every d_points / d_tangents entry belongs to one lane, which adds to it in reverse tick order;
 // d_du's three components meet in the lane of component 0 as (x + y) + z. No atomics, no LDS; the forward's comparisons select the branch
-// and nothing is contracted into fused multiply-adds, so the host restatement (wbc_workload.track_target_gradients) runs the same operations.
+// (wbc_track.h: one bad-row test, one default-tangent rule, one segment lookup and one Hermite basis for both kernels) and nothing is
+// contracted into fused multiply-adds, so the host restatement (wbc_workload.track_target_gradients) runs the same operations.
 // Rows >= B are never written.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -21,35 +22,14 @@
 
 namespace wbc {
 
-// (restated from wbc_k_traj.hip, whose unit stays as it is)
-__device__ __forceinline__ bool tv_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }   // false for NaN and +-inf
-
-// the branch traj_tangent takes for component c at interior milestone i (n >= 3, 0 < i < n - 1): 1..4 as include/wbc.h numbers them
-__device__ __forceinline__ int tv_case(double a, double x, double b) {
-  const double w = (b - a) * 0.5, third = 1.0 / 3.0;
-  if (x <= fmin(a, b) || x >= fmax(a, b)) return 1;
-  if ((w < 0.0 && x - w * third >= a) || (w > 0.0 && x - w * third <= a)) return 2;
-  if ((w < 0.0 && x + w * third < b) || (w > 0.0 && x + w * third > b)) return 3;
-  return 4;
-}
-// the default tangent of component c at milestone i; m: the instance's milestones at component c, stride 3
-__device__ __forceinline__ double tv_tangent(const double* __restrict__ m, int n, int i) {
-  if (n == 2) return m[3] - m[0];
-  if (i == 0 || i == n - 1) return 0.0;
-  const double a = m[3 * (i - 1)], x = m[3 * i], b = m[3 * (i + 1)];
-  switch (tv_case(a, x, b)) {
-    case 1: return 0.0;
-    case 2: return 3.0 * (x - a);
-    case 3: return 3.0 * (b - x);
-    default: return (b - a) * 0.5;
-  }
-}
-// its adjoint: vb, the cotangent of that tangent, into d (the instance's d_points at component c, stride 3): the plus term first
+// the adjoint of wbc_track.h's default tangent at milestone i: vb, the cotangent of that tangent, into d (the instance's d_points at this
+// component, stride 3) through the branch tangent_case takes: the plus term first
 __device__ __forceinline__ void tv_tangent_adj(const double* __restrict__ m, double* __restrict__ d, int n, int i, double vb) {
   if (n == 2) { d[3] = d[3] + vb; d[0] = d[0] - vb; return; }
   if (i == 0 || i == n - 1) return;
   const double a = m[3 * (i - 1)], x = m[3 * i], b = m[3 * (i + 1)];
-  switch (tv_case(a, x, b)) {
+  double w;
+  switch (tangent_case(a, x, b, w)) {
     case 1: return;
     case 2: d[3 * i] = d[3 * i] + 3.0 * vb; d[3 * (i - 1)] = d[3 * (i - 1)] - 3.0 * vb; return;
     case 3: d[3 * (i + 1)] = d[3 * (i + 1)] + 3.0 * vb; d[3 * i] = d[3 * i] - 3.0 * vb; return;
@@ -66,23 +46,7 @@ __global__ void __launch_bounds__(64) wbc_trackvjp_kernel(const TrackVjpArgs A) 
   if (STAGE == TRACKVJP_BEGIN && s == 0) {                          // wbc_traj_begin_kernel's test, one lane per instance
     bool bad = false;
 #pragma unroll 1
-    for (int j = 0; j < A.n_tracks; ++j) {
-      const TrackVjpTrack& T = A.tr[j];
-      const int n = T.n_points ? T.n_points[b] : T.S;
-      const double du = T.du ? T.du[b] : T.du_all;
-      const bool bad_n = n < 2 || n > T.S;
-      bad |= bad_n || !tv_finite(du) || !(du > 0.0);
-      if (!bad_n) {
-        const double* m = T.points + b * T.S * 3;
-#pragma unroll 1
-        for (int i = 0; i < 3 * n; ++i) bad |= !tv_finite(m[i]);
-        if (T.tangents) {
-          const double* v = T.tangents + b * T.S * 3;
-#pragma unroll 1
-          for (int i = 0; i < 3 * n; ++i) bad |= !tv_finite(v[i]);
-        }
-      }
-    }
+    for (int j = 0; j < A.n_tracks; ++j) bad |= track_bad(A.tr[j], b);
     if (bad) A.worst[b] = GRAD_NONFINITE;
   }
   const int dead = STAGE == TRACKVJP_TICK ? (A.worst[b] == GRAD_NONFINITE) : 0;   // a bad row, or a layer's non-finite: nothing is accumulated
@@ -116,31 +80,30 @@ __global__ void __launch_bounds__(64) wbc_trackvjp_kernel(const TrackVjpArgs A) 
         else if (A.d_ee_target) A.d_ee_target[b * 15 + 3 * T.target + c] = 0.0;
       }
       if (!dead) {                                                  // (n, du and the milestones passed BEGIN's test)
-        const int n = T.n_points ? T.n_points[b] : T.S;
-        const double du = T.du ? T.du[b] : T.du_all;
+        const int n = T.n_points ? T.n_points[b] : T.S;             // (track_n / track_du spelled out: through the calls this stage takes 76
+        const double du = T.du ? T.du[b] : T.du_all;                //  VGPRs instead of 72, one wave per SIMD less; tools/kernel_resources.py)
         const double* m = T.points + row;
-        const double t = (double)A.k * du;
-        if (t <= 0.0) {
+        const TrackSeg sg = track_segment((double)A.k * du, n);
+        if (sg.where == SEG_FIRST) {
           if (dp) dp[0] = dp[0] + e;
-        } else if (t >= (double)(n - 1)) {
+        } else if (sg.where == SEG_LAST) {
           if (dp) dp[3 * (n - 1)] = dp[3 * (n - 1)] + e;
         } else {
-          const double fi = floor(t);
-          const int i = (int)fi;                                    // 0 <= i <= n - 2 here
-          const double u = t - fi;
+          const int i = sg.i;                                       // 0 <= i <= n - 2 here
+          const double u = sg.u;
           const double m0 = m[3 * i], m1 = m[3 * i + 3];
           if (T.kind != WBC_TRACK_HERMITE) {
             if (dp) { dp[3 * i] = dp[3 * i] + (1.0 - u) * e; dp[3 * i + 3] = dp[3 * i + 3] + u * e; }
             x = (m1 - m0) * e;
           } else {
-            const double u2 = u * u, u3 = u * u2;
-            const double cx1 = (2.0 * u3 - 3.0 * u2) + 1.0, cx2 = (-2.0 * u3) + 3.0 * u2, cv1 = (u3 - 2.0 * u2) + u, cv2 = u3 - u2;
+            const double u2 = u * u;
+            const HermiteBasis h = hermite_basis(u);
             const double* v = T.tangents ? T.tangents + row : nullptr;
-            const double v0 = v ? v[3 * i] : tv_tangent(m, n, i), v1 = v ? v[3 * i + 3] : tv_tangent(m, n, i + 1);
+            const double v0 = v ? v[3 * i] : track_tangent(m, n, i), v1 = v ? v[3 * i + 3] : track_tangent(m, n, i + 1);
             const double dx1 = 6.0 * u2 - 6.0 * u, dx2 = (-6.0 * u2) + 6.0 * u, dv1 = (3.0 * u2 - 4.0 * u) + 1.0, dv2 = 3.0 * u2 - 2.0 * u;
             x = (((dx1 * m0 + dx2 * m1) + dv1 * v0) + dv2 * v1) * e;
-            if (dp) { dp[3 * i] = dp[3 * i] + cx1 * e; dp[3 * i + 3] = dp[3 * i + 3] + cx2 * e; }
-            const double vb0 = cv1 * e, vb1 = cv2 * e;
+            if (dp) { dp[3 * i] = dp[3 * i] + h.cx1 * e; dp[3 * i + 3] = dp[3 * i + 3] + h.cx2 * e; }
+            const double vb0 = h.cv1 * e, vb1 = h.cv2 * e;
             if (v) {
               if (dt) { dt[3 * i] = dt[3 * i] + vb0; dt[3 * i + 3] = dt[3 * i + 3] + vb1; }
             } else if (dp) {

@@ -18,55 +18,34 @@ namespace wbc {
 
 constexpr int TRAJ_BLOCK = 256;
 
-__device__ __forceinline__ bool traj_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }   // false for NaN and +-inf
-
-// default tangent of component c at milestone i of the n milestones m[n][3]: the rule of klampt's makeSpline(preventOvershoot=True) as
-// include/wbc.h states it (no segment of the spline leaves the interval of its two milestones)
-__device__ __forceinline__ double traj_tangent(const double* __restrict__ m, int n, int i, int c) {
-  if (n == 2) return m[3 + c] - m[c];
-  if (i == 0 || i == n - 1) return 0.0;
-  const double a = m[3 * (i - 1) + c], x = m[3 * i + c], b = m[3 * (i + 1) + c];
-  const double w = (b - a) * 0.5, third = 1.0 / 3.0;
-  if (x <= fmin(a, b) || x >= fmax(a, b)) return 0.0;
-  if ((w < 0.0 && x - w * third >= a) || (w > 0.0 && x - w * third <= a)) return 3.0 * (x - a);
-  if ((w < 0.0 && x + w * third < b) || (w > 0.0 && x + w * third > b)) return 3.0 * (b - x);
-  return w;
-}
-
-// _LinearTrajectory.eval(t) (HERMITE: _HermiteTrajectory.eval(t)) over the n milestones m[n][3] (Robot_Wrapper4.py): clamped ends, unit
-// parameter per segment. v: the caller's tangents [n][3] or null (HERMITE only)
+// _LinearTrajectory.eval(t) (HERMITE: _HermiteTrajectory.eval(t)) over the n milestones m[n][3] (Robot_Wrapper4.py): wbc_track.h's segment,
+// basis and default-tangent rule. v: the caller's tangents [n][3] or null (HERMITE only)
 template <bool HERMITE>
 __device__ __forceinline__ void traj_eval(const double* __restrict__ m, const double* __restrict__ v, int n, double t, double out[3]) {
-  if (t <= 0.0) {
-    out[0] = m[0]; out[1] = m[1]; out[2] = m[2];
-  } else if (t >= (double)(n - 1)) {
-    const double* e = m + 3 * (n - 1);
-    out[0] = e[0]; out[1] = e[1]; out[2] = e[2];
+  const TrackSeg sg = track_segment(t, n);
+  const double* a = m + 3 * sg.i;
+  if (sg.where != SEG_INSIDE) {
+    out[0] = a[0]; out[1] = a[1]; out[2] = a[2];
+  } else if (!HERMITE) {
+    const double u = sg.u;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[c] = (1.0 - u) * a[c] + u * a[3 + c];
   } else {
-    const double fi = floor(t);
-    const int i = (int)fi;                 // 0 <= i <= n - 2 here
-    const double u = t - fi;
-    const double* a = m + 3 * i;
-    if (!HERMITE) {
+    const int i = sg.i;
+    const HermiteBasis h = hermite_basis(sg.u);
 #pragma unroll
-      for (int c = 0; c < 3; ++c) out[c] = (1.0 - u) * a[c] + u * a[3 + c];
-    } else {
-      const double u2 = u * u, u3 = u * u2;
-      const double cx1 = (2.0 * u3 - 3.0 * u2) + 1.0, cx2 = (-2.0 * u3) + 3.0 * u2, cv1 = (u3 - 2.0 * u2) + u, cv2 = u3 - u2;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const double v0 = v ? v[3 * i + c] : traj_tangent(m, n, i, c);
-        const double v1 = v ? v[3 * i + 3 + c] : traj_tangent(m, n, i + 1, c);
-        out[c] = ((cx1 * a[c] + cx2 * a[3 + c]) + cv1 * v0) + cv2 * v1;
-      }
+    for (int c = 0; c < 3; ++c) {
+      const double v0 = v ? v[3 * i + c] : track_tangent(m + c, n, i);
+      const double v1 = v ? v[3 * i + 3 + c] : track_tangent(m + c, n, i + 1);
+      out[c] = ((h.cx1 * a[c] + h.cx2 * a[3 + c]) + h.cv1 * v0) + h.cv2 * v1;
     }
   }
 }
 
 // the target of track T for instance b at tick k (the parameter is the product k * du, not a running sum) into its row of the target blocks
-__device__ __forceinline__ void traj_write_target(const TrajArgs& A, const TrajTrack& T, int b, int k) {
-  const int n = T.n_points ? T.n_points[b] : T.S;
-  const double du = T.du ? T.du[b] : T.du_all;
+__device__ __forceinline__ void traj_write_target(const TrajArgs& A, const DevTrack& T, int b, int k) {
+  const int n = track_n(T, b);
+  const double du = track_du(T, b);
   const double* m = T.points + (size_t)b * T.S * 3;
   const double t = (double)k * du;
   double nx[3];
@@ -81,23 +60,7 @@ __global__ void __launch_bounds__(TRAJ_BLOCK) wbc_traj_begin_kernel(const TrajAr
   if (b >= A.B) return;
   bool bad = false;
 #pragma unroll 1
-  for (int j = 0; j < A.n_tracks; ++j) {
-    const TrajTrack& T = A.tr[j];
-    const int n = T.n_points ? T.n_points[b] : T.S;
-    const double du = T.du ? T.du[b] : T.du_all;
-    const bool bad_n = n < 2 || n > T.S;
-    bad |= bad_n || !traj_finite(du) || !(du > 0.0);
-    if (!bad_n) {
-      const double* m = T.points + (size_t)b * T.S * 3;
-#pragma unroll 1
-      for (int i = 0; i < 3 * n; ++i) bad |= !traj_finite(m[i]);
-      if (T.tangents) {
-        const double* v = T.tangents + (size_t)b * T.S * 3;
-#pragma unroll 1
-        for (int i = 0; i < 3 * n; ++i) bad |= !traj_finite(v[i]);
-      }
-    }
-  }
+  for (int j = 0; j < A.n_tracks; ++j) bad |= track_bad(A.tr[j], b);
   A.bad[b] = bad ? 1 : 0;
   int nsc = 0;
 #pragma unroll 1
@@ -144,11 +107,9 @@ __global__ void __launch_bounds__(TRAJ_BLOCK) wbc_traj_tick_kernel(const TrajArg
       }
     }
     if (bad) return;
-    const TrajTrack& T = A.tr[0];
-    const int n = T.n_points ? T.n_points[b] : T.S;
-    const double du = T.du ? T.du[b] : T.du_all;
+    const DevTrack& T = A.tr[0];
     double nx[3];
-    traj_eval<false>(T.points + (size_t)b * T.S * 3, nullptr, n, (double)(k + 1) * du, nx);   // the parameter is the product, not a running sum
+    traj_eval<false>(T.points + (size_t)b * T.S * 3, nullptr, track_n(T, b), (double)(k + 1) * track_du(T, b), nx);   // the parameter is the product, not a running sum
     double* out = A.ee_target + (size_t)b * 15 + 3 * T.target;
     out[0] = nx[0]; out[1] = nx[1]; out[2] = nx[2];
     return;

@@ -4,6 +4,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include "../../include/wbc.h"
+#include "wbc_track.h"
 
 namespace wbc {
 
@@ -15,15 +16,10 @@ namespace wbc {
 //   eval_b(k * du_b) into the track outputs, the followed rows <- 0; at k == 0 the followed rows of the caller's d_ee_target / d_trunk_target
 //   <- 0 and the all-zero rule on the track outputs.
 enum { TRACKVJP_BEGIN = 0, TRACKVJP_TICK = 1 };
-struct TrackVjpTrack {
-  int32_t target, kind, S, pad_;
-  const double* points;                 // [B][S][3]
-  const double* tangents;               // [B][S][3] or null (HERMITE: the default rule)
-  const int32_t* n_points;              // null => S
-  const double* du;                     // null => du_all
-  double du_all;
+struct TrackVjpTrack : DevTrack {       // the followed track (wbc_track.h), then its outputs
   double *d_points, *d_tangents, *d_du; // the caller's (or the staged) outputs, each optional: the accumulators live in them
 };
+static_assert(sizeof(TrackVjpTrack) == sizeof(DevTrack) + 3 * sizeof(double*) && sizeof(DevTrack) == 56, "the outputs directly behind the nine shared fields");
 struct TrackVjpArgs {
   int32_t B, k, n_tracks, pad_;
   TrackVjpTrack tr[WBC_MAX_TRACKS];

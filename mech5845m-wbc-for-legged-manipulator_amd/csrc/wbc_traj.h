@@ -4,20 +4,11 @@
 #include <stddef.h>
 #include <stdint.h>
 #include "../../include/wbc.h"
+#include "wbc_track.h"
 
 namespace wbc {
 
 constexpr int TRAJ_FRAMES = WBC_MAX_TRACKS;   // targets / frames 0..4: the end effectors, 5: the trunk
-
-// One followed target: per-instance milestones (and, HERMITE, tangents) as WbcTrack.
-struct TrajTrack {
-  int32_t target, kind, S, pad_;
-  const double* points;                 // [B][S][3]
-  const double* tangents;               // [B][S][3], HERMITE only; null => the default rule, computed on the fly
-  const int32_t* n_points;              // null => S
-  const double* du;                     // null => du_all
-  double du_all;
-};
 
 // The tracks of a call + the scores of the frames in `score_mask`. wbc_rollout_traj is the one-track call: a LINEAR track of end effector
 // `ee`, the gripper scored, its position read from the update kernel's grip_trace row (reached_stride 3, reached_off[4] 0).
@@ -26,7 +17,7 @@ struct TrajArgs {
   int32_t n_tracks, do_sum;             // do_sum 1: the per-tick kernel accumulates the scores
   int32_t score_mask;                   // bit f: frame f is scored (n_scored = popcount, frames in increasing order)
   int32_t one_track;                    // 1: wbc_rollout_traj's call (wbc_traj_tick_kernel<true>)
-  TrajTrack tr[WBC_MAX_TRACKS];
+  DevTrack tr[WBC_MAX_TRACKS];          // (wbc_track.h)
   double* ee_target;                    // the roll-out's [B][5][3] target block
   double* trunk_target;                 // the roll-out's [B][3] trunk target (null without one)
   const double* trunk_step;             // [B][3] added to trunk_target after the tick was scored (wbc_rollout_tracks without a trunk track), or null

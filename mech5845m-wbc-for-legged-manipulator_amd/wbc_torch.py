@@ -115,6 +115,28 @@ def _wanted(names, args, need, offered=None):
     return tuple("d_" + n for k, n in enumerate(names) if need[k] and args[k] is not None and (offered is None or "d_" + n in offered))
 
 
+def _state_seeds(g_q, g_qdot, g_trace, q_final, q_trace):
+    """the state seeds of WbcBatch.rollout_vjp from the raw gradients of a recorded roll-out's outputs (each may be None): q_K's and the
+    trace's from raw to tangent coordinates in ONE wbc_workload.raw_to_tangent call -> dict(g_q_final, g_qdot_last, g_q_trace)"""
+    import wbc_workload
+    K, B = q_trace.shape[0], q_trace.shape[1]
+    raw, at = [], []
+    if g_q is not None:
+        raw.append(g_q.reshape(B, -1))
+        at.append(q_final)
+    if g_trace is not None:
+        raw.append(g_trace.reshape(K * B, -1))
+        at.append(q_trace.reshape(K * B, -1))
+    gq_f = gq_t = None
+    if raw:
+        tang = wbc_workload.raw_to_tangent(torch.cat(at), torch.cat(raw).contiguous())
+        if g_q is not None:
+            gq_f = tang[:B].contiguous()
+        if g_trace is not None:
+            gq_t = tang[-K * B:].reshape(K, B, -1).contiguous()
+    return dict(g_q_final=gq_f, g_qdot_last=None if g_qdot is None else g_qdot.contiguous(), g_q_trace=gq_t)
+
+
 class _WbcTick(torch.autograd.Function):
     """wbc_tick (q None: the state is inputs["q"] and gets no gradient) and wbc_tick_state"""
     @staticmethod
@@ -279,26 +301,10 @@ class _WbcRolloutFused(torch.autograd.Function):
         (q_final, q_trace), args = _saved(ctx, 2)
         n_out = len(_FUSED_ARGS) + 6
         bt, tape = ctx.batch, ctx.tape
-        K, B = tape.ticks, tape.B
         want = _wanted(_FUSED_ARGS, args, ctx.needs_input_grad, set(bt.default_rollout_grad_wants(tape.call["mode"])))
         if (g_q is None and g_qdot is None and g_trace is None) or not want:
             return (None,) * n_out
-        # the seeds: raw -> tangent coordinates, q_K's and the trace's in one call
-        raw, at = [], []
-        if g_q is not None:
-            raw.append(g_q.reshape(B, -1))
-            at.append(q_final)
-        if g_trace is not None:
-            raw.append(g_trace.reshape(K * B, -1))
-            at.append(q_trace.reshape(K * B, -1))
-        gq_f = gq_t = None
-        if raw:
-            tang = wbc_workload.raw_to_tangent(torch.cat(at), torch.cat(raw).contiguous())
-            if g_q is not None:
-                gq_f = tang[:B].contiguous()
-            if g_trace is not None:
-                gq_t = tang[-K * B:].reshape(K, B, -1).contiguous()
-        r = bt.rollout_vjp(tape, g_q_final=gq_f, g_qdot_last=None if g_qdot is None else g_qdot.contiguous(), g_q_trace=gq_t, want=want)
+        r = bt.rollout_vjp(tape, want=want, **_state_seeds(g_q, g_qdot, g_trace, q_final, q_trace))
         res = [None if "d_" + n not in want else r["d_" + n].reshape(a.shape) if n != "q0" else wbc_workload.tangent_to_raw(a, r["d_q0"])
                for n, a in zip(_FUSED_ARGS, args)]
         return tuple(res) + (None,) * 6
@@ -316,62 +322,77 @@ def wbc_rollout_fused(q0, task_params, ee_target, prev_ee_target, trunk_target, 
                                   posture_u, ee_target_step, trunk_target_step, inputs, dt, ticks, batch, mode, imu)
 
 
+# ---- the two layers over a recorded roll-out along tracks: their arguments are (q0, task_params, eight that get no gradient, *flat)
+_TRACK_GRADS = ("d_points", "d_tangents", "d_du")
+
+
+def _flat_tracks(tracks):
+    """rollout_tracks' list of dicts -> (specs, flat): flat holds (points, tangents, du) per track, None where there is none; what is no
+    tensor (target, kind, n_points, a du given as a number) stays in the track's spec"""
+    specs, flat = [], []
+    for t in tracks:
+        du = t.get("du", 0.002)
+        specs.append({k: v for k, v in t.items() if k not in ("points", "tangents", "du")})
+        if not torch.is_tensor(du):
+            specs[-1]["du"] = du
+        flat += [t["points"], t.get("tangents"), du if torch.is_tensor(du) else None]
+    return specs, flat
+
+
+def _tracks_of(specs, flat):
+    """_flat_tracks undone"""
+    tracks = []
+    for j, spec in enumerate(specs):
+        t = dict(spec, points=flat[3 * j])
+        if flat[3 * j + 1] is not None:
+            t["tangents"] = flat[3 * j + 1]
+        if flat[3 * j + 2] is not None:
+            t["du"] = flat[3 * j + 2]
+        tracks.append(t)
+    return tracks
+
+
+def _tracks_record(ctx, q0, task_params, inputs, dt, ticks, batch, specs, flat, **kw):
+    """the forward of both layers: one WbcBatch.rollout_record along the tracks -> (its dict, the arguments as saved)"""
+    args = [_c(q0), _c(task_params)] + [_c(t) for t in flat]
+    out, tape = batch.rollout_record(dict(inputs, q=args[0]), dt, ticks, task_params=args[1], tracks=_tracks_of(specs, args[2:]), **kw)
+    ctx.batch, ctx.tape = batch, tape
+    return out, args
+
+
+def _tracks_sweep(ctx, args, g_q, g_qdot, g_trace, q_final, q_trace, **score):
+    """the backward of both layers: one WbcBatch.rollout_vjp for what needs a gradient, seeded with the raw gradients of q_final, qdot and
+    q_trace (each may be None) and, where the loss uses a score, score = dict(score_seed=...) -> the gradients of every forward argument"""
+    import wbc_workload
+    n_flat = len(args) - 2
+    need = ctx.needs_input_grad
+    want = [n for n, k in (("d_q0", 0), ("d_task_params", 1)) if need[k] and args[k] is not None]
+    need_flat = [bool(need[10 + i]) and args[2 + i] is not None for i in range(n_flat)]
+    want += [n for c, n in enumerate(_TRACK_GRADS) if any(need_flat[c::3])]
+    if (not score and g_q is None and g_qdot is None and g_trace is None) or not want:
+        return (None,) * (10 + n_flat)
+    r = ctx.batch.rollout_vjp(ctx.tape, want=want, **_state_seeds(g_q, g_qdot, g_trace, q_final, q_trace), **score)
+    res = [wbc_workload.tangent_to_raw(args[0], r["d_q0"]) if "d_q0" in want else None,
+           r["d_task_params"].reshape(args[1].shape) if "d_task_params" in want else None] + [None] * 8
+    for i in range(n_flat):
+        got = r["tracks"][i // 3].get(_TRACK_GRADS[i % 3]) if need_flat[i] else None
+        res.append(None if got is None else got.reshape(args[2 + i].shape))
+    return tuple(res)
+
+
 class _WbcRolloutTracksFused(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q0, task_params, inputs, dt, ticks, batch, mode, imu, trunk_target_step, specs, *flat):
-        args = [_c(q0), _c(task_params)] + [_c(t) for t in flat]
-        d = dict(inputs)
-        d["q"] = args[0]
-        tracks = []
-        for j, spec in enumerate(specs):     # flat: (points, tangents, du) per track; a du that is no tensor stays in the spec
-            t = dict(spec, points=args[2 + 3 * j])
-            if args[3 + 3 * j] is not None:
-                t["tangents"] = args[3 + 3 * j]
-            if args[4 + 3 * j] is not None:
-                t["du"] = args[4 + 3 * j]
-            tracks.append(t)
-        out, tape = batch.rollout_record(d, dt, ticks, trunk_target_step=_c(trunk_target_step), imu=_c(imu), mode=mode, task_params=args[1],
-                                         tracks=tracks)
-        ctx.batch, ctx.tape = batch, tape
+        out, args = _tracks_record(ctx, q0, task_params, inputs, dt, ticks, batch, specs, flat, trunk_target_step=_c(trunk_target_step),
+                                   imu=_c(imu), mode=mode)
         _save(ctx, (out["q"], out["q_trace"]), args)
         ctx.mark_non_differentiable(out["status"])
         return out["q"], out["qdot"], out["status"], out["q_trace"]
 
     @staticmethod
     def backward(ctx, g_q, g_qdot, _gst, g_trace):
-        import wbc_workload
         (q_final, q_trace), args = _saved(ctx, 2)
-        n_flat = len(args) - 2
-        bt, tape = ctx.batch, ctx.tape
-        K, B = tape.ticks, tape.B
-        need = ctx.needs_input_grad
-        want = [n for n, k in (("d_q0", 0), ("d_task_params", 1)) if need[k] and args[k] is not None]
-        names = ("d_points", "d_tangents", "d_du")
-        need_flat = [bool(need[10 + i]) and args[2 + i] is not None for i in range(n_flat)]
-        want += [n for c, n in enumerate(names) if any(need_flat[c::3])]
-        if (g_q is None and g_qdot is None and g_trace is None) or not want:
-            return (None,) * (10 + n_flat)
-        raw, at = [], []
-        if g_q is not None:
-            raw.append(g_q.reshape(B, -1))
-            at.append(q_final)
-        if g_trace is not None:
-            raw.append(g_trace.reshape(K * B, -1))
-            at.append(q_trace.reshape(K * B, -1))
-        gq_f = gq_t = None
-        if raw:
-            tang = wbc_workload.raw_to_tangent(torch.cat(at), torch.cat(raw).contiguous())
-            if g_q is not None:
-                gq_f = tang[:B].contiguous()
-            if g_trace is not None:
-                gq_t = tang[-K * B:].reshape(K, B, -1).contiguous()
-        r = bt.rollout_vjp(tape, g_q_final=gq_f, g_qdot_last=None if g_qdot is None else g_qdot.contiguous(), g_q_trace=gq_t, want=want)
-        res = [wbc_workload.tangent_to_raw(args[0], r["d_q0"]) if "d_q0" in want else None,
-               r["d_task_params"].reshape(args[1].shape) if "d_task_params" in want else None]
-        for i in range(n_flat):
-            got = r["tracks"][i // 3].get(names[i % 3]) if need_flat[i] else None
-            res.append(None if got is None else got.reshape(args[2 + i].shape))
-        return tuple(res[:2]) + (None,) * 8 + tuple(res[2:])
+        return _tracks_sweep(ctx, args, g_q, g_qdot, g_trace, q_final, q_trace)
 
 
 def wbc_rollout_tracks_fused(q0, task_params, tracks, inputs, dt, ticks, batch, mode=capi.ROLLOUT_RUNNING, imu=None, trunk_target_step=None):
@@ -383,33 +404,16 @@ def wbc_rollout_tracks_fused(q0, task_params, tracks, inputs, dt, ticks, batch, 
     task_params; the constant targets come from `inputs` and get none here (wbc_rollout_fused is the layer for those). Returns what
     wbc_rollout_fused returns: (q_final [B,27], qdot of the last tick [B,26], status [B] int32, q_trace [ticks,B,27]). A bad row (include/wbc.h)
     gets zero gradients everywhere. Contiguous float64 tensors on the handle's device."""
-    specs, flat = [], []
-    for t in tracks:
-        du = t.get("du", 0.002)
-        specs.append({k: v for k, v in t.items() if k not in ("points", "tangents", "du")})
-        if not torch.is_tensor(du):
-            specs[-1]["du"] = du
-        flat += [t["points"], t.get("tangents"), du if torch.is_tensor(du) else None]
+    specs, flat = _flat_tracks(tracks)
     return _WbcRolloutTracksFused.apply(q0, task_params, inputs, dt, ticks, batch, mode, imu, trunk_target_step, specs, *flat)
 
 
 class _WbcRolloutTracksScored(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q0, task_params, inputs, dt, ticks, batch, mode, trunk_target_step, score, specs, *flat):
-        args = [_c(q0), _c(task_params)] + [_c(t) for t in flat]
-        d = dict(inputs)
-        d["q"] = args[0]
-        tracks = []
-        for j, spec in enumerate(specs):     # flat: (points, tangents, du) per track; a du that is no tensor stays in the spec
-            t = dict(spec, points=args[2 + 3 * j])
-            if args[3 + 3 * j] is not None:
-                t["tangents"] = args[3 + 3 * j]
-            if args[4 + 3 * j] is not None:
-                t["du"] = args[4 + 3 * j]
-            tracks.append(t)
-        out, tape = batch.rollout_record(d, dt, ticks, trunk_target_step=_c(trunk_target_step), mode=mode, task_params=args[1], tracks=tracks,
-                                         score=score)
-        ctx.batch, ctx.tape, ctx.score = batch, tape, tuple(score)
+        out, args = _tracks_record(ctx, q0, task_params, inputs, dt, ticks, batch, specs, flat, trunk_target_step=_c(trunk_target_step),
+                                   mode=mode, score=score)
+        ctx.score = tuple(score)
         ctx.set_materialize_grads(False)     # an output the loss does not use gives None, not zeros: its seed is left out of the call
         _save(ctx, (out["q"], out["q_trace"], out["err_max_tick"]), args)
         ctx.mark_non_differentiable(out["status"], out["err_max_tick"])
@@ -417,46 +421,13 @@ class _WbcRolloutTracksScored(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_q, g_qdot, _gst, g_trace, g_sq, g_fin, g_max, _gtick):
-        import wbc_workload
         (q_final, q_trace, err_max_tick), args = _saved(ctx, 3)
-        n_flat = len(args) - 2
-        bt, tape = ctx.batch, ctx.tape
-        K, B = tape.ticks, tape.B
-        need = ctx.needs_input_grad
-        want = [n for n, k in (("d_q0", 0), ("d_task_params", 1)) if need[k] and args[k] is not None]
-        names = ("d_points", "d_tangents", "d_du")
-        need_flat = [bool(need[10 + i]) and args[2 + i] is not None for i in range(n_flat)]
-        want += [n for c, n in enumerate(names) if any(need_flat[c::3])]
-        scored = not (g_sq is None and g_fin is None and g_max is None)
-        if (g_q is None and g_qdot is None and g_trace is None and not scored) or not want:
-            return (None,) * (10 + n_flat)
-        raw, at = [], []
-        if g_q is not None:
-            raw.append(g_q.reshape(B, -1))
-            at.append(q_final)
-        if g_trace is not None:
-            raw.append(g_trace.reshape(K * B, -1))
-            at.append(q_trace.reshape(K * B, -1))
-        gq_f = gq_t = None
-        if raw:
-            tang = wbc_workload.raw_to_tangent(torch.cat(at), torch.cat(raw).contiguous())
-            if g_q is not None:
-                gq_f = tang[:B].contiguous()
-            if g_trace is not None:
-                gq_t = tang[-K * B:].reshape(K, B, -1).contiguous()
-        seed = None
-        if scored:
+        score = {}
+        if not (g_sq is None and g_fin is None and g_max is None):
             cg = lambda t: None if t is None else t.contiguous()      # noqa: E731
-            seed = dict(mask=ctx.score, g_err_sq_sum=cg(g_sq), g_err_final=cg(g_fin), g_err_max=cg(g_max),
-                        err_max_tick=None if g_max is None else err_max_tick, q_final=q_final)
-        r = bt.rollout_vjp(tape, g_q_final=gq_f, g_qdot_last=None if g_qdot is None else g_qdot.contiguous(), g_q_trace=gq_t, want=want,
-                           score_seed=seed)
-        res = [wbc_workload.tangent_to_raw(args[0], r["d_q0"]) if "d_q0" in want else None,
-               r["d_task_params"].reshape(args[1].shape) if "d_task_params" in want else None]
-        for i in range(n_flat):
-            got = r["tracks"][i // 3].get(names[i % 3]) if need_flat[i] else None
-            res.append(None if got is None else got.reshape(args[2 + i].shape))
-        return tuple(res[:2]) + (None,) * 8 + tuple(res[2:])
+            score["score_seed"] = dict(mask=ctx.score, g_err_sq_sum=cg(g_sq), g_err_final=cg(g_fin), g_err_max=cg(g_max),
+                                       err_max_tick=None if g_max is None else err_max_tick, q_final=q_final)
+        return _tracks_sweep(ctx, args, g_q, g_qdot, g_trace, q_final, q_trace, **score)
 
 
 def wbc_rollout_tracks_scored(q0, task_params, tracks, inputs, dt, ticks, batch, score=(4,), mode=capi.ROLLOUT_RUNNING, trunk_target_step=None):
@@ -467,11 +438,5 @@ def wbc_rollout_tracks_scored(q0, task_params, tracks, inputs, dt, ticks, batch,
     err_sq_sum, err_final, err_max [n_scored,B] (rows in increasing frame order; differentiable) and err_max_tick [n_scored,B] int32 (not
     differentiable). A loss may mix the scores with q_final, qdot and q_trace: the gradients are those of the sum. The group RMS is
     torch.sqrt(err_sq_sum.reshape(n, G, M).sum(-1) / (M * ticks)). No IMU quaternion is fed back under a score (include/wbc.h)."""
-    specs, flat = [], []
-    for t in tracks:
-        du = t.get("du", 0.002)
-        specs.append({k: v for k, v in t.items() if k not in ("points", "tangents", "du")})
-        if not torch.is_tensor(du):
-            specs[-1]["du"] = du
-        flat += [t["points"], t.get("tangents"), du if torch.is_tensor(du) else None]
+    specs, flat = _flat_tracks(tracks)
     return _WbcRolloutTracksScored.apply(q0, task_params, inputs, dt, ticks, batch, mode, trunk_target_step, tuple(score), specs, *flat)
