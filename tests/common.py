@@ -184,6 +184,134 @@ def far_tick_inputs(model, cfg, B, seed, narrow=False, edge=True, with_rot=False
     return d
 
 
+# ---- the velocity damper's zones: sample_q and the stress recipe reach the band 0 <= d < qs of one arm DoF and nothing else
+DAMPER_CLASSES = ("base", "leg", "arm")
+DAMPER_KINDS = ("regular", "flipped", "beyond", "edge", "qs")         # shares 3/8, 2/8, 1/8, 1/8, 1/8
+DAMPER_COUNTS = (1, 2, 3, 5)
+DAMPER_WIDEN = 0.06                                                   # rad: a written coordinate may leave its joint's own range by this much
+DAMPER_FAR_X = 11.0                                                   # m: the last instance's base x; 6 m beyond the upper limit, the clamp at -v_max
+
+
+def damper_class(i):
+    """class of DoF i, the variable the bound is on: the packed kernels eliminate base and stance-leg DoF and keep the arm's"""
+    return 0 if i < 6 else (1 if i < 18 else 2)
+
+
+def damper_candidates(model, cfg):
+    """DoF i < lock_from whose watched coordinate damper_qidx[i] is base x, y, z or a 1-DoF joint coordinate (never the quaternion)"""
+    return [i for i in range(min(model.nv, int(cfg.lock_from))) if cfg.damper_qidx[i] < 3 or cfg.damper_qidx[i] >= 7]
+
+
+def _damper_depth(cfg, rng, edges):
+    """-> (kind, d or None): the distance to the limit of one draw; None where the coordinate is formed from the limit as the code forms it"""
+    qi, qs = cfg.damper_qi, cfg.damper_qs
+    k = int(rng.integers(0, 8)) if edges else int(rng.integers(0, 6))
+    if k < 3:
+        return 0, rng.uniform(qs + 1e-3, qi - 1e-3)
+    if k < 5:
+        return 1, rng.uniform(0.0, qs - 1e-3)
+    if k == 5:
+        return 2, -rng.uniform(0.0, 0.05)
+    return (3, None) if k == 6 else (4, None)
+
+
+def damper_q(model, cfg, B, rng, edges=True, classes=DAMPER_CLASSES, far=True):
+    """wbc_workload.sample_q with n = (1, 2, 3, 5)[b % 4] DoF of instance b inside a damper zone: the first from the class
+    (base, leg, arm)[(b // 4) % 3] (the next class on where `classes` leaves it out), the others from every candidate of `classes`; each at a
+    random side, at a depth of _damper_depth. The watched coordinate becomes lo[i] + d or hi[i] - d (`edge`: lo + qi / hi - qi, `qs`: lo + qs /
+    hi - qs, each one double operation as the kernels form them); base z on the upper side only; a value outside the watched joint's own model
+    range widened by DAMPER_WIDEN is drawn again (DoF, side and depth; an instance of a narrowed pool that runs out of admissible DoF keeps
+    what it has). far: the last instance's base x is DAMPER_FAR_X (needs the base class)."""
+    q = wbc_workload.sample_q(model, B, rng)
+    cand = [i for i in damper_candidates(model, cfg) if DAMPER_CLASSES[damper_class(i)] in classes]
+    by_class = [[i for i in cand if damper_class(i) == c] for c in range(3)]
+    for b in range(B):
+        first = (b // 4) % 3
+        while not by_class[first]:
+            first = (first + 1) % 3
+        taken = []
+        for slot in range(DAMPER_COUNTS[b % 4]):
+            pool = [i for i in (by_class[first] if slot == 0 else cand) if i not in taken]
+            if not pool:                                              # (fewer candidates than n: a narrowed recipe)
+                break
+            for _ in range(64):
+                i = int(rng.choice(pool))
+                c = int(cfg.damper_qidx[i])
+                upper = True if c == 2 else bool(rng.random() < 0.5)
+                kind, d = _damper_depth(cfg, rng, edges)
+                lo, hi = cfg.damper_lo[i], cfg.damper_hi[i]
+                if kind == 3:
+                    v = hi - cfg.damper_qi if upper else lo + cfg.damper_qi
+                elif kind == 4:
+                    v = hi - cfg.damper_qs if upper else lo + cfg.damper_qs
+                else:
+                    v = hi - d if upper else lo + d
+                if model.q_lo[c] - DAMPER_WIDEN <= v <= model.q_hi[c] + DAMPER_WIDEN:
+                    q[b, c] = v
+                    taken.append(i)
+                    break
+            else:                                                     # (what is left of a narrowed recipe's pool admits no value)
+                break
+    if far and "base" in classes:
+        q[B - 1, 0] = DAMPER_FAR_X
+    return q
+
+
+def damper_zones(cfg, nv, q):
+    """-> zone [B, 26, 2] (lower side, upper side) of every DoF < lock_from: -1 outside every zone, else the index into DAMPER_KINDS, read off
+    q with the comparisons of the code: edge where the coordinate IS lo + qi / hi - qi, qs where it IS lo + qs / hi - qs"""
+    q = np.asarray(q, dtype=np.float64).reshape(-1, capi.Q_STRIDE)
+    z = np.full((q.shape[0], capi.V_STRIDE, 2), -1, dtype=np.int8)
+    for i in range(min(nv, int(cfg.lock_from))):
+        c, lo, hi = q[:, cfg.damper_qidx[i]], cfg.damper_lo[i], cfg.damper_hi[i]
+        for side, inside, d, edge, at_qs in ((0, c <= lo + cfg.damper_qi, c - lo, lo + cfg.damper_qi, lo + cfg.damper_qs),
+                                             (1, c >= hi - cfg.damper_qi, hi - c, hi - cfg.damper_qi, hi - cfg.damper_qs)):
+            kind = np.where(d < 0, 2, np.where(d < cfg.damper_qs, 1, 0))
+            kind = np.where(c == edge, 3, np.where(c == at_qs, 4, kind))
+            z[:, i, side] = np.where(inside, kind, -1)
+    return z
+
+
+def damper_active(cfg, nv, q, lb, ub, qdot, tol=1e-9):
+    """-> active [B, 26, 2]: q̇ on the bound (within tol) and the bound not -+v_max, lower and upper side"""
+    vm = np.array([cfg.damper_vmax[i] for i in range(capi.V_STRIDE)])[None, :]
+    act = np.zeros(qdot.shape + (2,), dtype=bool)
+    act[:, :, 0] = (np.abs(qdot - lb) <= tol) & (lb != -vm)
+    act[:, :, 1] = (np.abs(qdot - ub) <= tol) & (ub != vm)
+    act[:, min(nv, int(cfg.lock_from)):] = False
+    return act
+
+
+def damper_tick_inputs(model, cfg, B, seed, edges=True, classes=DAMPER_CLASSES, far=True, with_rot=False):
+    """tick inputs on damper_q poses; targets, trunk box, CoM target and rotation references as far_tick_inputs(edge=False) makes them (that
+    function draws its own poses and stays as it is): on the robot, the box centred on the robot's own angles"""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    fk = OracleFK([model])
+    q = damper_q(model, cfg, B, rng, edges, classes, far)
+    oMf = fk(q)
+    pos = oMf[:, :, 9:12]
+    trunk = pos[:, capi.FR_TRUNK, :].copy()
+    ee_target = pos[:, capi.FR_EE0:capi.FR_EE0 + 5, :].copy()
+    ee_target[:, 4, :] += rng.normal(0, 0.01, (B, 3))
+    d = dict(q=q, ee_target=ee_target, prev_ee_target=ee_target - rng.normal(0, 0.0005, (B, 5, 3)),
+             trunk_target=trunk.copy(), prev_trunk_target=trunk - rng.normal(0, 0.0005, (B, 3)))
+    eul = wbc_workload.R_to_euler_xyz(oMf[:, capi.FR_TRUNK, 0:9])
+    box = np.concatenate([trunk[:, 2:3], eul], axis=1)
+    if cfg.con_trunk:
+        pick = rng.random(B) < 0.25
+        frac = rng.uniform(0.245, 0.2505, B) * np.where(rng.random(B) < 0.5, 1.0, -1.0)
+        box[pick, 0] = trunk[pick, 2] / (1.0 + frac[pick])
+    d["trunk_box_center"] = box
+    d["trunk_ref_euler"] = eul.copy()
+    d["trunk_prev_rot"] = oMf[:, capi.FR_TRUNK, 0:9].copy()
+    if cfg.task_com:
+        d["com_target"] = fk.com(q) + rng.normal(0, 0.002, (B, 3))
+        d["com_target_vel"] = rng.normal(0, 0.05, (B, 3))
+    if with_rot:
+        add_rot_references(d, B, seed)
+    return d
+
+
 def kkt_residuals(H, g, C, lb, ub, cl, cu, x, act_tol=1e-7):
     """Solver-independent optimality certificate: (primal violation, stationarity residual with sign-correct multipliers)."""
     from scipy.optimize import lsq_linear

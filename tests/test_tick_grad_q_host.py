@@ -104,10 +104,13 @@ def _random_sides(rng, B, n):
     return ((1 << (np.arange(n)[None, :] + 32 * up)).sum(axis=1)).astype(np.uint64)
 
 
-def _algebra_problem(cfg_name, model_name, B, seed, dt=DT):
+def _algebra_problem(cfg_name, model_name, B, seed, dt=DT, inputs=None):
     m = tgp._model(model_name)
-    cfg = common.config(cfg_name, m)
-    d = common.tick_inputs(m, cfg, B, seed=seed, with_rot=True)
+    if inputs is None:
+        cfg = common.config(cfg_name, m)
+        d = common.tick_inputs(m, cfg, B, seed=seed, with_rot=True)
+    else:                                                                # inputs(model, cfg_name, B, seed) -> (configuration, tick inputs)
+        cfg, d = inputs(m, cfg_name, B, seed)
     rng = np.random.default_rng(seed + 17)
     if cfg.task_joint >= capi.JOINT_MANI:
         d["posture_u"] = rng.normal(0, 0.3, (B, capi.V_STRIDE))
@@ -139,10 +142,10 @@ def test_algebra_against_central_differences_of_the_assembly(cfg_name, model_nam
     algebra_check(cfg_name, model_name)
 
 
-def algebra_check(cfg_name, model_name, dt=DT):
-    """the check at step dt (test_dt_host.py runs it at steps other than 2 ms)"""
-    B = 4
-    m, cfg, d, res, asm, ms, pid = _algebra_problem(cfg_name, model_name, B, seed=31, dt=dt)
+def algebra_check(cfg_name, model_name, dt=DT, inputs=None, B=4):
+    """the check at step dt (test_dt_host.py runs it at steps other than 2 ms), on the inputs of a recipe other than tick_inputs where one is
+    given (test_damper_envelope_host.py); -> (model, configuration, inputs)"""
+    m, cfg, d, res, asm, ms, pid = _algebra_problem(cfg_name, model_name, B, seed=31, dt=dt, inputs=inputs)
     a0 = asm(d)
     size = sum(np.abs(_finite(a0[k])).reshape(B, -1).max(axis=1, initial=0.0) for k in QP_KEYS)
     l1 = sum(np.abs(res[GRAD_OF[k]]).reshape(B, -1).sum(axis=1) for k in QP_KEYS)
@@ -172,6 +175,7 @@ def algebra_check(cfg_name, model_name, dt=DT):
         assert np.abs(res["d_trunk_box_center"]).min() > 0
     else:
         assert (res["d_trunk_box_center"] == 0).all()
+    return m, cfg, d
 
 
 # ---- end to end
@@ -188,11 +192,14 @@ E2E_CASES = [("c2", "near", 3), ("c3", "near", 3), ("c3_trunk_task", "near", 3),
              ("c3", "far", 4)]
 
 
-def _e2e_setup(cfg_name, kind, seed):
+def _e2e_setup(cfg_name, kind, seed, inputs=None):
     B = E2E_B
     m = tgp._model("a1_wx200")
-    cfg = common.config(cfg_name, m)
-    d = (common.tick_inputs if kind == "near" else common.far_tick_inputs)(m, cfg, B, seed=seed, with_rot=True)
+    if inputs is None:
+        cfg = common.config(cfg_name, m)
+        d = (common.tick_inputs if kind == "near" else common.far_tick_inputs)(m, cfg, B, seed=seed, with_rot=True)
+    else:                                                                # as _algebra_problem
+        cfg, d = inputs(m, cfg_name, B, seed)
     rng = np.random.default_rng(seed + 23)
     v = gc.task_space_v([m], [cfg], None, d, rng)
     return m, cfg, d, rng, v
@@ -265,8 +272,13 @@ def _directional(m, cfg, d, v, q_of, side0, margin, ana, scale_terms, t0, a0, wh
 
 @pytest.mark.parametrize("cfg_name,kind,seed", E2E_CASES)
 def test_end_to_end_against_directional_differences_of_the_oracle_tick(cfg_name, kind, seed):
+    end_to_end_check(cfg_name, kind, seed)
+
+
+def end_to_end_check(cfg_name, kind, seed, inputs=None):
+    """-> (model, configuration, inputs, kept instances, the oracle's tick, its assembly, the active side of every bound and row)"""
     B = E2E_B
-    m, cfg, d, rng, v = _e2e_setup(cfg_name, kind, seed)
+    m, cfg, d, rng, v = _e2e_setup(cfg_name, kind, seed, inputs)
     t0, a0, cert, res, side0, margin = _certified(m, cfg, d, v)
     direc = np.zeros((B, 26))
     direc[:, :m.nv] = rng.choice([-1.0, 1.0], (B, m.nv)) * rng.uniform(0.5, 1.0, (B, m.nv))
@@ -286,6 +298,7 @@ def test_end_to_end_against_directional_differences_of_the_oracle_tick(cfg_name,
         print("  instances with an active damper bound that is not +-v_max: %d" % n)
         assert n >= 4
     assert ok, line
+    return m, cfg, d, keep, t0, a0, side0
 
 
 def test_tangent_to_raw_against_a_central_difference_in_raw_coordinates():
