@@ -3,67 +3,41 @@
 // (weights) x (an unweighted Jacobian row): the kernel never forms A, H or a Jacobian. It recomputes the kinematics from q (the task rows
 // see q, not q_con), sums the WORLD twists  sum_d col_d x_d  and  sum_d col_d u_d  of each task frame over the frame's support — J_r x and
 // J_r u of all six rows of the frame at once — and applies the block rules of include/wbc.h.
-// One kernel, wbc_slack_kernel's shape: four instances per wavefront (lane = 16 r + s), FK over the whole-tree schedule DevPlan.q_fk.
-// Lane s owns the DoF s and 16 + s (their WORLD Jacobian columns, pk_jac_col) and the bodies s and 16 + s (the CoM); sums over DoF are DPP row
-// butterflies. The 85 + 42 results of an instance are collected in LDS (zero-initialised: a switched-off task's entries are never touched)
+// One kernel of the whole-tree shape (wbc_qtree.h): four instances per wavefront (lane = 16 r + s), FK over the whole-tree schedule DevPlan.q_fk.
+// Lane s owns the DoF s and 16 + s (their WORLD Jacobian columns, qt_jac_cols) and the bodies s and 16 + s (the CoM); sums over DoF are DPP row
+// butterflies. The staged task image, the trunk target, the row terms and the exit rule are wbc_qtree.h's, shared with wbc_k_gradq.hip. The 85 + 42 results of an instance are collected in LDS (zero-initialised: a switched-off task's entries are never touched)
 // and leave in coalesced stores. Reads its inputs and the tables; writes nothing but its outputs, rows [0, B) only.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "wbc_packed.h"
 #include "wbc_grad.h"
+#include "wbc_qtree.h"
 
 namespace wbc {
 
-// tin: the staged task inputs of an instance
-constexpr int GI_EE = 0, GI_EEP = 15, GI_TR = 30, GI_CT = 48, GI_CV = 51, GI_PU = 54, GI_OM = 80, GI_N = 96;
 // tout: the target gradients of an instance
 constexpr int GO_EE = 0, GO_EEP = 15, GO_TT = 30, GO_TP = 33, GO_CT = 36, GO_CV = 39, GO_N = 42;
-constexpr int WT_TW = 65, WT_Tw = 71, WT_TG = 72, WT_JW = 84;   // trunk_W, trunk_w, trunk_gain, joint_w inside the weights image (wbc_packed.h WT_*)
-static_assert(offsetof(WbcTaskParams, trunk_W) == WT_TW * sizeof(double) && offsetof(WbcTaskParams, trunk_w) == WT_Tw * sizeof(double) &&
-              offsetof(WbcTaskParams, trunk_gain) == WT_TG * sizeof(double) && offsetof(WbcTaskParams, joint_w) == WT_JW * sizeof(double) &&
-              offsetof(WbcTaskParams, ee_w) == WT_w * sizeof(double) && offsetof(WbcTaskParams, ee_gain) == WT_G * sizeof(double) &&
-              offsetof(WbcTaskParams, com_W) == WT_CW * sizeof(double) && offsetof(WbcTaskParams, com_gain) == WT_CG * sizeof(double),
-              "the weights image is WbcTaskParams, double for double");
-
 struct __attribute__((aligned(16))) GInst {
-  double oMi[24 * 12];
-  double q[32];
-  double sc[64];
+  QtKin K;
   double wt[96];                            // the 85 weights and gains (WbcTaskParams layout), rest zero
-  double tin[GI_N];
+  double tin[TI_N];
   double mcw[24 * 4];                       // body j: m_j (R_j c_j + p_j), then m_j
   double sh[16];
   double gout[96];                          // d_task_params of the instance
   double tout[48];                          // d_ee_target [15], d_prev_ee_target [15], d_trunk_target, d_prev_trunk_target, d_com_target, d_com_target_vel
 };
 struct __attribute__((aligned(16))) GSmemP { GInst I[4]; };
-
-// Entry k of the staged inputs; an input the configuration does not read is 0 and is never loaded
-__device__ __forceinline__ double grad_input(const WbcTickIn& in, const size_t b, const int k, const unsigned eemask, const bool trunk, const bool com,
-                                             const bool pu) {
-  if (k < GI_TR) {
-    const int kk = (k < GI_EEP) ? k : k - GI_EEP, e = kk / 3;
-    if (!((eemask >> e) & 1u)) return 0.0;
-    return (k < GI_EEP) ? in.ee_target[b * 15 + kk] : in.prev_ee_target[b * 15 + kk];
-  }
-  if (k < GI_CT) return trunk ? pk_trunk_input(in, (int)b, k - GI_TR) : 0.0;
-  if (k < GI_CV) return com ? in.com_target[b * 3 + (k - GI_CT)] : 0.0;
-  if (k < GI_PU) return com ? in.com_target_vel[b * 3 + (k - GI_CV)] : 0.0;
-  if (k < GI_PU + NV) return pu ? in.posture_u[b * NV + (k - GI_PU)] : 0.0;
-  return 0.0;
-}
+static_assert(sizeof(GInst) == 6656 && offsetof(GInst, wt) == 3072 && offsetof(GInst, tin) == 3840 && offsetof(GInst, mcw) == 4608 &&
+              offsetof(GInst, sh) == 5376 && offsetof(GInst, gout) == 5504 && offsetof(GInst, tout) == 6272, "the instance's LDS record");
 
 template <bool ROT>   // ROT: rotated joint placements in the batch (wbc_k_sim3p.hip)
 __global__ void __launch_bounds__(64) wbc_grad_kernel(const GradArgs A, const DevModel* __restrict__ models, const WbcConfig* __restrict__ cfgs,
                                                       const DevPlan* __restrict__ plans) {
   __shared__ GSmemP SP;
-  const int lane = threadIdx.x, r = lane >> 4, s = lane & 15, rbase = lane & 48;
-  GInst& U = SP.I[r];
-  const int b_raw = 4 * blockIdx.x + r;
-  const bool valid = b_raw < A.B;
-  const size_t b = valid ? b_raw : A.B - 1;
-  int mid = 0;
-  if (A.in.model_id) { mid = A.in.model_id[b]; mid = mid < 0 ? 0 : (mid >= A.n_models ? A.n_models - 1 : mid); }
+  const QtLane T(A.B);
+  const int s = T.s; const size_t b = T.b;
+  GInst& U = SP.I[T.r];
+  const int mid = qt_model_index(A.in.model_id, b, A.n_models);
   const DevModel& M = models[mid];
   const WbcConfig& cfg = cfgs[mid];
   const DevPlan& P = plans[mid];
@@ -87,89 +61,29 @@ __global__ void __launch_bounds__(64) wbc_grad_kernel(const GradArgs A, const De
   const int st = A.status ? A.status[b] : 0, cst = A.cert_status ? A.cert_status[b] : 0;
   DevPlan::PkJoint fkn = P.q_fk[0][s];
   const int scq0 = P.q_scq[(2 + s) & 31], scq1 = P.q_scq[(18 + s) & 31];
-  const int cj0 = M.col_joint[h0 ? d0 : 0], cl0 = M.col_lin[h0 ? d0 : 0], ca0 = M.col_ang[h0 ? d0 : 0];
-  const int cj1 = M.col_joint[h1 ? d1 : 0], cl1 = M.col_lin[h1 ? d1 : 0], ca1 = M.col_ang[h1 ? d1 : 0];
+  const QtDof Dc(M, s, nv);                                         // ... and where their columns come from
   const unsigned sub0 = h0 ? M.col_subtree[d0] : 0u, sub1 = h1 ? M.col_subtree[d1] : 0u;
   const int j1 = 16 + s;                                            // bodies of this lane: joints s (>= 1) and 16 + s
   const bool hb0 = s >= 1 && s < nj, hb1 = j1 < nj;
   const DevPlan::QJnt m0 = P.q_jm[hb0 ? s : 1], m1 = P.q_jm[hb1 ? j1 : 1];
   bool bad = (s < nq && !is_finite(q0)) || (16 + s < nq && !is_finite(q1)) || !is_finite(xd0) || !is_finite(xd1) || !is_finite(ud0) ||
              !is_finite(ud1);
-  {
-    const double* cw = &cfg.ee_W[0][0];
-    const double* rw = A.tp ? reinterpret_cast<const double*>(A.tp + b) : cw;
+  bad = qt_stage_task_image(U.wt, U.tin, A.in, A.tp, cfg, b, s, eemask, t_trunk, t_com, pu_read, inv_dt) || bad;
 #pragma unroll
-    for (int i = 0; i < 6; ++i) {
-      const int k = s + 16 * i;
-      const double v = (k < WBC_TASK_PARAMS_DOUBLES) ? rw[k] : 0.0;
-      bad = bad || !is_finite(v);
-      U.wt[k] = v;
-      U.gout[k] = 0.0;
-    }
+  for (int i = 0; i < 6; ++i) U.gout[s + 16 * i] = 0.0;
 #pragma unroll
-    for (int i = 0; i < 5; ++i) {
-      const int k = s + 16 * i;
-      const double v = grad_input(A.in, b, k, eemask, t_trunk, t_com, pu_read);
-      bad = bad || !is_finite(v);
-      U.tin[k] = v;
-    }
-    const double om = (eemask >> ((s < 15 ? s : 0) / 3) & 1u) ? pk_ee_omega(A.in, (int)b, s, inv_dt) : 0.0;   // calcTargetVelEE3's feed-forward, one component per lane
-    bad = bad || !is_finite(om);
-    U.tin[GI_OM + s] = om;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) U.tout[s + 16 * i] = 0.0;
-  }
-  U.q[s] = q0; U.q[16 + s] = q1;
-  WSYNC();
-  const double* const qv = U.q;
-  double* const oMi = U.oMi;
+  for (int i = 0; i < 3; ++i) U.tout[s + 16 * i] = 0.0;
+  qt_fk<ROT>(U.K, q0, q1, scq0, scq1, M, P, fkn, s);
+  const double* const qv = U.K.q;
+  const double* const oMi = U.K.oMi;
   const double* const wt = U.wt;
   const double* const tin = U.tin;
-  pk_fk_seed(oMi, U.sc, qv, scq0, scq1, s);
-  WSYNC();
-  pk_fk_sweep<ROT>(oMi, U.sc, qv, M, P.q_fk, fkn, s);               // pin.forwardKinematics over every joint, level by level
   // ---- WORLD Jacobian columns of the lane's two DoF (computeJointJacobians: linear part at the world origin, angular part)
-  double l0[3] = {0.0, 0.0, 0.0}, a0[3] = {0.0, 0.0, 0.0}, l1[3] = {0.0, 0.0, 0.0}, a1[3] = {0.0, 0.0, 0.0};
-  if (h0) pk_jac_col(oMi, cj0, cl0, ca0, l0, a0);
-  if (h1) pk_jac_col(oMi, cj1, cl1, ca1, l1, a1);
-  // ---- the trunk frame and calcTargetVelTrunk2 (Robot_Wrapper4.py:948-1015), bug-compatible as pk_trunk_target_vel: vel [6], the literal qe [3]
-  double tvel[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, tqe[3] = {0.0, 0.0, 0.0}, ptr[3] = {0.0, 0.0, 0.0};
-  if (t_trunk) {
-    const double* Pt = oMi + 12 * M.frame_joint[WBC_FR_TRUNK];
-    const double f0 = M.frame_p[WBC_FR_TRUNK][0], f1 = M.frame_p[WBC_FR_TRUNK][1], f2 = M.frame_p[WBC_FR_TRUNK][2];
-    double Rtr[9], fq[4], rq[4], Rs[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      ptr[i] = Pt[9 + i] + Pt[i] * f0 + Pt[3 + i] * f1 + Pt[6 + i] * f2;
-#pragma unroll
-      for (int j = 0; j < 3; ++j) Rtr[3 * i + j] = Pt[3 * j + i];
-    }
-    R_to_quat(Rtr, fq);
-    const double* xt = tin + GI_TR;
-    const double* xp = tin + GI_TR + 3;
-    const double* er = tin + GI_TR + 6;
-    const SinCos t = sincos_cw(s < 3 ? er[s < 3 ? s : 0] : 0.5 * er[(s < 6 ? s : 3) - 3]);   // reference angles and their halves, one per lane
-    if (s < 6) { U.sh[2 * s] = t.s; U.sh[2 * s + 1] = t.c; }
-    WSYNC();
-    const double* sh = U.sh;
-    euler_to_R(sh[0], sh[1], sh[2], sh[3], sh[4], sh[5], Rs);
-    const double qx[4] = {sh[6], 0, 0, sh[7]}, qy[4] = {0, sh[8], 0, sh[9]}, qz[4] = {0, 0, sh[10], sh[11]};
-    double tq[4];
-    quat_mul(qy, qx, tq);
-    quat_mul(qz, tq, rq);
-    tqe[0] = fq[3] * rq[0] - fq[0] * rq[3] + fq[1] * rq[2] - fq[2] * rq[1];   // :974
-    tqe[1] = fq[3] * rq[1] - fq[1] * rq[3] - fq[0] * rq[2] + fq[2] * rq[0];   // :975
-    tqe[2] = fq[3] * rq[2] - fq[3] * rq[2] + fq[0] * rq[1] - fq[1] * rq[0];   // :976 (sic)
-    double D[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) D[i] = (Rs[i] - tin[GI_TR + 9 + i]) * inv_dt;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) tvel[i] = (xt[i] - xp[i]) * inv_dt + wt[WT_TG + i] * ((xt[i] - ptr[i]) * inv_dt);
-    // skew = D Rs (R*, not R*^T: :984); omega = (S[2][1], S[0][2], S[1][0]) + K qe
-    tvel[3] = (D[6] * Rs[1] + D[7] * Rs[4] + D[8] * Rs[7]) + wt[WT_TG + 3] * tqe[0];
-    tvel[4] = (D[0] * Rs[2] + D[1] * Rs[5] + D[2] * Rs[8]) + wt[WT_TG + 4] * tqe[1];
-    tvel[5] = (D[3] * Rs[0] + D[4] * Rs[3] + D[5] * Rs[6]) + wt[WT_TG + 5] * tqe[2];
-  }
+  double l0[3], a0[3], l1[3], a1[3];
+  qt_jac_cols(oMi, Dc, l0, a0, l1, a1);
+  // ---- the trunk frame and calcTargetVelTrunk2 (qt_trunk_target): vel [6], the literal qe [3]
+  double tvel[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, tqe[3] = {0.0, 0.0, 0.0}, ptr[3] = {0.0, 0.0, 0.0}, fq[4], rq[4];
+  if (t_trunk) qt_trunk_target(oMi, M, tin, wt, U.sh, inv_dt, s, true, ptr, fq, rq, tqe, tvel);
   // ---- Cartesian blocks: EE 0..4 (LOCAL_WORLD_ALIGNED rows, endEffectorA2 :474-484) and the trunk (WORLD rows, trunkA :487-490)
 #pragma unroll 1
   for (int f = 0; f < WBC_NEE + 1; ++f) {
@@ -185,11 +99,8 @@ __global__ void __launch_bounds__(64) wbc_grad_kernel(const GradArgs A, const De
       jx[c] = rsum16(fma(l0[c], x0, l1[c] * x1)); jx[3 + c] = rsum16(fma(a0[c], x0, a1[c] * x1));
       ju[c] = rsum16(fma(l0[c], u0, l1[c] * u1)); ju[3 + c] = rsum16(fma(a0[c], u0, a1[c] * u1));
     }
-    const double* Pj = oMi + 12 * M.frame_joint[fr];
-    const double f0 = M.frame_p[fr][0], f1 = M.frame_p[fr][1], f2 = M.frame_p[fr][2];
     double pf[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) pf[i] = Pj[9 + i] + Pj[i] * f0 + Pj[3 + i] * f1 + Pj[6 + i] * f2;
+    qt_frame_origin(oMi, M, fr, pf);
     if (ee) {                                                        // reference point at the frame origin: lin + ang x p
       double cx[3], cu[3];
       cross3(jx + 3, pf, cx); cross3(ju + 3, pf, cu);
@@ -197,23 +108,16 @@ __global__ void __launch_bounds__(64) wbc_grad_kernel(const GradArgs A, const De
       for (int i = 0; i < 3; ++i) { jx[i] += cx[i]; ju[i] += cu[i]; }
     }
     const int oW = ee ? WT_W + 6 * f : WT_TW, ow = ee ? WT_w + f : WT_Tw, oG = ee ? WT_G + 6 * f : WT_TG;
-    const double* xt = ee ? tin + GI_EE + 3 * f : tin + GI_TR;
-    const double* xp = ee ? tin + GI_EEP + 3 * f : tin + GI_TR + 3;
+    const double* xt = ee ? tin + TI_EE + 3 * f : tin + TI_TR;
     const double w = wt[ow];
-    double vel[6];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      vel[i] = ee ? (xt[i] - xp[i]) * inv_dt + wt[oG + i] * ((xt[i] - pf[i]) * inv_dt) : tvel[i];   // calcTargetVelEE3 :1063, :1070
-      vel[3 + i] = ee ? tin[GI_OM + 3 * f + i] : tvel[3 + i];
-    }
     double dw = 0.0;
 #pragma unroll
     for (int k = 0; k < 6; ++k) {
-      const double W = wt[oW + k], c = W * w;
-      const double sv = c * ju[k], rho = fma(w, vel[k], -(c * jx[k]));
-      const double t = fma(rho, ju[k], -(sv * jx[k]));
+      const QtRow R = qt_task_row(wt, tin, tvel, pf, ee, f, k, w, jx[k], ju[k], inv_dt);
+      const double W = wt[oW + k], sv = R.sv;
+      const double t = fma(R.rho, ju[k], -(sv * jx[k]));
       const double dvel = w * sv;
-      dw += fma(W, t, sv * vel[k]);
+      dw += fma(W, t, sv * R.vel);
       if (s == 0) {
         U.gout[oW + k] = w * t;
         if (k < 3) {
@@ -230,7 +134,7 @@ __global__ void __launch_bounds__(64) wbc_grad_kernel(const GradArgs A, const De
   // ---- CoM block (Robot_Wrapper2 comJacobian :600-603, cartesianTargetCoM :661-668): column d of Jcom is (m_sub lin_d + ang_d x mc_sub) / M over
   // the sub-tree of the DoF's joint
   if (t_com) {
-    {
+    {                                                                // (qt_body_mass_table's text: through the helper this kernel takes four SGPRs more)
       const double* Pa = oMi + 12 * (hb0 ? s : 1);
       const double* Pb = oMi + 12 * (hb1 ? j1 : 1);
 #pragma unroll
@@ -255,15 +159,12 @@ __global__ void __launch_bounds__(64) wbc_grad_kernel(const GradArgs A, const De
     }
     double c0[3], c1[3];                                             // M x column d of Jcom
     {
-      double mc[3] = {0.0, 0.0, 0.0}, ms = 0.0, cr[3];
-      unsigned mask = sub0 & 0x00FFFFFEu;
-      while (mask) { const int j = __ffs((int)mask) - 1; mask &= mask - 1; mc[0] += U.mcw[4 * j]; mc[1] += U.mcw[4 * j + 1]; mc[2] += U.mcw[4 * j + 2]; ms += U.mcw[4 * j + 3]; }
+      double mc[3], ms, cr[3];
+      qt_subtree_mass(U.mcw, sub0 & 0x00FFFFFEu, mc, ms);
       cross3(a0, mc, cr);
 #pragma unroll
       for (int i = 0; i < 3; ++i) c0[i] = fma(ms, l0[i], cr[i]);
-      mc[0] = mc[1] = mc[2] = 0.0; ms = 0.0;
-      mask = sub1 & 0x00FFFFFEu;
-      while (mask) { const int j = __ffs((int)mask) - 1; mask &= mask - 1; mc[0] += U.mcw[4 * j]; mc[1] += U.mcw[4 * j + 1]; mc[2] += U.mcw[4 * j + 2]; ms += U.mcw[4 * j + 3]; }
+      qt_subtree_mass(U.mcw, sub1 & 0x00FFFFFEu, mc, ms);
       cross3(a1, mc, cr);
 #pragma unroll
       for (int i = 0; i < 3; ++i) c1[i] = fma(ms, l1[i], cr[i]);
@@ -272,7 +173,7 @@ __global__ void __launch_bounds__(64) wbc_grad_kernel(const GradArgs A, const De
     for (int k = 0; k < 3; ++k) {
       const double jx = rsum16(fma(c0[k], xd0, c1[k] * xd1)) / cm, ju = rsum16(fma(c0[k], ud0, c1[k] * ud1)) / cm;
       const double W = wt[WT_CW + k], g = wt[WT_CG + k];
-      const double e = tin[GI_CT + k] - com[k], bv = tin[GI_CV + k] + g * e;
+      const double e = tin[TI_CT + k] - com[k], bv = tin[TI_CV + k] + g * e;
       const double sv = W * ju, rho = fma(-W, jx, bv);
       if (s == 0) {
         U.gout[WT_CW + k] = fma(rho, ju, -(sv * jx));
@@ -292,7 +193,7 @@ __global__ void __launch_bounds__(64) wbc_grad_kernel(const GradArgs A, const De
       up0 = p0; up1 = p1;
       if (t_joint >= WBC_JOINT_MANI) {
         if (pu_static) { up0 = ((P.post_zero >> d0) & 1u) ? 0.0 : p0; up1 = ((P.post_zero >> (d1 & 31)) & 1u) ? 0.0 : p1; }
-        else { up0 = tin[GI_PU + d0]; up1 = tin[GI_PU + (h1 ? d1 : 0)]; }
+        else { up0 = tin[TI_PU + d0]; up1 = tin[TI_PU + (h1 ? d1 : 0)]; }
       }
     }
     const double t0 = h0 ? d * (up0 - xd0) * ud0 : 0.0, t1 = h1 ? d * (up1 - xd1) * ud1 : 0.0;
@@ -308,9 +209,8 @@ __global__ void __launch_bounds__(64) wbc_grad_kernel(const GradArgs A, const De
   for (int i = 0; i < 6; ++i) { go[i] = U.gout[s + 16 * i]; obad = obad || !is_finite(go[i]); }
 #pragma unroll
   for (int i = 0; i < 3; ++i) { to[i] = U.tout[s + 16 * i]; obad = obad || !is_finite(to[i]); }
-  const bool nonfin = ((__ballot(bad || obad) >> rbase) & 0xFFFFull) != 0ull;
-  const int gs = st != 0 ? GRAD_UNSOLVED : (cst != 0 ? GRAD_CERT : (nonfin ? GRAD_NONFINITE : GRAD_OK));
-  if (!valid) return;
+  const int gs = qt_grad_status(st, cst, bad || obad, T.rbase);
+  if (!T.valid) return;
   const bool zero = gs != GRAD_OK;
   if (A.out.d_task_params) {
 #pragma unroll

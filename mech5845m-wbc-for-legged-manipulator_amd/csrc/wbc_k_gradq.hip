@@ -6,29 +6,21 @@
 // keeps ONE table per instance — the spatial velocity of every body under x and under u — and no second-order tensor. Per frame the rows'
 // coefficients fold into four uniform vectors: aW, bW [6] on the WORLD derivative under u and under x (LOCAL_WORLD_ALIGNED rows fold in
 // through p_f), E [3] on d p_f / d delta_k = l_k + a_k x p_f, Ea [3] on a_k; lane s then adds the terms of its DoF s and 16 + s.
-// wbc_grad_kernel's shape: four instances per wavefront (lane = 16 r + s), FK over the whole-tree schedule DevPlan.q_fk, sums over DoF by
-// DPP row butterflies. Reads its inputs and the tables; writes nothing but its outputs, rows [0, B) only.
+// The whole-tree shape (wbc_qtree.h): four instances per wavefront (lane = 16 r + s), FK over the whole-tree schedule DevPlan.q_fk, sums over
+// DoF by DPP row butterflies. The staged task image, the trunk target, the row terms and the exit rule are wbc_qtree.h's, as wbc_k_grad.hip's. Reads its inputs and the tables; writes nothing but its outputs, rows [0, B) only.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "wbc_packed.h"
 #include "wbc_grad.h"
 #include "wbc_gradq.h"
+#include "wbc_qtree.h"
 
 namespace wbc {
 
-// tin: the staged task inputs of an instance (wbc_k_grad.hip's layout)
-constexpr int QI_EE = 0, QI_EEP = 15, QI_TR = 30, QI_CT = 48, QI_CV = 51, QI_OM = 80, QI_N = 96;
-constexpr int QT_TW = 65, QT_Tw = 71, QT_TG = 72, QT_JW = 84;   // trunk_W, trunk_w, trunk_gain, joint_w inside the weights image
-static_assert(offsetof(WbcTaskParams, trunk_W) == QT_TW * sizeof(double) && offsetof(WbcTaskParams, trunk_w) == QT_Tw * sizeof(double) &&
-              offsetof(WbcTaskParams, trunk_gain) == QT_TG * sizeof(double) && offsetof(WbcTaskParams, joint_w) == QT_JW * sizeof(double),
-              "the weights image is WbcTaskParams, double for double");
-
 struct __attribute__((aligned(16))) QInst {
-  double oMi[24 * 12];
-  double q[32];
-  double sc[64];
+  QtKin K;
   double wt[96];                            // the 85 weights and gains (WbcTaskParams layout), rest zero
-  double tin[QI_N];
+  double tin[TI_N];
   double mcw[24 * 4];                       // body j: m_j (R_j c_j + p_j), then m_j
   double VT[24 * 12];                       // body j: its WORLD spatial velocity under x (lin, ang), then under u
   double sh[16];
@@ -38,19 +30,9 @@ struct __attribute__((aligned(16))) QInst {
   double craw[32];                          // raw coordinate c: the coefficient of d q_raw[c] / d delta
 };
 struct __attribute__((aligned(16))) QSmemP { QInst I[4]; };
-
-// Entry k of the staged inputs; an input the configuration does not read is 0 and is never loaded
-__device__ __forceinline__ double gq_input(const WbcTickIn& in, const size_t b, const int k, const unsigned eemask, const bool trunk, const bool com) {
-  if (k < QI_TR) {
-    const int kk = (k < QI_EEP) ? k : k - QI_EEP, e = kk / 3;
-    if (!((eemask >> e) & 1u)) return 0.0;
-    return (k < QI_EEP) ? in.ee_target[b * 15 + kk] : in.prev_ee_target[b * 15 + kk];
-  }
-  if (k < QI_CT) return trunk ? pk_trunk_input(in, (int)b, k - QI_TR) : 0.0;
-  if (k < QI_CV) return com ? in.com_target[b * 3 + (k - QI_CT)] : 0.0;
-  if (k < QI_CV + 3) return com ? in.com_target_vel[b * 3 + (k - QI_CV)] : 0.0;
-  return 0.0;
-}
+static_assert(sizeof(QInst) == 8960 && offsetof(QInst, wt) == 3072 && offsetof(QInst, tin) == 3840 && offsetof(QInst, mcw) == 4608 &&
+              offsetof(QInst, VT) == 5376 && offsetof(QInst, sh) == 7680 && offsetof(QInst, wy) == 7808 && offsetof(QInst, dmp) == 8192 &&
+              offsetof(QInst, pst) == 8448 && offsetof(QInst, craw) == 8704, "the instance's LDS record");
 
 // (dL/d lower, dL/d upper) of a constraint with value val, sides lo / hi and sensitivity w: wbc_qp_certificate's rule
 __device__ __forceinline__ void gq_share(const double w, const double val, const double lo, const double hi, const int bits, const bool have_ws,
@@ -150,13 +132,10 @@ template <bool ROT>   // ROT: rotated joint placements in the batch (wbc_k_sim3p
 __global__ void __launch_bounds__(64) wbc_gradq_kernel(const GradQArgs A, const DevModel* __restrict__ models, const WbcConfig* __restrict__ cfgs,
                                                        const DevPlan* __restrict__ plans) {
   __shared__ QSmemP SP;
-  const int lane = threadIdx.x, r = lane >> 4, s = lane & 15, rbase = lane & 48;
-  QInst& U = SP.I[r];
-  const int b_raw = 4 * blockIdx.x + r;
-  const bool valid = b_raw < A.B;
-  const size_t b = valid ? b_raw : A.B - 1;
-  int mid = 0;
-  if (A.in.model_id) { mid = A.in.model_id[b]; mid = mid < 0 ? 0 : (mid >= A.n_models ? A.n_models - 1 : mid); }
+  const QtLane T(A.B);
+  const int s = T.s; const size_t b = T.b;
+  QInst& U = SP.I[T.r];
+  const int mid = qt_model_index(A.in.model_id, b, A.n_models);
   const DevModel& M = models[mid];
   const WbcConfig& cfg = cfgs[mid];
   const DevPlan& P = plans[mid];
@@ -202,25 +181,8 @@ __global__ void __launch_bounds__(64) wbc_gradq_kernel(const GradQArgs A, const 
   bool bad = (s < nq && !is_finite(q0)) || (16 + s < nq && !is_finite(q1)) || !is_finite(xd0) || !is_finite(xd1) || !is_finite(ud0) ||
              !is_finite(ud1) || !is_finite(wb0) || !is_finite(wb1) || !is_finite(bc[0]) || !is_finite(bc[1]) || !is_finite(bc[2]) || !is_finite(bc[3]);
   {
-    const double* cw = &cfg.ee_W[0][0];
-    const double* rw = A.tp ? reinterpret_cast<const double*>(A.tp + b) : cw;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-      const int k = s + 16 * i;
-      const double v = (k < WBC_TASK_PARAMS_DOUBLES) ? rw[k] : 0.0;
-      bad = bad || !is_finite(v);
-      U.wt[k] = v;
-    }
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-      const int k = s + 16 * i;
-      const double v = gq_input(A.in, b, k, eemask, t_trunk, t_com);
-      bad = bad || !is_finite(v);
-      U.tin[k] = v;
-    }
-    const double om = (eemask >> ((s < 15 ? s : 0) / 3) & 1u) ? pk_ee_omega(A.in, (int)b, s, inv_dt) : 0.0;   // calcTargetVelEE3's feed-forward, one component per lane
-    bad = bad || !is_finite(om);
-    U.tin[QI_OM + s] = om;
+    const bool ibad = qt_stage_task_image(U.wt, U.tin, A.in, A.tp, cfg, b, s, eemask, t_trunk, t_com, false, inv_dt);
+    bad = bad || ibad;
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
       const int k = s + 16 * i, kk = (k < 24) ? k : k - 24;
@@ -231,18 +193,14 @@ __global__ void __launch_bounds__(64) wbc_gradq_kernel(const GradQArgs A, const 
 #pragma unroll
     for (int i = 0; i < 18; ++i) U.VT[s + 16 * i] = 0.0;
   }
-  U.q[s] = q0; U.q[16 + s] = q1;
-  WSYNC();
-  const double* const qv = U.q;
-  double* const oMi = U.oMi;
+  qt_fk<ROT>(U.K, q0, q1, scq0, scq1, M, P, fkn, s);
+  const double* const qv = U.K.q;
+  double* const oMi = U.K.oMi;
   const double* const wt = U.wt;
   const double* const tin = U.tin;
   const double* const wr = U.wy;
   const double* const yr = U.wy + 24;
-  pk_fk_seed(oMi, U.sc, qv, scq0, scq1, s);
-  WSYNC();
-  pk_fk_sweep<ROT>(oMi, U.sc, qv, M, P.q_fk, fkn, s);               // pin.forwardKinematics over every joint, level by level
-  // ---- WORLD Jacobian columns of the lane's two DoF (computeJointJacobians: linear part at the world origin, angular part)
+  // ---- WORLD Jacobian columns of the lane's two DoF; not QtDof / qt_jac_cols: with the record this kernel takes four VGPRs more
   double l0[3] = {0.0, 0.0, 0.0}, a0[3] = {0.0, 0.0, 0.0}, l1[3] = {0.0, 0.0, 0.0}, a1[3] = {0.0, 0.0, 0.0};
   if (h0) pk_jac_col(oMi, cj0, cl0, ca0, l0, a0);
   if (h1) pk_jac_col(oMi, cj1, cl1, ca1, l1, a1);
@@ -295,19 +253,7 @@ __global__ void __launch_bounds__(64) wbc_gradq_kernel(const GradQArgs A, const 
     }
   }
   // ---- the bodies' mass-weighted centres (CoM rows)
-  if (any_com) {
-    const double* Pa = oMi + 12 * (hb0 ? s : 1);
-    const double* Pb = oMi + 12 * (hb1 ? j1 : 1);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      const double ca = Pa[9 + i] + Pa[i] * m0.c0 + Pa[3 + i] * m0.c1 + Pa[6 + i] * m0.c2;
-      const double cb = Pb[9 + i] + Pb[i] * m1.c0 + Pb[3 + i] * m1.c1 + Pb[6 + i] * m1.c2;
-      U.mcw[4 * s + i] = hb0 ? m0.m * ca : 0.0;
-      if (j1 < 24) U.mcw[4 * j1 + i] = hb1 ? m1.m * cb : 0.0;
-    }
-    U.mcw[4 * s + 3] = hb0 ? m0.m : 0.0;
-    if (j1 < 24) U.mcw[4 * j1 + 3] = hb1 ? m1.m : 0.0;
-  }
+  if (any_com) qt_body_mass_table(U.mcw, oMi, m0, m1, hb0, hb1, s);
   WSYNC();
   const double* const VT = U.VT;
   const double* const Vk0 = VT + 12 * cj0;
@@ -331,57 +277,21 @@ __global__ void __launch_bounds__(64) wbc_gradq_kernel(const GradQArgs A, const 
       juc[i] = rsum16((hb0 ? fma(ma[3], Va[6 + i], cua[i]) : 0.0) + ((two && hb1) ? fma(mb[3], Vb[6 + i], cub[i]) : 0.0)) / cm;
     }
   }
-  // ---- the trunk frame; calcTargetVelTrunk2 (Robot_Wrapper4.py:948-1015) as wbc_k_grad.hip states it: vel [6], and fq, rq for the literal qe
-  double tvel[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, ptr[3] = {0.0, 0.0, 0.0}, fq[4] = {0.0, 0.0, 0.0, 1.0}, rq[4] = {0.0, 0.0, 0.0, 1.0};
+  // ---- the trunk frame; calcTargetVelTrunk2 (qt_trunk_target): vel [6], and fq, rq for the literal qe. A trunk box alone needs the origin.
+  double tvel[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, ptr[3] = {0.0, 0.0, 0.0}, fq[4] = {0.0, 0.0, 0.0, 1.0}, rq[4] = {0.0, 0.0, 0.0, 1.0}, tqe[3];
   const double* const Pt = oMi + 12 * M.frame_joint[WBC_FR_TRUNK];   // R column-major: R(i, j) = Pt[3 j + i]
-  if (t_trunk || c_trunk) {
-    const double f0 = M.frame_p[WBC_FR_TRUNK][0], f1 = M.frame_p[WBC_FR_TRUNK][1], f2 = M.frame_p[WBC_FR_TRUNK][2];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) ptr[i] = Pt[9 + i] + Pt[i] * f0 + Pt[3 + i] * f1 + Pt[6 + i] * f2;
-  }
-  if (t_trunk) {
-    double Rtr[9], Rs[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) Rtr[3 * i + j] = Pt[3 * j + i];
-    R_to_quat(Rtr, fq);
-    const double* xt = tin + QI_TR;
-    const double* xp = tin + QI_TR + 3;
-    const double* er = tin + QI_TR + 6;
-    const SinCos t = sincos_cw(s < 3 ? er[s < 3 ? s : 0] : 0.5 * er[(s < 6 ? s : 3) - 3]);   // reference angles and their halves, one per lane
-    if (s < 6) { U.sh[2 * s] = t.s; U.sh[2 * s + 1] = t.c; }
-    WSYNC();
-    const double* sh = U.sh;
-    euler_to_R(sh[0], sh[1], sh[2], sh[3], sh[4], sh[5], Rs);
-    const double qx[4] = {sh[6], 0, 0, sh[7]}, qy[4] = {0, sh[8], 0, sh[9]}, qz[4] = {0, 0, sh[10], sh[11]};
-    double tq[4];
-    quat_mul(qy, qx, tq);
-    quat_mul(qz, tq, rq);
-    const double tqe0 = fq[3] * rq[0] - fq[0] * rq[3] + fq[1] * rq[2] - fq[2] * rq[1];   // :974
-    const double tqe1 = fq[3] * rq[1] - fq[1] * rq[3] - fq[0] * rq[2] + fq[2] * rq[0];   // :975
-    const double tqe2 = fq[3] * rq[2] - fq[3] * rq[2] + fq[0] * rq[1] - fq[1] * rq[0];   // :976 (sic)
-    double D[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) D[i] = (Rs[i] - tin[QI_TR + 9 + i]) * inv_dt;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) tvel[i] = (xt[i] - xp[i]) * inv_dt + wt[QT_TG + i] * ((xt[i] - ptr[i]) * inv_dt);
-    tvel[3] = (D[6] * Rs[1] + D[7] * Rs[4] + D[8] * Rs[7]) + wt[QT_TG + 3] * tqe0;
-    tvel[4] = (D[0] * Rs[2] + D[1] * Rs[5] + D[2] * Rs[8]) + wt[QT_TG + 4] * tqe1;
-    tvel[5] = (D[3] * Rs[0] + D[4] * Rs[3] + D[5] * Rs[6]) + wt[QT_TG + 5] * tqe2;
-  }
+  if (t_trunk || c_trunk) qt_trunk_target(oMi, M, tin, wt, U.sh, inv_dt, s, t_trunk, ptr, fq, rq, tqe, tvel);
   // ---- which side each inequality row's w belongs to (the bounds recomputed from q), and d_trunk_box_center
   double cwl[2] = {0.0, 0.0}, cwu[2] = {0.0, 0.0}, twl[4] = {0.0, 0.0, 0.0, 0.0}, twu[4] = {0.0, 0.0, 0.0, 0.0};
   const double kc = cfg.com_box_scale * inv_dt, kt = cfg.trunk_box_scale * inv_dt;
   if (c_com) {
-    const double* Pa = oMi + 12 * M.frame_joint[WBC_FR_EE0 + 1];
-    const double* Pb = oMi + 12 * M.frame_joint[WBC_FR_EE0 + 2];
+    double pfl[3], prr[3];                                          // the FL and RR feet: x and y are read
+    qt_frame_origin(oMi, M, WBC_FR_EE0 + 1, pfl);
+    qt_frame_origin(oMi, M, WBC_FR_EE0 + 2, prr);
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      const double pfl = Pa[9 + i] + Pa[i] * M.frame_p[WBC_FR_EE0 + 1][0] + Pa[3 + i] * M.frame_p[WBC_FR_EE0 + 1][1] + Pa[6 + i] * M.frame_p[WBC_FR_EE0 + 1][2];
-      const double prr = Pb[9 + i] + Pb[i] * M.frame_p[WBC_FR_EE0 + 2][0] + Pb[3 + i] * M.frame_p[WBC_FR_EE0 + 2][1] + Pb[6 + i] * M.frame_p[WBC_FR_EE0 + 2][2];
-      gq_share(wr[i], jxc[i], ((prr - com[i]) * inv_dt) * cfg.com_box_scale, ((pfl - com[i]) * inv_dt) * cfg.com_box_scale, pk_ws_bits(ws1, i), have_ws,
-               cwl[i], cwu[i]);
+      gq_share(wr[i], jxc[i], ((prr[i] - com[i]) * inv_dt) * cfg.com_box_scale, ((pfl[i] - com[i]) * inv_dt) * cfg.com_box_scale, pk_ws_bits(ws1, i),
+               have_ws, cwl[i], cwu[i]);
     }
   }
   double tbc = 0.0;                                                 // d_trunk_box_center entry s < 4
@@ -414,15 +324,12 @@ __global__ void __launch_bounds__(64) wbc_gradq_kernel(const GradQArgs A, const 
     const unsigned sup = M.frame_support[fr];
     const bool on0 = h0 && ((sup >> d0) & 1u), on1 = h1 && ((sup >> (d1 & 31)) & 1u);
     const int fj = M.frame_joint[fr];
-    const double* Pj = oMi + 12 * fj;
     const double* Vf = VT + 12 * fj;
-    const double f0 = M.frame_p[fr][0], f1 = M.frame_p[fr][1], f2 = M.frame_p[fr][2];
     double pf[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) pf[i] = Pj[9 + i] + Pj[i] * f0 + Pj[3 + i] * f1 + Pj[6 + i] * f2;
+    qt_frame_origin(oMi, M, fr, pf);
     double aW[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, bW[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, E[3] = {0.0, 0.0, 0.0}, Ea[3] = {0.0, 0.0, 0.0};
     if (task) {
-      const int oW = ee ? WT_W + 6 * f : QT_TW, ow = ee ? WT_w + f : QT_Tw, oG = ee ? WT_G + 6 * f : QT_TG;
+      const int ow = ee ? WT_w + f : WT_Tw, oG = ee ? WT_G + 6 * f : WT_TG;
       const double w = wt[ow];
       double jx[6], ju[6];
 #pragma unroll
@@ -433,17 +340,12 @@ __global__ void __launch_bounds__(64) wbc_gradq_kernel(const GradQArgs A, const 
 #pragma unroll
         for (int i = 0; i < 3; ++i) { jx[i] += cx[i]; ju[i] += cu[i]; }
       }
-      const double* xt = tin + QI_EE + 3 * (ee ? f : 0);
-      const double* xp = tin + QI_EEP + 3 * (ee ? f : 0);
       double al[6], be[6], svv[6];
 #pragma unroll
       for (int k = 0; k < 6; ++k) {
-        double vel;
-        if (k < 3) vel = ee ? (xt[k] - xp[k]) * inv_dt + wt[oG + k] * ((xt[k] - pf[k]) * inv_dt) : tvel[k];   // calcTargetVelEE3 :1063, :1070
-        else vel = ee ? tin[QI_OM + 3 * (ee ? f : 0) + (k - 3)] : tvel[k];
-        const double c = wt[oW + k] * w;
-        const double sv = c * ju[k], rho = fma(w, vel, -(c * jx[k]));
-        al[k] = c * rho; be[k] = c * sv; svv[k] = sv;
+        const QtRow R = qt_task_row(wt, tin, tvel, pf, ee, f, k, w, jx[k], ju[k], inv_dt);
+        const double c = R.c, sv = R.sv;
+        al[k] = c * R.rho; be[k] = c * sv; svv[k] = sv;
         if (k < 3) E[k] -= sv * (w * wt[oG + k] * inv_dt);            // d b_k / d p_f
       }
       if (ee) {
@@ -502,7 +404,7 @@ __global__ void __launch_bounds__(64) wbc_gradq_kernel(const GradQArgs A, const 
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
         const double W = wt[WT_CW + k], g = wt[WT_CG + k];
-        const double bv = tin[QI_CV + k] + g * (tin[QI_CT + k] - com[k]);
+        const double bv = tin[TI_CV + k] + g * (tin[TI_CT + k] - com[k]);
         const double sv = W * juc[k], rho = fma(-W, jxc[k], bv);
         ac[k] = W * rho; bcf[k] = W * sv; Ec[k] = -(sv * g);
       }
@@ -529,7 +431,7 @@ __global__ void __launch_bounds__(64) wbc_gradq_kernel(const GradQArgs A, const 
       gq_share(wb1, xd1, lo, hi, pk_ws_bits(ws0, d1), have_ws, wl, wu);
       t1 = h1 ? wl * dl + wu * du : 0.0;
     }
-    const double dj = (t_joint == WBC_JOINT_PREV) ? (1.0 / nv) * wt[QT_JW] : 0.0;
+    const double dj = (t_joint == WBC_JOINT_PREV) ? (1.0 / nv) * wt[WT_JW] : 0.0;
     U.dmp[d0] = t0; U.dmp[d1] = t1;
     U.pst[d0] = h0 ? (dj * dj) * ud0 : 0.0; U.pst[d1] = h1 ? (dj * dj) * ud1 : 0.0;
     WSYNC();
@@ -563,9 +465,8 @@ __global__ void __launch_bounds__(64) wbc_gradq_kernel(const GradQArgs A, const 
   }
   // ---- out: zero rows for an unsolved / uncertified / non-finite instance; nothing non-finite leaves the instance
   const bool obad = !is_finite(res0) || !is_finite(res1) || !is_finite(tbc);
-  const bool nonfin = ((__ballot(bad || obad) >> rbase) & 0xFFFFull) != 0ull;
-  const int gs = st != 0 ? GRAD_UNSOLVED : (cst != 0 ? GRAD_CERT : (nonfin ? GRAD_NONFINITE : GRAD_OK));
-  if (!valid) return;
+  const int gs = qt_grad_status(st, cst, bad || obad, T.rbase);
+  if (!T.valid) return;
   const bool zero = gs != GRAD_OK;
   if (A.out.d_q) {
     A.out.d_q[b * NV + d0] = (zero || !h0) ? 0.0 : res0;

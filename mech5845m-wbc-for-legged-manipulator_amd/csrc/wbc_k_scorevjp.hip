@@ -2,7 +2,7 @@
 // where the sweep runs (include/wbc.h states the algebra). The sweep is wbc_rollout_vjp_tracks', kernel for kernel; in front
 // of every tick's step layer and between LINK and the track stage it launches one stage of
 //   wbc_scorevjp_kernel    four instances per wavefront (lane = 16 r + s)
-//     SEED    FK over the whole-tree schedule DevPlan.q_fk at q_(k+1) (wbc_slack_kernel's lane layout). Lane s < 6 owns frame s (0..4 the end
+//     SEED    FK over the whole-tree schedule DevPlan.q_fk at q_(k+1) (the whole-tree shape, wbc_qtree.h). Lane s < 6 owns frame s (0..4 the end
 //             effectors, 5 the trunk): position, d = position - target of tick k, e = sqrt((dx dx + dy dy) + dz dz),
 //                 c = ((2 g_sq + [k == K - 1] g_fin / e) + [k == err_max_tick] g_max / e) d          (the 1 / e terms: 0 where e == 0)
 //             and stash[b][s][:] <- -c (0 for an unscored frame). Lane s then owns DoF s and 16 + s: the WORLD Jacobian column (pk_jac_col)
@@ -20,18 +20,21 @@
 #include "wbc_grad.h"
 #include "wbc_scorevjp.h"
 
+#ifdef WBC_QTREE_H
+#error "wbc_qtree.h came in through an earlier include: qt_point would be contracted here; it must first be included behind the pragma below"
+#endif
 #pragma clang fp contract(off)
+#include "wbc_qtree.h"      // behind the pragma: its arithmetic (qt_point) is this unit's, uncontracted
 
 namespace wbc {
 
 struct __attribute__((aligned(16))) VInst {
-  double oMi[24 * 12];
-  double q[32];
-  double sc[64];
+  QtKin K;
   double pf[24];                            // the six frames' world positions (stride 4)
   double c[24];                             // their cotangents (stride 4; 0 for an unscored frame)
 };
 struct __attribute__((aligned(16))) VSmemP { VInst I[4]; };
+static_assert(sizeof(VInst) == 3456 && offsetof(VInst, pf) == 3072 && offsetof(VInst, c) == 3264, "the instance's LDS record");
 
 // this DoF's term: sum over the scored frames the column moves of (lin + ang x p_f) . c_f, the frames in increasing order
 __device__ __forceinline__ double sv_contract(const double* const pf, const double* const c, const DevModel& M, const int mask, const int d,
@@ -53,11 +56,10 @@ __device__ __forceinline__ double sv_contract(const double* const pf, const doub
 
 template <int STAGE, bool ROT>   // ROT: rotated joint placements in the batch (wbc_k_sim3p.hip); the TARGET stage has no kinematics
 __global__ void __launch_bounds__(64) wbc_scorevjp_kernel(const ScoreVjpArgs A) {
-  const int lane = threadIdx.x, r = lane >> 4, s = lane & 15, rbase = lane & 48;
-  const int b_raw = 4 * blockIdx.x + r;
+  const QtLane T(A.B); const int s = T.s;
   if (STAGE == SCOREVJP_TARGET) {
-    if (b_raw >= A.B) return;                                       // (no cross-lane traffic in this stage: a lane may leave)
-    const size_t b = (size_t)b_raw;
+    if (!T.valid) return;                                           // (no cross-lane traffic in this stage: a lane may leave)
+    const size_t b = (size_t)T.b_raw;
     if (A.worst[b] == GRAD_NONFINITE) return;                       // all-zero rows: LINK wrote them at k == 0, nothing is added
 #pragma unroll
     for (int pass = 0; pass < 2; ++pass) {
@@ -76,11 +78,9 @@ __global__ void __launch_bounds__(64) wbc_scorevjp_kernel(const ScoreVjpArgs A) 
   }
   // ---- SEED
   __shared__ VSmemP SP;
-  VInst& U = SP.I[r];
-  const bool valid = b_raw < A.B;
-  const size_t b = valid ? b_raw : A.B - 1, nB = (size_t)A.B;
-  int mid = 0;
-  if (A.model_id) { mid = A.model_id[b]; mid = mid < 0 ? 0 : (mid >= A.n_models ? A.n_models - 1 : mid); }
+  VInst& U = SP.I[T.r];
+  const size_t b = T.b, nB = (size_t)A.B;
+  const int mid = qt_model_index(A.model_id, b, A.n_models);
   const DevModel& M = A.models[mid];
   const DevPlan& P = A.plans[mid];
   const int nq = M.nq, nv = M.nv, mask = A.score_mask;
@@ -102,28 +102,19 @@ __global__ void __launch_bounds__(64) wbc_scorevjp_kernel(const ScoreVjpArgs A) 
   const int tk = (scored && A.g_max) ? A.err_max_tick[gi] : -1;
   const double* tg = (scored && f == WBC_TARGET_TRUNK) ? A.trunk_target + b * 3 : A.ee_target + b * 15 + 3 * f;   // the target tick k saw
   const double t0 = scored ? tg[0] : 0.0, t1 = scored ? tg[1] : 0.0, t2 = scored ? tg[2] : 0.0;
-  const int d0 = s, d1 = 16 + s;                                    // DoF of this lane
-  const bool h0 = d0 < nv, h1 = d1 < nv;
-  const int cj0 = M.col_joint[h0 ? d0 : 0], cl0 = M.col_lin[h0 ? d0 : 0], ca0 = M.col_ang[h0 ? d0 : 0];
-  const int cj1 = M.col_joint[h1 ? d1 : 0], cl1 = M.col_lin[h1 ? d1 : 0], ca1 = M.col_ang[h1 ? d1 : 0];
+  const QtDof Dc(M, s, nv);                                         // DoF of this lane
+  const int d0 = Dc.d0, d1 = Dc.d1; const bool h0 = Dc.h0, h1 = Dc.h1;
   const bool bad = lastk && ((s < nq && !is_finite(q0)) || (16 + s < nq && !is_finite(q1)) || !is_finite(gsq) || !is_finite(gfin) ||
                              !is_finite(gmax) || (gmax != 0.0 && (tk < 0 || tk >= A.K)));
-  const bool rowbad = ((__ballot(bad) >> rbase) & 0xFFFFull) != 0ull;
+  const bool rowbad = ((__ballot(bad) >> T.rbase) & 0xFFFFull) != 0ull;
   const bool dead = rowbad || A.worst[b] == GRAD_NONFINITE;
-  U.q[s] = q0; U.q[16 + s] = q1;
-  WSYNC();
-  const double* const qv = U.q;
-  double* const oMi = U.oMi;
-  pk_fk_seed(oMi, U.sc, qv, scq0, scq1, s);
-  WSYNC();
-  pk_fk_sweep<ROT>(oMi, U.sc, qv, M, P.q_fk, fkn, s);               // pin.forwardKinematics over every joint, level by level
+  qt_fk<ROT>(U.K, q0, q1, scq0, scq1, M, P, fkn, s);
+  const double* const oMi = U.K.oMi;
   // ---- the frame's position, d, e and c (wbc_traj_tick_kernel's expressions on the recomputed position)
   double cx = 0.0, cy = 0.0, cz = 0.0;
   {
     const double* Pj = oMi + 12 * fjoint;
-    const double px = ((Pj[9] + Pj[0] * f0) + Pj[3] * f1) + Pj[6] * f2;
-    const double py = ((Pj[10] + Pj[1] * f0) + Pj[4] * f1) + Pj[7] * f2;
-    const double pz = ((Pj[11] + Pj[2] * f0) + Pj[5] * f1) + Pj[8] * f2;
+    const double px = qt_point(Pj, f0, f1, f2, 0), py = qt_point(Pj, f0, f1, f2, 1), pz = qt_point(Pj, f0, f1, f2, 2);
     if (scored && !dead) {
       const double dx = px - t0, dy = py - t1, dz = pz - t2;
       const double e2 = (dx * dx + dy * dy) + dz * dz;
@@ -142,12 +133,11 @@ __global__ void __launch_bounds__(64) wbc_scorevjp_kernel(const ScoreVjpArgs A) 
   }
   WSYNC();
   // ---- WORLD Jacobian columns of the lane's two DoF, moved to each scored frame and contracted with its c
-  double l0[3] = {0.0, 0.0, 0.0}, a0[3] = {0.0, 0.0, 0.0}, l1[3] = {0.0, 0.0, 0.0}, a1[3] = {0.0, 0.0, 0.0};
-  if (h0) pk_jac_col(oMi, cj0, cl0, ca0, l0, a0);
-  if (h1) pk_jac_col(oMi, cj1, cl1, ca1, l1, a1);
+  double l0[3], a0[3], l1[3], a1[3];
+  qt_jac_cols(oMi, Dc, l0, a0, l1, a1);
   const double acc0 = h0 ? sv_contract(U.pf, U.c, M, mask, d0, l0, a0) : 0.0;
   const double acc1 = h1 ? sv_contract(U.pf, U.c, M, mask, d1, l1, a1) : 0.0;
-  if (!valid) return;
+  if (!T.valid) return;
   if (s < 6) {
     double* st = A.stash + b * 18 + 3 * s;
     const bool z = !scored || dead;

@@ -5,7 +5,7 @@
 //   2 trunk angles its three angle rows, the angles by the tick kernels' atan2 formula
 //   3 joint range  the model's own range of each free DoF's OWN joint (not the damper's index map)
 // Two kernels:
-//   wbc_slack_kernel         four instances per wavefront in wbc_update_packed_kernel's lane layout (lane = 16 r + s). FK over the whole-tree
+//   wbc_slack_kernel         the whole-tree shape (wbc_qtree.h): four instances per wavefront (lane = 16 r + s), FK over the whole-tree
 //                            schedule DevPlan.q_fk (the CoM needs every body). Writes the row (wbc_state_slack) and / or folds the tick into
 //                            the watch's accumulators (lanes s < 4 of a row, one family each): no second accumulation launch.
 //   wbc_slack_groups_kernel  once at the end: one wavefront per group of M consecutive instances, fixed-shape reduction (no atomics)
@@ -15,17 +15,17 @@
 #include <math.h>
 #include "wbc_packed.h"
 #include "wbc_slack.h"
+#include "wbc_qtree.h"
 
 namespace wbc {
 
 struct __attribute__((aligned(16))) SInst {
-  double oMi[24 * 12];
-  double q[32];
-  double sc[64];
+  QtKin K;
   double pf[12];                            // FL foot, RR foot, trunk frame: world positions (stride 4)
   double eul[4];                            // roll, pitch, yaw of the trunk rotation
 };
 struct __attribute__((aligned(16))) SSmemP { SInst I[4]; };
+static_assert(sizeof(SInst) == 3200 && offsetof(SInst, pf) == 3072 && offsetof(SInst, eul) == 3168, "the instance's LDS record");
 
 // (v, c) <- the smaller of (v, c) and (ov, oc): by value, a tie by the lower code — what a scan in increasing code order with a strict < gives
 __device__ __forceinline__ void slack_take(double& v, int& c, const double ov, const int oc) {
@@ -49,13 +49,10 @@ template <bool ROT>   // ROT: rotated joint placements in the batch (wbc_k_sim3p
 __global__ void __launch_bounds__(64) wbc_slack_kernel(const SlackArgs A, const DevModel* __restrict__ models, const WbcConfig* __restrict__ cfgs,
                                                        const DevPlan* __restrict__ plans) {
   __shared__ SSmemP SP;
-  const int lane = threadIdx.x, r = lane >> 4, s = lane & 15, rbase = lane & 48;
-  SInst& U = SP.I[r];
-  const int b_raw = 4 * blockIdx.x + r;
-  const bool valid = b_raw < A.B;
-  const size_t b = valid ? b_raw : A.B - 1;
-  int mid = 0;
-  if (A.model_id) { mid = A.model_id[b]; mid = mid < 0 ? 0 : (mid >= A.n_models ? A.n_models - 1 : mid); }
+  const QtLane T(A.B);
+  const int s = T.s; const size_t b = T.b;
+  SInst& U = SP.I[T.r];
+  const int mid = qt_model_index(A.model_id, b, A.n_models);
   const DevModel& M = models[mid];
   const WbcConfig& cfg = cfgs[mid];
   const DevPlan& P = plans[mid];
@@ -86,14 +83,10 @@ __global__ void __launch_bounds__(64) wbc_slack_kernel(const SlackArgs A, const 
   const double lo0 = Lm.lo[hd0 ? s : 6], hi0 = Lm.hi[hd0 ? s : 6], lo1 = Lm.lo[hd1 ? j1 : 6], hi1 = Lm.hi[hd1 ? j1 : 6];
   const double z_frac = cfg.trunk_box_z_frac, box_ang = cfg.trunk_box_ang;
   const bool qbad = (s < nq && !is_finite(q0)) || (16 + s < nq && !is_finite(q1));
-  const bool rowbad = ((__ballot(qbad) >> rbase) & 0xFFFFull) != 0ull;
-  U.q[s] = q0; U.q[16 + s] = q1;
-  WSYNC();
-  const double* const qv = U.q;
-  double* const oMi = U.oMi;
-  pk_fk_seed(oMi, U.sc, qv, scq0, scq1, s);
-  WSYNC();
-  pk_fk_sweep<ROT>(oMi, U.sc, qv, M, P.q_fk, fkn, s);               // pin.forwardKinematics over every joint, level by level
+  const bool rowbad = ((__ballot(qbad) >> T.rbase) & 0xFFFFull) != 0ull;
+  qt_fk<ROT>(U.K, q0, q1, scq0, scq1, M, P, fkn, s);
+  const double* const qv = U.K.q;
+  const double* const oMi = U.K.oMi;
   // ---- frame origins, the trunk's Euler angles (one atan2 per row on lanes 0..2, the tick kernels' formula: wbc_common.h, P6)
   {
     const double* Pj = oMi + 12 * fjoint;
@@ -104,11 +97,12 @@ __global__ void __launch_bounds__(64) wbc_slack_kernel(const SlackArgs A, const 
     const double eul = atan2(ay, ax);
     if (s < 3) {
 #pragma unroll
-      for (int rr = 0; rr < 3; ++rr) U.pf[4 * s + rr] = Pj[9 + rr] + Pj[rr] * f0 + Pj[3 + rr] * f1 + Pj[6 + rr] * f2;
+      for (int rr = 0; rr < 3; ++rr) U.pf[4 * s + rr] = qt_point(Pj, f0, f1, f2, rr);
       U.eul[s] = eul;
     }
   }
   // ---- data.com[0], x and y: lane s sums m_j (R_j c_j + p_j) over joints s and 16 + s in that order, then the row butterfly and one division each
+  // (qt_body_mass_table's centres, but two components summed per lane in this order: spelled out, and not through qt_point)
   double cx = 0.0, cy = 0.0, cm = 0.0;
   {
     const double* Pa = oMi + 12 * (hb0 ? s : 1);
@@ -159,7 +153,7 @@ __global__ void __launch_bounds__(64) wbc_slack_kernel(const SlackArgs A, const 
   if (bad2) { sl[2] = qnan; wh[2] = -1; }
 #pragma unroll
   for (int i = 0; i < SLACK_NC; ++i) if (i < 4 ? rowbad : (i < 6 ? bad1 : bad2)) comp[i] = qnan;
-  if (!valid) return;
+  if (!T.valid) return;
   // ---- the row (wbc_state_slack): component s on lane s < 12, family s on lane s < 4
   double cs = comp[0];
 #pragma unroll

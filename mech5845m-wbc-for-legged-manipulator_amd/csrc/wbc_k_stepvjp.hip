@@ -11,7 +11,8 @@
 //   Q = V / 2 + c1 (W V + V W + W V W) + c2 (W W V + V W W - 3 W V W) + c3 (W V W W + W W V W),   W = omega x, V = v x,
 // with a = sin t / t, b = (1 - cos t) / t^2, c1 = (1 - a) / t^2, c2 = (1 / 2 - b) / t^2, c3 = (3 c1 - b) / (2 t^2), t = |omega| dt. Below t = 1 all
 // five come from their power series in t^2 (sv_coef): the closed forms cancel like eps / t^2 (c1) and eps / t^4 (c2, c3).
-// wbc_slack_kernel's shape: four instances per wavefront (lane = 16 r + s), FK over the whole-tree schedule DevPlan.q_fk. No Jacobian is
+// The whole-tree shape (wbc_qtree.h): four instances per wavefront (lane = 16 r + s), FK over the whole-tree schedule DevPlan.q_fk (its own
+// sequence: q is assembled in LDS and the seed's rotation replaced, so not qt_fk). No Jacobian is
 // stored: lane s forms the transposed foot point-Jacobian product of its DoF s and 16 + s from the joint axes and origins in LDS. Reads its
 // inputs and the tables; writes nothing but its outputs, rows [0, B) only.
 #include <hip/hip_runtime.h>
@@ -19,6 +20,7 @@
 #include "wbc_packed.h"
 #include "wbc_grad.h"
 #include "wbc_stepvjp.h"
+#include "wbc_qtree.h"
 
 namespace wbc {
 
@@ -98,13 +100,10 @@ __device__ __forceinline__ double sv_jt(const double* const oMi, const int joint
 template <bool ROT>   // ROT: rotated joint placements in the batch (wbc_k_sim3p.hip)
 __global__ void __launch_bounds__(64) wbc_stepvjp_kernel(const StepVjpArgs A, const DevModel* __restrict__ models, const DevPlan* __restrict__ plans) {
   __shared__ VSmemP SP;
-  const int lane = threadIdx.x, r = lane >> 4, s = lane & 15, rbase = lane & 48;
-  VInst& U = SP.I[r];
-  const int b_raw = 4 * blockIdx.x + r;
-  const bool valid = b_raw < A.B;
-  const size_t b = valid ? b_raw : A.B - 1;
-  int mid = 0;
-  if (A.model_id) { mid = A.model_id[b]; mid = mid < 0 ? 0 : (mid >= A.n_models ? A.n_models - 1 : mid); }
+  const QtLane T(A.B);
+  const int s = T.s; const size_t b = T.b;
+  VInst& U = SP.I[T.r];
+  const int mid = qt_model_index(A.model_id, b, A.n_models);
   const DevModel& M = models[mid];
   const DevPlan& P = plans[mid];
   const int nq = M.nq, nv = M.nv;
@@ -122,8 +121,7 @@ __global__ void __launch_bounds__(64) wbc_stepvjp_kernel(const StepVjpArgs A, co
   const double im = (have_imu && s >= 3 && s < 7) ? A.imu[b * 4 + (s - 3)] : 0.0;
   DevPlan::PkJoint fkn = P.q_fk[0][s];
   const int scq0 = P.q_scq[(2 + s) & 31], scq1 = P.q_scq[(18 + s) & 31];
-  const int cj0 = M.col_joint[h0 ? d0 : 0], cl0 = M.col_lin[h0 ? d0 : 0], ca0 = M.col_ang[h0 ? d0 : 0];
-  const int cj1 = M.col_joint[h1 ? d1 : 0], cl1 = M.col_lin[h1 ? d1 : 0], ca1 = M.col_ang[h1 ? d1 : 0];
+  const QtDof Dc(M, s, nv);                                         // ... and where their columns come from
   const int cq0 = M.col_q[h0 ? d0 : 6], cq1 = M.col_q[h1 ? d1 : 6];
   unsigned sup0 = 0u, sup1 = 0u;                                    // bit e: the DoF moves foot frame e
 #pragma unroll
@@ -181,7 +179,7 @@ __global__ void __launch_bounds__(64) wbc_stepvjp_kernel(const StepVjpArgs A, co
     if (s < 5) {
       const double* Pj = oMi + 12 * fjoint;
 #pragma unroll
-      for (int rr = 0; rr < 3; ++rr) U.pf[4 * s + rr] = Pj[9 + rr] + Pj[rr] * f0 + Pj[3 + rr] * f1 + Pj[6 + rr] * f2;
+      for (int rr = 0; rr < 3; ++rr) U.pf[4 * s + rr] = qt_point(Pj, f0, f1, f2, rr);
     }
     WSYNC();
     const double* P1 = oMi + 12;                                    // the base rotation R_b, column-major: R_b(i, j) = P1[3 j + i]
@@ -202,8 +200,8 @@ __global__ void __launch_bounds__(64) wbc_stepvjp_kernel(const StepVjpArgs A, co
     cross3(BPA, gp, c1); cross3(rbar, Rtg, c2);
 #pragma unroll
     for (int i = 0; i < 3; ++i) { cp[i] = 0.0; cf[i] = have_imu ? 0.0 : gphi[i] - c1[i] - c2[i]; }
-    if (h0 && d0 >= 6) ct0 = gd0 - sv_jt(oMi, cj0, cl0, ca0, sup0, pf, gp);
-    if (h1) ct1 = gd1 - sv_jt(oMi, cj1, cl1, ca1, sup1, pf, gp);
+    if (h0 && d0 >= 6) ct0 = gd0 - sv_jt(oMi, Dc.cj0, Dc.cl0, Dc.ca0, sup0, pf, gp);
+    if (h1) ct1 = gd1 - sv_jt(oMi, Dc.cj1, Dc.cl1, Dc.ca1, sup1, pf, gp);
   }
   // ---- the integrate part on the base block
   double ql[3], qa[3], xl[3], xa[3];
@@ -239,8 +237,8 @@ __global__ void __launch_bounds__(64) wbc_stepvjp_kernel(const StepVjpArgs A, co
   const double rf = (running && fe < 4) ? ((fi == 0) ? Rg[0] : (fi == 1) ? Rg[1] : Rg[2]) / 4 : 0.0;
   // ---- out: zero rows for a non-finite instance; nothing non-finite leaves the instance
   const bool obad = (h0 && (!is_finite(rq0) || !is_finite(rx0))) || (h1 && (!is_finite(rq1) || !is_finite(rx1))) || !is_finite(rf);
-  const bool zero = ((__ballot(bad || obad) >> rbase) & 0xFFFFull) != 0ull;
-  if (!valid) return;
+  const bool zero = ((__ballot(bad || obad) >> T.rbase) & 0xFFFFull) != 0ull;
+  if (!T.valid) return;
   if (A.out.d_q) {
     A.out.d_q[b * NV + d0] = (zero || !h0) ? 0.0 : rq0;
     if (d1 < NV) A.out.d_q[b * NV + d1] = (zero || !h1) ? 0.0 : rq1;

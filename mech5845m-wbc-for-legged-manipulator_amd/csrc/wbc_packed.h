@@ -502,7 +502,12 @@ __device__ __forceinline__ void wo_finish(WaveOrder* wo, const WoGeom& wg, const
 // shared by the packed orth and box kernels: FK levels of their whole-tree schedule (DevPlan.q_fk) and the staged weights image wt [96]
 constexpr int QLEV = 6;
 static_assert(offsetof(WbcConfig, joint_w) - offsetof(WbcConfig, ee_W) == 84 * sizeof(double), "ee_W [30] ee_w [5] ee_gain [30] trunk [13] com_W [3] com_gain [3] joint_w");
-constexpr int WT_W = 0, WT_w = 30, WT_G = 35, WT_CW = 78, WT_CG = 81;   // offsets inside wt
+// offsets inside wt: ee_W, ee_w, ee_gain, trunk_W, trunk_w, trunk_gain, com_W, com_gain, joint_w
+constexpr int WT_W = 0, WT_w = 30, WT_G = 35, WT_TW = 65, WT_Tw = 71, WT_TG = 72, WT_CW = 78, WT_CG = 81, WT_JW = 84;
+#define WT_AT(field, k) (offsetof(WbcTaskParams, field) == (k) * sizeof(double))
+static_assert(WT_AT(ee_W, WT_W) && WT_AT(ee_w, WT_w) && WT_AT(ee_gain, WT_G) && WT_AT(trunk_W, WT_TW) && WT_AT(trunk_w, WT_Tw) && WT_AT(trunk_gain, WT_TG) &&
+              WT_AT(com_W, WT_CW) && WT_AT(com_gain, WT_CG) && WT_AT(joint_w, WT_JW), "the weights image is WbcTaskParams, double for double");
+#undef WT_AT
 
 // ---- the packed kinematics (tick kernels: sim3p over DevPlan.pk_fk, orthp / boxp over DevPlan.q_fk; wbc_update_packed_kernel over pk_fk).
 // oMi [joint][12]: R column-major then p; sc: sin / cos of joint j at 2 j; qv: the staged configuration.

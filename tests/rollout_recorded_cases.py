@@ -97,3 +97,28 @@ def run_cases(bt, z, conv=lambda a: a):
         got = call()
         stats = np.array([bt.stat(s) for s in STATS], np.int64)
         yield case, {k: (v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)) for k, v in got.items()}, stats
+
+
+# ---------------------------------------------------------------------------------------------- wbc_state_slack, rotated placements
+# No case above launches wbc_slack_kernel<ROT> (a1_wx200 has no rotated joint placement). One stand-alone wbc_state_slack on laikago_vx300 at
+# B = 5: one full four-instance wave and one with three padding rows. Its arrays are "b5__*" in the same file.
+B5, B5_MODEL, B5_CONFIG = 5, "laikago_vx300", "everything"
+
+
+def b5_inputs():
+    """-> dict(q [5, 27], box [5, 4]); made once by the tool and stored with the outputs, as make_inputs'"""
+    model = wbc_model.load_model(B5_MODEL)
+    d = common.tick_inputs(model, common.config(B5_CONFIG, model), B5, seed=11)
+    return dict(q=np.ascontiguousarray(d["q"]), box=np.ascontiguousarray(d["trunk_box_center"]))
+
+
+def run_b5(z, conv=lambda a: a):
+    """-> wbc_state_slack's outputs (slack, which, components) as numpy arrays, on a handle of its own"""
+    model = wbc_model.load_model(B5_MODEL)
+    bt = WbcBatch(model, MAX_BATCH)
+    bt.configure(common.config(B5_CONFIG, model))
+    try:
+        o = bt.state_slack(conv(np.ascontiguousarray(z["q"])), conv(np.ascontiguousarray(z["box"])), want_components=True)
+        return {k: (v.detach().cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)) for k, v in o.items()}
+    finally:
+        bt.close()

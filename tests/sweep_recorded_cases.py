@@ -286,6 +286,44 @@ def run_cases(bt, name, z, conv=lambda a: a):
         yield call, {k: _np(x) for k, x in got.items() if x is not None}, stats
 
 
+# ---------------------------------------------------------------------------------------------- the score seed without rotated placements
+# Both configurations hold laikago_vx300, so every call above launches wbc_scorevjp_kernel<SEED, ROT>. One record and one scored sweep on
+# a1_wx200 alone at B = 5 (one full four-instance wave and one with three padding rows) launch <SEED, no ROT>. The inputs are `rows`' own: its
+# a1_wx200 instances (model_id 0), repeated to five rows; nothing new is stored for them. The outputs are "b5__*" in the same file.
+B5 = 5
+
+
+def b5_rows(raw):
+    """-> the five rows of configuration `rows` (inputs_of's dict) the case runs on"""
+    own = np.flatnonzero(raw["d_model_id"] == 0)
+    assert len(own) >= 2 and BAD not in own
+    return own[np.arange(B5) % len(own)]
+
+
+def run_b5(z, conv=lambda a: a):
+    """-> (outputs of the record and of the scored sweep as numpy arrays, last_scorevjp_variant) on a handle of its own"""
+    raw = inputs_of(z, "rows")
+    idx = b5_rows(raw)
+    cut = lambda v: conv(np.ascontiguousarray(v[idx]))      # noqa: E731
+    d = {k[2:]: cut(v) for k, v in raw.items() if k.startswith("d_") and k != "d_model_id"}
+    tracks = []
+    for t in tracks_of(raw, "six"):
+        tracks.append({k: (cut(v) if isinstance(v, np.ndarray) else v) for k, v in t.items()})
+    ns = len(SIX_SCORE)
+    m = gr.tgp._model("a1_wx200")
+    bt = gr.tgp._handle([m], [gr.common.config(CONFIGS["rows"][0], m)], MAX_BATCH, {})
+    try:
+        rec, tape = bt.rollout_record(d, DT, K, task_params=cut(raw["task_params"]), tracks=tracks, score=SIX_SCORE)
+        sd = dict(mask=SIX_SCORE, q_final=rec["q"], err_max_tick=rec["err_max_tick"])
+        for k, name in (("g_sq", "sq_sum"), ("g_fin", "final"), ("g_max", "max")):
+            sd["g_err_" + name] = conv(np.ascontiguousarray(raw[k][:ns][:, idx]))
+        g = _flat(bt.rollout_vjp(tape, score_seed=sd, g_q_final=cut(raw["g_q_final"])))
+        out = dict({"rec_" + k: v for k, v in rec.items()}, **g)
+        return {k: _np(v) for k, v in out.items() if v is not None}, int(bt.stat("last_scorevjp_variant"))
+    finally:
+        bt.close()
+
+
 # ---------------------------------------------------------------------------------------------- refusals
 def run_refusals(bt, z):
     """Yields (name, code, message, ok) of every refused call of the sweep's own checks, on the `rows` handle bt: the tracks call's checks as

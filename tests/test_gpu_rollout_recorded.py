@@ -43,7 +43,7 @@ def test_the_record_holds_what_the_cases_claim(golden):
 @pytest.mark.parametrize("mem", ["host", "device"])
 def test_every_rollout_gives_the_recorded_bits(golden, mem):
     z = golden
-    inputs = {k[4:]: v for k, v in z.items() if k.startswith("in__")}
+    inputs = {k[4:]: v for k, v in z.items() if k.startswith("in__")}      # (the "b5__*" arrays are the test's below)
     conv = (lambda a: a) if mem == "host" else (lambda a: torch.from_numpy(a).cuda())
     bt = rc.handle()
     wrong = []
@@ -63,3 +63,17 @@ def test_every_rollout_gives_the_recorded_bits(golden, mem):
     bt.close()
     print("%s: differing from the record: %s" % (mem, wrong or "nothing"))
     assert not wrong, wrong
+
+
+@pytest.mark.parametrize("mem", ["host", "device"])
+def test_state_slack_with_rotated_placements_gives_the_recorded_bits(golden, mem):
+    """wbc_slack_kernel<ROT>, which no roll-out case launches: laikago_vx300 at B = 5 (a full wave and one with three padding rows), held to the
+    bits recorded from the library before the whole-tree kernels shared a header"""
+    z = golden
+    inputs = {k[len("b5__in__"):]: v for k, v in z.items() if k.startswith("b5__in__")}
+    want = {k[len("b5__out__"):]: v for k, v in z.items() if k.startswith("b5__out__")}
+    assert inputs["q"].shape == (rc.B5, 27) and set(want) == {"slack", "which", "components"} and np.isfinite(want["slack"]).all()
+    conv = (lambda a: a) if mem == "host" else (lambda a: torch.from_numpy(a).cuda())
+    got = rc.run_b5(inputs, conv)
+    wrong = [k for k in want if got[k].dtype != want[k].dtype or got[k].shape != want[k].shape or got[k].tobytes() != want[k].tobytes()]
+    assert set(got) == set(want) and not wrong, wrong

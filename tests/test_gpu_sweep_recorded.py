@@ -98,3 +98,19 @@ def test_every_refusal_keeps_its_code_and_its_text(golden):
     print("refusals differing from the record: %s" % (wrong or "nothing"))
     assert seen == {k for k in z if k.startswith("refusal__")}
     assert not wrong, wrong
+
+
+@pytest.mark.parametrize("mem", ["host", "device"])
+def test_the_score_seed_without_rotated_placements_gives_the_recorded_bits(golden, mem):
+    """wbc_scorevjp_kernel<SEED, no ROT>, which no call of CALLS launches: a1_wx200 alone at B = 5 (a full wave and one with three padding
+    rows), held to the bits recorded from the library before the whole-tree kernels shared a header"""
+    z = golden
+    inputs = {k[4:]: v for k, v in z.items() if k.startswith("in__")}
+    want = {k[len("b5__out__"):]: v for k, v in z.items() if k.startswith("b5__out__")}
+    assert want["d_q0"].shape == (sr.B5, 26) and want["d_q0"].any() and not want["grad_status"].any()
+    rot = [int(z["stats__rows__six_score_state"][2]), int(z["b5__variant"])]
+    assert rot[0] >= 0 and rot[1] >= 0 and rot[0] != rot[1], rot      # another variant than the configurations' calls
+    conv = (lambda a: a) if mem == "host" else (lambda a: torch.from_numpy(a).cuda())
+    got, variant = sr.run_b5(inputs, conv)
+    wrong = [k for k in want if k not in got or got[k].dtype != want[k].dtype or got[k].shape != want[k].shape or got[k].tobytes() != want[k].tobytes()]
+    assert set(got) == set(want) and variant == int(z["b5__variant"]) and not wrong, (wrong, variant)

@@ -7,6 +7,10 @@ wrapper of that commit), with this tool and tests/rollout_recorded_cases.py copi
 
     python __graft_entry__.py build && python tools/make_rollout_golden.py [output.npz]
 
+    python tools/make_rollout_golden.py --b5 [file.npz]: adds the "b5__*" arrays of rollout_recorded_cases.run_b5 (wbc_state_slack with
+    rotated placements, B = 5) to an existing file and leaves every other array as it is. The committed ones were made that way with the
+    library of the commit before the whole-tree kernels' shared header.
+
 Asserted while recording, so that the cases exercise what they claim to: the bad row is counted; an instance of the trajectory call passes a
 milestone inside its ticks; a watched family goes negative or has its minimum after tick 0; the calls without a watch and the repeated plain
 call give the bits of the calls they repeat; the file stays far below tests/golden/packed_qp_shared.npz."""
@@ -23,8 +27,26 @@ import rollout_recorded_cases as rc  # noqa: E402
 import wbc_workload  # noqa: E402
 
 
+def record_b5():
+    inputs = rc.b5_inputs()
+    o = rc.run_b5(inputs)
+    assert np.isfinite(o["slack"]).all() and o["slack"].shape == (rc.B5, 4) and o["components"].shape == (rc.B5, 12), o
+    assert all(rc.run_b5(inputs)[k].tobytes() == v.tobytes() for k, v in o.items()), "two runs differ"
+    z = {"b5__in__" + k: v for k, v in inputs.items()}
+    z.update({"b5__out__" + k: v for k, v in o.items()})
+    return z
+
+
 def main():
-    out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "tests", "golden", "rollout_recorded.npz")
+    args = [a for a in sys.argv[1:] if a != "--b5"]
+    out = args[0] if args else os.path.join(ROOT, "tests", "golden", "rollout_recorded.npz")
+    if "--b5" in sys.argv[1:]:
+        old = np.load(out)
+        z = {k: old[k] for k in old.files if not k.startswith("b5__")}
+        z.update(record_b5())
+        np.savez_compressed(out, **z)
+        print("added %s to %s" % (sorted(k for k in z if k.startswith("b5__")), out))
+        return
     inputs = rc.make_inputs()
     z = {"in__" + k: v for k, v in inputs.items()}
     # the trajectory call's milestone: the segment of tick K_TRAJ - 1 is not the first one
@@ -55,6 +77,7 @@ def main():
             assert moved, "%s: no watched family goes negative or has its minimum after tick 0" % case
             print("%-18s neg_ticks\n%s\nslack_min_tick\n%s" % (case, o["neg_ticks"], o["slack_min_tick"]))
     bt.close()
+    z.update(record_b5())
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     np.savez_compressed(out, **z)
     size = os.path.getsize(out)

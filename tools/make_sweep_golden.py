@@ -98,9 +98,31 @@ def record(seed=7):
     return z
 
 
+def record_b5(inputs):
+    """the "b5__*" arrays: sweep_recorded_cases.run_b5, the score seed without rotated placements at B = 5"""
+    o, variant = sr.run_b5(inputs)
+    o2, variant2 = sr.run_b5(inputs)
+    claim(variant == variant2 and variant >= 0 and set(o) == set(o2) and all(o[k].tobytes() == o2[k].tobytes() for k in o), "b5: two runs differ")
+    claim(not o["grad_status"].any() and o["d_q0"].any() and o["d_q0"].shape == (sr.B5, 26), ("b5", o["grad_status"].tolist()))
+    print("b5      last_scorevjp_variant %s keys %s" % (hex(variant), " ".join(sorted(o))))
+    z = {"b5__out__" + k: v for k, v in o.items()}
+    z["b5__variant"] = np.int64(variant)
+    return z
+
+
 def main():
-    out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "tests", "golden", "sweep_recorded.npz")
+    args = [a for a in sys.argv[1:] if a != "--b5"]
+    out = args[0] if args else os.path.join(ROOT, "tests", "golden", "sweep_recorded.npz")
+    if "--b5" in sys.argv[1:]:      # add the "b5__*" arrays to an existing file, every other array as it is
+        old = np.load(out)
+        z = {k: old[k] for k in old.files if not k.startswith("b5__")}
+        z.update(record_b5({k[4:]: v for k, v in z.items() if k.startswith("in__")}))
+        np.savez_compressed(out, **z)
+        print("added %d b5 arrays to %s" % (sum(k.startswith("b5__") for k in z), out))
+        assert not FAILED, FAILED
+        return
     z = record()
+    z.update(record_b5({k[4:]: v for k, v in z.items() if k.startswith("in__")}))
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     np.savez_compressed(out, **z)
     size = os.path.getsize(out)
