@@ -603,8 +603,9 @@ typedef struct WbcRolloutGrad {       /* all optional; an output left NULL is no
  * have their size a call allocates nothing, and with device buffers both calls can be captured into a HIP graph.
  * WBC_E_ARG, naming the field, before any launch: no seed; what wbc_rollout_record refuses; an output whose inputs the configuration does
  * not read (the rules of wbc_tick_vjp and wbc_tick_vjp_state; d_*_target_step as d_*_target). WBC_E_UNSUPPORTED as wbc_rollout_record.
- * Not offered: hold_ticks, the one-track trajectory call and the watch roll-outs (roll-outs along tracks: wbc_rollout_record_tracks /
- * wbc_rollout_vjp_tracks below), checkpoint-and-recompute (the tape holds every tick).
+ * Not offered: hold_ticks, the one-track trajectory call (roll-outs along tracks: wbc_rollout_record_tracks / wbc_rollout_vjp_tracks
+ * below; the watch roll-outs: wbc_rollout_record_watch / wbc_rollout_vjp_watched further below), checkpoint-and-recompute (the tape holds
+ * every tick).
  * Statistic "last_rollvjp_variant": the row of csrc/wbc_k_rollvjp.hip's table the last call launched last (key of the stage: 0 BEGIN, 1 ADDV,
  * 2 LINK), -1 before the first; wbc_variant_count("rollvjp") == 3. */
 int wbc_rollout_vjp(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r, const void* tape,
@@ -751,8 +752,8 @@ int wbc_rollout_tracks(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskPa
  * track (without one trunk_target_step stays allowed and d_trunk_target_step is wbc_rollout_vjp's); d_tangents on a LINEAR track or a
  * HERMITE track with tangents == NULL; tracks_out NULL; a tracks_out->track[j] member set for j >= n_tracks; what wbc_rollout_tracks and
  * what wbc_rollout_vjp refuse.
- * Not offered: hold ticks, the watch, gradients with respect to n_points, checkpoint-and-recompute (the scores as a loss:
- * wbc_rollout_vjp_scored below).
+ * Not offered: hold ticks, gradients with respect to n_points, checkpoint-and-recompute (the scores as a loss: wbc_rollout_vjp_scored
+ * below; the watch as a loss: wbc_rollout_vjp_watched further below).
  * Neither call allocates once the workspaces have their size; with device buffers both can be captured into a HIP graph.
  * Statistic "last_trackvjp_variant": the row of csrc/wbc_k_trackvjp.hip's table the last call launched last (key of the stage: 0 BEGIN,
  * 1 TICK), -1 before the first; wbc_variant_count("trackvjp") == 2. */
@@ -799,7 +800,7 @@ int wbc_rollout_tracks_grad_sizes(int32_t* sizeof_track_grad, int32_t* sizeof_tr
  * err_max_tick; q_final NULL; score_mask 0 or with bits >= 6; bit 5 without in0->trunk_target; r->imu not NULL (the state then discards the
  * orientation the scored position was formed with); whatever wbc_rollout_vjp_tracks refuses — except that `seed` may be NULL or empty here:
  * with both seeds the gradients are those of the summed loss. WBC_E_UNSUPPORTED as wbc_rollout_record (the packed whole-tree schedule).
- * Not offered: an IMU quaternion fed back under a score seed, hold ticks, the watch as a loss, wbc_rollout_traj's one-track summary, the
+ * Not offered: an IMU quaternion fed back under a score seed, hold ticks, wbc_rollout_traj's one-track summary, the
  * group scores (group RMS is an expression of err_sq_sum), gradients with respect to n_points, checkpoint-and-recompute.
  * The workspace lives in the handle with wbc_rollout_vjp's: no allocation after the first call of a size; with device buffers the call
  * can be captured into a HIP graph.
@@ -874,6 +875,90 @@ typedef struct WbcSlackWatch {
 int wbc_rollout_watch(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
                       const WbcTracks* tracks /* may be NULL */, const WbcTrackScores* scores /* may be NULL; needs tracks */,
                       const WbcSlackWatch* watch /* may be NULL */, int mem, void* stream);
+
+/* ------------------------------------------------------------------ constraint slack as a loss: dL/d(q, trunk_box_center) at a state
+ * wbc_state_slack_vjp is the cotangent of wbc_state_slack's outputs: with g_slack = dL/d slack [B][4] and g_components = dL/d components
+ * [B][12] (either may be NULL, not both) it returns dL/dq in tangent coordinates at q (wbc_tick_vjp_state's convention: base DoF in the
+ * base-local frame, joint DoF the identity) and dL/d trunk_box_center. One kernel launch (csrc/wbc_k_slackvjp.hip, the STATE stage), no
+ * allocation and no memset: with device buffers the call can be captured into a HIP graph.
+ * WHERE A FAMILY'S COTANGENT GOES. Component i of families 0..2 gets gamma_i = g_components[i] + g_slack[f], the second term only where i is
+ * family f's `which`: the component the forward's scan selects (increasing code order, strict <: the lowest code wins a tie). The kernel runs
+ * the forward's own evaluation (one set of inline functions, csrc/wbc_slack.h), so the selection is wbc_state_slack's bit for bit. At a tie
+ * the slack is not differentiable and what is returned is a SUBGRADIENT: the gradient of the selected component. The joint family has no
+ * exposed components: g_slack[3] goes to the DoF and side of its code (code -1: nowhere).
+ * THE COTANGENTS, with the components as stated under wbc_state_slack:
+ *     on p_FL (gamma1, gamma3, 0)     on p_RR (-gamma0, -gamma2, 0)     on com (gamma0 - gamma1, gamma2 - gamma3, 0)
+ *     on the trunk frame's z  gamma4 - gamma5           on trunk_box_center[0]  -(1 - z_frac) gamma4 + (1 + z_frac) gamma5
+ *     on angle a  c_e[a] = gamma(6 + 2a) - gamma(7 + 2a)  on trunk_box_center[1 + a]  -c_e[a]
+ *     joint range: d_q[d] += +gamma for the lower side (even code), -gamma for the upper side
+ * To the state, per DoF d with l, a its WORLD joint Jacobian column (linear part at the world origin, angular part), the frames' supports as
+ * the model states them, mc and ms the sums of m_j c_j and m_j over the bodies of d's sub-tree and M the total mass:
+ *     d_q[d] = [FL has d] (l + a x p_FL) . c_FL + [RR has d] (l + a x p_RR) . c_RR + ((ms l + a x mc) / M) . c_com
+ *            + [trunk has d] ((l + a x p_T)_z (gamma4 - gamma5) + a . sum_a c_e[a] N_a(R)) + the joint term
+ * N_a: d angle_a = N_a . omega under dR = [omega]x R, the three atan2 forms of wbc_tick_vjp_state's trunk box.
+ * EXACT ZEROS AND BAD ROWS. Columns >= nv of d_q are 0; rows >= B are never written. A row is bad if q holds a non-finite entry among the
+ * model's nq, if a cotangent of the row is not finite, or if a trunk_box_center entry is not finite while its family (1: entry 0; 2: entries
+ * 1..3) carries a non-zero cotangent (g_slack[f] or one of the family's g_components). A bad row gets all-zero d_q and d_trunk_box_center
+ * rows and WBC_GRAD_NONFINITE; the other rows keep their bits. `which` is no gradient: on every row it is wbc_state_slack's, bad or not.
+ * WBC_E_UNSUPPORTED as wbc_state_slack (the packed whole-tree schedule). WBC_E_ARG, naming the field: q NULL, out NULL, both g arrays NULL,
+ * model_id NULL with several models; trunk_box_center NULL together with a non-zero cotangent on family 1 or 2 — with host arrays; with
+ * device arrays the cotangents are not read on the host, a NULL box counts as non-finite entries and the row is a bad row.
+ * Statistic "last_slackvjp_variant": the row of csrc/wbc_k_slackvjp.hip's table the last call (this one or wbc_rollout_vjp_watched) launched
+ * (key of (STAGE, ROT): STAGE 0 STATE, 1 SEED), -1 before the first; wbc_variant_count("slackvjp") == 4. */
+typedef struct WbcSlackGrad {        /* all optional */
+  double*  d_q;                 /* [B][26] tangent coordinates at q; columns >= nv are 0 */
+  double*  d_trunk_box_center;  /* [B][4] */
+  int32_t* which;               /* [B][4] the component each family's cotangent went to: wbc_state_slack's `which`, bit for bit */
+  int32_t* grad_status;         /* [B] WBC_GRAD_OK / WBC_GRAD_NONFINITE */
+} WbcSlackGrad;
+int wbc_state_slack_vjp(WbcBatch* b, int B, const double* q, const double* trunk_box_center, const int32_t* model_id,
+                        const double* g_slack /* [B][4], may be NULL */, const double* g_components /* [B][12], may be NULL */, int mem,
+                        const WbcSlackGrad* out, void* stream);
+int wbc_slack_grad_sizes(int32_t* sizeof_grad); /* ctypes layout self-check */
+
+/* ------------------------------------------------------------------ the watch as a loss: dL/d(slack_min, slack_final, trace) through a roll-out
+ * wbc_rollout_record_watch is wbc_rollout_watch with the record extension behind the watch (tracks optional; scores needs tracks; watch
+ * required): every output is wbc_rollout_watch's bit for bit on the same inputs, the tape wbc_rollout_record's / _record_tracks'. It refuses
+ * what those calls refuse; hold_ticks is refused (a recorded roll-out has none).
+ * wbc_rollout_vjp_watched is the reverse sweep seeded (also, or alone) with the cotangents of what the watch returned. On tick k the
+ * cotangent of watched family f is
+ *     gamma_f = g_trace[k] + [k == K - 1] g_slack_final + [k == slack_min_tick] g_slack_min
+ * (g_trace: dL/d(WbcSlackWatch.trace), the hook for any per-tick penalty, hinge or barrier), applied through wbc_state_slack_vjp's algebra
+ * at q_(k+1) — the tape's q of tick k + 1, q_final behind the last tick — with in0->trunk_box_center as the box: ONE launch of the SEED
+ * stage in front of tick k's step layer, behind the score seed's SEED stage where both are given (the order is fixed: the bits depend on
+ * it). g(q_(k+1)) += the state term, the sweep's trunk_box_center accumulator += the box term; an exact zero is never added (all-zero
+ * cotangents beside a state seed give wbc_rollout_vjp's / _tracks' bits). The selected component is recomputed at the taped state by the
+ * forward's own evaluation; at a tie it is a subgradient as under wbc_state_slack_vjp.
+ * The slack is evaluated at the state the update kernel wrote, which is exactly the taped state: an IMU quaternion fed back is allowed here
+ * (the step layer zeroes the orientation part as it already does); a call with both a score seed and an IMU keeps the score's refusal.
+ * d_trunk_box_center keeps the sweep's rule (it needs the trunk constraint) and then also holds the watch's box term. wbc_rollout_vjp,
+ * _tracks and _scored launch what they launched and return the same bits.
+ * PER-INSTANCE FAULTS: a seeded cotangent of the tick that is not finite (found at that tick), a non-finite q_final entry (among the
+ * model's nq), a slack_min_tick outside [0, K) while g_slack_min != 0, a non-finite trunk_box_center entry of a family with a non-zero
+ * cotangent: the instance gets all-zero rows in every output and WBC_GRAD_NONFINITE, like a layer that reports it mid-sweep.
+ * WBC_E_ARG, naming the field, before any launch: watch NULL; no g array; g_slack_min without slack_min_tick; q_final NULL; mask 0 or with
+ * bits >= 4; family 1 or 2 without in0->trunk_box_center; tracks_out not NULL exactly when tracks is; score without tracks; whatever the
+ * sweep refuses — except that `seed` may be NULL or empty. The workspace is wbc_rollout_vjp's: no allocation after the first call of a
+ * size; with device buffers the call can be captured into a HIP graph.
+ * Not offered: hold ticks, wbc_rollout_traj's one-track call, the group minima (expressions of slack_min), neg_ticks / first_neg_tick
+ * (integers), gradients with respect to the box constants of WbcConfig, checkpoint-and-recompute. */
+typedef struct WbcWatchSeed {
+  int32_t mask, pad_;             /* families of the rows below, increasing order; n_w = popcount; bits < 4 */
+  const double*  g_slack_min;     /* [n_w][B]; optional, needs slack_min_tick */
+  const double*  g_slack_final;   /* [n_w][B]; optional */
+  const double*  g_trace;         /* [ticks][n_w][B]; optional */
+  const int32_t* slack_min_tick;  /* [n_w][B] as the record call returned it */
+  const double*  q_final;         /* [B][27] the state after the last tick */
+} WbcWatchSeed;
+int wbc_rollout_record_watch(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
+                             const WbcTracks* tracks /* may be NULL */, const WbcTrackScores* scores /* may be NULL; needs tracks */,
+                             const WbcSlackWatch* watch, void* tape, size_t tape_bytes, double* q_trace, int mem, void* stream);
+int wbc_rollout_vjp_watched(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
+                            const WbcTracks* tracks /* may be NULL */, const void* tape, size_t tape_bytes,
+                            const WbcRolloutSeed* seed /* may be NULL */, const WbcScoreSeed* score /* may be NULL; needs tracks */,
+                            const WbcWatchSeed* watch, int mem, const WbcRolloutGrad* out,
+                            const WbcTracksGrad* tracks_out /* NULL exactly when tracks is NULL */, void* stream);
+int wbc_rollout_watched_sizes(int32_t* sizeof_watch_seed); /* ctypes layout self-check */
 
 /* Knobs of a handle (none of them changes a result beyond rounding; defaults in brackets):
  *   "jtj_mfma"        [-1] H = A'A of wbc_tick / wbc_assemble (QP_Wrapper.py:17) on the fp64 matrix cores (v_mfma_f64_16x16x4_f64)

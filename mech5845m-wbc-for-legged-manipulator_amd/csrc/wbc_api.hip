@@ -17,6 +17,7 @@
 #include "wbc_rollvjp.h"
 #include "wbc_trackvjp.h"
 #include "wbc_scorevjp.h"
+#include "wbc_slackvjp.h"
 
 // (the layouts of the handle's roll-out workspaces d_roll, d_traj and d_slack: RollWs, TrajWs and SlackWs below)
 
@@ -103,6 +104,7 @@ struct WbcBatch {
   long long last_rollvjp_variant;   // ... and of the last link-kernel launch of wbc_rollout_vjp
   long long last_trackvjp_variant;  // ... and of the last track-adjoint launch of wbc_rollout_vjp_tracks
   long long last_scorevjp_variant;  // ... and of the last score-cotangent launch of wbc_rollout_vjp_scored
+  long long last_slackvjp_variant;  // ... and of the last slack-cotangent launch (wbc_state_slack_vjp, wbc_rollout_vjp_watched)
   long long last_tick_variant, last_qp_variant;   // variant_key(...) of the row the last tick / assemble / fk launch and the last stand-alone QP launch resolved (-1: none yet)
   int sim3p_fixd;        // option [1]: the packed sim3 kernel's FIXD form where the handle qualifies (fixd_dims)
   bool fixd_dims[WBC_MAX_MODELS];   // wbc_batch_configure: the model's plan has exactly the SIM3P_FIXD_* dimensions
@@ -415,7 +417,7 @@ extern "C" int wbc_batch_create(const WbcModel* const* models, int n_models, int
   if (!b) return fail(WBC_E_ARG, "out of memory");
   memset(b, 0, sizeof *b);
   b->device_id = device_id; b->n_models = n_models; b->max_batch = max_batch; b->presolve = 1; b->presolve_orth = 1; b->packed_update = 1; b->sim3_kernel = 1; b->sing_tol = 1e-7; b->wave_order = 1; b->sim3p_fixd = 1;
-  b->last_tick_variant = b->last_qp_variant = b->last_grad_variant = b->last_gradq_variant = b->last_stepvjp_variant = b->last_rollvjp_variant = b->last_trackvjp_variant = b->last_scorevjp_variant = -1;
+  b->last_tick_variant = b->last_qp_variant = b->last_grad_variant = b->last_gradq_variant = b->last_stepvjp_variant = b->last_rollvjp_variant = b->last_trackvjp_variant = b->last_scorevjp_variant = b->last_slackvjp_variant = -1;
   b->jtj_mfma = -1; b->refine = 1; b->packed_min_batch = WBC_SIM3P_MIN_BATCH; b->warm_start = 0; b->packed_kernel = 1; b->packed_orth = 1; b->packed_box = 1; b->posture_par = 1;
   std::vector<DevModel> dm(n_models);
   for (int i = 0; i < n_models; ++i) {
@@ -927,6 +929,7 @@ extern "C" int wbc_batch_get_stat(WbcBatch* b, const char* name, void* stream, i
   if (!strcmp(name, "last_rollvjp_variant")) { *out = b->last_rollvjp_variant; return WBC_OK; }
   if (!strcmp(name, "last_trackvjp_variant")) { *out = b->last_trackvjp_variant; return WBC_OK; }
   if (!strcmp(name, "last_scorevjp_variant")) { *out = b->last_scorevjp_variant; return WBC_OK; }
+  if (!strcmp(name, "last_slackvjp_variant")) { *out = b->last_slackvjp_variant; return WBC_OK; }
   if (!strcmp(name, "last_update_packed")) { *out = b->last_update_packed; return WBC_OK; }
   if (!strcmp(name, "last_posture_par")) { *out = b->last_posture_par; return WBC_OK; }
   if (!strcmp(name, "last_orth")) { *out = (b->last_path == TICK_GENERAL || b->last_path == TICK_ORTHP) ? b->last_orth : 0; return WBC_OK; }
@@ -1444,6 +1447,50 @@ extern "C" int wbc_state_slack(WbcBatch* b, int B, const double* q, const double
   if ((rc = st.stage())) return rc;
   if (int e = launch_slack(a, stream)) return fail(WBC_E_HIP, "slack kernel launch failed: %s", hipGetErrorString((hipError_t)e));
   return st.finish();
+}
+
+// The cotangent of the four slack families at q (include/wbc.h): argument checks, staging of host arrays, ONE launch of wbc_slackvjp_kernel's
+// STATE stage (csrc/wbc_k_slackvjp.hip). No memset; the kernel writes every row of every output it is given.
+static_assert(sizeof(WbcSlackGrad) == 4 * sizeof(void*), "wbc_capi.WbcSlackGrad");
+static void slackvjp_args(SlackVjpArgs& a, WbcBatch* b, int B, const double* q, const double* box, const int32_t* model_id) {
+  memset(&a, 0, sizeof a);
+  a.models = b->d_models; a.cfgs = b->d_cfgs; a.plans = b->d_plans; a.lim = b->d_slack_lim;
+  a.B = B; a.n_models = b->n_models; a.rot = b->rot;
+  a.q = q; a.box = box; a.model_id = model_id;
+}
+extern "C" int wbc_state_slack_vjp(WbcBatch* b, int B, const double* q, const double* trunk_box_center, const int32_t* model_id,
+                                   const double* g_slack, const double* g_components, int mem, const WbcSlackGrad* out, void* stream) {
+  const char* who = "wbc_state_slack_vjp";
+  int rc = check_batch(b, B, who, true);
+  if (rc) return rc;
+  if (!q) return fail(WBC_E_ARG, "%s: q is required", who);
+  if (!out) return fail(WBC_E_ARG, "%s: out is required", who);
+  if (!g_slack && !g_components) return fail(WBC_E_ARG, "%s: a cotangent is required (g_slack or g_components)", who);
+  if (b->n_models > 1 && !model_id) return fail(WBC_E_ARG, "%s: model_id is required with %d models", who, b->n_models);
+  if (!trunk_box_center && mem == WBC_MEM_HOST) {   // (device cotangents are not read here: the kernel then reports the row, see include/wbc.h)
+    for (int i = 0; i < B; ++i) {
+      bool on = g_slack && (g_slack[4 * i + WBC_SLACK_TRUNK_Z] != 0.0 || g_slack[4 * i + WBC_SLACK_TRUNK_ANG] != 0.0);
+      for (int c = 4; g_components && c < SLACK_NC; ++c) on = on || g_components[(size_t)SLACK_NC * i + c] != 0.0;
+      if (on) return fail(WBC_E_ARG, "%s: trunk_box_center is required: instance %d carries a non-zero cotangent on a trunk family", who, i);
+    }
+  }
+  HIP_TRY(hipSetDevice(b->device_id));
+  if ((rc = slack_ready(b, who))) return rc;
+  SlackVjpArgs a;
+  slackvjp_args(a, b, B, q, trunk_box_center, model_id);
+  a.g_slack = g_slack; a.g_comp = g_components;
+  a.d_q = out->d_q; a.d_box = out->d_trunk_box_center; a.which = out->which; a.grad_status = out->grad_status;
+  Stager st{b, mem, (hipStream_t)stream, {}};
+  const size_t n = (size_t)B;
+  st.in(&a.q, n * WBC_Q_STRIDE); st.in(&a.box, n * 4); st.in(&a.model_id, n); st.in(&a.g_slack, n * SLACK_NF); st.in(&a.g_comp, n * SLACK_NC);
+  st.out(&a.d_q, n * WBC_V_STRIDE); st.out(&a.d_box, n * 4); st.out(&a.which, n * SLACK_NF); st.out(&a.grad_status, n);
+  if ((rc = st.stage())) return rc;
+  if ((rc = launch_rc(launch_slackvjp(a, SLACKVJP_STATE, stream, &b->last_slackvjp_variant), "slack cotangent"))) return rc;
+  return st.finish();
+}
+extern "C" int wbc_slack_grad_sizes(int32_t* sizeof_grad) {
+  if (sizeof_grad) *sizeof_grad = (int32_t)sizeof(WbcSlackGrad);
+  return WBC_OK;
 }
 
 // ---- The roll-out pipeline (wbc_rollout / _tp / _traj / _tracks / _watch): rollout_run is the one loop — check, stage,
@@ -2008,18 +2055,59 @@ struct ScoreSeedExt {
   int after_link(const Sweep& W, int k) { return launch(W, SCOREVJP_TARGET, k); }
 };
 
+// The watch seed (wbc_rollout_vjp_watched): the SEED stage of wbc_slackvjp_kernel in front of every tick's step layer (g += the slack
+// families' cotangent at q_(k+1), the box term into acc_box). No after_link: a slack reads no target.
+struct WatchSeedExt {
+  const WbcWatchSeed* in;   // as the caller gave it: NULL is the sweep's first refusal
+  WbcWatchSeed ws; SlackVjpArgs sa; size_t nw;
+  explicit WatchSeedExt(const WbcWatchSeed* watch) : in(watch), ws{}, nw(0) { memset(&sa, 0, sizeof sa); }
+  // what wbc_rollout_vjp_watched refuses beyond the sweep's own refusals, before any launch
+  int check(const WbcTickIn* in0, const char* who) const {
+    const WbcWatchSeed& w = *in;
+    if (!w.g_slack_min && !w.g_slack_final && !w.g_trace)
+      return fail(WBC_E_ARG, "%s: a slack cotangent is required (g_slack_min, g_slack_final or g_trace)", who);
+    if (w.g_slack_min && !w.slack_min_tick) return fail(WBC_E_ARG, "%s: g_slack_min needs slack_min_tick (as the record call returned it)", who);
+    if (!w.q_final) return fail(WBC_E_ARG, "%s: q_final is required (the state after the last tick: the tape ends one state earlier)", who);
+    if (w.mask <= 0 || w.mask >= (1 << WBC_N_SLACK))
+      return fail(WBC_E_ARG, "%s: mask = 0x%x must have at least one of the bits 0..%d and none beyond", who, (unsigned)w.mask, WBC_N_SLACK - 1);
+    if ((w.mask & ((1 << WBC_SLACK_TRUNK_Z) | (1 << WBC_SLACK_TRUNK_ANG))) && !in0->trunk_box_center)
+      return fail(WBC_E_ARG, "%s: the trunk families (mask bits %d, %d) need in0->trunk_box_center", who, WBC_SLACK_TRUNK_Z, WBC_SLACK_TRUNK_ANG);
+    return WBC_OK;
+  }
+  void stage(Stager& st, size_t n, int K) {
+    ws = *in;
+    nw = (size_t)__builtin_popcount((unsigned)ws.mask);
+    st.in(&ws.g_slack_min, nw * n); st.in(&ws.g_slack_final, nw * n); st.in(&ws.g_trace, (size_t)K * nw * n); st.in(&ws.slack_min_tick, nw * n);
+    st.in(&ws.q_final, n * WBC_Q_STRIDE);
+  }
+  int begin(const Sweep& W) {
+    slackvjp_args(sa, W.b, W.B, nullptr, W.first.trunk_box_center, W.first.model_id);
+    sa.K = W.K; sa.mask = ws.mask; sa.g_min = ws.g_slack_min; sa.g_fin = ws.g_slack_final; sa.min_tick = ws.slack_min_tick;
+    sa.g = W.w.g; sa.acc_box = W.w.acc_box; sa.worst = W.w.worst;
+    return WBC_OK;
+  }
+  int before_step(const Sweep& W, int k) {   // q_(k+1): the tape's q of tick k + 1, the caller's q_final behind the last tick
+    sa.k = k;
+    sa.q = k == W.K - 1 ? ws.q_final : TapeWs::carve(W.tape, W.n, k + 1).q;
+    sa.g_trace = ws.g_trace ? ws.g_trace + (size_t)k * nw * W.n : nullptr;
+    return launch_rc(launch_slackvjp(sa, SLACKVJP_SEED, W.stream, &W.b->last_slackvjp_variant), "roll-out gradient slack cotangent");
+  }
+};
+
 static int rollout_vjp_run(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r, const void* tape,
                            size_t tape_bytes, const WbcRolloutSeed* seed, int mem, const WbcRolloutGrad* out, void* stream, const char* who,
-                           TrackAdjExt* tx = nullptr, ScoreSeedExt* sx = nullptr) {
+                           TrackAdjExt* tx = nullptr, ScoreSeedExt* sx = nullptr, WatchSeedExt* wx = nullptr) {
   int rc;
+  if (wx && !wx->in) return fail(WBC_E_ARG, "%s: watch is required (wbc_rollout_vjp / _tracks / _scored are the calls without one)", who);
   if (sx && !sx->in) return fail(WBC_E_ARG, "%s: score is required (wbc_rollout_vjp_tracks is the call without one)", who);
   if (tx && (rc = check_tracks_call(B, in0, r, tx->in, nullptr))) return rc;   // (first: tracks == NULL is refused before a field of it is read)
   if ((rc = check_record_call(b, B, in0, r, tape, tape_bytes, who))) return rc;
   if (!out) return fail(WBC_E_ARG, "%s: out is required", who);
   if (tx && (rc = tx->check(out, who))) return rc;
-  if (!sx && (!seed || !(seed->g_q_final || seed->g_qdot_last || seed->g_q_trace)))
+  if (!sx && !wx && (!seed || !(seed->g_q_final || seed->g_qdot_last || seed->g_q_trace)))
     return fail(WBC_E_ARG, "%s: a seed is required (g_q_final, g_qdot_last or g_q_trace)", who);
   if (sx && (rc = sx->check(in0, r, who))) return rc;
+  if (wx && (rc = wx->check(in0, who))) return rc;
   if ((rc = check_dt(dt, who))) return rc;
   if (r->mode != WBC_ROLLOUT_RUNNING && r->mode != WBC_ROLLOUT_WARMUP)
     return fail(WBC_E_ARG, "%s: mode = %d, want WBC_ROLLOUT_RUNNING (%d) or WBC_ROLLOUT_WARMUP (%d)", who, r->mode, WBC_ROLLOUT_RUNNING, WBC_ROLLOUT_WARMUP);
@@ -2028,6 +2116,7 @@ static int rollout_vjp_run(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTa
   const Reads rd(b, r->mode == WBC_ROLLOUT_RUNNING);   // the estimator reads ee_target: the step's d_foot_targets reaches it without an EE task
   if ((rc = check_outs(*out, ROLL_OUT, rd, who, false))) return rc;
   HIP_TRY(hipSetDevice(b->device_id));
+  if (wx && (rc = slack_ready(b, who))) return rc;
   // size the workspace: the task rows of wbc_assemble, the unit rows on the padded columns of the handle's smallest model, the constraint rows
   int min_nv = WBC_V_STRIDE;
   for (int i = 0; i < b->n_models; ++i) if (b->models[i]->dev.nv < min_nv) min_nv = b->models[i]->dev.nv;
@@ -2051,6 +2140,7 @@ static int rollout_vjp_run(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTa
   st.in(&tp, n); st.in(&imu, n * 4);
   st.in(&sd.g_q_final, n * WBC_V_STRIDE); st.in(&sd.g_qdot_last, n * WBC_V_STRIDE); st.in(&sd.g_q_trace, (size_t)K * n * WBC_V_STRIDE);
   if (sx) sx->stage(st, n);
+  if (wx) wx->stage(st, n, K);
   stage_outs(st, og, ROLL_OUT, n);
   st.out(&og.grad_status, n); st.out(&og.ticks_dropped, n);
   if (tx) tx->stage(st, n);
@@ -2088,7 +2178,7 @@ static int rollout_vjp_run(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTa
     return launch_rc(launch_rollvjp(L, stage, stream, &b->last_rollvjp_variant), "roll-out gradient link");
   };
   if ((rc = link(ROLLVJP_BEGIN, K - 1))) return rc;
-  if ((tx && (rc = tx->begin(W))) || (sx && (rc = sx->begin(W)))) return rc;
+  if ((tx && (rc = tx->begin(W))) || (sx && (rc = sx->begin(W))) || (wx && (rc = wx->begin(W)))) return rc;
   for (int k = K - 1; k >= 0; --k) {
     const TapeWs T = TapeWs::carve(W.tape, n, k);
     WbcTickIn in = first;   // the inputs tick k saw
@@ -2098,6 +2188,7 @@ static int rollout_vjp_run(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTa
     if (k > 0 && first.ee_prev_rot) in.ee_prev_rot = head.ee_prev_rot;
     if (k > 0 && first.trunk_prev_rot) in.trunk_prev_rot = head.trunk_prev_rot;
     if (sx && (rc = sx->before_step(W, k, T))) return rc;
+    if (wx && (rc = wx->before_step(W, k))) return rc;
     // the step: g -> d_q, v = d_qdot, d_foot_targets; on the last tick v += g_qdot_last
     if ((rc = step_layer(b, B, dt, r->mode, T.q, T.qdot, T.ee_target, imu, first.model_id, w.g, s_out, stream))) return rc;
     if (k == K - 1 && sd.g_qdot_last && (rc = link(ROLLVJP_ADDV, K - 1))) return rc;
@@ -2207,6 +2298,16 @@ extern "C" int wbc_rollout_tracks_grad_sizes(int32_t* sizeof_track_grad, int32_t
   return WBC_OK;
 }
 
+// what every call with a WbcSlackWatch refuses of it
+static int check_watch(const char* who, const WbcTickIn* in0, const WbcSlackWatch* watch, int B) {
+  if (watch->mask <= 0 || watch->mask >= (1 << WBC_N_SLACK))
+    return fail(WBC_E_ARG, "%s: mask = 0x%x must have at least one of the bits 0..%d and none beyond", who, (unsigned)watch->mask, WBC_N_SLACK - 1);
+  if (int rc = check_group_size(who, watch->group_size, B)) return rc;
+  if ((watch->mask & ((1 << WBC_SLACK_TRUNK_Z) | (1 << WBC_SLACK_TRUNK_ANG))) && in0 && !in0->trunk_box_center)
+    return fail(WBC_E_ARG, "%s: the trunk families (mask bits %d, %d) need in0->trunk_box_center", who, WBC_SLACK_TRUNK_Z, WBC_SLACK_TRUNK_ANG);
+  return WBC_OK;
+}
+
 // The roll-outs with the slack families watched (WbcSlackWatch): the watch's own argument checks, then the tracks call's (with tracks) and
 // the shared loop. watch == NULL: the call without a watch, launch for launch.
 extern "C" int wbc_rollout_watch(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
@@ -2214,16 +2315,49 @@ extern "C" int wbc_rollout_watch(WbcBatch* b, int B, const WbcTickIn* in0, const
   int rc;
   if (scores && !tracks) return fail(WBC_E_ARG, "wbc_rollout_watch: scores needs tracks");
   if (watch) {
-    if (watch->mask <= 0 || watch->mask >= (1 << WBC_N_SLACK))
-      return fail(WBC_E_ARG, "wbc_rollout_watch: mask = 0x%x must have at least one of the bits 0..%d and none beyond", (unsigned)watch->mask, WBC_N_SLACK - 1);
-    if ((rc = check_group_size("wbc_rollout_watch", watch->group_size, B))) return rc;
-    if ((watch->mask & ((1 << WBC_SLACK_TRUNK_Z) | (1 << WBC_SLACK_TRUNK_ANG))) && in0 && !in0->trunk_box_center)
-      return fail(WBC_E_ARG, "wbc_rollout_watch: the trunk families (mask bits %d, %d) need in0->trunk_box_center", WBC_SLACK_TRUNK_Z, WBC_SLACK_TRUNK_ANG);
+    if ((rc = check_watch("wbc_rollout_watch", in0, watch, B))) return rc;
   }
   if (tracks && (rc = check_tracks_call(B, in0, r, tracks, scores))) return rc;
   TracksExt tk(tracks ? *tracks : WbcTracks{}, scores, false);
   WatchExt wx(watch ? *watch : WbcSlackWatch{});
   return rollout_run(b, B, in0, tp, dt, r, mem, stream, tracks ? &tk : nullptr, watch ? &wx : nullptr);
+}
+
+// The recorded roll-out with the slack families watched, and its sweep seeded with the cotangents of what the watch returned (include/wbc.h;
+// DESIGN.md §3.50): wbc_rollout_watch's loop with the record extension behind the watch, then the one sweep with the watch seed's stage in
+// front of every step layer.
+extern "C" int wbc_rollout_record_watch(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
+                                        const WbcTracks* tracks, const WbcTrackScores* scores, const WbcSlackWatch* watch, void* tape,
+                                        size_t tape_bytes, double* q_trace, int mem, void* stream) {
+  const char* who = "wbc_rollout_record_watch";
+  int rc;
+  if (!watch) return fail(WBC_E_ARG, "%s: watch is required (wbc_rollout_record / _record_tracks are the calls without one)", who);
+  if (scores && !tracks) return fail(WBC_E_ARG, "%s: scores needs tracks", who);
+  if ((rc = check_watch(who, in0, watch, B))) return rc;
+  if (tracks && (rc = check_tracks_call(B, in0, r, tracks, scores))) return rc;
+  if ((rc = check_record_call(b, B, in0, r, tape, tape_bytes, who))) return rc;
+  TracksExt tk(tracks ? *tracks : WbcTracks{}, scores, false);
+  WatchExt wx(*watch);
+  RecordExt rx(tape, q_trace);
+  return rollout_run(b, B, in0, tp, dt, r, mem, stream, tracks ? &tk : nullptr, &wx, &rx);
+}
+static_assert(sizeof(WbcWatchSeed) == 8 + 5 * sizeof(void*), "wbc_capi.WbcWatchSeed");
+extern "C" int wbc_rollout_vjp_watched(WbcBatch* b, int B, const WbcTickIn* in0, const WbcTaskParams* tp, double dt, const WbcRollout* r,
+                                       const WbcTracks* tracks, const void* tape, size_t tape_bytes, const WbcRolloutSeed* seed,
+                                       const WbcScoreSeed* score, const WbcWatchSeed* watch, int mem, const WbcRolloutGrad* out,
+                                       const WbcTracksGrad* tracks_out, void* stream) {
+  const char* who = "wbc_rollout_vjp_watched";
+  if (!watch) return fail(WBC_E_ARG, "%s: watch is required (wbc_rollout_vjp / _tracks / _scored are the calls without one)", who);
+  if (score && !tracks) return fail(WBC_E_ARG, "%s: score needs tracks", who);
+  if (!tracks && tracks_out) return fail(WBC_E_ARG, "%s: tracks_out must be NULL without tracks", who);
+  TrackAdjExt tx(tracks, tracks_out);
+  ScoreSeedExt sx(score);
+  WatchSeedExt wx(watch);
+  return rollout_vjp_run(b, B, in0, tp, dt, r, tape, tape_bytes, seed, mem, out, stream, who, tracks ? &tx : nullptr, score ? &sx : nullptr, &wx);
+}
+extern "C" int wbc_rollout_watched_sizes(int32_t* sizeof_watch_seed) {
+  if (sizeof_watch_seed) *sizeof_watch_seed = (int32_t)sizeof(WbcWatchSeed);
+  return WBC_OK;
 }
 
 static int qp_common(WbcBatch* b, int B, QpArgs& a, int mem, void* stream, const char* who) {
@@ -2493,6 +2627,7 @@ extern "C" int wbc_variant_count(const char* family) {
   if (!strcmp(family, "rollvjp")) return rollvjp_variant_count();
   if (!strcmp(family, "trackvjp")) return trackvjp_variant_count();
   if (!strcmp(family, "scorevjp")) return scorevjp_variant_count();
+  if (!strcmp(family, "slackvjp")) return slackvjp_variant_count();
   return fail(WBC_E_ARG, "wbc_variant_count: unknown kernel family %s", family);
 }
 extern "C" int wbc_abi_sizes(int32_t* sb, int32_t* sc) {

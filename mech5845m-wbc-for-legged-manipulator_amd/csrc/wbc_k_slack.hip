@@ -9,13 +9,15 @@
 //                            schedule DevPlan.q_fk (the CoM needs every body). Writes the row (wbc_state_slack) and / or folds the tick into
 //                            the watch's accumulators (lanes s < 4 of a row, one family each): no second accumulation launch.
 //   wbc_slack_groups_kernel  once at the end: one wavefront per group of M consecutive instances, fixed-shape reduction (no atomics)
+// The evaluation itself (frames, CoM, joint scan, components, family scans) stands in wbc_slack.h as inline functions: wbc_k_slackvjp.hip, the
+// cotangent of these families, runs the same ones and so selects the same components.
 // Reads q, the box centres and the tables; writes nothing but its outputs, rows [0, B) only.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <math.h>
 #include "wbc_packed.h"
-#include "wbc_slack.h"
 #include "wbc_qtree.h"
+#include "wbc_slack.h"      // behind wbc_qtree.h: the evaluation is declared
 
 namespace wbc {
 
@@ -26,24 +28,6 @@ struct __attribute__((aligned(16))) SInst {
 };
 struct __attribute__((aligned(16))) SSmemP { SInst I[4]; };
 static_assert(sizeof(SInst) == 3200 && offsetof(SInst, pf) == 3072 && offsetof(SInst, eul) == 3168, "the instance's LDS record");
-
-// (v, c) <- the smaller of (v, c) and (ov, oc): by value, a tie by the lower code — what a scan in increasing code order with a strict < gives
-__device__ __forceinline__ void slack_take(double& v, int& c, const double ov, const int oc) {
-  if (ov < v || (ov == v && oc < c)) { v = ov; c = oc; }
-}
-template <int CTRL>
-__device__ __forceinline__ void slack_take_dpp(double& v, int& c) {
-  const double ov = dpp<CTRL>(v);
-  const int oc = __builtin_amdgcn_update_dpp(c, c, CTRL, 0xF, 0xF, false);
-  slack_take(v, c, ov, oc);
-}
-// minimum of N components scanned in increasing code order with a strict <
-template <int N>
-__device__ __forceinline__ void slack_scan(const double* c, double& v, int& w) {
-  v = c[0]; w = 0;
-#pragma unroll
-  for (int i = 1; i < N; ++i) if (c[i] < v) { v = c[i]; w = i; }
-}
 
 template <bool ROT>   // ROT: rotated joint placements in the batch (wbc_k_sim3p.hip)
 __global__ void __launch_bounds__(64) wbc_slack_kernel(const SlackArgs A, const DevModel* __restrict__ models, const WbcConfig* __restrict__ cfgs,
@@ -57,8 +41,8 @@ __global__ void __launch_bounds__(64) wbc_slack_kernel(const SlackArgs A, const 
   const WbcConfig& cfg = cfgs[mid];
   const DevPlan& P = plans[mid];
   const SlackLimits& Lm = A.lim[mid];
-  const int nq = M.nq, nv = M.nv, nj = M.njoints;
-  const double qnan = __longlong_as_double(0x7FF8000000000000ll), inf = __longlong_as_double(0x7FF0000000000000ll);
+  const int nq = M.nq;
+  const double qnan = __longlong_as_double(0x7FF8000000000000ll);
   // ---- every global read first
   const double* qg = A.q + b * NQ;
   const double q0 = qg[s], q1 = (16 + s < nq) ? qg[16 + s] : 0.0;
@@ -69,83 +53,24 @@ __global__ void __launch_bounds__(64) wbc_slack_kernel(const SlackArgs A, const 
   }
   DevPlan::PkJoint fkn = P.q_fk[0][s];
   const int scq0 = P.q_scq[(2 + s) & 31], scq1 = P.q_scq[(18 + s) & 31];
-  // frame of this lane: FL foot, RR foot (EE_frame_pos[1], [2]: the CoM box's corners), trunk
-  const int fr = (s == 0) ? WBC_FR_EE0 + 1 : ((s == 1) ? WBC_FR_EE0 + 2 : WBC_FR_TRUNK);
-  const int fjoint = M.frame_joint[fr];
-  const double f0 = M.frame_p[fr][0], f1 = M.frame_p[fr][1], f2 = M.frame_p[fr][2];
-  const int tjoint = M.frame_joint[WBC_FR_TRUNK];
-  const int j1 = 16 + s;                                          // bodies of this lane: joints s (>= 1) and 16 + s
-  const bool hb0 = s >= 1 && s < nj, hb1 = j1 < nj;
-  const DevPlan::QJnt m0 = P.q_jm[hb0 ? s : 1], m1 = P.q_jm[hb1 ? j1 : 1];
-  const int lock = cfg.lock_from;
-  const bool hd0 = s >= 6 && s < lock && s < nv, hd1 = j1 < lock && j1 < nv;   // free DoF of this lane: d = s and 16 + s
-  const int qi0 = Lm.qi[hd0 ? s : 6], qi1 = Lm.qi[hd1 ? j1 : 6];
-  const double lo0 = Lm.lo[hd0 ? s : 6], hi0 = Lm.hi[hd0 ? s : 6], lo1 = Lm.lo[hd1 ? j1 : 6], hi1 = Lm.hi[hd1 ? j1 : 6];
-  const double z_frac = cfg.trunk_box_z_frac, box_ang = cfg.trunk_box_ang;
+  const SlackLane L(M, cfg, P, Lm, s);
   const bool qbad = (s < nq && !is_finite(q0)) || (16 + s < nq && !is_finite(q1));
   const bool rowbad = ((__ballot(qbad) >> T.rbase) & 0xFFFFull) != 0ull;
   qt_fk<ROT>(U.K, q0, q1, scq0, scq1, M, P, fkn, s);
   const double* const qv = U.K.q;
   const double* const oMi = U.K.oMi;
-  // ---- frame origins, the trunk's Euler angles (one atan2 per row on lanes 0..2, the tick kernels' formula: wbc_common.h, P6)
-  {
-    const double* Pj = oMi + 12 * fjoint;
-    const double* Pt = oMi + 12 * tjoint;                           // R column-major: R(i, j) = Pt[3 j + i]
-    const double R21 = Pt[5], R22 = Pt[8], R20 = Pt[2], R10 = Pt[1], R00 = Pt[0];
-    const double ay = (s == 0) ? R21 : ((s == 1) ? -R20 : R10);
-    const double ax = (s == 0) ? R22 : ((s == 1) ? sqrt(fma(R21, R21, R22 * R22)) : R00);
-    const double eul = atan2(ay, ax);
-    if (s < 3) {
-#pragma unroll
-      for (int rr = 0; rr < 3; ++rr) U.pf[4 * s + rr] = qt_point(Pj, f0, f1, f2, rr);
-      U.eul[s] = eul;
-    }
-  }
-  // ---- data.com[0], x and y: lane s sums m_j (R_j c_j + p_j) over joints s and 16 + s in that order, then the row butterfly and one division each
-  // (qt_body_mass_table's centres, but two components summed per lane in this order: spelled out, and not through qt_point)
-  double cx = 0.0, cy = 0.0, cm = 0.0;
-  {
-    const double* Pa = oMi + 12 * (hb0 ? s : 1);
-    const double* Pb = oMi + 12 * (hb1 ? j1 : 1);
-    const double xa = Pa[9] + Pa[0] * m0.c0 + Pa[3] * m0.c1 + Pa[6] * m0.c2, ya = Pa[10] + Pa[1] * m0.c0 + Pa[4] * m0.c1 + Pa[7] * m0.c2;
-    const double xb = Pb[9] + Pb[0] * m1.c0 + Pb[3] * m1.c1 + Pb[6] * m1.c2, yb = Pb[10] + Pb[1] * m1.c0 + Pb[4] * m1.c1 + Pb[7] * m1.c2;
-    if (hb0) { cx = m0.m * xa; cy = m0.m * ya; cm = m0.m; }
-    if (hb1) { cx += m1.m * xb; cy += m1.m * yb; cm += m1.m; }
-  }
-  cx = rsum16(cx); cy = rsum16(cy); cm = rsum16(cm);
-  const double com0 = cx / cm, com1 = cy / cm;
-  // ---- joint range: one DoF pair per lane, then a 16-lane minimum that carries the code
-  double jv = inf;
-  int jc = INT_MAX;
-  {
-    const double x0 = qv[qi0], x1 = qv[qi1];
-    if (hd0) { slack_take(jv, jc, x0 - lo0, 2 * s); slack_take(jv, jc, hi0 - x0, 2 * s + 1); }
-    if (hd1) { slack_take(jv, jc, x1 - lo1, 2 * j1); slack_take(jv, jc, hi1 - x1, 2 * j1 + 1); }
-  }
-  slack_take_dpp<DPP_XOR1>(jv, jc); slack_take_dpp<DPP_XOR2>(jv, jc); slack_take_dpp<DPP_HALF_MIRROR>(jv, jc); slack_take_dpp<DPP_MIRROR>(jv, jc);
-  if (jc == INT_MAX) jc = -1;                                       // no free DoF: +inf, no code
+  // ---- the evaluation (wbc_slack.h)
+  slack_frames(U.pf, U.eul, oMi, L, s);
+  double com0, com1, cm;
+  slack_com_xy(oMi, L, s, com0, com1, cm);
+  double jv;
+  int jc;
+  slack_joint_scan(qv, L, s, jv, jc);
   WSYNC();                                                          // pf, eul are visible
-  // ---- the components of families 0..2 in code order, every lane of the row alike
-  double comp[SLACK_NC];
-  {
-    const double* pFL = U.pf;
-    const double* pRR = U.pf + 4;
-    comp[0] = -(pRR[0] - com0); comp[1] = pFL[0] - com0;
-    comp[2] = -(pRR[1] - com1); comp[3] = pFL[1] - com1;
-    const double z = U.pf[8 + 2], v = bc[0] * z_frac;
-    comp[4] = -((bc[0] - v) - z); comp[5] = (bc[0] + v) - z;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const double e = U.eul[a];
-      comp[6 + 2 * a] = -((bc[1 + a] - box_ang) - e); comp[7 + 2 * a] = (bc[1 + a] + box_ang) - e;
-    }
-  }
-  double sl[SLACK_NF];
+  double comp[SLACK_NC], sl[SLACK_NF];
   int wh[SLACK_NF];
-  slack_scan<4>(comp, sl[0], wh[0]);
-  slack_scan<2>(comp + 4, sl[1], wh[1]);
-  slack_scan<6>(comp + 6, sl[2], wh[2]);
-  sl[3] = jv; wh[3] = jc;
+  slack_components(U.pf, U.eul, com0, com1, bc, L, comp);
+  slack_families(comp, jv, jc, sl, wh);
   const bool bad1 = rowbad || !is_finite(bc[0]);
   const bool bad2 = rowbad || !is_finite(bc[1]) || !is_finite(bc[2]) || !is_finite(bc[3]);
   if (rowbad) { sl[0] = qnan; wh[0] = -1; sl[3] = qnan; wh[3] = -1; }

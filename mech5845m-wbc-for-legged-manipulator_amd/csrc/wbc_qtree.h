@@ -1,5 +1,5 @@
 // wbc_qtree.h — what the whole-tree kernels share (internal, C++): wbc_k_grad.hip, wbc_k_gradq.hip, wbc_k_slack.hip,
-// wbc_k_stepvjp.hip and wbc_k_scorevjp.hip, and no other unit. Their common shape: four instances per wavefront (lane = 16 r + s), FK over
+// wbc_k_stepvjp.hip, wbc_k_scorevjp.hip and wbc_k_slackvjp.hip, and no other unit. Their common shape: four instances per wavefront (lane = 16 r + s), FK over
 // the whole-tree schedule DevPlan.q_fk, lane s owning DoF s and 16 + s (and bodies s and 16 + s), sums over DoF by DPP row butterflies.
 // Everything is inlined into its caller and works on the caller's LDS block; a function keeps the operation order its callers had (their bits).
 // Floating-point contraction is the including unit's: wbc_k_scorevjp.hip includes this header behind its `fp contract(off)`.

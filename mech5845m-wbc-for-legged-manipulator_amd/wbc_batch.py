@@ -624,7 +624,8 @@ class WbcBatch:
         return out
 
     def rollout_record(self, inputs, dt, ticks, ee_target_step=None, trunk_target_step=None, imu=None, mode=capi.ROLLOUT_RUNNING,
-                       task_params=None, want_trace=True, tape=None, tracks=None, score=(), group_size=0):
+                       task_params=None, want_trace=True, tape=None, tracks=None, score=(), group_size=0, watch=(), watch_group_size=0,
+                       watch_trace=False):
         """wbc_rollout_record (include/wbc.h): rollout(..., want_trace=False) that also writes a tape for rollout_vjp. Returns (out, tape): out
         is rollout's dict plus q_trace [K, B, 27] (the state after every tick; want_trace); tape is a RolloutTape — device memory of
         wbc_rollout_tape_bytes(B, K) bytes (a torch uint8 tensor on the handle's device, allocated here or the caller's `tape.buf` when a
@@ -633,8 +634,15 @@ class WbcBatch:
         inputs must not hold q_con; posture modes MANI / HYBRID need inputs["posture_u"].
         tracks (rollout_tracks' list of dicts; None: the call above, argument for argument): wbc_rollout_record_tracks — rollout_tracks(...,
         score, group_size) that also writes the tape; out then holds rollout_tracks' results too, and rollout_vjp returns the gradients
-        with respect to every track's points, tangents and du. Not together with ee_target_step."""
+        with respect to every track's points, tangents and du. Not together with ee_target_step.
+        watch (rollout_watch's families; empty: the calls above): wbc_rollout_record_watch — rollout_watch(..., watch, group_size =
+        watch_group_size, want_trace = watch_trace) that also writes the tape, with or without tracks; out then holds rollout_watch's
+        results too (slack_min, slack_final, slack_min_tick, ... [n_w, B], slack_trace [K, n_w, B]), whose cotangents rollout_vjp takes as
+        watch_seed."""
         import torch
+        fams = sorted({self._slack_family(f_) for f_ in watch})
+        if len(fams) != len(list(watch)):
+            raise capi.WbcError("watch: a family is listed twice")
         keep = []
         arrays = []
         if tracks is not None:
@@ -669,6 +677,12 @@ class WbcBatch:
                          tracks=None if tracks is None else [dict(t) for t in tracks])
         tin = self._tick_in(inputs, keep, B)
         tp = _task_params(task_params, B, keep, self.device_id)
+        if fams:
+            wt = self._watch_struct(out, inputs["q"], fams, B, K, self._check_ticks_groups(B, K, watch_group_size), watch_trace, keep)
+            capi.check(self.lib.wbc_rollout_record_watch(self._h, B, C.byref(tin), tp, float(dt), C.byref(r), C.byref(tk) if tk is not None else None,
+                                                         C.byref(sc) if sc is not None else None, C.byref(wt), tape.buf.data_ptr(), nbytes,
+                                                         self._p(out.get("q_trace"), np.float64, keep), mem, self._stream(mem)), self.lib)
+            return out, tape
         if tk is not None:
             capi.check(self.lib.wbc_rollout_record_tracks(self._h, B, C.byref(tin), tp, float(dt), C.byref(r), C.byref(tk),
                                                           C.byref(sc) if sc is not None else None, tape.buf.data_ptr(), nbytes,
@@ -678,7 +692,7 @@ class WbcBatch:
                                                 self._p(out.get("q_trace"), np.float64, keep), mem, self._stream(mem)), self.lib)
         return out, tape
 
-    def rollout_vjp(self, tape, g_q_final=None, g_qdot_last=None, g_q_trace=None, want=None, out=None, score_seed=None):
+    def rollout_vjp(self, tape, g_q_final=None, g_qdot_last=None, g_q_trace=None, want=None, out=None, score_seed=None, watch_seed=None):
         """wbc_rollout_vjp (include/wbc.h): the reverse sweep over a recorded roll-out, everything on the device. tape: rollout_record's.
         Seeds (numpy or torch, at least one; tangent coordinates — wbc_workload.raw_to_tangent turns a raw gradient into one): g_q_final
         [B,26] at q_K, g_qdot_last [B,26], g_q_trace [K,B,26] at the state after each tick. want: names of capi.ROLLOUT_GRAD_FIELDS (None:
@@ -690,7 +704,12 @@ class WbcBatch:
         score_seed (None: exactly the calls above; a tape recorded with tracks): wbc_rollout_vjp_scored — dict(mask: the score mask or the
         scored frames as rollout_record's `score` lists them, g_err_sq_sum, g_err_final, g_err_max [n_scored,B] (at least one), err_max_tick
         [n_scored,B] int32 (with g_err_max), q_final [B,27]: the record call's outputs). The cotangents of the scores are formed on the
-        device; the state seeds become optional and, where given, the gradients are those of the summed loss."""
+        device; the state seeds become optional and, where given, the gradients are those of the summed loss.
+        watch_seed (None: exactly the calls above; any tape): wbc_rollout_vjp_watched — dict(mask: the watch mask or the families as
+        rollout_record's `watch` lists them, g_slack_min, g_slack_final [n_w,B], g_trace [K,n_w,B] (at least one), slack_min_tick [n_w,B]
+        int32 (with g_slack_min), q_final [B,27]: the record call's outputs). The cotangents of the slacks are formed on the device at the
+        taped states; the other seeds become optional and the gradients are those of the summed loss. d_trunk_box_center (where the
+        configuration offers it) then also holds the watch's own box term."""
         keep = []
         c = tape.call
         inputs, B, K = c["inputs"], tape.B, tape.ticks
@@ -702,7 +721,9 @@ class WbcBatch:
             if tracks is None:
                 raise capi.WbcError("score_seed: needs a tape recorded with tracks")
             sseed = {k: score_seed.get(k) for k in capi.SCORE_SEED_FIELDS}
-        like = next((a for a in (g_q_final, g_qdot_last, g_q_trace) + tuple((sseed or {}).values()) if a is not None), inputs["q"])
+        wseed = None if watch_seed is None else {k: watch_seed.get(k) for k in capi.WATCH_SEED_FIELDS}
+        like = next((a for a in (g_q_final, g_qdot_last, g_q_trace) + tuple((sseed or {}).values()) + tuple((wseed or {}).values())
+                     if a is not None), inputs["q"])
         default = lambda: self.default_rollout_grad_wants(c["mode"])
         tk = tg = None
         t_outs, arrays = [], []
@@ -727,7 +748,7 @@ class WbcBatch:
             arrays += self._track_arrays(tracks)
         out, o = self._grad_outs(capi.ROLLOUT_GRAD_FIELDS, capi.WbcRolloutGrad, like, B, keep, want, default, out, extras=("grad_status", "ticks_dropped"))
         mem = _mem_of(list(inputs.values()) + list(out.values()) + arrays + [c["imu"], c["task_params"], g_q_final, g_qdot_last, g_q_trace] +
-                      list((sseed or {}).values()))
+                      list((sseed or {}).values()) + list((wseed or {}).values()))
         f, P = np.float64, self._p
         sd = capi.WbcRolloutSeed()
         sd.g_q_final, sd.g_qdot_last = P(g_q_final, f, keep, B, NV, "g_q_final"), P(g_qdot_last, f, keep, B, NV, "g_qdot_last")
@@ -740,10 +761,7 @@ class WbcBatch:
         r.imu = P(c["imu"], f, keep, B, 4, "imu")
         tin = self._tick_in(inputs, keep, B)
         tp = _task_params(c["task_params"], B, keep, self.device_id)
-        if tk is None:
-            capi.check(self.lib.wbc_rollout_vjp(self._h, B, C.byref(tin), tp, c["dt"], C.byref(r), tape.buf.data_ptr(), tape.buf.numel(),
-                                                 C.byref(sd), mem, C.byref(o), self._stream(mem)), self.lib)
-            return out
+        ss = None
         if sseed is not None:
             ss = capi.WbcScoreSeed()
             m_ = score_seed.get("mask")
@@ -753,6 +771,29 @@ class WbcBatch:
                 setattr(ss, k_, P(sseed[k_], f, keep, ns, B, k_))
             ss.err_max_tick = P(sseed["err_max_tick"], np.int32, keep, ns, B, "err_max_tick")
             ss.q_final = P(sseed["q_final"], f, keep, B, NQS, "q_final")
+        if wseed is not None:
+            ws = capi.WbcWatchSeed()
+            m_ = watch_seed.get("mask")
+            ws.mask = int(m_) if isinstance(m_, (int, np.integer)) else sum(1 << self._slack_family(f_) for f_ in set(m_ or ()))
+            nw = bin(ws.mask & 0xFFFFFFFF).count("1")
+            for k_ in ("g_slack_min", "g_slack_final"):
+                setattr(ws, k_, P(wseed[k_], f, keep, nw, B, k_))
+            if wseed["g_trace"] is not None:
+                if tuple(wseed["g_trace"].shape) != (K, nw, B):
+                    raise capi.WbcError("g_trace: shape %s, want (%d, %d, %d)" % (tuple(wseed["g_trace"].shape), K, nw, B))
+                ws.g_trace = P(wseed["g_trace"], f, keep)
+            ws.slack_min_tick = P(wseed["slack_min_tick"], np.int32, keep, nw, B, "slack_min_tick")
+            ws.q_final = P(wseed["q_final"], f, keep, B, NQS, "q_final")
+            capi.check(self.lib.wbc_rollout_vjp_watched(self._h, B, C.byref(tin), tp, c["dt"], C.byref(r), C.byref(tk) if tk is not None else None,
+                                                        tape.buf.data_ptr(), tape.buf.numel(), C.byref(sd), C.byref(ss) if ss is not None else None,
+                                                        C.byref(ws), mem, C.byref(o), C.byref(tg) if tk is not None else None,
+                                                        self._stream(mem)), self.lib)
+            return out if tk is None else dict(out, tracks=t_outs)
+        if tk is None:
+            capi.check(self.lib.wbc_rollout_vjp(self._h, B, C.byref(tin), tp, c["dt"], C.byref(r), tape.buf.data_ptr(), tape.buf.numel(),
+                                                 C.byref(sd), mem, C.byref(o), self._stream(mem)), self.lib)
+            return out
+        if ss is not None:
             capi.check(self.lib.wbc_rollout_vjp_scored(self._h, B, C.byref(tin), tp, c["dt"], C.byref(r), C.byref(tk), tape.buf.data_ptr(),
                                                        tape.buf.numel(), C.byref(sd), C.byref(ss), mem, C.byref(o), C.byref(tg),
                                                        self._stream(mem)), self.lib)
@@ -859,6 +900,27 @@ class WbcBatch:
         f = np.float64
         capi.check(self.lib.wbc_state_slack(self._h, B, self._p(q, f, keep), self._p(trunk_box_center, f, keep, B, 4, "trunk_box_center"),
                                             self._p(model_id, np.int32, keep, B, 1, "model_id"), mem, C.byref(o), self._stream(mem)), self.lib)
+        return out
+
+    def state_slack_grad(self, q, trunk_box_center=None, g_slack=None, g_components=None, model_id=None):
+        """The cotangent of state_slack's outputs (wbc_state_slack_vjp, include/wbc.h; restated in numpy by wbc_workload.slack_gradients):
+        g_slack [B, 4] = dL/d slack and / or g_components [B, 12] = dL/d components -> dict(d_q [B, 26] in tangent coordinates at q
+        (wbc_workload.tangent_to_raw), d_trunk_box_center [B, 4], which [B, 4] int32: the component each family's cotangent went to,
+        state_slack's `which`; grad_status [B] int32). One kernel launch, nothing allocated by the library."""
+        keep = []
+        mem = _mem_of([q, trunk_box_center, model_id, g_slack, g_components])
+        B = self._batch_of(q)
+        out = {k: self._alloc(q, (B,) + shp) for k, shp in capi.SLACK_GRAD_FIELDS.items()}
+        out["which"] = self._alloc(q, (B, capi.N_SLACK), np.int32)
+        out["grad_status"] = self._alloc(q, (B,), np.int32)
+        o = capi.WbcSlackGrad()
+        for k, v in out.items():
+            setattr(o, k, self._p(v, np.int32 if k in ("which", "grad_status") else np.float64, keep))
+        f, P = np.float64, self._p
+        capi.check(self.lib.wbc_state_slack_vjp(self._h, B, P(q, f, keep), P(trunk_box_center, f, keep, B, 4, "trunk_box_center"),
+                                                P(model_id, np.int32, keep, B, 1, "model_id"), P(g_slack, f, keep, B, capi.N_SLACK, "g_slack"),
+                                                P(g_components, f, keep, B, capi.N_SLACK_COMPONENTS, "g_components"), mem, C.byref(o),
+                                                self._stream(mem)), self.lib)
         return out
 
     def rollout_watch(self, inputs, dt, ticks, watch=("com", "trunk_z", "trunk_ang", "joint"), tracks=None, score=(), group_size=0,

@@ -213,6 +213,22 @@ class WbcScoreSeed(C.Structure):
     _fields_ = [("score_mask", C.c_int32), ("pad_", C.c_int32)] + [(n, C.c_void_p) for n in SCORE_SEED_FIELDS]
 
 
+# wbc_state_slack_vjp: dL/dq (tangent coordinates) and dL/d trunk_box_center of the slack families at a state (include/wbc.h)
+SLACK_GRAD_FIELDS = dict(d_q=(V_STRIDE,), d_trunk_box_center=(4,))     # output name -> per-instance shape
+
+
+class WbcSlackGrad(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in tuple(SLACK_GRAD_FIELDS) + ("which", "grad_status")]
+
+
+# wbc_rollout_vjp_watched: the cotangents of the watch's results as a seed of the sweep (include/wbc.h)
+WATCH_SEED_FIELDS = ("g_slack_min", "g_slack_final", "g_trace", "slack_min_tick", "q_final")
+
+
+class WbcWatchSeed(C.Structure):
+    _fields_ = [("mask", C.c_int32), ("pad_", C.c_int32)] + [(n, C.c_void_p) for n in WATCH_SEED_FIELDS]
+
+
 class WbcFkOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("oMi", "oMf", "J", "com", "Jcom")]
 
@@ -280,6 +296,14 @@ SIGNATURES = {
     "wbc_state_slack": (_i, [_vp, _i, _vp, _vp, _vp, _i, C.POINTER(WbcSlackOut), _vp]),
     "wbc_rollout_watch": (_i, [_vp, _i, C.POINTER(WbcTickIn), _vp, _d, C.POINTER(WbcRollout), C.POINTER(WbcTracks),
                                C.POINTER(WbcTrackScores), C.POINTER(WbcSlackWatch), _i, _vp]),
+    "wbc_state_slack_vjp": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(WbcSlackGrad), _vp]),
+    "wbc_slack_grad_sizes": (_i, [c_int32_p]),
+    "wbc_rollout_record_watch": (_i, [_vp, _i, C.POINTER(WbcTickIn), _vp, _d, C.POINTER(WbcRollout), C.POINTER(WbcTracks),
+                                      C.POINTER(WbcTrackScores), C.POINTER(WbcSlackWatch), _vp, C.c_size_t, _vp, _i, _vp]),
+    "wbc_rollout_vjp_watched": (_i, [_vp, _i, C.POINTER(WbcTickIn), _vp, _d, C.POINTER(WbcRollout), C.POINTER(WbcTracks), _vp, C.c_size_t,
+                                     C.POINTER(WbcRolloutSeed), C.POINTER(WbcScoreSeed), C.POINTER(WbcWatchSeed), _i,
+                                     C.POINTER(WbcRolloutGrad), C.POINTER(WbcTracksGrad), _vp]),
+    "wbc_rollout_watched_sizes": (_i, [c_int32_p]),
     "wbc_integrate": (_i, [_vp, _i, _vp, _vp, _vp, _d, _i, _vp, _vp]),
     "wbc_batch_set_option": (_i, [_vp, C.c_char_p, _i]),
     "wbc_batch_get_stat": (_i, [_vp, C.c_char_p, _vp, C.POINTER(C.c_int64)]),
@@ -351,6 +375,12 @@ def load_library(path=None):
     lib.wbc_rollout_scored_sizes(C.byref(sb))
     if sb.value != C.sizeof(WbcScoreSeed):
         raise WbcError("ABI mismatch (WbcScoreSeed): library %d vs ctypes %d" % (sb.value, C.sizeof(WbcScoreSeed)))
+    lib.wbc_slack_grad_sizes(C.byref(sb))
+    if sb.value != C.sizeof(WbcSlackGrad):
+        raise WbcError("ABI mismatch (WbcSlackGrad): library %d vs ctypes %d" % (sb.value, C.sizeof(WbcSlackGrad)))
+    lib.wbc_rollout_watched_sizes(C.byref(sb))
+    if sb.value != C.sizeof(WbcWatchSeed):
+        raise WbcError("ABI mismatch (WbcWatchSeed): library %d vs ctypes %d" % (sb.value, C.sizeof(WbcWatchSeed)))
     if path is None:
         _lib = lib
     return lib

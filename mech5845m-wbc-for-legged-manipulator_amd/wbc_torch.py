@@ -21,6 +21,9 @@ d_q goes to raw coordinates through ``wbc_workload.tangent_to_raw``.
 ``q_new = wbc_step(q, qdot, foot_targets, imu, dt, batch, mode)`` is the state step between two ticks (integrate, then the estimator) with
 ``wbc_step_vjp`` behind it, and ``wbc_rollout(q0, task_params, ee_target, ..., inputs, dt, ticks, batch)`` chains K ticks out of the two layers.
 ``wbc_rollout_fused`` takes the same arguments and is one layer: forward ``wbc_rollout_record``, backward ``wbc_rollout_vjp``.
+
+``slack, components, which = wbc_state_slack(q, trunk_box_center, batch)`` is the constraint slack at a state with ``wbc_state_slack_vjp``
+behind it, and ``wbc_rollout_watched`` a recorded roll-out whose watched slacks (minimum, final, per-tick trace) are differentiable outputs.
 """
 import torch
 
@@ -440,3 +443,85 @@ def wbc_rollout_tracks_scored(q0, task_params, tracks, inputs, dt, ticks, batch,
     torch.sqrt(err_sq_sum.reshape(n, G, M).sum(-1) / (M * ticks)). No IMU quaternion is fed back under a score (include/wbc.h)."""
     specs, flat = _flat_tracks(tracks)
     return _WbcRolloutTracksScored.apply(q0, task_params, inputs, dt, ticks, batch, mode, trunk_target_step, tuple(score), specs, *flat)
+
+
+# ---- the constraint slack as a loss (wbc_state_slack_vjp / wbc_rollout_vjp_watched, include/wbc.h)
+class _WbcStateSlack(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, trunk_box_center, batch, model_id):
+        q, box = _c(q), _c(trunk_box_center)
+        out = batch.state_slack(q, box, model_id=model_id, want_components=True)
+        ctx.batch, ctx.model_id, ctx.have_box = batch, model_id, box is not None
+        ctx.set_materialize_grads(False)     # an output the loss does not use gives None: its cotangent is left out of the call
+        ctx.save_for_backward(q, *([box] if box is not None else []))
+        ctx.mark_non_differentiable(out["which"])
+        return out["slack"], out["components"], out["which"]
+
+    @staticmethod
+    def backward(ctx, g_slack, g_comp, _gw):
+        import wbc_workload
+        q, *rest = ctx.saved_tensors
+        if g_slack is None and g_comp is None:
+            return None, None, None, None
+        cg = lambda t: None if t is None else t.contiguous()      # noqa: E731
+        r = ctx.batch.state_slack_grad(q, rest[0] if ctx.have_box else None, g_slack=cg(g_slack), g_components=cg(g_comp), model_id=ctx.model_id)
+        need = ctx.needs_input_grad
+        return (wbc_workload.tangent_to_raw(q, r["d_q"]) if need[0] else None,
+                r["d_trunk_box_center"] if (need[1] and ctx.have_box) else None, None, None)
+
+
+def wbc_state_slack(q, trunk_box_center, batch, model_id=None):
+    """WbcBatch.state_slack as a differentiable layer: returns (slack [B,4], components [B,12], which [B,4] int32). slack and components are
+    differentiable with respect to q [B,27] (raw coordinates: wbc_workload.tangent_to_raw of wbc_state_slack_vjp's d_q) and trunk_box_center
+    [B,4]; a family's gradient is that of the component `which` names (at a tie: the lowest code, a subgradient). backward is ONE
+    wbc_state_slack_vjp launch. A loss that puts a non-zero gradient on a trunk family needs trunk_box_center; a bad row (include/wbc.h) gets
+    zero gradients. Contiguous float64 tensors on the handle's device."""
+    return _WbcStateSlack.apply(q, trunk_box_center, batch, model_id)
+
+
+class _WbcRolloutWatched(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q0, task_params, inputs, dt, ticks, batch, mode, held, watch, specs, *flat):      # (ten arguments, then the tracks': _tracks_sweep's layout)
+        args = [_c(q0), _c(task_params)] + [_c(t) for t in flat]
+        score = tuple(held.get("score", ()))
+        out, tape = batch.rollout_record(dict(inputs, q=args[0]), dt, ticks, task_params=args[1], tracks=_tracks_of(specs, args[2:]) if specs else None,
+                                         mode=mode, watch=watch, watch_trace=True, score=score, **{k: _c(v) for k, v in held.items() if k != "score"})
+        ctx.batch, ctx.tape, ctx.watch, ctx.score = batch, tape, tuple(watch), score
+        ctx.set_materialize_grads(False)     # an output the loss does not use gives None, not zeros: its seed is left out of the call
+        _save(ctx, (out["q"], out["q_trace"], out["slack_min_tick"]) + ((out["err_max_tick"],) if score else ()), args)
+        ctx.mark_non_differentiable(out["status"], out["slack_min_tick"], out["slack_min_which"], *((out["err_max_tick"],) if score else ()))
+        res = (out["q"], out["qdot"], out["status"], out["q_trace"], out["slack_min"], out["slack_final"], out["slack_trace"], out["slack_min_tick"],
+               out["slack_min_which"])
+        return res + ((out["err_sq_sum"], out["err_final"], out["err_max"], out["err_max_tick"]) if score else ())
+
+    @staticmethod
+    def backward(ctx, g_q, g_qdot, _gst, g_trace, g_min, g_fin, g_str, _gt, _gw, g_sq=None, g_efin=None, g_max=None, _gtick=None):
+        head, args = _saved(ctx, 4 if ctx.score else 3)
+        q_final, q_trace, min_tick = head[:3]
+        cg = lambda t: None if t is None else t.contiguous()      # noqa: E731
+        seed = {}
+        if not (g_min is None and g_fin is None and g_str is None):
+            seed["watch_seed"] = dict(mask=ctx.watch, g_slack_min=cg(g_min), g_slack_final=cg(g_fin), g_trace=cg(g_str),
+                                      slack_min_tick=None if g_min is None else min_tick, q_final=q_final)
+        if not (g_sq is None and g_efin is None and g_max is None):
+            seed["score_seed"] = dict(mask=ctx.score, g_err_sq_sum=cg(g_sq), g_err_final=cg(g_efin), g_err_max=cg(g_max),
+                                      err_max_tick=None if g_max is None else head[3], q_final=q_final)
+        return _tracks_sweep(ctx, args, g_q, g_qdot, g_trace, q_final, q_trace, **seed)
+
+
+def wbc_rollout_watched(q0, task_params, inputs, dt, ticks, batch, watch=("com", "trunk_z", "trunk_ang", "joint"), tracks=None,
+                        mode=capi.ROLLOUT_RUNNING, imu=None, trunk_target_step=None, ee_target_step=None, score=()):
+    """A recorded roll-out with the slack families in `watch` as differentiable outputs ("and stay legal" as a loss): the forward is one
+    WbcBatch.rollout_record(..., watch=watch, watch_trace=True) (wbc_rollout_record_watch, include/wbc.h), the backward one
+    WbcBatch.rollout_vjp(..., watch_seed=...) (wbc_rollout_vjp_watched: the slacks' cotangents are formed where the sweep runs). tracks:
+    None, or wbc_rollout_tracks_fused's list of dicts (points, tangents and du may require a gradient); without tracks ee_target_step is
+    allowed (held constant). Returns wbc_rollout_tracks_fused's (q_final, qdot, status, q_trace) and then slack_min, slack_final [n_w,B],
+    trace [ticks,n_w,B] (rows in increasing family order; differentiable: a hinge or barrier on trace is any per-tick penalty) and
+    slack_min_tick, slack_min_which [n_w,B] int32 (not differentiable). score (with tracks; no IMU then): the scored frames as
+    wbc_rollout_tracks_scored takes them — the tuple then ends with that layer's err_sq_sum, err_final, err_max (differentiable) and
+    err_max_tick. Gradients flow to q0 (raw coordinates), task_params and the tracks; a loss may mix the slacks with the scores, q_final,
+    qdot and q_trace: the gradients are those of the sum. An IMU quaternion may be fed back. Contiguous float64 tensors on the handle's
+    device."""
+    specs, flat = _flat_tracks(tracks) if tracks else ([], [])
+    held = dict(imu=imu, trunk_target_step=trunk_target_step, ee_target_step=ee_target_step, score=tuple(score))
+    return _WbcRolloutWatched.apply(q0, task_params, inputs, dt, ticks, batch, mode, held, tuple(watch), specs, *flat)

@@ -1158,12 +1158,119 @@ def score_seed_gradients(model, q_after, ee_target, trunk_target, fk, mask, g_er
     return dict(g_q_trace=g, c=c_all, e=e_all)
 
 
+# ---- the constraint slack as a loss (wbc_state_slack_vjp / wbc_rollout_vjp_watched, include/wbc.h)
+_SLACK_BLOCKS = ((0, 4), (4, 6), (6, 12))      # the components of families 0..2
+
+
+def slack_gradients(model, cfg, q, trunk_box_center, fk, g_slack=None, g_components=None):
+    """wbc_state_slack_vjp restated for B instances of ONE model: the cotangent of state_slack's outputs. q [B, 27], trunk_box_center [B, 4] or
+    None, fk as tick_state_gradients takes it (fk(q) -> oMf, fk.com(q), fk.jacobians(q) -> (J, Jcom)); g_slack [B, 4] = dL/d slack and / or
+    g_components [B, 12] = dL/d components. Component i of families 0..2 gets gamma_i = g_components[i] + g_slack[f] where i is the component
+    state_slack selects for family f (the lowest code on a tie: a subgradient there); g_slack[3] goes to the DoF and side of the joint
+    family's code. The first-order pieces are frame_rows' LOCAL_WORLD_ALIGNED rows of the FL / RR feet and the trunk frame and Jcom; the
+    angles go through d angle_a = N_a . omega. Returns dict(d_q [B, 26] tangent at q, d_trunk_box_center [B, 4], which [B, 4] int32 —
+    state_slack's —, grad_status [B] int32, gamma [B, 12]). A bad row (non-finite q or cotangent, non-finite box entry of a family with a
+    non-zero cotangent) gives zero rows and GRAD_NONFINITE."""
+    q = np.array(q, dtype=np.float64).reshape(-1, capi.Q_STRIDE)
+    B = q.shape[0]
+    if g_slack is None and g_components is None:
+        raise ValueError("a cotangent is required (g_slack or g_components)")
+    gs = np.zeros((B, capi.N_SLACK)) if g_slack is None else np.array(g_slack, dtype=np.float64).reshape(B, capi.N_SLACK)
+    gc = np.zeros((B, capi.N_SLACK_COMPONENTS)) if g_components is None else np.array(g_components, dtype=np.float64).reshape(B, capi.N_SLACK_COMPONENTS)
+    on1 = (gs[:, 1] != 0.0) | (gc[:, 4:6] != 0.0).any(axis=1)
+    on2 = (gs[:, 2] != 0.0) | (gc[:, 6:12] != 0.0).any(axis=1)
+    if trunk_box_center is None:
+        if (on1 | on2).any():
+            raise ValueError("trunk_box_center is required with a non-zero cotangent on a trunk family")
+        c = np.full((B, 4), np.nan)
+    else:
+        c = np.asarray(trunk_box_center, dtype=np.float64).reshape(B, 4)
+    st = state_slack(model, cfg, q, trunk_box_center, fk)
+    which = st["which"]
+    bad = ~np.isfinite(q[:, :model.nq]).all(axis=1) | ~np.isfinite(gs).all(axis=1) | ~np.isfinite(gc).all(axis=1)
+    bad |= (on1 & ~np.isfinite(c[:, 0])) | (on2 & ~np.isfinite(c[:, 1:]).all(axis=1))
+    neutral = np.zeros(capi.Q_STRIDE)
+    neutral[6] = 1.0
+    q[bad] = neutral
+    gs, gc = np.where(bad[:, None], 0.0, gs), np.where(bad[:, None], 0.0, gc)
+    gamma = gc.copy()
+    rows = np.arange(B)
+    for f, (lo, hi) in enumerate(_SLACK_BLOCKS):
+        sel = which[:, f] >= 0
+        gamma[rows[sel], lo + which[sel, f]] += gs[sel, f]
+    oMf = fk(q)
+    J, Jcom = fk.jacobians(q)
+    JFL = frame_rows(model, J, oMf, capi.FR_EE0 + 1, world=False)
+    JRR = frame_rows(model, J, oMf, capi.FR_EE0 + 2, world=False)
+    JT = frame_rows(model, J, oMf, capi.FR_TRUNK, world=False)
+    col = lambda v: v[:, None]      # noqa: E731
+    dq = col(gamma[:, 1]) * JFL[:, 0] + col(gamma[:, 3]) * JFL[:, 1] - col(gamma[:, 0]) * JRR[:, 0] - col(gamma[:, 2]) * JRR[:, 1]
+    dq = dq + col(gamma[:, 0] - gamma[:, 1]) * Jcom[:, 0] + col(gamma[:, 2] - gamma[:, 3]) * Jcom[:, 1]
+    dq = dq + col(gamma[:, 4] - gamma[:, 5]) * JT[:, 2]
+    # the three atan2 angles through dR = [omega] R: d angle_a = N_a . omega (R row-major: R[:, 3 i + j] = R_ij)
+    R = oMf[:, capi.FR_TRUNK, 0:9]
+    R00, R01, R02, R10, R11, R12, R20, R21, R22 = (R[:, i] for i in range(9))
+    n0 = R21 * R21 + R22 * R22
+    cxy = np.sqrt(n0)
+    n1, n2 = R20 * R20 + n0, R00 * R00 + R10 * R10
+    z = np.zeros(B)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t1 = R20 / cxy
+        N = [np.stack([R22 * R11 - R21 * R12, R21 * R02 - R22 * R01, z], axis=1) / col(n0),
+             np.stack([-cxy * R10 + t1 * (R21 * R11 + R22 * R12), cxy * R00 - t1 * (R21 * R01 + R22 * R02), z], axis=1) / col(n1),
+             np.stack([-R00 * R20, -R10 * R20, R00 * R00 + R10 * R10], axis=1) / col(n2)]
+    ce = np.stack([gamma[:, 6 + 2 * a] - gamma[:, 7 + 2 * a] for a in range(3)], axis=1)
+    for a in range(3):
+        Na = np.where(col(ce[:, a]) != 0.0, N[a], 0.0)                    # (a zero cotangent takes no part, whatever the rotation)
+        dq = dq + col(ce[:, a]) * np.einsum("bi,bik->bk", Na, JT[:, 3:6])
+    code = which[:, 3]
+    sel = (code >= 0) & (gs[:, 3] != 0.0)
+    dq[rows[sel], code[sel] >> 1] += np.where(code[sel] & 1, -gs[sel, 3], gs[sel, 3])
+    dq[:, model.nv:] = 0.0
+    zf = float(cfg.trunk_box_z_frac)
+    dbox = np.concatenate([col(-(1.0 - zf) * gamma[:, 4] + (1.0 + zf) * gamma[:, 5]), -ce], axis=1)
+    dq[bad], dbox[bad] = 0.0, 0.0
+    return dict(d_q=dq, d_trunk_box_center=dbox, which=which, grad_status=np.where(bad, capi.GRAD_NONFINITE, capi.GRAD_OK).astype(np.int32),
+                gamma=gamma)
+
+
+def watch_seed_gradients(model, cfg, q_after, trunk_box_center, fk, mask, g_slack_min=None, g_slack_final=None, g_trace=None,
+                         slack_min_tick=None):
+    """The cotangent of wbc_rollout_watch's results restated for B instances of ONE model. q_after [K, B, 27]: the state after every tick
+    (q_(k+1)); mask: the watched families (rows of the arrays below in increasing family order); g_slack_min, g_slack_final [n_w, B], g_trace
+    [K, n_w, B], each optional; slack_min_tick [n_w, B] as the record call returned it. On tick k family f carries
+    g_trace[k] + [k == K - 1] g_slack_final + [k == slack_min_tick] g_slack_min, applied through slack_gradients at q_(k+1). Returns
+    dict(g_q_trace [K, B, 26] tangent at q_(k+1), d_trunk_box_center [B, 4]: the sum over the ticks from the last, g_slack [K, B, 4])."""
+    q_after = np.asarray(q_after, dtype=np.float64)
+    K, B = q_after.shape[:2]
+    fams = [f for f in range(capi.N_SLACK) if (int(mask) >> f) & 1]
+    take = lambda a, lead: None if a is None else np.asarray(a, dtype=np.float64).reshape(lead + (len(fams), B))      # noqa: E731
+    g_min, g_fin, g_tr = take(g_slack_min, ()), take(g_slack_final, ()), take(g_trace, (K,))
+    tick = None if slack_min_tick is None else np.asarray(slack_min_tick).reshape(len(fams), B)
+    if g_min is not None and tick is None:
+        raise ValueError("g_slack_min needs slack_min_tick")
+    g, dbox, gs_all = np.zeros((K, B, capi.V_STRIDE)), np.zeros((B, 4)), np.zeros((K, B, capi.N_SLACK))
+    for k in range(K - 1, -1, -1):
+        gs = np.zeros((B, capi.N_SLACK))
+        for i, f in enumerate(fams):
+            x = np.zeros(B) if g_tr is None else g_tr[k, i]
+            if g_fin is not None and k == K - 1:
+                x = x + g_fin[i]
+            if g_min is not None:
+                x = x + np.where(tick[i] == k, g_min[i], 0.0)
+            gs[:, f] = x
+        r = slack_gradients(model, cfg, q_after[k], trunk_box_center, fk, g_slack=gs)
+        g[k], gs_all[k] = r["d_q"], gs
+        dbox = dbox + r["d_trunk_box_center"]
+    return dict(g_q_trace=g, d_trunk_box_center=dbox, g_slack=gs_all)
+
+
 # ---- K ticks as one reverse sweep (wbc_rollout_vjp, include/wbc.h; DESIGN.md §3.42)
 _ROLLOUT_SUMS = ("d_task_params", "d_com_target", "d_com_target_vel", "d_posture_u")
 
 
 def rollout_gradients(model, cfg, ticks_in, x, dt, fk, assemble, g_q_final=None, g_qdot_last=None, g_q_trace=None, task_params=None, imu=None,
-                      mode=capi.ROLLOUT_RUNNING, status=None, working_set=None, tracks=None, score_seed=None):
+                      mode=capi.ROLLOUT_RUNNING, status=None, working_set=None, tracks=None, score_seed=None, watch_seed=None):
     """wbc_rollout_vjp restated for B instances of ONE model over step_gradients, qp_certificate, tick_gradients and tick_state_gradients,
     tick by tick from the last. ticks_in: K dicts, the inputs tick k SAW (q, the targets as running sums, the previous rotations); x [K, B, 26]:
     the ticks' qdot; assemble(inputs) -> dict(A, b, C, Clb, Cub, lb, ub) of a tick's problem (a model with nv < 26 gets unit rows on its padded
@@ -1182,8 +1289,18 @@ def rollout_gradients(model, cfg, ticks_in, x, dt, fk, assemble, g_q_final=None,
     d_tangents, d_du), ...] from track_target_gradients; the followed rows of d_ee_target / d_trunk_target are 0 and the steps mean nothing.
     score_seed (wbc_rollout_vjp_scored): dict(mask, q_final [B, 27], g_err_sq_sum, g_err_final, g_err_max, err_max_tick) — the cotangents of
     the track scores through score_seed_gradients: its g_q_trace rows join the state seed where g_q_trace enters, and -c_k joins the
-    cotangent of tick k's targets BEHIND that tick's bookkeeping (so the step sums see the later ticks' alone) and in front of the tracks."""
+    cotangent of tick k's targets BEHIND that tick's bookkeeping (so the step sums see the later ticks' alone) and in front of the tracks.
+    watch_seed (wbc_rollout_vjp_watched): dict(mask, q_final [B, 27], g_slack_min, g_slack_final, g_trace, slack_min_tick) — the cotangents of
+    the watch's results through watch_seed_gradients at the states after the ticks, with ticks_in[0]["trunk_box_center"] as the box: its
+    g_q_trace rows join the state seed where g_q_trace enters, its box term joins d_trunk_box_center."""
     K = len(ticks_in)
+    w_box = None
+    if watch_seed is not None:
+        q_after = np.stack([np.asarray(ticks_in[k + 1]["q"], dtype=np.float64) for k in range(K - 1)] + [np.asarray(watch_seed["q_final"], dtype=np.float64)])
+        wg = watch_seed_gradients(model, cfg, q_after, ticks_in[0].get("trunk_box_center"), fk, watch_seed["mask"], watch_seed.get("g_slack_min"),
+                                  watch_seed.get("g_slack_final"), watch_seed.get("g_trace"), watch_seed.get("slack_min_tick"))
+        g_q_trace = wg["g_q_trace"] if g_q_trace is None else np.asarray(g_q_trace, dtype=np.float64).reshape(wg["g_q_trace"].shape) + wg["g_q_trace"]
+        w_box = wg["d_trunk_box_center"]
     sc_c = None
     if score_seed is not None:
         q_after = np.stack([np.asarray(ticks_in[k + 1]["q"], dtype=np.float64) for k in range(K - 1)] + [np.asarray(score_seed["q_final"], dtype=np.float64)])
@@ -1254,6 +1371,8 @@ def rollout_gradients(model, cfg, ticks_in, x, dt, fk, assemble, g_q_final=None,
             else:
                 e_tracks[j][k] = Eb[:, f]
                 Eb[:, f] = 0.0
+    if w_box is not None:
+        acc["d_trunk_box_center"] = acc["d_trunk_box_center"] + w_box
     if tracks:
         names = ("d_points", "d_tangents", "d_du")
         acc["tracks"] = [dict(zip(names, track_target_gradients(t["points"], t.get("n_points"), t.get("du", 0.002), K, t.get("kind", "linear"),

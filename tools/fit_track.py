@@ -11,7 +11,11 @@ wbc_rollout_vjp_scored) and masked by the roll-out's status: nothing crosses to 
     sum     err_sq_sum: the squared tracking error summed over every tick
 It prints the loss per iteration and, for both variants, the gripper's distance to the goal after the last tick (from the library's
 kinematics, once, outside the loop); a demonstration, no assertion.
-    python3 tools/fit_track.py [B] [K] [steps]"""
+--keep-inside FAMILY:MARGIN (FAMILY: com, trunk_z, trunk_ang or joint; MARGIN in the family's unit, metres or radians) adds "and stay legal":
+the roll-out also watches that constraint slack on every tick (wbc_torch.wbc_rollout_watched, wbc_rollout_vjp_watched) and the loss gains
+the hinge sum_k max(0, MARGIN - slack_k) on its trace, so "keep the CoM 2 cm inside the feet" is --keep-inside com:0.02. The smallest slack
+over the ticks is printed beside the loss.
+    python3 tools/fit_track.py [--keep-inside FAMILY:MARGIN] [B] [K] [steps]"""
 import os
 import sys
 
@@ -26,6 +30,12 @@ import wbc_torch
 import wbc_workload
 from wbc_batch import WbcBatch
 
+KEEP = None
+if "--keep-inside" in sys.argv:
+    i = sys.argv.index("--keep-inside")
+    family, _, margin = sys.argv[i + 1].partition(":")
+    KEEP = (family, float(margin))
+    del sys.argv[i:i + 2]
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 64
 K = int(sys.argv[2]) if len(sys.argv) > 2 else 24
 STEPS = int(sys.argv[3]) if len(sys.argv) > 3 else 30
@@ -54,16 +64,24 @@ def fit(variant):
     for step in range(STEPS):
         points = torch.cat([ends[:, :1], inner, ends[:, 3:]], dim=1).contiguous()
         track = dict(target=4, kind="hermite", points=points, du=torch.exp(log_du))
-        q, qdot, status, _, err_sq_sum, err_final, err_max, _ = wbc_torch.wbc_rollout_tracks_scored(dev["q"], None, [track], rest, DT, K, bt, score=(4,))
+        legal = ""
+        if KEEP is None:
+            q, qdot, status, _, err_sq_sum, err_final, err_max, _ = wbc_torch.wbc_rollout_tracks_scored(dev["q"], None, [track], rest, DT, K, bt, score=(4,))
+            hinge = 0.0
+        else:
+            res = wbc_torch.wbc_rollout_watched(dev["q"], None, rest, DT, K, bt, watch=(KEEP[0],), tracks=[track], score=(4,))
+            q, qdot, status, trace, err_sq_sum, err_final, err_max = res[0], res[1], res[2], res[6], res[9], res[10], res[11]
+            hinge = torch.clamp(KEEP[1] - trace[:, 0], min=0.0).sum(dim=0)
+            legal = "   %s slack: smallest %.5f, hinge %.3e" % (KEEP[0], float(trace.detach().min()), float(hinge.detach().sum()))
         solved = (status == 0).to(q.dtype)
-        per = (err_final[0] ** 2 if variant == "final" else err_sq_sum[0]) * solved
+        per = ((err_final[0] ** 2 if variant == "final" else err_sq_sum[0]) + hinge) * solved
         loss = per.sum()
         opt.zero_grad()
         loss.backward()
         opt.step()
         print("%s, iteration %3d: loss %.6e   tracking error, mm: final mean %.4f  max over the ticks %.4f   du: median %.4f  (solved %d / %d)" % (
             variant, step, float(loss.detach()), 1e3 * float(err_final.detach().mean()), 1e3 * float(err_max.detach().max()),
-            float(torch.exp(log_du).detach().median()), int(solved.sum()), B))
+            float(torch.exp(log_du).detach().median()), int(solved.sum()), B) + legal)
     return q.detach()
 
 
